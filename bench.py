@@ -1,9 +1,22 @@
 #!/usr/bin/env python3
 """bench.py — training throughput of the IPSR inpainting step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the per-step median, the
+host's queueing share, the losses of the last timed step).  `--full` adds everything else described below: the per-kernel
+rooflines, the IPSR layer alone at every BASELINE configuration, the strict-reference and split-bf16 steps, a fresh mask per step
+and the CPU twin.  `--dump-outputs DIR` writes, on rank 0, the arrays of the last timed step that its seeded inputs and fixed weights
+determine, as DIR/<name>.npy (float32): `input_A` (the step's input image, its hole blanked) and the frozen VGG16's features of the
+reference and of the ground truth (`ref_relu1_2` .. `ref_relu4_3`, `gt_relu1_2` .. `gt_relu4_3`, set_ref_latent / set_gt_latent).
+An array longer than its cap (DUMP_CAP) is replaced by a fixed, seeded sample of that many of its numbers (under 48 MB in all at
+batch 16).  Two runs with the same arguments write the same arrays.  What the trained nets compute (images, losses, weights) is not
+dumped: it is not repeatable from run to run — MIOpen's convolutions accumulate atomically, the IPSR layer's truncated attention
+turns their last-bit differences into whole gradient columns, and Adam's first steps (lr * sign(grad)) carry those into the
+weights; two identical 25-step runs end with losses ~10 % apart, and MIOpen's deterministic mode neither fixes that nor keeps the
+step's speed (4x slower).
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks ITSELF: the parent — before any GPU call, and
 never touching the GPU afterwards — runs the second command above as a CHILD process (no exec), lets rank 0's JSON line through and
@@ -17,7 +30,7 @@ tensors of BASELINE.json config 2:  set_input + set_ref_latent + set_gt_latent +
 skipped inside the timed region: 4 nets forward/backward, 3 VGG passes (the reference's 4th is a
 recomputation of identical features and is reused), 4 Adam steps, the IPSR layer forward/backward.
 
-Rank 0 prints ONE JSON line.  `value` = images/s of the whole job (all ranks).  Extra objects:
+Rank 0 prints ONE JSON line.  `value` = images/s of the whole job (all ranks).  Extra objects (with --full; `step_graph` always):
   roofline      the layer's dominant kernel (fp32-MFMA correlation + arg-max): algorithmic FLOPs per launch
                 (2*N*N*C per sample) over its mean duration, measured live with HIP events on
                 the launch stream inside the timed steps (C-ABI hook ipsr_profile_*).
@@ -70,6 +83,7 @@ REF_FLOPS_PER_IMAGE = 414.9e9      # the reference's own sequence (SURVEY §8d, 
 PEAK_FP32_MFMA_TFLOPS = 157.3          # MI355X_MICROARCH.md: fp32-input MFMA = 64 FLOP/clk/SIMD
 PEAK_BF16_MFMA_TFLOPS = 2500.0         # dense bf16 MFMA, same guide (the 5 PF headline figure includes 2:1 sparsity)
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic_corr_argmax.json")
+DUMP_CAP = {"input": 1 << 22, "features": 1 << 20}   # numbers per dumped array: input + 8 feature maps under 48 MB of float32
 
 
 def quiet(fn, *a, **k):
@@ -91,6 +105,26 @@ def train_step(model, img, mask, ref):
     model.set_ref_latent()
     model.set_gt_latent()
     model.optimize_parameters()
+
+
+def dump_outputs(model, out_dir):
+    """`--dump-outputs`: the arrays of the last training step fixed by its inputs (module text) as float32 .npy files, an array
+    longer than its DUMP_CAP cut to a seeded sample of its numbers (the same positions in every run)."""
+    import numpy as np
+
+    def capped(t, cap):
+        t = t.detach().float()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        return t.cpu().numpy()
+    arrays = {"input_A": capped(model.input_A, DUMP_CAP["input"])}
+    for tag, feats in (("ref", model.ref_latent), ("gt", model._gt_latent)):
+        for name, t in feats._asdict().items():
+            arrays[tag + "_" + name] = capped(t, DUMP_CAP["features"])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def _layer_case(device, B, h, fine, mask_img, patch, iters, corr="fp32"):
@@ -439,146 +473,9 @@ def dry_run(args):
     return 0 if in_sync else 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (BASELINE config 2 = 8)")
-    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
-                    help="f32 = the reference's precision and the headline metric; bf16 = BASELINE config 5 (convs under "
-                         "bf16 autocast, IPSR layer and losses fp32) — a separate, clearly labelled measurement")
-    ap.add_argument("--rccl-algo", default=None, help="NCCL_ALGO for the gradient all-reduce (default: RCCL's tuner)")
-    ap.add_argument("--rccl-proto", default=None, help="NCCL_PROTO (e.g. Simple)")
-    ap.add_argument("--rccl-min-channels", default=None, help="NCCL_MIN_NCHANNELS")
-    ap.add_argument("--conv-math", choices=("fp32", "bf16x6", "bf16x3"), default="fp32",
-                    help="arithmetic of the Winograd convolution GEMMs for fp32 activations (default fp32 = the reference's; the split-bf16 "
-                         "forms are reported as what they are, never as the headline)")
-    ap.add_argument("--debug-opt", action="append", default=[], help="key=value for ipsr_debug_set_option (kernel-variant A/B; never set by default)")
-    ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
-                    help="nccl = RCCL over xGMI (the measurement); gloo = DRY MODE on the CPU: launcher + argument plumbing + the "
-                         "gradient exchange on stand-in nets, no kernels (tests/test_bench_launcher.py)")
-    ap.add_argument("--ddp-bucket-mb", type=int, default=64, help="gradient bucket size of the all-reduce (dist.GradBucketReducer)")
-    ap.add_argument("--graph", choices=("on", "off"), default="off",
-                    help="on: replay the training step from one HIP graph (deepinpainting_amd/stepgraph.py, one GPU only) instead of queueing its "
-                         "~1100-1400 kernels from Python every step.  Off by default: measured at --dtype bf16 --batch 16 the replay takes 22.0 ms "
-                         "against 21.2 ms for the eager step (hipGraphLaunch orders its ~1400 nodes one by one), although it frees the host "
-                         "(0.4 ms instead of 21.9 ms of queueing per step)")
-    args = ap.parse_args()
-    if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
-        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
-    if args.backend == "gloo":
-        return dry_run(args)
-    if args.debug_opt:
-        from deepinpainting_amd import _lib as _dbg_lib
-        for kv in args.debug_opt:
-            k, v = map(int, kv.split("="))
-            _dbg_lib.check(_dbg_lib.lib().ipsr_debug_set_option(k, v), "ipsr_debug_set_option")
-
-    from deepinpainting_amd import _lib, dist as idist
-    from deepinpainting_amd.models.models import create_model
-    from deepinpainting_amd.options import Option
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the IPSR layer has no CPU path (the CPU twin is only the reported baseline)")
-    # the device is chosen from the launcher's LOCAL_RANK before the communicator exists; init_distributed sets it again for nccl
-    rank, world, local_rank = idist.init_distributed(backend="nccl", rccl_algo=args.rccl_algo, rccl_proto=args.rccl_proto,
-                                                        rccl_channels=args.rccl_min_channels)
-    if world != args.gpus:
-        if args.gpus != 1 or world != 1:
-            raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with torch.distributed.run --nproc-per-node %d" % (args.gpus, world, args.gpus))
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    # MIOpen exhaustive find (cudnn.benchmark) costs minutes on a fresh box for the ~60 conv shapes of the
-    # step; off by default so the run finishes quickly, opt in with IPSR_BENCH_MIOPEN_FIND=1
-    torch.backends.cudnn.benchmark = os.environ.get("IPSR_BENCH_MIOPEN_FIND", "0") == "1"
-
-    opt = Option(gpu_ids=[local_rank], batchSize=args.batch, use_dropout=True, quiet=True, allow_random_vgg=True,
-                 batch_vgg=os.environ.get("IPSR_BENCH_BATCH_VGG", "0") == "1", batch_disc=os.environ.get("IPSR_BENCH_BATCH_DISC", "1") == "1", amp_bf16=(args.dtype == "bf16"), conv_math=args.conv_math,
-                 ddp_bucket_mb=args.ddp_bucket_mb, checkpoints_dir=os.path.join("/tmp", "ipsr_bench_ckpt_%d" % rank))
-    torch.manual_seed(1234)                       # identical init on every rank (rank 0 is broadcast anyway)
-    model = quiet(create_model, opt)
-    reducers = {"D": model._reducer_D, "G": model._reducer_G}
-    for red in reducers.values():
-        if red is not None:
-            red.timing = world > 1
-    cl = os.environ.get("IPSR_BENCH_CHANNELS_LAST", "0")             # experiment knob, not the default: "1" = all nets,
-    if cl != "0":                                                    # or a comma list of netG,netP,netD,netF,vgg
-        names = ("netG", "netP", "netD", "netF", "vgg") if cl == "1" else tuple(cl.split(","))
-        for name in names:
-            getattr(model, name).to(memory_format=torch.channels_last)
-    img, mask, ref = synthetic_batch(device, args.batch, 1234 + rank)
-
-    lib = _lib.lib()
-    for i in range(args.warmup):
-        train_step(model, img, mask, ref)
-        torch.cuda.synchronize()
-        if rank == 0:
-            print("[bench] warm-up step %d/%d done (%.1f s since start)" % (i + 1, args.warmup, time.perf_counter() - T_START),
-                  file=sys.stderr, flush=True)
-    # A CPython gen-2 collection walks every live object (the module trees, ~100 ms here) and would land inside one
-    # timed step (measured: one 123 ms step in every ~25).  Collect now and freeze the survivors out of future scans.
-    import gc
-    gc.collect()
-    gc.freeze()
-    for red in reducers.values():
-        if red is not None:
-            red.exposed_ms()                      # drop the warm-up steps' records
-    # One GPU: the step is replayed from a HIP graph recorded here (the recording's own warm-up steps are undone, see StepGraph._record);
-    # if the recording fails the loop below queues the kernels from Python as before, and the JSON line says so.
-    graph_info = {"used": False, "reason": "--graph off (the default)" if args.graph == "off" else "N > 1: the gradient exchange is not recorded"}
-    sgraph = None
-    if world == 1 and args.graph == "on":
-        from deepinpainting_amd.stepgraph import StepGraph
-        try:
-            sgraph = StepGraph(model)
-            sgraph.step(img, mask, ref)
-            torch.cuda.synchronize()
-            graph_info = {"used": True, "recordings": sgraph.recordings,
-                          "note": "timed steps = hipGraphLaunch of the recorded step (same kernels, same order); the per-kernel HIP-event "
-                                  "timings of this line are taken in eager steps right after the timed loop (events are not recorded into a graph)"}
-        except Exception as e:                                      # noqa: BLE001 — report and measure the eager step instead
-            sgraph = None
-            graph_info = {"used": False, "reason": "recording failed: %s: %s" % (type(e).__name__, str(e)[:300])}
-            torch.cuda.synchronize()
-        if rank == 0:
-            print("[bench] step graph: %s (%.1f s since start)" % (graph_info, time.perf_counter() - T_START), file=sys.stderr, flush=True)
-
-    def one_step():
-        if sgraph is not None:
-            sgraph.step(img, mask, ref)
-        else:
-            train_step(model, img, mask, ref)
-    if sgraph is None:
-        lib.ipsr_profile_enable(max(args.steps, 1))
-    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    step_ev[0].record()
-    for i in range(args.steps):
-        one_step()
-        step_ev[i + 1].record()
-    host_enqueue_ms = (time.perf_counter() - t0) * 1e3 / max(args.steps, 1)      # the host's share: launches queued, nothing waited for
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    step_ms = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
-    # a step that went wrong must not pass for a throughput number: the losses of the last timed step are reported and flagged
-    timed_losses = {k: float(v) for k, v in model.get_current_errors().items()}
-    losses_finite = all(v == v and abs(v) != float("inf") for v in timed_losses.values())
-    if not losses_finite and rank == 0:
-        print("[bench] WARNING: non-finite losses after the timed steps: %s — the rate below measures a broken step" % timed_losses, file=sys.stderr, flush=True)
-    ddp = ddp_report(args, world, rank, device, elapsed, step_ms, reducers, "nccl") if world > 1 else None
-    for red in reducers.values():
-        if red is not None:
-            red.timing = False
-
+def full_measurements(args, model, lib, device, img, mask, ref, world, sgraph):
+    """--full, on every rank right after the timed loop: the layer's in-step event timings, a few profiled extra steps for the
+    kernels' rooflines, then the strict-reference, split-bf16 and new-mask-per-step variants of the step."""
     def read_region(region):
         buf = (ctypes.c_float * max(args.steps, 1))()
         n = lib.ipsr_profile_read_region(region, ctypes.cast(buf, ctypes.c_void_p), args.steps)
@@ -681,19 +578,15 @@ def main():
     newmask = None
     if args.dtype == "f32" and world == 1 and os.environ.get("IPSR_BENCH_STEP_ONLY", "0") != "1":
         newmask = new_mask_each_step(model, img, ref, device, args.batch, max(3, min(10, args.steps)))
+    return {"kern_ms": kern_ms, "fwd_in_step": fwd_in_step, "bwd_in_step": bwd_in_step, "gsteps": gsteps,
+            "conv_roofline": conv_roofline(args, ng, gsteps, gemm_ms, gemm_flops, gemm_useful), "conv_roofline_direct_bf16": direct,
+            "innercos_roofline": ic_step, "strict_reference": strict, "alt_arithmetic": alt, "new_mask_each_step": newmask}
 
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-    if rank != 0:
-        if world > 1:
-            torch.distributed.destroy_process_group()
-        return
 
-    errs = model.get_current_errors()
-    ms_per_step = elapsed / args.steps * 1e3
-    value = args.batch * world * args.steps / elapsed
+def full_report(args, device, world, value, sgraph, fm):
+    """--full, rank 0: the objects of the line beyond the headline, in the line's order, from full_measurements() (`fm`)
+    and the IPSR layer's stand-alone micro-benchmarks, which run here."""
+    kern_ms, fwd_in_step, bwd_in_step, gsteps = fm["kern_ms"], fm["fwd_in_step"], fm["bwd_in_step"], fm["gsteps"]
     n_feat = H_FEAT * H_FEAT
     flops = 2.0 * n_feat * n_feat * C_FEAT * args.batch
     corr_peak = PEAK_FP32_MFMA_TFLOPS if args.dtype == "f32" else PEAK_BF16_MFMA_TFLOPS      # the kernel of the layer that actually ran
@@ -708,28 +601,8 @@ def main():
         if "corr_argmax" in tj.get("kernel", "") and tj.get("workload", "").endswith("[%d,%d,%d,%d]" % (args.batch, C_FEAT, H_FEAT, H_FEAT)):
             traffic = tj.get("hbm_bytes_per_launch")
             traffic_src = "stored rocprofv3 --pmc figure (profiles/traffic_corr_argmax.json, FETCH_SIZE x2 + WRITE_SIZE), not re-measured in this run"
-    if os.environ.get("IPSR_BENCH_STEP_ONLY", "0") == "1":
-        # profiling aid (rocprofv3 of the training steps alone): no layer micro-benchmarks, no CPU twin
-        print(json.dumps({"metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-                          "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "note": "IPSR_BENCH_STEP_ONLY=1 (profiling run)"}), flush=True)
-        if world > 1:
-            torch.distributed.destroy_process_group()
-        return
     fwd_ms, bwd_ms = layer_timing(device)
-    out = {
-        "metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_step_median": round(statistics.median(step_ms), 3),
-        "host_enqueue_ms_per_step": round(host_enqueue_ms, 3), "step_graph": graph_info,
-        "images_per_sec_median_step": round(args.batch * world / (statistics.median(step_ms) * 1e-3), 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": ("BASELINE config 2: 256x256 synthetic images, 128x128 centre mask (M=256 of N=1024 "
-                                "feature positions), batch %d/GPU, fp32, full IPSR training step" % args.batch)
-                   if args.dtype == "f32" else
-                   ("BASELINE config 5 (NOT the headline metric): as config 2 with the convolutions under bf16 autocast, "
-                    "IPSR layer / InnerCos / losses fp32, batch %d/GPU" % args.batch),
-                   "global_batch": args.batch * world, "parallelism": "dp%d" % world, "dropout": True,
-                   "conv_math": (args.conv_math if args.dtype == "f32" else "bf16x3 (Winograd operands split hi + lo on the bf16 MFMA, fp32 accumulate)"),
-                   "vgg16": "seeded random init (no pretrained weights offline)"},
+    return {
         "ipsr_layer_ms": {"forward": round(fwd_ms, 4), "backward": round(bwd_ms, 4), "total": round(fwd_ms + bwd_ms, 4),
                           "shape": "[%d,%d,%d,%d], M=256" % (BATCH, C_FEAT, H_FEAT, H_FEAT),
                           "inputs": "standalone, synthetic x=|N(0,1)|, ref=relu(N(0,1)), median of 50",
@@ -755,8 +628,8 @@ def main():
         # inside the timed steps; flops = the multiplies the kernel executes (4x fewer than the direct convolutions it replaces)
         # `achieved` / `frac`: USEFUL flops (unpadded channels / tiles) over the kernel's time; `executed_*`: the flops the kernel
         # really issues (rows / columns rounded up to the 128 x 128 tile — the difference is arithmetic on zero padding)
-        "conv_roofline": conv_roofline(args, ng, gsteps, gemm_ms, gemm_flops, gemm_useful),
-        "conv_roofline_direct_bf16": direct,
+        "conv_roofline": fm["conv_roofline"],
+        "conv_roofline_direct_bf16": fm["conv_roofline_direct_bf16"],
         "step_roofline": {"bound": "mfma", "flops_per_image": STEP_FLOPS_PER_IMAGE,
                           "achieved_direct_equivalent": round(STEP_FLOPS_PER_IMAGE * value / world / 1e12, 2), "peak": PEAK_FP32_MFMA_TFLOPS,
                           "unit": "TFLOP/s per GPU",
@@ -765,15 +638,206 @@ def main():
                                   "kernels (this repo's F(4x4,3x3) / F(3x3,4x4) / F(5x5,2x2), MIOpen's F(2x2,3x3)) execute 2.25-4x fewer "
                                   "multiplies than this count, so the figure could exceed 1"}
         if args.dtype == "f32" else None,
-        "alt_arithmetic": alt,
-        "new_mask_each_step": newmask,
-        "innercos_roofline": ic_step,
-        "strict_reference": strict,
-        "ddp": ddp,
-        "losses_last_step": {k: round(v, 4) for k, v in errs.items()},
-        "losses_last_timed_step": {k: round(v, 4) for k, v in timed_losses.items()}, "losses_finite": losses_finite,
+        "alt_arithmetic": fm["alt_arithmetic"],
+        "new_mask_each_step": fm["new_mask_each_step"],
+        "innercos_roofline": fm["innercos_roofline"],
+        "strict_reference": fm["strict_reference"],
     }
-    if world == 1 and not args.no_cpu_baseline:
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU twin")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, measure everything else the line can carry: in-step layer and kernel timings, "
+                         "rooflines, the strict-reference / split-bf16 / new-mask-per-step variants, the layer alone at every "
+                         "BASELINE config, the CPU twin (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step that its seeded inputs determine (module text) as DIR/<name>.npy")
+    ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (BASELINE config 2 = 8)")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
+                    help="f32 = the reference's precision and the headline metric; bf16 = BASELINE config 5 (convs under "
+                         "bf16 autocast, IPSR layer and losses fp32) — a separate, clearly labelled measurement")
+    ap.add_argument("--rccl-algo", default=None, help="NCCL_ALGO for the gradient all-reduce (default: RCCL's tuner)")
+    ap.add_argument("--rccl-proto", default=None, help="NCCL_PROTO (e.g. Simple)")
+    ap.add_argument("--rccl-min-channels", default=None, help="NCCL_MIN_NCHANNELS")
+    ap.add_argument("--conv-math", choices=("fp32", "bf16x6", "bf16x3"), default="fp32",
+                    help="arithmetic of the Winograd convolution GEMMs for fp32 activations (default fp32 = the reference's; the split-bf16 "
+                         "forms are reported as what they are, never as the headline)")
+    ap.add_argument("--debug-opt", action="append", default=[], help="key=value for ipsr_debug_set_option (kernel-variant A/B; never set by default)")
+    ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
+                    help="nccl = RCCL over xGMI (the measurement); gloo = DRY MODE on the CPU: launcher + argument plumbing + the "
+                         "gradient exchange on stand-in nets, no kernels (tests/test_bench_launcher.py)")
+    ap.add_argument("--ddp-bucket-mb", type=int, default=64, help="gradient bucket size of the all-reduce (dist.GradBucketReducer)")
+    ap.add_argument("--graph", choices=("on", "off"), default="off",
+                    help="on: replay the training step from one HIP graph (deepinpainting_amd/stepgraph.py, one GPU only) instead of queueing its "
+                         "~1100-1400 kernels from Python every step.  Off by default: measured at --dtype bf16 --batch 16 the replay takes 22.0 ms "
+                         "against 21.2 ms for the eager step (hipGraphLaunch orders its ~1400 nodes one by one), although it frees the host "
+                         "(0.4 ms instead of 21.9 ms of queueing per step)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
+        raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
+    if args.backend == "gloo":
+        return dry_run(args)
+    if args.debug_opt:
+        from deepinpainting_amd import _lib as _dbg_lib
+        for kv in args.debug_opt:
+            k, v = map(int, kv.split("="))
+            _dbg_lib.check(_dbg_lib.lib().ipsr_debug_set_option(k, v), "ipsr_debug_set_option")
+
+    from deepinpainting_amd import _lib, dist as idist
+    from deepinpainting_amd.models.models import create_model
+    from deepinpainting_amd.options import Option
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: the IPSR layer has no CPU path (the CPU twin is only the reported baseline)")
+    # the device is chosen from the launcher's LOCAL_RANK before the communicator exists; init_distributed sets it again for nccl
+    rank, world, local_rank = idist.init_distributed(backend="nccl", rccl_algo=args.rccl_algo, rccl_proto=args.rccl_proto,
+                                                        rccl_channels=args.rccl_min_channels)
+    if world != args.gpus:
+        if args.gpus != 1 or world != 1:
+            raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with torch.distributed.run --nproc-per-node %d" % (args.gpus, world, args.gpus))
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    # MIOpen exhaustive find (cudnn.benchmark) costs minutes on a fresh box for the ~60 conv shapes of the
+    # step; off by default so the run finishes quickly, opt in with IPSR_BENCH_MIOPEN_FIND=1
+    torch.backends.cudnn.benchmark = os.environ.get("IPSR_BENCH_MIOPEN_FIND", "0") == "1"
+
+    opt = Option(gpu_ids=[local_rank], batchSize=args.batch, use_dropout=True, quiet=True, allow_random_vgg=True,
+                 batch_vgg=os.environ.get("IPSR_BENCH_BATCH_VGG", "0") == "1", batch_disc=os.environ.get("IPSR_BENCH_BATCH_DISC", "1") == "1", amp_bf16=(args.dtype == "bf16"), conv_math=args.conv_math,
+                 ddp_bucket_mb=args.ddp_bucket_mb, checkpoints_dir=os.path.join("/tmp", "ipsr_bench_ckpt_%d" % rank))
+    torch.manual_seed(1234)                       # identical init on every rank (rank 0 is broadcast anyway)
+    model = quiet(create_model, opt)
+    reducers = {"D": model._reducer_D, "G": model._reducer_G}
+    for red in reducers.values():
+        if red is not None:
+            red.timing = world > 1
+    cl = os.environ.get("IPSR_BENCH_CHANNELS_LAST", "0")             # experiment knob, not the default: "1" = all nets,
+    if cl != "0":                                                    # or a comma list of netG,netP,netD,netF,vgg
+        names = ("netG", "netP", "netD", "netF", "vgg") if cl == "1" else tuple(cl.split(","))
+        for name in names:
+            getattr(model, name).to(memory_format=torch.channels_last)
+    img, mask, ref = synthetic_batch(device, args.batch, 1234 + rank)
+
+    lib = _lib.lib()
+    for i in range(args.warmup):
+        train_step(model, img, mask, ref)
+        torch.cuda.synchronize()
+        if rank == 0:
+            print("[bench] warm-up step %d/%d done (%.1f s since start)" % (i + 1, args.warmup, time.perf_counter() - T_START),
+                  file=sys.stderr, flush=True)
+    # A CPython gen-2 collection walks every live object (the module trees, ~100 ms here) and would land inside one
+    # timed step (measured: one 123 ms step in every ~25).  Collect now and freeze the survivors out of future scans.
+    import gc
+    gc.collect()
+    gc.freeze()
+    for red in reducers.values():
+        if red is not None:
+            red.exposed_ms()                      # drop the warm-up steps' records
+    # One GPU: the step is replayed from a HIP graph recorded here (the recording's own warm-up steps are undone, see StepGraph._record);
+    # if the recording fails the loop below queues the kernels from Python as before, and the JSON line says so.
+    graph_info = {"used": False, "reason": "--graph off (the default)" if args.graph == "off" else "N > 1: the gradient exchange is not recorded"}
+    sgraph = None
+    if world == 1 and args.graph == "on":
+        from deepinpainting_amd.stepgraph import StepGraph
+        try:
+            sgraph = StepGraph(model)
+            sgraph.step(img, mask, ref)
+            torch.cuda.synchronize()
+            graph_info = {"used": True, "recordings": sgraph.recordings,
+                          "note": "timed steps = hipGraphLaunch of the recorded step (same kernels, same order); the per-kernel HIP-event "
+                                  "timings of this line are taken in eager steps right after the timed loop (events are not recorded into a graph)"}
+        except Exception as e:                                      # noqa: BLE001 — report and measure the eager step instead
+            sgraph = None
+            graph_info = {"used": False, "reason": "recording failed: %s: %s" % (type(e).__name__, str(e)[:300])}
+            torch.cuda.synchronize()
+        if rank == 0:
+            print("[bench] step graph: %s (%.1f s since start)" % (graph_info, time.perf_counter() - T_START), file=sys.stderr, flush=True)
+
+    def one_step():
+        if sgraph is not None:
+            sgraph.step(img, mask, ref)
+        else:
+            train_step(model, img, mask, ref)
+    if sgraph is None and args.full:
+        lib.ipsr_profile_enable(max(args.steps, 1))
+    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    step_ev[0].record()
+    for i in range(args.steps):
+        one_step()
+        step_ev[i + 1].record()
+    host_enqueue_ms = (time.perf_counter() - t0) * 1e3 / max(args.steps, 1)      # the host's share: launches queued, nothing waited for
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    step_ms = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
+    # a step that went wrong must not pass for a throughput number: the losses of the last timed step are reported and flagged
+    timed_losses = {k: float(v) for k, v in model.get_current_errors().items()}
+    losses_finite = all(v == v and abs(v) != float("inf") for v in timed_losses.values())
+    if not losses_finite and rank == 0:
+        print("[bench] WARNING: non-finite losses after the timed steps: %s — the rate below measures a broken step" % timed_losses, file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+    ddp = ddp_report(args, world, rank, device, elapsed, step_ms, reducers, "nccl") if world > 1 else None
+    for red in reducers.values():
+        if red is not None:
+            red.timing = False
+
+    fm = full_measurements(args, model, lib, device, img, mask, ref, world, sgraph) if args.full else None
+
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if rank != 0:
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = args.batch * world * args.steps / elapsed
+    if args.full and os.environ.get("IPSR_BENCH_STEP_ONLY", "0") == "1":
+        # profiling aid (rocprofv3 of the training steps alone): no layer micro-benchmarks, no CPU twin
+        print(json.dumps({"metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+                          "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "note": "IPSR_BENCH_STEP_ONLY=1 (profiling run)"}), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    out = {
+        "metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_step_median": round(statistics.median(step_ms), 3),
+        "host_enqueue_ms_per_step": round(host_enqueue_ms, 3), "step_graph": graph_info,
+        "images_per_sec_median_step": round(args.batch * world / (statistics.median(step_ms) * 1e-3), 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": ("BASELINE config 2: 256x256 synthetic images, 128x128 centre mask (M=256 of N=1024 "
+                                "feature positions), batch %d/GPU, fp32, full IPSR training step" % args.batch)
+                   if args.dtype == "f32" else
+                   ("BASELINE config 5 (NOT the headline metric): as config 2 with the convolutions under bf16 autocast, "
+                    "IPSR layer / InnerCos / losses fp32, batch %d/GPU" % args.batch),
+                   "global_batch": args.batch * world, "parallelism": "dp%d" % world, "dropout": True,
+                   "conv_math": (args.conv_math if args.dtype == "f32" else "bf16x3 (Winograd operands split hi + lo on the bf16 MFMA, fp32 accumulate)"),
+                   "vgg16": "seeded random init (no pretrained weights offline)"},
+    }
+    if args.full:
+        out.update(full_report(args, device, world, value, sgraph, fm))
+    out["ddp"] = ddp
+    if args.full:
+        out["losses_last_step"] = {k: round(v, 4) for k, v in model.get_current_errors().items()}
+    out["losses_last_timed_step"] = {k: round(v, 4) for k, v in timed_losses.items()}
+    out["losses_finite"] = losses_finite
+    if args.full and world == 1 and not args.no_cpu_baseline:
         print("[bench] GPU part done: %.2f images/s; timing the CPU twin ..." % value, file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
