@@ -14,8 +14,8 @@ it), which is value-identical: the reference's in-place LeakyReLU rewrites the v
 so nobody ever sees the un-activated values (that is also why the skip connection carries the activated tensor).
 
 Activations may be fp32 or bf16 (BASELINE config 5 runs the convolutions under bf16 autocast; the kernels then read and
-write bf16 and compute in fp32).  CPU tensors, other dtypes, planes above 128x128 and `FusedSequential.enabled = False`
-take the plain module-by-module path.
+write bf16 and compute in fp32).  CPU tensors, other dtypes, planes above 256x256 (ops.INSTNORM_MAX_PLANE) or above 16384 elements
+and not a multiple of 4, and `FusedSequential.enabled = False` take the plain module-by-module path.
 """
 import torch
 import torch.nn as nn
@@ -35,18 +35,18 @@ def _ticket_words(x, bias):
 class _InstNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, gamma, beta, eps, act, slope):
-        y, mean, rstd = ops.instnorm_act_forward(x, bias, gamma, beta, eps, act, slope)
-        ctx.save_for_backward(x, bias, gamma, y, mean, rstd)
+        y, mean, rstd, tickets = ops.instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, return_tickets=True)
+        ctx.save_for_backward(x, bias, gamma, y, mean, rstd, tickets)
         ctx.act, ctx.slope = act, slope
         ctx.has_affine = gamma is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, bias, gamma, y, mean, rstd = ctx.saved_tensors
+        x, bias, gamma, y, mean, rstd, tickets = ctx.saved_tensors
         need_bias = bias is not None and ctx.needs_input_grad[1]
         need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
-        dx, dg, db, dbias = ops.instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, ctx.act, ctx.slope, need_affine, need_bias)
+        dx, dg, db, dbias = ops.instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, ctx.act, ctx.slope, need_affine, need_bias, tickets=tickets)
         return dx, dbias, dg, db, None, None, None
 
 
@@ -121,20 +121,20 @@ class _InstNormReLUCat(torch.autograd.Function):
     def forward(ctx, y, bias, gamma, beta, eps, x):
         B, C1, C2 = y.shape[0], y.shape[1], x.shape[1]
         out = torch.empty((B, C1 + C2) + tuple(y.shape[2:]), dtype=y.dtype, device=y.device)
-        _, mean, rstd = ops.instnorm_act_forward(y, bias, gamma, beta, eps, "relu", 0.0, into=out)
+        _, mean, rstd, tickets = ops.instnorm_act_forward(y, bias, gamma, beta, eps, "relu", 0.0, into=out, return_tickets=True)
         ops.cat_relu_skip_half_(out, x)
-        ctx.save_for_backward(y, bias, gamma, out, mean, rstd)
+        ctx.save_for_backward(y, bias, gamma, out, mean, rstd, tickets)
         ctx.c1 = C1
         ctx.has_affine = gamma is not None
         return out
 
     @staticmethod
     def backward(ctx, g):
-        y, bias, gamma, out, mean, rstd = ctx.saved_tensors
+        y, bias, gamma, out, mean, rstd, tickets = ctx.saved_tensors
         need_bias = bias is not None and ctx.needs_input_grad[1]
         need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         g = g.contiguous()
-        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias)
+        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias, tickets=tickets)
         _, dx = ops.cat_relu_backward(g, out, ctx.c1, skip_half_only=True)
         return dyn, dbias, dg, db, None, dx
 
@@ -148,21 +148,21 @@ class _InstNormActSkip(torch.autograd.Function):
     def forward(ctx, y, bias, gamma, beta, eps, act, slope, c1):
         B, C2 = y.shape[0], y.shape[1]
         buf = torch.empty((B, c1 + C2) + tuple(y.shape[2:]), dtype=y.dtype, device=y.device)
-        x_act, mean, rstd = ops.instnorm_act_forward(y, bias, gamma, beta, eps, act, slope, relu_into=buf, relu_at=c1)
-        ctx.save_for_backward(y, bias, gamma, x_act, mean, rstd)
+        x_act, mean, rstd, tickets = ops.instnorm_act_forward(y, bias, gamma, beta, eps, act, slope, relu_into=buf, relu_at=c1, return_tickets=True)
+        ctx.save_for_backward(y, bias, gamma, x_act, mean, rstd, tickets)
         ctx.act, ctx.slope, ctx.c1 = act, slope, c1
         ctx.has_affine = gamma is not None
         return x_act, buf
 
     @staticmethod
     def backward(ctx, g_x, g_buf):
-        y, bias, gamma, x_act, mean, rstd = ctx.saved_tensors
+        y, bias, gamma, x_act, mean, rstd, tickets = ctx.saved_tensors
         need_bias = bias is not None and ctx.needs_input_grad[1]
         need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         if g_x is None:
             g_x = torch.zeros_like(x_act)
         dx, dg, db, dbias = ops.instnorm_act_backward(g_x.contiguous(), x_act, y, bias, gamma, mean, rstd, ctx.act, ctx.slope, need_affine, need_bias,
-                                                      dy2=None if g_buf is None else g_buf.contiguous(), dy2_at=ctx.c1)
+                                                      dy2=None if g_buf is None else g_buf.contiguous(), dy2_at=ctx.c1, tickets=tickets)
         return dx, dbias, dg, db, None, None, None, None
 
 
@@ -172,19 +172,19 @@ class _InstNormReLUCatInto(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, bias, gamma, beta, eps, buf):
-        _, mean, rstd = ops.instnorm_act_forward(y, bias, gamma, beta, eps, "relu", 0.0, into=buf, into_at=0)
+        _, mean, rstd, tickets = ops.instnorm_act_forward(y, bias, gamma, beta, eps, "relu", 0.0, into=buf, into_at=0, return_tickets=True)
         ctx.mark_dirty(buf)
-        ctx.save_for_backward(y, bias, gamma, buf, mean, rstd)
+        ctx.save_for_backward(y, bias, gamma, buf, mean, rstd, tickets)
         ctx.has_affine = gamma is not None
         return buf
 
     @staticmethod
     def backward(ctx, g):
-        y, bias, gamma, out, mean, rstd = ctx.saved_tensors
+        y, bias, gamma, out, mean, rstd, tickets = ctx.saved_tensors
         need_bias = bias is not None and ctx.needs_input_grad[1]
         need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         g = g.contiguous()
-        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias)
+        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias, tickets=tickets)
         return dyn, dbias, dg, db, None, g
 
 
@@ -315,9 +315,13 @@ class FusedSequential(nn.Sequential):
                 hw = y.size(2) * y.size(3)
                 if hw > ops.INSTNORM_MAX_PLANE or (hw > 16384 and hw % 4) or hw < 2 or not y.is_contiguous() \
                         or y.dtype not in (torch.float32, torch.bfloat16):
+                    dt = y.dtype
                     if conv:                       # too large for the plane-in-registers kernel: plain modules
                         y = y + m.bias.view(1, -1, 1, 1)
-                    x = norm(y)
+                    # torch's own kernels, not MIOpen's batch norm (its backward put dx 30 % and dgamma 2 % off on 145x113 planes),
+                    # and in fp32: bf16 activations are normalised in fp32 and stay bf16
+                    with torch.backends.cudnn.flags(enabled=False):
+                        x = norm(y.float()).to(dt) if dt == torch.bfloat16 else norm(y)
                     i = j
                     continue
                 nxt = mods[j] if j < n else None

@@ -364,10 +364,14 @@ def _select_wrw(mode, _nosm, transposed, B, Cin, H, W, Cout, k, stride, pad, dil
     return "miopen"
 
 
-def _bf16_direct_call(op, inp, w, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, out_dtype):
-    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form."""
+def _bf16_direct_call(op, inp, w, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, out_dtype, param=None):
+    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form.
+    param: the module's weight Parameter when `w` is a detached view of it (the no-grad path).  Frozen weights (a leaf Parameter
+    with requires_grad False, outside autograd) keep their packed bf16 image, cached under the Parameter."""
     if k == 3:
-        return ops.conv3x3_bf16(op, inp, w, (B, Cin, H, W), Cout, out_dtype=out_dtype, keep_packed=not w.requires_grad and not torch.is_grad_enabled())
+        param = w if param is None else param
+        frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
+        return ops.conv3x3_bf16(op, inp, w, (B, Cin, H, W), Cout, out_dtype=out_dtype, keep_packed=frozen, pack_key=param)
     return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), out_dtype=out_dtype)
 
 
@@ -548,7 +552,8 @@ def conv_nobias(m, x, weight=None):
             return ops.conv2d(op, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, k, stride, pad, dil)
         elif eng == "bf16d":
             xb = x.contiguous()
-            return _bf16_direct_call(op, xb if xb.dtype == torch.bfloat16 else xb.to(torch.bfloat16), w.detach(), transposed, B, Cin, H, W, Cout, k, stride, pad, dil, act)
+            return _bf16_direct_call(op, xb if xb.dtype == torch.bfloat16 else xb.to(torch.bfloat16), w.detach(), transposed, B, Cin, H, W, Cout, k, stride, pad, dil, act,
+                                     param=w)
         elif eng == "wino_dil":
             return ops.conv4x4_dilated_winograd(0, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, geom=ops.conv4x4_geometry(k, stride, pad, dil),
                                                 math=math, out_dtype=act)

@@ -82,7 +82,11 @@ class Vgg16(torch.nn.Module):
         """No-grad HIP path of one slice (fp32, or bf16 activations under autocast).  Per convolution:
           * Winograd F(4x4,3x3) (csrc/winograd.hip) where models/hipconv.py selects it, with the bias + ReLU (+ the 2x2
             max-pool when it follows) done in the kernel's output transform and the transformed filter cached per layer
-            (the weights are frozen);
+            (the weights are frozen; the cache is keyed by the weight's data pointer and version counter, so `copy_`,
+            `load_state_dict` and a device round trip refill it, but a write through `weight.data` is not seen: `.data`
+            has a version counter of its own);
+          * under bf16 the direct bf16 kernel where hipconv selects it, its packed bf16 weights cached under the Parameter
+            (ops.conv3x3_bf16, same key and the same limit);
           * conv1_1 (3 input channels at full resolution): csrc/thin_conv.hip, bias + ReLU in the same pass;
           * otherwise the convolution without bias (MIOpen has none; PyTorch would add it in a separate pass), then ONE pass
             for bias + ReLU (+ pool) — ops.bias_act_ / ops.bias_relu_pool2.

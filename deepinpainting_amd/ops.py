@@ -277,8 +277,10 @@ def _check_wide(wide, x, what):
         raise RuntimeError("%s %s does not extend %s along the channels" % (what, tuple(wide.shape), tuple(x.shape)))
 
 
-def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_at=0, relu_into=None, relu_at=0):
+def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_at=0, relu_into=None, relu_at=0, return_tickets=False):
     """y = act(InstanceNorm(x + bias[c]) * gamma[c] + beta[c]) -> (y, mean [B*C], rstd [B*C]); x contiguous fp32 / bf16 [B,C,H,W].
+    return_tickets: also return tickets [C] int32, the arrival counters of the backward's in-launch batch sums, zeroed by this
+    launch — hand them to `instnorm_act_backward` together with the statistics (one set per autograd node, like `bias_act_`'s).
     into / into_at: a contiguous [B,Ctot,H,W] tensor whose channels [into_at, into_at + C) receive y (a skip concatenation written
     in place); the returned y is then `into` itself.  relu_into / relu_at: a second destination of the same kind that receives
     relu(normalised value) — the skip half of the CHILD level's concatenated tensor."""
@@ -287,13 +289,13 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
     hw = x.numel() // (B * C)
     # one allocation: mean [B*C] | rstd [B*C] | the C ticket words of the backward's in-launch batch sums, zeroed by this launch
     stats = torch.empty(2 * B * C + C, dtype=torch.float32, device=x.device)
-    mean, rstd, tickets = stats[:B * C], stats[B * C:2 * B * C], stats[2 * B * C:]
+    mean, rstd, tickets = stats[:B * C], stats[B * C:2 * B * C], stats[2 * B * C:].view(torch.int32)
     if into is None and relu_into is None:
         y = torch.empty_like(x)
         _lib.check(_lib.lib().ipsr_instnorm_act_forward(x.data_ptr(), _ptr(_f32(bias)), _ptr(_f32(gamma)), _ptr(_f32(beta)), float(eps),
                                                         ACT_CODE[act], float(slope), B, C, hw, bf, y.data_ptr(), mean.data_ptr(),
                                                         rstd.data_ptr(), tickets.data_ptr(), _stream()), "ipsr_instnorm_act_forward")
-        return y, mean, rstd
+        return (y, mean, rstd, tickets) if return_tickets else (y, mean, rstd)
     if into is not None:
         _check_wide(into, x, "instnorm_act_forward: `into`")
         if into_at < 0 or into_at + C > into.shape[1]:
@@ -312,33 +314,28 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
                                                           ACT_CODE[act], float(slope), B, C, hw, bf, yp, ybs, y2p, y2bs,
                                                           mean.data_ptr(), rstd.data_ptr(), tickets.data_ptr(), _stream()),
                "ipsr_instnorm_act_forward_slice")
-    return y, mean, rstd
+    return (y, mean, rstd, tickets) if return_tickets else (y, mean, rstd)
 
 
-def _tickets_behind(mean, rstd, B, C):
-    """The ticket words `instnorm_act_forward` allocated behind its statistics (and zeroed in its launch); statistics that came from
-    somewhere else get fresh zeroed words."""
-    n = B * C
-    if mean.dtype == torch.float32 and mean.numel() == n and rstd.numel() == n and rstd.data_ptr() == mean.data_ptr() + 4 * n \
-            and mean.untyped_storage().nbytes() - 4 * mean.storage_offset() >= 4 * (2 * n + C):
-        return mean.data_ptr() + 8 * n, None
-    t = torch.zeros(C, dtype=torch.int32, device=mean.device)
-    return t.data_ptr(), t
-
-
-def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_affine, need_bias, at=0, dy2=None, dy2_at=0):
+def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_affine, need_bias, at=0, dy2=None, dy2_at=0, tickets=None):
     """-> (dx, dgamma [C] | None, dbeta [C] | None, dbias [C] | None).  dy and y may be WIDER than x along the channels (contiguous
     [B,Ctot,H,W]): their channels [at, at + C) are the operands (a skip concatenation and its gradient, read in place).  dy2 / dy2_at:
-    the gradient of the relu'd second output of the forward (channels [dy2_at, dy2_at + C) of a wide tensor), added inside the kernel."""
+    the gradient of the relu'd second output of the forward (channels [dy2_at, dy2_at + C) of a wide tensor), added inside the kernel.
+    tickets: the int32 [C] words `instnorm_act_forward(..., return_tickets=True)` returned (None: fresh zeroed words are allocated
+    here; they are never looked up behind `mean` / `rstd`)."""
     x, bf = _req_io(x, "x")
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
+    if tickets is None:
+        tickets = torch.zeros(C, dtype=torch.int32, device=x.device)
+    elif tickets.dtype != torch.int32 or tickets.numel() != C or not tickets.is_contiguous() or tickets.device != x.device:
+        raise RuntimeError("instnorm_act_backward: `tickets` must be the contiguous int32 [%d] words of the forward on %s" % (C, x.device))
+    tick = tickets.data_ptr()
     dy, _ = _req_io(dy.to(x.dtype), "grad_output")
     dx = torch.empty_like(x)
     part = torch.empty((3, B, C), dtype=torch.float32, device=x.device)
     # the batch sums of the per-plane partials are written by the same launch (the last plane of each channel to finish)
     sums = torch.empty((3, C), dtype=torch.float32, device=x.device)
-    tick, _keep = _tickets_behind(mean, rstd, B, C)
     L = _lib.lib()
     if dy.shape[1] == C and y.shape[1] == C and dy2 is None:
         _lib.check(L.ipsr_instnorm_act_backward(dy.data_ptr(), y.data_ptr(), x.data_ptr(), _ptr(_f32(bias)), _ptr(_f32(gamma)),
@@ -558,10 +555,13 @@ def conv3x3_bf16_supported(op, B, Cin, H, W, Cout):
     return _lib.lib().ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout) > 0
 
 
-# frozen weights: weight tensor (weakly held) -> {op: (version, shape, buffer holding the re-packed bf16 weights)}.  Keyed by the tensor OBJECT:
-# a storage pointer comes back to life with another tensor's data once the first is freed (two test cases with equal shapes met that way).
-# (id-keyed with a weak reference for liveness: tensors compare elementwise, which rules out a WeakKeyDictionary)
+# frozen weights: weight tensor (weakly held) -> {op: ((version, data pointer), shape, buffer holding the re-packed bf16 weights)}.  Keyed by
+# the tensor OBJECT (the module's Parameter, `pack_key`): a storage pointer comes back to life with another tensor's data once the first is
+# freed (two test cases with equal shapes met that way).  (id-keyed with a weak reference for liveness: tensors compare elementwise, which
+# rules out a WeakKeyDictionary)
 _BF16_PACKS = {}
+# conv3x3_bf16 calls that ran the weight-packing launch (a cache miss, or no cache asked for): what tests count the cache's hits by
+bf16_pack_launches = 0
 
 
 def _packs_of(weight):
@@ -573,11 +573,14 @@ def _packs_of(weight):
     return ent[1]
 
 
-def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep_packed=False):
+def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep_packed=False, pack_key=None):
     """k3 s1 p1 convolution / transposed convolution / their input gradients as ONE direct implicit GEMM on the bf16 matrix cores
     (ipsr_conv3x3_bf16, csrc/conv_bf16.hip): bf16 activations in, bf16 or fp32 out, fp32 weights cast inside.  BASELINE config 5.
-    keep_packed: the weights are FROZEN (VGG16): their re-packed bf16 image is kept (keyed by storage pointer and version) and the
-    packing launch skipped from the second call on."""
+    keep_packed: the weights are FROZEN (VGG16): their re-packed bf16 image is kept and the packing launch skipped from the second
+    call on.  The image is cached under the tensor object `pack_key` (default `weight`; pass the Parameter when `weight` is a
+    detached view of it, which is a new object on every call) and is valid while the key's version counter and data pointer are
+    unchanged.  Writes through `weight.data` are not seen: `.data` has a version counter of its own."""
+    global bf16_pack_launches
     B, Cin, H, W = in_shape
     inp, in_bf = _act(inp, "conv input")
     if not in_bf:
@@ -597,7 +600,7 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
     out = torch.empty((B, Cout if fwd else Cin, H, W), dtype=out_dtype, device=inp.device)
     valid = 0
     if keep_packed:
-        packs = _packs_of(weight)
+        packs = _packs_of(weight if pack_key is None else pack_key)
         ent = packs.get(op)
         if ent is not None and ent[0] == (weight._version, weight.data_ptr()) and ent[1] == tuple(weight.shape) and ent[2].numel() >= nbytes \
                 and ent[2].device == inp.device:
@@ -607,6 +610,7 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
             packs[op] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
     else:
         ws = _workspace(nbytes, inp.device)
+    bf16_pack_launches += 1 - valid
     _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, int(out_dtype == torch.bfloat16),
                                           valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
     return out

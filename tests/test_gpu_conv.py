@@ -616,49 +616,90 @@ def test_split_bf16_winograd_arithmetic_all_families(math, io_bf16):
         assert _relerr(y, y64) <= otol and _relerr(dx, dx64) <= otol and _relerr(dw, dw64) <= tol, ("s2", Kc, Cf, nh, nw, _relerr(y, y64), _relerr(dx, dx64), _relerr(dw, dw64))
 
 
-def test_every_engine_call_of_a_training_step_checked_in_situ(tmp_path):
-    """One full optimize_parameters() at BASELINE config 2's batch (8 x 256x256, dropout on, as bench.py runs it): EVERY
-    convolution call that goes through a HIP engine — forward, input gradient and weight gradient, on the tensors the step really
-    produces — is recomputed by MIOpen on the same operands and compared: within 1e-4 of the result's scale.  (A whole-net
-    gradient comparison cannot discriminate: netG's backward amplifies fp32 forward noise to 0.7 % between two MIOpen-only runs,
-    tests/test_gpu_model.py::test_all_four_nets_gradients_...; per call there is nothing to amplify.)  Also proves which engines
-    the step runs on."""
+# ---- every engine call of a real training step, recomputed by MIOpen on the same operands -----------------------------------------
+# What each engine does to an fp32 operand on a call with a bf16 side (the reference is an fp32 MIOpen convolution of exactly what the
+# kernel multiplied; on an all-fp32 call nothing is rounded anywhere):
+#   engine      weights                                                          fp32 activation operand
+#   bf16d       rounded: csrc/conv_bf16.hip:95 (cb_pack_weights_kernel, (__bf16)v;  rounded: models/hipconv.py:403 / :461 (.to(bf16)
+#               the k4 s2 p1 form packs through the same kernel)                  before the kernel)
+#   thin_f2m    rounded: csrc/thin_conv.hip:470 (f2bf(w))                         rounded: the window gather feeds v_mfma_*_bf16
+#   thin        rounded: csrc/thin_conv.hip:47 / :98 (thin_rb when a side is bf16) rounded: csrc/thin_conv.hip:64 / :126
+#   thin_mfma   (weight gradient: does not read the weights)                      rounded: csrc/thin_conv.hip:355 (f2bf2), hipconv.py:465
+#   winograd, wino_dil, wino_s2 (bf16x3)
+#               split, not rounded: csrc/winograd.hip:123-126 (hi + lo bf16)      split as well; the weight gradient reads x cast to
+#                                                                                 dy's dtype (hipconv.py:461)
+#   one, smallmap   fp32 weights                                                  exact fp32 copies (hipconv.py:411-413, :475-478)
+_ROUNDS_WEIGHTS = ("bf16d", "thin_f2m", "thin")
+_ROUNDS_INPUT = ("bf16d", "thin_f2m", "thin")                                    # forward / input gradient
+_WRW_KEEPS_X = ("one", "smallmap", "miopen")                                    # weight gradient: every other engine reads x in bf16
+
+
+def _band(engine, math, result):
+    """Bound of one call's error relative to the reference's max |value|, from the unit test that bounds the engine:
+        split-bf16 Winograd (bf16x3): 1e-3  (test_split_bf16_winograd_arithmetic_all_families);
+        fp32 Winograd, direct bf16 (bf16d / thin_f2m / thin_mfma, fp32 accumulation: <= 1e-5 against fp64 in
+        test_direct_bf16_conv_all_passes / test_thin_*) and the cast engines (one / smallmap / thin): 1e-4, MIOpen's own fp32 noise;
+        a bf16 result adds its own rounding, 2^-8."""
+    base = 1e-3 if (engine in ("winograd", "wino_dil", "wino_s2") and math == "bf16x3") else 1e-4
+    return base + (2.0 ** -8 if result.dtype == torch.bfloat16 else 0.0)
+
+
+def _check_step_in_situ(tmp_path, opt_kw, img, mask, ref):
+    """Build a trainer from Option(**opt_kw), run two optimize_parameters(); the second (on weights Adam has moved: real, non-initial
+    statistics) goes through hipconv._check_hook, which recomputes every call a HIP engine made — forward, input gradient, weight
+    gradient, on the tensors the step really produces — with MIOpen in fp32 on the same operands (bf16 activations upcast exactly,
+    weights rounded to bf16 only for the engines that round them: table above).  -> (model, {(kind, engine, x shape, w shape, stride,
+    pad, dil): (worst error, band)}, {(kind, engine): [worst error per shape]}, netG's first weight before the steps, number of HIP calls)."""
     import contextlib
     import io
     import torch.nn.functional as F_
     from deepinpainting_amd.models import hipconv
     from deepinpainting_amd.options import Option
     from deepinpainting_amd.models.models import create_model
-    opt = Option(gpu_ids=[0], batchSize=8, use_dropout=True, quiet=True, allow_random_vgg=True, checkpoints_dir=str(tmp_path))
+    opt = Option(gpu_ids=[0], quiet=True, allow_random_vgg=True, checkpoints_dir=str(tmp_path), **opt_kw)
     torch.manual_seed(5)
     with contextlib.redirect_stdout(io.StringIO()):
         m = create_model(opt)
-    g = torch.Generator(device="cuda").manual_seed(21)
-    img = torch.rand(8, 3, 256, 256, device="cuda", generator=g) * 2 - 1
-    ref = torch.rand(8, 3, 256, 256, device="cuda", generator=g) * 2 - 1
-    mask = torch.zeros(1, 1, 256, 256, dtype=torch.bool, device="cuda")
-    mask[:, :, 64:192, 64:192] = 1
+    w0 = m.netG.model.model[0].weight.detach().clone()
     seen = {}
+    calls = [0]
+
+    def rnd(t):
+        return t.to(torch.bfloat16).float()
 
     def hook(kind, engine, geom, operands, result):
         if engine == "miopen":
             return
+        calls[0] += 1
         transposed, k, stride, pad, dil, Cout = geom
-        with torch.no_grad():
+        bf16_call = result.dtype == torch.bfloat16 or any(t.dtype == torch.bfloat16 for t in operands)
+        math = hipconv._MATH["bf16" if bf16_call else "fp32"]
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
             if kind == "forward":
                 x, w = operands
+                x, w = x.float(), w.float()
+                if bf16_call:
+                    x = rnd(x) if engine in _ROUNDS_INPUT else x
+                    w = rnd(w) if engine in _ROUNDS_WEIGHTS else w
                 want = F_.conv_transpose2d(x, w, None, stride, pad, 0, 1, dil) if transposed else F_.conv2d(x, w, None, stride, pad, dil)
             else:
                 dy, x, w = operands
+                dy, x, w = dy.float(), x.float(), w.float()
+                if bf16_call:
+                    dy = rnd(dy)
+                    if kind == "input_grad":
+                        w = rnd(w) if engine in _ROUNDS_WEIGHTS else w
+                    elif engine not in _WRW_KEEPS_X:
+                        x = rnd(x)
                 which = [kind == "input_grad", kind == "weight_grad", False]
                 out = torch.ops.aten.convolution_backward(dy, x, w, None, [stride, stride], [pad, pad], [dil, dil], transposed, [0, 0], 1, which)
                 want = out[0] if kind == "input_grad" else out[1]
             scale = float(want.abs().max())
             err = float((result.float() - want).abs().max()) / max(scale, 1e-30)
         key = (kind, engine, tuple(operands[-2].shape) if kind != "forward" else tuple(operands[0].shape), tuple(w.shape), stride, pad, dil)
-        seen[key] = max(seen.get(key, 0.0), err)
+        seen[key] = (max(seen.get(key, (0.0,))[0], err), _band(engine, math, result))
 
-    for step in range(2):               # the second step runs on weights Adam has moved (real, non-initial statistics)
+    for step in range(2):
         hipconv._check_hook = hook if step == 1 else None
         try:
             m.set_input(img, mask, ref)
@@ -669,21 +710,88 @@ def test_every_engine_call_of_a_training_step_checked_in_situ(tmp_path):
             hipconv._check_hook = None
     torch.cuda.synchronize()
     engines = {}
-    for (kind, engine, xs, ws_, st, pd, dl), err in sorted(seen.items(), key=lambda kv: -kv[1]):
+    for (kind, engine, xs, ws_, st, pd, dl), (err, band) in seen.items():
         engines.setdefault((kind, engine), []).append(err)
-    worst = sorted(seen.items(), key=lambda kv: -kv[1])[:12]
-    print("engine calls checked: %d distinct (kind, engine, shape)" % len(seen))
+    print("engine calls checked: %d, %d distinct (kind, engine, shape)" % (calls[0], len(seen)))
     for (kind, engine), errs in sorted(engines.items()):
-        print("  %-12s %-9s %3d shapes, worst %.1e" % (kind, engine, len(errs), max(errs)))
-    for key, err in worst:
-        print("  worst: %.2e %s" % (err, key))
+        bands = [b for kk, (e, b) in seen.items() if kk[:2] == (kind, engine)]
+        print("  %-12s %-9s %3d shapes, worst %.1e  (band %.1e)" % (kind, engine, len(errs), max(errs), max(bands)))
+    for key, (err, band) in sorted(seen.items(), key=lambda kv: -kv[1][0] / kv[1][1])[:12]:
+        print("  worst against its band: %.2e / %.1e %s" % (err, band, key))
+    return m, seen, engines, w0, calls[0]
+
+
+def _step_inputs(B, S, hole, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    img = torch.rand(B, 3, S, S, device="cuda", generator=g) * 2 - 1
+    ref = torch.rand(B, 3, S, S, device="cuda", generator=g) * 2 - 1
+    mask = torch.zeros(1, 1, S, S, dtype=torch.bool, device="cuda")
+    lo = (S - hole) // 2
+    mask[:, :, lo:lo + hole, lo:lo + hole] = 1
+    return img, mask, ref
+
+
+def test_every_engine_call_of_a_training_step_checked_in_situ(tmp_path):
+    """One full optimize_parameters() at BASELINE config 2's batch (8 x 256x256, dropout on, as bench.py runs it): EVERY
+    convolution call that goes through a HIP engine — forward, input gradient and weight gradient, on the tensors the step really
+    produces — is recomputed by MIOpen on the same operands and compared: within 1e-4 of the result's scale.  (A whole-net
+    gradient comparison cannot discriminate: netG's backward amplifies fp32 forward noise to 0.7 % between two MIOpen-only runs,
+    tests/test_gpu_model.py::test_all_four_nets_gradients_...; per call there is nothing to amplify.)  Also proves which engines
+    the step runs on."""
+    img, mask, ref = _step_inputs(8, 256, 128, 21)
+    _, seen, engines, _, _ = _check_step_in_situ(tmp_path, dict(batchSize=8, use_dropout=True), img, mask, ref)
     assert len(seen) >= 60
     for need in (("forward", "winograd"), ("input_grad", "winograd"), ("weight_grad", "winograd"), ("forward", "wino_s2"), ("input_grad", "wino_s2"),
                  ("weight_grad", "wino_s2"), ("forward", "wino_dil"), ("input_grad", "wino_dil"), ("weight_grad", "wino_dil"),
                  ("weight_grad", "smallmap"), ("forward", "smallmap"), ("input_grad", "smallmap"), ("input_grad", "direct")):
         assert need in engines, "the step did not run %s on the %s engine" % need
-    bad = [(k, e) for k, e in seen.items() if not e <= 1e-4]
+    bad = [(k, e) for k, (e, _) in seen.items() if not e <= 1e-4]
     assert not bad, bad
+
+
+def test_every_engine_call_of_the_bf16_step_checked_in_situ(tmp_path):
+    """BASELINE config 5 (bf16 autocast, batch 16, 256x256, dropout on, the 128x128 centre hole; the inputs of
+    tests/test_gpu_model.py::test_trainer_bf16_config5_at_batch16): every HIP call of the second step within its engine's band of
+    an fp32 MIOpen convolution of the same operands (`_band`).  At step level the bf16 trainer is otherwise held only to 8 % of the
+    fp32 trainer's losses; here a wrong layer shape, tile edge or reduction split of one engine is named."""
+    img, mask, ref = _step_inputs(16, 256, 128, 11)
+    _, seen, engines, _, ncalls = _check_step_in_situ(tmp_path, dict(batchSize=16, use_dropout=True, amp_bf16=True), img, mask, ref)
+    # profiles/r04_engine_map_bf16.txt: 123 HIP calls per step; netP and netG share layer shapes, so 94 distinct ones (measured)
+    assert ncalls >= 100 and len(seen) >= 90, (ncalls, len(seen))
+    for kind, names in (("forward", ("bf16d", "thin_f2m", "wino_dil", "smallmap", "one")),
+                        ("input_grad", ("bf16d", "wino_dil", "smallmap", "thin")),
+                        ("weight_grad", ("bf16d", "thin_mfma", "winograd", "wino_dil", "smallmap", "one"))):
+        for name in names:
+            assert (kind, name) in engines, "the bf16 step did not run %s on the %s engine" % (kind, name)
+    k3 = [key for key in seen if key[1] == "bf16d" and key[3][-1] == 3]
+    assert any(key[2][-1] == 16 for key in k3), "the direct bf16 kernel never ran on a 16x16 map (the split reduction)"
+    assert any(key[2][-1] >= 128 for key in seen if key[1] == "bf16d"), "the direct bf16 kernel never ran on a map >= 128 wide"
+    bad = [(k, e, b) for k, (e, b) in seen.items() if not e <= b]
+    assert not bad, bad
+
+
+def test_every_engine_call_of_the_512_step_checked_in_situ(tmp_path):
+    """BASELINE config 4: fp32, 512x512, batch 4, 3x3 patches in the IPSR layer, a 256x256 centre hole.  Two steps: losses finite,
+    netG's first weight moves, every HIP call of the second step within 1e-4 of MIOpen on the same operands, and no engine the
+    dispatcher picks at these extents refuses its call (VGG conv1_x and the thin kernels on 512-wide maps, 256x256 instance-norm planes
+    at the kernel's limit)."""
+    img, mask, ref = _step_inputs(4, 512, 256, 41)
+    m, seen, engines, w0, _ = _check_step_in_situ(tmp_path, dict(batchSize=4, fineSize=512, shift_sz=3, use_dropout=True), img, mask, ref)
+    e = m.get_current_errors()
+    assert all(np.isfinite(v) for v in e.values()), e
+    assert tuple(m.fake_B.shape) == (4, 3, 512, 512) and not torch.equal(m.netG.model.model[0].weight.detach(), w0)
+    print("engines reached at 512x512:", sorted(engines))
+    for need in _ENGINES_AT_512:
+        assert need in engines, "the 512x512 step did not run %s on the %s engine" % need
+    bad = [(k, e) for k, (e, _) in seen.items() if not e <= 1e-4]
+    assert not bad, bad
+
+
+# what the 512x512 step reaches (printed by the test above on an MI355X): a later change must not route these to MIOpen unnoticed
+_ENGINES_AT_512 = (("forward", "smallmap"), ("forward", "thin"), ("forward", "wino_dil"), ("forward", "wino_s2"), ("forward", "winograd"),
+                   ("input_grad", "direct"), ("input_grad", "smallmap"), ("input_grad", "thin"), ("input_grad", "wino_dil"), ("input_grad", "wino_s2"),
+                   ("input_grad", "winograd"), ("weight_grad", "smallmap"), ("weight_grad", "thin_mfma"), ("weight_grad", "wino_dil"),
+                   ("weight_grad", "wino_s2"), ("weight_grad", "winograd"))
 
 
 @pytest.mark.parametrize("tr,Cin,H,W,Cout,B", [(False, 32, 16, 16, 48, 2), (False, 128, 32, 32, 160, 3), (True, 64, 32, 64, 48, 2), (False, 16, 128, 128, 16, 1),
@@ -895,3 +1003,149 @@ def test_vgg_and_unet_outputs_unchanged_by_the_engines():
     for eng in ("direct", "auto"):          # the one-launch implicit GEMM everywhere; the dispatcher's own per-shape choices
         for a, b in zip(grads[eng], grads["miopen"]):
             assert float((a - b).abs().max()) <= 1e-3 * float(b.abs().max()) + 3e-4 * gmax, eng
+
+
+# ---- VGG16's fused no-grad slices (models/vgg16.py::_fused_slice): they call the engines directly, the in-situ hook never sees them ----
+def _vgg_slice_reference(seq, x, bf16):
+    """The plain modules of one slice in fp32 on MIOpen, on the same input (bf16 upcast).  Under bf16 the roundings the fused path
+    makes are made here too, so that only the engines' arithmetic and the LAST rounding are left to compare: the weights of the
+    engines that round them (and MIOpen's under autocast), an fp32 input those engines read in bf16, the bf16 convolution result
+    of the split path (convolution -> bf16 tensor -> bias pass) and every intermediate activation.  The last layer stays unrounded.
+    -> (fp32 result, band, engines): the widest `_band` of the slice's convolutions, plus 2^-8 for the rounding of the bf16 result and
+    one more 2^-8 when the last convolution's result is rounded before its bias pass (two roundings of half an ulp each)."""
+    from deepinpainting_amd import ops
+    from deepinpainting_amd.models import hipconv
+    mods = list(seq)
+    convs = [i for i, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
+    h = x.float()
+    base, engines = 0.0, []
+    for i in convs:
+        m = mods[i]
+        pool = i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d)
+        B, Cin, H, W = h.shape
+        eng = hipconv.select(ops.CONV_FWD, B, Cin, H, W, m.out_channels, 3, 1, 1, 1, bf16)
+        engines.append(eng)
+        base = max(base, _band(eng, hipconv._MATH["bf16" if bf16 else "fp32"], h))
+        fused_epilogue = eng == "winograd" or (eng == "thin" and not pool)
+        w = m.weight.detach()
+        if bf16 and eng in _ROUNDS_WEIGHTS + ("miopen",):
+            w, h = w.to(torch.bfloat16).float(), h.to(torch.bfloat16).float()
+        y = F.conv2d(h, w, None, 1, 1)
+        last = i == convs[-1]
+        if bf16 and not fused_epilogue and not last:
+            y = y.to(torch.bfloat16).float()
+        y = torch.relu(y + m.bias.detach().view(1, -1, 1, 1))
+        if pool:
+            y = F.max_pool2d(y, 2, 2)
+        h = y if (last or not bf16) else y.to(torch.bfloat16).float()
+        if last and bf16:
+            base += 2.0 ** -8 + (0.0 if fused_epilogue else 2.0 ** -8)
+    return h, base, engines
+
+
+@pytest.mark.parametrize("bf16,B,S", [(False, 16, 256), (True, 16, 256), (False, 4, 512), (True, 4, 512)])
+def test_vgg_fused_slices_and_their_weight_caches(bf16, B, S):
+    """Each of the four fused slices against its plain modules on the same input (so errors do not compound), fp32 and bf16 autocast,
+    at the trainer's two image sizes; the whole Vgg16.forward the trainer calls; a second call gives the same bits (the Winograd
+    filter cache and the bf16 packed-weight cache hit); and after `copy_`, `load_torchvision_state_dict` and a device round trip
+    with a `copy_` in between (new storage, possibly at the old address) the fused output follows the new weights."""
+    import contextlib
+    from deepinpainting_amd import ops
+    from deepinpainting_amd.models import hipconv
+    from deepinpainting_amd.models.vgg16 import Vgg16
+    vgg = Vgg16().cuda().eval()
+    g = torch.Generator(device="cuda").manual_seed(61)
+    x = torch.rand(B, 3, S, S, device="cuda", generator=g) * 2 - 1
+    slices = (vgg.slice1, vgg.slice2, vgg.slice3, vgg.slice4)
+    amp = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if bf16 else contextlib.nullcontext
+    info = []
+
+    def check(tag):
+        outs, h = [], x
+        for n, seq in enumerate(slices, start=1):
+            with torch.no_grad(), amp():
+                y = vgg._fused_slice(seq, h)
+            assert y.dtype == (torch.bfloat16 if bf16 else torch.float32), (tag, n, y.dtype)
+            with torch.no_grad():
+                want, band, engines = _vgg_slice_reference(seq, h, bf16)
+            err = float((y.float() - want).abs().max()) / float(want.abs().max())
+            print("  %-10s slice%d %s %s: %.2e (band %.1e)" % (tag, n, tuple(y.shape), "/".join(engines), err, band))
+            info.append((band, engines))
+            assert err <= band, (tag, n, err, band)
+            outs.append(y)
+            h = y
+        return outs
+
+    first = check("first")
+    with torch.no_grad(), amp():
+        again, h = [], x
+        for seq in slices:
+            again.append(vgg._fused_slice(seq, h))
+            h = again[-1]
+        whole = vgg(x)
+    for n, (a, b, c, (band, engines)) in enumerate(zip(first, again, whole, info), start=1):
+        assert c.dtype == a.dtype
+        if "miopen" not in engines:     # MIOpen may switch solvers between calls: bit-identity where no layer of the chain runs there
+            assert torch.equal(a, b), "slice%d: a second call (cached filters / packed weights) changed the bits" % n
+        if all("miopen" not in e for _, e in info[:n]):
+            assert torch.equal(c, a), "slice%d: Vgg16.forward differs from its fused slices" % n
+        else:
+            assert float((c.float() - a.float()).abs().max()) <= band * float(a.float().abs().max()), n
+
+    def new_weights(seed):
+        gg = torch.Generator().manual_seed(seed)
+        return {k: v.cpu() * (0.5 + torch.rand(v.shape, generator=gg)) for k, v in vgg.state_dict().items() if k.endswith("weight")}
+
+    def moved(outs):
+        return all(not torch.equal(a, b) for a, b in zip(outs, first))
+
+    with torch.no_grad():
+        for k, v in new_weights(1).items():
+            vgg.get_parameter(k).copy_(v.cuda())
+    assert moved(check("copy_"))
+    sd = {}
+    for k, v in vgg.state_dict().items():                         # the same weights under torchvision's names, then new ones
+        si, idx, what = k.split(".")
+        sd["features.%s.%s" % (idx, what)] = v.cpu()
+    for k, v in new_weights(2).items():
+        si, idx, what = k.split(".")
+        sd["features.%s.%s" % (idx, what)] = v.cpu()
+    vgg.load_torchvision_state_dict(sd)
+    assert moved(check("load_sd"))
+    vgg.cpu()
+    with torch.no_grad():
+        for k, v in new_weights(3).items():
+            vgg.get_parameter(k).copy_(v)
+    vgg.cuda()
+    assert moved(check("roundtrip"))
+
+
+def test_bf16_packed_weight_cache_hits_for_frozen_vgg():
+    """Two bf16 no-grad Vgg16 forwards: the direct bf16 kernel's packed weights are made once per (layer, op) and kept under the
+    Parameter — the second forward runs no packing launch.  Trainable weights on the no-grad path are not kept."""
+    from deepinpainting_amd import ops
+    from deepinpainting_amd.models.vgg16 import Vgg16
+    vgg = Vgg16().cuda().eval()
+    x = torch.rand(16, 3, 256, 256, device="cuda") * 2 - 1
+    counts = [ops.bf16_pack_launches]
+    for _ in range(2):
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            vgg(x)
+        counts.append(ops.bf16_pack_launches)
+    torch.cuda.synchronize()
+    convs = [m for m in vgg.modules() if isinstance(m, nn.Conv2d)]
+    kept = [ops._BF16_PACKS[id(m.weight)][1] for m in convs if id(m.weight) in ops._BF16_PACKS]
+    print("packing launches per forward:", counts[1] - counts[0], counts[2] - counts[1], " layers kept:", len(kept))
+    assert counts[1] > counts[0], "no VGG layer ran on the direct bf16 kernel: the test checks nothing"
+    assert counts[2] == counts[1], "the second forward packed the frozen weights again: the cache never hits"
+    assert 1 <= len(kept) <= len(convs) and all(len(ent) == 1 for ent in kept)
+    assert counts[1] - counts[0] == len(kept)
+    # a trainable layer on the no-grad path: packed on every call, nothing kept under its weight
+    conv = nn.Conv2d(128, 128, 3, 1, 1).cuda()
+    from deepinpainting_amd.models import hipconv
+    xb = torch.randn(16, 128, 128, 128, device="cuda").to(torch.bfloat16)
+    n0 = ops.bf16_pack_launches
+    with torch.no_grad():
+        y1 = hipconv.conv_nobias(conv, xb)
+        y2 = hipconv.conv_nobias(conv, xb)
+    assert ops.bf16_pack_launches - n0 == 2 and id(conv.weight) not in ops._BF16_PACKS and torch.equal(y1, y2)
