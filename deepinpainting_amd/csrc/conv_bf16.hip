@@ -1059,8 +1059,9 @@ int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* 
 {
     if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: null pointer");
     if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: bad argument");
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: in / workspace must be 16-byte aligned");
+    // out: the bf16 tile leaves as uint4 rows (conv_bf16_kernel's epilogue), the split reduction stores 4-element vectors
+    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: in / out / workspace must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (op) {       // (sc, sk, flip) as in ipsr_conv3x3_winograd_mp: C = reduction channels, K = produced channels
         case 0: return launch_conv_bf16(in, weight, out, B, Cin, Cout, H, W, 9, (long)Cin * 9, 0, out_bf16, ws, ws_bytes, st, pack_valid);
@@ -1081,7 +1082,8 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
 {
     if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: null pointer");
     if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: bad argument");
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 7u))
+    // out: the fine -> coarse bf16 tile leaves as uint4 rows, the split reduction stores 4-element vectors (16 bytes of fp32)
+    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: in / out / workspace must be 16-byte aligned");
     // weight [Kc][Cf][4][4] in both modules (Conv2d: [Cout][Cin], ConvTranspose2d: [Cin][Cout]), as in ipsr_conv4x4s2_winograd
     return launch_conv_bf16_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));

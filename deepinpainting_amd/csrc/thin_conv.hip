@@ -739,7 +739,8 @@ int ipsr_conv3x3_thin_io(int op, const void* in, const float* w, const float* bi
     if (op == 0) {          // few -> many
         if (O % THIN_OC != 0 || (I != 3 && I != 6)) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs 3 or 6 inputs and outputs %% 16 == 0 (got %d -> %d)", I, O);
         if ((size_t)B * (O / THIN_OC) > 65535 || H > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: grid too large");
-        if ((W & 1) || (reinterpret_cast<uintptr_t>(out) & (ob ? 3u : 7u))) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs an even width and an aligned output (W=%d)", W);
+        if (W & 1) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs an even width (W=%d)", W);
+        if (reinterpret_cast<uintptr_t>(out) & (ob ? 3u : 7u)) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin: few->many stores pixel pairs: out must be aligned to two elements");
         const dim3 grid(cdiv(W, 512), H, B * (O / THIN_OC));
 #define THIN_F2M(II, TI, TO) thin_f2m_kernel<II, TI, TO><<<grid, 256, 0, st>>>(static_cast<const TI*>(in), w, bias, relu, static_cast<TO*>(out), B, O, H, W, so, si, flip)
 #define THIN_F2M_IO(II) do { if (ib && ob) THIN_F2M(II, bf16_t, bf16_t); else if (ib) THIN_F2M(II, bf16_t, float); else if (ob) THIN_F2M(II, float, bf16_t); else THIN_F2M(II, float, float); } while (0)

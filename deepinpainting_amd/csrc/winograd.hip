@@ -2167,6 +2167,9 @@ int ipsr_conv3x3_winograd_mp(int op, const void* in, const float* weight, const 
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_winograd: out / workspace / filter_cache must be 16-byte aligned");
     ConvArith ar;
     if (int rc = arith_from("ipsr_conv3x3_winograd_mp", math, io, &ar)) return rc;
+    // in: wino_input_kernel reads each window's inner four columns as one 4-element vector (16 bytes of fp32, 8 of bf16)
+    if (reinterpret_cast<uintptr_t>(in) & (ar.in_bf16 ? 7u : 15u))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_winograd: in must be aligned to four elements");
     hipStream_t st = static_cast<hipStream_t>(stream);
     // k3 s1 p1: input and output have the same extent.  C = reduction channels, K = produced channels.
     switch (op) {
@@ -2250,6 +2253,9 @@ int ipsr_conv4x4s2_winograd_mp(int mode, const void* a, const void* b, void* out
     if (mode < 0 || mode > 2 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_winograd: bad argument");
     if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_winograd: out / workspace must be 16-byte aligned");
+    // b of the data passes: the filter transforms read each 4x4 weight as four float4
+    if (mode != 2 && (reinterpret_cast<uintptr_t>(b) & 15u))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_winograd: the weight must be 16-byte aligned");
     ConvArith ar;
     if (int rc = arith_from("ipsr_conv4x4s2_winograd_mp", math, io, &ar)) return rc;
     return launch_winograd_s2(mode, a, b, out, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream), ar);

@@ -30,6 +30,16 @@ def _workspace(nbytes, device):
     return buf
 
 
+def _empty(shape, dtype, device):
+    """Every result, cache and ticket buffer of this module is allocated here or in `_zeros` (scratch comes from `_workspace`):
+    the seams tests replace to place each buffer between guard bands (tests/guarded.py)."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _zeros(shape, dtype, device):
+    return torch.zeros(shape, dtype=dtype, device=device)
+
+
 def _on_current_device(t, name):
     # the kernels are launched on the CURRENT device's stream with raw pointers: a tensor living on another GPU would fault
     if t.device.index != torch._C._cuda_getDevice():        # (the C getter: this check runs ~700 times per training step)
@@ -59,7 +69,7 @@ def feat_mask(mask_hw, layers, threshold):
         m = m.to(torch.uint8)
     m = _req(m, torch.uint8, "mask")
     H, W = m.shape
-    out = torch.empty((feat_mask_out_dim(H, layers), feat_mask_out_dim(W, layers)), dtype=torch.uint8, device=m.device)
+    out = _empty((feat_mask_out_dim(H, layers), feat_mask_out_dim(W, layers)), dtype=torch.uint8, device=m.device)
     L = _lib.lib()
     nbytes = L.ipsr_feat_mask_workspace_bytes(H, W, layers)
     ws = _workspace(nbytes, m.device)
@@ -73,9 +83,9 @@ def index_prep(feat_hw, patch, stride, mask_thred):
     f = _req(feat_hw, torch.uint8, "feature mask")
     h, w = f.shape
     n = ((h - patch) // stride + 1) * ((w - patch) // stride + 1)
-    flag = torch.empty(n, dtype=torch.int32, device=f.device)
-    mpi = torch.empty(n, dtype=torch.int32, device=f.device)
-    cnt = torch.empty(1, dtype=torch.int32, device=f.device)
+    flag = _empty(n, dtype=torch.int32, device=f.device)
+    mpi = _empty(n, dtype=torch.int32, device=f.device)
+    cnt = _empty(1, dtype=torch.int32, device=f.device)
     _lib.check(_lib.lib().ipsr_index_prep(f.data_ptr(), h, w, patch, stride, int(mask_thred), flag.data_ptr(),
                                           mpi.data_ptr(), cnt.data_ptr(), _stream()), "ipsr_index_prep")
     return flag, mpi, cnt
@@ -85,8 +95,8 @@ def patch_normalize(x_bcn):
     """K3.  x [B,C,N] -> (xn [B,C,N], inv [B,N])."""
     x = _req(x_bcn, torch.float32, "x")
     B, C, N = x.shape
-    xn = torch.empty_like(x)
-    inv = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    xn = _empty(x.shape, x.dtype, x.device)
+    inv = _empty((B, N), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().ipsr_patch_normalize(x.data_ptr(), B, C, N, xn.data_ptr(), inv.data_ptr(), _stream()),
                "ipsr_patch_normalize")
     return xn, inv
@@ -98,8 +108,8 @@ def corr_argmax(xn_bcn, ref_bcn, want_S=False, corr="fp32"):
     xn = _req(xn_bcn, torch.float32, "xn")
     ref = _req(ref_bcn, torch.float32, "ref")
     B, C, N = xn.shape
-    ind = torch.empty((B, N), dtype=torch.int32, device=xn.device)
-    vmax = torch.empty((B, N), dtype=torch.float32, device=xn.device)
+    ind = _empty((B, N), dtype=torch.int32, device=xn.device)
+    vmax = _empty((B, N), dtype=torch.float32, device=xn.device)
     if corr == "bf16":
         if want_S:
             raise ValueError("corr_argmax: the bf16 kernel does not materialise S")
@@ -110,7 +120,7 @@ def corr_argmax(xn_bcn, ref_bcn, want_S=False, corr="fp32"):
         return ind, vmax, None
     if corr != "fp32":
         raise ValueError("corr must be 'fp32' or 'bf16'")
-    S = torch.empty((B, N, N), dtype=torch.float32, device=xn.device) if want_S else None
+    S = _empty((B, N, N), dtype=torch.float32, device=xn.device) if want_S else None
     L = _lib.lib()
     ws = _workspace(L.ipsr_corr_argmax_workspace_bytes(B, C, N), xn.device)
     _lib.check(L.ipsr_corr_argmax(xn.data_ptr(), ref.data_ptr(), B, C, N, ind.data_ptr(), vmax.data_ptr(),
@@ -177,11 +187,11 @@ def forward(x, ref, mask_point_idx_i32, patch=1, stride=1, want_attn=False, want
         M = int(mpi.numel())
     L = _lib.lib()
     dev = x.device
-    out = torch.empty_like(x)
-    ind = torch.empty((B, N), dtype=torch.int32, device=dev)
-    vmax = torch.empty((B, N), dtype=torch.float32, device=dev)
-    attn = torch.empty((B, M, N), dtype=torch.float32, device=dev) if (want_attn and M > 0) else None
-    bidx = torch.empty((B, L.ipsr_bwd_index_ints(N, M)), dtype=torch.int32, device=dev) if want_index else None
+    out = _empty(x.shape, x.dtype, x.device)
+    ind = _empty((B, N), dtype=torch.int32, device=dev)
+    vmax = _empty((B, N), dtype=torch.float32, device=dev)
+    attn = _empty((B, M, N), dtype=torch.float32, device=dev) if (want_attn and M > 0) else None
+    bidx = _empty((B, L.ipsr_bwd_index_ints(N, M)), dtype=torch.int32, device=dev) if want_index else None
     bf = corr == "bf16"
     nbytes = (L.ipsr_forward_bf16corr_workspace_bytes if bf else L.ipsr_forward_workspace_bytes)(B, C, h, w, M, patch, stride)
     ws = _workspace(nbytes, dev)
@@ -199,7 +209,7 @@ def forward(x, ref, mask_point_idx_i32, patch=1, stride=1, want_attn=False, want
         bidx.data_ptr() if bidx is not None else None, ws.data_ptr(), ws.numel(), _stream()),
         "ipsr_forward_bf16corr" if bf else "ipsr_forward")
     if want_attn and attn is None:
-        attn = torch.empty((B, 0, N), dtype=torch.float32, device=dev)
+        attn = _empty((B, 0, N), dtype=torch.float32, device=dev)
     return Forward(out, ind, vmax, attn, bidx)
 
 
@@ -208,7 +218,7 @@ def backward(grad_out, bwd_index, triple_w, M, patch=1):
     patch > 1: the extension described at ipsr_backward_patch (include/ipsr_hip.h)."""
     g = _req(grad_out, torch.float32, "grad_output")
     B, C, h, w = g.shape
-    gin = torch.empty_like(g)
+    gin = _empty(g.shape, g.dtype, g.device)
     L = _lib.lib()
     if patch == 1:
         _lib.check(L.ipsr_backward(g.data_ptr(), None, int(M), None, bwd_index.data_ptr(), float(triple_w),
@@ -288,10 +298,10 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
     # one allocation: mean [B*C] | rstd [B*C] | the C ticket words of the backward's in-launch batch sums, zeroed by this launch
-    stats = torch.empty(2 * B * C + C, dtype=torch.float32, device=x.device)
+    stats = _empty(2 * B * C + C, dtype=torch.float32, device=x.device)
     mean, rstd, tickets = stats[:B * C], stats[B * C:2 * B * C], stats[2 * B * C:].view(torch.int32)
     if into is None and relu_into is None:
-        y = torch.empty_like(x)
+        y = _empty(x.shape, x.dtype, x.device)
         _lib.check(_lib.lib().ipsr_instnorm_act_forward(x.data_ptr(), _ptr(_f32(bias)), _ptr(_f32(gamma)), _ptr(_f32(beta)), float(eps),
                                                         ACT_CODE[act], float(slope), B, C, hw, bf, y.data_ptr(), mean.data_ptr(),
                                                         rstd.data_ptr(), tickets.data_ptr(), _stream()), "ipsr_instnorm_act_forward")
@@ -302,7 +312,7 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
             raise RuntimeError("instnorm_act_forward: channels [%d, %d) outside `into` %s" % (into_at, into_at + C, tuple(into.shape)))
         y, (yp, ybs) = into, _slot(into, into_at, hw)
     else:
-        y = torch.empty_like(x)
+        y = _empty(x.shape, x.dtype, x.device)
         yp, ybs = y.data_ptr(), C * hw
     y2p, y2bs = None, 0
     if relu_into is not None:
@@ -327,15 +337,15 @@ def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_af
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
     if tickets is None:
-        tickets = torch.zeros(C, dtype=torch.int32, device=x.device)
+        tickets = _zeros(C, dtype=torch.int32, device=x.device)
     elif tickets.dtype != torch.int32 or tickets.numel() != C or not tickets.is_contiguous() or tickets.device != x.device:
         raise RuntimeError("instnorm_act_backward: `tickets` must be the contiguous int32 [%d] words of the forward on %s" % (C, x.device))
     tick = tickets.data_ptr()
     dy, _ = _req_io(dy.to(x.dtype), "grad_output")
-    dx = torch.empty_like(x)
-    part = torch.empty((3, B, C), dtype=torch.float32, device=x.device)
+    dx = _empty(x.shape, x.dtype, x.device)
+    part = _empty((3, B, C), dtype=torch.float32, device=x.device)
     # the batch sums of the per-plane partials are written by the same launch (the last plane of each channel to finish)
-    sums = torch.empty((3, C), dtype=torch.float32, device=x.device)
+    sums = _empty((3, C), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     if dy.shape[1] == C and y.shape[1] == C and dy2 is None:
         _lib.check(L.ipsr_instnorm_act_backward(dy.data_ptr(), y.data_ptr(), x.data_ptr(), _ptr(_f32(bias)), _ptr(_f32(gamma)),
@@ -370,11 +380,11 @@ def bias_act_backward(dy, y, act, slope, need_bias, dy2=None, dy2_at=0, tickets=
     dy, bf = _req_io(dy.to(y.dtype), "grad_output")
     B, C = y.shape[0], y.shape[1]
     hw = y.numel() // (B * C)
-    dx = torch.empty_like(y)
-    part = torch.empty((B, C), dtype=torch.float32, device=y.device) if need_bias else None
-    sums = torch.empty(C, dtype=torch.float32, device=y.device) if need_bias else None
+    dx = _empty(y.shape, y.dtype, y.device)
+    part = _empty((B, C), dtype=torch.float32, device=y.device) if need_bias else None
+    sums = _empty(C, dtype=torch.float32, device=y.device) if need_bias else None
     if need_bias and tickets is None:
-        tickets = torch.zeros(C, dtype=torch.int32, device=y.device)
+        tickets = _zeros(C, dtype=torch.int32, device=y.device)
     if dy2 is None:
         _lib.check(_lib.lib().ipsr_bias_act_backward(dy.data_ptr(), y.data_ptr(), ACT_CODE[act], float(slope), B, C, hw, bf, dx.data_ptr(),
                                                      _ptr(part), _ptr(sums), _ptr(tickets), _stream()), "ipsr_bias_act_backward")
@@ -398,7 +408,7 @@ def cat_relu_forward(y, x):
         raise RuntimeError("cat_relu: mismatched operands %s %s / %s %s" % (tuple(y.shape), y.dtype, tuple(x.shape), x.dtype))
     B, C1, C2 = y.shape[0], y.shape[1], x.shape[1]
     hw = y.numel() // (B * C1)
-    out = torch.empty((B, C1 + C2) + tuple(y.shape[2:]), dtype=y.dtype, device=y.device)
+    out = _empty((B, C1 + C2) + tuple(y.shape[2:]), dtype=y.dtype, device=y.device)
     _lib.check(_lib.lib().ipsr_cat_relu_forward(y.data_ptr(), x.data_ptr(), B, C1, C2, hw, bf, out.data_ptr(), _stream()),
                "ipsr_cat_relu_forward")
     return out
@@ -425,8 +435,8 @@ def cat_relu_backward(grad_out, out, C1, skip_half_only=False):
     B, C = out.shape[0], out.shape[1]
     C2 = C - C1
     hw = out.numel() // (B * C)
-    dy = None if skip_half_only else torch.empty((B, C1) + tuple(out.shape[2:]), dtype=out.dtype, device=out.device)
-    dx = torch.empty((B, C2) + tuple(out.shape[2:]), dtype=out.dtype, device=out.device)
+    dy = None if skip_half_only else _empty((B, C1) + tuple(out.shape[2:]), dtype=out.dtype, device=out.device)
+    dx = _empty((B, C2) + tuple(out.shape[2:]), dtype=out.dtype, device=out.device)
     _lib.check(_lib.lib().ipsr_cat_relu_backward(g.data_ptr(), out.data_ptr(), B, C1, C2, hw, bf, _ptr(dy), dx.data_ptr(), _stream()),
                "ipsr_cat_relu_backward")
     return dy, dx
@@ -436,7 +446,7 @@ def bias_relu_pool2(x, bias):
     """max_pool2d(relu(x + bias[c]), 2, 2) of a contiguous fp32 [B,C,H,W] tensor in one pass."""
     x, bf = _req_io(x, "x")
     B, C, H, W = x.shape
-    y = torch.empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    y = _empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
     _lib.check(_lib.lib().ipsr_bias_relu_pool2(x.data_ptr(), _ptr(_f32(bias)), B, C, H, W, bf, y.data_ptr(), _stream()),
                "ipsr_bias_relu_pool2")
     return y
@@ -489,7 +499,7 @@ def conv2d(op, inp, weight, in_shape, Cout, k, stride, pad, dil):
     want_w = (Cout, Cin, k, k) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, k, k)
     if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
         raise RuntimeError("conv2d op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
-    out = torch.empty((B, Cout, Ho, Wo) if fwd else (B, Cin, H, W), dtype=torch.float32, device=inp.device)
+    out = _empty((B, Cout, Ho, Wo) if fwd else (B, Cin, H, W), dtype=torch.float32, device=inp.device)
     L = _lib.lib()
     nbytes = L.ipsr_conv2d_workspace_bytes(op, B, Cin, H, W, Cout, k, stride, pad, dil)
     if nbytes == 0:
@@ -511,7 +521,7 @@ _EPILOGUE = {None: 0, "none": 0, "relu": 1, "relu_pool": 2}
 def winograd_filter_cache(op, Cin, Cout, device):
     """An empty buffer for the transformed filter of one layer (see conv3x3_winograd's `filter_cache`)."""
     n = _lib.lib().ipsr_conv3x3_winograd_filter_floats(op, Cin, Cout)
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return _empty(n, dtype=torch.float32, device=device)
 
 
 def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, filter_cache=None, filter_cache_valid=False,
@@ -537,7 +547,7 @@ def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, 
         raise RuntimeError("conv3x3_winograd: relu_pool needs even extents, got %dx%d" % (H, W))
     kout = Cout if fwd else Cin
     oshape = (B, kout, H // 2, W // 2) if epi == 2 else (B, kout, H, W)
-    out = torch.empty(oshape, dtype=out_dtype, device=inp.device)
+    out = _empty(oshape, dtype=out_dtype, device=inp.device)
     L = _lib.lib()
     nbytes = L.ipsr_conv3x3_winograd_workspace_bytes(op, B, Cin, H, W, Cout)
     if nbytes == 0:
@@ -597,7 +607,7 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
     nbytes = L.ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout)
     if nbytes == 0:
         raise NotImplementedError("ipsr_conv3x3_bf16: op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), _lib.lib().ipsr_last_error().decode("utf-8", "replace")))
-    out = torch.empty((B, Cout if fwd else Cin, H, W), dtype=out_dtype, device=inp.device)
+    out = _empty((B, Cout if fwd else Cin, H, W), dtype=out_dtype, device=inp.device)
     valid = 0
     if keep_packed:
         packs = _packs_of(weight if pack_key is None else pack_key)
@@ -606,7 +616,7 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
                 and ent[2].device == inp.device:
             ws, valid = ent[2], 1
         else:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=inp.device)
+            ws = _empty(nbytes, dtype=torch.uint8, device=inp.device)
             packs[op] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
     else:
         ws = _workspace(nbytes, inp.device)
@@ -638,7 +648,7 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
     if nbytes == 0:
         raise NotImplementedError("ipsr_conv4x4s2_bf16: mode %d on %s is not implemented (%s)" % (mode, (B, Kc, Cf, nh, nw), L.ipsr_last_error().decode("utf-8", "replace")))
     oshape = (B, Kc, nh, nw) if mode == S2_FINE_TO_COARSE else (B, Cf, 2 * nh, 2 * nw)
-    out = torch.empty(oshape, dtype=out_dtype, device=inp.device)
+    out = _empty(oshape, dtype=out_dtype, device=inp.device)
     ws = _workspace(nbytes, inp.device)
     _lib.check(L.ipsr_conv4x4s2_bf16(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, int(out_dtype == torch.bfloat16),
                                      ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4s2_bf16")
@@ -665,7 +675,7 @@ def conv4x4s2_bf16_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     nbytes = L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw)
     if nbytes == 0:
         raise NotImplementedError("ipsr_conv4x4s2_bf16_wrw: %s is not implemented (%s)" % ((B, Kc, Cf, nh, nw), L.ipsr_last_error().decode("utf-8", "replace")))
-    dw = out if out is not None else torch.empty(shape, dtype=torch.float32, device=fine.device)
+    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=fine.device)
     ws = _workspace(nbytes, fine.device)
     _lib.check(L.ipsr_conv4x4s2_bf16_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
                "ipsr_conv4x4s2_bf16_wrw")
@@ -693,7 +703,7 @@ def conv3x3_bf16_wrw(transposed, x, dy, Cout, out=None):
     nbytes = L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout)
     if nbytes == 0:
         raise NotImplementedError("ipsr_conv3x3_bf16_wrw: %s is not implemented (%s)" % ((B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
-    dw = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=x.device)
     ws = _workspace(nbytes, x.device)
     _lib.check(L.ipsr_conv3x3_bf16_wrw(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
                                        _stream()), "ipsr_conv3x3_bf16_wrw")
@@ -738,7 +748,7 @@ def conv4x4_dilated_winograd(mode, a, b, in_shape, Cout, out=None, geom=GEOM_K4_
     if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != res_dtype or not out.is_contiguous() or out.device != a.device):
         raise RuntimeError("conv4x4_winograd: `out` must be a contiguous %s %s tensor on %s" % (res_dtype, tuple(want[2]), a.device))
     if out is None:
-        out = torch.empty(want[2], dtype=res_dtype, device=a.device)
+        out = _empty(want[2], dtype=res_dtype, device=a.device)
     L = _lib.lib()
     nbytes = L.ipsr_conv4x4_winograd_workspace_bytes(geom, mode, B, Cin, H, W, Cout)
     if nbytes == 0:
@@ -776,7 +786,7 @@ def conv4x4s2_winograd(mode, a, b, B, Kc, Cf, nh, nw, out=None, math=None, out_d
     if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != res_dtype or not out.is_contiguous() or out.device != a.device):
         raise RuntimeError("conv4x4s2_winograd: `out` must be a contiguous %s %s tensor on %s" % (res_dtype, tuple(want[2]), a.device))
     if out is None:
-        out = torch.empty(want[2], dtype=res_dtype, device=a.device)
+        out = _empty(want[2], dtype=res_dtype, device=a.device)
     L = _lib.lib()
     nbytes = L.ipsr_conv4x4s2_winograd_workspace_bytes(mode, B, Kc, Cf, nh, nw)
     if nbytes == 0:
@@ -811,7 +821,7 @@ def conv_to_one(x, w, pad):
     K = int(w.shape[-1])
     if tuple(w.shape) != (1, C, K, K):
         raise RuntimeError("conv_to_one: weight %s does not match %d input channels / one output" % (tuple(w.shape), C))
-    y = torch.empty((B, 1, H + 2 * pad - K + 1, W + 2 * pad - K + 1), dtype=torch.float32, device=x.device)
+    y = _empty((B, 1, H + 2 * pad - K + 1, W + 2 * pad - K + 1), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     ws = _workspace(L.ipsr_conv_to_one_workspace_bytes(B, C, H, W, K, int(pad)), x.device)
     _lib.check(L.ipsr_conv_to_one(0, x.data_ptr(), w.data_ptr(), y.data_ptr(), B, C, H, W, K, int(pad), ws.data_ptr(), ws.numel(), _stream()),
@@ -826,7 +836,7 @@ def conv_to_one_wrw(x, dy, K, pad, out=None):
     B, C, H, W = x.shape
     if tuple(dy.shape) != (B, 1, H + 2 * pad - K + 1, W + 2 * pad - K + 1):
         raise RuntimeError("conv_to_one_wrw: grad_output %s does not match input %s, k=%d, pad=%d" % (tuple(dy.shape), tuple(x.shape), K, pad))
-    dw = out if out is not None else torch.empty((1, C, K, K), dtype=torch.float32, device=x.device)
+    dw = out if out is not None else _empty((1, C, K, K), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().ipsr_conv_to_one(2, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, K, int(pad), None, 0, _stream()),
                "ipsr_conv_to_one")
     return dw
@@ -853,7 +863,7 @@ def conv3x3_thin(op, inp, weight, in_shape, Cout, bias=None, relu=False, out=Non
     so, si, flip = {CONV_FWD: (Cin * 9, 9, 0), CONV_BWD_DATA: (9, Cin * 9, 1), CONVT_FWD: (9, Cout * 9, 1), CONVT_BWD_DATA: (Cout * 9, 9, 0)}[op]
     io = _io_code(inp.dtype == torch.bfloat16, out_dtype)
     if out is None:
-        out = torch.empty((B, O, H, W), dtype=out_dtype, device=inp.device)
+        out = _empty((B, O, H, W), dtype=out_dtype, device=inp.device)
     elif tuple(out.shape) != (B, O, H, W) or out.dtype != out_dtype or not out.is_contiguous() or out.device != inp.device:
         raise RuntimeError("conv3x3_thin: `out` must be a contiguous %s %s tensor on %s" % (out_dtype, (B, O, H, W), inp.device))
     few2many = I in (3, 6) and O % 16 == 0
@@ -874,7 +884,7 @@ def conv3x3_thin_wrw(transposed, x, dy, out=None):
     Cb, Cs = big.shape[1], small.shape[1]
     L = _lib.lib()
     if Cs in (3, 6):
-        g = out if out is not None else torch.empty(wshape, dtype=torch.float32, device=x.device)
+        g = out if out is not None else _empty(wshape, dtype=torch.float32, device=x.device)
         nbytes = L.ipsr_conv3x3_thin_wrw_workspace_bytes(B, Cb, Cs, H, W)
         if nbytes == 0:
             raise NotImplementedError("ipsr_conv3x3_thin_wrw: Cb=%d Cs=%d %dx%d is not implemented" % (Cb, Cs, H, W))
@@ -919,7 +929,7 @@ def conv_thin_f2m_mfma(op, inp, weight, in_shape, Cout, k, stride, bias=None, re
     want_w = (Cout, Cin, k, k) if op == CONV_FWD else (Cin, Cout, k, k)
     if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
         raise RuntimeError("conv_thin_f2m_mfma op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
-    out = torch.empty((B, O, Ho, Wo), dtype=out_dtype, device=inp.device)
+    out = _empty((B, O, Ho, Wo), dtype=out_dtype, device=inp.device)
     _lib.check(_lib.lib().ipsr_conv_thin_f2m_mfma(inp.data_ptr(), weight.data_ptr(), _ptr(_f32(bias)) if bias is not None else None, int(bool(relu)),
                                                   out.data_ptr(), B, Cs, O, Ho, Wo, k, stride, so, si, flip, _io_code(in_bf, out_dtype), _stream()),
                "ipsr_conv_thin_f2m_mfma")
@@ -954,7 +964,7 @@ def conv_thin_wrw_mfma(transposed, x, dy, k, stride, out=None):
     nbytes = L.ipsr_conv_thin_wrw_mfma_workspace_bytes(B, Kb, Cs, Hb, Wb, k, stride)
     if nbytes == 0:
         raise NotImplementedError("ipsr_conv_thin_wrw_mfma: Kb=%d Cs=%d %dx%d k%d s%d is not implemented" % (Kb, Cs, Hb, Wb, k, stride))
-    g = out if out is not None else torch.empty((Kb, Cs, k, k), dtype=torch.float32, device=x.device)
+    g = out if out is not None else _empty((Kb, Cs, k, k), dtype=torch.float32, device=x.device)
     if tuple(g.shape) != (Kb, Cs, k, k) or g.dtype != torch.float32 or not g.is_contiguous():
         raise RuntimeError("conv_thin_wrw_mfma: `out` must be a contiguous fp32 %s tensor" % ((Kb, Cs, k, k),))
     ws = _workspace(nbytes, x.device)
@@ -984,7 +994,7 @@ def conv_smallmap(op, a, b, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, out=N
     if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a.device):
         raise RuntimeError("conv_smallmap: `out` must be a contiguous fp32 %s tensor on %s" % (tuple(want[2]), a.device))
     if out is None:
-        out = torch.empty(want[2], dtype=torch.float32, device=a.device)
+        out = _empty(want[2], dtype=torch.float32, device=a.device)
     L = _lib.lib()
     nbytes = L.ipsr_conv_smallmap_workspace_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil)
     if nbytes == 0:
@@ -1009,7 +1019,7 @@ def conv3x3_winograd_wrw(transposed, x, dy, Cout, out=None, math=None):
     shape = (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3)
     if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
         raise RuntimeError("conv3x3_winograd_wrw: `out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
-    dw = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=x.device)
     L = _lib.lib()
     ws = _workspace(L.ipsr_conv3x3_winograd_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device)
     _lib.check(L.ipsr_conv3x3_winograd_wrw_mp(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, MATH_CODE[math],
@@ -1029,7 +1039,7 @@ def innercos_loss(x, cuse, mask_f32, target, strength, one_launch=False):
     N = x.shape[2] * x.shape[3]
     if tuple(target.shape) != (B, cuse, x.shape[2], x.shape[3]) or mask.numel() != N:
         raise RuntimeError("InnerCos: target %s / mask %s do not match input %s" % (tuple(target.shape), tuple(mask.shape), tuple(x.shape)))
-    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    loss = _empty((), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     ws = _workspace(L.innercos_workspace_bytes(B, cuse, N), x.device)
     if one_launch:
@@ -1039,7 +1049,7 @@ def innercos_loss(x, cuse, mask_f32, target, strength, one_launch=False):
         key = (x.device.index, _stream())
         ticket = _IC_TICKETS.get(key)
         if ticket is None:
-            ticket = _IC_TICKETS[key] = torch.zeros(64, dtype=torch.int32, device=x.device)
+            ticket = _IC_TICKETS[key] = _zeros(64, dtype=torch.int32, device=x.device)
         _lib.check(L.innercos_loss_fused(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(), float(strength),
                                          loss.data_ptr(), ws.data_ptr(), ws.numel(), ticket.data_ptr(), _stream()), "innercos_loss_fused")
         return loss
@@ -1055,7 +1065,7 @@ def innercos_loss_backward(x, cuse, mask_f32, target, strength, grad_loss):
     gl = _req(grad_loss.reshape(1).to(torch.float32), torch.float32, "grad_loss")
     B, Cx = x.shape[0], x.shape[1]
     N = x.shape[2] * x.shape[3]
-    gx = torch.empty_like(x)
+    gx = _empty(x.shape, x.dtype, x.device)
     _lib.check(_lib.lib().innercos_loss_backward(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(),
                                                  float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
                "innercos_loss_backward")
