@@ -279,6 +279,9 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
     const FwdPlan p = plan_forward(B, C, h, w, M, patch, sz, corr_bf16);
     if (corr_bf16 && !corr_bf16_supported(p.K, p.ld))
         return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C*p*p %% 64 == 0 and N %% 128 == 0 for shift_sz = 1 (got %d, %d)", p.K, p.N);
+    // the layer's limits are refused here, before the first launch: a refused call leaves every output untouched
+    if (int rc = attention_limits(p.Cp, p.N, M, p.Mc)) return rc;
+    if (patch > 1 && corr_bf16) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: shift_sz > 1 runs the fp32 shifted-sum correlation only");
     if (ws_bytes < p.total) return fail(IPSR_ERR_WORKSPACE, "ipsr_forward: workspace %zu < %zu", ws_bytes, p.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfileScope scope(st, 1);
@@ -295,7 +298,6 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
     float* outs = out;
     AttnArgs a{};                      // every field defined (mcount = NULL, mpi_stride = 0: one shared mask)
     if (patch > 1) {
-        if (corr_bf16) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: shift_sz > 1 runs the fp32 shifted-sum correlation only");
         // window norms + patch-major raw windows straight from the feature; the correlation of p x p windows = sums of shifted
         // diagonals of the 1x1 correlation R = x^T ref (8x fewer flops at p = 3, nothing unfolded): corr_argmax.hip
         float* R = xn;                                              // WS_XN slot

@@ -792,18 +792,34 @@ __global__ void __launch_bounds__(256) recon_masked_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------
+// dynamic LDS of the stage kernel (the recurrence's step lists, or the prepare role's 4*N ints) and of attn_compress_kernel
+static size_t stage_lds_bytes(int N, int M)
+{
+    const size_t lds_rec = M > 0 ? (size_t)6 * (((M + 3) & ~3) + 3 * RING) * sizeof(int) : 0;
+    const size_t lds_prep = (size_t)4 * N * sizeof(int);
+    return lds_rec > lds_prep ? lds_rec : lds_prep;
+}
+static size_t compress_lds_bytes(int M, int Mc) { return ((size_t)4 * M + Mc + 1 + M) * sizeof(int); }
+
+// The limits of launch_attention, for the entry point to check BEFORE its first launch: a refused call writes no output.
+int attention_limits(int Cp, int N, int M, int Mc)
+{
+    if (stage_lds_bytes(N, M) > 150 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward: N=%d / M=%d too large for the stage kernel's LDS", N, M);
+    if (cdiv(Cp, 512) > 16) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward: patch length C*p*p=%d (padded to 8) > 8192 not supported", Cp);
+    if (M > 0 && compress_lds_bytes(M, Mc) > 150 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward: M=%d too large for attn_compress_kernel", M);
+    return IPSR_OK;
+}
+
 int launch_attention(const AttnArgs& a, hipStream_t st)
 {
     const int B = a.B, C = a.C, Cp = a.Cp, N = a.N, M = a.M, Mc = a.Mc;
     const size_t ints = 2 * ((size_t)N + 1) + (size_t)N + (size_t)M * (M + 1);     // ipsr_bwd_index_ints(N, M)
     int nbits = 1;
     while ((1 << nbits) < N) ++nbits;
+    if (int rc = attention_limits(Cp, N, M, Mc)) return rc;
     {
         const int nch = cdiv(Cp, 512);
-        const size_t lds_rec = M > 0 ? (size_t)6 * (((M + 3) & ~3) + 3 * RING) * sizeof(int) : 0;
-        const size_t lds_prep = (size_t)4 * N * sizeof(int);
-        const size_t lds = lds_rec > lds_prep ? lds_rec : lds_prep;
-        if (lds > 150 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward: N=%d / M=%d too large for the stage kernel's LDS", N, M);
+        const size_t lds = stage_lds_bytes(N, M);
         const int nrec = M > 0 ? B : 0;
         const int grid = nrec + B + cdiv(N, 32) * cdiv(C, 32) * B;
 #define LAUNCH_STAGE2(NCH, FULL)                                                                                     \
@@ -835,8 +851,7 @@ int launch_attention(const AttnArgs& a, hipStream_t st)
     }
     const bool need_index = a.bwd_index != nullptr;
     if (M > 0) {
-        const size_t lds_c = ((size_t)4 * M + Mc + 1 + M) * sizeof(int);
-        if (lds_c > 150 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward: M=%d too large for attn_compress_kernel", M);
+        const size_t lds_c = compress_lds_bytes(M, Mc);
         if (lds_c > 48 * 1024) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_compress_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_compress_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);

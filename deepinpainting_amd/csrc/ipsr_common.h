@@ -199,6 +199,7 @@ struct AttnArgs {
     int32_t* bwd_index;    // [B, ipsr_bwd_index_ints(N,M)], optional
 };
 int launch_attention(const AttnArgs& a, hipStream_t st);
+int attention_limits(int Cp, int N, int M, int Mc);      // IPSR_ERR_UNSUPPORTED past the layer's limits, else IPSR_OK
 
 int launch_backward(const float* g, const int32_t* mpi, int M, const float* attn, const int32_t* bwd_index,
                     float triple_w, int B, int C, int N, float* gin, hipStream_t st, int identity = 1);
