@@ -82,7 +82,8 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 struct FwdPlan {
     int N, Cp, Mc;
-    int K, ld;         // patch length C*p*p and the row stride of the unfolded operands (p > 1: N rounded up to 128)
+    int K, ld;         // patch length C*p*p and the row stride of the correlation operands: N, or for the bf16 correlation with
+                       // p > 1 (operands: the raw [C][h*w] features) h*w rounded up to 128
     size_t total;
 };
 
@@ -97,7 +98,8 @@ static FwdPlan plan_forward(int B, int C, int h, int w, int M, int patch, size_t
     FwdPlan p;
     p.K = C * patch * patch;
     p.N = (h - patch + 1) * (w - patch + 1);
-    p.ld = p.N;
+    const bool win_bf16 = patch > 1 && corr_bf16;
+    p.ld = win_bf16 ? (h * w + 127) & ~127 : p.N;
     p.Cp = (p.K + 7) & ~7;
     p.Mc = M > 0 ? (M + 31) & ~31 : 32;
     const size_t Mx = M > 0 ? M : 1;
@@ -105,10 +107,13 @@ static FwdPlan plan_forward(int B, int C, int h, int w, int M, int patch, size_t
     const size_t hw = (size_t)h * w;
     // patch > 1 (shifted-sum form): WS_XN = the 1x1 correlation matrix R [B][hw][hw]; WS_XU = the per-position norms n1 [B][hw];
     // WS_CORR = partials of the 1x1 correlation launch; WS_RU = partials of the window arg-max.  Nothing is unfolded but xT.
+    // patch > 1 with the bf16 correlation: R from the bf16 kernel, WS_CORR = its partials and the two packed [C/8][ld][8] bf16
+    // copies of the raw features.
     sz[WS_XN] = patch > 1 ? (size_t)B * hw * hw * 4 : (size_t)B * p.K * p.ld * 4;
     sz[WS_XT] = (size_t)B * p.N * p.Cp * 4;
     sz[WS_INV] = (size_t)B * p.N * 4;
-    if (patch > 1) sz[WS_CORR] = corr_argmax_ws_bytes(B, C, (int)hw);
+    if (win_bf16) sz[WS_CORR] = corr_argmax_bf16_ws_bytes(B, C, (int)hw, p.ld);
+    else if (patch > 1) sz[WS_CORR] = corr_argmax_ws_bytes(B, C, (int)hw);
     else sz[WS_CORR] = corr_bf16 ? corr_argmax_bf16_ws_bytes(B, p.K, p.N, p.ld) : corr_argmax_ws_bytes(B, p.K, p.N);
     sz[WS_XU] = patch > 1 ? (size_t)B * hw * 4 : 0;
     sz[WS_RU] = patch > 1 ? window_corr_ws_bytes(B, p.N) : 0;
@@ -133,7 +138,7 @@ using namespace ipsr;
 
 extern "C" {
 
-int ipsr_abi_version(void) { return 14; }
+int ipsr_abi_version(void) { return 15; }
 
 int ipsr_debug_set_option(int key, int value)
 {
@@ -277,11 +282,12 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
         return fail(IPSR_ERR_INVALID, "ipsr_forward: x/ref/out/attn_rows/ws must be 16-byte aligned");
     size_t sz[WS_COUNT];
     const FwdPlan p = plan_forward(B, C, h, w, M, patch, sz, corr_bf16);
-    if (corr_bf16 && !corr_bf16_supported(p.K, p.ld))
-        return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C*p*p %% 64 == 0 and N %% 128 == 0 for shift_sz = 1 (got %d, %d)", p.K, p.N);
     // the layer's limits are refused here, before the first launch: a refused call leaves every output untouched
+    if (corr_bf16 && patch > 1 && !corr_bf16_supported(C, p.ld))
+        return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C %% 64 == 0 for shift_sz > 1 (got C=%d)", C);
+    if (corr_bf16 && patch == 1 && !corr_bf16_supported(p.K, p.ld))
+        return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C %% 64 == 0 and N %% 128 == 0 for shift_sz = 1 (got %d, %d)", p.K, p.N);
     if (int rc = attention_limits(p.Cp, p.N, M, p.Mc)) return rc;
-    if (patch > 1 && corr_bf16) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: shift_sz > 1 runs the fp32 shifted-sum correlation only");
     if (ws_bytes < p.total) return fail(IPSR_ERR_WORKSPACE, "ipsr_forward: workspace %zu < %zu", ws_bytes, p.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfileScope scope(st, 1);
@@ -299,12 +305,17 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
     AttnArgs a{};                      // every field defined (mcount = NULL, mpi_stride = 0: one shared mask)
     if (patch > 1) {
         // window norms + patch-major raw windows straight from the feature; the correlation of p x p windows = sums of shifted
-        // diagonals of the 1x1 correlation R = x^T ref (8x fewer flops at p = 3, nothing unfolded): corr_argmax.hip
+        // diagonals of the 1x1 correlation R = x^T ref (8x fewer flops at p = 3, nothing unfolded): corr_argmax.hip.  With the
+        // bf16 correlation R comes from the bf16 matrix cores (raw features rounded); the stencil and everything after it is fp32.
         float* R = xn;                                              // WS_XN slot
         float* n1 = reinterpret_cast<float*>(slice[WS_XU]);
         if (int rc = launch_window_prepare(x, B, C, h, w, patch, n1, inv, xT, p.Cp, st)) return rc;
-        CorrPartials unused;
-        if (int rc = launch_corr_argmax(x, ref, B, C, h * w, nullptr, nullptr, R, slice[WS_CORR], sz[WS_CORR], st, &unused, 0)) return rc;
+        if (corr_bf16) {
+            if (int rc = launch_corr_R_bf16(x, ref, B, C, h * w, R, slice[WS_CORR], sz[WS_CORR], st)) return rc;
+        } else {
+            CorrPartials unused;
+            if (int rc = launch_corr_argmax(x, ref, B, C, h * w, nullptr, nullptr, R, slice[WS_CORR], sz[WS_CORR], st, &unused, 0)) return rc;
+        }
         if (int rc = launch_window_corr_argmax(R, inv, B, h, w, patch, slice[WS_RU], sz[WS_RU], st, &a.part)) return rc;
         outs = reinterpret_cast<float*>(slice[WS_OU]);
     } else {

@@ -405,16 +405,18 @@ constexpr int PF = 4;     // k-steps (16 channels each) of fragment loads in fli
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__global__ void __launch_bounds__(256) pack_bf16_k8_kernel(const float* __restrict__ src, int C, int ld, int C8, uint4* __restrict__ dst)
+// src rows have stride lds; columns n in [nsrc, ld) are packed as zeros (lds = nsrc = ld: a plain copy)
+__global__ void __launch_bounds__(256) pack_bf16_k8_kernel(const float* __restrict__ src, int C, int lds, int nsrc, int ld, int C8,
+                                                           uint4* __restrict__ dst)
 {
     // one thread per (channel group, position): 8 strided fp32 reads (coalesced across positions), one 16-byte store
     const int n = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y, b = blockIdx.z;
     if (n >= ld) return;
-    const float* s = src + ((size_t)b * C + (size_t)g * 8) * ld + n;
+    const float* s = src + ((size_t)b * C + (size_t)g * 8) * lds + n;
     unsigned short h[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float v = (g * 8 + e < C) ? s[(size_t)e * ld] : 0.0f;
+        const float v = (g * 8 + e < C && n < nsrc) ? s[(size_t)e * lds] : 0.0f;
         h[e] = __builtin_bit_cast(unsigned short, (__bf16)v);          // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
     }
     uint4 o;
@@ -423,10 +425,12 @@ __global__ void __launch_bounds__(256) pack_bf16_k8_kernel(const float* __restri
     dst[((size_t)b * C8 + g) * ld + n] = o;
 }
 
-template <bool RAGGED>
+// WRITE_S: also store every correlation S_out[b][k][q] (N x N; the 1x1 correlation R of the shift_sz > 1 path)
+template <bool RAGGED, bool WRITE_S>
 __global__ void __launch_bounds__(NTHREADS, 2)
 corr_argmax_bf16_kernel(const uint4* __restrict__ xnp, const uint4* __restrict__ refp, int C8, int N, int ld,
-                        int qtiles, int ksplit, int ktiles, int kt_per_wg, float* __restrict__ pval, int32_t* __restrict__ pidx)
+                        int qtiles, int ksplit, int ktiles, int kt_per_wg, float* __restrict__ S_out, float* __restrict__ pval,
+                        int32_t* __restrict__ pidx)
 {
     __shared__ float red_v[2 * 2 * 32];
     __shared__ int red_i[2 * 2 * 32];
@@ -483,6 +487,7 @@ corr_argmax_bf16_kernel(const uint4* __restrict__ xnp, const uint4* __restrict__
         }
 #pragma unroll
         for (int jn = 0; jn < 2; ++jn) {
+            const int q = q0 + wn * 64 + jn * 32 + r;
 #pragma unroll
             for (int im = 0; im < 2; ++im) {
 #pragma unroll
@@ -491,6 +496,7 @@ corr_argmax_bf16_kernel(const uint4* __restrict__ xnp, const uint4* __restrict__
                     const float v = acc[im][jn][e];
                     if (!RAGGED || k < N) {
                         if (takes_over(v, best[jn])) { best[jn] = v; bidx[jn] = k; }
+                        if (WRITE_S) { if (!RAGGED || q < N) S_out[((size_t)b * N + k) * N + q] = v; }
                     }
                 }
             }
@@ -722,13 +728,13 @@ int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int
     uint4* xp = cv.take<uint4>((size_t)B * C8 * ld);
     uint4* rp = cv.take<uint4>((size_t)B * C8 * ld);
     const dim3 pg(cdiv(ld, 256), C8, B);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(xn, C, ld, C8, xp);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, ld, C8, rp);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(xn, C, ld, ld, ld, C8, xp);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, ld, ld, ld, C8, rp);
     if (int rc = check_launch("pack_bf16_k8_kernel")) return rc;
     const int grid = B * qt * ks;
     profile_mark_start(st);
-    if (ld == N) corr_argmax_bf16_kernel<false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, pval, pidx);
-    else corr_argmax_bf16_kernel<true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, pval, pidx);
+    if (ld == N) corr_argmax_bf16_kernel<false, false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, nullptr, pval, pidx);
+    else corr_argmax_bf16_kernel<true, false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, nullptr, pval, pidx);
     profile_mark_stop(st);
     if (int rc = check_launch("corr_argmax_bf16_kernel")) return rc;
     if (partials) {
@@ -739,6 +745,39 @@ int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int
     }
     argmax_merge_kernel<<<cdiv(B * N, 256), 256, 0, st>>>(pval, pidx, B, N, ks, ind, vmax);
     return check_launch("argmax_merge_kernel");
+}
+
+// shift_sz > 1 on the bf16 kernel: the 1x1 correlation R = x^T ref [B][N][N] (N = h*w) of the shifted-sum form, on the RAW
+// features rounded to bf16 (products exact, fp32 accumulation), for launch_window_corr_argmax's fp32 stencil.  The window's
+// inverse norm is applied after the stencil as in the fp32 path; a scale leaves the relative rounding error of a product alone.
+// Operands packed with a row stride ld = N rounded up to 128 (zero columns past N); the arg-max partials it also produces
+// are not used.  (Contracting the unfolded, normalised windows instead, 2*N'^2*C*p^2 flop on the same kernel, measured slower
+// than the fp32 R + stencil at BASELINE config 4: DESIGN.md 5.4.)
+int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, float* R, void* ws, size_t ws_bytes, hipStream_t st)
+{
+    const int ld = cdiv(N, BM) * BM;
+    if (!corr_bf16_supported(C, ld))
+        return fail(IPSR_ERR_UNSUPPORTED, "bf16 window correlation: needs C %% %d == 0 (got %d)", 16 * PF, C);
+    int qt, kt, ks, kpw;
+    plan(B, N, &qt, &kt, &ks, &kpw);
+    if (ws_bytes < corr_argmax_bf16_ws_bytes(B, C, N, ld))
+        return fail(IPSR_ERR_WORKSPACE, "bf16 window correlation: workspace %zu < %zu", ws_bytes, corr_argmax_bf16_ws_bytes(B, C, N, ld));
+    Carver cv(ws, ws_bytes);
+    float* pval = cv.take<float>((size_t)B * ks * N);
+    int32_t* pidx = cv.take<int32_t>((size_t)B * ks * N);
+    const int C8 = C / 8;
+    uint4* xp = cv.take<uint4>((size_t)B * C8 * ld);
+    uint4* rp = cv.take<uint4>((size_t)B * C8 * ld);
+    const dim3 pg(cdiv(ld, 256), C8, B);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(x, C, N, N, ld, C8, xp);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, N, N, ld, C8, rp);
+    if (int rc = check_launch("pack_bf16_k8_kernel")) return rc;
+    const int grid = B * qt * ks;
+    profile_mark_start(st);
+    if (ld == N) corr_argmax_bf16_kernel<false, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, R, pval, pidx);
+    else corr_argmax_bf16_kernel<true, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, R, pval, pidx);
+    profile_mark_stop(st);
+    return check_launch("corr_argmax_bf16_kernel");
 }
 
 }  // namespace ipsr

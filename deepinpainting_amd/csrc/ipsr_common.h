@@ -168,6 +168,9 @@ bool corr_bf16_supported(int C, int ld);
 size_t corr_argmax_bf16_ws_bytes(int B, int C, int N, int ld = 0);
 int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int N, int32_t* ind, float* vmax,
                             void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials = nullptr, int ld = 0);
+// shift_sz > 1 on the bf16 kernel: the 1x1 correlation R [B][N][N] of the raw features x, ref [B][C][N] (operands rounded to
+// bf16), for launch_window_corr_argmax; workspace corr_argmax_bf16_ws_bytes(B, C, N, roundup(N, 128)), needs C % 64 == 0
+int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, float* R, void* ws, size_t ws_bytes, hipStream_t st);
 
 // conv_gemm.hip — implicit-GEMM convolutions on the fp32 matrix cores (see the file header)
 size_t conv_gemm_ws_bytes(int transposed, int B, int Cred, int M, int Hin, int Win, int Hout, int Wout, int k, int stride, int pad, int dil);

@@ -98,7 +98,7 @@ class IPSR(BaseModel):
             opt.input_nc, opt.output_nc, opt.ngf, opt.which_model_netP, opt, self.mask_global, opt.norm,
             opt.use_dropout, opt.init_type, self.gpu_ids, opt.init_gain)
         # BASELINE config 5 names "bf16 MFMA for patch-corr + convs": with amp_bf16 the layer's correlation runs on the bf16
-        # MFMA kernel too (opt.bf16_corr = False keeps it fp32); every other part of the layer stays fp32
+        # MFMA kernel too, for every shift_sz (opt.bf16_corr = False keeps it fp32); every other part of the layer stays fp32
         self.CSA_model[0].corr_bf16 = self.amp_bf16 and bool(getattr(opt, 'bf16_corr', True)) and self.device.type == 'cuda'
         if self.isTrain:
             use_sigmoid = opt.gan_type == 'vanilla'

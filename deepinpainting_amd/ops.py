@@ -138,8 +138,9 @@ _precision = threading.local()
 @contextlib.contextmanager
 def corr_precision(corr):
     """`with ops.corr_precision("bf16"):` — layer forwards issued by this thread inside the block run their correlation on
-    the bf16 MFMA kernel (BASELINE config 5).  The autograd surface IPSRFunction.apply has the reference's fixed 12
-    arguments, so the choice travels this way (IPSR_model sets it from its `corr_bf16` attribute)."""
+    the bf16 MFMA kernel (BASELINE config 5), for every shift_sz (p > 1: the 1x1 correlation under the fp32 window sums).
+    The autograd surface IPSRFunction.apply has the reference's fixed 12 arguments, so the choice travels this way
+    (IPSR_model sets it from its `corr_bf16` attribute)."""
     if corr not in ("fp32", "bf16"):
         raise ValueError("corr must be 'fp32' or 'bf16'")
     prev = getattr(_precision, "corr", "fp32")
@@ -155,8 +156,8 @@ def forward(x, ref, mask_point_idx_i32, patch=1, stride=1, want_attn=False, want
     want_attn:  also materialise the dense attention rows [B,M,N] (the reference's `in_attention`; tests and
                 inspection only — the layer itself works on the compressed form);
     want_index: build the sparse trunc(kbar) the backward needs (skip under no_grad);
-    corr:       "fp32" (the reference's arithmetic, default) or "bf16" (opt-in bf16-MFMA correlation); None = what the
-                enclosing `corr_precision` block says;
+    corr:       "fp32" (the reference's arithmetic, default) or "bf16" (opt-in bf16-MFMA correlation; C % 64 == 0, and for
+                patch == 1 N % 128 == 0, else NotImplementedError); None = what the enclosing `corr_precision` block says;
     counts:     [B] int32 DEVICE tensor = masked positions per sample (ipsr_forward_masks).  mask_point_idx is then [Mcap]
                 (one index shared by the batch, e.g. straight from `index_prep`, no host sync) or [B,Mcap] (one row per
                 sample: per-sample masks); entries past counts[b] are ignored.  Everything sized by M (attn_rows, bwd_index)

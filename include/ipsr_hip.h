@@ -13,7 +13,8 @@
  *   - all tensors are dense, row-major, NCHW:  x[b][c][y][x]  ->  ((b*C + c)*h + y)*w + x.
  *     N = number of patches = nH*nW with nH = (h-patch)/stride+1 (reference util/util.py:95-98).
  *     patch (the reference's shift_sz) >= 1 with stride == 1 is implemented (the reference itself raises for
- *     shift_sz != 1 at models/IPSRFunction.py:134, see ipsr_forward below); stride != 1 returns IPSR_ERR_UNSUPPORTED.
+ *     shift_sz != 1 at models/IPSRFunction.py:134, see ipsr_forward below), with the fp32 or the bf16 correlation;
+ *     stride != 1 returns IPSR_ERR_UNSUPPORTED.
  *   - `stream` is a hipStream_t passed as void*; NULL = the default stream.  No entry point
  *     allocates, frees or synchronises: the caller owns every buffer incl. the workspace whose size
  *     the matching *_workspace_bytes() query returns.  All entry points are re-entrant per stream.
@@ -38,7 +39,8 @@ extern "C" {
 #define IPSR_ERR_WORKSPACE     -3   /* workspace too small                                        */
 #define IPSR_ERR_LAUNCH        -4   /* hipLaunchKernel / hipMemsetAsync reported an error         */
 
-/* ABI version: bumped whenever a signature changes. */
+/* ABI version: bumped whenever a signature changes or an entry starts accepting what it refused (15: the bf16 correlation
+ * entries accept shift_sz > 1). */
 int ipsr_abi_version(void);
 /* Thread-local message of the last failing call ("" if none). */
 const char* ipsr_last_error(void);
@@ -128,8 +130,13 @@ int ipsr_forward_masks(const float* x, const float* ref, const int32_t* mask_poi
  * Everything else — normalisation, arg-max rule, recurrence, reconstruction, backward index — is the fp32 path above.
  * Not the reference's arithmetic: an arg-max moves wherever the two best patches are closer than bf16 rounding; the
  * agreement rate with ipsr_forward is measured by bench.py and tests/test_gpu_parity.py.  Same arguments as
- * ipsr_forward / ipsr_corr_argmax (fp32 tensors in and out; the bf16 copies live in the workspace).  Shapes: C*patch^2
- * a multiple of 64 and, for patch == 1, N a multiple of 128; anything else -> IPSR_ERR_UNSUPPORTED (no silent fp32 run). */
+ * ipsr_forward / ipsr_corr_argmax (fp32 tensors in and out; the bf16 copies live in the workspace).
+ *   patch == 1: the normalised patches and ref are rounded; C a multiple of 64 and N a multiple of 128.
+ *   patch > 1:  the 1x1 correlation R = x^T ref of the shifted-sum form runs on the bf16 matrix cores on the RAW features
+ *               rounded to bf16; the p x p window sums, the window norms and the arg-max stay fp32 (a window's correlation
+ *               differs from the fp32 one by at most 2^-8 of sum |xn * ref| plus fp32 accumulation).  C a multiple of 64;
+ *               h*w and N' are free (tests/test_gpu_bf16_patch_corr.py).
+ * Anything else -> IPSR_ERR_UNSUPPORTED before the first launch (no silent fp32 run, no output written). */
 size_t ipsr_forward_bf16corr_workspace_bytes(int B, int C, int h, int w, int M, int patch, int stride);
 int ipsr_forward_bf16corr(const float* x, const float* ref, const int32_t* mask_point_idx, int M,
                           int B, int C, int h, int w, int patch, int stride,
