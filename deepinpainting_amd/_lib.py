@@ -132,6 +132,10 @@ def lib():
         raise IpsrLibraryError(
             "libipsr_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C deepinpainting_amd/csrc`.  The IPSR layer has no CPU/eager fallback." % LIB_PATH)
+    # torch first: a ROCm wheel of torch carries its own HIP runtime, and libipsr_hip.so must bind to THAT one.  Loaded before torch
+    # it pulls in the system's libamdhip64 instead; the process then holds two runtimes and every launch of this library fails with
+    # "no ROCm-capable device is detected" (`python __graft_entry__.py smoke`, where build() loads the library before anything else)
+    import torch  # noqa: F401
     h = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(h, name)            # AttributeError here = the .so does not match include/ipsr_hip.h

@@ -1,0 +1,433 @@
+"""The launch planners of csrc/conv_bf16.hip restated in Python: which kernel instantiation and LDS plan a shape reaches.
+
+A plain module (like golden_cases.py, guarded.py).  tests/test_bf16_conv_plan.py ties it to the built library through the four
+`*_workspace_bytes` queries (kt, ktiles, nstage and nsplit all show in the byte count), tests/test_gpu_bf16_conv_variants.py
+asserts through it the variant every case reaches before it compares numbers.  Each function names the lines it mirrors; integer
+arithmetic is C's (all operands non-negative, so `//` is the same division).
+
+A plan is a dict, `None` = the shape is refused (IPSR_ERR_UNSUPPORTED).  Forward / input-gradient plans:
+    mode "S1" | "F2C" | "C2F", kt (128 | 64), ptile (256 | 512), R (lane-grid rows per tile), tiles_per_img, ptiles, ktiles, nphase,
+    nsub, nstage, ntap, raw1, lds (bytes of dynamic LDS), nblocks (16-channel blocks of the reduction), nsplit (runs), bps (blocks per
+    run), last_bps (blocks of the last run), uneven (last run shorter), wgs (workgroups before the cut), p512 ("taken", or why a
+    <= 64-channel layer did not get the 512-pixel tile: "rows" | "lds"; None above 64 channels), Wl (lane-grid width), Hout, Wout,
+    B, C, K.  With `why=True` a planner returns (plan, message fragment of the refusal).
+Weight-gradient plans: RS, groups (stages per image), spw0 (the fill-the-chip value before clamping), spw (stages_per_wg), lowered
+    (the `while (groups % spw)` loop ran), nsplit (slabs), ktiles, ctiles.
+"""
+
+CB_K, CB_P, CB_C, CB_THREADS = 128, 256, 16, 512          # conv_bf16.hip:40
+CB_LDS_MAX = 160 * 1024                                   # :45
+WB_K, WB_C, WB_THREADS, WB_PX = 128, 64, 512, 128         # :595
+WB_X_BYTES = 96 * 1024                                    # :597
+W2_K, W2_C, W2_PX = 128, 32, 64                           # :820
+
+
+def cb_tr_max(ptile):                                     # :43
+    return 6 if ptile == 256 else 10
+
+
+def cb_xj(ptile):                                         # :44
+    return 3 if ptile == 256 else 5
+
+
+def align_up(x, a):
+    return (x + a - 1) // a * a
+
+
+def cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def cb_lane_grid(Hl, Wl, ptile):
+    """:353-362 -> (R, None) or (None, message fragment)."""
+    if Wl not in (16, 32, 64, 128, 256):
+        return None, "grid width %d" % Wl
+    R = ptile // Wl
+    if Hl % R != 0:
+        return None, "%d rows are not a multiple of the %d rows of a tile" % (Hl, R)
+    return R, None
+
+
+def cb_finish(g):
+    """:364-390: k tile, the reduction cut, the LDS plan.  g holds B, C, K, Hl, R, Win, NR, PW, nsub, nphase, ntap, ptile."""
+    g["NPOS"] = g["NR"] * g["PW"]
+    g["kt"] = 64 if g["K"] <= 64 else CB_K                                               # :367
+    g["ktiles"] = cdiv(g["K"], g["kt"])
+    g["tiles_per_img"] = g["Hl"] // g["R"]
+    g["ptiles"] = g["B"] * g["tiles_per_img"]                                            # :369
+    g["nstage"] = (g["C"] // CB_C) * g["nsub"]
+    wgs, nblocks = g["ktiles"] * g["nphase"] * g["ptiles"], g["C"] // CB_C               # :374
+    ns = 1
+    if wgs < 128 and nblocks >= 8:                                                       # :376
+        ns = min(min(4, nblocks // 4), cdiv(256, wgs))
+    bps = cdiv(nblocks, max(ns, 1))                                                      # :377
+    g["nsplit"] = cdiv(nblocks, bps)                                                     # :378
+    g["sps"] = bps * g["nsub"]
+    g["wgs"], g["nblocks"], g["bps"] = wgs, nblocks, bps
+    g["last_bps"] = nblocks - (g["nsplit"] - 1) * bps
+    g["uneven"] = g["last_bps"] != bps
+    planes = g["nsub"]                                                                   # :381
+    g["a_bytes"] = g["ntap"] * 2 * g["kt"] * 16
+    g["t_bytes"] = align_up(planes * 2 * g["NPOS"] * 16, 256)
+    g["raw_bytes"] = align_up(CB_C * g["NR"] * g["Win"] * 2, 1024)
+    g["raw1"] = 2 * (g["a_bytes"] + g["t_bytes"] + g["raw_bytes"]) > CB_LDS_MAX          # :385
+    g["lds"] = 2 * (g["a_bytes"] + g["t_bytes"]) + (1 if g["raw1"] else 2) * g["raw_bytes"]
+    if g["lds"] > CB_LDS_MAX or 4 * g["NR"] * (g["Win"] // 16) > 32 * cb_tr_max(g["ptile"]) or \
+            CB_C * g["NR"] * (g["Win"] // 8) > cb_xj(g["ptile"]) * CB_THREADS:           # :386-387
+        return None, "a tile of %d rows x %d does not fit the LDS plan" % (g["NR"], g["Win"])
+    return g, None
+
+
+def cb_geometry_p(B, C, K, H, W, ptile):
+    """:393-403, k3 s1 p1 at one tile size."""
+    if C % CB_C != 0:
+        return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
+    R, msg = cb_lane_grid(H, W, ptile)
+    if R is None:
+        return None, msg
+    g = dict(mode="S1", B=B, C=C, K=K, Hl=H, Wl=W, R=R, ptile=ptile, Hin=H, Win=W, Hout=H, Wout=W, NR=R + 2, PW=W + 2, nsub=1, nphase=1, ntap=9)
+    return cb_finish(g)
+
+
+def _two_tiles(K, geometry_p):
+    """:406-410 / :414-418: <= 64 produced channels try the 512-pixel tile first; any refusal falls back to 256, silently."""
+    p512 = None
+    if K <= 64:
+        g, msg = geometry_p(2 * CB_P)
+        if g is not None:
+            g["p512"] = "taken"
+            return g, None
+        p512 = "rows" if "rows" in msg else ("lds" if "LDS" in msg else "other")
+    g, msg = geometry_p(CB_P)
+    if g is not None:
+        g["p512"] = p512
+    return g, msg
+
+
+def cb_geometry(B, C, K, H, W, why=False):
+    """:406-410: k3 s1 p1, C reduction channels -> K produced."""
+    g, msg = _two_tiles(K, lambda p: cb_geometry_p(B, C, K, H, W, p))
+    return (g, msg) if why else g
+
+
+def cb_geometry_s2_p(form, B, C, K, nh, nw, ptile):
+    """:420-453, k4 s2 p1 at one tile size.  form 0: fine -> coarse (C = Cf, K = Kc); 1: coarse -> fine (C = Kc, K = Cf)."""
+    if C % CB_C != 0:
+        return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
+    R, msg = cb_lane_grid(nh, nw, ptile)
+    if R is None:
+        return None, msg
+    g = dict(B=B, C=C, K=K, Hl=nh, Wl=nw, R=R, ptile=ptile, ntap=8)
+    if form == 0:
+        g.update(mode="F2C", Hin=2 * nh, Win=2 * nw, Hout=nh, Wout=nw, NR=R + 1, PW=nw + 1, nsub=2, nphase=1)
+    else:
+        g.update(mode="C2F", Hin=nh, Win=nw, Hout=2 * nh, Wout=2 * nw, NR=R + 2, PW=nw + 2, nsub=1, nphase=2)
+    return cb_finish(g)
+
+
+def cb_geometry_s2(form, B, C, K, nh, nw, why=False):
+    """:414-418."""
+    g, msg = _two_tiles(K, lambda p: cb_geometry_s2_p(form, B, C, K, nh, nw, p))
+    return (g, msg) if why else g
+
+
+def cb_partial_bytes(g):                                  # :456
+    return align_up(g["nsplit"] * g["B"] * g["K"] * g["Hout"] * g["Wout"] * 4, 256) if g["nsplit"] > 1 else 0
+
+
+def cb_ws_bytes(g):
+    """:472-484: zero page + packed weights + fp32 partials of a cut reduction; 0 for a refused shape."""
+    if g is None:
+        return 0
+    return 256 + g["ktiles"] * g["nphase"] * g["nstage"] * g["ntap"] * 2 * g["kt"] * 16 + cb_partial_bytes(g)
+
+
+def _spw(tiles, B, groups):
+    """:771-777 / :998-1004: one round of one workgroup per CU, lowered until it divides the stages of an image."""
+    spw0 = (tiles * B * groups + 255) // 256
+    spw = min(max(spw0, 1), groups)
+    lowered = groups % spw != 0
+    while groups % spw:
+        spw -= 1
+    return spw0, spw, lowered
+
+
+def wb_geometry(B, Ka, Cb, H, W, why=False):
+    """:758-779: k3 weight gradient dW[Ka][Cb][3][3]."""
+    def out(g, msg=None):
+        return (g, msg) if why else g
+    if W not in (16, 32, 64, 128):
+        return out(None, "image width %d" % W)
+    RS = WB_PX // W
+    if H % RS != 0:
+        return out(None, "%d rows are not a multiple of %d" % (H, RS))
+    NSLOT, pitch = 2 * RS + 2, W // 8 + 3
+    ktiles, ctiles = cdiv(Ka, WB_K), cdiv(Cb, WB_C)
+    if NSLOT * WB_C * pitch * 16 > WB_X_BYTES or RS * WB_C * pitch > 5 * WB_THREADS:     # :767 (never true for the four widths)
+        return out(None, "the row ring")
+    groups = H // RS
+    spw0, spw, lowered = _spw(ktiles * ctiles, B, groups)
+    return out(dict(B=B, Ka=Ka, Cb=Cb, H=H, W=W, RS=RS, groups=groups, spw0=spw0, spw=spw, lowered=lowered, nsplit=B * (groups // spw),
+                    ktiles=ktiles, ctiles=ctiles))
+
+
+def wb_ws_bytes(g):                                       # :781-786
+    return 0 if g is None else 256 + g["nsplit"] * 9 * g["ktiles"] * WB_K * g["ctiles"] * WB_C * 4
+
+
+def w2_geometry(B, Kc, Cf, nh, nw, why=False):
+    """:988-1006: k4 s2 p1 weight gradient dW[Kc][Cf][4][4]."""
+    def out(g, msg=None):
+        return (g, msg) if why else g
+    if nw not in (16, 32, 64):
+        return out(None, "coarse width %d" % nw)
+    RS = W2_PX // nw
+    if nh % RS != 0:
+        return out(None, "%d coarse rows are not a multiple of %d" % (nh, RS))
+    pitch = 2 * nw // 8 + 3
+    ktiles, ctiles = cdiv(Kc, W2_K), cdiv(Cf, W2_C)
+    if (RS + 1) * 2 * W2_C * pitch > 5 * 512:                                            # :997 (never true for the three widths)
+        return out(None, "row ring")
+    groups = nh // RS
+    spw0, spw, lowered = _spw(ktiles * ctiles, B, groups)
+    return out(dict(B=B, Kc=Kc, Cf=Cf, nh=nh, nw=nw, RS=RS, groups=groups, spw0=spw0, spw=spw, lowered=lowered, nsplit=B * (groups // spw),
+                    ktiles=ktiles, ctiles=ctiles))
+
+
+def w2_ws_bytes(g):                                       # :1008-1013
+    return 0 if g is None else 256 + g["nsplit"] * 16 * g["ktiles"] * W2_K * g["ctiles"] * W2_C * 4
+
+
+# ---- the C entries' argument orders (conv_bf16.hip:1044-1049, :1074-1078, :1092-1096, :1108-1112) ------------------------------------
+def k3_plan(op, B, Cin, H, W, Cout, why=False):
+    """ipsr_conv3x3_bf16: op 0 Conv2d forward, 1 its input gradient, 2 ConvTranspose2d forward, 3 its input gradient."""
+    fwd = op in (0, 2)
+    return cb_geometry(B, Cin if fwd else Cout, Cout if fwd else Cin, H, W, why)
+
+
+def s2_plan(mode, B, Kc, Cf, nh, nw, why=False):
+    """ipsr_conv4x4s2_bf16: mode 0 fine -> coarse, 1 coarse -> fine."""
+    return cb_geometry_s2(mode, B, Cf if mode == 0 else Kc, Kc if mode == 0 else Cf, nh, nw, why)
+
+
+def k3_wrw_plan(transposed, B, Cin, H, W, Cout, why=False):
+    return wb_geometry(B, Cin, Cout, H, W, why) if transposed else wb_geometry(B, Cout, Cin, H, W, why)
+
+
+def s2_wrw_plan(B, Kc, Cf, nh, nw, why=False):
+    return w2_geometry(B, Kc, Cf, nh, nw, why)
+
+
+def k3_ws(op, B, Cin, H, W, Cout):
+    return cb_ws_bytes(k3_plan(op, B, Cin, H, W, Cout))
+
+
+def s2_ws(mode, B, Kc, Cf, nh, nw):
+    return cb_ws_bytes(s2_plan(mode, B, Kc, Cf, nh, nw))
+
+
+def k3_wrw_ws(transposed, B, Cin, H, W, Cout):
+    return wb_ws_bytes(k3_wrw_plan(transposed, B, Cin, H, W, Cout))
+
+
+def s2_wrw_ws(B, Kc, Cf, nh, nw):
+    return w2_ws_bytes(s2_wrw_plan(B, Kc, Cf, nh, nw))
+
+
+# ---- the GPU cases and the plans they must reach --------------------------------------------------------------------------------------
+# A requirement is a dict of plan fields that must match exactly; REFUSED = the planner must refuse.  Passes: "fwd" / "dx" (forward,
+# input gradient) and "dw".  k3: forward reduces Cin, the input gradient reduces Cout (ops 0 / 1, transposed: 2 / 3).
+REFUSED = "refused"
+
+# id: ((tr, Cin, H, W, Cout, B), {pass: requirement})
+K3_CASES = {
+    "k3_c64_24x32_k160_b3": ((False, 64, 24, 32, 160, 3), dict(
+        fwd=dict(kt=128, ptile=256, tiles_per_img=3, raw1=False, nsplit=1),
+        dx=dict(kt=64, ptile=256, p512="rows", tiles_per_img=3, nsplit=2, uneven=False),
+        dw=dict(groups=6, lowered=False, nsplit=18))),
+    "k3_c48_96x16_k32_b2": ((False, 48, 96, 16, 32, 2), dict(
+        fwd=dict(kt=64, ptile=512, Wl=16, tiles_per_img=3, raw1=False, nsplit=1),
+        dx=dict(kt=64, ptile=512, Wl=16, tiles_per_img=3, nsplit=1),
+        dw=dict(groups=12, nsplit=24))),
+    "k3T_c32_48x32_k64_b1": ((True, 32, 48, 32, 64, 1), dict(
+        fwd=dict(kt=64, ptile=512, Wl=32, tiles_per_img=3, nsplit=1),
+        dx=dict(kt=64, ptile=512, Wl=32, tiles_per_img=3, nsplit=1),
+        dw=dict(groups=12, nsplit=12))),
+    "k3_c32_6x256_k144_b2": ((False, 32, 6, 256, 144, 2), dict(
+        fwd=dict(kt=128, ptile=256, Wl=256, R=1, raw1=True, tiles_per_img=6, nsplit=1),
+        dx=dict(kt=64, ptile=512, Wl=256, R=2, raw1=True, tiles_per_img=3, nsplit=2, bps=5, last_bps=4, uneven=True),
+        dw=REFUSED)),
+    "k3_c256_16x16_k64_b1": ((False, 256, 16, 16, 64, 1), dict(
+        fwd=dict(kt=64, ptile=256, p512="rows", nsplit=4, uneven=False),
+        dx=dict(kt=128, nsplit=1),
+        dw=dict(nsplit=2))),
+    "k3T_c208_32x16_k48_b1": ((True, 208, 32, 16, 48, 1), dict(
+        fwd=dict(kt=64, ptile=512, nsplit=3, bps=5, last_bps=3, uneven=True),
+        dx=dict(kt=128),
+        dw=dict(nsplit=4))),
+    "k3_c64_12x64_k128_b2": ((False, 64, 12, 64, 128, 2), dict(
+        fwd=dict(kt=128, Wl=64, tiles_per_img=3),
+        dx=dict(kt=64, ptile=256, p512="rows", tiles_per_img=3),
+        dw=dict(groups=6))),
+    "k3_c32_10x128_k80_b1": ((False, 32, 10, 128, 80, 1), dict(
+        fwd=dict(kt=128, Wl=128, tiles_per_img=5),
+        dx=dict(kt=64, ptile=256, p512="rows", tiles_per_img=5),
+        dw=dict(groups=10))),
+}
+
+# weight gradient only: id: ((tr, Cin, H, W, Cout, B), requirement) — Conv2d: Ka = Cout, Cb = Cin
+K3_WRW_CASES = {
+    "k3w_ka512_cb256_48x16_b9": ((False, 256, 48, 16, 512, 9), dict(groups=6, spw0=4, spw=3, lowered=True, nsplit=18)),
+    "k3w_ka1024_cb1088_16x16_b1": ((False, 1088, 16, 16, 1024, 1), dict(groups=2, spw=2, nsplit=1)),
+}
+
+# id: ((Kc, Cf, nh, nw, B), {pass: requirement}); "f2c" reduces Cf and produces Kc, "c2f" reduces Kc and produces Cf
+S2_CASES = {
+    "s2_64_32_32x16_b2": ((64, 32, 32, 16, 2), dict(
+        f2c=dict(kt=64, ptile=512, raw1=True, Wl=16), c2f=dict(kt=64, ptile=512, raw1=False), dw=dict(nsplit=16))),
+    "s2_48_16_4x128_b1": ((48, 16, 4, 128, 1), dict(
+        f2c=dict(kt=64, ptile=512, raw1=True, Wl=128, lds=156672), c2f=dict(kt=64, ptile=512, Wl=128), dw=REFUSED)),
+    "s2_128_64_6x128_b1": ((128, 64, 6, 128, 1), dict(
+        f2c=dict(kt=128, ptile=256, raw1=True, Wl=128, lds=139776, tiles_per_img=3), c2f=dict(kt=64, ptile=256, p512="rows", nsplit=2), dw=REFUSED)),
+    "s2_32_80_4x128_b1": ((32, 80, 4, 128, 1), dict(
+        f2c=dict(kt=64, ptile=512, raw1=True, Wl=128), c2f=dict(kt=128, ptile=256, Wl=128), dw=REFUSED)),
+    "s2_16_16_2x256_b1": ((16, 16, 2, 256, 1), dict(
+        f2c=REFUSED, c2f=dict(kt=64, ptile=512, raw1=True, Wl=256), dw=REFUSED)),
+    "s2_128_144_16x16_b1": ((128, 144, 16, 16, 1), dict(
+        f2c=dict(kt=128, nsplit=2, bps=5, last_bps=4, uneven=True, nsub=2), c2f=dict(kt=128, nsplit=2, uneven=False), dw=dict(ctiles=5))),
+    "s2_64_208_16x16_b1": ((64, 208, 16, 16, 1), dict(
+        f2c=dict(kt=64, nsplit=3, bps=5, last_bps=3, uneven=True), c2f=dict(kt=128, nsplit=1), dw=dict())),
+    "s2_208_64_16x16_b1": ((208, 64, 16, 16, 1), dict(
+        f2c=dict(kt=128, nsplit=1), c2f=dict(kt=64, nsplit=3, bps=5, last_bps=3, uneven=True), dw=dict())),
+    "s2_96_48_24x32_b2": ((96, 48, 24, 32, 2), dict(
+        f2c=dict(tiles_per_img=3), c2f=dict(tiles_per_img=3, nphase=2), dw=dict(groups=12))),
+    # added to the issue's list: the 512-pixel fine -> coarse tile (always `raw1`) at the two widths its cases leave out
+    "s2_48_32_48x32_b1": ((48, 32, 48, 32, 1), dict(
+        f2c=dict(kt=64, ptile=512, raw1=True, Wl=32, tiles_per_img=3), c2f=dict(kt=64, ptile=512, Wl=32, tiles_per_img=3), dw=dict(groups=24))),
+    "s2_16_16_24x64_b2": ((16, 16, 24, 64, 2), dict(
+        f2c=dict(kt=64, ptile=512, raw1=True, Wl=64, tiles_per_img=3), c2f=dict(kt=64, ptile=512, Wl=64, tiles_per_img=3), dw=dict(groups=24))),
+    # ... and `raw1` coarse -> fine over MORE than one stage (s2_16_16_2x256_b1 reduces 16 channels: its in-loop transposition never runs)
+    "s2_48_16_4x256_b2": ((48, 16, 4, 256, 2), dict(
+        f2c=REFUSED, c2f=dict(kt=64, ptile=512, raw1=True, Wl=256, nstage=3, tiles_per_img=2, nsplit=1), dw=REFUSED)),
+}
+
+S2_WRW_CASES = {
+    "s2w_512_512_24x32_b5": ((512, 512, 24, 32, 5), dict(groups=12, spw=12, nsplit=5)),
+    "s2w_512_1056_8x16_b1": ((512, 1056, 8, 16, 1), dict(groups=2, spw=2, nsplit=1)),
+}
+
+
+def case_plans(cid):
+    """-> {pass: plan or None} of a case of the four tables above."""
+    if cid in K3_CASES:
+        (tr, Cin, H, W, Cout, B), _ = K3_CASES[cid]
+        return dict(fwd=k3_plan(2 if tr else 0, B, Cin, H, W, Cout), dx=k3_plan(3 if tr else 1, B, Cin, H, W, Cout),
+                    dw=k3_wrw_plan(tr, B, Cin, H, W, Cout))
+    if cid in K3_WRW_CASES:
+        (tr, Cin, H, W, Cout, B), _ = K3_WRW_CASES[cid]
+        return dict(dw=k3_wrw_plan(tr, B, Cin, H, W, Cout))
+    if cid in S2_CASES:
+        (Kc, Cf, nh, nw, B), _ = S2_CASES[cid]
+        return dict(f2c=s2_plan(0, B, Kc, Cf, nh, nw), c2f=s2_plan(1, B, Kc, Cf, nh, nw), dw=s2_wrw_plan(B, Kc, Cf, nh, nw))
+    (Kc, Cf, nh, nw, B), _ = S2_WRW_CASES[cid]
+    return dict(dw=s2_wrw_plan(B, Kc, Cf, nh, nw))
+
+
+def case_requirements(cid):
+    for table in (K3_CASES, S2_CASES):
+        if cid in table:
+            return table[cid][1]
+    for table in (K3_WRW_CASES, S2_WRW_CASES):
+        if cid in table:
+            return dict(dw=table[cid][1])
+    raise KeyError(cid)
+
+
+def check_case(cid):
+    """Assert that every pass of a case reaches the plan written beside it -> {pass: plan or None}."""
+    plans = case_plans(cid)
+    for name, want in case_requirements(cid).items():
+        got = plans[name]
+        if want == REFUSED:
+            assert got is None, "%s/%s: should be refused, got %s" % (cid, name, got)
+            continue
+        assert got is not None, "%s/%s: refused" % (cid, name)
+        miss = {k: (got.get(k), v) for k, v in want.items() if got.get(k) != v}
+        assert not miss, "%s/%s reaches another variant: (got, wanted) %s" % (cid, name, miss)
+    return plans
+
+
+def same_cut(p, q):
+    """Two forward / input-gradient plans (a batch and a batch of one) add their channel blocks in the same order."""
+    return (p["nsplit"], p["bps"], p["kt"], p["ptile"]) == (q["nsplit"], q["bps"], q["kt"], q["ptile"])
+
+
+# ---- the variant table: (variant, selecting lines, predicate on a plan, ((case id, pass), ...)) ------------------------------------------
+def _multi(p):
+    return p["tiles_per_img"] > 1 and p["tiles_per_img"] & (p["tiles_per_img"] - 1) != 0
+
+
+VARIANTS = (
+    ("S1 KT128 P256, 3 tiles per image (W 32)", ":134, :369", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["tiles_per_img"] == 3 and p["Wl"] == 32,
+     (("k3_c64_24x32_k160_b3", "fwd"),)),
+    ("S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128", ":134, :369", lambda p: p["mode"] == "S1" and p["kt"] == 128 and _multi(p) and p["Wl"] in (64, 128),
+     (("k3_c64_12x64_k128_b2", "fwd"), ("k3_c32_10x128_k80_b1", "fwd"))),
+    ("S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image", ":406-410, :385", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["Wl"] == 256 and p["R"] == 1 and p["raw1"] and p["tiles_per_img"] == 6,
+     (("k3_c32_6x256_k144_b2", "fwd"),)),
+    ("S1 KT64 P512 at W 16, 3 tiles per image", ":408", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 16 and p["tiles_per_img"] == 3,
+     (("k3_c48_96x16_k32_b2", "fwd"), ("k3_c48_96x16_k32_b2", "dx"))),
+    ("S1 KT64 P512 at W 32, 3 tiles per image", ":408", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+     (("k3T_c32_48x32_k64_b1", "fwd"), ("k3T_c32_48x32_k64_b1", "dx"))),
+    ("S1 KT64, P512 refused by the rows -> P256", ":408, :358", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["p512"] == "rows",
+     (("k3_c64_24x32_k160_b3", "dx"), ("k3_c64_12x64_k128_b2", "dx"), ("k3_c32_10x128_k80_b1", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
+    ("S1 KT64 P256, reduction cut in 2 / in 4", ":373-380", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] in (2, 4),
+     (("k3_c64_24x32_k160_b3", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
+    ("S1 KT64 P512, cut in 3 uneven (5 + 5 + 3 blocks)", ":373-380", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and (p["nsplit"], p["bps"], p["last_bps"]) == (3, 5, 3),
+     (("k3T_c208_32x16_k48_b1", "fwd"),)),
+    ("S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)", ":373-380, :385", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and (p["nsplit"], p["bps"], p["last_bps"]) == (2, 5, 4),
+     (("k3_c32_6x256_k144_b2", "dx"),)),
+    ("F2C KT64 P512 raw1 at nw 16", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 16,
+     (("s2_64_32_32x16_b2", "f2c"),)),
+    ("F2C KT64 P512 raw1 at nw 32, 3 tiles per image", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+     (("s2_48_32_48x32_b1", "f2c"),)),
+    ("F2C KT64 P512 raw1 at nw 64, 3 tiles per image", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 64 and p["tiles_per_img"] == 3,
+     (("s2_16_16_24x64_b2", "f2c"),)),
+    ("F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)", ":414-418, :385-386", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 156672,
+     (("s2_48_16_4x128_b1", "f2c"), ("s2_32_80_4x128_b1", "f2c"))),
+    ("F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image", ":385-386", lambda p: p["mode"] == "F2C" and p["kt"] == 128 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 139776 and p["tiles_per_img"] == 3,
+     (("s2_128_64_6x128_b1", "f2c"),)),
+    ("F2C cut in 2 uneven, a run = bps x nsub stages (10 + 8)", ":373-380", lambda p: p["mode"] == "F2C" and p["nsub"] == 2 and (p["nsplit"], p["sps"], p["last_bps"] * p["nsub"]) == (2, 10, 8),
+     (("s2_128_144_16x16_b1", "f2c"),)),
+    ("F2C KT64 cut in 3 uneven", ":373-380", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
+     (("s2_64_208_16x16_b1", "f2c"),)),
+    ("F2C 3 tiles per image (KT128)", ":134, :369", lambda p: p["mode"] == "F2C" and p["tiles_per_img"] == 3 and p["kt"] == 128,
+     (("s2_96_48_24x32_b2", "f2c"),)),
+    ("C2F KT64 P512 at nw 128", ":414-418", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 128,
+     (("s2_48_16_4x128_b1", "c2f"),)),
+    ("C2F KT128 P256 at nw 128", ":414-418", lambda p: p["mode"] == "C2F" and p["kt"] == 128 and p["Wl"] == 128,
+     (("s2_32_80_4x128_b1", "c2f"),)),
+    ("C2F KT64 P512 raw1 at nw 256", ":414-418, :385", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 256,
+     (("s2_16_16_2x256_b1", "c2f"),)),
+    ("C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image", ":414-418, :285-288", lambda p: p["mode"] == "C2F" and p["raw1"] and p["Wl"] == 256 and p["nstage"] == 3 and p["nsplit"] == 1 and p["tiles_per_img"] == 2,
+     (("s2_48_16_4x256_b2", "c2f"),)),
+    ("C2F KT64 P256 (rows) cut in 2, 3 tiles per image", ":373-380", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] == 2 and p["tiles_per_img"] == 3,
+     (("s2_128_64_6x128_b1", "c2f"),)),
+    ("C2F KT64 cut in 3 uneven", ":373-380", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
+     (("s2_208_64_16x16_b1", "c2f"),)),
+    ("C2F 3 tiles per image, both row phases", ":134, :369", lambda p: p["mode"] == "C2F" and p["tiles_per_img"] == 3 and p["nphase"] == 2,
+     (("s2_96_48_24x32_b2", "c2f"), ("s2_48_32_48x32_b1", "c2f"))),
+    ("k3 weight gradient: groups 6 / 10 / 12 (not a power of two)", ":771", lambda p: "RS" in p and "Ka" in p and p["groups"] in (6, 10, 12),
+     (("k3_c64_24x32_k160_b3", "dw"), ("k3_c32_10x128_k80_b1", "dw"), ("k3_c48_96x16_k32_b2", "dw"))),
+    ("k3 weight gradient: stages_per_wg lowered by the loop (4 -> 3), 1 < spw < groups", ":772-777", lambda p: "Ka" in p and p["lowered"] and 1 < p["spw"] < p["groups"],
+     (("k3w_ka512_cb256_48x16_b9", "dw"),)),
+    ("k3 weight gradient: spw = groups, ONE slab", ":772-777", lambda p: "Ka" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
+     (("k3w_ka1024_cb1088_16x16_b1", "dw"),)),
+    ("k4 s2 weight gradient: groups 12 / 24 (not a power of two)", ":998", lambda p: "Kc" in p and p["groups"] in (12, 24),
+     (("s2_96_48_24x32_b2", "dw"), ("s2_48_32_48x32_b1", "dw"))),
+    ("k4 s2 weight gradient: spw = groups 12, one slab per image", ":998-1004", lambda p: "Kc" in p and p["spw"] == p["groups"] == 12 and p["nsplit"] == p["B"],
+     (("s2w_512_512_24x32_b5", "dw"),)),
+    ("k4 s2 weight gradient: ONE slab", ":998-1004", lambda p: "Kc" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
+     (("s2w_512_1056_8x16_b1", "dw"),)),
+)
+
+ALL_CASE_IDS = tuple(K3_CASES) + tuple(K3_WRW_CASES) + tuple(S2_CASES) + tuple(S2_WRW_CASES)

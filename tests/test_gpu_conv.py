@@ -794,6 +794,47 @@ _ENGINES_AT_512 = (("forward", "smallmap"), ("forward", "thin"), ("forward", "wi
                    ("weight_grad", "wino_s2"), ("weight_grad", "winograd"))
 
 
+def test_every_engine_call_of_the_bf16_512_step_checked_in_situ(tmp_path):
+    """BASELINE config 4's shapes in config 5's arithmetic: bf16 autocast, 512x512, batch 4, 3x3 patches in the IPSR layer (the bf16
+    patch correlation for shift_sz > 1), a 256x256 centre hole.  Two steps: losses finite, netG's first weight moves, every HIP call of
+    the second step within its engine's band of an fp32 MIOpen convolution of the same operands (`_band`), the direct bf16 engine seen
+    in all three passes — among them k4 s2 calls on a 128-wide coarse grid (64 -> 128 down and 128 / 256 -> 64 up: the `raw1`
+    fine -> coarse plan at nw = 128 and the coarse -> fine one; the 128 -> 3 ConvTranspose2d even runs coarse -> fine at nw = 256) and k3
+    calls on a 256-wide map (64 -> 128 and 256 -> 64: one image row per tile) — and the engines of `_ENGINES_AT_512_BF16` reached.  The
+    weight gradients of those wide layers are not the direct kernel's (its k4 form stops at nw = 64, its k3 form at W = 128): the dispatcher
+    leaves them to other engines; the widest direct weight gradient is 128 -> 256 k4 on a 64-wide coarse grid.
+    Measured on an MI355X (batch 4 fits beside the fp32 MIOpen recomputation; the test takes 20-85 s): 111 HIP calls, 100 distinct
+    (kind, engine, shape); the floors below are those rounded down to the ten.  Worst error against its band: 3.5e-3 of 4.0e-3
+    (bf16 results: the rounding of the result itself), weight gradients on the direct kernel 1.9e-6 of 1e-4."""
+    img, mask, ref = _step_inputs(4, 512, 256, 43)
+    m, seen, engines, w0, ncalls = _check_step_in_situ(tmp_path, dict(batchSize=4, fineSize=512, shift_sz=3, use_dropout=True, amp_bf16=True), img, mask, ref)
+    e = m.get_current_errors()
+    assert all(np.isfinite(v) for v in e.values()), e
+    assert tuple(m.fake_B.shape) == (4, 3, 512, 512) and not torch.equal(m.netG.model.model[0].weight.detach(), w0)
+    print("engines reached at 512x512 in bf16:", sorted(engines))
+    print("calls %d, distinct %d" % (ncalls, len(seen)))
+    for key in sorted(k for k in seen if k[1] == "bf16d" and (k[2][-1] >= 256 or (k[3][-1] == 4 and k[2][-1] >= 128))):
+        print("  bf16d on a wide map: %s" % (key,))
+    bad = [(k, e, b) for k, (e, b) in seen.items() if not e <= b]
+    assert not bad, bad
+    for kind in ("forward", "input_grad", "weight_grad"):
+        assert (kind, "bf16d") in engines, "the 512x512 bf16 step did not run %s on the direct bf16 engine" % kind
+    k4 = [k for k in seen if k[1] == "bf16d" and k[3][-1] == 4 and k[4] == 2]
+    # x is the module's input: a Conv2d (weight [Cout, Cin]) halves it, a ConvTranspose2d (weight [Cin, Cout]) reads the coarse grid
+    assert any((k[3][1] == k[2][1] and k[2][-1] == 256) or (k[3][1] != k[2][1] and k[3][0] == k[2][1] and k[2][-1] == 128) for k in k4), \
+        "no direct bf16 k4 s2 call on a 128-wide coarse grid"
+    assert any(k[1] == "bf16d" and k[3][-1] == 3 and k[2][-1] == 256 for k in seen), "no direct bf16 k3 call on a 256-wide map"
+    for need in _ENGINES_AT_512_BF16:
+        assert need in engines, "the 512x512 bf16 step did not run %s on the %s engine" % need
+    assert ncalls >= 110 and len(seen) >= 100, (ncalls, len(seen))
+
+
+# what the 512x512 bf16 step reaches (printed by the test above on an MI355X)
+_ENGINES_AT_512_BF16 = (("forward", "bf16d"), ("forward", "smallmap"), ("forward", "thin_f2m"), ("forward", "wino_dil"), ("input_grad", "bf16d"),
+                        ("input_grad", "smallmap"), ("input_grad", "thin"), ("input_grad", "wino_dil"), ("weight_grad", "bf16d"), ("weight_grad", "smallmap"),
+                        ("weight_grad", "thin_mfma"), ("weight_grad", "wino_dil"), ("weight_grad", "winograd"))
+
+
 @pytest.mark.parametrize("tr,Cin,H,W,Cout,B", [(False, 32, 16, 16, 48, 2), (False, 128, 32, 32, 160, 3), (True, 64, 32, 64, 48, 2), (False, 16, 128, 128, 16, 1),
                                                (True, 256, 8, 32, 304, 2), (False, 64, 64, 64, 64, 2), (True, 144, 64, 16, 208, 1), (False, 512, 32, 32, 512, 16), (False, 64, 256, 256, 64, 1), (True, 32, 4, 256, 16, 2),
                                                (False, 256, 16, 16, 256, 2), (True, 512, 16, 16, 272, 3)])          # (the last two: reduction cut into four runs)
