@@ -2,8 +2,9 @@
 nn.ConvTranspose2d modules whose parameters, names and state_dict keys are untouched (models/networks.py:220-259,
 404-432, 470-495, 510-515; models/vgg16.py:9-21).
 
-Three engines per (operation, geometry), chosen by `select()` from measurements on MI355X at the step's shapes
-(tools/bench_hipconv.py -> profiles/r02_hipconv_*.txt):
+One engine per (operation, geometry), chosen by `select()` / `select_wrw()` from measurements on MI355X at the step's shapes
+(tools/bench_hipconv.py -> profiles/r02_hipconv_*.txt).  The engines are the records of `_ENGINES` below — the call that runs each
+pass and what the engine needs; a new engine is one record there plus its rule in `_select` / `_select_wrw`:
 
   "winograd"  csrc/winograd.hip   k3 s1 p1 forward / backward-data of Conv2d and ConvTranspose2d, F(4x4,3x3) on fp32 MFMA:
                                   2.0-2.4x MIOpen's F(2x2,3x3) assembly from 16x16 maps and 128 channels up
@@ -25,17 +26,17 @@ Three engines per (operation, geometry), chosen by `select()` from measurements 
                                   where it measured >= 7 % faster
   "one"       csrc/thin_conv.hip  Conv2d with ONE output channel, stride 1 (netD's last layer, 512 -> 1 on 31x31): forward and weight
                                   gradient as one pass over the input
+  "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
+                                  gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
 
 `IPSR_CONV_ENGINE=miopen|direct|winograd|auto` (default auto) forces one engine wherever it is implemented — for the
-per-engine parity tests and for A/B timing.  bf16 activations (BASELINE config 5): "bf16d" (csrc/conv_bf16.hip, the direct bf16
-implicit GEMM, forward / input gradient / weight gradient of the k3 s1 p1 layers) and the split-bf16 Winograd engines where they win;
-non-contiguous inputs and other dtypes take MIOpen.
+per-engine parity tests and for A/B timing.  Non-contiguous inputs and other dtypes take MIOpen.
 """
-import functools
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -48,13 +49,6 @@ _FORCE = None          # test hook: overrides the environment
 # Arithmetic of the Winograd GEMMs (ops.MATH_CODE): "fp32" for fp32 activations (the reference's arithmetic; "bf16x6" / "bf16x3" are
 # opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
-_BF16_ENGINES = ("winograd", "wino_dil", "wino_s2", "bf16d")         # the engines that read / write bf16 activation tensors
-
-
-# fp32 engines whose operands are small next to their weight stream / single pass (the innermost levels, netD's one-channel head): under
-# bf16 activations they run on fp32 copies of the activations (a cast of a few hundred KB) instead of falling back to MIOpen's
-# transposes + 40-160 us kernels
-_CAST_ENGINES = ("one", "smallmap")
 
 
 def set_conv_math(fp32=None, bf16=None):
@@ -89,8 +83,6 @@ def _env(name, default):
 def reload_env():
     _ENV.clear()
     _SEL.clear()
-    for f in (_select, _select_wrw, _bf16_direct, _bf16_direct_wrw):
-        f.cache_clear()
 
 
 def _mode():
@@ -104,39 +96,42 @@ def select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
     key = (0, _FORCE, op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
     eng = _SEL.get(key)
     if eng is None:
-        eng = _SEL[key] = _select_any(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
+        eng = _SEL[key] = _select_any(op, (op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA), B, Cin, H, W, Cout, k, stride, pad, dil), bf16)
     return eng
 
 
-def _select_any(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16):
-    eng = _select(_mode(), _env("IPSR_NO_SMALLMAP", "0") + _env("IPSR_NO_THIN", "0") + _env("IPSR_SMALLMAP_MAX_POS", "32"), op, B, Cin, H, W, Cout, k, stride, pad, dil)
+# Below `select` / `select_wrw` a layer travels as ONE tuple, `lay` = (transposed, B, Cin, H, W, Cout, k, stride, pad, dil): (Cin, H, W) =
+# the module's input whatever the operation.  The rule functions read the switches through `_mode()` / `_env()`; `_SEL` is the only memo.
+def _select_any(op, lay, bf16):
+    eng = _select(op, lay)
     if not bf16:
         return eng
-    if _bf16_wins(eng, Cin, H, W, Cout) or eng in _CAST_ENGINES:
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
         return eng
-    if _mode() == "auto" and _thin_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil, True):
+    if _mode() == "auto" and _thin_wins(op, lay, True):
         return "thin"            # the vector-ALU stream kernels read / write bf16 tensors themselves (ipsr_conv3x3_thin_io)
     if _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and op == ops.CONV_FWD and Cin == 3 and (k, stride, pad, dil) == (4, 2, 1, 1) and H * W >= 4096 \
             and ops.thin_f2m_mfma_supported(op, B, Cin, H, W, Cout, k, stride):
         # the first Conv2d of netP / netD (3 -> 64, k4 s2): the window gather on the matrix cores, 0.041-0.045 vs MIOpen's 0.059 ms and one
         # launch instead of four (profiles/r04_thin_bf16.txt; for the 3x3 thin layers the vector-ALU kernels and MIOpen stay ahead or level)
         return "thin_f2m"
-    return _bf16_direct(_env("IPSR_BF16_ENGINES", ""), _mode(), op, B, Cin, H, W, Cout, k, stride, pad, dil)
+    return _bf16_direct(op, lay)
 
 
-@functools.lru_cache(maxsize=4096)
-def _bf16_direct(force, mode, op, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _bf16_direct(op, lay):
     """bf16 activations, and the split-bf16 Winograd engines do not win this shape: the DIRECT bf16 implicit GEMM (csrc/conv_bf16.hip,
     ops.conv3x3_bf16: one launch, NCHW in and out) where it is implemented — k3 s1 p1 on maps of 16..128 pixels width — else MIOpen.
     Measured at batch 16 (profiles/r04_conv_bf16_layers.txt): 700-870 TF against MIOpen's 350-570 incl. its layout transposes on
     every map from 32x32 up; on 16x16 maps MIOpen ties (and the Winograd engines win from 512 channels)."""
-    if force == "none" or mode in ("miopen", "winograd", "direct"):
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if _env("IPSR_BF16_ENGINES", "") == "none" or _mode() in ("miopen", "winograd", "direct"):
         return "miopen"
     if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 256 and ops.conv3x3_bf16_supported(op, B, Cin, H, W, Cout):
         return "bf16d"           # 16x16 maps too since the reduction is cut over workgroups there (0.041-0.063 vs 0.056-0.081 split-Winograd, 0.070-0.122 MIOpen)
     # (measured and not kept: the small-map engine on fp32 copies for the innermost levels beyond 32 positions per batch — 708 images/s at
     # 32, 706 at 64, 696 at 256, 658 at 1024: MIOpen's tiny bf16 convolutions cost 45-60 us per CALL but far less device time)
-    g = _s2_geometry(op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA), B, Cin, H, W, Cout, k, stride, pad, dil)
+    g = _s2_geometry(lay)
     if g is not None and ops.conv4x4s2_bf16_supported(_s2_mode(op), B, *g):
         # the 4x4 stride-2 family (profiles/r04_conv_bf16_layers.txt, batch 16): 1.3-2x MIOpen wherever the launch has enough tiles;
         # a 16x16 coarse grid gives one pixel tile per image (64 workgroups at 512 channels) and MIOpen ties or wins
@@ -158,7 +153,7 @@ def _bf16_wins(eng, Cin, H, W, Cout, wrw=False):
     they lose on larger maps and on the whole 4x4 stride-2 family (1.1-1.7x) — those stay on MIOpen.  IPSR_BF16_ENGINES=all|none
     overrides (A/B timing)."""
     force = _env("IPSR_BF16_ENGINES", "")
-    if eng not in _BF16_ENGINES or force == "none":
+    if not _ENGINES[eng].bf16_io or force == "none":
         return False
     if force == "all":
         return True
@@ -172,8 +167,9 @@ def _bf16_wins(eng, Cin, H, W, Cout, wrw=False):
     return False
 
 
-@functools.lru_cache(maxsize=4096)
-def _select(mode, _nosm, op, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _select(op, lay):
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    mode = _mode()
     fwd = op in (ops.CONV_FWD, ops.CONVT_FWD)
     cred, kout = (Cin, Cout) if fwd else (Cout, Cin)            # reduction / produced channels of this operation
     wino_ok = k == 3 and stride == 1 and pad == 1 and dil == 1 and cred % 16 == 0
@@ -193,12 +189,12 @@ def _select(mode, _nosm, op, B, Cin, H, W, Cout, k, stride, pad, dil):
         return "wino_dil"        # netD's 4x4 stride-1 convolution: the same F(3x3,4x4) pipeline on the image itself
     if mode == "auto" and op == ops.CONV_FWD and Cout == 1 and Cin >= 64 and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil):
         return "one"             # netD's last layer (512 -> 1): a single pass over the input, 15 vs 80-143 us
-    if mode == "auto" and _thin_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil):
+    if mode == "auto" and _thin_wins(op, lay):
         return "thin"            # 3/6-channel side at full resolution: one pass over the wide tensor on the vector ALUs
-    if mode == "auto" and _smallmap_data_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil):
+    if mode == "auto" and _smallmap_data_wins(op, lay):
         return "smallmap"        # innermost levels (<= 32 positions per batch): the weight tensor streamed once into MFMA operands
     if mode == "auto":
-        g = _s2_geometry(op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA), B, Cin, H, W, Cout, k, stride, pad, dil)
+        g = _s2_geometry(lay)
         if g is not None and _s2_wins(g, _s2_mode(op), B) and ops.s2_winograd_supported(_s2_mode(op), B, *g):
             return "wino_s2"     # 4x4 stride-2 layers: polyphase Winograd F(5x5,2x2)
     # auto: measured rules (MI355X, batch 8; profiles/r03_hipconv_k3.txt).  64 produced channels run on the GEMM's 64-row tile:
@@ -214,8 +210,9 @@ def _is_dilated4(k, stride, pad, dil):
     return k == 4 and stride == 2 and pad == 3 and dil == 2
 
 
-def _s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _s2_geometry(lay):
     """(Kc, Cf, nh, nw) of a k4 s2 p1 layer in the coarse / fine terms of ipsr_conv4x4s2_winograd, or None."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if not (k == 4 and stride == 2 and pad == 1 and dil == 1):
         return None
     if transposed:
@@ -241,9 +238,10 @@ def _s2_mode(op):
     return ops.S2_FINE_TO_COARSE if op in (ops.CONV_FWD, ops.CONVT_BWD_DATA) else ops.S2_COARSE_TO_FINE
 
 
-def _smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _smallmap_geometry(lay):
     """(B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil) of ipsr_conv_smallmap for this module call: R / (Ho, Wo) = the weight's first
     channel dimension and its grid, Cq / (Hf, Wf) = the second."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if transposed:
         Hy, Wy = (H - 1) * stride - 2 * pad + dil * (k - 1) + 1, (W - 1) * stride - 2 * pad + dil * (k - 1) + 1
         return B, Cin, Cout, H, W, Hy, Wy, k, stride, pad, dil
@@ -251,7 +249,7 @@ def _smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
     return B, Cout, Cin, Hy, Wy, H, W, k, stride, pad, dil
 
 
-def _thin_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
+def _thin_wins(op, lay, bf16=False):
     """3x3 stride-1 layers with a 3- or 6-channel side on maps of >= 64x64 (profiles/r02_thin.txt, device time at 256x256, batch 8):
     many -> few (VGG conv1_1 input gradient 185 -> 61 us, netG's last ConvTranspose2d forward 217 -> 130 us) and 3 -> many
     (VGG conv1_1 forward 70 -> 52 us, and the bias + ReLU pass goes into the kernel); 6 -> 64 forward and the weight gradients
@@ -260,6 +258,7 @@ def _thin_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
     on MIOpen (175 vs 156 us) and many -> 3 on the direct MFMA kernel (252 vs 300 us)."""
     if _env("IPSR_NO_THIN", "0") == "1":           # A/B switch
         return False
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if not (k == 3 and stride == 1 and pad == 1 and dil == 1) or H * W < 4096 or not ops.thin_supported(op, Cin, H, W, Cout):
         return False
     fwd = op in (ops.CONV_FWD, ops.CONVT_FWD)
@@ -274,21 +273,23 @@ def _smallmap_op(op):
     return ops.SM_FWD if op in (ops.CONV_FWD, ops.CONVT_BWD_DATA) else ops.SM_DATA
 
 
-def _smallmap_data_wins(op, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _smallmap_data_wins(op, lay):
     """Forward / input gradient on grids of <= 32 positions per batch (2x2 and 1x1 at batch 8): 15-20 us on the device against
     MIOpen's 40-50 (profiles/r02_hipconv_small.txt); from 128 positions up the op is a real GEMM and MIOpen ties."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if _env("IPSR_NO_SMALLMAP", "0") == "1" or k not in (3, 4) or min(Cin, Cout) < 256:
         return False
-    g = _smallmap_geometry(op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA), B, Cin, H, W, Cout, k, stride, pad, dil)
+    g = _smallmap_geometry(lay)
     return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= int(_env("IPSR_SMALLMAP_MAX_POS", "32")) and ops.smallmap_supported(_smallmap_op(op), *g)
 
 
-def _smallmap_wrw_wins(transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _smallmap_wrw_wins(lay):
     """Weight gradients of the 4x4 layers on grids of <= 256 positions per batch (the four innermost levels at batch 8): the GEMM
     writes dW in place, 27-39 us against MIOpen's 41-57 (profiles/r02_hipconv_small.txt)."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if k != 4 or stride != 2 or _env("IPSR_NO_SMALLMAP", "0") == "1":        # the switch is for A/B timing
         return False
-    g = _smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)
+    g = _smallmap_geometry(lay)
     return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= 256 and min(Cin, Cout) >= 256 and ops.smallmap_supported(ops.SM_WRW, *g)
 
 
@@ -302,43 +303,45 @@ def select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
     key = (1, _FORCE, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
     eng = _SEL.get(key)
     if eng is None:
-        eng = _SEL[key] = _select_wrw_any(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
+        eng = _SEL[key] = _select_wrw_any((transposed, B, Cin, H, W, Cout, k, stride, pad, dil), bf16)
     return eng
 
 
-def _select_wrw_any(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16):
-    eng = _select_wrw(_mode(), _env("IPSR_NO_SMALLMAP", "0"), transposed, B, Cin, H, W, Cout, k, stride, pad, dil)
+def _select_wrw_any(lay, bf16):
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    eng = _select_wrw(lay)
     thin = _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and pad == 1 and dil == 1 and (k, stride) in ((3, 1), (4, 2)) and H * W >= 4096 \
         and ops.thin_wrw_mfma_supported(transposed, B, Cin, H, W, Cout, k, stride)
     if not bf16:
         # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
         return "thin_mfma" if thin and eng == "miopen" else eng
-    if _bf16_wins(eng, Cin, H, W, Cout, True) or eng in _CAST_ENGINES:
+    if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
         return eng
     if thin:
         # 3 / 6 channels on the narrow side: the pixel reduction on the bf16 matrix cores straight from NCHW (profiles/r04_thin_bf16.txt, batch 16:
         # 3 -> 64 k4 s2 0.033 vs MIOpen's 0.057 ms, ConvT 128 -> 3 k3 0.152 vs 0.202, k4 s2 0.052 vs 0.063, 6 -> 64 0.118 vs 0.125 — and 2
         # launches instead of MIOpen's 5-6)
         return "thin_mfma"
-    return _bf16_direct_wrw(_env("IPSR_BF16_ENGINES", ""), _mode(), transposed, B, Cin, H, W, Cout, k, stride, pad, dil)
+    return _bf16_direct_wrw(lay)
 
 
-@functools.lru_cache(maxsize=4096)
-def _bf16_direct_wrw(force, mode, transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _bf16_direct_wrw(lay):
     """Weight gradient on bf16 activations by the direct kernel (ops.conv3x3_bf16_wrw): 1.1-2.0x MIOpen on every map from 32x32 up (one
     run per CU: the partial-sum slabs are what it costs)."""
-    if force == "none" or mode in ("miopen", "winograd", "direct"):
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if _env("IPSR_BF16_ENGINES", "") == "none" or _mode() in ("miopen", "winograd", "direct"):
         return "miopen"
     if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and ops.conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):
         return "bf16d"
-    g = _s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)
+    g = _s2_geometry(lay)
     if g is not None and g[3] >= 32 and ((g[0] + 127) // 128) * ((g[1] + 31) // 32) >= 4 and ops.conv4x4s2_bf16_wrw_supported(B, *g):
         return "bf16d"           # 1.2-1.4x MIOpen from four 128 x 32 output tiles up on coarse grids >= 32 wide; 16-wide grids and single tiles lose
     return "miopen"
 
 
-@functools.lru_cache(maxsize=4096)
-def _select_wrw(mode, _nosm, transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+def _select_wrw(lay):
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    mode = _mode()
     if mode == "auto" and not transposed and Cout == 1 and Cin >= 64 and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil):
         return "one"
     if mode == "auto" and not transposed and _is_dilated4(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 32 <= H <= 128 \
@@ -347,10 +350,10 @@ def _select_wrw(mode, _nosm, transposed, B, Cin, H, W, Cout, k, stride, pad, dil
     if mode == "auto" and not transposed and _is_k4s1(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 16 <= H <= 128:
         return "wino_dil"
     if mode == "auto":
-        g = _s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)
+        g = _s2_geometry(lay)
         if g is not None and _s2_wins(g):
             return "wino_s2"
-    if mode == "auto" and _smallmap_wrw_wins(transposed, B, Cin, H, W, Cout, k, stride, pad, dil):
+    if mode == "auto" and _smallmap_wrw_wins(lay):
         return "smallmap"
     ok = k == 3 and stride == 1 and pad == 1 and dil == 1
     if mode in ("miopen", "direct") or not ok:
@@ -364,15 +367,93 @@ def _select_wrw(mode, _nosm, transposed, B, Cin, H, W, Cout, k, stride, pad, dil
     return "miopen"
 
 
-def _bf16_direct_call(op, inp, w, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, out_dtype, param=None):
+# ---- the engines: one record each, the source of the list in the module docstring -----------------------------------------------------
+# data:  (op, inp, w, lay, math, out_dtype, param) -> y / dx: forward (inp = x) and input gradient (inp = dy) share the call
+# wrw:   (x, dy, lay, math, sink) -> dW (fp32, the module's layout); None: the engine has no such pass
+#        ("miopen" has neither: it runs through _miopen_forward / _miopen_backward).  lay[1:5] = (B, Cin, H, W), lay[5] = Cout, lay[6:] = (k, stride, pad, dil)
+# bf16_io:     reads / writes bf16 activation tensors in competition with MIOpen's bf16 kernels: the engines `_bf16_wins` rules on (the thin
+#              engines read bf16 too, by rules of their own in `_select_any` / `_select_wrw_any`)
+# fp32_copies: an fp32 engine whose operands are small next to its weight stream / single pass (the innermost levels, netD's one-channel
+#              head): under bf16 activations it runs on fp32 copies of the activations (a cast of a few hundred KB) instead of falling
+#              back to MIOpen's transposes + 40-160 us kernels
+# sink:        data parallel: may write the weight gradient straight into its slice of the armed gradient bucket (dist.py)
+# wrw_x_as_dy: a weight gradient that reads both operands in one dtype: x is cast to dy's
+_Engine = namedtuple("_Engine", "data wrw bf16_io fp32_copies sink wrw_x_as_dy", defaults=(None, None, False, False, False, False))
+
+
+def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
     """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form.
     param: the module's weight Parameter when `w` is a detached view of it (the no-grad path).  Frozen weights (a leaf Parameter
     with requires_grad False, outside autograd) keep their packed bf16 image, cached under the Parameter."""
-    if k == 3:
+    if inp.dtype != torch.bfloat16:
+        inp = inp.to(torch.bfloat16)
+    if lay[6] == 3:
         param = w if param is None else param
         frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
-        return ops.conv3x3_bf16(op, inp, w, (B, Cin, H, W), Cout, out_dtype=out_dtype, keep_packed=frozen, pack_key=param)
-    return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), out_dtype=out_dtype)
+        return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, keep_packed=frozen, pack_key=param)
+    return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), out_dtype=out_dtype)
+
+
+def _bf16d_wrw(x, dy, lay, math, sink):
+    if lay[6] == 3:
+        return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
+    return ops.conv4x4s2_bf16_wrw(*((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink)       # (fine, coarse)
+
+
+def _thin_mfma_wrw(x, dy, lay, math, sink):
+    if lay[0] and dy.dtype == torch.bfloat16 and x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)                 # the WIDE tensor decides the arithmetic
+    return ops.conv_thin_wrw_mfma(lay[0], x, dy, lay[6], lay[7], out=sink)
+
+
+_ENGINES = {
+    "winograd": _Engine(
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_winograd(op, inp, w, lay[1:5], lay[5], math=math, out_dtype=out_dtype),
+        lambda x, dy, lay, math, sink: ops.conv3x3_winograd_wrw(lay[0], x, dy, lay[5], out=sink, math=math),
+        bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "wino_dil": _Engine(         # mode 0 forward, 1 input gradient, 2 weight gradient
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv4x4_dilated_winograd(
+            int(op != ops.CONV_FWD), inp, w, lay[1:5], lay[5], geom=ops.conv4x4_geometry(*lay[6:]), math=math, out_dtype=out_dtype),
+        lambda x, dy, lay, math, sink: ops.conv4x4_dilated_winograd(2, x, dy, lay[1:5], lay[5], out=sink, geom=ops.conv4x4_geometry(*lay[6:]), math=math),
+        bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "wino_s2": _Engine(          # the weight gradient takes (fine, coarse)
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv4x4s2_winograd(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), math=math, out_dtype=out_dtype),
+        lambda x, dy, lay, math, sink: ops.conv4x4s2_winograd(ops.S2_WEIGHT_GRAD, *((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink, math=math),
+        bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "thin": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_thin(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype)),
+    "thin_f2m": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv_thin_f2m_mfma(op, inp, w, lay[1:5], lay[5], lay[6], lay[7], out_dtype=out_dtype)),
+    "thin_mfma": _Engine(None, _thin_mfma_wrw, sink=True),
+    "smallmap": _Engine(         # the weight gradient takes (coarse, fine)
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv_smallmap(_smallmap_op(op), inp, w, *_smallmap_geometry(lay)),
+        lambda x, dy, lay, math, sink: ops.conv_smallmap(ops.SM_WRW, *((x, dy) if lay[0] else (dy, x)), *_smallmap_geometry(lay), out=sink),
+        fp32_copies=True, sink=True),
+    "direct": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv2d(op, inp, w, lay[1:5], *lay[5:])),
+    "one": _Engine(
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv_to_one(inp, w, lay[8]),
+        lambda x, dy, lay, math, sink: ops.conv_to_one_wrw(x, dy, lay[6], lay[8], out=sink),
+        fp32_copies=True, sink=True),
+    "bf16d": _Engine(_bf16d_data, _bf16d_wrw, bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "miopen": _Engine(),
+}
+
+
+def _run_data(eng, op, inp, w, lay, math, out_dtype, param=None):
+    """Forward (inp = x) or input gradient (inp = dy) of one layer on a HIP engine; `inp` contiguous."""
+    e = _ENGINES[eng]
+    if e.fp32_copies:
+        return e.data(op, inp.float(), w, lay, math, torch.float32, param).to(out_dtype)
+    return e.data(op, inp, w, lay, math, out_dtype, param)
+
+
+def _run_wrw(eng, x, dy, w, lay, math):
+    """Weight gradient of one layer on a HIP engine (fp32, the module's layout); x, dy contiguous."""
+    e = _ENGINES[eng]
+    sink = ipsr_dist.grad_sink_for(w.data_ptr(), w.shape) if e.sink else None
+    if e.fp32_copies:
+        x, dy = x.float(), dy.float()
+    elif e.wrw_x_as_dy and x.dtype != dy.dtype:
+        x = x.to(dy.dtype)
+    return e.wrw(x, dy, lay, math, sink)
 
 
 def _miopen_forward(x, w, transposed, stride, pad, dil):
@@ -394,33 +475,15 @@ class _HipConv(torch.autograd.Function):
     (MIOpen where none is faster).  `math` = the Winograd engines' arithmetic, `act` = dtype of the activation tensors produced."""
 
     @staticmethod
-    def forward(ctx, x, w, transposed, k, stride, pad, dil, eng_fwd, math, act):
-        B, Cin, H, W = x.shape
-        Cout = w.shape[1] if transposed else w.shape[0]
-        op = ops.CONVT_FWD if transposed else ops.CONV_FWD
+    def forward(ctx, x, w, lay, eng_fwd, math, act):
+        transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
         xc = x.contiguous()
-        if eng_fwd == "winograd":
-            y = ops.conv3x3_winograd(op, xc, w, (B, Cin, H, W), Cout, math=math, out_dtype=act)
-        elif eng_fwd == "direct":
-            y = ops.conv2d(op, xc, w, (B, Cin, H, W), Cout, k, stride, pad, dil)
-        elif eng_fwd == "bf16d":
-            y = _bf16_direct_call(op, xc if xc.dtype == torch.bfloat16 else xc.to(torch.bfloat16), w, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, act)
-        elif eng_fwd == "wino_dil":
-            y = ops.conv4x4_dilated_winograd(0, xc, w, (B, Cin, H, W), Cout, geom=ops.conv4x4_geometry(k, stride, pad, dil), math=math, out_dtype=act)
-        elif eng_fwd == "thin":
-            y = ops.conv3x3_thin(op, xc, w, (B, Cin, H, W), Cout, out_dtype=act)
-        elif eng_fwd == "thin_f2m":
-            y = ops.conv_thin_f2m_mfma(op, xc, w, (B, Cin, H, W), Cout, k, stride, out_dtype=act)
-        elif eng_fwd == "one":
-            y = ops.conv_to_one(xc.float(), w, pad).to(act)
-        elif eng_fwd == "smallmap":
-            y = ops.conv_smallmap(_smallmap_op(op), xc.float(), w, *_smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)).to(act)
-        elif eng_fwd == "wino_s2":
-            y = ops.conv4x4s2_winograd(_s2_mode(op), xc, w, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), math=math, out_dtype=act)
-        else:
+        if eng_fwd == "miopen":
             y = _miopen_forward(xc, w, transposed, stride, pad, dil)
+        else:
+            y = _run_data(eng_fwd, ops.CONVT_FWD if transposed else ops.CONV_FWD, xc, w, lay, math, act)
         ctx.save_for_backward(xc, w)
-        ctx.geom = (transposed, k, stride, pad, dil, Cout)
+        ctx.lay, ctx.geom = lay, (transposed, k, stride, pad, dil, Cout)
         ctx.math, ctx.bf16 = math, act == torch.bfloat16
         if _check_hook is not None:
             _check_hook("forward", eng_fwd, ctx.geom, (xc, w), y)
@@ -429,9 +492,8 @@ class _HipConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        transposed, k, stride, pad, dil, Cout = ctx.geom
-        math, bf16 = ctx.math, ctx.bf16
-        B, Cin, H, W = x.shape
+        lay, math, bf16 = ctx.lay, ctx.math, ctx.bf16
+        transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
         dy = dy.contiguous()
         if bf16 and dy.dtype != torch.bfloat16:
             dy = dy.to(torch.bfloat16)
@@ -439,55 +501,23 @@ class _HipConv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             op = ops.CONVT_BWD_DATA if transposed else ops.CONV_BWD_DATA
             eng = select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
-            if eng == "winograd":
-                dx = ops.conv3x3_winograd(op, dy, w, (B, Cin, H, W), Cout, math=math, out_dtype=x.dtype)
-            elif eng == "direct":
-                dx = ops.conv2d(op, dy, w, (B, Cin, H, W), Cout, k, stride, pad, dil)
-            elif eng == "bf16d":
-                dx = _bf16_direct_call(op, dy, w, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, x.dtype)
-            elif eng == "wino_dil":
-                dx = ops.conv4x4_dilated_winograd(1, dy, w, (B, Cin, H, W), Cout, geom=ops.conv4x4_geometry(k, stride, pad, dil), math=math, out_dtype=x.dtype)
-            elif eng == "thin":
-                dx = ops.conv3x3_thin(op, dy, w, (B, Cin, H, W), Cout, out_dtype=x.dtype)
-            elif eng == "smallmap":
-                dx = ops.conv_smallmap(_smallmap_op(op), dy.float(), w, *_smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)).to(x.dtype)
-            elif eng == "wino_s2":
-                dx = ops.conv4x4s2_winograd(_s2_mode(op), dy, w, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), math=math, out_dtype=x.dtype)
-            else:
+            if eng == "miopen":
                 dx = _miopen_backward(dy, x, w, transposed, stride, pad, dil, [True, False, False])[0]
                 if dx.dtype != x.dtype:
                     dx = dx.to(x.dtype)
+            else:
+                dx = _run_data(eng, op, dy, w, lay, math, x.dtype)
             if _check_hook is not None:
                 _check_hook("input_grad", eng, ctx.geom, (dy, x, w), dx)
-        weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if ctx.needs_input_grad[1] else None
-        # data parallel: write the weight gradient straight into its slice of the armed gradient bucket (dist.py)
-        sink = ipsr_dist.grad_sink_for(w.data_ptr(), w.shape) if weng in ("winograd", "wino_dil", "wino_s2", "smallmap", "one", "bf16d", "thin_mfma") else None
-        xw = x if (x.dtype == dy.dtype or weng in (None, "miopen", "thin_mfma")) else x.to(dy.dtype)      # a weight gradient reads both operands in one dtype
-        if weng == "winograd":
-            dw = ops.conv3x3_winograd_wrw(transposed, xw, dy, Cout, out=sink, math=math)
-        elif weng == "thin_mfma":
-            xa = x.to(torch.bfloat16) if (bf16 and transposed and x.dtype != torch.bfloat16) else x       # the WIDE tensor decides the arithmetic
-            dw = ops.conv_thin_wrw_mfma(transposed, xa, dy, k, stride, out=sink)
-        elif weng == "bf16d" and k == 3:
-            dw = ops.conv3x3_bf16_wrw(transposed, xw, dy, Cout, out=sink)
-        elif weng == "bf16d":
-            fine, coarse = (dy, xw) if transposed else (xw, dy)
-            dw = ops.conv4x4s2_bf16_wrw(fine, coarse, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), out=sink)
-        elif weng == "wino_dil":
-            dw = ops.conv4x4_dilated_winograd(2, xw, dy, (B, Cin, H, W), Cout, out=sink, geom=ops.conv4x4_geometry(k, stride, pad, dil), math=math)
-        elif weng == "one":
-            dw = ops.conv_to_one_wrw(x.float(), dy.float(), k, pad, out=sink)
-        elif weng == "smallmap":
-            coarse, fine = (x.float(), dy.float()) if transposed else (dy.float(), x.float())
-            dw = ops.conv_smallmap(ops.SM_WRW, coarse, fine, *_smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), out=sink)
-        elif weng == "wino_s2":
-            fine, coarse = (dy, xw) if transposed else (xw, dy)
-            dw = ops.conv4x4s2_winograd(ops.S2_WEIGHT_GRAD, fine, coarse, B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil), out=sink, math=math)
-        elif ctx.needs_input_grad[1]:
-            dw = _miopen_backward(dy, x, w, transposed, stride, pad, dil, [False, True, False])[1]
-        if _check_hook is not None and dw is not None:
-            _check_hook("weight_grad", weng or "miopen", ctx.geom, (dy, x, w), dw)
-        return dx, dw, None, None, None, None, None, None, None, None
+        if ctx.needs_input_grad[1]:
+            weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
+            if weng == "miopen":
+                dw = _miopen_backward(dy, x, w, transposed, stride, pad, dil, [False, True, False])[1]
+            else:
+                dw = _run_wrw(weng, x, dy, w, lay, math)
+            if _check_hook is not None:
+                _check_hook("weight_grad", weng, ctx.geom, (dy, x, w), dw)
+        return dx, dw, None, None, None, None
 
 
 def _geometry(m):
@@ -502,18 +532,32 @@ def _geometry(m):
     return ks[0], st[0], pd[0], dl[0]
 
 
+def _layer_of(m, x, w):
+    """-> (lay, bf16) when the call m(x) with the weight w is one the engines can take (a 4-d fp32 / bf16 GPU tensor, fp32 weights, no
+    autocast other than bf16), else None.  bf16: the activations are bf16 (a bf16 tensor, or any input under bf16 autocast)."""
+    g = _geometry(m)
+    if g is None or not x.is_cuda or x.dim() != 4 or w.dtype != torch.float32 or x.dtype not in (torch.float32, torch.bfloat16):
+        return None
+    amp = _amp_bf16()
+    if not amp and torch.is_autocast_enabled():
+        return None
+    transposed = isinstance(m, nn.ConvTranspose2d)
+    B, Cin, H, W = x.shape
+    return (transposed, B, Cin, H, W, w.shape[1] if transposed else w.shape[0]) + g, amp or x.dtype == torch.bfloat16
+
+
+def conv_math(bf16):
+    """The arithmetic (ops.MATH_CODE) the Winograd engines run under fp32 (False) / bf16 (True) activations: see `set_conv_math`."""
+    return _MATH["bf16" if bf16 else "fp32"]
+
+
 def any_engine(m, x):
     """True when at least one pass of m(x) would run on a HIP engine (so the caller should split the bias off and come through
     conv_nobias); False = all three passes are MIOpen's and the plain module call loses nothing."""
-    g = _geometry(m)
-    if g is None or not x.is_cuda or x.dim() != 4 or m.weight.dtype != torch.float32 or x.dtype not in (torch.float32, torch.bfloat16) \
-            or (torch.is_autocast_enabled() and not _amp_bf16()):
+    lb = _layer_of(m, x, m.weight)
+    if lb is None:
         return False
-    transposed = isinstance(m, nn.ConvTranspose2d)
-    k, stride, pad, dil = g
-    B, Cin, H, W = x.shape
-    Cout = m.weight.shape[1] if transposed else m.weight.shape[0]
-    bf16 = _amp_bf16() or x.dtype == torch.bfloat16
+    (transposed, B, Cin, H, W, Cout, k, stride, pad, dil), bf16 = lb
     fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if transposed else (ops.CONV_FWD, ops.CONV_BWD_DATA)
     return select(fop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) != "miopen" \
         or select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) != "miopen" \
@@ -522,52 +566,26 @@ def any_engine(m, x):
 
 def conv_nobias(m, x, weight=None):
     """m(x) without the bias (the fused epilogue kernels add it): HIP engine where `select` says so, else MIOpen.  fp32 activations:
-    every engine; bf16 activations (a bf16 tensor, or any input under bf16 autocast — BASELINE config 5): the Winograd engines, which
-    read / write bf16 and multiply split-bf16 operands on the bf16 matrix cores (`_MATH`); the weights stay fp32 parameters."""
+    every engine; bf16 activations (a bf16 tensor, or any input under bf16 autocast — BASELINE config 5): the engines that read / write
+    bf16 or run on fp32 copies (`_ENGINES`), the Winograd ones on split-bf16 operands (`_MATH`); the weights stay fp32 parameters."""
     w = m.weight if weight is None else weight
-    transposed = isinstance(m, nn.ConvTranspose2d)
-    g = _geometry(m)
-    amp = _amp_bf16()
-    if g is not None and x.is_cuda and w.dtype == torch.float32 and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) \
-            and (amp or not torch.is_autocast_enabled()):
-        k, stride, pad, dil = g
-        B, Cin, H, W = x.shape
-        Cout = w.shape[1] if transposed else w.shape[0]
+    lb = _layer_of(m, x, w)
+    if lb is not None:
+        lay, bf16 = lb
+        transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
         op = ops.CONVT_FWD if transposed else ops.CONV_FWD
-        bf16 = amp or x.dtype == torch.bfloat16
         act = torch.bfloat16 if bf16 else torch.float32
         math = _MATH["bf16" if bf16 else "fp32"]
         eng = select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
-        if needs_grad:
+        if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
             # the backward may use a HIP engine even where the forward stays on MIOpen
             bop = ops.CONVT_BWD_DATA if transposed else ops.CONV_BWD_DATA
             beng = select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if x.requires_grad else "miopen"
             weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if w.requires_grad else "miopen"
             if eng != "miopen" or beng != "miopen" or weng != "miopen":
-                return _HipConv.apply(x, w, transposed, k, stride, pad, dil, eng, math, act)
-        elif eng == "winograd":
-            return ops.conv3x3_winograd(op, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, math=math, out_dtype=act)
-        elif eng == "direct":
-            return ops.conv2d(op, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, k, stride, pad, dil)
-        elif eng == "bf16d":
-            xb = x.contiguous()
-            return _bf16_direct_call(op, xb if xb.dtype == torch.bfloat16 else xb.to(torch.bfloat16), w.detach(), transposed, B, Cin, H, W, Cout, k, stride, pad, dil, act,
-                                     param=w)
-        elif eng == "wino_dil":
-            return ops.conv4x4_dilated_winograd(0, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, geom=ops.conv4x4_geometry(k, stride, pad, dil),
-                                                math=math, out_dtype=act)
-        elif eng == "thin":
-            return ops.conv3x3_thin(op, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, out_dtype=act)
-        elif eng == "thin_f2m":
-            return ops.conv_thin_f2m_mfma(op, x.contiguous(), w.detach(), (B, Cin, H, W), Cout, k, stride, out_dtype=act)
-        elif eng == "one":
-            return ops.conv_to_one(x.contiguous().float(), w.detach(), pad).to(act)
-        elif eng == "smallmap":
-            return ops.conv_smallmap(_smallmap_op(op), x.contiguous().float(), w.detach(), *_smallmap_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil)).to(act)
-        elif eng == "wino_s2":
-            return ops.conv4x4s2_winograd(_s2_mode(op), x.contiguous(), w.detach(), B, *_s2_geometry(transposed, B, Cin, H, W, Cout, k, stride, pad, dil),
-                                          math=math, out_dtype=act)
-    if transposed:
+                return _HipConv.apply(x, w, lay, eng, math, act)
+        elif eng != "miopen":
+            return _run_data(eng, op, x.contiguous(), w.detach(), lay, math, act, param=w)
+    if isinstance(m, nn.ConvTranspose2d):
         return F.conv_transpose2d(x, w, None, m.stride, m.padding, m.output_padding, m.groups, m.dilation)
     return F.conv2d(x, w, None, m.stride, m.padding, m.dilation, m.groups)

@@ -101,9 +101,9 @@ class Vgg16(torch.nn.Module):
                 pool = i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d) and x.size(2) % 2 == 0 and x.size(3) % 2 == 0
                 B, Cin, H, W = x.shape
                 bf16 = hipconv._amp_bf16() or x.dtype == torch.bfloat16
-                if (bf16 or not torch.is_autocast_enabled()) and not m.weight.requires_grad and \
-                        hipconv.select(ops.CONV_FWD, B, Cin, H, W, m.out_channels, 3, 1, 1, 1, bf16) == "winograd":
-                    math = hipconv._MATH["bf16" if bf16 else "fp32"]
+                eng = hipconv.select(ops.CONV_FWD, B, Cin, H, W, m.out_channels, 3, 1, 1, 1, bf16)
+                if (bf16 or not torch.is_autocast_enabled()) and not m.weight.requires_grad and eng == "winograd":
+                    math = hipconv.conv_math(bf16)
                     key = (m.weight.data_ptr(), m.weight._version, x.device, math)
                     cache = getattr(m, "_ipsr_wino_filter", None)
                     valid = cache is not None and cache[0] == key
@@ -115,8 +115,7 @@ class Vgg16(torch.nn.Module):
                                              math=math, out_dtype=torch.bfloat16 if bf16 else torch.float32)
                     i += 3 if pool else 2
                     continue
-                if (bf16 or (x.dtype == torch.float32 and not torch.is_autocast_enabled())) and not pool and \
-                        hipconv.select(ops.CONV_FWD, B, Cin, H, W, m.out_channels, 3, 1, 1, 1, bf16) == "thin":
+                if (bf16 or (x.dtype == torch.float32 and not torch.is_autocast_enabled())) and not pool and eng == "thin":
                     x = ops.conv3x3_thin(ops.CONV_FWD, x.contiguous(), m.weight, (B, Cin, H, W), m.out_channels, bias=m.bias, relu=True,
                                          out_dtype=torch.bfloat16 if bf16 else torch.float32)                                        # conv1_1
                     i += 2

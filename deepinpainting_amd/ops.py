@@ -231,14 +231,14 @@ def backward(grad_out, bwd_index, triple_w, M, patch=1):
     return gin
 
 
-def _req_io(t, name):
-    """Activation tensors of the glue kernels: contiguous fp32 or bf16 on the GPU -> (tensor, io_bf16 flag)."""
+def _act(t, name):
+    """Activation operand of the glue and convolution kernels: contiguous fp32 or bf16 on the current device -> (tensor, is_bf16)."""
     if not torch.is_tensor(t) or not t.is_cuda:
         raise RuntimeError("%s must be a CUDA/HIP tensor" % name)
+    _on_current_device(t, name)
     if t.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
-    _on_current_device(t, name)
-    return (t if t.is_contiguous() else t.contiguous()), int(t.dtype == torch.bfloat16)
+    return (t if t.is_contiguous() else t.contiguous()), t.dtype == torch.bfloat16
 
 
 def _f32(t):
@@ -253,17 +253,14 @@ def bias_act_(x, bias, act="relu", slope=0.2, relu_into=None, relu_at=0, tickets
     batch sum of the bias gradient (the arrival counters live in the caller's memory, one set per autograd node)."""
     if not x.is_contiguous():
         raise RuntimeError("bias_act_ works in place and needs a contiguous tensor")
-    x, bf = _req_io(x, "x")
+    x, bf = _act(x, "x")
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
     if relu_into is None:
         _lib.check(_lib.lib().ipsr_bias_act(x.data_ptr(), _ptr(_f32(bias)), B, C, hw, ACT_CODE[act], float(slope), bf, _ptr(tickets), _stream()),
                    "ipsr_bias_act")
         return x
-    _check_wide(relu_into, x, "bias_act_: `relu_into`")
-    if relu_at < 0 or relu_at + C > relu_into.shape[1]:
-        raise RuntimeError("bias_act_: channels [%d, %d) outside `relu_into` %s" % (relu_at, relu_at + C, tuple(relu_into.shape)))
-    y2p, y2bs = _slot(relu_into, relu_at, hw)
+    y2p, y2bs = _wide_slot(relu_into, x, relu_at, C, hw, "bias_act_: `relu_into`")
     _lib.check(_lib.lib().ipsr_bias_act_skip(x.data_ptr(), _ptr(_f32(bias)), B, C, hw, ACT_CODE[act], float(slope), bf, y2p, y2bs, _ptr(tickets),
                                              _stream()), "ipsr_bias_act_skip")
     return x
@@ -288,6 +285,14 @@ def _check_wide(wide, x, what):
         raise RuntimeError("%s %s does not extend %s along the channels" % (what, tuple(wide.shape), tuple(x.shape)))
 
 
+def _wide_slot(wide, x, at, C, hw, what):
+    """`_slot` of the channels [at, at + C) of `wide`, a contiguous tensor that extends x along the channels."""
+    _check_wide(wide, x, what)
+    if at < 0 or at + C > wide.shape[1]:
+        raise RuntimeError("%s: channels [%d, %d) outside %s" % (what, at, at + C, tuple(wide.shape)))
+    return _slot(wide, at, hw)
+
+
 def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_at=0, relu_into=None, relu_at=0, return_tickets=False):
     """y = act(InstanceNorm(x + bias[c]) * gamma[c] + beta[c]) -> (y, mean [B*C], rstd [B*C]); x contiguous fp32 / bf16 [B,C,H,W].
     return_tickets: also return tickets [C] int32, the arrival counters of the backward's in-launch batch sums, zeroed by this
@@ -295,7 +300,7 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
     into / into_at: a contiguous [B,Ctot,H,W] tensor whose channels [into_at, into_at + C) receive y (a skip concatenation written
     in place); the returned y is then `into` itself.  relu_into / relu_at: a second destination of the same kind that receives
     relu(normalised value) — the skip half of the CHILD level's concatenated tensor."""
-    x, bf = _req_io(x, "x")
+    x, bf = _act(x, "x")
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
     # one allocation: mean [B*C] | rstd [B*C] | the C ticket words of the backward's in-launch batch sums, zeroed by this launch
@@ -308,19 +313,13 @@ def instnorm_act_forward(x, bias, gamma, beta, eps, act, slope, into=None, into_
                                                         rstd.data_ptr(), tickets.data_ptr(), _stream()), "ipsr_instnorm_act_forward")
         return (y, mean, rstd, tickets) if return_tickets else (y, mean, rstd)
     if into is not None:
-        _check_wide(into, x, "instnorm_act_forward: `into`")
-        if into_at < 0 or into_at + C > into.shape[1]:
-            raise RuntimeError("instnorm_act_forward: channels [%d, %d) outside `into` %s" % (into_at, into_at + C, tuple(into.shape)))
-        y, (yp, ybs) = into, _slot(into, into_at, hw)
+        y, (yp, ybs) = into, _wide_slot(into, x, into_at, C, hw, "instnorm_act_forward: `into`")
     else:
         y = _empty(x.shape, x.dtype, x.device)
         yp, ybs = y.data_ptr(), C * hw
     y2p, y2bs = None, 0
     if relu_into is not None:
-        _check_wide(relu_into, x, "instnorm_act_forward: `relu_into`")
-        if relu_at < 0 or relu_at + C > relu_into.shape[1]:
-            raise RuntimeError("instnorm_act_forward: channels [%d, %d) outside `relu_into` %s" % (relu_at, relu_at + C, tuple(relu_into.shape)))
-        y2p, y2bs = _slot(relu_into, relu_at, hw)
+        y2p, y2bs = _wide_slot(relu_into, x, relu_at, C, hw, "instnorm_act_forward: `relu_into`")
     _lib.check(_lib.lib().ipsr_instnorm_act_forward_slice(x.data_ptr(), _ptr(_f32(bias)), _ptr(_f32(gamma)), _ptr(_f32(beta)), float(eps),
                                                           ACT_CODE[act], float(slope), B, C, hw, bf, yp, ybs, y2p, y2bs,
                                                           mean.data_ptr(), rstd.data_ptr(), tickets.data_ptr(), _stream()),
@@ -334,7 +333,7 @@ def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_af
     the gradient of the relu'd second output of the forward (channels [dy2_at, dy2_at + C) of a wide tensor), added inside the kernel.
     tickets: the int32 [C] words `instnorm_act_forward(..., return_tickets=True)` returned (None: fresh zeroed words are allocated
     here; they are never looked up behind `mean` / `rstd`)."""
-    x, bf = _req_io(x, "x")
+    x, bf = _act(x, "x")
     B, C = x.shape[0], x.shape[1]
     hw = x.numel() // (B * C)
     if tickets is None:
@@ -342,7 +341,7 @@ def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_af
     elif tickets.dtype != torch.int32 or tickets.numel() != C or not tickets.is_contiguous() or tickets.device != x.device:
         raise RuntimeError("instnorm_act_backward: `tickets` must be the contiguous int32 [%d] words of the forward on %s" % (C, x.device))
     tick = tickets.data_ptr()
-    dy, _ = _req_io(dy.to(x.dtype), "grad_output")
+    dy, _ = _act(dy.to(x.dtype), "grad_output")
     dx = _empty(x.shape, x.dtype, x.device)
     part = _empty((3, B, C), dtype=torch.float32, device=x.device)
     # the batch sums of the per-plane partials are written by the same launch (the last plane of each channel to finish)
@@ -362,11 +361,8 @@ def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_af
         yp, ybs = _slot(y, at if y.shape[1] != C else 0, hw)
         d2p, d2bs = None, 0
         if dy2 is not None:
-            dy2, _ = _req_io(dy2.to(x.dtype), "second grad_output")
-            _check_wide(dy2, x, "instnorm_act_backward: second grad_output")
-            if dy2_at < 0 or dy2_at + C > dy2.shape[1]:
-                raise RuntimeError("instnorm_act_backward: channels [%d, %d) outside the second gradient %s" % (dy2_at, dy2_at + C, tuple(dy2.shape)))
-            d2p, d2bs = _slot(dy2, dy2_at, hw)
+            dy2, _ = _act(dy2.to(x.dtype), "second grad_output")
+            d2p, d2bs = _wide_slot(dy2, x, dy2_at, C, hw, "instnorm_act_backward: second grad_output")
         _lib.check(L.ipsr_instnorm_act_backward_slice(dyp, dybs, d2p, d2bs, yp, ybs, x.data_ptr(), _ptr(_f32(bias)),
                                                       _ptr(_f32(gamma)), mean.data_ptr(), rstd.data_ptr(), ACT_CODE[act], float(slope), B, C, hw, bf,
                                                       dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), part[2].data_ptr(),
@@ -378,7 +374,7 @@ def instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_af
 def bias_act_backward(dy, y, act, slope, need_bias, dy2=None, dy2_at=0, tickets=None):
     """dx = dy * act'(y) (+ dy2[:, dy2_at : dy2_at + C] * relu'(y): the gradient of bias_act_'s second output), dbias [C] | None.
     tickets: the int32 [C] tensor the forward `bias_act_` zeroed (None: fresh zeroed words are allocated here)."""
-    dy, bf = _req_io(dy.to(y.dtype), "grad_output")
+    dy, bf = _act(dy.to(y.dtype), "grad_output")
     B, C = y.shape[0], y.shape[1]
     hw = y.numel() // (B * C)
     dx = _empty(y.shape, y.dtype, y.device)
@@ -390,11 +386,8 @@ def bias_act_backward(dy, y, act, slope, need_bias, dy2=None, dy2_at=0, tickets=
         _lib.check(_lib.lib().ipsr_bias_act_backward(dy.data_ptr(), y.data_ptr(), ACT_CODE[act], float(slope), B, C, hw, bf, dx.data_ptr(),
                                                      _ptr(part), _ptr(sums), _ptr(tickets), _stream()), "ipsr_bias_act_backward")
     else:
-        dy2, _ = _req_io(dy2.to(y.dtype), "second grad_output")
-        _check_wide(dy2, y, "bias_act_backward: second grad_output")
-        if dy2_at < 0 or dy2_at + C > dy2.shape[1]:
-            raise RuntimeError("bias_act_backward: channels [%d, %d) outside the second gradient %s" % (dy2_at, dy2_at + C, tuple(dy2.shape)))
-        d2p, d2bs = _slot(dy2, dy2_at, hw)
+        dy2, _ = _act(dy2.to(y.dtype), "second grad_output")
+        d2p, d2bs = _wide_slot(dy2, y, dy2_at, C, hw, "bias_act_backward: second grad_output")
         _lib.check(_lib.lib().ipsr_bias_act_backward_skip(dy.data_ptr(), d2p, d2bs, y.data_ptr(), ACT_CODE[act], float(slope), B, C, hw, bf,
                                                           dx.data_ptr(), _ptr(part), _ptr(sums), _ptr(tickets), _stream()),
                    "ipsr_bias_act_backward_skip")
@@ -403,8 +396,8 @@ def bias_act_backward(dy, y, act, slope, need_bias, dy2=None, dy2_at=0, tickets=
 
 def cat_relu_forward(y, x):
     """relu(torch.cat([y, x], 1)) in one pass; y [B,C1,H,W], x [B,C2,H,W] contiguous, same fp32/bf16 dtype."""
-    y, bf = _req_io(y, "y")
-    x, bf2 = _req_io(x, "x")
+    y, bf = _act(y, "y")
+    x, bf2 = _act(x, "x")
     if bf != bf2 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:]:
         raise RuntimeError("cat_relu: mismatched operands %s %s / %s %s" % (tuple(y.shape), y.dtype, tuple(x.shape), x.dtype))
     B, C1, C2 = y.shape[0], y.shape[1], x.shape[1]
@@ -418,8 +411,8 @@ def cat_relu_forward(y, x):
 def cat_relu_skip_half_(out, x):
     """out[:, C1:] = relu(x) for a contiguous out [B,C1+C2,H,W] whose first C1 channels are already written (instnorm_act_forward
     with `into`): the skip half of relu(torch.cat([y, x], 1))."""
-    x, bf = _req_io(x, "x")
-    out, bf2 = _req_io(out, "out")
+    x, bf = _act(x, "x")
+    out, bf2 = _act(out, "out")
     B, C2 = x.shape[0], x.shape[1]
     C1 = out.shape[1] - C2
     if bf != bf2 or out.shape[0] != B or C1 < 1 or out.shape[2:] != x.shape[2:]:
@@ -432,7 +425,7 @@ def cat_relu_skip_half_(out, x):
 def cat_relu_backward(grad_out, out, C1, skip_half_only=False):
     """-> (dy [B,C1,..] | None, dx [B,C2,..]): the ReLU mask from `out`, the channel slices as contiguous tensors; skip_half_only: dy is
     not produced (its consumer reads grad_out's slice in place)."""
-    g, bf = _req_io(grad_out.to(out.dtype), "grad_output")
+    g, bf = _act(grad_out.to(out.dtype), "grad_output")
     B, C = out.shape[0], out.shape[1]
     C2 = C - C1
     hw = out.numel() // (B * C)
@@ -445,7 +438,7 @@ def cat_relu_backward(grad_out, out, C1, skip_half_only=False):
 
 def bias_relu_pool2(x, bias):
     """max_pool2d(relu(x + bias[c]), 2, 2) of a contiguous fp32 [B,C,H,W] tensor in one pass."""
-    x, bf = _req_io(x, "x")
+    x, bf = _act(x, "x")
     B, C, H, W = x.shape
     y = _empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
     _lib.check(_lib.lib().ipsr_bias_relu_pool2(x.data_ptr(), _ptr(_f32(bias)), B, C, H, W, bf, y.data_ptr(), _stream()),
@@ -461,20 +454,35 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3}
 
 
-def _act(t, name):
-    """activation operand: contiguous fp32 or bf16 on the current device -> (tensor, is_bf16)"""
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA/HIP tensor" % name)
-    _on_current_device(t, name)
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
-    return (t if t.is_contiguous() else t.contiguous()), t.dtype == torch.bfloat16
-
-
 def _io_code(in_bf16, out_dtype):
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("out_dtype must be float32 or bfloat16")
     return int(bool(in_bf16)) | (2 if out_dtype == torch.bfloat16 else 0)
+
+
+def _data_pass_shapes(op, in_shape, Cout, k, out_hw):
+    """-> (input, weight, result) shapes of a forward / input-gradient pass in the MODULE's terms: `in_shape` = (B, Cin, H, W) of the
+    module's input whatever the op, out_hw = (Ho, Wo) of its output; the pass reads x (forward ops) or dy (backward-data ops)."""
+    B, Cin, H, W = in_shape
+    xs, ys = (B, Cin, H, W), (B, Cout) + out_hw
+    wsh = (Cout, Cin, k, k) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, k, k)
+    return (xs, wsh, ys) if op in (CONV_FWD, CONVT_FWD) else (ys, wsh, xs)
+
+
+def _result(out, shape, dtype, device, what):
+    """The tensor a front-end writes: a fresh one, or the caller's `out` (e.g. a slice of a gradient bucket) once it is checked."""
+    if out is None:
+        return _empty(shape, dtype, device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != device:
+        raise RuntimeError("%s: `out` must be a contiguous %s %s tensor on %s" % (what, dtype, tuple(shape), device))
+    return out
+
+
+def _probed_workspace(L, nbytes, device, what, args):
+    """The scratch buffer for the answer `nbytes` of a workspace query; 0 = the library does not implement the shape (`what % args`)."""
+    if nbytes == 0:
+        raise NotImplementedError("%s is not implemented: %s" % (what % args, L.ipsr_last_error().decode("utf-8", "replace")))
+    return _workspace(nbytes, device)
 
 
 def conv_out_dim(op, n, k, stride, pad, dil):
@@ -495,18 +503,13 @@ def conv2d(op, inp, weight, in_shape, Cout, k, stride, pad, dil):
     Ho, Wo = conv_out_dim(op, H, k, stride, pad, dil), conv_out_dim(op, W, k, stride, pad, dil)
     inp = _req(inp, torch.float32, "conv input")
     weight = _req(weight, torch.float32, "conv weight")
-    fwd = op in (CONV_FWD, CONVT_FWD)
-    want_in = (B, Cin, H, W) if fwd else (B, Cout, Ho, Wo)
-    want_w = (Cout, Cin, k, k) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, k, k)
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, k, (Ho, Wo))
     if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
         raise RuntimeError("conv2d op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
-    out = _empty((B, Cout, Ho, Wo) if fwd else (B, Cin, H, W), dtype=torch.float32, device=inp.device)
+    out = _empty(oshape, dtype=torch.float32, device=inp.device)
     L = _lib.lib()
-    nbytes = L.ipsr_conv2d_workspace_bytes(op, B, Cin, H, W, Cout, k, stride, pad, dil)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv2d: op %d with k=%d stride=%d pad=%d dil=%d, Cin=%d Cout=%d is not implemented: %s"
-                                  % (op, k, stride, pad, dil, Cin, Cout, L.ipsr_last_error().decode("utf-8", "replace")))
-    ws = _workspace(nbytes, inp.device)
+    ws = _probed_workspace(L, L.ipsr_conv2d_workspace_bytes(op, B, Cin, H, W, Cout, k, stride, pad, dil), inp.device,
+                           "ipsr_conv2d: op %d with k=%d stride=%d pad=%d dil=%d, Cin=%d Cout=%d", (op, k, stride, pad, dil, Cin, Cout))
     _lib.check(L.ipsr_conv2d(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, k, stride, pad, dil,
                              ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv2d")
     return out
@@ -537,8 +540,7 @@ def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, 
     weight = _req(weight, torch.float32, "conv weight")
     out_dtype = out_dtype or inp.dtype
     fwd = op in (CONV_FWD, CONVT_FWD)
-    want_in = (B, Cin, H, W) if fwd else (B, Cout, H, W)
-    want_w = (Cout, Cin, 3, 3) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, 3, 3)
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
     if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
         raise RuntimeError("conv3x3_winograd op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
     epi = _EPILOGUE[epilogue]
@@ -546,16 +548,11 @@ def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, 
         raise ValueError("conv3x3_winograd: an epilogue only makes sense on a forward op")
     if epi == 2 and (H % 2 or W % 2):
         raise RuntimeError("conv3x3_winograd: relu_pool needs even extents, got %dx%d" % (H, W))
-    kout = Cout if fwd else Cin
-    oshape = (B, kout, H // 2, W // 2) if epi == 2 else (B, kout, H, W)
-    out = _empty(oshape, dtype=out_dtype, device=inp.device)
+    out = _empty((B, Cout, H // 2, W // 2) if epi == 2 else oshape, dtype=out_dtype, device=inp.device)      # (an epilogue: a forward op)
     L = _lib.lib()
-    nbytes = L.ipsr_conv3x3_winograd_workspace_bytes(op, B, Cin, H, W, Cout)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv3x3_winograd: op %d Cin=%d Cout=%d is not implemented" % (op, Cin, Cout))
+    ws = _probed_workspace(L, L.ipsr_conv3x3_winograd_workspace_bytes(op, B, Cin, H, W, Cout), inp.device, "ipsr_conv3x3_winograd: op %d Cin=%d Cout=%d", (op, Cin, Cout))
     if filter_cache is not None and filter_cache.numel() != L.ipsr_conv3x3_winograd_filter_floats(op, Cin, Cout):
         raise RuntimeError("conv3x3_winograd: filter_cache has the wrong size")
-    ws = _workspace(nbytes, inp.device)
     _lib.check(L.ipsr_conv3x3_winograd_mp(op, inp.data_ptr(), weight.data_ptr(), _ptr(_f32(bias)), epi, _ptr(filter_cache),
                                           int(bool(filter_cache_valid)), out.data_ptr(), B, Cin, H, W, Cout, MATH_CODE[math], _io_code(in_bf, out_dtype),
                                           ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_winograd_mp")
@@ -599,16 +596,14 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
     weight = _req(weight, torch.float32, "conv weight")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise TypeError("conv3x3_bf16 writes bf16 or fp32, not %s" % out_dtype)
-    fwd = op in (CONV_FWD, CONVT_FWD)
-    want_in = (B, Cin, H, W) if fwd else (B, Cout, H, W)
-    want_w = (Cout, Cin, 3, 3) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, 3, 3)
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
     if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
         raise RuntimeError("conv3x3_bf16 op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
     L = _lib.lib()
     nbytes = L.ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout)
     if nbytes == 0:
-        raise NotImplementedError("ipsr_conv3x3_bf16: op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), _lib.lib().ipsr_last_error().decode("utf-8", "replace")))
-    out = _empty((B, Cout if fwd else Cin, H, W), dtype=out_dtype, device=inp.device)
+        raise NotImplementedError("ipsr_conv3x3_bf16: op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
+    out = _empty(oshape, dtype=out_dtype, device=inp.device)
     valid = 0
     if keep_packed:
         packs = _packs_of(weight if pack_key is None else pack_key)
@@ -645,12 +640,9 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
     if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
         raise RuntimeError("conv4x4s2_bf16 mode %d: input %s / weight %s do not match %s / %s" % (mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
     L = _lib.lib()
-    nbytes = L.ipsr_conv4x4s2_bf16_workspace_bytes(mode, B, Kc, Cf, nh, nw)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv4x4s2_bf16: mode %d on %s is not implemented (%s)" % (mode, (B, Kc, Cf, nh, nw), L.ipsr_last_error().decode("utf-8", "replace")))
     oshape = (B, Kc, nh, nw) if mode == S2_FINE_TO_COARSE else (B, Cf, 2 * nh, 2 * nw)
     out = _empty(oshape, dtype=out_dtype, device=inp.device)
-    ws = _workspace(nbytes, inp.device)
+    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_workspace_bytes(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_conv4x4s2_bf16: mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
     _lib.check(L.ipsr_conv4x4s2_bf16(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, int(out_dtype == torch.bfloat16),
                                      ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4s2_bf16")
     return out
@@ -669,15 +661,9 @@ def conv4x4s2_bf16_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
         raise TypeError("conv4x4s2_bf16_wrw reads bf16 tensors")
     if tuple(fine.shape) != (B, Cf, 2 * nh, 2 * nw) or tuple(coarse.shape) != (B, Kc, nh, nw):
         raise RuntimeError("conv4x4s2_bf16_wrw: fine %s / coarse %s do not match %s / %s" % (tuple(fine.shape), tuple(coarse.shape), (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)))
-    shape = (Kc, Cf, 4, 4)
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != fine.device):
-        raise RuntimeError("conv4x4s2_bf16_wrw: `out` must be a contiguous fp32 %s tensor on %s" % (shape, fine.device))
     L = _lib.lib()
-    nbytes = L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv4x4s2_bf16_wrw: %s is not implemented (%s)" % ((B, Kc, Cf, nh, nw), L.ipsr_last_error().decode("utf-8", "replace")))
-    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=fine.device)
-    ws = _workspace(nbytes, fine.device)
+    dw = _result(out, (Kc, Cf, 4, 4), torch.float32, fine.device, "conv4x4s2_bf16_wrw")
+    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw), fine.device, "ipsr_conv4x4s2_bf16_wrw: %s", ((B, Kc, Cf, nh, nw),))
     _lib.check(L.ipsr_conv4x4s2_bf16_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
                "ipsr_conv4x4s2_bf16_wrw")
     return dw
@@ -697,15 +683,9 @@ def conv3x3_bf16_wrw(transposed, x, dy, Cout, out=None):
     B, Cin, H, W = x.shape
     if tuple(dy.shape) != (B, Cout, H, W):
         raise RuntimeError("conv3x3_bf16_wrw: grad_output %s does not match %s" % (tuple(dy.shape), (B, Cout, H, W)))
-    shape = (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3)
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
-        raise RuntimeError("conv3x3_bf16_wrw: `out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
     L = _lib.lib()
-    nbytes = L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv3x3_bf16_wrw: %s is not implemented (%s)" % ((B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
-    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=x.device)
-    ws = _workspace(nbytes, x.device)
+    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_bf16_wrw")
+    ws = _probed_workspace(L, L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device, "ipsr_conv3x3_bf16_wrw: %s", ((B, Cin, H, W, Cout),))
     _lib.check(L.ipsr_conv3x3_bf16_wrw(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
                                        _stream()), "ipsr_conv3x3_bf16_wrw")
     return dw
@@ -746,15 +726,10 @@ def conv4x4_dilated_winograd(mode, a, b, in_shape, Cout, out=None, geom=GEOM_K4_
     want = {0: (xs, wsh, ys), 1: (ys, wsh, xs), 2: (xs, ys, wsh)}[mode]
     if tuple(a.shape) != want[0] or tuple(b.shape) != want[1]:
         raise RuntimeError("conv4x4_winograd mode %d: operands %s / %s do not match %s / %s" % (mode, tuple(a.shape), tuple(b.shape), want[0], want[1]))
-    if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != res_dtype or not out.is_contiguous() or out.device != a.device):
-        raise RuntimeError("conv4x4_winograd: `out` must be a contiguous %s %s tensor on %s" % (res_dtype, tuple(want[2]), a.device))
-    if out is None:
-        out = _empty(want[2], dtype=res_dtype, device=a.device)
+    out = _result(out, want[2], res_dtype, a.device, "conv4x4_winograd")
     L = _lib.lib()
-    nbytes = L.ipsr_conv4x4_winograd_workspace_bytes(geom, mode, B, Cin, H, W, Cout)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv4x4_winograd: geometry %d mode %d Cin=%d Cout=%d %dx%d is not implemented" % (geom, mode, Cin, Cout, H, W))
-    ws = _workspace(nbytes, a.device)
+    ws = _probed_workspace(L, L.ipsr_conv4x4_winograd_workspace_bytes(geom, mode, B, Cin, H, W, Cout), a.device,
+                           "ipsr_conv4x4_winograd: geometry %d mode %d Cin=%d Cout=%d %dx%d", (geom, mode, Cin, Cout, H, W))
     _lib.check(L.ipsr_conv4x4_winograd_mp(geom, mode, a.data_ptr(), b.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, MATH_CODE[math],
                                           _io_code(a_bf, res_dtype), ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4_winograd_mp")
     return out
@@ -784,15 +759,10 @@ def conv4x4s2_winograd(mode, a, b, B, Kc, Cf, nh, nw, out=None, math=None, out_d
     want = {0: (fine, wsh, coarse), 1: (coarse, wsh, fine), 2: (fine, coarse, wsh)}[mode]
     if tuple(a.shape) != want[0] or tuple(b.shape) != want[1]:
         raise RuntimeError("conv4x4s2_winograd mode %d: operands %s / %s do not match %s / %s" % (mode, tuple(a.shape), tuple(b.shape), want[0], want[1]))
-    if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != res_dtype or not out.is_contiguous() or out.device != a.device):
-        raise RuntimeError("conv4x4s2_winograd: `out` must be a contiguous %s %s tensor on %s" % (res_dtype, tuple(want[2]), a.device))
-    if out is None:
-        out = _empty(want[2], dtype=res_dtype, device=a.device)
+    out = _result(out, want[2], res_dtype, a.device, "conv4x4s2_winograd")
     L = _lib.lib()
-    nbytes = L.ipsr_conv4x4s2_winograd_workspace_bytes(mode, B, Kc, Cf, nh, nw)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv4x4s2_winograd: mode %d Kc=%d Cf=%d %dx%d is not implemented" % (mode, Kc, Cf, nh, nw))
-    ws = _workspace(nbytes, a.device)
+    ws = _probed_workspace(L, L.ipsr_conv4x4s2_winograd_workspace_bytes(mode, B, Kc, Cf, nh, nw), a.device,
+                           "ipsr_conv4x4s2_winograd: mode %d Kc=%d Cf=%d %dx%d", (mode, Kc, Cf, nh, nw))
     _lib.check(L.ipsr_conv4x4s2_winograd_mp(mode, a.data_ptr(), b.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, MATH_CODE[math],
                                             _io_code(a_bf, res_dtype), ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4s2_winograd_mp")
     return out
@@ -837,7 +807,7 @@ def conv_to_one_wrw(x, dy, K, pad, out=None):
     B, C, H, W = x.shape
     if tuple(dy.shape) != (B, 1, H + 2 * pad - K + 1, W + 2 * pad - K + 1):
         raise RuntimeError("conv_to_one_wrw: grad_output %s does not match input %s, k=%d, pad=%d" % (tuple(dy.shape), tuple(x.shape), K, pad))
-    dw = out if out is not None else _empty((1, C, K, K), dtype=torch.float32, device=x.device)
+    dw = _result(out, (1, C, K, K), torch.float32, x.device, "conv_to_one_wrw")
     _lib.check(_lib.lib().ipsr_conv_to_one(2, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, C, H, W, K, int(pad), None, 0, _stream()),
                "ipsr_conv_to_one")
     return dw
@@ -852,21 +822,17 @@ def conv3x3_thin(op, inp, weight, in_shape, Cout, bias=None, relu=False, out=Non
     inp, _ = _act(inp, "input")
     weight = _req(weight, torch.float32, "weight")
     out_dtype = out_dtype or (out.dtype if out is not None else inp.dtype)
-    fwd = op in (CONV_FWD, CONVT_FWD)
-    I, O = (Cin, Cout) if fwd else (Cout, Cin)
-    if tuple(inp.shape) != (B, I, H, W):
-        raise RuntimeError("conv3x3_thin: input %s does not match %s" % (tuple(inp.shape), (B, I, H, W)))
-    want_w = (Cout, Cin, 3, 3) if op in (CONV_FWD, CONV_BWD_DATA) else (Cin, Cout, 3, 3)
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
+    I, O = want_in[1], oshape[1]
+    if tuple(inp.shape) != want_in:
+        raise RuntimeError("conv3x3_thin: input %s does not match %s" % (tuple(inp.shape), want_in))
     if tuple(weight.shape) != want_w:
         raise RuntimeError("conv3x3_thin op %d: weight %s does not match %s" % (op, tuple(weight.shape), want_w))
     if not thin_supported(op, Cin, H, W, Cout):
         raise NotImplementedError("conv3x3_thin op %d: Cin=%d Cout=%d %dx%d is not a thin-layer shape" % (op, Cin, Cout, H, W))
     so, si, flip = {CONV_FWD: (Cin * 9, 9, 0), CONV_BWD_DATA: (9, Cin * 9, 1), CONVT_FWD: (9, Cout * 9, 1), CONVT_BWD_DATA: (Cout * 9, 9, 0)}[op]
     io = _io_code(inp.dtype == torch.bfloat16, out_dtype)
-    if out is None:
-        out = _empty((B, O, H, W), dtype=out_dtype, device=inp.device)
-    elif tuple(out.shape) != (B, O, H, W) or out.dtype != out_dtype or not out.is_contiguous() or out.device != inp.device:
-        raise RuntimeError("conv3x3_thin: `out` must be a contiguous %s %s tensor on %s" % (out_dtype, (B, O, H, W), inp.device))
+    out = _result(out, oshape, out_dtype, inp.device, "conv3x3_thin")
     few2many = I in (3, 6) and O % 16 == 0
     _lib.check(_lib.lib().ipsr_conv3x3_thin_io(0 if few2many else 1, inp.data_ptr(), weight.data_ptr(), _ptr(_f32(bias)) if bias is not None else None,
                                                int(bool(relu)), out.data_ptr(), B, I, O, H, W, so, si, flip, io, _stream()), "ipsr_conv3x3_thin_io")
@@ -885,11 +851,8 @@ def conv3x3_thin_wrw(transposed, x, dy, out=None):
     Cb, Cs = big.shape[1], small.shape[1]
     L = _lib.lib()
     if Cs in (3, 6):
-        g = out if out is not None else _empty(wshape, dtype=torch.float32, device=x.device)
-        nbytes = L.ipsr_conv3x3_thin_wrw_workspace_bytes(B, Cb, Cs, H, W)
-        if nbytes == 0:
-            raise NotImplementedError("ipsr_conv3x3_thin_wrw: Cb=%d Cs=%d %dx%d is not implemented" % (Cb, Cs, H, W))
-        ws = _workspace(nbytes, x.device)
+        g = _result(out, wshape, torch.float32, x.device, "conv3x3_thin_wrw")
+        ws = _probed_workspace(L, L.ipsr_conv3x3_thin_wrw_workspace_bytes(B, Cb, Cs, H, W), x.device, "ipsr_conv3x3_thin_wrw: Cb=%d Cs=%d %dx%d", (Cb, Cs, H, W))
         io = int(big.dtype == torch.bfloat16) | (2 if small.dtype == torch.bfloat16 else 0)
         _lib.check(L.ipsr_conv3x3_thin_wrw_io(big.data_ptr(), small.data_ptr(), g.data_ptr(), B, Cb, Cs, H, W, io, ws.data_ptr(), ws.numel(), _stream()),
                    "ipsr_conv3x3_thin_wrw_io")
@@ -962,13 +925,9 @@ def conv_thin_wrw_mfma(transposed, x, dy, k, stride, out=None):
     if tuple(small.shape) != (B, Cs, Hb * stride, Wb * stride):
         raise RuntimeError("conv_thin_wrw_mfma: narrow tensor %s does not match wide %s at stride %d" % (tuple(small.shape), tuple(big.shape), stride))
     L = _lib.lib()
-    nbytes = L.ipsr_conv_thin_wrw_mfma_workspace_bytes(B, Kb, Cs, Hb, Wb, k, stride)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv_thin_wrw_mfma: Kb=%d Cs=%d %dx%d k%d s%d is not implemented" % (Kb, Cs, Hb, Wb, k, stride))
-    g = out if out is not None else _empty((Kb, Cs, k, k), dtype=torch.float32, device=x.device)
-    if tuple(g.shape) != (Kb, Cs, k, k) or g.dtype != torch.float32 or not g.is_contiguous():
-        raise RuntimeError("conv_thin_wrw_mfma: `out` must be a contiguous fp32 %s tensor" % ((Kb, Cs, k, k),))
-    ws = _workspace(nbytes, x.device)
+    g = _result(out, (Kb, Cs, k, k), torch.float32, x.device, "conv_thin_wrw_mfma")
+    ws = _probed_workspace(L, L.ipsr_conv_thin_wrw_mfma_workspace_bytes(B, Kb, Cs, Hb, Wb, k, stride), x.device,
+                           "ipsr_conv_thin_wrw_mfma: Kb=%d Cs=%d %dx%d k%d s%d", (Kb, Cs, Hb, Wb, k, stride))
     _lib.check(L.ipsr_conv_thin_wrw_mfma(big.data_ptr(), small.data_ptr(), g.data_ptr(), B, Kb, Cs, Hb, Wb, k, stride, int(big.dtype == torch.bfloat16) | (2 if small.dtype == torch.bfloat16 else 0),
                                          ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv_thin_wrw_mfma")
     return g
@@ -992,15 +951,10 @@ def conv_smallmap(op, a, b, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, out=N
     want = {SM_DATA: (coarse, wsh, fine), SM_WRW: (coarse, fine, wsh), SM_FWD: (fine, wsh, coarse)}[op]
     if tuple(a.shape) != want[0] or tuple(b.shape) != want[1]:
         raise RuntimeError("conv_smallmap op %d: operands %s / %s do not match %s / %s" % (op, tuple(a.shape), tuple(b.shape), want[0], want[1]))
-    if out is not None and (tuple(out.shape) != tuple(want[2]) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a.device):
-        raise RuntimeError("conv_smallmap: `out` must be a contiguous fp32 %s tensor on %s" % (tuple(want[2]), a.device))
-    if out is None:
-        out = _empty(want[2], dtype=torch.float32, device=a.device)
+    out = _result(out, want[2], torch.float32, a.device, "conv_smallmap")
     L = _lib.lib()
-    nbytes = L.ipsr_conv_smallmap_workspace_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv_smallmap: op %d R=%d Cq=%d %dx%d -> %dx%d k%d s%d p%d d%d is not implemented" % (op, R, Cq, Hf, Wf, Ho, Wo, k, stride, pad, dil))
-    ws = _workspace(nbytes, a.device)
+    ws = _probed_workspace(L, L.ipsr_conv_smallmap_workspace_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil), a.device,
+                           "ipsr_conv_smallmap: op %d R=%d Cq=%d %dx%d -> %dx%d k%d s%d p%d d%d", (op, R, Cq, Hf, Wf, Ho, Wo, k, stride, pad, dil))
     _lib.check(L.ipsr_conv_smallmap(op, a.data_ptr(), b.data_ptr(), out.data_ptr(), B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil,
                                     ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv_smallmap")
     return out
@@ -1017,10 +971,7 @@ def conv3x3_winograd_wrw(transposed, x, dy, Cout, out=None, math=None):
     B, Cin, H, W = x.shape
     if tuple(dy.shape) != (B, Cout, H, W):
         raise RuntimeError("conv3x3_winograd_wrw: grad_output %s does not match %s" % (tuple(dy.shape), (B, Cout, H, W)))
-    shape = (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3)
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
-        raise RuntimeError("conv3x3_winograd_wrw: `out` must be a contiguous fp32 %s tensor on %s" % (shape, x.device))
-    dw = out if out is not None else _empty(shape, dtype=torch.float32, device=x.device)
+    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_winograd_wrw")
     L = _lib.lib()
     ws = _workspace(L.ipsr_conv3x3_winograd_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device)
     _lib.check(L.ipsr_conv3x3_winograd_wrw_mp(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, MATH_CODE[math],

@@ -143,3 +143,80 @@ def test_conv_dispatcher_rules_on_the_host():
         hipconv._FORCE = was
         os.environ.pop("IPSR_NO_THIN", None)
         hipconv.reload_env()
+
+
+# ---- the whole selection, replayed against a recorded grid ----------------------------------------------------------------------------
+# tests/golden/engine_selection.json.gz holds what `select` / `select_wrw` answered over the grid below, once per setting of the A/B
+# switches: one character per grid point (the engine's index in "engines", base 36), in the order `_selection_grid` walks.  The answers
+# depend on the rules of models/hipconv.py AND on the library's workspace probes, so a pull request that re-routes or widens an engine
+# regenerates the file (IPSR_REGENERATE_ENGINE_SELECTION=1 python -m pytest tests/test_abi.py -k recorded_grid) and shows the difference.
+_SEL_FIXTURE = os.path.join(ROOT, "tests", "golden", "engine_selection.json.gz")
+_SEL_SWITCHES = ("IPSR_CONV_ENGINE", "IPSR_NO_SMALLMAP", "IPSR_NO_THIN", "IPSR_SMALLMAP_MAX_POS", "IPSR_BF16_ENGINES")
+_SEL_SETTINGS = (("default", {}), ("engine_miopen", {"IPSR_CONV_ENGINE": "miopen"}), ("engine_winograd", {"IPSR_CONV_ENGINE": "winograd"}),
+                 ("engine_direct", {"IPSR_CONV_ENGINE": "direct"}), ("no_smallmap", {"IPSR_NO_SMALLMAP": "1"}), ("no_thin", {"IPSR_NO_THIN": "1"}),
+                 ("bf16_all", {"IPSR_BF16_ENGINES": "all"}), ("bf16_none", {"IPSR_BF16_ENGINES": "none"}))
+_SEL_AXES = {"batch_bf16": [[8, False], [16, True], [16, False]],
+             "k_stride_pad_dil": [[3, 1, 1, 1], [4, 2, 1, 1], [4, 2, 3, 2], [4, 1, 1, 1]],
+             "channels": [1, 3, 6, 64, 128, 256, 512, 1024],             # Cin and Cout each
+             "extent": [1, 2, 4, 8, 16, 31, 32, 64, 128, 256],           # H = W
+             "pass": ["CONV_FWD", "CONV_BWD_DATA", "CONVT_FWD", "CONVT_BWD_DATA", "wrw", "wrw_transposed"]}
+_SEL_ENGINES = ["miopen", "winograd", "wino_dil", "wino_s2", "thin", "thin_f2m", "thin_mfma", "smallmap", "direct", "one", "bf16d"]
+
+
+def _selection_grid():
+    """-> one engine name per grid point, for the switches the environment holds right now (the caller has called reload_env)."""
+    from deepinpainting_amd import ops
+    from deepinpainting_amd.models import hipconv
+    out = []
+    for B, bf16 in _SEL_AXES["batch_bf16"]:
+        for k, stride, pad, dil in _SEL_AXES["k_stride_pad_dil"]:
+            for Cin in _SEL_AXES["channels"]:
+                for Cout in _SEL_AXES["channels"]:
+                    for H in _SEL_AXES["extent"]:
+                        for op in (ops.CONV_FWD, ops.CONV_BWD_DATA, ops.CONVT_FWD, ops.CONVT_BWD_DATA):
+                            out.append(hipconv.select(op, B, Cin, H, H, Cout, k, stride, pad, dil, bf16))
+                        for transposed in (False, True):
+                            out.append(hipconv.select_wrw(transposed, B, Cin, H, H, Cout, k, stride, pad, dil, bf16))
+    return out
+
+
+def test_engine_selection_matches_the_recorded_grid(built, monkeypatch):
+    """`select` / `select_wrw` over 46 080 (dtype, batch, geometry, channels, extent, pass) points x 8 switch settings answer what the
+    fixture recorded, entry by entry — pure host logic plus workspace probes, no kernel is launched.  The existing dispatcher tests pin
+    ~90 hand-picked shapes, nearly all under the default switches; this one pins the rest, so that moving the rules cannot move an answer."""
+    import gzip
+    import json
+    from deepinpainting_amd.models import hipconv
+    digits = "0123456789abcdefghijklmnopqrstuvwxyz"
+    monkeypatch.setattr(hipconv, "_FORCE", None)
+    got = {}
+    try:
+        for name, switches in _SEL_SETTINGS:
+            for var in _SEL_SWITCHES:
+                monkeypatch.delenv(var, raising=False)
+            for var, val in switches.items():
+                monkeypatch.setenv(var, val)
+            hipconv.reload_env()
+            got[name] = _selection_grid()
+    finally:
+        monkeypatch.undo()
+        hipconv.reload_env()
+    if os.environ.get("IPSR_REGENERATE_ENGINE_SELECTION") == "1":
+        doc = {"axes": _SEL_AXES, "engines": _SEL_ENGINES, "order": "nested loops over the axes in the order listed, `pass` innermost",
+               "settings": {name: "".join(digits[_SEL_ENGINES.index(e)] for e in got[name]) for name, _ in _SEL_SETTINGS}}
+        with open(_SEL_FIXTURE, "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", mtime=0, filename="") as z:
+            z.write(json.dumps(doc, sort_keys=True).encode("ascii"))
+    with gzip.open(_SEL_FIXTURE, "rb") as z:
+        doc = json.loads(z.read().decode("ascii"))
+    assert doc["axes"] == _SEL_AXES and sorted(doc["settings"]) == sorted(name for name, _ in _SEL_SETTINGS)
+    n = 1
+    for axis in ("batch_bf16", "k_stride_pad_dil", "channels", "channels", "extent", "pass"):
+        n *= len(_SEL_AXES[axis])
+    for name, _ in _SEL_SETTINGS:
+        want = [doc["engines"][digits.index(c)] for c in doc["settings"][name]]
+        assert len(want) == n == len(got[name]), (name, len(want), n, len(got[name]))
+        diff = [(i, want[i], got[name][i]) for i in range(n) if want[i] != got[name][i]]
+        assert not diff, "%s: %d of %d selections moved, first (grid index, recorded, now): %s" % (name, len(diff), n, diff[:8])
+    # a grid that misses an engine cannot pass silently: every engine the dispatcher knows occurs under the default switches
+    seen = set(doc["engines"][digits.index(c)] for c in doc["settings"]["default"])
+    assert seen == set(_SEL_ENGINES) == set(doc["engines"]), sorted(set(_SEL_ENGINES) - seen)

@@ -620,15 +620,16 @@ def test_split_bf16_winograd_arithmetic_all_families(math, io_bf16):
 # What each engine does to an fp32 operand on a call with a bf16 side (the reference is an fp32 MIOpen convolution of exactly what the
 # kernel multiplied; on an all-fp32 call nothing is rounded anywhere):
 #   engine      weights                                                          fp32 activation operand
-#   bf16d       rounded: csrc/conv_bf16.hip:95 (cb_pack_weights_kernel, (__bf16)v;  rounded: models/hipconv.py:403 / :461 (.to(bf16)
-#               the k4 s2 p1 form packs through the same kernel)                  before the kernel)
+#   bf16d       rounded: csrc/conv_bf16.hip:95 (cb_pack_weights_kernel, (__bf16)v;  rounded: models/hipconv.py `_bf16d_data` (.to(bf16)
+#               the k4 s2 p1 form packs through the same kernel)                  before the kernel; `_HipConv.backward` casts dy)
 #   thin_f2m    rounded: csrc/thin_conv.hip:470 (f2bf(w))                         rounded: the window gather feeds v_mfma_*_bf16
 #   thin        rounded: csrc/thin_conv.hip:47 / :98 (thin_rb when a side is bf16) rounded: csrc/thin_conv.hip:64 / :126
-#   thin_mfma   (weight gradient: does not read the weights)                      rounded: csrc/thin_conv.hip:355 (f2bf2), hipconv.py:465
+#   thin_mfma   (weight gradient: does not read the weights)                      rounded: csrc/thin_conv.hip:355 (f2bf2); `_thin_mfma_wrw`
 #   winograd, wino_dil, wino_s2 (bf16x3)
 #               split, not rounded: csrc/winograd.hip:123-126 (hi + lo bf16)      split as well; the weight gradient reads x cast to
-#                                                                                 dy's dtype (hipconv.py:461)
-#   one, smallmap   fp32 weights                                                  exact fp32 copies (hipconv.py:411-413, :475-478)
+#                                                                                 dy's dtype (`_run_wrw`, `_ENGINES[...].wrw_x_as_dy`)
+#   one, smallmap   fp32 weights                                                  exact fp32 copies (`_run_data` / `_run_wrw`,
+#                                                                                 `_ENGINES[...].fp32_copies`)
 _ROUNDS_WEIGHTS = ("bf16d", "thin_f2m", "thin")
 _ROUNDS_INPUT = ("bf16d", "thin_f2m", "thin")                                    # forward / input gradient
 _WRW_KEEPS_X = ("one", "smallmap", "miopen")                                    # weight gradient: every other engine reads x in bf16
