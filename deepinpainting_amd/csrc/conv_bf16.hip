@@ -36,6 +36,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((address_space(3))) s16x4* lds_s4_t;
+// LDS reads that run beside an LDS-DMA use ext-vector types: a HIP_vector_type (uint4) load is a struct copy that reaches the back end
+// without alias metadata, and hipcc then drains the DMA queue (s_waitcnt vmcnt(0)) in front of it — the prefetch stops overlapping.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CB_K = 128, CB_P = 256, CB_C = 16, CB_THREADS = 512, CB_MAXTAP = 9;
 // per-thread loop bounds of a stage, by pixels per tile (256 / 512): transposition blocks (4 channels x 16 pixels) per 16-lane group, and
@@ -77,8 +80,11 @@ struct CbGeom {
 // packed weights: Wp[kt][phase][cb][sub][t][cg][k & 127][c & 7] bf16 (zero for k >= K); source element (k, c, tap) at w[c * sc + k * sk + srctap]
 struct CbPack { int ntap, nsub, nphase, kt; int srctap[2][2][CB_MAXTAP]; };      // kt: rows per k tile (128 or 64); srctap[phase][sub][t]
 
+// SPLIT (the fp32-activation kernel below): two such images, hi = bf16(w) and, `lo_plane` uint4 further on, lo = bf16(w - hi) — the fp32
+// residual w - hi is exact (hi keeps w's leading 8 significand bits), so hi + lo carries 16.
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) cb_pack_weights_kernel(const float* __restrict__ w, int C, int K, long sc, long sk, CbPack pk,
-                                                              uint4* __restrict__ Wp, uint4* __restrict__ zero_page)
+                                                              uint4* __restrict__ Wp, uint4* __restrict__ zero_page, size_t lo_plane)
 {
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 4) zero_page[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     const int k = blockIdx.x * 256 + threadIdx.x;          // padded produced channel
@@ -87,19 +93,26 @@ __global__ void __launch_bounds__(256) cb_pack_weights_kernel(const float* __res
     const int ktiles = (K + pk.kt - 1) / pk.kt;
     if (k >= ktiles * pk.kt) return;
     const int tap = pk.srctap[phase][sub][t];
-    unsigned short h[8];
+    unsigned short h[8], l[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int c = c8 * 8 + e;
         const float v = k < K ? w[(long)c * sc + (long)k * sk + tap] : 0.0f;
         h[e] = __builtin_bit_cast(unsigned short, (__bf16)v);
+        if (SPLIT) l[e] = __builtin_bit_cast(unsigned short, (__bf16)(v - bf2f(h[e])));
     }
     uint4 o;
     o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
     o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
     const int kt = k / pk.kt, kl = k - kt * pk.kt, cb = c8 >> 1, cg = c8 & 1;
     const int ncb = C / CB_C;
-    Wp[((((((size_t)kt * pk.nphase + phase) * ncb + cb) * pk.nsub + sub) * pk.ntap + t) * 2 + cg) * pk.kt + kl] = o;
+    const size_t at = ((((((size_t)kt * pk.nphase + phase) * ncb + cb) * pk.nsub + sub) * pk.ntap + t) * 2 + cg) * pk.kt + kl;
+    Wp[at] = o;
+    if (SPLIT) {
+        o.x = l[0] | ((unsigned)l[1] << 16); o.y = l[2] | ((unsigned)l[3] << 16);
+        o.z = l[4] | ((unsigned)l[5] << 16); o.w = l[6] | ((unsigned)l[7] << 16);
+        Wp[lo_plane + at] = o;
+    }
 }
 
 // KT = produced channels per workgroup tile: 128 (waves 2 x 4, a wave 64 x 64), or 64 for layers that produce <= 64 channels (waves 1 x 8, a
@@ -499,7 +512,7 @@ static int cb_launch(const CbGeom& g, CbPack pk, const void* in, const float* w,
     uint4* Wp = zero_page + 16;
     pk.kt = g.kt;
     if (!pack_valid) {
-        cb_pack_weights_kernel<<<dim3(cdiv(g.ktiles * g.kt, 256), g.C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(w, g.C, g.K, sc, sk, pk, Wp, zero_page);
+        cb_pack_weights_kernel<false><<<dim3(cdiv(g.ktiles * g.kt, 256), g.C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(w, g.C, g.K, sc, sk, pk, Wp, zero_page, 0);
         if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
     }
     const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
@@ -579,6 +592,253 @@ int launch_conv_bf16_s2(int form, const void* in, const float* w, void* out, int
 }
 
 // =====================================================================================================================================
+// The same k3 s1 p1 form on FP32 tensors with SPLIT-bf16 operands ("direct_bf16x3", io code 2 of ipsr_conv3x3_bf16): every operand a is
+// taken as hi + lo, hi = bf16(a), lo = bf16(a - hi) (round to nearest even; a - hi is exact in fp32), and every product as
+// lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 — three MFMAs into the same fp32 accumulators, smallest terms first, lo*lo dropped.
+// bf16 x bf16 is exact in fp32, so what is lost per product is lo*lo and the two residuals: <= 3 * 2^-18 |a||b|.  No transform amplifies
+// it (the split-bf16 Winograd engines: ~1.4e-4 of the output scale; this: ~6e-6), there are no transform passes and no fp32-wide
+// intermediates in HBM: one launch per pass, NCHW fp32 in and out.
+//   * weights: the packing launch writes the image above twice (hi plane, lo plane); a stage's A tile is 2 x 18 KB, by LDS-DMA;
+//   * activations: a stage's 16 channels x (R + 2 rows) x full width go global -> registers -> split -> T: a lane loads 4 pixels of each of
+//     the 8 channels of a group as 16-byte vectors (32 registers in flight, issued ahead of the stage's multiplications), converts, and
+//     stores 16 bytes per pixel and plane into the position-major images T[plane][c group][row][x + halo][8 c].  No raw buffer, no
+//     ds_read_b64_tr_b16, no separate split pass; every tap's B fragment stays one aligned ds_read_b128 per plane.
+// Workgroup = 512 threads = 8 waves (1 x 8), tile 64 channels x 256 pixels, a wave owns 64 x 32: per tap 4 A + 2 B fragment reads for
+// 6 MFMAs.  LDS plan: A[2] = 2 x 36 KB (hi + lo, double-buffered) | T = ONE buffer of <= 48.4 KB (hi + lo; W = 256: 3 rows x 258 positions)
+// = 120.4 KB at most.  T has one buffer at every width (two would not fit at W = 256): the registers are the second one — the loads of stage
+// s + 1 fly during the multiplications of stage s, the conversion and the stores follow them between two barriers.
+// Small maps: the reduction cut of the bf16 kernel (fp32 partials behind the packed weights + cb_split_reduce_kernel).
+// Supported: W in {16 .. 256} a power of two, H a multiple of 256 / W, reduction channels a multiple of 16.
+constexpr int CX_K = 64, CX_A_BYTES = 2 * 9 * 2 * CX_K * 16;
+
+struct CxGeom {
+    int B, C, K, H, W, wshift;
+    int R, NR, PW, NPOS;        // image rows per tile, rows with halo, padded width, positions per (plane, c group)
+    int ktiles, ptiles, nstage, nsplit, sps;
+    int t_bytes;                // both planes
+    int tapoff[9];
+};
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_kernel(const float* __restrict__ in, const uint4* __restrict__ Wp, size_t lo_plane,
+                                                                   CxGeom g, float* __restrict__ out)
+{
+    constexpr int KT = CX_K, NTAP = 9;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | T
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    const int per_pt = g.ktiles * g.nsplit;
+    const int pt = L / per_pt, kps = L - pt * per_pt;
+    const int split = kps % g.nsplit, kt = kps / g.nsplit;
+    const int s_lo = split * g.sps, s_hi = min(g.nstage, s_lo + g.sps);
+    out += (size_t)split * g.B * g.K * g.H * g.W;
+    const int tiles_per_img = g.H / g.R;
+    const int b = pt / tiles_per_img, y0 = (pt - b * tiles_per_img) * g.R;
+    const size_t HW = (size_t)g.H * g.W;
+
+    // ---- stage-invariant addresses ------------------------------------------------------------------------------------------
+    // activation item = (c group, row, 4-pixel segment): at most 2 x 3 x 64 = 384 of them, one per thread
+    const int segs = g.W >> 2, nitem = 2 * g.NR * segs;
+    const int seg = tid % segs, row = (tid / segs) % g.NR, cg = min(tid / (segs * g.NR), 1);
+    const int yin = y0 - 1 + row;
+    const bool xlive = tid < nitem && (unsigned)yin < (unsigned)g.H;            // rows outside the image keep T's zeros
+    const float* gx = in + (((size_t)b * g.C + cg * 8) * g.H + (xlive ? yin : 0)) * g.W + seg * 4;
+    const size_t xstride = (size_t)CB_C * HW;
+    const int t_base = 2 * CX_A_BYTES, t_plane = 2 * g.NPOS * 16;
+    const int t_wr = t_base + (cg * g.NPOS + row * g.PW + seg * 4 + 1) * 16;
+    // A tile DMA: 2 planes x 18 pieces of 1 KiB, piece = wave + 8 j
+    constexpr int PPP = NTAP * KT / 32, NPIECE = 2 * PPP, APW = (NPIECE + 7) / 8;
+    const uint4* ga = Wp + (size_t)kt * g.nstage * (NTAP * 2 * KT) + lane;
+    const int a_off = (h * KT + r) * 16;
+    const int p = wave * 32 + r;
+    const int b_off = t_base + (h * g.NPOS + (p >> g.wshift) * g.PW + (p & (g.W - 1))) * 16;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][e] = 0.0f;
+
+    auto dma_a = [&](int buf, int stage) {
+        const uint4* src = ga + (size_t)stage * (NTAP * 2 * KT);
+#pragma unroll
+        for (int j = 0; j < APW; ++j) {
+            const int piece = wave + 8 * j;
+            if (piece < NPIECE) {
+                const uint4* s = piece < PPP ? src + piece * 64 : src + lo_plane + (piece - PPP) * 64;
+                __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(lds + buf * CX_A_BYTES + piece * 1024), 16, 0, 0);
+            }
+        }
+    };
+    f32x4 xr[8];
+    auto load_x = [&](int stage) {
+        if (xlive) {
+            const float* src = gx + (size_t)stage * xstride;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) xr[c] = *reinterpret_cast<const f32x4*>(src + (size_t)c * HW);
+        }
+    };
+    auto split_store = [&]() {                                 // registers -> T (hi plane, lo plane)
+        if (xlive) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                unsigned hi[8], lo[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const float v = xr[c][i];
+                    hi[c] = __builtin_bit_cast(unsigned short, (__bf16)v);
+                    lo[c] = __builtin_bit_cast(unsigned short, (__bf16)(v - __uint_as_float(hi[c] << 16)));
+                }
+                u32x4 vh, vl;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { vh[c] = hi[2 * c] | (hi[2 * c + 1] << 16); vl[c] = lo[2 * c] | (lo[2 * c + 1] << 16); }
+                *reinterpret_cast<u32x4*>(lds + t_wr + i * 16) = vh;
+                *reinterpret_cast<u32x4*>(lds + t_wr + t_plane + i * 16) = vl;
+            }
+        }
+    };
+
+    // T starts as zeros: the halo columns and the rows outside the image are never written
+    for (int i = tid; i < g.t_bytes / 16; i += CB_THREADS) *reinterpret_cast<u32x4*>(lds + t_base + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    load_x(s_lo);
+    dma_a(0, s_lo);
+    __syncthreads();
+    split_store();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    for (int s = s_lo; s < s_hi; ++s) {
+        const int cur = (s - s_lo) & 1;
+        if (s + 1 < s_hi) {
+            load_x(s + 1);                                     // consumed behind this stage's multiplications
+            dma_a(cur ^ 1, s + 1);                             // A[nxt] was last read in stage s-1
+        }
+        const unsigned char* A = lds + cur * CX_A_BYTES + a_off;
+        const unsigned char* T = lds + b_off;
+        // the tap pipeline of conv_bf16_kernel: the six fragments of tap t + 1 are read behind tap t's first multiplication
+        bf16x8 fa[2][2][2], fb[2][2];                          // [set][plane][row tile], [set][plane]
+        auto load_tap = [&](int t, int set) {
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+                fa[set][pl][0] = *reinterpret_cast<const bf16x8*>(A + pl * (CX_A_BYTES / 2) + (t * 2 * KT) * 16);
+                fa[set][pl][1] = *reinterpret_cast<const bf16x8*>(A + pl * (CX_A_BYTES / 2) + (t * 2 * KT + 32) * 16);
+                fb[set][pl] = *reinterpret_cast<const bf16x8*>(T + pl * t_plane + g.tapoff[t] * 16);
+            }
+        };
+        load_tap(0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+#pragma unroll
+        for (int t = 0; t < NTAP; ++t) {
+            const int set = t & 1;
+            if (t + 1 < NTAP) load_tap(t + 1, set ^ 1);
+            // smallest terms first: lo(w) hi(x), hi(w) lo(x), hi(w) hi(x); the two row tiles alternate so that no MFMA waits for its predecessor
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][1][0], fb[set][0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][1][1], fb[set][0], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][0], fb[set][1], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][1], fb[set][1], acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][0], fb[set][0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][1], fb[set][0], acc[1], 0, 0, 0);
+            if (t + 1 < NTAP) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this stage's DMA and loads are the next stage's operands
+        __syncthreads();                                       // every wave is done reading T
+        if (s + 1 < s_hi) {
+            split_store();
+            __syncthreads();
+        }
+    }
+
+    // epilogue: lane = pixel, register = channel
+    const int py = y0 + (p >> g.wshift), px = p & (g.W - 1);
+    float* op = out + (size_t)b * g.K * HW + (size_t)py * g.W + px;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int k = kt * KT + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (k < g.K) op[(size_t)k * HW] = acc[i][e];
+        }
+}
+
+static int cx_geometry(int B, int C, int K, int H, int W, CxGeom* g)
+{
+    const char* who = "split-bf16 direct conv";
+    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d reduction channels are not a multiple of %d", who, C, CB_C);
+    if (W != 16 && W != 32 && W != 64 && W != 128 && W != 256) return fail(IPSR_ERR_UNSUPPORTED, "%s: width %d (16 .. 256, a power of two)", who, W);
+    g->R = CB_P / W;
+    if (H % g->R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", who, H, g->R);
+    g->B = B; g->C = C; g->K = K; g->H = H; g->W = W;
+    g->wshift = W == 16 ? 4 : (W == 32 ? 5 : (W == 64 ? 6 : (W == 128 ? 7 : 8)));
+    g->NR = g->R + 2; g->PW = W + 2; g->NPOS = g->NR * g->PW;
+    for (int t = 0; t < 9; ++t) g->tapoff[t] = (t / 3) * g->PW + (t % 3);
+    g->ktiles = (K + CX_K - 1) / CX_K;
+    g->ptiles = B * (H / g->R);
+    g->nstage = C / CB_C;
+    // the bf16 kernel's rule for small maps: fewer than 128 workgroups and >= 8 channel blocks -> up to four runs of whole channel blocks
+    const int wgs = g->ktiles * g->ptiles;
+    int ns = 1;
+    if (wgs < 128 && g->nstage >= 8) ns = min(min(4, g->nstage / 4), (256 + wgs - 1) / wgs);
+    g->sps = (g->nstage + ns - 1) / ns;
+    g->nsplit = (g->nstage + g->sps - 1) / g->sps;
+    g->t_bytes = (int)align_up((size_t)2 * 2 * g->NPOS * 16, 256);
+    if (2 * CX_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (W / 4) > CB_THREADS)
+        return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, W);
+    return IPSR_OK;
+}
+
+static size_t cx_pack_bytes(const CxGeom& g) { return (size_t)g.ktiles * g.nstage * 9 * 2 * CX_K * 16; }      // one plane
+
+// zero page | hi plane | lo plane | fp32 partials of a split reduction
+size_t conv_bf16x3_ws_bytes(int B, int C, int K, int H, int W)
+{
+    CxGeom g;
+    if (cx_geometry(B, C, K, H, W, &g) != IPSR_OK) return 0;
+    return 256 + align_up(2 * cx_pack_bytes(g), 256) + (g.nsplit > 1 ? align_up((size_t)g.nsplit * B * K * H * W * sizeof(float), 256) : 0);
+}
+
+// in [B,C,H,W] fp32, weight as in launch_conv_bf16, out [B,K,H,W] fp32
+int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C, int K, int H, int W, long sc, long sk, int flip,
+                       void* ws, size_t ws_bytes, hipStream_t st, int pack_valid)
+{
+    CxGeom g;
+    if (int rc = cx_geometry(B, C, K, H, W, &g)) return rc;
+    const size_t need = conv_bf16x3_ws_bytes(B, C, K, H, W);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 direct conv: workspace %zu < %zu", ws_bytes, need);
+    uint4* zero_page = static_cast<uint4*>(ws);
+    uint4* Wp = zero_page + 16;
+    const size_t lo_plane = cx_pack_bytes(g) / 16;
+    if (!pack_valid) {
+        CbPack pk{};
+        pk.ntap = 9; pk.nsub = 1; pk.nphase = 1; pk.kt = CX_K;
+        for (int t = 0; t < 9; ++t) pk.srctap[0][0][t] = flip ? 8 - t : t;
+        cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * CX_K, 256), C / 8, 9), 256, 0, st>>>(w, C, K, sc, sk, pk, Wp, zero_page, lo_plane);
+        if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
+    }
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
+    float* dst = g.nsplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wp) + align_up(2 * cx_pack_bytes(g), 256)) : out;
+    const unsigned grid = (unsigned)(g.ktiles * g.ptiles * g.nsplit);
+    const double outs = (double)B * H * W;
+    profile_mark_start(st, 4);
+    conv_bf16x3_kernel<<<grid, CB_THREADS, 2 * CX_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, dst);
+    if (g.nsplit > 1) {
+        if (int rc = check_launch("conv_bf16x3_kernel")) return rc;
+        const size_t n = (size_t)B * K * H * W;                // a multiple of 4: W is
+        cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(dst, g.nsplit, n / 4, out);
+    }
+    profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * C * (double)(g.ktiles * CX_K) * outs, 2.0 * 9.0 * C * (double)K * outs);
+    return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16x3_kernel");
+}
+
+// =====================================================================================================================================
 // Weight gradient of the k3 s1 p1 layers on the bf16 matrix cores:
 //      dW[ka][cb][t] = sum_{b, y, x}  a[b][ka][y][x] * w[b][cb][y + dy_t][x + dx_t]            (w zero outside the image)
 // Conv2d: a = dy (Ka = Cout), w = x (Cb = Cin);  ConvTranspose2d: a = x (Ka = Cin), w = dy (Cb = Cout) — dW comes out in the module's
@@ -602,10 +862,6 @@ struct WbGeom {
     int stages_per_wg, nsplit;  // stages of RS rows a workgroup reduces; B * H / (RS * stages_per_wg) runs
     int ktiles, ctiles;
 };
-
-// LDS reads that run beside an LDS-DMA use ext-vector types: a HIP_vector_type (uint4) load is a struct copy that reaches the back end
-// without alias metadata, and hipcc then drains the DMA queue (s_waitcnt vmcnt(0)) in front of it — the prefetch stops overlapping.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
 
@@ -1048,27 +1304,39 @@ size_t ipsr_conv3x3_bf16_workspace_bytes(int op, int B, int Cin, int H, int W, i
     return conv_bf16_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
 
-int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int out_bf16,
-                      void* ws, size_t ws_bytes, void* stream)
+size_t ipsr_conv3x3_bf16x3_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout)
 {
-    return ipsr_conv3x3_bf16_packed(op, in, weight, out, B, Cin, H, W, Cout, out_bf16, 0, ws, ws_bytes, stream);
+    if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16x3_workspace_bytes: bad argument"); return 0; }
+    const bool fwd = op == 0 || op == 2;
+    return conv_bf16x3_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
 
-int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int out_bf16,
+int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
+                      void* ws, size_t ws_bytes, void* stream)
+{
+    return ipsr_conv3x3_bf16_packed(op, in, weight, out, B, Cin, H, W, Cout, io, 0, ws, ws_bytes, stream);
+}
+
+int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
                              int pack_valid, void* ws, size_t ws_bytes, void* stream)
 {
     if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: null pointer");
     if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: bad argument");
-    // out: the bf16 tile leaves as uint4 rows (conv_bf16_kernel's epilogue), the split reduction stores 4-element vectors
+    if (io < 0 || io > 2) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: io code %d (0 bf16 -> fp32, 1 bf16 -> bf16, 2 fp32 -> fp32 on split-bf16 operands)", io);
+    // out: the bf16 tile leaves as uint4 rows (conv_bf16_kernel's epilogue), the split reduction stores 4-element vectors; io 2 reads the fp32
+    // rows of `in` as 16-byte vectors
     if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: in / out / workspace must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (op) {       // (sc, sk, flip) as in ipsr_conv3x3_winograd_mp: C = reduction channels, K = produced channels
-        case 0: return launch_conv_bf16(in, weight, out, B, Cin, Cout, H, W, 9, (long)Cin * 9, 0, out_bf16, ws, ws_bytes, st, pack_valid);
-        case 1: return launch_conv_bf16(in, weight, out, B, Cout, Cin, H, W, (long)Cin * 9, 9, 1, out_bf16, ws, ws_bytes, st, pack_valid);
-        case 2: return launch_conv_bf16(in, weight, out, B, Cin, Cout, H, W, (long)Cout * 9, 9, 1, out_bf16, ws, ws_bytes, st, pack_valid);
-        default: return launch_conv_bf16(in, weight, out, B, Cout, Cin, H, W, 9, (long)Cout * 9, 0, out_bf16, ws, ws_bytes, st, pack_valid);
-    }
+    const bool fwd = op == 0 || op == 2;
+    const int C = fwd ? Cin : Cout, K = fwd ? Cout : Cin;      // reduction / produced channels
+    // (sc, sk, flip) as in ipsr_conv3x3_winograd_mp: weight element (reduction channel c, produced channel k, tap) at w[c * sc + k * sk + tap]
+    const long wc = (long)(op < 2 ? Cin : Cout) * 9;           // stride of the weight's first dimension
+    const long sc = (op == 0 || op == 3) ? 9 : wc, sk = (op == 0 || op == 3) ? wc : 9;
+    const int flip = op == 1 || op == 2;
+    if (io == 2)
+        return launch_conv_bf16x3(static_cast<const float*>(in), weight, static_cast<float*>(out), B, C, K, H, W, sc, sk, flip, ws, ws_bytes, st, pack_valid);
+    return launch_conv_bf16(in, weight, out, B, C, K, H, W, sc, sk, flip, io, ws, ws_bytes, st, pack_valid);
 }
 
 size_t ipsr_conv4x4s2_bf16_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)

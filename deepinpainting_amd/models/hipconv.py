@@ -28,6 +28,9 @@ pass and what the engine needs; a new engine is one record there plus its rule i
                                   gradient as one pass over the input
   "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
+  "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3")`, `opt.conv_math`): the direct kernel on split-bf16
+                                  operands (hi + lo, three products) for the forward / input gradient of the k3 s1 p1 layers that "winograd"
+                                  has by default — no transform passes, error ~6e-6 of the output scale; weight gradients stay where they are
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
@@ -47,18 +50,21 @@ from .. import dist as ipsr_dist
 
 _FORCE = None          # test hook: overrides the environment
 # Arithmetic of the Winograd GEMMs (ops.MATH_CODE): "fp32" for fp32 activations (the reference's arithmetic; "bf16x6" / "bf16x3" are
-# opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).
+# opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).  "direct_bf16x3" for
+# fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d".
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
 
 
 def set_conv_math(fp32=None, bf16=None):
-    """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast)."""
+    """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast); fp32="direct_bf16x3":
+    the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere."""
     from .. import ops as _ops
     for key, val in (("fp32", fp32), ("bf16", bf16)):
         if val is not None:
-            if val not in _ops.MATH_CODE:
+            if val not in _ops.MATH_CODE or (key == "bf16" and val == "direct_bf16x3"):
                 raise ValueError("conv math must be one of %s" % sorted(k for k in _ops.MATH_CODE if k))
             _MATH[key] = val
+    _SEL.clear()           # `select` memoises without the arithmetic
 
 
 def _amp_bf16():
@@ -104,9 +110,11 @@ def select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
 # the module's input whatever the operation.  The rule functions read the switches through `_mode()` / `_env()`; `_SEL` is the only memo.
 def _select_any(op, lay, bf16):
     eng = _select(op, lay)
-    if not bf16:
-        return eng
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if not bf16:
+        if eng == "winograd" and _MATH["fp32"] == "direct_bf16x3" and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
+            return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
+        return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
         return eng
     if _mode() == "auto" and _thin_wins(op, lay, True):
@@ -394,6 +402,13 @@ def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
     return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), out_dtype=out_dtype)
 
 
+def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
+    """fp32 activations on the direct split-bf16 kernel (k3 s1 p1); frozen weights keep their packed planes as in `_bf16d_data`."""
+    param = w if param is None else param
+    frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
+    return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], keep_packed=frozen, pack_key=param)
+
+
 def _bf16d_wrw(x, dy, lay, math, sink):
     if lay[6] == 3:
         return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
@@ -433,6 +448,7 @@ _ENGINES = {
         lambda x, dy, lay, math, sink: ops.conv_to_one_wrw(x, dy, lay[6], lay[8], out=sink),
         fp32_copies=True, sink=True),
     "bf16d": _Engine(_bf16d_data, _bf16d_wrw, bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "bf16x3d": _Engine(_bf16x3d_data),
     "miopen": _Engine(),
 }
 

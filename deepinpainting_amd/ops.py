@@ -450,8 +450,10 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 
 # arithmetic of the Winograd GEMMs (include/ipsr_hip.h, ipsr_conv3x3_winograd_mp): "fp32" = fp32 operands on the fp32 MFMA (the
 # reference's arithmetic, default); "bf16x3" / "bf16x6" = transformed operands split into 2 / 3 bf16 numbers, multiplied on the bf16
-# MFMA with fp32 accumulation (error ~1e-4 / ~1e-5 of the output scale; a plain bf16 convolution: ~2e-3)
-MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3}
+# MFMA with fp32 accumulation (error ~1e-4 / ~1e-5 of the output scale; a plain bf16 convolution: ~2e-3).
+# "direct_bf16x3" = the k3 s1 p1 data passes the dispatcher has on "winograd" go to the DIRECT kernel on split-bf16 operands instead
+# (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply
+MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0}
 
 
 def _io_code(in_bf16, out_dtype):
@@ -618,6 +620,45 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
         ws = _workspace(nbytes, inp.device)
     bf16_pack_launches += 1 - valid
     _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, int(out_dtype == torch.bfloat16),
+                                          valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
+    return out
+
+
+def conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
+    return _lib.lib().ipsr_conv3x3_bf16x3_workspace_bytes(op, B, Cin, H, W, Cout) > 0
+
+
+def conv3x3_bf16x3(op, inp, weight, in_shape, Cout, keep_packed=False, pack_key=None):
+    """k3 s1 p1 convolution / transposed convolution / their input gradients on FP32 tensors as ONE direct implicit GEMM on the bf16
+    matrix cores with split operands (io code 2 of ipsr_conv3x3_bf16, csrc/conv_bf16.hip): every operand hi + lo, every product
+    lo*hi + hi*lo + hi*hi, fp32 accumulation; fp32 in, fp32 out.  keep_packed / pack_key: as in conv3x3_bf16 (the hi and lo planes of
+    the packed weights are kept; cached apart from the bf16 kernel's pack of the same weight)."""
+    global bf16_pack_launches
+    B, Cin, H, W = in_shape
+    inp = _req(inp, torch.float32, "conv input")
+    weight = _req(weight, torch.float32, "conv weight")
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
+    if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
+        raise RuntimeError("conv3x3_bf16x3 op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
+    L = _lib.lib()
+    nbytes = L.ipsr_conv3x3_bf16x3_workspace_bytes(op, B, Cin, H, W, Cout)
+    if nbytes == 0:
+        raise NotImplementedError("ipsr_conv3x3_bf16 (io 2): op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
+    out = _empty(oshape, dtype=torch.float32, device=inp.device)
+    valid = 0
+    if keep_packed:
+        packs = _packs_of(weight if pack_key is None else pack_key)
+        ent = packs.get(("x3", op))
+        if ent is not None and ent[0] == (weight._version, weight.data_ptr()) and ent[1] == tuple(weight.shape) and ent[2].numel() >= nbytes \
+                and ent[2].device == inp.device:
+            ws, valid = ent[2], 1
+        else:
+            ws = _empty(nbytes, dtype=torch.uint8, device=inp.device)
+            packs[("x3", op)] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
+    else:
+        ws = _workspace(nbytes, inp.device)
+    bf16_pack_launches += 1 - valid
+    _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, 2,
                                           valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
     return out
 

@@ -446,17 +446,28 @@ int ipsr_conv4x4s2_winograd_mp(int mode, const void* a, const void* b, void* out
 /* ---- direct bf16 convolutions (BASELINE config 5: "CDNA4 bf16 MFMA for ... convs") --------------------------------------------
  * replaces nn.Conv2d / nn.ConvTranspose2d(k3 s1 p1) under bf16 autocast — models/networks.py:220-243 (`downconv_3` / `upconv_3` of
  * every netG level), models/vgg16.py:9-21 — and their input gradients: ONE implicit-GEMM launch on v_mfma_f32_32x32x16_bf16 (bf16
- * operands, fp32 accumulation), NCHW bf16 activations in, NCHW bf16 (out_bf16 = 1) or fp32 (0) out, fp32 weights cast inside.
+ * operands, fp32 accumulation), NCHW bf16 activations in, NCHW bf16 (io = 1) or fp32 (0) out, fp32 weights cast inside.
  * op as in ipsr_conv2d (0 Conv2d forward, 1 Conv2d backward-data, 2 ConvTranspose2d forward, 3 ConvTranspose2d backward-data);
  * (Cin, H, W) describe the module's input.  Supported: W in {16, 32, 64, 128, 256}, H a multiple of 256 / W, reduction channels a
  * multiple of 16; anything else -> IPSR_ERR_UNSUPPORTED.  Not bit-comparable with anything: operands are rounded to bf16 (tests
- * compare with an fp64 convolution of the bf16-rounded operands). */
+ * compare with an fp64 convolution of the bf16-rounded operands).
+ *   io   0  bf16 activations in, fp32 out;
+ *        1  bf16 activations in, bf16 out;
+ *        2  FP32 activations in, fp32 out, SPLIT-bf16 operands (the opt-in arithmetic "direct_bf16x3" of the fp32 nets): every operand
+ *           a = hi + lo with hi = bf16(a), lo = bf16(a - hi), every product lo*hi + hi*lo + hi*hi on the bf16 matrix cores, fp32
+ *           accumulation; the split happens inside the kernel (no extra pass, no intermediates).  Error per output <= 2^-16 of
+ *           sum |x||w| plus the fp32 accumulation's — nothing amplifies it (the split-bf16 Winograd arithmetic: ~1.4e-4 of the output
+ *           scale; this: ~6e-6).  Same shape limits; the workspace is ipsr_conv3x3_bf16x3_workspace_bytes (0 = unsupported, reason
+ *           in ipsr_last_error), and `in`, `out`, `ws` must be 16-byte aligned (as for the other codes);
+ *        any other value -> IPSR_ERR_INVALID. */
 size_t ipsr_conv3x3_bf16_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout);
-int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int out_bf16,
+size_t ipsr_conv3x3_bf16x3_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout);
+int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
                       void* ws, size_t ws_bytes, void* stream);
 /* _packed: `ws` doubles as the caller-owned cache of the re-packed bf16 weights (same size as the workspace query): pack_valid = 0
- * packs into it, pack_valid = 1 reuses what an earlier call on the SAME weights, op and channel counts left there (frozen VGG16). */
-int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int out_bf16,
+ * packs into it, pack_valid = 1 reuses what an earlier call on the SAME weights, op, channel counts and io class (0 / 1, or 2: hi and
+ * lo planes) left there (frozen VGG16). */
+int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
                              int pack_valid, void* ws, size_t ws_bytes, void* stream);
 /* the 4x4 stride-2 pad-1 layers (every down convolution of netP / netD / netF, every up convolution of netP / netG: models/networks.py:
  * 235-243, 404-432, 470-495, 510-515) in the coarse / fine terms of ipsr_conv4x4s2_winograd: fine = the 2n-grid tensor [B,Cf,2nh,2nw],

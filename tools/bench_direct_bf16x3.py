@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""The direct split-bf16 3x3 convolution on fp32 tensors (ops.conv3x3_bf16x3, engine "bf16x3d", opt.conv_math="direct_bf16x3"):
+
+  layers   the training step's k3 s1 p1 shapes at batch 8, forward and input gradient: device time of the new engine, of the fp32
+           Winograd engine, of the split-bf16 ("bf16x3") Winograd engine and of MIOpen, and each one's error against an fp64
+           convolution (max |err| / max |y64|, first two images).  Times are HIP events around `--iters` back-to-back calls, the
+           engines alternated over `--rounds` rounds, median of the rounds (min .. max in brackets for the new engine).
+  steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "bf16x3" and
+           "direct_bf16x3" in ONE process, alternated over `--rounds` rounds.
+
+    python tools/bench_direct_bf16x3.py [--what layers steps] [--out profiles/direct_bf16x3_layers.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402  (private MIOpen db copy, the step function)
+from deepinpainting_amd import ops  # noqa: E402
+
+LAYERS = [("conv", 64, 256, 64), ("conv", 128, 128, 128), ("conv", 256, 64, 256), ("conv", 512, 32, 512), ("conv", 512, 16, 512), ("convT", 512, 64, 128)]
+
+
+def burst_ms(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def layers(B, iters, rounds, emit):
+    g = torch.Generator(device="cuda").manual_seed(5)
+    emit("batch %d, fp32 NCHW in and out; ms = device time per call (HIP events, %d calls per burst, median of %d alternated rounds); TF = useful flop / time" % (B, iters, rounds))
+    emit("err = max |y - y64| / max |y64| against the fp64 convolution of the unrounded operands")
+    emit("%-22s %-5s | %-31s | %-18s | %-18s | %-18s" % ("layer", "pass", "direct bf16x3  ms [min..max]  TF   err", "fp32 Winograd ms err", "bf16x3 Winograd ms err", "MIOpen ms err"))
+    for kind, Cin, H, Cout in LAYERS:
+        tr = kind == "convT"
+        w = torch.randn((Cin, Cout, 3, 3) if tr else (Cout, Cin, 3, 3), device="cuda", generator=g) * (1.0 / (3.0 * (Cin ** 0.5)))
+        x = torch.randn(B, Cin, H, H, device="cuda", generator=g)
+        dy = torch.randn(B, Cout, H, H, device="cuda", generator=g)
+        fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if tr else (ops.CONV_FWD, ops.CONV_BWD_DATA)
+        flops = 2.0 * 9 * Cin * Cout * B * H * H
+        for name, op, inp in (("fwd", fop, x), ("bwdD", bop, dy)):
+            shp = (B, Cin, H, H)
+            if name == "fwd":
+                mi = (lambda: F.conv_transpose2d(x, w, None, 1, 1)) if tr else (lambda: F.conv2d(x, w, None, 1, 1))
+                f64 = F.conv_transpose2d if tr else F.conv2d
+            else:
+                mi = lambda: torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [1, 1], [1, 1], tr, [0, 0], 1, [True, False, False])[0]
+                f64 = F.conv2d if tr else F.conv_transpose2d
+            ref = f64(inp[:2].double(), w.double(), None, 1, 1)
+            engines = [("direct", lambda: ops.conv3x3_bf16x3(op, inp, w, shp, Cout)),
+                       ("wino_fp32", lambda: ops.conv3x3_winograd(op, inp, w, shp, Cout, math="fp32")),
+                       ("wino_bf16x3", lambda: ops.conv3x3_winograd(op, inp, w, shp, Cout, math="bf16x3")),
+                       ("miopen", mi)]
+            if not ops.conv3x3_bf16x3_supported(op, *shp, Cout):
+                emit("%-5s %4d->%-4d @%-3d %-5s | unsupported" % (kind, Cin, Cout, H, name))
+                continue
+            err, ms = {}, {k: [] for k, _ in engines}
+            for k, fn in engines:
+                for _ in range(3):
+                    y = fn()
+                err[k] = float((y[:2].double() - ref).abs().max() / ref.abs().max())
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for k, fn in engines:
+                    ms[k].append(burst_ms(fn, iters))
+            md = {k: statistics.median(v) for k, v in ms.items()}
+            emit("%-5s %4d->%-4d @%-3d    %-5s | %7.4f [%6.4f..%6.4f] %6.1f %.1e | %7.4f %.1e | %7.4f %.1e | %7.4f %.1e" %
+                 (kind, Cin, Cout, H, name, md["direct"], min(ms["direct"]), max(ms["direct"]), flops / md["direct"] / 1e9, err["direct"],
+                  md["wino_fp32"], err["wino_fp32"], md["wino_bf16x3"], err["wino_bf16x3"], md["miopen"], err["miopen"]))
+
+
+def steps(B, ksteps, rounds, emit):
+    from deepinpainting_amd.models import hipconv
+    from deepinpainting_amd.models.models import create_model
+    from deepinpainting_amd.options import Option
+    device = torch.device("cuda", 0)
+    opt = Option(gpu_ids=[0], batchSize=B, use_dropout=True, quiet=True, allow_random_vgg=True, batch_vgg=False, batch_disc=True, amp_bf16=False,
+                 conv_math="fp32", checkpoints_dir=os.path.join("/tmp", "ipsr_bench_direct_bf16x3"))
+    torch.manual_seed(1234)
+    model = bench.quiet(create_model, opt)
+    img, mask, ref = bench.synthetic_batch(device, B, 1234)
+    maths = ("fp32", "bf16x3", "direct_bf16x3")
+    rate = {m: [] for m in maths}
+    try:
+        for m in maths:                                        # every arithmetic's shapes warmed before any is timed
+            hipconv.set_conv_math(fp32=m)
+            for _ in range(3):
+                bench.train_step(model, img, mask, ref)
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for m in maths:
+                hipconv.set_conv_math(fp32=m)
+                bench.train_step(model, img, mask, ref)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(ksteps):
+                    bench.train_step(model, img, mask, ref)
+                torch.cuda.synchronize()
+                rate[m].append(B * ksteps / (time.perf_counter() - t0))
+    finally:
+        hipconv.set_conv_math(fp32="fp32")
+    emit("whole fp32 training step (bench.py's model and step, batch %d, eager, one process): images/s over %d steps, %d alternated rounds" % (B, ksteps, rounds))
+    for m in maths:
+        emit("  conv_math %-14s median %7.1f   rounds %s" % (m, statistics.median(rate[m]), " ".join("%.1f" % r for r in rate[m])))
+    losses = {k: float(v) for k, v in model.get_current_errors().items()}
+    emit("  losses after the last step finite: %s" % all(v == v and abs(v) != float("inf") for v in losses.values()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "steps"))
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("needs the GPU: nothing is measured without one")
+    fh = open(a.out, "w") if a.out else None
+
+    def emit(line):
+        print(line, flush=True)
+        if fh:
+            fh.write(line + "\n")
+            fh.flush()
+    emit("# tools/bench_direct_bf16x3.py on %s" % torch.cuda.get_device_name(0))
+    if "layers" in a.what:
+        layers(a.batch, a.iters, a.rounds, emit)
+    if "steps" in a.what:
+        steps(a.batch, a.steps, a.rounds, emit)
+
+
+if __name__ == "__main__":
+    main()
