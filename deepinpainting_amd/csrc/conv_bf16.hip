@@ -1064,6 +1064,283 @@ int launch_conv_bf16_wrw(const void* a, const void* w, float* dW, int B, int Ka,
 }
 
 // =====================================================================================================================================
+// The same weight gradient on FP32 tensors with split-bf16 operands (forms 2 / 3 of ipsr_conv3x3_bf16_wrw; the opt-in arithmetic
+// "direct_bf16x3_dw" of the fp32 nets).  Every operand v is taken as hi + lo, hi = bf16(v), lo = bf16(v - hi) (round to nearest even; the
+// fp32 residual is exact), every product as lo*hi + hi*lo + hi*hi: per tap and k-step three MFMAs into the same fp32 accumulator,
+// smallest terms first; lo*lo (2^-18 of the product) is dropped.  A plain pixel reduction amplifies nothing: the error is the 3 * 2^-18 per
+// product of the split plus the fp32 accumulation.
+// The structure is conv_bf16_wrw_kernel's: 8-pixel fragments, the dx = +-1 taps by five v_alignbit_b32 from the aligned chunk and its
+// neighbouring dwords (now for a hi and a lo image), runs of whole image rows cut over workgroups, partial [t][ka][cb] slabs added in
+// ascending order by conv_bf16_wrw_reduce_kernel.  What changed is the plan, because hi + lo images of both operands do not fit the old one:
+//   * the split happens in the kernel, global -> registers -> v_cvt_pk_bf16_f32 -> LDS at the swizzled addresses (no pass over HBM, no
+//     fp32-sized intermediates, no LDS-DMA): the REGISTERS are the second buffer — the loads of stage s + 1 (40 dwords per lane) fly during
+//     the multiplications of stage s, the conversion and the stores follow between two barriers — so LDS holds ONE buffer of each image;
+//   * tile = 128 a-channels x 32 w-channels x 9 taps, stage = 128 pixels (RS = 128 / W image rows).  8 waves = 4 (a-channels) x 2 (halves
+//     of the stage's pixels): a wave owns 32 x 32 x 9 = nine MFMA tiles (9 x 16 accumulator registers, as before) over four of the eight
+//     k-steps; the two halves are added through LDS (fixed order: first half + second half) before the slab is written;
+//   * the w rows live in a ring of RS + 2 image rows (a stage reads RS + 2; the next stage's RS new rows replace the RS oldest after the
+//     barrier); its halo slots and the rows outside the image are zeros.
+// LDS: a hi | a lo = 2 x 32 KB; ring hi | ring lo = 2 x (RS + 2) x 32 c x (W / 8 + 3) slots x 16 B:
+//      W = 16: 65536 + 51200 = 116736 B   W = 32: 65536 + 43008 = 108544 B   W = 64: 65536 + 45056 = 110592 B   W = 128: 65536 + 58368 = 123904 B
+// Supported: W in {16, 32, 64, 128}, H a multiple of 128 / W.  Deterministic: no atomics, every sum in a fixed order.
+constexpr int WX_K = 128, WX_C = 32, WX_PX = 128;
+constexpr int WX_A_PLANE = WX_K * WX_PX * 2;                 // 32 KB per plane
+
+struct WxGeom {
+    int B, Ka, Cb, H, W, wshift;
+    int RS, NSLOT, pitch;       // image rows per stage, ring rows (RS + 2), 16-byte slots per (row, channel): W / 8 + 3
+    int stages_per_wg, nsplit;  // stages of RS rows a workgroup reduces; B * H / (RS * stages_per_wg) runs
+    int ktiles, ctiles;
+    int ring_plane;             // bytes of one plane of the ring
+};
+
+// 8 consecutive fp32 pixels -> their hi and lo bf16 images (16 bytes each)
+__device__ __forceinline__ void wx_split8(const f32x4& v0, const f32x4& v1, u32x4* hi, u32x4* lo)
+{
+    unsigned h16[8], l16[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float v = i < 4 ? v0[i] : v1[i - 4];
+        h16[i] = __builtin_bit_cast(unsigned short, (__bf16)v);
+        l16[i] = __builtin_bit_cast(unsigned short, (__bf16)(v - __uint_as_float(h16[i] << 16)));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { (*hi)[i] = h16[2 * i] | (h16[2 * i + 1] << 16); (*lo)[i] = l16[2 * i] | (l16[2 * i + 1] << 16); }
+}
+
+__global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const float* __restrict__ a, const float* __restrict__ w, WxGeom g,
+                                                                        float* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // a hi | a lo | ring hi | ring lo
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, wp = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = g.ktiles * g.ctiles;
+    const int tile = L % tiles, split = L / tiles;
+    const int kt = tile % g.ktiles, ct = tile / g.ktiles;
+    const int rows_per_wg = g.RS * g.stages_per_wg;
+    const int runs_per_img = g.H / rows_per_wg;
+    const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
+    const size_t HW = (size_t)g.H * g.W;
+    const int cpr = g.W >> 3;                                // 16-byte bf16 chunks per image row
+    unsigned char* const ring = lds + 2 * WX_A_PLANE;
+    const int ring_row_bytes = WX_C * g.pitch * 16;
+
+    // ---- a rows: a lane owns chunk c8 = tid & 15 (8 pixels; a stage's pixels are contiguous in NCHW) of the channels (tid >> 4) + 32 j; slot
+    // k * 16 + (c8 ^ (k & 15)) as in the bf16 kernel (k & 15 is the same for the four j) ------------------------------------------------------
+    const int c8 = tid & 15, k0 = tid >> 4;
+    const float* ga[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ka = kt * WX_K + k0 + 32 * j;
+        ga[j] = ka < g.Ka ? a + ((size_t)b * g.Ka + ka) * HW + (size_t)ylo * g.W + c8 * 8 : nullptr;
+    }
+    const int a_wr = ((k0 << 4) + (c8 ^ (k0 & 15))) * 16;    // + j * 8192
+    // ---- w rows: a lane owns chunk c8 (row rr, chunk cx of the stage's RS new rows) of channel tid >> 4 -------------------------------------
+    const int rr = c8 / cpr, cx = c8 - rr * cpr;
+    const int cbw = ct * WX_C + k0;
+    const float* gw = cbw < g.Cb ? w + ((size_t)b * g.Cb + cbw) * HW + c8 * 8 : nullptr;
+    const int w_wr = (k0 * g.pitch + 1 + cx) * 16;
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+
+    f32x4 ar[8], wr[2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ar[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};           // channels past Ka stay zeros
+    // stage s: its 128 pixels of a, and the RS rows y0 + 1 .. y0 + RS of w (the rows stage s needs beyond those of stage s - 1)
+    auto load_stage = [&](int s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (ga[j]) {
+                const float* src = ga[j] + (size_t)s * WX_PX;
+                ar[2 * j] = *reinterpret_cast<const f32x4*>(src);
+                ar[2 * j + 1] = *reinterpret_cast<const f32x4*>(src + 4);
+            }
+        const int y1 = ylo + s * g.RS + 1;
+        if (gw && y1 + rr < g.H) {
+            const float* src = gw + (size_t)y1 * g.W;
+            wr[0] = *reinterpret_cast<const f32x4*>(src);
+            wr[1] = *reinterpret_cast<const f32x4*>(src + 4);
+        } else {
+            wr[0] = wr[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    };
+    auto store_stage = [&](int s) {
+        u32x4 vh, vl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            wx_split8(ar[2 * j], ar[2 * j + 1], &vh, &vl);
+            *reinterpret_cast<u32x4*>(lds + a_wr + j * 8192) = vh;
+            *reinterpret_cast<u32x4*>(lds + WX_A_PLANE + a_wr + j * 8192) = vl;
+        }
+        const int slot = (ylo + s * g.RS + 2 + rr) % g.NSLOT;                    // image row y lives in ring slot (y + 1) mod NSLOT
+        wx_split8(wr[0], wr[1], &vh, &vl);
+        *reinterpret_cast<u32x4*>(ring + slot * ring_row_bytes + w_wr) = vh;
+        *reinterpret_cast<u32x4*>(ring + g.ring_plane + slot * ring_row_bytes + w_wr) = vl;
+    };
+
+    // prologue: the ring starts as zeros (its halo slots are never written); rows ylo - 1 and ylo, then stage 0
+    for (int i = tid; i < 2 * g.ring_plane / 16; i += WB_THREADS) *reinterpret_cast<u32x4*>(ring + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    load_stage(0);
+    __syncthreads();
+    for (int i = tid; i < 2 * WX_C * cpr; i += WB_THREADS) {
+        const int e = i / (WX_C * cpr), rem = i - e * (WX_C * cpr);
+        const int c = rem / cpr, x8 = rem - c * cpr;
+        const int y = ylo - 1 + e, cb = ct * WX_C + c;
+        if (cb < g.Cb && y >= 0) {                           // else: the zeros stay
+            const float* src = w + ((size_t)b * g.Cb + cb) * HW + (size_t)y * g.W + x8 * 8;
+            u32x4 vh, vl;
+            wx_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), &vh, &vl);
+            const int off = ((y + 1) % g.NSLOT) * ring_row_bytes + (c * g.pitch + 1 + x8) * 16;
+            *reinterpret_cast<u32x4*>(ring + off) = vh;
+            *reinterpret_cast<u32x4*>(ring + g.ring_plane + off) = vl;
+        }
+    }
+    store_stage(0);
+    __syncthreads();
+
+    const int a_row = wk * 32 + r;                            // a fragment: channel row; w fragment: channel column r
+    for (int s = 0; s < g.stages_per_wg; ++s) {
+        const int y0 = ylo + s * g.RS;
+        if (s + 1 < g.stages_per_wg) load_stage(s + 1);       // consumed behind this stage's multiplications
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {                      // this wave's k-steps of 16 pixels
+            const int j = 4 * wp + jj;
+            const int f8 = 2 * j + h;
+            const unsigned char* A = lds + ((a_row << 4) + (f8 ^ (a_row & 15))) * 16;
+            const bf16x8 fah = *reinterpret_cast<const bf16x8*>(A), fal = *reinterpret_cast<const bf16x8*>(A + WX_A_PLANE);
+            const int p0 = 16 * j;                            // stage pixel of the k-step
+            const int rs = p0 >> g.wshift, px = (p0 & (g.W - 1)) + 8 * h;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const int slot = (y0 + rs + dy) % g.NSLOT;    // image row y0 + rs + dy - 1
+                const unsigned char* X = ring + slot * ring_row_bytes + (r * g.pitch + 1 + (px >> 3)) * 16;
+                u32x4 ctr[2], left[2], right[2];
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const unsigned char* Xp = X + pl * g.ring_plane;
+                    const u32x4 c4 = *reinterpret_cast<const u32x4*>(Xp);
+                    const unsigned prev = *reinterpret_cast<const unsigned*>(Xp - 4);
+                    const unsigned next = *reinterpret_cast<const unsigned*>(Xp + 16);
+                    const unsigned s0 = alignbit16(c4.x, prev), s1 = alignbit16(c4.y, c4.x), s2 = alignbit16(c4.z, c4.y), s3 = alignbit16(c4.w, c4.z),
+                                   s4 = alignbit16(next, c4.w);
+                    ctr[pl] = c4; left[pl] = u32x4{s0, s1, s2, s3}; right[pl] = u32x4{s1, s2, s3, s4};
+                }
+                f32x16& a0 = acc[dy * 3 + 0];
+                f32x16& a1 = acc[dy * 3 + 1];
+                f32x16& a2 = acc[dy * 3 + 2];
+                // smallest terms first: lo(a) hi(w), hi(a) lo(w), hi(a) hi(w); the three taps alternate so that no MFMA waits for its predecessor
+                a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, left[0]), a0, 0, 0, 0);
+                a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, ctr[0]), a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, right[0]), a2, 0, 0, 0);
+                a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, left[1]), a0, 0, 0, 0);
+                a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, ctr[1]), a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, right[1]), a2, 0, 0, 0);
+                a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, left[0]), a0, 0, 0, 0);
+                a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, ctr[0]), a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, right[0]), a2, 0, 0, 0);
+            }
+        }
+        __syncthreads();                                       // every wave is done reading this stage
+        if (s + 1 < g.stages_per_wg) {
+            store_stage(s + 1);
+            __syncthreads();
+        }
+    }
+
+    // the two pixel halves of a tile: second half -> LDS (three taps at a time, 48 KB over the a images), first half adds and keeps the sum
+    float* red = reinterpret_cast<float*>(lds);
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        if (wp == 1) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) red[((wk * 3 + t) * 16 + e) * 64 + lane] = acc[dy * 3 + t][e];
+        }
+        __syncthreads();
+        if (wp == 0) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[dy * 3 + t][e] += red[((wk * 3 + t) * 16 + e) * 64 + lane];
+        }
+        __syncthreads();
+    }
+    if (wp != 0) return;
+
+    // partial result: slab[split][t][ka][cb] (lanes along cb: coalesced)
+    const int Kap = g.ktiles * WX_K, Cbp = g.ctiles * WX_C;
+    float* out = slabs + (size_t)split * 9 * Kap * Cbp;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ka = kt * WX_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)t * Kap + ka) * Cbp + ct * WX_C + r] = acc[t][e];
+        }
+}
+
+static int wx_geometry(int B, int Ka, int Cb, int H, int W, WxGeom* g)
+{
+    const char* who = "split-bf16 weight gradient";
+    if (W != 16 && W != 32 && W != 64 && W != 128) return fail(IPSR_ERR_UNSUPPORTED, "%s: image width %d (16, 32, 64 or 128)", who, W);
+    const int RS = WX_PX / W;
+    if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a stage", who, H, RS);
+    g->B = B; g->Ka = Ka; g->Cb = Cb; g->H = H; g->W = W;
+    g->wshift = W == 16 ? 4 : (W == 32 ? 5 : (W == 64 ? 6 : 7));
+    g->RS = RS; g->NSLOT = RS + 2; g->pitch = W / 8 + 3;
+    g->ktiles = (Ka + WX_K - 1) / WX_K; g->ctiles = (Cb + WX_C - 1) / WX_C;
+    g->ring_plane = g->NSLOT * WX_C * g->pitch * 16;
+    if (2 * WX_A_PLANE + 2 * g->ring_plane > CB_LDS_MAX)
+        return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide image does not fit the LDS plan", who, W);
+    // runs: one round of one workgroup per CU, as wb_geometry (every run costs a partial slab written and read back)
+    const int groups = H / RS;                                // stages per image
+    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
+    if (spw < 1) spw = 1;
+    if (spw > groups) spw = groups;
+    while (groups % spw) --spw;
+    g->stages_per_wg = spw;
+    g->nsplit = B * (groups / spw);
+    return IPSR_OK;
+}
+
+// the partial slabs, nothing else
+size_t conv_bf16x3_wrw_ws_bytes(int B, int Ka, int Cb, int H, int W)
+{
+    WxGeom g;
+    if (wx_geometry(B, Ka, Cb, H, W, &g) != IPSR_OK) return 0;
+    return (size_t)g.nsplit * 9 * g.ktiles * WX_K * g.ctiles * WX_C * 4;
+}
+
+// a [B,Ka,H,W], w [B,Cb,H,W] fp32 -> dW [Ka][Cb][3][3] fp32
+int launch_conv_bf16x3_wrw(const float* a, const float* w, float* dW, int B, int Ka, int Cb, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
+{
+    WxGeom g;
+    if (int rc = wx_geometry(B, Ka, Cb, H, W, &g)) return rc;
+    const size_t need = conv_bf16x3_wrw_ws_bytes(B, Ka, Cb, H, W);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 weight gradient: workspace %zu < %zu", ws_bytes, need);
+    float* slabs = static_cast<float*>(ws);
+    const size_t smem = 2 * (size_t)WX_A_PLANE + 2 * (size_t)g.ring_plane;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_wrw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
+    const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
+    profile_mark_start(st, 4);
+    conv_bf16x3_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(a, w, g, slabs);
+    profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * (double)(g.ktiles * WX_K) * (g.ctiles * WX_C) * B * H * W, 2.0 * 9.0 * (double)Ka * Cb * B * H * W);
+    if (int rc = check_launch("conv_bf16x3_wrw_kernel")) return rc;
+    conv_bf16_wrw_reduce_kernel<<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WX_K, g.ctiles * WX_C, dW);
+    return check_launch("conv_bf16_wrw_reduce_kernel");
+}
+
+// =====================================================================================================================================
 // Weight gradient of the k4 s2 p1 layers (Conv2d [Kc][Cf] and ConvTranspose2d [Kc][Cf] alike, in the coarse / fine terms above):
 //      dW[kc][cf][r][s] = sum_{b, oy, ox}  coarse[b][kc][oy][ox] * fine[b][cf][2 oy - 1 + r][2 ox - 1 + s]
 // The reduction runs over COARSE pixels: the coarse operand's fragments are aligned 16-byte reads as in the k3 kernel; the fine
@@ -1379,15 +1656,30 @@ size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int
     return transposed ? conv_bf16_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16_wrw_ws_bytes(B, Cout, Cin, H, W);
 }
 
-int ipsr_conv3x3_bf16_wrw(int transposed, const void* x, const void* dy, float* dw, int B, int Cin, int H, int W, int Cout,
+size_t ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)
+{
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16x3_wrw_workspace_bytes: bad argument"); return 0; }
+    return transposed ? conv_bf16x3_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16x3_wrw_ws_bytes(B, Cout, Cin, H, W);
+}
+
+int ipsr_conv3x3_bf16_wrw(int form, const void* x, const void* dy, float* dw, int B, int Cin, int H, int W, int Cout,
                           void* ws, size_t ws_bytes, void* stream)
 {
+    if (form < 0 || form > 3)
+        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: form code %d (0 Conv2d, 1 ConvTranspose2d on bf16 tensors; 2, 3 the same on fp32 tensors, split-bf16 operands)", form);
     if (!x || !dy || !dw || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: null pointer");
     if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: bad argument");
     if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(x) & 15u) || (reinterpret_cast<uintptr_t>(dy) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: x / dy / workspace must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool transposed = form & 1;
     // Conv2d: dW[co][ci][t] = sum dy[co][p] x[ci][p + t];  ConvTranspose2d: dW[ci][co][t] = sum x[ci][p] dy[co][p + t]
+    if (form >= 2) {
+        const float* xf = static_cast<const float*>(x);
+        const float* dyf = static_cast<const float*>(dy);
+        if (transposed) return launch_conv_bf16x3_wrw(xf, dyf, dw, B, Cin, Cout, H, W, ws, ws_bytes, st);
+        return launch_conv_bf16x3_wrw(dyf, xf, dw, B, Cout, Cin, H, W, ws, ws_bytes, st);
+    }
     if (transposed) return launch_conv_bf16_wrw(x, dy, dw, B, Cin, Cout, H, W, ws, ws_bytes, st);
     return launch_conv_bf16_wrw(dy, x, dw, B, Cout, Cin, H, W, ws, ws_bytes, st);
 }

@@ -31,6 +31,9 @@ pass and what the engine needs; a new engine is one record there plus its rule i
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3")`, `opt.conv_math`): the direct kernel on split-bf16
                                   operands (hi + lo, three products) for the forward / input gradient of the k3 s1 p1 layers that "winograd"
                                   has by default — no transform passes, error ~6e-6 of the output scale; weight gradients stay where they are
+  "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3_dw")`): the weight gradient of the k3 s1 p1 layers
+                                  that "winograd" / "miopen" have by default, as a pixel reduction on split-bf16 operands (two launches, the
+                                  split in the kernel); the data passes run "bf16x3d" as under "direct_bf16x3"
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
@@ -51,17 +54,20 @@ from .. import dist as ipsr_dist
 _FORCE = None          # test hook: overrides the environment
 # Arithmetic of the Winograd GEMMs (ops.MATH_CODE): "fp32" for fp32 activations (the reference's arithmetic; "bf16x6" / "bf16x3" are
 # opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).  "direct_bf16x3" for
-# fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d".
+# fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d";
+# "direct_bf16x3_dw" does the same and `select_wrw` moves the k3 s1 p1 weight gradients of "winograd" / "miopen" to "bf16x3w".
+_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw")
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
 
 
 def set_conv_math(fp32=None, bf16=None):
     """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast); fp32="direct_bf16x3":
-    the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere."""
+    the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere;
+    fp32="direct_bf16x3_dw": that, and the direct split-bf16 weight gradient where `select_wrw` has "winograd" or "miopen"."""
     from .. import ops as _ops
     for key, val in (("fp32", fp32), ("bf16", bf16)):
         if val is not None:
-            if val not in _ops.MATH_CODE or (key == "bf16" and val == "direct_bf16x3"):
+            if val not in _ops.MATH_CODE or (key == "bf16" and val in _DIRECT_MATH):
                 raise ValueError("conv math must be one of %s" % sorted(k for k in _ops.MATH_CODE if k))
             _MATH[key] = val
     _SEL.clear()           # `select` memoises without the arithmetic
@@ -112,7 +118,7 @@ def _select_any(op, lay, bf16):
     eng = _select(op, lay)
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if not bf16:
-        if eng == "winograd" and _MATH["fp32"] == "direct_bf16x3" and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
+        if eng == "winograd" and _MATH["fp32"] in _DIRECT_MATH and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
             return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
@@ -322,7 +328,11 @@ def _select_wrw_any(lay, bf16):
         and ops.thin_wrw_mfma_supported(transposed, B, Cin, H, W, Cout, k, stride)
     if not bf16:
         # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
-        return "thin_mfma" if thin and eng == "miopen" else eng
+        if thin and eng == "miopen":
+            return "thin_mfma"
+        if _MATH["fp32"] == "direct_bf16x3_dw" and _bf16x3_wrw_wins(eng, lay):
+            return "bf16x3w"
+        return eng
     if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
         return eng
     if thin:
@@ -345,6 +355,20 @@ def _bf16_direct_wrw(lay):
     if g is not None and g[3] >= 32 and ((g[0] + 127) // 128) * ((g[1] + 31) // 32) >= 4 and ops.conv4x4s2_bf16_wrw_supported(B, *g):
         return "bf16d"           # 1.2-1.4x MIOpen from four 128 x 32 output tiles up on coarse grids >= 32 wide; 16-wide grids and single tiles lose
     return "miopen"
+
+
+def _bf16x3_wrw_wins(eng, lay):
+    """fp32 activations under the opt-in "direct_bf16x3_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
+    split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured at batch 8
+    (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient on 256 -> 256 /
+    512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer multiplications and its
+    transforms are small there), so maps below 64x64 with >= 512 channels on both sides stay where they are."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if eng not in ("winograd", "miopen") or _mode() != "auto":
+        return False
+    if H * W < 4096 and min(Cin, Cout) >= 512:
+        return False
+    return k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and ops.conv3x3_bf16x3_wrw_supported(transposed, B, Cin, H, W, Cout)
 
 
 def _select_wrw(lay):
@@ -449,6 +473,7 @@ _ENGINES = {
         fp32_copies=True, sink=True),
     "bf16d": _Engine(_bf16d_data, _bf16d_wrw, bf16_io=True, sink=True, wrw_x_as_dy=True),
     "bf16x3d": _Engine(_bf16x3d_data),
+    "bf16x3w": _Engine(None, lambda x, dy, lay, math, sink: ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink), sink=True),
     "miopen": _Engine(),
 }
 

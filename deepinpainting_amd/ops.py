@@ -452,8 +452,9 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 # reference's arithmetic, default); "bf16x3" / "bf16x6" = transformed operands split into 2 / 3 bf16 numbers, multiplied on the bf16
 # MFMA with fp32 accumulation (error ~1e-4 / ~1e-5 of the output scale; a plain bf16 convolution: ~2e-3).
 # "direct_bf16x3" = the k3 s1 p1 data passes the dispatcher has on "winograd" go to the DIRECT kernel on split-bf16 operands instead
-# (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply
-MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0}
+# (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply.
+# "direct_bf16x3_dw" = the same, and the k3 s1 p1 weight gradients go to the direct split-bf16 kernel too (conv3x3_bf16x3_wrw)
+MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0}
 
 
 def _io_code(in_bf16, out_dtype):
@@ -728,6 +729,27 @@ def conv3x3_bf16_wrw(transposed, x, dy, Cout, out=None):
     dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_bf16_wrw")
     ws = _probed_workspace(L, L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device, "ipsr_conv3x3_bf16_wrw: %s", ((B, Cin, H, W, Cout),))
     _lib.check(L.ipsr_conv3x3_bf16_wrw(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
+                                       _stream()), "ipsr_conv3x3_bf16_wrw")
+    return dw
+
+
+def conv3x3_bf16x3_wrw_supported(transposed, B, Cin, H, W, Cout):
+    return _lib.lib().ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout) > 0
+
+
+def conv3x3_bf16x3_wrw(transposed, x, dy, Cout, out=None):
+    """Weight gradient of a k3 s1 p1 Conv2d (-> [Cout,Cin,3,3]) / ConvTranspose2d (-> [Cin,Cout,3,3]) on FP32 tensors with split-bf16
+    operands (forms 2 / 3 of ipsr_conv3x3_bf16_wrw): x, dy fp32; the result fp32 (optionally written into `out`, e.g. a slice of a
+    gradient bucket)."""
+    x = _req(x, torch.float32, "conv input")
+    dy = _req(dy, torch.float32, "grad_output")
+    B, Cin, H, W = x.shape
+    if tuple(dy.shape) != (B, Cout, H, W):
+        raise RuntimeError("conv3x3_bf16x3_wrw: grad_output %s does not match %s" % (tuple(dy.shape), (B, Cout, H, W)))
+    L = _lib.lib()
+    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_bf16x3_wrw")
+    ws = _probed_workspace(L, L.ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device, "ipsr_conv3x3_bf16_wrw (split-bf16): %s", ((B, Cin, H, W, Cout),))
+    _lib.check(L.ipsr_conv3x3_bf16_wrw(2 + int(bool(transposed)), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
                                        _stream()), "ipsr_conv3x3_bf16_wrw")
     return dw
 

@@ -482,11 +482,18 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
                             void* ws, size_t ws_bytes, void* stream);
-/* their weight gradient: x [B,Cin,H,W], dy [B,Cout,H,W] bf16 -> dw fp32 in the module's layout (transposed = 0: Conv2d [Cout][Cin][3][3];
- * 1: ConvTranspose2d [Cin][Cout][3][3]).  The reduction over pixels is cut over workgroups; the partial results are added in a fixed
- * order by a second launch (deterministic).  Same shape limits as above. */
+/* their weight gradient: x [B,Cin,H,W], dy [B,Cout,H,W] -> dw fp32 in the module's layout.  The reduction over pixels is cut over
+ * workgroups; the partial results are added in a fixed order by a second launch (deterministic).  W in {16, 32, 64, 128}, H a multiple
+ * of 128 / W.  form:
+ *        0  Conv2d [Cout][Cin][3][3], x and dy bf16                      1  ConvTranspose2d [Cin][Cout][3][3], x and dy bf16
+ *        2  Conv2d, x and dy FP32, SPLIT-bf16 operands                   3  ConvTranspose2d, likewise
+ * Forms 2 / 3 (the opt-in arithmetic "direct_bf16x3_dw" of the fp32 nets): every operand is taken as hi + lo (hi = bf16(v), lo = bf16(v - hi)),
+ * every product as lo*hi + hi*lo + hi*hi on the bf16 matrix cores with fp32 accumulation; the split happens in the kernel.  Forms 0 / 1 take
+ * the workspace of ipsr_conv3x3_bf16_wrw_workspace_bytes, forms 2 / 3 that of ipsr_conv3x3_bf16x3_wrw_workspace_bytes (0 = unsupported,
+ * reason in ipsr_last_error()).  Any other form is IPSR_ERR_INVALID; x, dy and the workspace are 16-byte aligned. */
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout);
-int ipsr_conv3x3_bf16_wrw(int transposed, const void* x, const void* dy, float* dw, int B, int Cin, int H, int W, int Cout,
+size_t ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout);
+int ipsr_conv3x3_bf16_wrw(int form, const void* x, const void* dy, float* dw, int B, int Cin, int H, int W, int Cout,
                           void* ws, size_t ws_bytes, void* stream);
 
 /* How the reduction of the 36 Winograd GEMMs of a layer is cut over workgroups (csrc/winograd.hip, wino_choose_split): for a GEMM

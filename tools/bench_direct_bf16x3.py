@@ -5,10 +5,13 @@
            Winograd engine, of the split-bf16 ("bf16x3") Winograd engine and of MIOpen, and each one's error against an fp64
            convolution (max |err| / max |y64|, first two images).  Times are HIP events around `--iters` back-to-back calls, the
            engines alternated over `--rounds` rounds, median of the rounds (min .. max in brackets for the new engine).
-  steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "bf16x3" and
-           "direct_bf16x3" in ONE process, alternated over `--rounds` rounds.
+  wrw      the weight gradient of the same shapes, as Conv2d and as ConvTranspose2d (ops.conv3x3_bf16x3_wrw, engine "bf16x3w",
+           opt.conv_math="direct_bf16x3_dw"): the new engine against the engine `select_wrw` answers for the shape by default, same
+           process, same rounds; err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the whole batch.
+  steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "direct_bf16x3",
+           "direct_bf16x3_dw" and "bf16x3" in ONE process, alternated over `--rounds` rounds.
 
-    python tools/bench_direct_bf16x3.py [--what layers steps] [--out profiles/direct_bf16x3_layers.txt]
+    python tools/bench_direct_bf16x3.py [--what layers wrw steps] [--out profiles/direct_bf16x3_layers.txt]
 """
 import argparse
 import os
@@ -79,6 +82,46 @@ def layers(B, iters, rounds, emit):
                   md["wino_fp32"], err["wino_fp32"], md["wino_bf16x3"], err["wino_bf16x3"], md["miopen"], err["miopen"]))
 
 
+def wrw(B, iters, rounds, emit):
+    from deepinpainting_amd.models import hipconv
+    g = torch.Generator(device="cuda").manual_seed(6)
+    emit("weight gradient, batch %d, fp32 NCHW operands, dW fp32 in the module's layout; ms = device time per call (HIP events, %d calls per burst, "
+         "median of %d alternated rounds); TF = useful flop / time" % (B, iters, rounds))
+    emit("err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the unrounded operands; today = the engine select_wrw answers under conv_math fp32")
+    emit("%-22s | %-38s | %-28s | %s" % ("layer", "direct bf16x3 wrw  ms [min..max]  TF   err", "today's engine  ms  err", "today / direct"))
+    for kind, Cin, H, Cout in [(k, ci, h, co) for _, ci, h, co in LAYERS for k in ("conv", "convT")]:
+        tr = kind == "convT"
+        lay = (tr, B, Cin, H, H, Cout, 3, 1, 1, 1)
+        label = "%-5s %4d->%-4d @%-3d" % (kind, Cin, Cout, H)
+        if not ops.conv3x3_bf16x3_wrw_supported(tr, B, Cin, H, H, Cout):
+            emit("%s    | unsupported" % label)
+            continue
+        x = torch.randn(B, Cin, H, H, device="cuda", generator=g)
+        dy = torch.randn(B, Cout, H, H, device="cuda", generator=g)
+        w = torch.zeros((Cin, Cout, 3, 3) if tr else (Cout, Cin, 3, 3), device="cuda")
+        today = hipconv.select_wrw(*lay)
+        if today == "miopen":
+            base = lambda: torch.ops.aten.convolution_backward(dy, x, w, None, [1, 1], [1, 1], [1, 1], tr, [0, 0], 1, [False, True, False])[1]
+        else:
+            base = lambda: hipconv._run_wrw(today, x, dy, w, lay, "fp32")
+        ref = torch.ops.aten.convolution_backward(dy.double(), x.double(), w.double(), None, [1, 1], [1, 1], [1, 1], tr, [0, 0], 1, [False, True, False])[1]
+        engines = [("direct", lambda: ops.conv3x3_bf16x3_wrw(tr, x, dy, Cout)), ("today", base)]
+        err, ms = {}, {k: [] for k, _ in engines}
+        for k, fn in engines:
+            for _ in range(3):
+                d = fn()
+            err[k] = float((d.double() - ref).abs().max() / ref.abs().max())
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, fn in engines:
+                ms[k].append(burst_ms(fn, iters))
+        md = {k: statistics.median(v) for k, v in ms.items()}
+        flops = 2.0 * 9 * Cin * Cout * B * H * H
+        emit("%s    | %7.4f [%6.4f..%6.4f] %6.1f %.1e     | %-9s %7.4f %.1e     | %.2fx" %
+             (label, md["direct"], min(ms["direct"]), max(ms["direct"]), flops / md["direct"] / 1e9, err["direct"], today, md["today"], err["today"],
+              md["today"] / md["direct"]))
+
+
 def steps(B, ksteps, rounds, emit):
     from deepinpainting_amd.models import hipconv
     from deepinpainting_amd.models.models import create_model
@@ -89,7 +132,7 @@ def steps(B, ksteps, rounds, emit):
     torch.manual_seed(1234)
     model = bench.quiet(create_model, opt)
     img, mask, ref = bench.synthetic_batch(device, B, 1234)
-    maths = ("fp32", "bf16x3", "direct_bf16x3")
+    maths = ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "bf16x3")
     rate = {m: [] for m in maths}
     try:
         for m in maths:                                        # every arithmetic's shapes warmed before any is timed
@@ -111,14 +154,14 @@ def steps(B, ksteps, rounds, emit):
         hipconv.set_conv_math(fp32="fp32")
     emit("whole fp32 training step (bench.py's model and step, batch %d, eager, one process): images/s over %d steps, %d alternated rounds" % (B, ksteps, rounds))
     for m in maths:
-        emit("  conv_math %-14s median %7.1f   rounds %s" % (m, statistics.median(rate[m]), " ".join("%.1f" % r for r in rate[m])))
+        emit("  conv_math %-17s median %7.1f   rounds %s" % (m, statistics.median(rate[m]), " ".join("%.1f" % r for r in rate[m])))
     losses = {k: float(v) for k, v in model.get_current_errors().items()}
     emit("  losses after the last step finite: %s" % all(v == v and abs(v) != float("inf") for v in losses.values()))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "steps"))
+    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "steps"))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
@@ -137,6 +180,8 @@ def main():
     emit("# tools/bench_direct_bf16x3.py on %s" % torch.cuda.get_device_name(0))
     if "layers" in a.what:
         layers(a.batch, a.iters, a.rounds, emit)
+    if "wrw" in a.what:
+        wrw(a.batch, a.iters, a.rounds, emit)
     if "steps" in a.what:
         steps(a.batch, a.steps, a.rounds, emit)
 
