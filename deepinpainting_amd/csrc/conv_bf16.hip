@@ -374,6 +374,17 @@ static int cb_lane_grid(int Hl, int Wl, int ptile, CbGeom* g, const char* who)
     return IPSR_OK;
 }
 
+// (ktiles, nphase, ptiles, nsub set) -> nsplit, sps
+static void cb_cut_reduction(CbGeom* g)
+{
+    const int wgs = g->ktiles * g->nphase * g->ptiles, nblocks = g->C / CB_C;
+    int ns = 1;
+    if (wgs < 128 && nblocks >= 8) ns = min(min(4, nblocks / 4), (256 + wgs - 1) / wgs);
+    const int bps = (nblocks + ns - 1) / max(ns, 1);      // channel blocks per run
+    g->nsplit = (nblocks + bps - 1) / bps;
+    g->sps = bps * g->nsub;
+}
+
 static int cb_finish(CbGeom* g, const char* who)
 {
     g->NPOS = g->NR * g->PW;
@@ -383,14 +394,7 @@ static int cb_finish(CbGeom* g, const char* who)
     g->nstage = (g->C / CB_C) * g->nsub;
     // Small maps leave the chip idle (a 16x16 map is ONE pixel tile per image: 64 workgroups at 512 produced channels and batch 16): the
     // reduction is cut into up to four runs of whole channel blocks, each run a workgroup of its own writing an fp32 partial.
-    {
-        const int wgs = g->ktiles * g->nphase * g->ptiles, nblocks = g->C / CB_C;
-        int ns = 1;
-        if (wgs < 128 && nblocks >= 8) ns = min(min(4, nblocks / 4), (256 + wgs - 1) / wgs);
-        const int bps = (nblocks + ns - 1) / max(ns, 1);      // channel blocks per run
-        g->nsplit = (nblocks + bps - 1) / bps;
-        g->sps = bps * g->nsub;
-    }
+    cb_cut_reduction(g);
     const int planes = g->nsub;                               // F2C keeps the two column phases
     g->a_bytes = g->ntap * 2 * g->kt * 16;
     g->t_bytes = (int)align_up((size_t)planes * 2 * g->NPOS * 16, 256);
@@ -430,11 +434,9 @@ static int cb_geometry_s2(int form, int B, int C, int K, int nh, int nw, CbGeom*
     return cb_geometry_s2_p(form, B, C, K, nh, nw, CB_P, g);
 }
 
-static int cb_geometry_s2_p(int form, int B, int C, int K, int nh, int nw, int ptile, CbGeom* g)
+// the two k4 s2 p1 forms on a lane grid already set (cb_lane_grid): tensors, halo rows, row maps, tap offsets
+static void cb_s2_form(int form, int nh, int nw, CbGeom* g)
 {
-    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 direct 4x4 stride-2 conv: %d reduction channels are not a multiple of %d", C, CB_C);
-    if (int rc = cb_lane_grid(nh, nw, ptile, g, "bf16 direct 4x4 stride-2 conv")) return rc;
-    g->B = B; g->C = C; g->K = K;
     if (form == 0) {
         g->Hin = 2 * nh; g->Win = 2 * nw; g->Hout = nh; g->Wout = nw;
         g->NR = g->R + 1; g->PW = nw + 1;
@@ -462,6 +464,14 @@ static int cb_geometry_s2_p(int form, int B, int C, int K, int nh, int nw, int p
                 g->tapoff[ey][t] = (1 + ey - ai) * g->PW + (1 + ex - bi);
             }
     }
+}
+
+static int cb_geometry_s2_p(int form, int B, int C, int K, int nh, int nw, int ptile, CbGeom* g)
+{
+    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 direct 4x4 stride-2 conv: %d reduction channels are not a multiple of %d", C, CB_C);
+    if (int rc = cb_lane_grid(nh, nw, ptile, g, "bf16 direct 4x4 stride-2 conv")) return rc;
+    g->B = B; g->C = C; g->K = K;
+    cb_s2_form(form, nh, nw, g);
     return cb_finish(g, "bf16 direct 4x4 stride-2 conv");
 }
 
@@ -560,6 +570,30 @@ int launch_conv_bf16(const void* in, const float* w, void* out, int B, int C, in
     return cb_launch<CB_S1>(g, pk, in, w, out, sc, sk, out_bf16, ws, st, 9.0, pack_valid);
 }
 
+// source taps of the packed images of the two k4 s2 p1 forms: srctap[phase][sub][t] = r * 4 + s of the module's 4x4 kernel
+static CbPack cb_s2_pack(int form)
+{
+    CbPack pk{};
+    pk.ntap = 8;
+    if (form == 0) {
+        pk.nsub = 2; pk.nphase = 1;
+        for (int e = 0; e < 2; ++e)
+            for (int t = 0; t < 8; ++t) {
+                const int ri = t >> 2, sx = t & 3, rr = e ? 2 * ri : 2 * ri + 1;
+                pk.srctap[0][e][t] = rr * 4 + sx;
+            }
+        return pk;
+    }
+    pk.nsub = 1; pk.nphase = 2;
+    for (int ey = 0; ey < 2; ++ey)
+        for (int t = 0; t < 8; ++t) {
+            const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
+            const int rr = ey == 0 ? (ai ? 3 : 1) : (ai ? 2 : 0), ss = ex == 0 ? (bi ? 3 : 1) : (bi ? 2 : 0);
+            pk.srctap[ey][0][t] = rr * 4 + ss;
+        }
+    return pk;
+}
+
 // k4 s2 p1.  weight [Kc][Cf][4][4]: element (coarse channel kc, fine channel cf, r, s) at w[kc * skc + cf * scf + r * 4 + s].
 // form 0 (fine -> coarse): in = fine [B,Cf,2nh,2nw], out = coarse [B,Kc,nh,nw].   form 1 (coarse -> fine): in = coarse, out = fine.
 int launch_conv_bf16_s2(int form, const void* in, const float* w, void* out, int B, int Kc, int Cf, int nh, int nw, long skc, long scf,
@@ -570,24 +604,8 @@ int launch_conv_bf16_s2(int form, const void* in, const float* w, void* out, int
     if (int rc = cb_geometry_s2(form, B, C, K, nh, nw, &g)) return rc;
     const size_t need = conv_bf16_s2_ws_bytes(form, B, C, K, nh, nw);
     if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "bf16 direct 4x4 stride-2 conv: workspace %zu < %zu", ws_bytes, need);
-    CbPack pk{};
-    pk.ntap = 8;
-    if (form == 0) {
-        pk.nsub = 2; pk.nphase = 1;
-        for (int e = 0; e < 2; ++e)
-            for (int t = 0; t < 8; ++t) {
-                const int ri = t >> 2, sx = t & 3, rr = e ? 2 * ri : 2 * ri + 1;
-                pk.srctap[0][e][t] = rr * 4 + sx;
-            }
-        return cb_launch<CB_F2C>(g, pk, in, w, out, scf, skc, out_bf16, ws, st, 16.0);
-    }
-    pk.nsub = 1; pk.nphase = 2;
-    for (int ey = 0; ey < 2; ++ey)
-        for (int t = 0; t < 8; ++t) {
-            const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
-            const int rr = ey == 0 ? (ai ? 3 : 1) : (ai ? 2 : 0), ss = ex == 0 ? (bi ? 3 : 1) : (bi ? 2 : 0);
-            pk.srctap[ey][0][t] = rr * 4 + ss;
-        }
+    const CbPack pk = cb_s2_pack(form);
+    if (form == 0) return cb_launch<CB_F2C>(g, pk, in, w, out, scf, skc, out_bf16, ws, st, 16.0);
     return cb_launch<CB_C2F>(g, pk, in, w, out, skc, scf, out_bf16, ws, st, 4.0);
 }
 
@@ -836,6 +854,269 @@ int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C
     }
     profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * C * (double)(g.ktiles * CX_K) * outs, 2.0 * 9.0 * C * (double)K * outs);
     return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16x3_kernel");
+}
+
+// =====================================================================================================================================
+// The k4 s2 p1 forms (F2C / C2F above) on FP32 tensors with the same split-bf16 operands ("direct_bf16x3_s2", ipsr_conv4x4s2_bf16x3):
+// conv_bf16x3_kernel's structure on the geometry, tap maps and source-tap tables of the bf16 stride-2 kernel (cb_s2_form, cb_s2_pack).
+//   * weights: cb_pack_weights_kernel<true> writes the hi and lo planes of Wp[kt][phase][cb][sub][t][cg][64 k][8 c]; a stage's A tile is
+//     2 x 16 KB by LDS-DMA, double-buffered;
+//   * activations: global -> registers -> split -> T, one item (c group, input row, 4 floats) per thread, 8 channels each.
+//     F2C: a stage = 16 channels x the R + 1 fine rows of ONE row parity, full fine width (up to 256 floats); the split store deals the four
+//     floats of an item to the two column-phase planes, T[hi | lo][ex][cg][R + 1][nw + 1][8 c].  C2F: a stage = 16 channels x R + 2 coarse
+//     rows, T[hi | lo][cg][R + 2][nw + 2][8 c]; a workgroup makes the fine rows of one parity, two accumulator sets hold the column parities
+//     and a lane stores both as one 8-byte vector.
+//   * T has ONE buffer, shared by the two F2C sub-stages.  A row slot outside the image for one row parity (slot 0 of the first tile under
+//     the odd rows, slot R of the last tile under the even rows) lies inside it for the other, so rows outside the image are WRITTEN as
+//     zeros every stage (conv_bf16x3_kernel's "they keep T's zeros" does not hold here); only the halo columns keep their initial zeros.
+// Workgroup = 512 threads = 8 waves (1 x 8), tile 64 channels x 256 lane-grid pixels, a wave owns 64 x 32 (C2F: twice, the column parities):
+// per tap 4 A + 2 B fragment reads for 6 MFMAs.  LDS: A[2] = 2 x 32 KB | T <= 48.5 KB (F2C at nw = 128: 8 planes x 3 rows x 129 positions).
+// Small maps: the reduction cut of cb_finish (cb_cut_reduction), fp32 partials behind the packed planes, cb_split_reduce_kernel<float>.
+// Supported: coarse width nw in {16, 32, 64, 128}, nh a multiple of 256 / nw, reduction channels a multiple of 16.
+constexpr int C2_K = 64, C2_A_BYTES = 2 * 8 * 2 * C2_K * 16;
+
+template <int MODE>
+__global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const float* __restrict__ in, const uint4* __restrict__ Wp, size_t lo_plane,
+                                                                      CbGeom g, float* __restrict__ out)
+{
+    static_assert(MODE == CB_F2C || MODE == CB_C2F, "form");
+    constexpr int KT = C2_K, NTAP = 8, NSET = MODE == CB_C2F ? 2 : 1, TPSET = NTAP / NSET;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | T
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    const int per_pt = g.ktiles * g.nphase * g.nsplit;
+    const int pt = L / per_pt, kps = L - pt * per_pt;
+    const int split = kps % g.nsplit, kp = kps / g.nsplit;
+    const int kt = kp % g.ktiles, phase = kp / g.ktiles;
+    const int s_lo = split * g.sps, s_hi = min(g.nstage, s_lo + g.sps);        // (F2C: sps is even, a run starts on sub-stage 0)
+    const size_t HWi = (size_t)g.Hin * g.Win, HWo = (size_t)g.Hout * g.Wout;
+    out += (size_t)split * g.B * g.K * HWo;
+    const int tiles_per_img = g.Hl / g.R;
+    const int b = pt / tiles_per_img, y0 = (pt - b * tiles_per_img) * g.R;
+
+    // ---- stage-invariant addresses ------------------------------------------------------------------------------------------
+    // activation item = (c group, row slot, 4-float segment of the input row): at most 2 x 3 x 64 = 384, one per thread
+    const int segs = g.Win >> 2, nitem = 2 * g.NR * segs;
+    const bool item = tid < nitem;
+    const int seg = tid % segs, row = (tid / segs) % g.NR, cg = min(tid / (segs * g.NR), 1);
+    const int ya = g.ymul * y0 + g.yoff[0] + g.rowstep * row, yb = g.ymul * y0 + g.yoff[1] + g.rowstep * row;     // sub-stage 0 / 1 (F2C)
+    const bool in_a = (unsigned)ya < (unsigned)g.Hin, in_b = (unsigned)yb < (unsigned)g.Hin;
+    const float* gbase = in + ((size_t)b * g.C + cg * 8) * HWi + seg * 4;
+    const float* gxa = gbase + (size_t)(in_a ? ya : 0) * g.Win;                 // a row outside the image reads row 0 and stores zeros
+    const float* gxb = gbase + (size_t)(in_b ? yb : 0) * g.Win;
+    const size_t xstride = (size_t)CB_C * HWi;
+    const int t_base = 2 * C2_A_BYTES, t_plane = g.t_bytes / 2;
+    // F2C: float i of the item is fine column 4 seg + i = 2 j + ex -> plane ex, position j + ex (plane 1 starts at j = -1)
+    const int t_wr = t_base + (cg * g.NPOS + row * g.PW + (MODE == CB_F2C ? 2 * seg : 4 * seg + 1)) * 16;
+    const int t_ex = 2 * g.NPOS * 16;
+    // A tile DMA: 2 planes x 16 pieces of 1 KiB, piece = wave + 8 j
+    constexpr int PPP = NTAP * KT / 32, NPIECE = 2 * PPP, APW = NPIECE / 8;
+    const uint4* ga = Wp + ((size_t)(kt * g.nphase + phase) * g.nstage) * (NTAP * 2 * KT) + lane;
+    const int a_off = (h * KT + r) * 16;
+    const int p = wave * 32 + r;
+    const int b_off = t_base + (h * g.NPOS + (p >> g.wshift) * g.PW + (p & (g.Wl - 1))) * 16;
+
+    f32x16 acc[NSET][2];
+#pragma unroll
+    for (int q = 0; q < NSET; ++q)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[q][i][e] = 0.0f;
+
+    auto dma_a = [&](int buf, int stage) {
+        const uint4* src = ga + (size_t)stage * (NTAP * 2 * KT);
+#pragma unroll
+        for (int j = 0; j < APW; ++j) {
+            const int piece = wave + 8 * j;
+            const uint4* s = piece < PPP ? src + piece * 64 : src + lo_plane + (piece - PPP) * 64;
+            __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(lds + buf * C2_A_BYTES + piece * 1024), 16, 0, 0);
+        }
+    };
+    f32x4 xr[8];
+    auto load_x = [&](int stage) {
+        if (item) {
+            const int cb = MODE == CB_F2C ? stage >> 1 : stage;
+            const float* src = ((MODE == CB_F2C && (stage & 1)) ? gxb : gxa) + (size_t)cb * xstride;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) xr[c] = *reinterpret_cast<const f32x4*>(src + (size_t)c * HWi);
+        }
+    };
+    auto split_store = [&](int stage) {                        // registers -> T (hi planes, lo planes)
+        if (item) {
+            const bool inside = (MODE == CB_F2C && (stage & 1)) ? in_b : in_a;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                unsigned hi[8], lo[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const float v = inside ? xr[c][i] : 0.0f;
+                    hi[c] = __builtin_bit_cast(unsigned short, (__bf16)v);
+                    lo[c] = __builtin_bit_cast(unsigned short, (__bf16)(v - __uint_as_float(hi[c] << 16)));
+                }
+                u32x4 vh, vl;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { vh[c] = hi[2 * c] | (hi[2 * c + 1] << 16); vl[c] = lo[2 * c] | (lo[2 * c + 1] << 16); }
+                const int at = t_wr + (MODE == CB_F2C ? (i & 1) * t_ex + ((i >> 1) + (i & 1)) * 16 : i * 16);
+                *reinterpret_cast<u32x4*>(lds + at) = vh;
+                *reinterpret_cast<u32x4*>(lds + at + t_plane) = vl;
+            }
+        }
+    };
+
+    // T starts as zeros: the halo columns are never written
+    for (int i = tid; i < g.t_bytes / 16; i += CB_THREADS) *reinterpret_cast<u32x4*>(lds + t_base + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    load_x(s_lo);
+    dma_a(0, s_lo);
+    __syncthreads();
+    split_store(s_lo);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    for (int s = s_lo; s < s_hi; ++s) {
+        const int cur = (s - s_lo) & 1;
+        if (s + 1 < s_hi) {
+            load_x(s + 1);                                     // consumed behind this stage's multiplications
+            dma_a(cur ^ 1, s + 1);                             // A[nxt] was last read in stage s-1
+        }
+        const unsigned char* A = lds + cur * C2_A_BYTES + a_off;
+        const unsigned char* T = lds + b_off;
+        const int* toff = g.tapoff[MODE == CB_F2C ? (s & 1) : phase];
+        // the tap pipeline of conv_bf16x3_kernel: the six fragments of tap t + 1 are read behind tap t's first multiplication
+        bf16x8 fa[2][2][2], fb[2][2];                          // [set][plane][row tile], [set][plane]
+        auto load_tap = [&](int t, int set) {
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+                fa[set][pl][0] = *reinterpret_cast<const bf16x8*>(A + pl * (C2_A_BYTES / 2) + (t * 2 * KT) * 16);
+                fa[set][pl][1] = *reinterpret_cast<const bf16x8*>(A + pl * (C2_A_BYTES / 2) + (t * 2 * KT + 32) * 16);
+                fb[set][pl] = *reinterpret_cast<const bf16x8*>(T + pl * t_plane + toff[t] * 16);
+            }
+        };
+        load_tap(0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+#pragma unroll
+        for (int t = 0; t < NTAP; ++t) {
+            const int q = t / TPSET, set = t & 1;
+            if (t + 1 < NTAP) load_tap(t + 1, set ^ 1);
+            // smallest terms first: lo(w) hi(x), hi(w) lo(x), hi(w) hi(x); the two row tiles alternate so that no MFMA waits for its predecessor
+            acc[q][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][1][0], fb[set][0], acc[q][0], 0, 0, 0);
+            acc[q][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][1][1], fb[set][0], acc[q][1], 0, 0, 0);
+            acc[q][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][0], fb[set][1], acc[q][0], 0, 0, 0);
+            acc[q][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][1], fb[set][1], acc[q][1], 0, 0, 0);
+            acc[q][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][0], fb[set][0], acc[q][0], 0, 0, 0);
+            acc[q][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[set][0][1], fb[set][0], acc[q][1], 0, 0, 0);
+            if (t + 1 < NTAP) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this stage's DMA and loads are the next stage's operands
+        __syncthreads();                                       // every wave is done reading T
+        if (s + 1 < s_hi) {
+            split_store(s + 1);
+            __syncthreads();
+        }
+    }
+
+    // epilogue: lane = lane-grid pixel, register = channel
+    const int py = y0 + (p >> g.wshift), px = p & (g.Wl - 1);
+    if (MODE == CB_C2F) {
+        // fine row 2 py + phase, fine columns 2 px and 2 px + 1 (the two accumulator sets): one 8-byte store
+        float* op = out + (size_t)b * g.K * HWo + (size_t)(2 * py + phase) * g.Wout + 2 * px;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int k = kt * KT + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (k < g.K) *reinterpret_cast<float2*>(op + (size_t)k * HWo) = make_float2(acc[0][i][e], acc[NSET - 1][i][e]);
+            }
+    } else {
+        float* op = out + (size_t)b * g.K * HWo + (size_t)py * g.Wout + px;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int k = kt * KT + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (k < g.K) op[(size_t)k * HWo] = acc[0][i][e];
+            }
+    }
+}
+
+// form 0: fine -> coarse (C = Cf reduced, K = Kc produced); 1: coarse -> fine.  The limits, before any launch.
+static int c2_geometry(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
+{
+    const char* who = "split-bf16 direct 4x4 stride-2 conv";
+    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d reduction channels are not a multiple of %d", who, C, CB_C);
+    if (nw != 16 && nw != 32 && nw != 64 && nw != 128) return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width %d (16 .. 128, a power of two)", who, nw);
+    if (int rc = cb_lane_grid(nh, nw, CB_P, g, who)) return rc;
+    g->B = B; g->C = C; g->K = K;
+    cb_s2_form(form, nh, nw, g);
+    g->kt = C2_K;
+    g->ktiles = (K + C2_K - 1) / C2_K;
+    g->ptiles = B * (g->Hl / g->R);
+    g->nstage = (C / CB_C) * g->nsub;
+    cb_cut_reduction(g);
+    g->a_bytes = C2_A_BYTES;
+    g->t_bytes = (int)align_up((size_t)2 * g->nsub * 2 * g->NPOS * 16, 256);     // hi | lo, each [column phase][c group][positions]
+    g->raw_bytes = 0; g->raw1 = 0;
+    if (2 * C2_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (g->Win / 4) > CB_THREADS)
+        return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, g->Win);
+    return IPSR_OK;
+}
+
+static size_t c2_pack_bytes(const CbGeom& g) { return (size_t)g.ktiles * g.nphase * g.nstage * 8 * 2 * C2_K * 16; }      // one plane
+
+// zero page | hi plane | lo plane | fp32 partials of a split reduction
+size_t conv_bf16x3_s2_ws_bytes(int form, int B, int C, int K, int nh, int nw)
+{
+    CbGeom g;
+    if (c2_geometry(form, B, C, K, nh, nw, &g) != IPSR_OK) return 0;
+    return 256 + align_up(2 * c2_pack_bytes(g), 256) + cb_partial_bytes(g);
+}
+
+template <int MODE>
+static int c2_launch_kernel(const CbGeom& g, const float* in, const uint4* Wp, size_t lo_plane, float* out, hipStream_t st)
+{
+    // the attribute belongs to the device the launch goes to: set per launch, not once per process
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
+    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "conv_bf16x3_s2_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", CB_LDS_MAX, hipGetErrorString(e));
+    const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
+    conv_bf16x3_s2_kernel<MODE><<<grid, CB_THREADS, 2 * C2_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, out);
+    return IPSR_OK;
+}
+
+// weight and forms as in launch_conv_bf16_s2; in / out fp32
+int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out, int B, int Kc, int Cf, int nh, int nw, long skc, long scf,
+                          void* ws, size_t ws_bytes, hipStream_t st)
+{
+    CbGeom g;
+    const int C = form == 0 ? Cf : Kc, K = form == 0 ? Kc : Cf;
+    if (int rc = c2_geometry(form, B, C, K, nh, nw, &g)) return rc;
+    const size_t need = conv_bf16x3_s2_ws_bytes(form, B, C, K, nh, nw);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 direct 4x4 stride-2 conv: workspace %zu < %zu", ws_bytes, need);
+    uint4* zero_page = static_cast<uint4*>(ws);
+    uint4* Wp = zero_page + 16;
+    const size_t lo_plane = c2_pack_bytes(g) / 16;
+    CbPack pk = cb_s2_pack(form);
+    pk.kt = C2_K;
+    cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * C2_K, 256), C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(
+        w, C, K, form == 0 ? scf : skc, form == 0 ? skc : scf, pk, Wp, zero_page, lo_plane);
+    if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
+    float* dst = g.nsplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wp) + align_up(2 * c2_pack_bytes(g), 256)) : out;
+    const double outs = (double)B * g.Hout * g.Wout, taps = form == 0 ? 16.0 : 4.0;
+    profile_mark_start(st, 4);
+    if (int rc = form == 0 ? c2_launch_kernel<CB_F2C>(g, in, Wp, lo_plane, dst, st) : c2_launch_kernel<CB_C2F>(g, in, Wp, lo_plane, dst, st)) return rc;
+    if (g.nsplit > 1) {
+        if (int rc = check_launch("conv_bf16x3_s2_kernel")) return rc;
+        const size_t n = (size_t)B * K * g.Hout * g.Wout;      // a multiple of 4: Wout is
+        cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(dst, g.nsplit, n / 4, out);
+    }
+    profile_mark_stop(st, 4, 3.0 * 2.0 * taps * C * (double)(g.ktiles * C2_K) * outs, 2.0 * taps * C * (double)K * outs);
+    return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16x3_s2_kernel");
 }
 
 // =====================================================================================================================================
@@ -1632,6 +1913,24 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: in / out / workspace must be 16-byte aligned");
     // weight [Kc][Cf][4][4] in both modules (Conv2d: [Cout][Cin], ConvTranspose2d: [Cin][Cout]), as in ipsr_conv4x4s2_winograd
     return launch_conv_bf16_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
+{
+    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_workspace_bytes: bad argument"); return 0; }
+    return conv_bf16x3_s2_ws_bytes(mode, B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
+}
+
+int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
+                          void* ws, size_t ws_bytes, void* stream)
+{
+    if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: null pointer");
+    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1)
+        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: bad argument (mode %d: 0 fine -> coarse, 1 coarse -> fine)", mode);
+    // in: its fp32 rows are read as 16-byte vectors; out: the coarse -> fine rows leave as 8-byte pairs, the split reduction stores 16 bytes
+    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: in / out / workspace must be 16-byte aligned");
+    return launch_conv_bf16x3_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)

@@ -30,7 +30,10 @@ pass and what the engine needs; a new engine is one record there plus its rule i
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3")`, `opt.conv_math`): the direct kernel on split-bf16
                                   operands (hi + lo, three products) for the forward / input gradient of the k3 s1 p1 layers that "winograd"
-                                  has by default — no transform passes, error ~6e-6 of the output scale; weight gradients stay where they are
+                                  has by default — no transform passes, error ~6e-6 of the output scale; weight gradients stay where they are.
+                                  Under `set_conv_math(fp32="direct_bf16x3_s2")` also the forward / input gradient of the k4 s2 p1 layers
+                                  that `_bf16x3_s2_wins` names ("wino_s2"'s, 1.2-2.5x it, and one row of MIOpen's, 2.7x), one launch instead
+                                  of three to four
   "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3_dw")`): the weight gradient of the k3 s1 p1 layers
                                   that "winograd" / "miopen" have by default, as a pixel reduction on split-bf16 operands (two launches, the
                                   split in the kernel); the data passes run "bf16x3d" as under "direct_bf16x3"
@@ -56,14 +59,18 @@ _FORCE = None          # test hook: overrides the environment
 # opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).  "direct_bf16x3" for
 # fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d";
 # "direct_bf16x3_dw" does the same and `select_wrw` moves the k3 s1 p1 weight gradients of "winograd" / "miopen" to "bf16x3w".
-_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw")
+# "direct_bf16x3_s2" does what "direct_bf16x3_dw" does and `select` moves the k4 s2 p1 data passes of `_bf16x3_s2_wins` to "bf16x3d".
+_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2")
+_DIRECT_WRW_MATH = ("direct_bf16x3_dw", "direct_bf16x3_s2")
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
 
 
 def set_conv_math(fp32=None, bf16=None):
     """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast); fp32="direct_bf16x3":
     the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere;
-    fp32="direct_bf16x3_dw": that, and the direct split-bf16 weight gradient where `select_wrw` has "winograd" or "miopen"."""
+    fp32="direct_bf16x3_dw": that, and the direct split-bf16 weight gradient where `select_wrw` has "winograd" or "miopen";
+    fp32="direct_bf16x3_s2": that, and the direct split-bf16 kernel for the forward / input gradient of the k4 s2 p1 layers where `select`
+    has "wino_s2" (`_bf16x3_s2_wins`; also the one k4 s2 p1 row of MIOpen's that measured faster).  The three direct names are for fp32 activations only."""
     from .. import ops as _ops
     for key, val in (("fp32", fp32), ("bf16", bf16)):
         if val is not None:
@@ -120,6 +127,8 @@ def _select_any(op, lay, bf16):
     if not bf16:
         if eng == "winograd" and _MATH["fp32"] in _DIRECT_MATH and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
             return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
+        if _MATH["fp32"] == "direct_bf16x3_s2" and _bf16x3_s2_wins(eng, op, lay):
+            return "bf16x3d"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
         return eng
@@ -330,7 +339,7 @@ def _select_wrw_any(lay, bf16):
         # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
         if thin and eng == "miopen":
             return "thin_mfma"
-        if _MATH["fp32"] == "direct_bf16x3_dw" and _bf16x3_wrw_wins(eng, lay):
+        if _MATH["fp32"] in _DIRECT_WRW_MATH and _bf16x3_wrw_wins(eng, lay):
             return "bf16x3w"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
@@ -357,8 +366,23 @@ def _bf16_direct_wrw(lay):
     return "miopen"
 
 
+def _bf16x3_s2_wins(eng, op, lay):
+    """fp32 activations under the opt-in "direct_bf16x3_s2": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct
+    split-bf16 kernel (ops.conv4x4s2_bf16x3) where it takes the shape.  Measured at batch 8 on every such row of the step
+    (profiles/direct_bf16x3_s2_layers.txt): 1.23-2.51x "wino_s2" (0.037-0.106 vs 0.079-0.197 ms), every row's slowest round of the kernel faster than
+    the fastest of "wino_s2", no row loses — so the rule is every "wino_s2" data pass the kernel takes; other batches and channel counts inside it were not measured.
+    Of MIOpen's k4 s2 p1 rows the kernel takes one in the step, netG's outermost ConvTranspose2d 64 -> 64 @128 input gradient (0.072 vs
+    0.197 ms, 2.72x): that shape moves too, at any batch though only batch 8 was measured; nothing else of MIOpen's does.  A forced engine is never overridden."""
+    if eng not in ("wino_s2", "miopen") or _mode() != "auto":
+        return False
+    g = _s2_geometry(lay)
+    if g is None or (eng == "miopen" and not (_s2_mode(op) == ops.S2_FINE_TO_COARSE and g == (64, 64, 128, 128))):
+        return False
+    return ops.conv4x4s2_bf16x3_supported(_s2_mode(op), lay[1], *g)
+
+
 def _bf16x3_wrw_wins(eng, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
+    """fp32 activations under the opt-in "direct_bf16x3_dw" / "direct_bf16x3_s2": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
     split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured at batch 8
     (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient on 256 -> 256 /
     512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer multiplications and its
@@ -427,7 +451,10 @@ def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
 
 
 def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
-    """fp32 activations on the direct split-bf16 kernel (k3 s1 p1); frozen weights keep their packed planes as in `_bf16d_data`."""
+    """fp32 activations on the direct split-bf16 kernels: k3 s1 p1 (frozen weights keep their packed planes as in `_bf16d_data`), or
+    k4 s2 p1 in its coarse / fine form."""
+    if lay[6] == 4:
+        return ops.conv4x4s2_bf16x3(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay))
     param = w if param is None else param
     frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
     return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], keep_packed=frozen, pack_key=param)

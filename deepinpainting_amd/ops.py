@@ -454,7 +454,8 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 # "direct_bf16x3" = the k3 s1 p1 data passes the dispatcher has on "winograd" go to the DIRECT kernel on split-bf16 operands instead
 # (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply.
 # "direct_bf16x3_dw" = the same, and the k3 s1 p1 weight gradients go to the direct split-bf16 kernel too (conv3x3_bf16x3_wrw)
-MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0}
+# "direct_bf16x3_s2" = the same, and the k4 s2 p1 data passes the dispatcher has on "wino_s2" go to the direct split-bf16 kernel (conv4x4s2_bf16x3)
+MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0, "direct_bf16x3_s2": 0}
 
 
 def _io_code(in_bf16, out_dtype):
@@ -687,6 +688,30 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
     ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_workspace_bytes(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_conv4x4s2_bf16: mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
     _lib.check(L.ipsr_conv4x4s2_bf16(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, int(out_dtype == torch.bfloat16),
                                      ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4s2_bf16")
+    return out
+
+
+def conv4x4s2_bf16x3_supported(mode, B, Kc, Cf, nh, nw):
+    return mode in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE) and _lib.lib().ipsr_conv4x4s2_bf16x3_workspace_bytes(mode, B, Kc, Cf, nh, nw) > 0
+
+
+def conv4x4s2_bf16x3(mode, inp, weight, B, Kc, Cf, nh, nw):
+    """The k4 s2 p1 layers on FP32 tensors as ONE direct implicit GEMM on the bf16 matrix cores with split operands (ipsr_conv4x4s2_bf16x3,
+    csrc/conv_bf16.hip): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32 accumulation; fp32 in, fp32 out.  mode, shapes
+    and weight as in conv4x4s2_bf16."""
+    inp = _req(inp, torch.float32, "conv input")
+    weight = _req(weight, torch.float32, "conv weight")
+    if mode not in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE):
+        raise ValueError("conv4x4s2_bf16x3: mode %r" % (mode,))
+    want_in = (B, Cf, 2 * nh, 2 * nw) if mode == S2_FINE_TO_COARSE else (B, Kc, nh, nw)
+    if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
+        raise RuntimeError("conv4x4s2_bf16x3 mode %d: input %s / weight %s do not match %s / %s" % (mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
+    L = _lib.lib()
+    oshape = (B, Kc, nh, nw) if mode == S2_FINE_TO_COARSE else (B, Cf, 2 * nh, 2 * nw)
+    out = _empty(oshape, dtype=torch.float32, device=inp.device)
+    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16x3_workspace_bytes(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_conv4x4s2_bf16x3: mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
+    _lib.check(L.ipsr_conv4x4s2_bf16x3(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
+               "ipsr_conv4x4s2_bf16x3")
     return out
 
 

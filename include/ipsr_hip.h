@@ -477,6 +477,16 @@ int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* 
 size_t ipsr_conv4x4s2_bf16_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
                         void* ws, size_t ws_bytes, void* stream);
+/* the same two passes on FP32 tensors with SPLIT-bf16 operands (the opt-in arithmetic "direct_bf16x3_s2" of the fp32 nets): fp32 NCHW in and
+ * out, every operand a = hi + lo with hi = bf16(a), lo = bf16(a - hi), every product lo*hi + hi*lo + hi*hi on the bf16 matrix cores, fp32
+ * accumulation; the split happens inside the kernel (one launch per pass plus the weight packing, no fp32-wide intermediates).  Error per
+ * output <= 2^-16 of sum |x||w| plus the fp32 accumulation's.  mode and weight as above (an entry of its own: ipsr_conv4x4s2_bf16 takes any
+ * non-zero out_bf16 as "bf16 out").  Supported: nw in {16, 32, 64, 128} in both modes, nh a multiple of 256 / nw, reduction channels (mode 0:
+ * Cf, mode 1: Kc) a multiple of 16; anything else -> IPSR_ERR_UNSUPPORTED, checked before any launch.  The workspace query returns 0 where
+ * the shape is unsupported, reason in ipsr_last_error(); `in`, `out`, `ws` must be 16-byte aligned; any other mode is IPSR_ERR_INVALID. */
+size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw);
+int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
+                          void* ws, size_t ws_bytes, void* stream);
 /* weight gradient of the 4x4 stride-2 layers: fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw] bf16 -> dw [Kc][Cf][4][4] fp32 (both modules' layout);
  * nw in {16, 32, 64}, nh a multiple of 64 / nw.  Partial sums added in a fixed order by a second launch. */
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);

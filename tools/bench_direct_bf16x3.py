@@ -8,10 +8,13 @@
   wrw      the weight gradient of the same shapes, as Conv2d and as ConvTranspose2d (ops.conv3x3_bf16x3_wrw, engine "bf16x3w",
            opt.conv_math="direct_bf16x3_dw"): the new engine against the engine `select_wrw` answers for the shape by default, same
            process, same rounds; err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the whole batch.
+  s2       every k4 s2 p1 layer of the step at batch 8, forward and input gradient (ops.conv4x4s2_bf16x3, engine "bf16x3d" under
+           opt.conv_math="direct_bf16x3_s2"): the new kernel against the engine `select` answers for the shape under conv_math "fp32",
+           same process, same rounds; err = max |y - y64| / max |y64| against the fp64 convolution (first two images).
   steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "direct_bf16x3",
-           "direct_bf16x3_dw" and "bf16x3" in ONE process, alternated over `--rounds` rounds.
+           "direct_bf16x3_dw", "direct_bf16x3_s2" and "bf16x3" in ONE process, alternated over `--rounds` rounds.
 
-    python tools/bench_direct_bf16x3.py [--what layers wrw steps] [--out profiles/direct_bf16x3_layers.txt]
+    python tools/bench_direct_bf16x3.py [--what layers wrw s2 steps] [--out profiles/direct_bf16x3_layers.txt]
 """
 import argparse
 import os
@@ -122,6 +125,61 @@ def wrw(B, iters, rounds, emit):
               md["today"] / md["direct"]))
 
 
+# (kind, Kc, Cf, coarse n): Conv2d Cf -> Kc on 2n x 2n, ConvTranspose2d Kc -> Cf on n x n (netP / netD / netF down, netP / netG up)
+S2_LAYERS = [("conv", 128, 64, 64), ("conv", 256, 128, 32), ("conv", 512, 256, 16), ("conv", 512, 512, 8), ("conv", 512, 512, 4),
+             ("convT", 64, 64, 128), ("convT", 128, 128, 64), ("convT", 256, 256, 32), ("convT", 512, 512, 16), ("convT", 256, 64, 64),
+             ("convT", 512, 128, 32), ("convT", 1024, 256, 16), ("convT", 1024, 512, 8), ("convT", 512, 512, 8)]
+
+
+def s2(B, iters, rounds, emit):
+    from deepinpainting_amd.models import hipconv
+    g = torch.Generator(device="cuda").manual_seed(7)
+    hipconv.set_conv_math(fp32="fp32")
+    emit("k4 s2 p1 data passes, batch %d, fp32 NCHW in and out; ms = device time per call (HIP events, %d calls per burst, median of %d alternated "
+         "rounds, [min..max]); TF = useful flop / time" % (B, iters, rounds))
+    emit("err = max |y - y64| / max |y64| against the fp64 convolution of the unrounded operands; today = the engine select answers under conv_math fp32")
+    emit("%-25s %-5s | %-40s | %-44s | %s" % ("layer", "pass", "direct bf16x3  ms [min..max]  TF   err", "today's engine  ms [min..max]  err", "today / direct"))
+    for kind, Kc, Cf, n in S2_LAYERS:
+        tr = kind == "convT"
+        Cin, Cout, H = (Kc, Cf, n) if tr else (Cf, Kc, 2 * n)
+        Ho = 2 * n if tr else n
+        lay = (tr, B, Cin, H, H, Cout, 4, 2, 1, 1)
+        w = torch.randn(Kc, Cf, 4, 4, device="cuda", generator=g) * (1.0 / (4.0 * (Cin ** 0.5)))
+        x = torch.randn(B, Cin, H, H, device="cuda", generator=g)
+        dy = torch.randn(B, Cout, Ho, Ho, device="cuda", generator=g)
+        fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if tr else (ops.CONV_FWD, ops.CONV_BWD_DATA)
+        flops = 2.0 * 16 * Kc * Cf * B * n * n
+        for name, op, inp in (("fwd", fop, x), ("bwdD", bop, dy)):
+            mode = hipconv._s2_mode(op)
+            label = "%-5s Kc=%4d Cf=%4d n=%-3d %-5s" % (kind, Kc, Cf, n, name)
+            today = hipconv.select(op, B, Cin, H, H, Cout, 4, 2, 1, 1)
+            if not ops.conv4x4s2_bf16x3_supported(mode, B, Kc, Cf, n, n):
+                emit("%s | unsupported (today: %s)" % (label, today))
+                continue
+            if today != "miopen":
+                base = lambda: hipconv._run_data(today, op, inp, w, lay, "fp32", torch.float32)
+            elif name == "fwd":
+                base = (lambda: F.conv_transpose2d(x, w, None, 2, 1)) if tr else (lambda: F.conv2d(x, w, None, 2, 1))
+            else:
+                base = lambda: torch.ops.aten.convolution_backward(dy, x, w, None, [2, 2], [1, 1], [1, 1], tr, [0, 0], 1, [True, False, False])[0]
+            f64 = F.conv2d if mode == ops.S2_FINE_TO_COARSE else F.conv_transpose2d
+            ref = f64(inp[:2].double(), w.double(), None, 2, 1)
+            engines = [("direct", lambda: ops.conv4x4s2_bf16x3(mode, inp, w, B, Kc, Cf, n, n)), ("today", base)]
+            err, ms = {}, {k: [] for k, _ in engines}
+            for k, fn in engines:
+                for _ in range(3):
+                    y = fn()
+                err[k] = float((y[:2].double() - ref).abs().max() / ref.abs().max())
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for k, fn in engines:
+                    ms[k].append(burst_ms(fn, iters))
+            md = {k: statistics.median(v) for k, v in ms.items()}
+            emit("%s | %7.4f [%6.4f..%6.4f] %6.1f %.1e | %-9s %7.4f [%6.4f..%6.4f] %.1e | %.2fx" %
+                 (label, md["direct"], min(ms["direct"]), max(ms["direct"]), flops / md["direct"] / 1e9, err["direct"], today, md["today"],
+                  min(ms["today"]), max(ms["today"]), err["today"], md["today"] / md["direct"]))
+
+
 def steps(B, ksteps, rounds, emit):
     from deepinpainting_amd.models import hipconv
     from deepinpainting_amd.models.models import create_model
@@ -132,7 +190,7 @@ def steps(B, ksteps, rounds, emit):
     torch.manual_seed(1234)
     model = bench.quiet(create_model, opt)
     img, mask, ref = bench.synthetic_batch(device, B, 1234)
-    maths = ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "bf16x3")
+    maths = ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "bf16x3")
     rate = {m: [] for m in maths}
     try:
         for m in maths:                                        # every arithmetic's shapes warmed before any is timed
@@ -161,7 +219,7 @@ def steps(B, ksteps, rounds, emit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "steps"))
+    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "s2", "steps"))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
@@ -182,6 +240,8 @@ def main():
         layers(a.batch, a.iters, a.rounds, emit)
     if "wrw" in a.what:
         wrw(a.batch, a.iters, a.rounds, emit)
+    if "s2" in a.what:
+        s2(a.batch, a.iters, a.rounds, emit)
     if "steps" in a.what:
         steps(a.batch, a.steps, a.rounds, emit)
 
