@@ -1849,6 +1849,260 @@ int launch_conv_bf16_wrw_s2(const void* fine, const void* coarse, float* dW, int
     return check_launch("conv_bf16_wrw_s2_reduce_kernel");
 }
 
+// =====================================================================================================================================
+// The same k4 s2 p1 weight gradient on FP32 tensors with split-bf16 operands (ipsr_conv4x4s2_bf16x3_wrw; the opt-in arithmetic
+// "direct_bf16x3_s2_dw" of the fp32 nets).  Operands and products as in conv_bf16x3_wrw_kernel: v = hi + lo, hi = bf16(v),
+// lo = bf16(v - hi), every product lo*hi + hi*lo + hi*hi into the same fp32 accumulator, smallest terms first, lo*lo dropped.
+// Tile, wave layout, fragments (aligned 16-byte coarse reads; 16 consecutive fine pixels + the dword before and after, the even / odd
+// halves by v_perm_b32 — now from a hi and a lo image), run cut and slab reduction are conv_bf16_wrw_s2_kernel's.  The plan is
+// conv_bf16x3_wrw_kernel's, because two coarse buffers and a (2 RS + 1)-pair ring of hi + lo images do not fit:
+//   * the split happens in the kernel, global -> registers -> v_cvt_pk_bf16_f32 -> LDS; the REGISTERS are the second buffer: the loads of
+//     stage s + 1 (16 dwords of coarse, 16 of fine per lane) fly during the multiplications of stage s, conversion and stores follow between
+//     two barriers, so LDS holds ONE coarse buffer and a ring of the RS + 1 row pairs a stage reads (pair i = fine rows 2 i - 1, 2 i in
+//     entry i mod (RS + 1)); the next stage's RS new pairs — 2 RS consecutive fine rows, 256 contiguous floats per channel — replace the
+//     RS oldest;
+//   * a fine row outside the image (row -1: the ring's initial zeros, written before anything else; row 2 nh: zeros STORED by the stage
+//     that would load it, so a slot that held data one stage earlier reads as zeros) and the channels past Cf are zeros; the halo slots
+//     of every (row, channel) are zeroed once and never written.
+// LDS: coarse hi | lo = 2 x 16 KB; ring hi | lo = 2 x (RS + 1) pairs x 2 rows x 32 cf x (2 nw / 8 + 3) slots x 16 B:
+//      nw = 16: 32768 + 71680 = 104448 B     nw = 32: 32768 + 67584 = 100352 B     nw = 64: 32768 + 77824 = 110592 B
+// nw = 128 is refused: a stage of 64 coarse pixels is half a coarse row, and a ring of whole fine rows costs 2 planes x 2 pairs x 2 rows x
+// 32 cf x 35 slots x 16 B = 143360 B + 32768 = 176128 B > 160 KB of LDS.
+// Supported: nw in {16, 32, 64}, nh a multiple of 64 / nw.  Deterministic: no atomics, every sum in a fixed order.
+struct X2Geom {
+    int B, Kc, Cf, nh, nw, wshift;
+    int RS, NPAIR, pitch;               // coarse rows per stage, ring entries (RS + 1 pairs of fine rows), slots per (fine row, channel)
+    int stages_per_wg, nsplit, ktiles, ctiles;
+    int ring_plane;                     // bytes of one plane (hi or lo) of the ring
+};
+
+__global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float* __restrict__ coarse, const float* __restrict__ fine, X2Geom g,
+                                                                     float* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // coarse hi | coarse lo | ring hi | ring lo
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, rh = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles = g.ktiles * g.ctiles;
+    const int tile = L % tiles, split = L / tiles;
+    const int kt = tile % g.ktiles, ct = tile / g.ktiles;
+    const int rows_per_wg = g.RS * g.stages_per_wg;
+    const int runs_per_img = g.nh / rows_per_wg;
+    const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
+    const int Hf = 2 * g.nh, Wf = 2 * g.nw;
+    const size_t HWc = (size_t)g.nh * g.nw, HWf = (size_t)Hf * Wf;
+    const int cprf = Wf >> 3;                                // 8-pixel chunks per fine row
+    unsigned char* const ring = lds + 2 * W2_A_BYTES;
+    const int row_bytes = W2_C * g.pitch * 16;
+    const int pair_bytes = 2 * row_bytes;
+
+    // ---- coarse rows: a stage's 64 pixels are contiguous in NCHW; a lane owns chunk c8 = tid & 7 of the channels (tid >> 3) + 64 j, slot
+    // k * 8 + (c8 ^ (k & 7)) as in the bf16 kernel (k & 7 is the same for both j) --------------------------------------------------------------
+    const int c8 = tid & 7, k0 = tid >> 3;
+    const float* ga[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int kc = kt * W2_K + k0 + 64 * j;
+        ga[j] = kc < g.Kc ? coarse + ((size_t)b * g.Kc + kc) * HWc + (size_t)ylo * g.nw + c8 * 8 : nullptr;
+    }
+    const int a_wr = ((k0 << 3) + (c8 ^ (k0 & 7))) * 16;     // + j * 8192
+    // ---- fine rows: the 2 RS new rows of a stage are 32 chunks per channel; a lane owns chunk fi = tid & 31 (row fr, chunk fx) of the
+    // channels (tid >> 5) + 16 j ------------------------------------------------------------------------------------------------------------
+    const int fi = tid & 31, c0 = tid >> 5;
+    const int fr = fi / cprf, fx = fi - fr * cprf;
+    const float* gf[2];                                      // channels past Cf: a valid address (the last channel), zeros are stored
+    bool fok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int cf = ct * W2_C + c0 + 16 * j;
+        fok[j] = cf < g.Cf;
+        gf[j] = fine + ((size_t)b * g.Cf + (fok[j] ? cf : g.Cf - 1)) * HWf + fi * 8;
+    }
+    const int f_wr = (c0 * g.pitch + 1 + fx) * 16;           // + j * 16 * pitch * 16
+
+    f32x16 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+
+    f32x4 ar[4], fw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ar[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};           // channels past Kc stay zeros
+    // stage s: its 64 coarse pixels, and the fine rows 2 y0 + 1 .. 2 y0 + 2 RS = the pairs y0 + 1 .. y0 + RS (what stage s reads beyond
+    // the last pair of stage s - 1)
+    auto load_stage = [&](int s) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (ga[j]) {
+                const float* src = ga[j] + (size_t)s * W2_PX;
+                ar[2 * j] = *reinterpret_cast<const f32x4*>(src);
+                ar[2 * j + 1] = *reinterpret_cast<const f32x4*>(src + 4);
+            }
+        // unconditional loads (no branch between the loads and the multiplications): the one row that can lie outside the image, row
+        // 2 nh, reads row 2 nh - 1 instead and store_stage stores zeros for it
+        const int yf0 = 2 * (ylo + s * g.RS) + 1;
+        const int yld = yf0 + fr < Hf ? yf0 : yf0 - 1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float* src = gf[j] + (size_t)yld * Wf;
+            fw[2 * j] = *reinterpret_cast<const f32x4*>(src);
+            fw[2 * j + 1] = *reinterpret_cast<const f32x4*>(src + 4);
+        }
+    };
+    auto store_stage = [&](int s) {
+        u32x4 vh, vl;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            wx_split8(ar[2 * j], ar[2 * j + 1], &vh, &vl);
+            *reinterpret_cast<u32x4*>(lds + a_wr + j * 8192) = vh;
+            *reinterpret_cast<u32x4*>(lds + W2_A_BYTES + a_wr + j * 8192) = vl;
+        }
+        const int u = 2 * (ylo + s * g.RS) + 2 + fr;          // fine row + 1: pair u >> 1, member u & 1
+        unsigned char* dst = ring + ((u >> 1) % g.NPAIR) * pair_bytes + (u & 1) * row_bytes + f_wr;
+        const bool inside = u - 1 < Hf;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            wx_split8(fw[2 * j], fw[2 * j + 1], &vh, &vl);
+            if (!(inside && fok[j])) vh = vl = u32x4{0u, 0u, 0u, 0u};           // row 2 nh / channel past Cf
+            *reinterpret_cast<u32x4*>(dst + j * 16 * g.pitch * 16) = vh;
+            *reinterpret_cast<u32x4*>(dst + g.ring_plane + j * 16 * g.pitch * 16) = vl;
+        }
+    };
+
+    // prologue: the ring starts as zeros (halo slots and row -1 keep them); the pair ylo (rows 2 ylo - 1, 2 ylo), then stage 0
+    for (int i = tid; i < 2 * g.ring_plane / 16; i += 512) *reinterpret_cast<u32x4*>(ring + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    load_stage(0);
+    __syncthreads();
+    for (int i = tid; i < 2 * W2_C * cprf; i += 512) {
+        const int m = i / (W2_C * cprf), rem = i - m * (W2_C * cprf);
+        const int c = rem / cprf, x8 = rem - c * cprf;
+        const int y = 2 * ylo - 1 + m, cf = ct * W2_C + c;
+        if (cf < g.Cf && y >= 0) {                           // else: the zeros stay
+            const float* src = fine + ((size_t)b * g.Cf + cf) * HWf + (size_t)y * Wf + x8 * 8;
+            u32x4 vh, vl;
+            wx_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), &vh, &vl);
+            const int off = (ylo % g.NPAIR) * pair_bytes + m * row_bytes + (c * g.pitch + 1 + x8) * 16;
+            *reinterpret_cast<u32x4*>(ring + off) = vh;
+            *reinterpret_cast<u32x4*>(ring + g.ring_plane + off) = vl;
+        }
+    }
+    store_stage(0);
+    __syncthreads();
+
+    const int a_row = wk * 32 + r;
+    for (int s = 0; s < g.stages_per_wg; ++s) {
+        const int y0 = ylo + s * g.RS;
+        if (s + 1 < g.stages_per_wg) load_stage(s + 1);       // consumed behind this stage's multiplications
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                         // k-steps of 16 coarse pixels
+            const int f8 = 2 * j + h;
+            const unsigned char* A = lds + ((a_row << 3) + (f8 ^ (a_row & 7))) * 16;
+            const bf16x8 fah = *reinterpret_cast<const bf16x8*>(A), fal = *reinterpret_cast<const bf16x8*>(A + W2_A_BYTES);
+            const int p0 = 16 * j;
+            const int rs = p0 >> g.wshift, ox0 = (p0 & (g.nw - 1)) + 8 * h;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const int u = 2 * (y0 + rs) + 2 * rh + ri;    // = fine row + 1 (tap row 2 rh + ri)
+                const unsigned char* X = ring + ((u >> 1) % g.NPAIR) * pair_bytes + (u & 1) * row_bytes + (r * g.pitch + 1 + (ox0 >> 2)) * 16;
+                u32x4 f[2][4];                               // [plane][column tap]
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const unsigned char* Xp = X + pl * g.ring_plane;
+                    const u32x4 lo4 = *reinterpret_cast<const u32x4*>(Xp);
+                    const u32x4 hi4 = *reinterpret_cast<const u32x4*>(Xp + 16);
+                    const unsigned prev = *reinterpret_cast<const unsigned*>(Xp - 4);
+                    const unsigned next = *reinterpret_cast<const unsigned*>(Xp + 32);
+                    const unsigned d0 = lo4.x, d1 = lo4.y, d2 = lo4.z, d3 = lo4.w, d4 = hi4.x, d5 = hi4.y, d6 = hi4.z, d7 = hi4.w;
+                    f[pl][0] = u32x4{pack_hi(prev, d0), pack_hi(d1, d2), pack_hi(d3, d4), pack_hi(d5, d6)};
+                    f[pl][1] = u32x4{pack_lo(d0, d1), pack_lo(d2, d3), pack_lo(d4, d5), pack_lo(d6, d7)};
+                    f[pl][2] = u32x4{pack_hi(d0, d1), pack_hi(d2, d3), pack_hi(d4, d5), pack_hi(d6, d7)};
+                    f[pl][3] = u32x4{pack_lo(d1, d2), pack_lo(d3, d4), pack_lo(d5, d6), pack_lo(d7, next)};
+                }
+                // smallest terms first: lo(coarse) hi(fine), hi(coarse) lo(fine), hi hi; the four taps alternate so that no MFMA waits for its predecessor
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, f[0][t]), acc[ri * 4 + t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, f[1][t]), acc[ri * 4 + t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, f[0][t]), acc[ri * 4 + t], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                       // every wave is done reading this stage
+        if (s + 1 < g.stages_per_wg) {
+            store_stage(s + 1);
+            __syncthreads();
+        }
+    }
+
+    // partial result: slab[split][t = r * 4 + s][kc][cf] (lanes along cf)
+    const int Kp = g.ktiles * W2_K, Cp = g.ctiles * W2_C;
+    float* out = slabs + (size_t)split * 16 * Kp * Cp;
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int kc = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)(rh * 8 + t) * Kp + kc) * Cp + ct * W2_C + r] = acc[t][e];
+        }
+}
+
+static int x2_geometry(int B, int Kc, int Cf, int nh, int nw, X2Geom* g)
+{
+    const char* who = "split-bf16 4x4 stride-2 weight gradient";
+    if (nw == 128)
+        return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width 128: the ring of whole fine rows for a half-row stage needs 176128 bytes of LDS (16, 32 or 64)", who);
+    if (nw != 16 && nw != 32 && nw != 64) return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width %d (16, 32 or 64)", who, nw);
+    const int RS = W2_PX / nw;
+    if (nh % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d coarse rows are not a multiple of the %d rows of a stage", who, nh, RS);
+    g->B = B; g->Kc = Kc; g->Cf = Cf; g->nh = nh; g->nw = nw;
+    g->wshift = nw == 16 ? 4 : (nw == 32 ? 5 : 6);
+    g->RS = RS; g->NPAIR = RS + 1; g->pitch = 2 * nw / 8 + 3;
+    g->ktiles = (Kc + W2_K - 1) / W2_K; g->ctiles = (Cf + W2_C - 1) / W2_C;
+    g->ring_plane = g->NPAIR * 2 * W2_C * g->pitch * 16;
+    if (2 * W2_A_BYTES + 2 * g->ring_plane > CB_LDS_MAX) return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide grid does not fit the LDS plan", who, nw);
+    // runs: one round of one workgroup per CU, as w2_geometry
+    const int groups = nh / RS;
+    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
+    if (spw < 1) spw = 1;
+    if (spw > groups) spw = groups;
+    while (groups % spw) --spw;
+    g->stages_per_wg = spw;
+    g->nsplit = B * (groups / spw);
+    return IPSR_OK;
+}
+
+// the partial slabs, nothing else
+size_t conv_bf16x3_wrw_s2_ws_bytes(int B, int Kc, int Cf, int nh, int nw)
+{
+    X2Geom g;
+    if (x2_geometry(B, Kc, Cf, nh, nw, &g) != IPSR_OK) return 0;
+    return (size_t)g.nsplit * 16 * g.ktiles * W2_K * g.ctiles * W2_C * 4;
+}
+
+// fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw] fp32 -> dW [Kc][Cf][4][4] fp32
+int launch_conv_bf16x3_wrw_s2(const float* fine, const float* coarse, float* dW, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, hipStream_t st)
+{
+    X2Geom g;
+    if (int rc = x2_geometry(B, Kc, Cf, nh, nw, &g)) return rc;
+    const size_t need = conv_bf16x3_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 4x4 stride-2 weight gradient: workspace %zu < %zu", ws_bytes, need);
+    float* slabs = static_cast<float*>(ws);
+    const size_t smem = 2 * (size_t)W2_A_BYTES + 2 * (size_t)g.ring_plane;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
+    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "conv_bf16x3_wrw_s2_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", CB_LDS_MAX, hipGetErrorString(e));
+    const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
+    profile_mark_start(st, 4);
+    conv_bf16x3_wrw_s2_kernel<<<grid, 512, smem, st>>>(coarse, fine, g, slabs);
+    profile_mark_stop(st, 4, 3.0 * 2.0 * 16.0 * (double)(g.ktiles * W2_K) * (g.ctiles * W2_C) * B * nh * nw, 2.0 * 16.0 * (double)Kc * Cf * B * nh * nw);
+    if (int rc = check_launch("conv_bf16x3_wrw_s2_kernel")) return rc;
+    conv_bf16_wrw_s2_reduce_kernel<<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
+    return check_launch("conv_bf16_wrw_s2_reduce_kernel");
+}
+
 }  // namespace ipsr
 
 using namespace ipsr;
@@ -1947,6 +2201,23 @@ int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int
         (reinterpret_cast<uintptr_t>(dw) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16_wrw: operands / workspace must be 16-byte aligned");
     return launch_conv_bf16_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
+{
+    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes: bad argument"); return 0; }
+    return conv_bf16x3_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
+}
+
+int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
+{
+    if (!fine || !coarse || !dw || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: null pointer");
+    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: bad argument");
+    // fine / coarse: their fp32 rows are read as 16-byte vectors; dw: a [4][4] block leaves as four 16-byte vectors
+    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(fine) & 15u) || (reinterpret_cast<uintptr_t>(coarse) & 15u) ||
+        (reinterpret_cast<uintptr_t>(dw) & 15u))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: operands / workspace must be 16-byte aligned");
+    return launch_conv_bf16x3_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)

@@ -36,7 +36,9 @@ pass and what the engine needs; a new engine is one record there plus its rule i
                                   of three to four
   "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3_dw")`): the weight gradient of the k3 s1 p1 layers
                                   that "winograd" / "miopen" have by default, as a pixel reduction on split-bf16 operands (two launches, the
-                                  split in the kernel); the data passes run "bf16x3d" as under "direct_bf16x3"
+                                  split in the kernel); the data passes run "bf16x3d" as under "direct_bf16x3".  Under
+                                  `set_conv_math(fp32="direct_bf16x3_s2_dw")` also the weight gradient of the k4 s2 p1 layers that
+                                  `_bf16x3_s2_wrw_wins` names (ops.conv4x4s2_bf16x3_wrw, two launches instead of "wino_s2"'s three to four)
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
@@ -60,8 +62,10 @@ _FORCE = None          # test hook: overrides the environment
 # fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d";
 # "direct_bf16x3_dw" does the same and `select_wrw` moves the k3 s1 p1 weight gradients of "winograd" / "miopen" to "bf16x3w".
 # "direct_bf16x3_s2" does what "direct_bf16x3_dw" does and `select` moves the k4 s2 p1 data passes of `_bf16x3_s2_wins` to "bf16x3d".
-_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2")
-_DIRECT_WRW_MATH = ("direct_bf16x3_dw", "direct_bf16x3_s2")
+# "direct_bf16x3_s2_dw" does what "direct_bf16x3_s2" does and `select_wrw` moves the k4 s2 p1 weight gradients of `_bf16x3_s2_wrw_wins` to "bf16x3w".
+_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw")
+_DIRECT_WRW_MATH = ("direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw")
+_DIRECT_S2_MATH = ("direct_bf16x3_s2", "direct_bf16x3_s2_dw")
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
 
 
@@ -70,7 +74,9 @@ def set_conv_math(fp32=None, bf16=None):
     the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere;
     fp32="direct_bf16x3_dw": that, and the direct split-bf16 weight gradient where `select_wrw` has "winograd" or "miopen";
     fp32="direct_bf16x3_s2": that, and the direct split-bf16 kernel for the forward / input gradient of the k4 s2 p1 layers where `select`
-    has "wino_s2" (`_bf16x3_s2_wins`; also the one k4 s2 p1 row of MIOpen's that measured faster).  The three direct names are for fp32 activations only."""
+    has "wino_s2" (`_bf16x3_s2_wins`; also the one k4 s2 p1 row of MIOpen's that measured faster);
+    fp32="direct_bf16x3_s2_dw": that, and the direct split-bf16 weight gradient of the k4 s2 p1 layers that `_bf16x3_s2_wrw_wins` names.
+    The four direct names are for fp32 activations only."""
     from .. import ops as _ops
     for key, val in (("fp32", fp32), ("bf16", bf16)):
         if val is not None:
@@ -127,7 +133,7 @@ def _select_any(op, lay, bf16):
     if not bf16:
         if eng == "winograd" and _MATH["fp32"] in _DIRECT_MATH and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
             return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
-        if _MATH["fp32"] == "direct_bf16x3_s2" and _bf16x3_s2_wins(eng, op, lay):
+        if _MATH["fp32"] in _DIRECT_S2_MATH and _bf16x3_s2_wins(eng, op, lay):
             return "bf16x3d"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
@@ -341,6 +347,8 @@ def _select_wrw_any(lay, bf16):
             return "thin_mfma"
         if _MATH["fp32"] in _DIRECT_WRW_MATH and _bf16x3_wrw_wins(eng, lay):
             return "bf16x3w"
+        if _MATH["fp32"] == "direct_bf16x3_s2_dw" and _bf16x3_s2_wrw_wins(eng, lay):
+            return "bf16x3w"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
         return eng
@@ -367,7 +375,7 @@ def _bf16_direct_wrw(lay):
 
 
 def _bf16x3_s2_wins(eng, op, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_s2": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct
+    """fp32 activations under the opt-in "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct
     split-bf16 kernel (ops.conv4x4s2_bf16x3) where it takes the shape.  Measured at batch 8 on every such row of the step
     (profiles/direct_bf16x3_s2_layers.txt): 1.23-2.51x "wino_s2" (0.037-0.106 vs 0.079-0.197 ms), every row's slowest round of the kernel faster than
     the fastest of "wino_s2", no row loses — so the rule is every "wino_s2" data pass the kernel takes; other batches and channel counts inside it were not measured.
@@ -382,7 +390,7 @@ def _bf16x3_s2_wins(eng, op, lay):
 
 
 def _bf16x3_wrw_wins(eng, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_dw" / "direct_bf16x3_s2": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
+    """fp32 activations under the opt-in "direct_bf16x3_dw" / "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
     split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured at batch 8
     (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient on 256 -> 256 /
     512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer multiplications and its
@@ -393,6 +401,20 @@ def _bf16x3_wrw_wins(eng, lay):
     if H * W < 4096 and min(Cin, Cout) >= 512:
         return False
     return k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and ops.conv3x3_bf16x3_wrw_supported(transposed, B, Cin, H, W, Cout)
+
+
+def _bf16x3_s2_wrw_wins(eng, lay):
+    """fp32 activations under the opt-in "direct_bf16x3_s2_dw": the k4 s2 p1 weight gradients that "wino_s2" has go to the direct split-bf16
+    kernel (ops.conv4x4s2_bf16x3_wrw) where it takes the shape (coarse grids 16, 32 or 64 wide).  Measured at batch 8 on every such row of the step
+    (profiles/direct_bf16x3_s2_wrw_layers.txt): 1.21-1.87x "wino_s2" (0.050-0.091 vs 0.079-0.145 ms), every row's slowest round of the kernel
+    faster than the fastest of "wino_s2" (the closest: Conv2d 64 -> 128 on a 64-wide coarse grid, 0.0823 vs 0.0947), no row loses — so the rule is
+    every "wino_s2" weight gradient the kernel takes; other batches and the channel counts / grids `_s2_wins` admits beyond the step's were not measured.
+    A forced engine is never overridden; MIOpen's rows ("thin_mfma"'s 3-channel ends, netG's outermost 64 -> 64 on a 128-wide coarse grid,
+    which the kernel refuses), "smallmap", "one", the dilated family and grids below 16 wide stay where they are."""
+    if eng != "wino_s2" or _mode() != "auto":
+        return False
+    g = _s2_geometry(lay)
+    return g is not None and ops.conv4x4s2_bf16x3_wrw_supported(lay[1], *g)
 
 
 def _select_wrw(lay):
@@ -466,6 +488,12 @@ def _bf16d_wrw(x, dy, lay, math, sink):
     return ops.conv4x4s2_bf16_wrw(*((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink)       # (fine, coarse)
 
 
+def _bf16x3w_wrw(x, dy, lay, math, sink):
+    if lay[6] == 3:
+        return ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink)
+    return ops.conv4x4s2_bf16x3_wrw(*((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink)     # (fine, coarse)
+
+
 def _thin_mfma_wrw(x, dy, lay, math, sink):
     if lay[0] and dy.dtype == torch.bfloat16 and x.dtype != torch.bfloat16:
         x = x.to(torch.bfloat16)                 # the WIDE tensor decides the arithmetic
@@ -500,7 +528,7 @@ _ENGINES = {
         fp32_copies=True, sink=True),
     "bf16d": _Engine(_bf16d_data, _bf16d_wrw, bf16_io=True, sink=True, wrw_x_as_dy=True),
     "bf16x3d": _Engine(_bf16x3d_data),
-    "bf16x3w": _Engine(None, lambda x, dy, lay, math, sink: ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink), sink=True),
+    "bf16x3w": _Engine(None, _bf16x3w_wrw, sink=True),
     "miopen": _Engine(),
 }
 

@@ -455,7 +455,8 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 # (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply.
 # "direct_bf16x3_dw" = the same, and the k3 s1 p1 weight gradients go to the direct split-bf16 kernel too (conv3x3_bf16x3_wrw)
 # "direct_bf16x3_s2" = the same, and the k4 s2 p1 data passes the dispatcher has on "wino_s2" go to the direct split-bf16 kernel (conv4x4s2_bf16x3)
-MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0, "direct_bf16x3_s2": 0}
+# "direct_bf16x3_s2_dw" = the same, and the k4 s2 p1 weight gradients of hipconv._bf16x3_s2_wrw_wins go to the direct split-bf16 kernel (conv4x4s2_bf16x3_wrw)
+MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0, "direct_bf16x3_s2": 0, "direct_bf16x3_s2_dw": 0}
 
 
 def _io_code(in_bf16, out_dtype):
@@ -733,6 +734,26 @@ def conv4x4s2_bf16_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw), fine.device, "ipsr_conv4x4s2_bf16_wrw: %s", ((B, Kc, Cf, nh, nw),))
     _lib.check(L.ipsr_conv4x4s2_bf16_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
                "ipsr_conv4x4s2_bf16_wrw")
+    return dw
+
+
+def conv4x4s2_bf16x3_wrw_supported(B, Kc, Cf, nh, nw):
+    return _lib.lib().ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(B, Kc, Cf, nh, nw) > 0
+
+
+def conv4x4s2_bf16x3_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
+    """Weight gradient [Kc,Cf,4,4] (fp32) of a k4 s2 p1 layer from its FP32 fine [B,Cf,2nh,2nw] and coarse [B,Kc,nh,nw] tensors on the bf16
+    matrix cores with split operands (ipsr_conv4x4s2_bf16x3_wrw): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32
+    accumulation, the split in the kernel; `out`: optional contiguous fp32 destination (a gradient bucket slice)."""
+    fine = _req(fine, torch.float32, "fine tensor")
+    coarse = _req(coarse, torch.float32, "coarse tensor")
+    if tuple(fine.shape) != (B, Cf, 2 * nh, 2 * nw) or tuple(coarse.shape) != (B, Kc, nh, nw):
+        raise RuntimeError("conv4x4s2_bf16x3_wrw: fine %s / coarse %s do not match %s / %s" % (tuple(fine.shape), tuple(coarse.shape), (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)))
+    L = _lib.lib()
+    dw = _result(out, (Kc, Cf, 4, 4), torch.float32, fine.device, "conv4x4s2_bf16x3_wrw")
+    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(B, Kc, Cf, nh, nw), fine.device, "ipsr_conv4x4s2_bf16x3_wrw: %s", ((B, Kc, Cf, nh, nw),))
+    _lib.check(L.ipsr_conv4x4s2_bf16x3_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
+               "ipsr_conv4x4s2_bf16x3_wrw")
     return dw
 
 

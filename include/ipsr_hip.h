@@ -492,6 +492,19 @@ int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float*
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
                             void* ws, size_t ws_bytes, void* stream);
+/* the same weight gradient on FP32 tensors with SPLIT-bf16 operands (the opt-in arithmetic "direct_bf16x3_s2_dw" of the fp32 nets): fine
+ * [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw] fp32 NCHW -> dw [Kc][Cf][4][4] fp32,
+ *        dw[kc][cf][r][s] = sum_{b,oy,ox} coarse[b][kc][oy][ox] * fine[b][cf][2 oy - 1 + r][2 ox - 1 + s]   (zeros outside the image).
+ * Every operand a = hi + lo with hi = bf16(a), lo = bf16(a - hi) (nearest even), every product lo*hi + hi*lo + hi*hi on the bf16 matrix
+ * cores, smallest terms first, fp32 accumulation; the split happens inside the kernel (no pre-split pass, no fp32-wide intermediates).  Two
+ * launches: partial [tap][kc][cf] slabs of the pixel runs, added in ascending order (deterministic, no atomics).  Error per element
+ * <= 2^-16 of sum |coarse||fine| plus the fp32 accumulation's.  Supported: nw in {16, 32, 64}, nh a multiple of 64 / nw, any Kc, Cf, B >= 1;
+ * anything else (nw = 128 included: its row ring does not fit the LDS) -> IPSR_ERR_UNSUPPORTED, checked before any launch and before anything
+ * is written.  The workspace query returns 0 where the shape is unsupported, reason in ipsr_last_error(); a short workspace is
+ * IPSR_ERR_WORKSPACE; fine, coarse, dw and ws must be 16-byte aligned. */
+size_t ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
+int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
+                              void* ws, size_t ws_bytes, void* stream);
 /* their weight gradient: x [B,Cin,H,W], dy [B,Cout,H,W] -> dw fp32 in the module's layout.  The reduction over pixels is cut over
  * workgroups; the partial results are added in a fixed order by a second launch (deterministic).  W in {16, 32, 64, 128}, H a multiple
  * of 128 / W.  form:

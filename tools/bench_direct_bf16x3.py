@@ -11,10 +11,14 @@
   s2       every k4 s2 p1 layer of the step at batch 8, forward and input gradient (ops.conv4x4s2_bf16x3, engine "bf16x3d" under
            opt.conv_math="direct_bf16x3_s2"): the new kernel against the engine `select` answers for the shape under conv_math "fp32",
            same process, same rounds; err = max |y - y64| / max |y64| against the fp64 convolution (first two images).
+  s2wrw    the weight gradient of the same k4 s2 p1 layers (ops.conv4x4s2_bf16x3_wrw, engine "bf16x3w" under
+           opt.conv_math="direct_bf16x3_s2_dw"): the new kernel against the engine `select_wrw` answers for the shape under conv_math
+           "fp32", same process, same rounds; err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the whole batch.
   steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "direct_bf16x3",
-           "direct_bf16x3_dw", "direct_bf16x3_s2" and "bf16x3" in ONE process, alternated over `--rounds` rounds.
+           "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw" and "bf16x3" in ONE process, alternated over `--rounds` rounds
+           (`--maths` narrows the list).
 
-    python tools/bench_direct_bf16x3.py [--what layers wrw s2 steps] [--out profiles/direct_bf16x3_layers.txt]
+    python tools/bench_direct_bf16x3.py [--what layers wrw s2 s2wrw steps] [--out profiles/direct_bf16x3_layers.txt]
 """
 import argparse
 import os
@@ -180,7 +184,52 @@ def s2(B, iters, rounds, emit):
                   min(ms["today"]), max(ms["today"]), err["today"], md["today"] / md["direct"]))
 
 
-def steps(B, ksteps, rounds, emit):
+def s2wrw(B, iters, rounds, emit):
+    from deepinpainting_amd.models import hipconv
+    g = torch.Generator(device="cuda").manual_seed(8)
+    hipconv.set_conv_math(fp32="fp32")
+    emit("k4 s2 p1 weight gradients, batch %d, fp32 NCHW operands, dW fp32 [Kc][Cf][4][4]; ms = device time per call (HIP events, %d calls per burst, "
+         "median of %d alternated rounds, [min..max]); TF = useful flop / time" % (B, iters, rounds))
+    emit("err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the unrounded operands; today = the engine select_wrw answers under conv_math fp32")
+    emit("wins = the kernel's slowest round is faster than today's fastest round")
+    emit("%-25s | %-40s | %-44s | %s" % ("layer", "direct bf16x3 wrw  ms [min..max]  TF   err", "today's engine  ms [min..max]  err", "today / direct"))
+    for kind, Kc, Cf, n in S2_LAYERS:
+        tr = kind == "convT"
+        Cin, Cout, H = (Kc, Cf, n) if tr else (Cf, Kc, 2 * n)
+        Ho = 2 * n if tr else n
+        lay = (tr, B, Cin, H, H, Cout, 4, 2, 1, 1)
+        label = "%-5s Kc=%4d Cf=%4d n=%-3d" % (kind, Kc, Cf, n)
+        today = hipconv.select_wrw(*lay)
+        if not ops.conv4x4s2_bf16x3_wrw_supported(B, Kc, Cf, n, n):
+            emit("%s | unsupported (today: %s)" % (label, today))
+            continue
+        x = torch.randn(B, Cin, H, H, device="cuda", generator=g)
+        dy = torch.randn(B, Cout, Ho, Ho, device="cuda", generator=g)
+        w = torch.zeros(Kc, Cf, 4, 4, device="cuda")
+        fine, coarse = (dy, x) if tr else (x, dy)
+        if today == "miopen":
+            base = lambda: torch.ops.aten.convolution_backward(dy, x, w, None, [2, 2], [1, 1], [1, 1], tr, [0, 0], 1, [False, True, False])[1]
+        else:
+            base = lambda: hipconv._run_wrw(today, x, dy, w, lay, "fp32")
+        ref = torch.ops.aten.convolution_backward(dy.double(), x.double(), w.double(), None, [2, 2], [1, 1], [1, 1], tr, [0, 0], 1, [False, True, False])[1]
+        engines = [("direct", lambda: ops.conv4x4s2_bf16x3_wrw(fine, coarse, B, Kc, Cf, n, n)), ("today", base)]
+        err, ms = {}, {k: [] for k, _ in engines}
+        for k, fn in engines:
+            for _ in range(3):
+                d = fn()
+            err[k] = float((d.double() - ref).abs().max() / ref.abs().max())
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, fn in engines:
+                ms[k].append(burst_ms(fn, iters))
+        md = {k: statistics.median(v) for k, v in ms.items()}
+        flops = 2.0 * 16 * Kc * Cf * B * n * n
+        emit("%s | %7.4f [%6.4f..%6.4f] %6.1f %.1e | %-9s %7.4f [%6.4f..%6.4f] %.1e | %.2fx %s" %
+             (label, md["direct"], min(ms["direct"]), max(ms["direct"]), flops / md["direct"] / 1e9, err["direct"], today, md["today"],
+              min(ms["today"]), max(ms["today"]), err["today"], md["today"] / md["direct"], "wins" if max(ms["direct"]) < min(ms["today"]) else "loses"))
+
+
+def steps(B, ksteps, rounds, emit, maths=None):
     from deepinpainting_amd.models import hipconv
     from deepinpainting_amd.models.models import create_model
     from deepinpainting_amd.options import Option
@@ -190,7 +239,7 @@ def steps(B, ksteps, rounds, emit):
     torch.manual_seed(1234)
     model = bench.quiet(create_model, opt)
     img, mask, ref = bench.synthetic_batch(device, B, 1234)
-    maths = ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "bf16x3")
+    maths = tuple(maths) if maths else ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw", "bf16x3")
     rate = {m: [] for m in maths}
     try:
         for m in maths:                                        # every arithmetic's shapes warmed before any is timed
@@ -212,14 +261,15 @@ def steps(B, ksteps, rounds, emit):
         hipconv.set_conv_math(fp32="fp32")
     emit("whole fp32 training step (bench.py's model and step, batch %d, eager, one process): images/s over %d steps, %d alternated rounds" % (B, ksteps, rounds))
     for m in maths:
-        emit("  conv_math %-17s median %7.1f   rounds %s" % (m, statistics.median(rate[m]), " ".join("%.1f" % r for r in rate[m])))
+        emit("  conv_math %-19s median %7.1f   rounds %s" % (m, statistics.median(rate[m]), " ".join("%.1f" % r for r in rate[m])))
     losses = {k: float(v) for k, v in model.get_current_errors().items()}
     emit("  losses after the last step finite: %s" % all(v == v and abs(v) != float("inf") for v in losses.values()))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "s2", "steps"))
+    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "s2", "s2wrw", "steps"))
+    ap.add_argument("--maths", nargs="+", default=None, help="the arithmetics of the step table (default: all six)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
@@ -242,8 +292,10 @@ def main():
         wrw(a.batch, a.iters, a.rounds, emit)
     if "s2" in a.what:
         s2(a.batch, a.iters, a.rounds, emit)
+    if "s2wrw" in a.what:
+        s2wrw(a.batch, a.iters, a.rounds, emit)
     if "steps" in a.what:
-        steps(a.batch, a.steps, a.rounds, emit)
+        steps(a.batch, a.steps, a.rounds, emit, a.maths)
 
 
 if __name__ == "__main__":
