@@ -27,6 +27,7 @@
 // Supported: image width W in {16, 32, 64, 128} (power of two), H a multiple of 256 / W, reduction channels a multiple of 16.
 // Anything else -> IPSR_ERR_UNSUPPORTED (the dispatcher leaves it where it was).
 #include "ipsr_common.h"
+#include <initializer_list>
 
 namespace ipsr {
 
@@ -363,6 +364,47 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
     }
 }
 
+// log2 of a lane-grid width; the planners admit powers of two from 16 up only
+static int cb_wshift(int w) { return 31 - __builtin_clz((unsigned)w); }
+
+// The run cut of the four weight-gradient planners: ONE round of one workgroup per CU — every run costs a partial slab written and read
+// back (PMC, bf16 3x3 128 -> 128 @128x128: 512 runs = 151 MB each way against 134 MB of operands).  tiles = output tiles, groups = stages
+// per image -> stages a workgroup reduces (a divisor of groups) and the number of runs.
+static void cb_cut_runs(int tiles, int B, int groups, int* stages_per_wg, int* nsplit)
+{
+    int spw = (int)(((long)tiles * B * groups + 255) / 256);
+    if (spw < 1) spw = 1;
+    if (spw > groups) spw = groups;
+    while (groups % spw) --spw;
+    *stages_per_wg = spw;
+    *nsplit = B * (groups / spw);
+}
+
+// dW[k][c][t] = sum_s slab[s][t][k][c], t = 0..NT-1, s ascending.  NT = 9: dW + 9 (k C + c) is only 4-byte aligned, scalar stores;
+// NT = 16: four 16-byte vectors.
+template <int NT>
+__global__ void __launch_bounds__(256) cb_slab_reduce_kernel(const float* __restrict__ slabs, int nsplit, int K, int C, int Kp, int Cp,
+                                                             float* __restrict__ dW)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (c >= C) return;
+    float o[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) o[t] = 0.0f;
+    const size_t slab = (size_t)NT * Kp * Cp;
+    for (int s = 0; s < nsplit; ++s)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) o[t] += slabs[(size_t)s * slab + ((size_t)t * Kp + k) * Cp + c];
+    float* d = dW + ((size_t)k * C + c) * NT;
+    if constexpr (NT % 4 == 0) {
+#pragma unroll
+        for (int i = 0; i < NT / 4; ++i) reinterpret_cast<float4*>(d)[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+    } else {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) d[t] = o[t];
+    }
+}
+
 static int cb_lane_grid(int Hl, int Wl, int ptile, CbGeom* g, const char* who)
 {
     if (Wl != 16 && Wl != 32 && Wl != 64 && Wl != 128 && Wl != 256) return fail(IPSR_ERR_UNSUPPORTED, "%s: grid width %d (16 .. 256, a power of two)", who, Wl);
@@ -370,7 +412,7 @@ static int cb_lane_grid(int Hl, int Wl, int ptile, CbGeom* g, const char* who)
     g->ptile = ptile;
     if (Hl % R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", who, Hl, R);
     g->Hl = Hl; g->Wl = Wl; g->R = R;
-    g->wshift = Wl == 16 ? 4 : (Wl == 32 ? 5 : (Wl == 64 ? 6 : (Wl == 128 ? 7 : 8)));
+    g->wshift = cb_wshift(Wl);
     return IPSR_OK;
 }
 
@@ -794,7 +836,7 @@ static int cx_geometry(int B, int C, int K, int H, int W, CxGeom* g)
     g->R = CB_P / W;
     if (H % g->R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", who, H, g->R);
     g->B = B; g->C = C; g->K = K; g->H = H; g->W = W;
-    g->wshift = W == 16 ? 4 : (W == 32 ? 5 : (W == 64 ? 6 : (W == 128 ? 7 : 8)));
+    g->wshift = cb_wshift(W);
     g->NR = g->R + 2; g->PW = W + 2; g->NPOS = g->NR * g->PW;
     for (int t = 0; t < 9; ++t) g->tapoff[t] = (t / 3) * g->PW + (t % 3);
     g->ktiles = (K + CX_K - 1) / CX_K;
@@ -1274,44 +1316,18 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
         }
 }
 
-// dW[ka][cb][t] = sum_s slab[s][t][ka][cb]
-__global__ void __launch_bounds__(256) conv_bf16_wrw_reduce_kernel(const float* __restrict__ slabs, int nsplit, int Ka, int Cb, int Kap, int Cbp,
-                                                                   float* __restrict__ dW)
-{
-    const int cb = blockIdx.x * 256 + threadIdx.x, ka = blockIdx.y;
-    if (cb >= Cb) return;
-    float o[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) o[t] = 0.0f;
-    const size_t slab = (size_t)9 * Kap * Cbp;
-    for (int s = 0; s < nsplit; ++s)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) o[t] += slabs[(size_t)s * slab + ((size_t)t * Kap + ka) * Cbp + cb];
-    float* d = dW + ((size_t)ka * Cb + cb) * 9;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) d[t] = o[t];
-}
-
 static int wb_geometry(int B, int Ka, int Cb, int H, int W, WbGeom* g)
 {
     if (W != 16 && W != 32 && W != 64 && W != 128) return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: image width %d (16, 32, 64 or 128)", W);
     const int RS = WB_PX / W;
     if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: %d rows are not a multiple of %d", H, RS);
     g->B = B; g->Ka = Ka; g->Cb = Cb; g->H = H; g->W = W;
-    g->wshift = W == 16 ? 4 : (W == 32 ? 5 : (W == 64 ? 6 : 7));
+    g->wshift = cb_wshift(W);
     g->RS = RS; g->NSLOT = 2 * RS + 2; g->pitch = W / 8 + 3;
     g->ktiles = (Ka + WB_K - 1) / WB_K; g->ctiles = (Cb + WB_C - 1) / WB_C;
     if (g->NSLOT * WB_C * g->pitch * 16 > WB_X_BYTES || RS * WB_C * g->pitch > 5 * WB_THREADS)
         return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: the row ring of a %d-wide image does not fit the LDS plan", W);
-    // runs: ONE round of one workgroup per CU — every run costs a 295-KB partial slab written and read back (PMC, 128 -> 128 @128x128:
-    // 512 runs = 151 MB each way against 134 MB of operands)
-    const int groups = H / RS;                                // stages per image
-    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
-    if (spw < 1) spw = 1;
-    if (spw > groups) spw = groups;
-    while (groups % spw) --spw;
-    g->stages_per_wg = spw;
-    g->nsplit = B * (groups / spw);
+    cb_cut_runs(g->ktiles * g->ctiles, B, H / RS, &g->stages_per_wg, &g->nsplit);
     return IPSR_OK;
 }
 
@@ -1340,7 +1356,7 @@ int launch_conv_bf16_wrw(const void* a, const void* w, float* dW, int B, int Ka,
     conv_bf16_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
     profile_mark_stop(st, 4, 2.0 * 9.0 * (double)(g.ktiles * WB_K) * (g.ctiles * WB_C) * B * H * W, 2.0 * 9.0 * (double)Ka * Cb * B * H * W);
     if (int rc = check_launch("conv_bf16_wrw_kernel")) return rc;
-    conv_bf16_wrw_reduce_kernel<<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WB_K, g.ctiles * WB_C, dW);
+    cb_slab_reduce_kernel<9><<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WB_K, g.ctiles * WB_C, dW);
     return check_launch("conv_bf16_wrw_reduce_kernel");
 }
 
@@ -1352,7 +1368,7 @@ int launch_conv_bf16_wrw(const void* a, const void* w, float* dW, int B, int Ka,
 // product of the split plus the fp32 accumulation.
 // The structure is conv_bf16_wrw_kernel's: 8-pixel fragments, the dx = +-1 taps by five v_alignbit_b32 from the aligned chunk and its
 // neighbouring dwords (now for a hi and a lo image), runs of whole image rows cut over workgroups, partial [t][ka][cb] slabs added in
-// ascending order by conv_bf16_wrw_reduce_kernel.  What changed is the plan, because hi + lo images of both operands do not fit the old one:
+// ascending order by cb_slab_reduce_kernel<9>.  What changed is the plan, because hi + lo images of both operands do not fit the old one:
 //   * the split happens in the kernel, global -> registers -> v_cvt_pk_bf16_f32 -> LDS at the swizzled addresses (no pass over HBM, no
 //     fp32-sized intermediates, no LDS-DMA): the REGISTERS are the second buffer — the loads of stage s + 1 (40 dwords per lane) fly during
 //     the multiplications of stage s, the conversion and the stores follow between two barriers — so LDS holds ONE buffer of each image;
@@ -1576,20 +1592,13 @@ static int wx_geometry(int B, int Ka, int Cb, int H, int W, WxGeom* g)
     const int RS = WX_PX / W;
     if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a stage", who, H, RS);
     g->B = B; g->Ka = Ka; g->Cb = Cb; g->H = H; g->W = W;
-    g->wshift = W == 16 ? 4 : (W == 32 ? 5 : (W == 64 ? 6 : 7));
+    g->wshift = cb_wshift(W);
     g->RS = RS; g->NSLOT = RS + 2; g->pitch = W / 8 + 3;
     g->ktiles = (Ka + WX_K - 1) / WX_K; g->ctiles = (Cb + WX_C - 1) / WX_C;
     g->ring_plane = g->NSLOT * WX_C * g->pitch * 16;
     if (2 * WX_A_PLANE + 2 * g->ring_plane > CB_LDS_MAX)
         return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide image does not fit the LDS plan", who, W);
-    // runs: one round of one workgroup per CU, as wb_geometry (every run costs a partial slab written and read back)
-    const int groups = H / RS;                                // stages per image
-    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
-    if (spw < 1) spw = 1;
-    if (spw > groups) spw = groups;
-    while (groups % spw) --spw;
-    g->stages_per_wg = spw;
-    g->nsplit = B * (groups / spw);
+    cb_cut_runs(g->ktiles * g->ctiles, B, H / RS, &g->stages_per_wg, &g->nsplit);
     return IPSR_OK;
 }
 
@@ -1617,7 +1626,7 @@ int launch_conv_bf16x3_wrw(const float* a, const float* w, float* dW, int B, int
     conv_bf16x3_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(a, w, g, slabs);
     profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * (double)(g.ktiles * WX_K) * (g.ctiles * WX_C) * B * H * W, 2.0 * 9.0 * (double)Ka * Cb * B * H * W);
     if (int rc = check_launch("conv_bf16x3_wrw_kernel")) return rc;
-    conv_bf16_wrw_reduce_kernel<<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WX_K, g.ctiles * WX_C, dW);
+    cb_slab_reduce_kernel<9><<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WX_K, g.ctiles * WX_C, dW);
     return check_launch("conv_bf16_wrw_reduce_kernel");
 }
 
@@ -1781,41 +1790,17 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
         }
 }
 
-// dW[kc][cf][t] = sum_s slab[s][t][kc][cf], t = 0..15
-__global__ void __launch_bounds__(256) conv_bf16_wrw_s2_reduce_kernel(const float* __restrict__ slabs, int nsplit, int Kc, int Cf, int Kp, int Cp,
-                                                                      float* __restrict__ dW)
-{
-    const int cf = blockIdx.x * 256 + threadIdx.x, kc = blockIdx.y;
-    if (cf >= Cf) return;
-    float o[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) o[t] = 0.0f;
-    const size_t slab = (size_t)16 * Kp * Cp;
-    for (int s = 0; s < nsplit; ++s)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) o[t] += slabs[(size_t)s * slab + ((size_t)t * Kp + kc) * Cp + cf];
-    float4* d = reinterpret_cast<float4*>(dW + ((size_t)kc * Cf + cf) * 16);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
-}
-
 static int w2_geometry(int B, int Kc, int Cf, int nh, int nw, W2Geom* g)
 {
     if (nw != 16 && nw != 32 && nw != 64) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: coarse width %d (16, 32 or 64)", nw);
     const int RS = W2_PX / nw;
     if (nh % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: %d coarse rows are not a multiple of %d", nh, RS);
     g->B = B; g->Kc = Kc; g->Cf = Cf; g->nh = nh; g->nw = nw;
-    g->wshift = nw == 16 ? 4 : (nw == 32 ? 5 : 6);
+    g->wshift = cb_wshift(nw);
     g->RS = RS; g->NPAIR = 2 * RS + 1; g->pitch = 2 * nw / 8 + 3;
     g->ktiles = (Kc + W2_K - 1) / W2_K; g->ctiles = (Cf + W2_C - 1) / W2_C;
     if ((RS + 1) * 2 * W2_C * g->pitch > 5 * 512) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: row ring of a %d-wide grid", nw);
-    const int groups = nh / RS;
-    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
-    if (spw < 1) spw = 1;
-    if (spw > groups) spw = groups;
-    while (groups % spw) --spw;
-    g->stages_per_wg = spw;
-    g->nsplit = B * (groups / spw);
+    cb_cut_runs(g->ktiles * g->ctiles, B, nh / RS, &g->stages_per_wg, &g->nsplit);
     return IPSR_OK;
 }
 
@@ -1845,7 +1830,7 @@ int launch_conv_bf16_wrw_s2(const void* fine, const void* coarse, float* dW, int
     conv_bf16_wrw_s2_kernel<<<grid, 512, smem, st>>>(static_cast<const unsigned short*>(coarse), static_cast<const unsigned short*>(fine), zero_page, g, slabs);
     profile_mark_stop(st, 4, 2.0 * 16.0 * (double)(g.ktiles * W2_K) * (g.ctiles * W2_C) * B * nh * nw, 2.0 * 16.0 * (double)Kc * Cf * B * nh * nw);
     if (int rc = check_launch("conv_bf16_wrw_s2_kernel")) return rc;
-    conv_bf16_wrw_s2_reduce_kernel<<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
+    cb_slab_reduce_kernel<16><<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
     return check_launch("conv_bf16_wrw_s2_reduce_kernel");
 }
 
@@ -2059,19 +2044,12 @@ static int x2_geometry(int B, int Kc, int Cf, int nh, int nw, X2Geom* g)
     const int RS = W2_PX / nw;
     if (nh % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d coarse rows are not a multiple of the %d rows of a stage", who, nh, RS);
     g->B = B; g->Kc = Kc; g->Cf = Cf; g->nh = nh; g->nw = nw;
-    g->wshift = nw == 16 ? 4 : (nw == 32 ? 5 : 6);
+    g->wshift = cb_wshift(nw);
     g->RS = RS; g->NPAIR = RS + 1; g->pitch = 2 * nw / 8 + 3;
     g->ktiles = (Kc + W2_K - 1) / W2_K; g->ctiles = (Cf + W2_C - 1) / W2_C;
     g->ring_plane = g->NPAIR * 2 * W2_C * g->pitch * 16;
     if (2 * W2_A_BYTES + 2 * g->ring_plane > CB_LDS_MAX) return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide grid does not fit the LDS plan", who, nw);
-    // runs: one round of one workgroup per CU, as w2_geometry
-    const int groups = nh / RS;
-    int spw = (int)(((long)g->ktiles * g->ctiles * B * groups + 255) / 256);
-    if (spw < 1) spw = 1;
-    if (spw > groups) spw = groups;
-    while (groups % spw) --spw;
-    g->stages_per_wg = spw;
-    g->nsplit = B * (groups / spw);
+    cb_cut_runs(g->ktiles * g->ctiles, B, nh / RS, &g->stages_per_wg, &g->nsplit);
     return IPSR_OK;
 }
 
@@ -2099,7 +2077,7 @@ int launch_conv_bf16x3_wrw_s2(const float* fine, const float* coarse, float* dW,
     conv_bf16x3_wrw_s2_kernel<<<grid, 512, smem, st>>>(coarse, fine, g, slabs);
     profile_mark_stop(st, 4, 3.0 * 2.0 * 16.0 * (double)(g.ktiles * W2_K) * (g.ctiles * W2_C) * B * nh * nw, 2.0 * 16.0 * (double)Kc * Cf * B * nh * nw);
     if (int rc = check_launch("conv_bf16x3_wrw_s2_kernel")) return rc;
-    conv_bf16_wrw_s2_reduce_kernel<<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
+    cb_slab_reduce_kernel<16><<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
     return check_launch("conv_bf16_wrw_s2_reduce_kernel");
 }
 
@@ -2107,18 +2085,33 @@ int launch_conv_bf16x3_wrw_s2(const float* fine, const float* coarse, float* dW,
 
 using namespace ipsr;
 
+// The argument checks of the entries below; `who` = the entry's name as its messages have always spelled it, `what` = the pointers the
+// kernels read and write as 16-byte vectors (uint4 rows of bf16, 4-element vectors of fp32).
+static bool cb_dims_ok(bool code_ok, std::initializer_list<int> dims) { for (int d : dims) code_ok = code_ok && d >= 1; return code_ok; }
+static int cb_bad_dims(const char* who, bool code_ok, std::initializer_list<int> dims) { return cb_dims_ok(code_ok, dims) ? IPSR_OK : fail(IPSR_ERR_INVALID, "%s: bad argument", who); }
+static int cb_null(const char* who, std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs) if (!p) return fail(IPSR_ERR_INVALID, "%s: null pointer", who);
+    return IPSR_OK;
+}
+static int cb_misaligned(const char* who, const char* what, std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs) if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(IPSR_ERR_INVALID, "%s: %s must be 16-byte aligned", who, what);
+    return IPSR_OK;
+}
+
 extern "C" {
 
 size_t ipsr_conv3x3_bf16_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout)
 {
-    if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return 0;
+    if (!cb_dims_ok(op >= 0 && op <= 3, {B, Cin, Cout, H, W})) return 0;
     const bool fwd = op == 0 || op == 2;
     return conv_bf16_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
 
 size_t ipsr_conv3x3_bf16x3_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout)
 {
-    if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16x3_workspace_bytes: bad argument"); return 0; }
+    if (cb_bad_dims("ipsr_conv3x3_bf16x3_workspace_bytes", op >= 0 && op <= 3, {B, Cin, Cout, H, W})) return 0;
     const bool fwd = op == 0 || op == 2;
     return conv_bf16x3_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
@@ -2132,13 +2125,10 @@ int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, in
 int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
                              int pack_valid, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: null pointer");
-    if (op < 0 || op > 3 || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: bad argument");
+    if (int rc = cb_null("ipsr_conv3x3_bf16", {in, weight, out, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv3x3_bf16", op >= 0 && op <= 3, {B, Cin, Cout, H, W})) return rc;
     if (io < 0 || io > 2) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: io code %d (0 bf16 -> fp32, 1 bf16 -> bf16, 2 fp32 -> fp32 on split-bf16 operands)", io);
-    // out: the bf16 tile leaves as uint4 rows (conv_bf16_kernel's epilogue), the split reduction stores 4-element vectors; io 2 reads the fp32
-    // rows of `in` as 16-byte vectors
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16: in / out / workspace must be 16-byte aligned");
+    if (int rc = cb_misaligned("ipsr_conv3x3_bf16", "in / out / workspace", {ws, in, out})) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool fwd = op == 0 || op == 2;
     const int C = fwd ? Cin : Cout, K = fwd ? Cout : Cin;      // reduction / produced channels
@@ -2153,82 +2143,73 @@ int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* 
 
 size_t ipsr_conv4x4s2_bf16_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
-    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return 0;
+    if (!cb_dims_ok(mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return 0;
     return conv_bf16_s2_ws_bytes(mode, B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
                         void* ws, size_t ws_bytes, void* stream)
 {
-    if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: null pointer");
-    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: bad argument");
-    // out: the fine -> coarse bf16 tile leaves as uint4 rows, the split reduction stores 4-element vectors (16 bytes of fp32)
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16: in / out / workspace must be 16-byte aligned");
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16", {in, weight, out, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16", mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16", "in / out / workspace", {ws, in, out})) return rc;
     // weight [Kc][Cf][4][4] in both modules (Conv2d: [Cout][Cin], ConvTranspose2d: [Cin][Cout]), as in ipsr_conv4x4s2_winograd
     return launch_conv_bf16_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
-    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_workspace_bytes: bad argument"); return 0; }
+    if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_workspace_bytes", mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return 0;
     return conv_bf16x3_s2_ws_bytes(mode, B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
                           void* ws, size_t ws_bytes, void* stream)
 {
-    if (!in || !weight || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: null pointer");
-    if (mode < 0 || mode > 1 || B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1)
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16x3", {in, weight, out, ws})) return rc;
+    if (!cb_dims_ok(mode == 0 || mode == 1, {B, Kc, Cf, nh, nw}))
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: bad argument (mode %d: 0 fine -> coarse, 1 coarse -> fine)", mode);
-    // in: its fp32 rows are read as 16-byte vectors; out: the coarse -> fine rows leave as 8-byte pairs, the split reduction stores 16 bytes
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: in / out / workspace must be 16-byte aligned");
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3", "in / out / workspace", {ws, in, out})) return rc;
     return launch_conv_bf16x3_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
 {
-    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return 0;
+    if (!cb_dims_ok(true, {B, Kc, Cf, nh, nw})) return 0;
     return conv_bf16_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!fine || !coarse || !dw || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16_wrw: null pointer");
-    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16_wrw: bad argument");
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(fine) & 15u) || (reinterpret_cast<uintptr_t>(coarse) & 15u) ||
-        (reinterpret_cast<uintptr_t>(dw) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16_wrw: operands / workspace must be 16-byte aligned");
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16_wrw", {fine, coarse, dw, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
     return launch_conv_bf16_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
 {
-    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes: bad argument"); return 0; }
+    if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes", true, {B, Kc, Cf, nh, nw})) return 0;
     return conv_bf16x3_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!fine || !coarse || !dw || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: null pointer");
-    if (B < 1 || Kc < 1 || Cf < 1 || nh < 1 || nw < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: bad argument");
-    // fine / coarse: their fp32 rows are read as 16-byte vectors; dw: a [4][4] block leaves as four 16-byte vectors
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(fine) & 15u) || (reinterpret_cast<uintptr_t>(coarse) & 15u) ||
-        (reinterpret_cast<uintptr_t>(dw) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3_wrw: operands / workspace must be 16-byte aligned");
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16x3_wrw", {fine, coarse, dw, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16x3_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
     return launch_conv_bf16x3_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)
 {
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return 0;
+    if (!cb_dims_ok(true, {B, Cin, Cout, H, W})) return 0;
     return transposed ? conv_bf16_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16_wrw_ws_bytes(B, Cout, Cin, H, W);
 }
 
 size_t ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)
 {
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) { fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16x3_wrw_workspace_bytes: bad argument"); return 0; }
+    if (cb_bad_dims("ipsr_conv3x3_bf16x3_wrw_workspace_bytes", true, {B, Cin, Cout, H, W})) return 0;
     return transposed ? conv_bf16x3_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16x3_wrw_ws_bytes(B, Cout, Cin, H, W);
 }
 
@@ -2237,10 +2218,9 @@ int ipsr_conv3x3_bf16_wrw(int form, const void* x, const void* dy, float* dw, in
 {
     if (form < 0 || form > 3)
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: form code %d (0 Conv2d, 1 ConvTranspose2d on bf16 tensors; 2, 3 the same on fp32 tensors, split-bf16 operands)", form);
-    if (!x || !dy || !dw || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: null pointer");
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: bad argument");
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(x) & 15u) || (reinterpret_cast<uintptr_t>(dy) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_bf16_wrw: x / dy / workspace must be 16-byte aligned");
+    if (int rc = cb_null("ipsr_conv3x3_bf16_wrw", {x, dy, dw, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv3x3_bf16_wrw", true, {B, Cin, Cout, H, W})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv3x3_bf16_wrw", "x / dy / workspace", {ws, x, dy})) return rc;          // dW leaves as scalars: 9 floats per (k, c)
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool transposed = form & 1;
     // Conv2d: dW[co][ci][t] = sum dy[co][p] x[ci][p + t];  ConvTranspose2d: dW[ci][co][t] = sum x[ci][p] dy[co][p + t]

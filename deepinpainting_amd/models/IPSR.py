@@ -55,12 +55,7 @@ class IPSR(BaseModel):
         self.amp_bf16 = bool(getattr(opt, 'amp_bf16', False))
         # arithmetic of the Winograd convolution engines (models/hipconv.py, ops.MATH_CODE): fp32 operands on the fp32 matrix cores by
         # default (the reference's arithmetic); "bf16x6" (fp32-accurate, split operands on the bf16 matrix cores) / "bf16x3" are opt-in.
-        # "direct_bf16x3": the k3 s1 p1 forward / input-gradient passes of the Winograd engine run the direct split-bf16 kernel instead.
-        # "direct_bf16x3_dw": that, and the k3 s1 p1 weight gradients of the Winograd engine / MIOpen run the direct split-bf16 pixel reduction.
-        # "direct_bf16x3_s2": that, and the k4 s2 p1 forward / input-gradient passes of the polyphase Winograd engine that the direct split-bf16
-        # kernel measured faster on run it (hipconv._bf16x3_s2_wins).
-        # "direct_bf16x3_s2_dw": that, and the k4 s2 p1 weight gradients that hipconv._bf16x3_s2_wrw_wins names run the direct split-bf16
-        # pixel reduction (ops.conv4x4s2_bf16x3_wrw).
+        # The four "direct_bf16x3*" names move passes to the direct split-bf16 kernels instead: ops.DIRECT_PASSES says which.
         # Under amp_bf16 the engines read / write bf16 activations and multiply split-bf16 operands (`conv_math_bf16`, default "bf16x3").
         from . import hipconv
         hipconv.set_conv_math(fp32=getattr(opt, 'conv_math', 'fp32'), bf16=getattr(opt, 'conv_math_bf16', 'bf16x3'))

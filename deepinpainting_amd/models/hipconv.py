@@ -28,17 +28,8 @@ pass and what the engine needs; a new engine is one record there plus its rule i
                                   gradient as one pass over the input
   "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
-  "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3")`, `opt.conv_math`): the direct kernel on split-bf16
-                                  operands (hi + lo, three products) for the forward / input gradient of the k3 s1 p1 layers that "winograd"
-                                  has by default — no transform passes, error ~6e-6 of the output scale; weight gradients stay where they are.
-                                  Under `set_conv_math(fp32="direct_bf16x3_s2")` also the forward / input gradient of the k4 s2 p1 layers
-                                  that `_bf16x3_s2_wins` names ("wino_s2"'s, 1.2-2.5x it, and one row of MIOpen's, 2.7x), one launch instead
-                                  of three to four
-  "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32="direct_bf16x3_dw")`): the weight gradient of the k3 s1 p1 layers
-                                  that "winograd" / "miopen" have by default, as a pixel reduction on split-bf16 operands (two launches, the
-                                  split in the kernel); the data passes run "bf16x3d" as under "direct_bf16x3".  Under
-                                  `set_conv_math(fp32="direct_bf16x3_s2_dw")` also the weight gradient of the k4 s2 p1 layers that
-                                  `_bf16x3_s2_wrw_wins` names (ops.conv4x4s2_bf16x3_wrw, two launches instead of "wino_s2"'s three to four)
+  "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32=...)`, the four direct names of ops.DIRECT_PASSES): forward / input gradient on split-bf16 operands
+  "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (the same names): the weight gradient as a pixel reduction on split-bf16 operands, two launches
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
@@ -58,29 +49,19 @@ from .. import dist as ipsr_dist
 
 _FORCE = None          # test hook: overrides the environment
 # Arithmetic of the Winograd GEMMs (ops.MATH_CODE): "fp32" for fp32 activations (the reference's arithmetic; "bf16x6" / "bf16x3" are
-# opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).  "direct_bf16x3" for
-# fp32 activations is no Winograd arithmetic (those engines keep fp32 under it): `select` moves "winograd"'s data passes to "bf16x3d";
-# "direct_bf16x3_dw" does the same and `select_wrw` moves the k3 s1 p1 weight gradients of "winograd" / "miopen" to "bf16x3w".
-# "direct_bf16x3_s2" does what "direct_bf16x3_dw" does and `select` moves the k4 s2 p1 data passes of `_bf16x3_s2_wins` to "bf16x3d".
-# "direct_bf16x3_s2_dw" does what "direct_bf16x3_s2" does and `select_wrw` moves the k4 s2 p1 weight gradients of `_bf16x3_s2_wrw_wins` to "bf16x3w".
-_DIRECT_MATH = ("direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw")
-_DIRECT_WRW_MATH = ("direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw")
-_DIRECT_S2_MATH = ("direct_bf16x3_s2", "direct_bf16x3_s2_dw")
+# opt-in, models/IPSR.py `opt.conv_math`), "bf16x3" for bf16 activations / under bf16 autocast (BASELINE config 5).  The four direct names
+# for fp32 activations are no Winograd arithmetic: see ops.DIRECT_PASSES for the passes each moves to "bf16x3d" / "bf16x3w".
 _MATH = {"fp32": "fp32", "bf16": "bf16x3"}
 
 
 def set_conv_math(fp32=None, bf16=None):
-    """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast); fp32="direct_bf16x3":
-    the direct split-bf16 kernel where `select` has "winograd" and the kernel takes the shape, fp32 Winograd arithmetic elsewhere;
-    fp32="direct_bf16x3_dw": that, and the direct split-bf16 weight gradient where `select_wrw` has "winograd" or "miopen";
-    fp32="direct_bf16x3_s2": that, and the direct split-bf16 kernel for the forward / input gradient of the k4 s2 p1 layers where `select`
-    has "wino_s2" (`_bf16x3_s2_wins`; also the one k4 s2 p1 row of MIOpen's that measured faster);
-    fp32="direct_bf16x3_s2_dw": that, and the direct split-bf16 weight gradient of the k4 s2 p1 layers that `_bf16x3_s2_wrw_wins` names.
-    The four direct names are for fp32 activations only."""
+    """Choose the arithmetic of the Winograd engines for fp32 activations and for bf16 activations (autocast).  fp32 may also be one of the
+    four direct names of ops.DIRECT_PASSES (the table says which passes each moves to the direct split-bf16 kernels); they are for fp32
+    activations only."""
     from .. import ops as _ops
     for key, val in (("fp32", fp32), ("bf16", bf16)):
         if val is not None:
-            if val not in _ops.MATH_CODE or (key == "bf16" and val in _DIRECT_MATH):
+            if val not in _ops.MATH_CODE or (key == "bf16" and val in _ops.DIRECT_PASSES):
                 raise ValueError("conv math must be one of %s" % sorted(k for k in _ops.MATH_CODE if k))
             _MATH[key] = val
     _SEL.clear()           # `select` memoises without the arithmetic
@@ -131,9 +112,9 @@ def _select_any(op, lay, bf16):
     eng = _select(op, lay)
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if not bf16:
-        if eng == "winograd" and _MATH["fp32"] in _DIRECT_MATH and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
+        if eng == "winograd" and ops.direct_moves(_MATH["fp32"], "k3_data") and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
             return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
-        if _MATH["fp32"] in _DIRECT_S2_MATH and _bf16x3_s2_wins(eng, op, lay):
+        if ops.direct_moves(_MATH["fp32"], "s2_data") and _bf16x3_s2_wins(eng, op, lay):
             return "bf16x3d"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
@@ -345,9 +326,9 @@ def _select_wrw_any(lay, bf16):
         # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
         if thin and eng == "miopen":
             return "thin_mfma"
-        if _MATH["fp32"] in _DIRECT_WRW_MATH and _bf16x3_wrw_wins(eng, lay):
+        if ops.direct_moves(_MATH["fp32"], "k3_wrw") and _bf16x3_wrw_wins(eng, lay):
             return "bf16x3w"
-        if _MATH["fp32"] == "direct_bf16x3_s2_dw" and _bf16x3_s2_wrw_wins(eng, lay):
+        if ops.direct_moves(_MATH["fp32"], "s2_wrw") and _bf16x3_s2_wrw_wins(eng, lay):
             return "bf16x3w"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
@@ -459,39 +440,45 @@ def _select_wrw(lay):
 _Engine = namedtuple("_Engine", "data wrw bf16_io fp32_copies sink wrw_x_as_dy", defaults=(None, None, False, False, False, False))
 
 
+def _frozen_pack(w, param):
+    """-> the keep_packed / pack_key arguments of the direct 3x3 data passes.  param: the module's weight Parameter when `w` is a detached
+    view of it (the no-grad path).  Frozen weights (a leaf Parameter with requires_grad False, outside autograd) keep their packed image,
+    cached under the Parameter."""
+    param = w if param is None else param
+    return dict(keep_packed=isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled(), pack_key=param)
+
+
+def _fine_coarse(x, dy, lay):
+    """(fine, coarse, B, Kc, Cf, nh, nw): the operands of a k4 s2 p1 weight gradient in the terms of the coarse / fine entries."""
+    return ((dy, x) if lay[0] else (x, dy)) + (lay[1],) + _s2_geometry(lay)
+
+
 def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
-    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form.
-    param: the module's weight Parameter when `w` is a detached view of it (the no-grad path).  Frozen weights (a leaf Parameter
-    with requires_grad False, outside autograd) keep their packed bf16 image, cached under the Parameter."""
+    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form."""
     if inp.dtype != torch.bfloat16:
         inp = inp.to(torch.bfloat16)
     if lay[6] == 3:
-        param = w if param is None else param
-        frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
-        return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, keep_packed=frozen, pack_key=param)
+        return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, **_frozen_pack(w, param))
     return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), out_dtype=out_dtype)
 
 
 def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
-    """fp32 activations on the direct split-bf16 kernels: k3 s1 p1 (frozen weights keep their packed planes as in `_bf16d_data`), or
-    k4 s2 p1 in its coarse / fine form."""
-    if lay[6] == 4:
-        return ops.conv4x4s2_bf16x3(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay))
-    param = w if param is None else param
-    frozen = isinstance(param, nn.Parameter) and not param.requires_grad and not torch.is_grad_enabled()
-    return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], keep_packed=frozen, pack_key=param)
+    """fp32 activations on the direct split-bf16 kernels: the same two shapes."""
+    if lay[6] == 3:
+        return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], **_frozen_pack(w, param))
+    return ops.conv4x4s2_bf16x3(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay))
 
 
 def _bf16d_wrw(x, dy, lay, math, sink):
     if lay[6] == 3:
         return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
-    return ops.conv4x4s2_bf16_wrw(*((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink)       # (fine, coarse)
+    return ops.conv4x4s2_bf16_wrw(*_fine_coarse(x, dy, lay), out=sink)
 
 
 def _bf16x3w_wrw(x, dy, lay, math, sink):
     if lay[6] == 3:
         return ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink)
-    return ops.conv4x4s2_bf16x3_wrw(*((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink)     # (fine, coarse)
+    return ops.conv4x4s2_bf16x3_wrw(*_fine_coarse(x, dy, lay), out=sink)
 
 
 def _thin_mfma_wrw(x, dy, lay, math, sink):
@@ -512,7 +499,7 @@ _ENGINES = {
         bf16_io=True, sink=True, wrw_x_as_dy=True),
     "wino_s2": _Engine(          # the weight gradient takes (fine, coarse)
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv4x4s2_winograd(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), math=math, out_dtype=out_dtype),
-        lambda x, dy, lay, math, sink: ops.conv4x4s2_winograd(ops.S2_WEIGHT_GRAD, *((dy, x) if lay[0] else (x, dy)), lay[1], *_s2_geometry(lay), out=sink, math=math),
+        lambda x, dy, lay, math, sink: ops.conv4x4s2_winograd(ops.S2_WEIGHT_GRAD, *_fine_coarse(x, dy, lay), out=sink, math=math),
         bf16_io=True, sink=True, wrw_x_as_dy=True),
     "thin": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_thin(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype)),
     "thin_f2m": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv_thin_f2m_mfma(op, inp, w, lay[1:5], lay[5], lay[6], lay[7], out_dtype=out_dtype)),

@@ -451,12 +451,27 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 # arithmetic of the Winograd GEMMs (include/ipsr_hip.h, ipsr_conv3x3_winograd_mp): "fp32" = fp32 operands on the fp32 MFMA (the
 # reference's arithmetic, default); "bf16x3" / "bf16x6" = transformed operands split into 2 / 3 bf16 numbers, multiplied on the bf16
 # MFMA with fp32 accumulation (error ~1e-4 / ~1e-5 of the output scale; a plain bf16 convolution: ~2e-3).
-# "direct_bf16x3" = the k3 s1 p1 data passes the dispatcher has on "winograd" go to the DIRECT kernel on split-bf16 operands instead
-# (conv3x3_bf16x3, error ~6e-6); the Winograd engines keep fp32 arithmetic (code 0) wherever that kernel does not apply.
-# "direct_bf16x3_dw" = the same, and the k3 s1 p1 weight gradients go to the direct split-bf16 kernel too (conv3x3_bf16x3_wrw)
-# "direct_bf16x3_s2" = the same, and the k4 s2 p1 data passes the dispatcher has on "wino_s2" go to the direct split-bf16 kernel (conv4x4s2_bf16x3)
-# "direct_bf16x3_s2_dw" = the same, and the k4 s2 p1 weight gradients of hipconv._bf16x3_s2_wrw_wins go to the direct split-bf16 kernel (conv4x4s2_bf16x3_wrw)
-MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, "direct_bf16x3": 0, "direct_bf16x3_dw": 0, "direct_bf16x3_s2": 0, "direct_bf16x3_s2_dw": 0}
+#
+# The four opt-in "direct" names (fp32 activations only) are no Winograd arithmetic: the Winograd engines keep fp32 (code 0) under them,
+# and the dispatcher (models/hipconv.py) moves the passes named here to the DIRECT kernels on split-bf16 operands (csrc/conv_bf16.hip:
+# every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32 accumulation, error ~6e-6), wherever the kernel takes the shape:
+#   "k3_data"  forward / input gradient of the k3 s1 p1 layers that "winograd" has               -> conv3x3_bf16x3      (engine "bf16x3d")
+#   "k3_wrw"   weight gradient of the k3 s1 p1 layers that hipconv._bf16x3_wrw_wins names      -> conv3x3_bf16x3_wrw  (engine "bf16x3w")
+#   "s2_data"  forward / input gradient of the k4 s2 p1 layers that hipconv._bf16x3_s2_wins names -> conv4x4s2_bf16x3   (engine "bf16x3d")
+#   "s2_wrw"   weight gradient of the k4 s2 p1 layers that hipconv._bf16x3_s2_wrw_wins names   -> conv4x4s2_bf16x3_wrw (engine "bf16x3w")
+# Each name moves what the one before it moves, plus one more pass.  This table is the one place that says so.
+DIRECT_PASSES = {
+    "direct_bf16x3": frozenset({"k3_data"}),
+    "direct_bf16x3_dw": frozenset({"k3_data", "k3_wrw"}),
+    "direct_bf16x3_s2": frozenset({"k3_data", "k3_wrw", "s2_data"}),
+    "direct_bf16x3_s2_dw": frozenset({"k3_data", "k3_wrw", "s2_data", "s2_wrw"}),
+}
+MATH_CODE = {None: 0, "fp32": 0, "bf16x3": 2, "bf16x6": 3, **dict.fromkeys(DIRECT_PASSES, 0)}
+
+
+def direct_moves(math, which):
+    """True when the arithmetic name `math` moves the pass `which` (a key of DIRECT_PASSES' sets) to the direct split-bf16 kernels."""
+    return which in DIRECT_PASSES.get(math, ())
 
 
 def _io_code(in_bf16, out_dtype):
@@ -564,16 +579,26 @@ def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, 
     return out
 
 
-def conv3x3_bf16_supported(op, B, Cin, H, W, Cout):
-    return _lib.lib().ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout) > 0
+# ---- the direct kernels of csrc/conv_bf16.hip: one implementation per pass shape.  `arith` = "bf16" (bf16 activations in, bf16 or fp32 out:
+# BASELINE config 5) or "bf16x3" (fp32 in and out, operands split into hi + lo in the kernel); it is also the part of the public functions'
+# and of the C entries' names that differs, so every message names the function the caller used.
+
+def _direct_operands(arith, who, *named):
+    """The activation operands (tensor, name, ...) of a direct pass: all bf16 under "bf16", all fp32 under "bf16x3"."""
+    if arith == "bf16x3":
+        return [_req(t, torch.float32, name) for t, name in zip(named[::2], named[1::2])]
+    acts = [_act(t, name) for t, name in zip(named[::2], named[1::2])]
+    if not all(bf for _, bf in acts):
+        raise TypeError("%s reads bf16 %s" % (who, "tensors" if len(acts) > 1 else "activations, got %s" % acts[0][0].dtype))
+    return [t for t, _ in acts]
 
 
-# frozen weights: weight tensor (weakly held) -> {op: ((version, data pointer), shape, buffer holding the re-packed bf16 weights)}.  Keyed by
+# frozen weights: weight tensor (weakly held) -> {key: ((version, data pointer), shape, buffer holding the re-packed bf16 weights)}.  Keyed by
 # the tensor OBJECT (the module's Parameter, `pack_key`): a storage pointer comes back to life with another tensor's data once the first is
 # freed (two test cases with equal shapes met that way).  (id-keyed with a weak reference for liveness: tensors compare elementwise, which
 # rules out a WeakKeyDictionary)
 _BF16_PACKS = {}
-# conv3x3_bf16 calls that ran the weight-packing launch (a cache miss, or no cache asked for): what tests count the cache's hits by
+# conv3x3_bf16 / conv3x3_bf16x3 calls that ran the weight-packing launch (a cache miss, or no cache asked for): what tests count the cache's hits by
 bf16_pack_launches = 0
 
 
@@ -586,6 +611,100 @@ def _packs_of(weight):
     return ent[1]
 
 
+def _pack_workspace(weight, pack_key, key, nbytes, device, keep_packed):
+    """-> (workspace, valid) of a 3x3 data pass.  keep_packed: the packed weights live in a buffer of their own, cached under the tensor
+    object `pack_key` (default `weight`) and `key`; valid = 1 when it already holds this weight's image (same version counter, data
+    pointer and shape), so the packing launch is skipped.  Otherwise the shared scratch buffer, packed on every call."""
+    global bf16_pack_launches
+    valid = 0
+    if keep_packed:
+        packs = _packs_of(weight if pack_key is None else pack_key)
+        ent = packs.get(key)
+        if ent is not None and ent[0] == (weight._version, weight.data_ptr()) and ent[1] == tuple(weight.shape) and ent[2].numel() >= nbytes \
+                and ent[2].device == device:
+            ws, valid = ent[2], 1
+        else:
+            ws = _empty(nbytes, dtype=torch.uint8, device=device)
+            packs[key] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
+    else:
+        ws = _workspace(nbytes, device)
+    bf16_pack_launches += 1 - valid
+    return ws, valid
+
+
+def _conv3x3_direct(arith, op, inp, weight, in_shape, Cout, out_dtype, keep_packed, pack_key):
+    who, x3 = "conv3x3_" + arith, arith == "bf16x3"
+    B, Cin, H, W = in_shape
+    inp, = _direct_operands(arith, who, inp, "conv input")
+    weight = _req(weight, torch.float32, "conv weight")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("%s writes bf16 or fp32, not %s" % (who, out_dtype))
+    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
+    if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
+        raise RuntimeError("%s op %d: input %s / weight %s do not match %s / %s" % (who, op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
+    L = _lib.lib()
+    nbytes = getattr(L, "ipsr_conv3x3_%s_workspace_bytes" % arith)(op, B, Cin, H, W, Cout)
+    if nbytes == 0:
+        raise NotImplementedError("ipsr_conv3x3_bf16%s: op %d on %s is not implemented (%s)" % (" (io 2)" if x3 else "", op, (B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
+    out = _empty(oshape, dtype=out_dtype, device=inp.device)
+    ws, valid = _pack_workspace(weight, pack_key, ("x3", op) if x3 else op, nbytes, inp.device, keep_packed)
+    _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, 2 if x3 else int(out_dtype == torch.bfloat16),
+                                          valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
+    return out
+
+
+def _conv4x4s2_direct(arith, mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype):
+    who = "conv4x4s2_" + arith
+    inp, = _direct_operands(arith, who, inp, "conv input")
+    weight = _req(weight, torch.float32, "conv weight")
+    if mode not in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE):
+        raise ValueError("%s: mode %r" % (who, mode))
+    fine, coarse = (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)
+    want_in, oshape = (fine, coarse) if mode == S2_FINE_TO_COARSE else (coarse, fine)
+    if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
+        raise RuntimeError("%s mode %d: input %s / weight %s do not match %s / %s" % (who, mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
+    L = _lib.lib()
+    out = _empty(oshape, dtype=out_dtype, device=inp.device)
+    ws = _probed_workspace(L, getattr(L, "ipsr_%s_workspace_bytes" % who)(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_" + who + ": mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
+    io = () if arith == "bf16x3" else (int(out_dtype == torch.bfloat16),)          # ipsr_conv4x4s2_bf16x3 has no io code: fp32 in and out
+    _lib.check(getattr(L, "ipsr_" + who)(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, *io, ws.data_ptr(), ws.numel(), _stream()),
+               "ipsr_" + who)
+    return out
+
+
+def _conv4x4s2_direct_wrw(arith, fine, coarse, B, Kc, Cf, nh, nw, out):
+    who = "conv4x4s2_%s_wrw" % arith
+    fine, coarse = _direct_operands(arith, who, fine, "fine tensor", coarse, "coarse tensor")
+    if tuple(fine.shape) != (B, Cf, 2 * nh, 2 * nw) or tuple(coarse.shape) != (B, Kc, nh, nw):
+        raise RuntimeError("%s: fine %s / coarse %s do not match %s / %s" % (who, tuple(fine.shape), tuple(coarse.shape), (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)))
+    L = _lib.lib()
+    dw = _result(out, (Kc, Cf, 4, 4), torch.float32, fine.device, who)
+    ws = _probed_workspace(L, getattr(L, "ipsr_%s_workspace_bytes" % who)(B, Kc, Cf, nh, nw), fine.device, "ipsr_" + who + ": %s", ((B, Kc, Cf, nh, nw),))
+    _lib.check(getattr(L, "ipsr_" + who)(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
+               "ipsr_" + who)
+    return dw
+
+
+def _conv3x3_direct_wrw(arith, transposed, x, dy, Cout, out):
+    who, x3 = "conv3x3_%s_wrw" % arith, arith == "bf16x3"
+    x, dy = _direct_operands(arith, who, x, "conv input", dy, "grad_output")
+    B, Cin, H, W = x.shape
+    if tuple(dy.shape) != (B, Cout, H, W):
+        raise RuntimeError("%s: grad_output %s does not match %s" % (who, tuple(dy.shape), (B, Cout, H, W)))
+    L = _lib.lib()
+    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, who)
+    ws = _probed_workspace(L, getattr(L, "ipsr_%s_workspace_bytes" % who)(int(transposed), B, Cin, H, W, Cout), x.device,
+                           "ipsr_conv3x3_bf16_wrw%s: %%s" % (" (split-bf16)" if x3 else ""), ((B, Cin, H, W, Cout),))
+    form = int(bool(transposed)) + (2 if x3 else 0)              # forms 0 / 1: bf16 operands, 2 / 3: fp32 operands split in the kernel
+    _lib.check(L.ipsr_conv3x3_bf16_wrw(form, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
+                                       _stream()), "ipsr_conv3x3_bf16_wrw")
+    return dw
+
+
+def conv3x3_bf16_supported(op, B, Cin, H, W, Cout):
+    return _lib.lib().ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout) > 0
+
+
 def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep_packed=False, pack_key=None):
     """k3 s1 p1 convolution / transposed convolution / their input gradients as ONE direct implicit GEMM on the bf16 matrix cores
     (ipsr_conv3x3_bf16, csrc/conv_bf16.hip): bf16 activations in, bf16 or fp32 out, fp32 weights cast inside.  BASELINE config 5.
@@ -593,38 +712,7 @@ def conv3x3_bf16(op, inp, weight, in_shape, Cout, out_dtype=torch.bfloat16, keep
     call on.  The image is cached under the tensor object `pack_key` (default `weight`; pass the Parameter when `weight` is a
     detached view of it, which is a new object on every call) and is valid while the key's version counter and data pointer are
     unchanged.  Writes through `weight.data` are not seen: `.data` has a version counter of its own."""
-    global bf16_pack_launches
-    B, Cin, H, W = in_shape
-    inp, in_bf = _act(inp, "conv input")
-    if not in_bf:
-        raise TypeError("conv3x3_bf16 reads bf16 activations, got %s" % inp.dtype)
-    weight = _req(weight, torch.float32, "conv weight")
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError("conv3x3_bf16 writes bf16 or fp32, not %s" % out_dtype)
-    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
-    if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
-        raise RuntimeError("conv3x3_bf16 op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
-    L = _lib.lib()
-    nbytes = L.ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv3x3_bf16: op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
-    out = _empty(oshape, dtype=out_dtype, device=inp.device)
-    valid = 0
-    if keep_packed:
-        packs = _packs_of(weight if pack_key is None else pack_key)
-        ent = packs.get(op)
-        if ent is not None and ent[0] == (weight._version, weight.data_ptr()) and ent[1] == tuple(weight.shape) and ent[2].numel() >= nbytes \
-                and ent[2].device == inp.device:
-            ws, valid = ent[2], 1
-        else:
-            ws = _empty(nbytes, dtype=torch.uint8, device=inp.device)
-            packs[op] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
-    else:
-        ws = _workspace(nbytes, inp.device)
-    bf16_pack_launches += 1 - valid
-    _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, int(out_dtype == torch.bfloat16),
-                                          valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
-    return out
+    return _conv3x3_direct("bf16", op, inp, weight, in_shape, Cout, out_dtype, keep_packed, pack_key)
 
 
 def conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
@@ -636,34 +724,7 @@ def conv3x3_bf16x3(op, inp, weight, in_shape, Cout, keep_packed=False, pack_key=
     matrix cores with split operands (io code 2 of ipsr_conv3x3_bf16, csrc/conv_bf16.hip): every operand hi + lo, every product
     lo*hi + hi*lo + hi*hi, fp32 accumulation; fp32 in, fp32 out.  keep_packed / pack_key: as in conv3x3_bf16 (the hi and lo planes of
     the packed weights are kept; cached apart from the bf16 kernel's pack of the same weight)."""
-    global bf16_pack_launches
-    B, Cin, H, W = in_shape
-    inp = _req(inp, torch.float32, "conv input")
-    weight = _req(weight, torch.float32, "conv weight")
-    want_in, want_w, oshape = _data_pass_shapes(op, in_shape, Cout, 3, (H, W))
-    if tuple(inp.shape) != want_in or tuple(weight.shape) != want_w:
-        raise RuntimeError("conv3x3_bf16x3 op %d: input %s / weight %s do not match %s / %s" % (op, tuple(inp.shape), tuple(weight.shape), want_in, want_w))
-    L = _lib.lib()
-    nbytes = L.ipsr_conv3x3_bf16x3_workspace_bytes(op, B, Cin, H, W, Cout)
-    if nbytes == 0:
-        raise NotImplementedError("ipsr_conv3x3_bf16 (io 2): op %d on %s is not implemented (%s)" % (op, (B, Cin, H, W, Cout), L.ipsr_last_error().decode("utf-8", "replace")))
-    out = _empty(oshape, dtype=torch.float32, device=inp.device)
-    valid = 0
-    if keep_packed:
-        packs = _packs_of(weight if pack_key is None else pack_key)
-        ent = packs.get(("x3", op))
-        if ent is not None and ent[0] == (weight._version, weight.data_ptr()) and ent[1] == tuple(weight.shape) and ent[2].numel() >= nbytes \
-                and ent[2].device == inp.device:
-            ws, valid = ent[2], 1
-        else:
-            ws = _empty(nbytes, dtype=torch.uint8, device=inp.device)
-            packs[("x3", op)] = ((weight._version, weight.data_ptr()), tuple(weight.shape), ws)
-    else:
-        ws = _workspace(nbytes, inp.device)
-    bf16_pack_launches += 1 - valid
-    _lib.check(L.ipsr_conv3x3_bf16_packed(op, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Cin, H, W, Cout, 2,
-                                          valid, ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv3x3_bf16")
-    return out
+    return _conv3x3_direct("bf16x3", op, inp, weight, in_shape, Cout, torch.float32, keep_packed, pack_key)
 
 
 def conv4x4s2_bf16_supported(mode, B, Kc, Cf, nh, nw):
@@ -674,22 +735,7 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
     """The k4 s2 p1 layers as ONE direct implicit GEMM on the bf16 matrix cores (ipsr_conv4x4s2_bf16), in the coarse / fine terms of
     conv4x4s2_winograd: mode S2_FINE_TO_COARSE: inp = fine [B,Cf,2nh,2nw] -> coarse [B,Kc,nh,nw]; S2_COARSE_TO_FINE: the reverse.
     weight [Kc,Cf,4,4] fp32 (Conv2d: [Cout,Cin]; ConvTranspose2d: [Cin,Cout])."""
-    inp, in_bf = _act(inp, "conv input")
-    if not in_bf:
-        raise TypeError("conv4x4s2_bf16 reads bf16 activations, got %s" % inp.dtype)
-    weight = _req(weight, torch.float32, "conv weight")
-    if mode not in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE):
-        raise ValueError("conv4x4s2_bf16: mode %r" % (mode,))
-    want_in = (B, Cf, 2 * nh, 2 * nw) if mode == S2_FINE_TO_COARSE else (B, Kc, nh, nw)
-    if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
-        raise RuntimeError("conv4x4s2_bf16 mode %d: input %s / weight %s do not match %s / %s" % (mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
-    L = _lib.lib()
-    oshape = (B, Kc, nh, nw) if mode == S2_FINE_TO_COARSE else (B, Cf, 2 * nh, 2 * nw)
-    out = _empty(oshape, dtype=out_dtype, device=inp.device)
-    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_workspace_bytes(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_conv4x4s2_bf16: mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
-    _lib.check(L.ipsr_conv4x4s2_bf16(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, int(out_dtype == torch.bfloat16),
-                                     ws.data_ptr(), ws.numel(), _stream()), "ipsr_conv4x4s2_bf16")
-    return out
+    return _conv4x4s2_direct("bf16", mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype)
 
 
 def conv4x4s2_bf16x3_supported(mode, B, Kc, Cf, nh, nw):
@@ -700,20 +746,7 @@ def conv4x4s2_bf16x3(mode, inp, weight, B, Kc, Cf, nh, nw):
     """The k4 s2 p1 layers on FP32 tensors as ONE direct implicit GEMM on the bf16 matrix cores with split operands (ipsr_conv4x4s2_bf16x3,
     csrc/conv_bf16.hip): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32 accumulation; fp32 in, fp32 out.  mode, shapes
     and weight as in conv4x4s2_bf16."""
-    inp = _req(inp, torch.float32, "conv input")
-    weight = _req(weight, torch.float32, "conv weight")
-    if mode not in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE):
-        raise ValueError("conv4x4s2_bf16x3: mode %r" % (mode,))
-    want_in = (B, Cf, 2 * nh, 2 * nw) if mode == S2_FINE_TO_COARSE else (B, Kc, nh, nw)
-    if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
-        raise RuntimeError("conv4x4s2_bf16x3 mode %d: input %s / weight %s do not match %s / %s" % (mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
-    L = _lib.lib()
-    oshape = (B, Kc, nh, nw) if mode == S2_FINE_TO_COARSE else (B, Cf, 2 * nh, 2 * nw)
-    out = _empty(oshape, dtype=torch.float32, device=inp.device)
-    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16x3_workspace_bytes(mode, B, Kc, Cf, nh, nw), inp.device, "ipsr_conv4x4s2_bf16x3: mode %d on %s", (mode, (B, Kc, Cf, nh, nw)))
-    _lib.check(L.ipsr_conv4x4s2_bf16x3(mode, inp.data_ptr(), weight.data_ptr(), out.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
-               "ipsr_conv4x4s2_bf16x3")
-    return out
+    return _conv4x4s2_direct("bf16x3", mode, inp, weight, B, Kc, Cf, nh, nw, torch.float32)
 
 
 def conv4x4s2_bf16_wrw_supported(B, Kc, Cf, nh, nw):
@@ -723,18 +756,7 @@ def conv4x4s2_bf16_wrw_supported(B, Kc, Cf, nh, nw):
 def conv4x4s2_bf16_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     """Weight gradient [Kc,Cf,4,4] (fp32) of a k4 s2 p1 layer from its bf16 fine [B,Cf,2nh,2nw] and coarse [B,Kc,nh,nw] tensors
     (ipsr_conv4x4s2_bf16_wrw); `out`: optional contiguous fp32 destination (a gradient bucket slice)."""
-    fine, f_bf = _act(fine, "fine tensor")
-    coarse, c_bf = _act(coarse, "coarse tensor")
-    if not (f_bf and c_bf):
-        raise TypeError("conv4x4s2_bf16_wrw reads bf16 tensors")
-    if tuple(fine.shape) != (B, Cf, 2 * nh, 2 * nw) or tuple(coarse.shape) != (B, Kc, nh, nw):
-        raise RuntimeError("conv4x4s2_bf16_wrw: fine %s / coarse %s do not match %s / %s" % (tuple(fine.shape), tuple(coarse.shape), (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)))
-    L = _lib.lib()
-    dw = _result(out, (Kc, Cf, 4, 4), torch.float32, fine.device, "conv4x4s2_bf16_wrw")
-    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw), fine.device, "ipsr_conv4x4s2_bf16_wrw: %s", ((B, Kc, Cf, nh, nw),))
-    _lib.check(L.ipsr_conv4x4s2_bf16_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
-               "ipsr_conv4x4s2_bf16_wrw")
-    return dw
+    return _conv4x4s2_direct_wrw("bf16", fine, coarse, B, Kc, Cf, nh, nw, out)
 
 
 def conv4x4s2_bf16x3_wrw_supported(B, Kc, Cf, nh, nw):
@@ -745,16 +767,7 @@ def conv4x4s2_bf16x3_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     """Weight gradient [Kc,Cf,4,4] (fp32) of a k4 s2 p1 layer from its FP32 fine [B,Cf,2nh,2nw] and coarse [B,Kc,nh,nw] tensors on the bf16
     matrix cores with split operands (ipsr_conv4x4s2_bf16x3_wrw): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32
     accumulation, the split in the kernel; `out`: optional contiguous fp32 destination (a gradient bucket slice)."""
-    fine = _req(fine, torch.float32, "fine tensor")
-    coarse = _req(coarse, torch.float32, "coarse tensor")
-    if tuple(fine.shape) != (B, Cf, 2 * nh, 2 * nw) or tuple(coarse.shape) != (B, Kc, nh, nw):
-        raise RuntimeError("conv4x4s2_bf16x3_wrw: fine %s / coarse %s do not match %s / %s" % (tuple(fine.shape), tuple(coarse.shape), (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)))
-    L = _lib.lib()
-    dw = _result(out, (Kc, Cf, 4, 4), torch.float32, fine.device, "conv4x4s2_bf16x3_wrw")
-    ws = _probed_workspace(L, L.ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(B, Kc, Cf, nh, nw), fine.device, "ipsr_conv4x4s2_bf16x3_wrw: %s", ((B, Kc, Cf, nh, nw),))
-    _lib.check(L.ipsr_conv4x4s2_bf16x3_wrw(fine.data_ptr(), coarse.data_ptr(), dw.data_ptr(), B, Kc, Cf, nh, nw, ws.data_ptr(), ws.numel(), _stream()),
-               "ipsr_conv4x4s2_bf16x3_wrw")
-    return dw
+    return _conv4x4s2_direct_wrw("bf16x3", fine, coarse, B, Kc, Cf, nh, nw, out)
 
 
 def conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):
@@ -764,19 +777,7 @@ def conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):
 def conv3x3_bf16_wrw(transposed, x, dy, Cout, out=None):
     """Weight gradient of a k3 s1 p1 Conv2d (-> [Cout,Cin,3,3]) / ConvTranspose2d (-> [Cin,Cout,3,3]) on the bf16 matrix cores
     (ipsr_conv3x3_bf16_wrw): x, dy bf16; the result fp32 (optionally written into `out`, e.g. a slice of a gradient bucket)."""
-    x, x_bf = _act(x, "conv input")
-    dy, dy_bf = _act(dy, "grad_output")
-    if not (x_bf and dy_bf):
-        raise TypeError("conv3x3_bf16_wrw reads bf16 tensors")
-    B, Cin, H, W = x.shape
-    if tuple(dy.shape) != (B, Cout, H, W):
-        raise RuntimeError("conv3x3_bf16_wrw: grad_output %s does not match %s" % (tuple(dy.shape), (B, Cout, H, W)))
-    L = _lib.lib()
-    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_bf16_wrw")
-    ws = _probed_workspace(L, L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device, "ipsr_conv3x3_bf16_wrw: %s", ((B, Cin, H, W, Cout),))
-    _lib.check(L.ipsr_conv3x3_bf16_wrw(int(transposed), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
-                                       _stream()), "ipsr_conv3x3_bf16_wrw")
-    return dw
+    return _conv3x3_direct_wrw("bf16", transposed, x, dy, Cout, out)
 
 
 def conv3x3_bf16x3_wrw_supported(transposed, B, Cin, H, W, Cout):
@@ -787,17 +788,7 @@ def conv3x3_bf16x3_wrw(transposed, x, dy, Cout, out=None):
     """Weight gradient of a k3 s1 p1 Conv2d (-> [Cout,Cin,3,3]) / ConvTranspose2d (-> [Cin,Cout,3,3]) on FP32 tensors with split-bf16
     operands (forms 2 / 3 of ipsr_conv3x3_bf16_wrw): x, dy fp32; the result fp32 (optionally written into `out`, e.g. a slice of a
     gradient bucket)."""
-    x = _req(x, torch.float32, "conv input")
-    dy = _req(dy, torch.float32, "grad_output")
-    B, Cin, H, W = x.shape
-    if tuple(dy.shape) != (B, Cout, H, W):
-        raise RuntimeError("conv3x3_bf16x3_wrw: grad_output %s does not match %s" % (tuple(dy.shape), (B, Cout, H, W)))
-    L = _lib.lib()
-    dw = _result(out, (Cin, Cout, 3, 3) if transposed else (Cout, Cin, 3, 3), torch.float32, x.device, "conv3x3_bf16x3_wrw")
-    ws = _probed_workspace(L, L.ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout), x.device, "ipsr_conv3x3_bf16_wrw (split-bf16): %s", ((B, Cin, H, W, Cout),))
-    _lib.check(L.ipsr_conv3x3_bf16_wrw(2 + int(bool(transposed)), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, ws.data_ptr(), ws.numel(),
-                                       _stream()), "ipsr_conv3x3_bf16_wrw")
-    return dw
+    return _conv3x3_direct_wrw("bf16x3", transposed, x, dy, Cout, out)
 
 
 GEOM_K4_S2_P3_D2 = 0       # Conv2d(k4, stride 2, pad 3, dilation 2): netG's down convolution

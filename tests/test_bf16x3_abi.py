@@ -2,27 +2,16 @@
 before any HIP call, and the dispatcher's opt-in rule.  Nothing here launches a kernel; the calls on fake addresses run in a child
 process with every GPU hidden, as in tests/test_abi_alignment.py.
 """
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import bf16_conv_plan as P
+from bf16x3_harness import fake_pointers, hipconv, lib, refused_calls  # noqa: F401  (fixtures by name)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IPSR_ERR_INVALID = -1
 # (B, Cin, Cout, H, W): the shapes of tests/test_gpu_bf16x3_conv.py
 SHAPES = [(2, 16, 48, 16, 16), (3, 48, 80, 32, 16), (2, 64, 64, 2, 256), (2, 32, 64, 12, 64), (1, 128, 128, 16, 16)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from deepinpainting_amd import _lib
-    return _lib.lib()
 
 
 def test_workspace_query_accepts_the_gpu_shapes(lib):
@@ -49,24 +38,14 @@ def test_the_bf16_plan_is_untouched(lib):
             assert lib.ipsr_conv3x3_bf16_workspace_bytes(op, B, Cin, H, W, Cout) == P.k3_ws(op, B, Cin, H, W, Cout) > 0
 
 
-def _child():
-    sys.path.insert(0, ROOT)
-    from deepinpainting_amd import _lib
-    L = _lib.lib()
-    base, out = 1 << 40, {}
-    for name, io, off in (("in+8", 2, (8, 0, 0)), ("out+8", 2, (0, 8, 0)), ("ws+8", 2, (0, 0, 8)), ("io7", 7, (0, 0, 0))):
-        for entry, extra in (("ipsr_conv3x3_bf16", ()), ("ipsr_conv3x3_bf16_packed", (0,))):
-            rc = getattr(L, entry)(0, base + off[0], base + (1 << 20), base + (2 << 20) + off[1], 2, 32, 16, 16, 48, io, *extra, base + (3 << 20) + off[2], 1 << 40, None)
-            out["%s:%s" % (entry, name)] = (rc, L.ipsr_last_error().decode("utf-8", "replace"))
-    print(json.dumps(out))
-
-
 @pytest.fixture(scope="module")
 def refusals(lib):
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    return json.loads(res.stdout.strip().splitlines()[-1])
+    calls = {}
+    for name, io, off in (("in+8", 2, (8, 0, 0, 0)), ("out+8", 2, (0, 0, 8, 0)), ("ws+8", 2, (0, 0, 0, 8)), ("io7", 7, (0, 0, 0, 0))):
+        inp, w, out, ws = fake_pointers(off, stride=1 << 20)
+        for entry, extra in (("ipsr_conv3x3_bf16", ()), ("ipsr_conv3x3_bf16_packed", (0,))):
+            calls["%s:%s" % (entry, name)] = (entry, (0, inp, w, out, 2, 32, 16, 16, 48, io, *extra, ws, 1 << 40, None))
+    return refused_calls(calls)
 
 
 @pytest.mark.parametrize("entry", ["ipsr_conv3x3_bf16", "ipsr_conv3x3_bf16_packed"])
@@ -74,19 +53,6 @@ def refusals(lib):
 def test_refused_before_any_hip_call(refusals, entry, case):
     rc, msg = refusals["%s:%s" % (entry, case)]
     assert rc == IPSR_ERR_INVALID and ("io code 7" if case == "io7" else "align") in msg, (rc, msg)
-
-
-@pytest.fixture
-def hipconv(lib, monkeypatch):
-    from deepinpainting_amd.models import hipconv as hc
-    monkeypatch.setattr(hc, "_FORCE", None)
-    monkeypatch.delenv("IPSR_CONV_ENGINE", raising=False)
-    hc.reload_env()
-    was = hc._MATH["fp32"]
-    yield hc
-    hc._FORCE = None
-    hc.set_conv_math(fp32=was)
-    hc.reload_env()
 
 
 def test_selection_is_opt_in(hipconv):
@@ -136,5 +102,16 @@ def test_unknown_arithmetic_still_raises(hipconv):
     assert hipconv._MATH == {"fp32": "fp32", "bf16": "bf16x3"}
 
 
-if __name__ == "__main__" and sys.argv[1:] == ["--child"]:
-    _child()
+def test_the_direct_names_are_a_chain_of_supersets(hipconv):
+    """ops.DIRECT_PASSES is the one table of the opt-in names: each moves what the one before it moves plus more, none is a Winograd
+    arithmetic (code 0), none is for bf16 activations."""
+    from deepinpainting_amd import ops
+    chain = ["direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw"]
+    assert list(ops.DIRECT_PASSES) == chain
+    assert all(ops.DIRECT_PASSES[a] < ops.DIRECT_PASSES[b] for a, b in zip(chain, chain[1:]))       # strict subsets
+    assert ops.DIRECT_PASSES[chain[-1]] == {"k3_data", "k3_wrw", "s2_data", "s2_wrw"}
+    assert set(ops.MATH_CODE) == {None, "fp32", "bf16x3", "bf16x6", *chain} and all(ops.MATH_CODE[n] == 0 for n in chain)
+    for name in chain:
+        with pytest.raises(ValueError):
+            hipconv.set_conv_math(bf16=name)
+    assert hipconv._MATH == {"fp32": "fp32", "bf16": "bf16x3"}

@@ -3,28 +3,17 @@ under `set_conv_math(fp32="direct_bf16x3_s2")`) without a GPU: its workspace que
 before any HIP call, and the dispatcher's opt-in rule.  Nothing here launches a kernel; the calls on fake addresses run in a child process
 with every GPU hidden, as in tests/test_bf16x3_abi.py.
 """
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import bf16_conv_plan as P
 import bf16x3_s2_plan as S
+from bf16x3_harness import fake_pointers, hipconv, lib, refused_calls  # noqa: F401  (fixtures by name)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
 # the k4 s2 p1 data rows of the step at batch 8 that "wino_s2" has today: (Kc, Cf, n)
 STEP_ROWS = [(128, 64, 64), (256, 128, 32), (512, 256, 16), (128, 128, 64), (256, 256, 32), (512, 512, 16), (256, 64, 64), (512, 128, 32), (1024, 256, 16)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from deepinpainting_amd import _lib
-    return _lib.lib()
 
 
 def test_the_cases_reach_their_variants():
@@ -65,12 +54,9 @@ def test_the_bf16_query_answers_as_before(lib):
                     assert lib.ipsr_conv4x4s2_bf16_workspace_bytes(mode, B, Kc, Cf, nh, nw) == P.s2_ws(mode, B, Kc, Cf, nh, nw), (mode, B, Kc, Cf, nh, nw)
 
 
-def _child():
-    sys.path.insert(0, ROOT)
-    from deepinpainting_amd import _lib
-    L = _lib.lib()
-    base, out = 1 << 40, {}
-    need = L.ipsr_conv4x4s2_bf16x3_workspace_bytes(0, 2, 48, 16, 16, 16)
+@pytest.fixture(scope="module")
+def refusals(lib):
+    need = lib.ipsr_conv4x4s2_bf16x3_workspace_bytes(0, 2, 48, 16, 16, 16)
     good = (2, 48, 16, 16, 16)
     # name: (mode, shape, (in, weight, out, ws) offsets or None for a null pointer, workspace bytes)
     calls = {"w24": (0, (1, 16, 16, 12, 24), (0, 0, 0, 0), 1 << 30), "c8": (0, (1, 16, 8, 16, 16), (0, 0, 0, 0), 1 << 30),
@@ -78,19 +64,11 @@ def _child():
              "null_in": (0, good, (None, 0, 0, 0), 1 << 30), "null_ws": (1, good, (0, 0, 0, None), 1 << 30),
              "in+8": (0, good, (8, 0, 0, 0), 1 << 30), "out+8": (1, good, (0, 0, 8, 0), 1 << 30), "ws+4": (0, good, (0, 0, 0, 4), 1 << 30),
              "ws_short": (0, good, (0, 0, 0, 0), need - 1)}
+    table = {}
     for name, (mode, shape, off, nbytes) in calls.items():
-        ptr = [None if o is None else base + (i << 28) + o for i, o in enumerate(off)]
-        rc = L.ipsr_conv4x4s2_bf16x3(mode, ptr[0], ptr[1], ptr[2], *shape, ptr[3], nbytes, None)
-        out[name] = (rc, L.ipsr_last_error().decode("utf-8", "replace"))
-    print(json.dumps(out))
-
-
-@pytest.fixture(scope="module")
-def refusals(lib):
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    return json.loads(res.stdout.strip().splitlines()[-1])
+        ptr = fake_pointers(off)
+        table[name] = ("ipsr_conv4x4s2_bf16x3", (mode, ptr[0], ptr[1], ptr[2], *shape, ptr[3], nbytes, None))
+    return refused_calls(table)
 
 
 @pytest.mark.parametrize("case,rc,msg", [("w24", IPSR_ERR_UNSUPPORTED, "coarse width 24"), ("c8", IPSR_ERR_UNSUPPORTED, "8 reduction channels"),
@@ -102,20 +80,6 @@ def refusals(lib):
 def test_refused_before_any_hip_call(refusals, case, rc, msg):
     got, text = refusals[case]
     assert got == rc and msg in text, (got, text)
-
-
-@pytest.fixture
-def hipconv(lib, monkeypatch):
-    from deepinpainting_amd.models import hipconv as hc
-    monkeypatch.setattr(hc, "_FORCE", None)
-    for name in ("IPSR_CONV_ENGINE", "IPSR_NO_SMALLMAP", "IPSR_NO_THIN", "IPSR_SMALLMAP_MAX_POS", "IPSR_BF16_ENGINES"):
-        monkeypatch.delenv(name, raising=False)
-    hc.reload_env()
-    was = hc._MATH["fp32"]
-    yield hc
-    hc._FORCE = None
-    hc.set_conv_math(fp32=was)
-    hc.reload_env()
 
 
 def test_selection_is_opt_in(hipconv):
@@ -200,7 +164,3 @@ def test_the_new_name_is_fp32_only(hipconv):
     with pytest.raises(ValueError):
         hipconv.set_conv_math(bf16="direct_bf16x3_s2")
     assert hipconv._MATH == {"fp32": "fp32", "bf16": "bf16x3"}
-
-
-if __name__ == "__main__" and sys.argv[1:] == ["--child"]:
-    _child()

@@ -3,17 +3,14 @@
 the restated plan, the refusals that come before any HIP call, and the dispatcher's opt-in rule.  Nothing here launches a kernel; the
 calls on fake addresses run in a child process with every GPU hidden, as in tests/test_bf16x3_s2_abi.py.
 """
-import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
 import bf16x3_s2_wrw_plan as X
+from bf16x3_harness import ROOT, fake_pointers, hipconv, lib, refused_calls  # noqa: F401  (fixtures by name)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
 ENTRIES = ("ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes", "ipsr_conv4x4s2_bf16x3_wrw")
 # every k4 s2 p1 layer of the step at batch 8 as (transposed, Cin, H, Cout) of the module, and what select_wrw answered for it on the parent
@@ -26,14 +23,6 @@ STEP_ROWS = {
 }
 # the rows of the rule (profiles/direct_bf16x3_s2_wrw_layers.txt)
 RULE_ROWS = [k for k, v in STEP_ROWS.items() if v == "wino_s2"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from deepinpainting_amd import _lib
-    return _lib.lib()
 
 
 def test_the_cases_reach_their_variants():
@@ -79,31 +68,20 @@ def test_workspace_query_refuses_with_a_message(lib, shape, msg):
     assert msg in lib.ipsr_last_error().decode("utf-8", "replace")
 
 
-def _child():
-    sys.path.insert(0, ROOT)
-    from deepinpainting_amd import _lib
-    L = _lib.lib()
-    base, out = 1 << 40, {}
+@pytest.fixture(scope="module")
+def refusals(lib):
     good = (2, 48, 16, 8, 16)
-    need = L.ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(*good)
+    need = lib.ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(*good)
     # name: (shape, (fine, coarse, dw, ws) offsets or None for a null pointer, workspace bytes)
     calls = {"w24": ((1, 16, 16, 4, 24), (0, 0, 0, 0), 1 << 30), "w128": ((1, 32, 64, 2, 128), (0, 0, 0, 0), 1 << 30), "rows": ((1, 16, 16, 6, 16), (0, 0, 0, 0), 1 << 30),
              "b0": ((0, 48, 16, 8, 16), (0, 0, 0, 0), 1 << 30), "null_fine": (good, (None, 0, 0, 0), 1 << 30), "null_dw": (good, (0, 0, None, 0), 1 << 30),
              "null_ws": (good, (0, 0, 0, None), 1 << 30), "fine+8": (good, (8, 0, 0, 0), 1 << 30), "coarse+4": (good, (0, 4, 0, 0), 1 << 30),
              "dw+8": (good, (0, 0, 8, 0), 1 << 30), "ws+4": (good, (0, 0, 0, 4), 1 << 30), "ws_short": (good, (0, 0, 0, 0), need - 1)}
+    table = {}
     for name, (shape, off, nbytes) in calls.items():
-        ptr = [None if o is None else base + (i << 28) + o for i, o in enumerate(off)]
-        rc = L.ipsr_conv4x4s2_bf16x3_wrw(ptr[0], ptr[1], ptr[2], *shape, ptr[3], nbytes, None)
-        out[name] = (rc, L.ipsr_last_error().decode("utf-8", "replace"))
-    print(json.dumps(out))
-
-
-@pytest.fixture(scope="module")
-def refusals(lib):
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    return json.loads(res.stdout.strip().splitlines()[-1])
+        ptr = fake_pointers(off)
+        table[name] = ("ipsr_conv4x4s2_bf16x3_wrw", (ptr[0], ptr[1], ptr[2], *shape, ptr[3], nbytes, None))
+    return refused_calls(table)
 
 
 @pytest.mark.parametrize("case,rc,msg", [("w24", IPSR_ERR_UNSUPPORTED, "coarse width 24"), ("w128", IPSR_ERR_UNSUPPORTED, "coarse width 128"),
@@ -115,20 +93,6 @@ def refusals(lib):
 def test_refused_before_any_hip_call(refusals, case, rc, msg):
     got, text = refusals[case]
     assert got == rc and msg in text, (got, text)
-
-
-@pytest.fixture
-def hipconv(lib, monkeypatch):
-    from deepinpainting_amd.models import hipconv as hc
-    monkeypatch.setattr(hc, "_FORCE", None)
-    for name in ("IPSR_CONV_ENGINE", "IPSR_NO_SMALLMAP", "IPSR_NO_THIN", "IPSR_SMALLMAP_MAX_POS", "IPSR_BF16_ENGINES"):
-        monkeypatch.delenv(name, raising=False)
-    hc.reload_env()
-    was = hc._MATH["fp32"]
-    yield hc
-    hc._FORCE = None
-    hc.set_conv_math(fp32=was)
-    hc.reload_env()
 
 
 def _wrw(hc, row, B=8):
@@ -207,7 +171,3 @@ def test_the_new_name_is_fp32_only(hipconv):
     with pytest.raises(ValueError):
         hipconv.set_conv_math(bf16="direct_bf16x3_s2_dw")
     assert hipconv._MATH == {"fp32": "fp32", "bf16": "bf16x3"}
-
-
-if __name__ == "__main__" and sys.argv[1:] == ["--child"]:
-    _child()

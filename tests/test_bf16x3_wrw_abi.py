@@ -3,26 +3,15 @@ without a GPU: its workspace query, the refusals that come before any HIP call, 
 (`set_conv_math(fp32="direct_bf16x3_dw")`).  Nothing here launches a kernel; the calls on fake addresses run in a child process with
 every GPU hidden, as in tests/test_bf16x3_abi.py.
 """
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import bf16_conv_plan as P
 import bf16x3_wrw_plan as X
+from bf16x3_harness import fake_pointers, hipconv, lib, refused_calls  # noqa: F401  (fixtures by name)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IPSR_ERR_INVALID = -1
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from deepinpainting_amd import _lib
-    return _lib.lib()
 
 
 def test_the_cases_reach_their_variants():
@@ -52,23 +41,13 @@ def test_the_bf16_plan_is_untouched(lib):
         assert lib.ipsr_conv3x3_bf16_wrw_workspace_bytes(tr, B, Cin, H, W, Cout) == P.k3_wrw_ws(tr, B, Cin, H, W, Cout) > 0, cid
 
 
-def _child():
-    sys.path.insert(0, ROOT)
-    from deepinpainting_amd import _lib
-    L = _lib.lib()
-    base, out = 1 << 40, {}
-    for name, form, off in (("x+8", 2, (8, 0, 0)), ("dy+8", 3, (0, 8, 0)), ("ws+8", 2, (0, 0, 8)), ("form4", 4, (0, 0, 0)), ("form-1", -1, (0, 0, 0))):
-        rc = L.ipsr_conv3x3_bf16_wrw(form, base + off[0], base + (1 << 24) + off[1], base + (2 << 24), 2, 32, 16, 16, 48, base + (3 << 24) + off[2], 1 << 40, None)
-        out[name] = (rc, L.ipsr_last_error().decode("utf-8", "replace"))
-    print(json.dumps(out))
-
-
 @pytest.fixture(scope="module")
 def refusals(lib):
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    return json.loads(res.stdout.strip().splitlines()[-1])
+    calls = {}
+    for name, form, off in (("x+8", 2, (8, 0, 0, 0)), ("dy+8", 3, (0, 8, 0, 0)), ("ws+8", 2, (0, 0, 0, 8)), ("form4", 4, (0, 0, 0, 0)), ("form-1", -1, (0, 0, 0, 0))):
+        x, dy, dw, ws = fake_pointers(off, stride=1 << 24)
+        calls[name] = ("ipsr_conv3x3_bf16_wrw", (form, x, dy, dw, 2, 32, 16, 16, 48, ws, 1 << 40, None))
+    return refused_calls(calls)
 
 
 @pytest.mark.parametrize("case", ["x+8", "dy+8", "ws+8", "form4", "form-1"])
@@ -76,20 +55,6 @@ def test_refused_before_any_hip_call(refusals, case):
     rc, msg = refusals[case]
     want = {"form4": "form code 4", "form-1": "form code -1"}.get(case, "align")
     assert rc == IPSR_ERR_INVALID and want in msg, (rc, msg)
-
-
-@pytest.fixture
-def hipconv(lib, monkeypatch):
-    from deepinpainting_amd.models import hipconv as hc
-    monkeypatch.setattr(hc, "_FORCE", None)
-    for name in ("IPSR_CONV_ENGINE", "IPSR_NO_SMALLMAP", "IPSR_NO_THIN", "IPSR_SMALLMAP_MAX_POS", "IPSR_BF16_ENGINES"):
-        monkeypatch.delenv(name, raising=False)
-    hc.reload_env()
-    was = hc._MATH["fp32"]
-    yield hc
-    hc._FORCE = None
-    hc.set_conv_math(fp32=was)
-    hc.reload_env()
 
 
 def test_selection_is_opt_in(hipconv):
@@ -154,7 +119,3 @@ def test_the_new_name_is_fp32_only(hipconv):
     with pytest.raises(ValueError):
         hipconv.set_conv_math(bf16="direct_bf16x3_dw")
     assert hipconv._MATH == {"fp32": "fp32", "bf16": "bf16x3"}
-
-
-if __name__ == "__main__" and sys.argv[1:] == ["--child"]:
-    _child()

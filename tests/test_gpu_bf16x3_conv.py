@@ -24,12 +24,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from guarded import Arena
+from bf16x3_harness import NAN_BITS, _bits, _in_band, _module_pass, _same, check_bf16_representable, check_guarded, direct_math, draw  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
-F32, BF16 = torch.float32, torch.bfloat16
+F32 = torch.float32
 
 SHAPES = {
     "one_stage": (2, 16, 48, 16, 16),
@@ -60,24 +60,12 @@ def x3_plan(op, B, Cin, H, W, Cout):
     return dict(nsplit=nsplit, sps=sps, ktiles=ktiles, tiles_per_img=H // R, nstage=nstage, ws=ws)
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
 def _operands(op, B, Cin, Cout, H, W, seed):
     """(input of the op, weight in the module's layout): normal draws times a per-channel power of two in 2^-6 .. 2^6."""
     g = torch.Generator(device="cuda").manual_seed(seed)
     cin_op = Cin if op in (0, 2) else Cout
     wshape = (Cout, Cin, 3, 3) if op < 2 else (Cin, Cout, 3, 3)
-    x = torch.randn(B, cin_op, H, W, device="cuda", generator=g)
-    x = x * torch.exp2(torch.randint(-6, 7, (1, cin_op, 1, 1), device="cuda", generator=g).float())
-    w = torch.randn(wshape, device="cuda", generator=g)
-    w = w * torch.exp2(torch.randint(-6, 7, (wshape[0], 1, 1, 1), device="cuda", generator=g).float())
-    return x, w
+    return draw(g, (B, cin_op, H, W), 1), draw(g, wshape, 0)
 
 
 def _ref64(op, x, w):
@@ -88,13 +76,6 @@ def _ref64(op, x, w):
 
 def _band(op, x, w, y64):
     return 2.0 ** -16 * _ref64(op, x.abs(), w.abs()) + 1e-5 * y64.abs().max()
-
-
-def _in_band(tag, y, y64, band):
-    err = (y.double() - y64).abs()
-    worst = float((err / band).max())
-    print("%s: max |err| / band %.3f, max |err| / max|y64| %.2e" % (tag, worst, float(err.max() / y64.abs().max())))
-    assert torch.isfinite(y).all() and worst <= 1.0, (tag, worst)
 
 
 @pytest.mark.parametrize("sid", list(SHAPES))
@@ -130,26 +111,12 @@ def test_split_bf16_direct_conv(sid, monkeypatch):
                 _in_band("%s op %d image %d" % (sid, op, b), yb, y64[b:b + 1], _band(op, x, w, y64)[b:b + 1])
                 if (one["nsplit"], one["sps"]) == (plan["nsplit"], plan["sps"]):
                     assert _same(yb, y[b:b + 1]), "%s op %d: image %d alone differs from the batch" % (sid, op, b)
-        # between guard bands, on a NaN-filled workspace of exactly the size asked for
-        arena = Arena(ws_fill="nan")
-        gx, gw = arena.guarded_copy(x, "x"), arena.guarded_copy(w, "w")
-        with arena.installed(monkeypatch):
-            yg = run(gx, gw)
-        torch.cuda.synchronize()
-        arena.check_guards()
-        assert _same(gx, x) and _same(gw, w), "an input was modified"
-        assert _same(yg, y), "%s op %d: the guarded run differs" % (sid, op)
-        assert arena.workspaces and arena.workspaces[0][0] == plan["ws"]
-        # bf16-representable operands: lo = 0, the products are exact, only the fp32 accumulation is left
-        xr, wr = x.to(BF16).float(), w.to(BF16).float()
-        r64 = _ref64(op, xr, wr)
-        e = float((run(xr, wr).double() - r64).abs().max() / r64.abs().max())
-        print("%s op %d bf16-representable operands: %.2e of the output scale" % (sid, op, e))
-        assert e <= 1e-5, (sid, op, e)
+        check_guarded(monkeypatch, run, (x, w), ("x", "w"), y, plan["ws"], "%s op %d" % (sid, op))
+        check_bf16_representable(run, lambda a, ww: _ref64(op, a, ww), (x, w), "%s op %d" % (sid, op))
 
 
 def _nan_fill(t):
-    _bits(t).fill_(0x7FC00DAD)
+    _bits(t).fill_(NAN_BITS)
     return t
 
 
@@ -185,28 +152,6 @@ def test_refusals_write_nothing(what):
 
 
 # ---- through the modules ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def direct_math(request):
-    from deepinpainting_amd.models import hipconv
-    was = (hipconv._MATH["fp32"], hipconv._check_hook)
-
-    def restore():
-        hipconv.set_conv_math(fp32=was[0])
-        hipconv._check_hook = was[1]
-    request.addfinalizer(restore)
-    return hipconv
-
-
-def _module_pass(hipconv, m, x, dy):
-    seen = {}
-    hipconv._check_hook = lambda kind, eng, geom, operands, result: seen.__setitem__(kind, eng)
-    xr = x.clone().requires_grad_(True)
-    y = hipconv.conv_nobias(m, xr)
-    dx, dw = torch.autograd.grad(y, (xr, m.weight), dy)
-    torch.cuda.synchronize()
-    return seen, y.detach(), dx, dw
-
-
 @pytest.mark.parametrize("mk", [lambda: nn.Conv2d(64, 64, 3, padding=1), lambda: nn.ConvTranspose2d(128, 64, 3, padding=1)], ids=["conv64", "convT128_64"])
 def test_modules_run_the_engine_when_asked(mk, direct_math):
     hipconv = direct_math

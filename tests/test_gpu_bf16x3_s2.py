@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import bf16x3_s2_plan as S
-from guarded import Arena
+from bf16x3_harness import NAN_BITS, _bits, _in_band, _module_pass, _same, check_bf16_representable, check_guarded, direct_math, draw  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +24,11 @@ IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
 F32, BF16 = torch.float32, torch.bfloat16
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
 def _operands(mode, B, Kc, Cf, nh, nw, seed):
     """(input of the pass, weight [Kc,Cf,4,4]): normal draws times a per-channel power of two in 2^-6 .. 2^6."""
     g = torch.Generator(device="cuda").manual_seed(seed)
     shape = (B, Cf, 2 * nh, 2 * nw) if mode == 0 else (B, Kc, nh, nw)
-    x = torch.randn(shape, device="cuda", generator=g)
-    x = x * torch.exp2(torch.randint(-6, 7, (1, shape[1], 1, 1), device="cuda", generator=g).float())
-    w = torch.randn(Kc, Cf, 4, 4, device="cuda", generator=g)
-    w = w * torch.exp2(torch.randint(-6, 7, (Kc, 1, 1, 1), device="cuda", generator=g).float())
-    return x, w
+    return draw(g, shape, 1), draw(g, (Kc, Cf, 4, 4), 0)
 
 
 def _ref64(mode, x, w):
@@ -50,13 +38,6 @@ def _ref64(mode, x, w):
 
 def _band(mode, x, w, y64):
     return 2.0 ** -16 * _ref64(mode, x.abs(), w.abs()) + 1e-5 * y64.abs().max()
-
-
-def _in_band(tag, y, y64, band):
-    err = (y.double() - y64).abs()
-    worst = float((err / band).max())
-    print("%s: max |err| / band %.3f, max |err| / max|y64| %.2e" % (tag, worst, float(err.max() / y64.abs().max())))
-    assert torch.isfinite(y).all() and worst <= 1.0, (tag, worst)
 
 
 @pytest.mark.parametrize("mode", [0, 1], ids=["fine_to_coarse", "coarse_to_fine"])
@@ -88,26 +69,12 @@ def test_split_bf16_direct_s2(cid, mode, monkeypatch):
             _in_band("%s image %d" % (tag, b), yb, y64[b:b + 1], band[b:b + 1])
             if (one["nsplit"], one["sps"]) == (plan["nsplit"], plan["sps"]):
                 assert _same(yb, y[b:b + 1]), "%s: image %d alone differs from the batch" % (tag, b)
-    # between guard bands, on a NaN-filled workspace of exactly the size asked for
-    arena = Arena(ws_fill="nan")
-    gx, gw = arena.guarded_copy(x, "x"), arena.guarded_copy(w, "w")
-    with arena.installed(monkeypatch):
-        yg = run(gx, gw)
-    torch.cuda.synchronize()
-    arena.check_guards()
-    assert _same(gx, x) and _same(gw, w), "an input was modified"
-    assert _same(yg, y), "%s: the guarded run differs" % tag
-    assert arena.workspaces and arena.workspaces[0][0] == plan["ws"]
-    # bf16-representable operands: lo = 0, the products are exact, only the fp32 accumulation is left
-    xr, wr = x.to(BF16).float(), w.to(BF16).float()
-    r64 = _ref64(mode, xr, wr)
-    e = float((run(xr, wr).double() - r64).abs().max() / r64.abs().max())
-    print("%s bf16-representable operands: %.2e of the output scale" % (tag, e))
-    assert e <= 1e-5, (tag, e)
+    check_guarded(monkeypatch, run, (x, w), ("x", "w"), y, plan["ws"], tag)
+    check_bf16_representable(run, lambda a, ww: _ref64(mode, a, ww), (x, w), tag)
 
 
 def _nan_fill(t):
-    _bits(t).fill_(0x7FC00DAD)
+    _bits(t).fill_(NAN_BITS)
     return t
 
 
@@ -160,28 +127,6 @@ def test_wrong_dtype_and_shape_raise():
 
 
 # ---- through the modules ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def direct_math(request):
-    from deepinpainting_amd.models import hipconv
-    was = (hipconv._MATH["fp32"], hipconv._check_hook)
-
-    def restore():
-        hipconv.set_conv_math(fp32=was[0])
-        hipconv._check_hook = was[1]
-    request.addfinalizer(restore)
-    return hipconv
-
-
-def _module_pass(hipconv, m, x, dy):
-    seen = {}
-    hipconv._check_hook = lambda kind, eng, geom, operands, result: seen.__setitem__(kind, eng)
-    xr = x.clone().requires_grad_(True)
-    y = hipconv.conv_nobias(m, xr)
-    dx, dw = torch.autograd.grad(y, (xr, m.weight), dy)
-    torch.cuda.synchronize()
-    return seen, y.detach(), dx, dw
-
-
 @pytest.mark.parametrize("mk", [lambda: nn.Conv2d(64, 128, 4, 2, 1), lambda: nn.ConvTranspose2d(128, 64, 4, 2, 1)], ids=["conv64_128", "convT128_64"])
 def test_modules_run_the_engine_when_asked(mk, direct_math):
     hipconv = direct_math

@@ -23,7 +23,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import bf16x3_s2_wrw_plan as X
-from guarded import Arena
+from bf16x3_harness import NAN_BITS, _bits, _module_pass, _same, check_bf16_representable, check_guarded, check_out_slice, draw
+from bf16x3_harness import _in_band as _in_band_of
+from bf16x3_harness import direct_math_deterministic  # noqa: F401  (the fixture `direct_math`)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +33,10 @@ IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
 F32, BF16 = torch.float32, torch.bfloat16
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
 def _operands(B, Kc, Cf, nh, nw, seed):
     """(fine, coarse): normal draws times a per-channel power of two in 2^-6 .. 2^6."""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    fine = torch.randn(B, Cf, 2 * nh, 2 * nw, device="cuda", generator=g)
-    fine = fine * torch.exp2(torch.randint(-6, 7, (1, Cf, 1, 1), device="cuda", generator=g).float())
-    coarse = torch.randn(B, Kc, nh, nw, device="cuda", generator=g)
-    coarse = coarse * torch.exp2(torch.randint(-6, 7, (1, Kc, 1, 1), device="cuda", generator=g).float())
-    return fine, coarse
+    return draw(g, (B, Cf, 2 * nh, 2 * nw), 1), draw(g, (B, Kc, nh, nw), 1)
 
 
 def _wrw64(fine, coarse):
@@ -60,10 +50,7 @@ def _band(fine, coarse, d64):
 
 
 def _in_band(tag, d, d64, band):
-    err = (d.double() - d64).abs()
-    worst = float((err / band).max())
-    print("%s: max |err| / band %.3f, max |err| / max|dW64| %.2e" % (tag, worst, float(err.max() / d64.abs().max())))
-    assert torch.isfinite(d).all() and worst <= 1.0, (tag, worst)
+    _in_band_of(tag, d, d64, band, ref="dW64")
 
 
 _REF = {}
@@ -92,38 +79,16 @@ def test_split_bf16_s2_weight_gradient(cid, monkeypatch):
     assert ops.conv4x4s2_bf16x3_wrw_supported(*shape)
     assert L.ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(*shape) == plan["ws"], (cid, plan)
     fine, coarse, d64, band = _case(cid)
-    f0, c0 = fine.clone(), coarse.clone()
     d = ops.conv4x4s2_bf16x3_wrw(fine, coarse, *shape)
     torch.cuda.synchronize()
     assert d.dtype == F32 and tuple(d.shape) == (Kc, Cf, 4, 4)
     _in_band(cid, d, d64, band)
     # a second call: the same bits
     assert _same(ops.conv4x4s2_bf16x3_wrw(fine, coarse, *shape), d), "%s: two calls differ" % cid
-    # between guard bands, on a NaN-filled workspace of exactly the size asked for
-    arena = Arena(ws_fill="nan")
-    gf, gc = arena.guarded_copy(fine, "fine"), arena.guarded_copy(coarse, "coarse")
-    with arena.installed(monkeypatch):
-        dg = ops.conv4x4s2_bf16x3_wrw(gf, gc, *shape)
-    torch.cuda.synchronize()
-    arena.check_guards()
-    assert _same(gf, f0) and _same(gc, c0) and _same(fine, f0) and _same(coarse, c0), "an input was modified"
-    assert _same(dg, d), "%s: the guarded run differs" % cid
-    assert arena.workspaces and arena.workspaces[0][0] == plan["ws"]
-    # out= into the middle of a larger buffer (a gradient bucket slice): the same bits, the neighbours untouched
-    n, pad = d.numel(), 96
-    buf = torch.empty(n + 2 * pad, device="cuda")
-    _bits(buf).fill_(0x7FC00DAD)
-    keep = buf.clone()
-    got = ops.conv4x4s2_bf16x3_wrw(fine, coarse, *shape, out=buf[pad:pad + n].view(Kc, Cf, 4, 4))
-    torch.cuda.synchronize()
-    assert got.data_ptr() == buf.data_ptr() + 4 * pad and _same(got, d)
-    assert _same(buf[:pad], keep[:pad]) and _same(buf[pad + n:], keep[pad + n:]), "%s: out='s neighbours were written" % cid
-    # bf16-representable operands: lo = 0, the products are exact, only the fp32 accumulation is left
-    fr, cr = fine.to(BF16).float(), coarse.to(BF16).float()
-    r64 = _wrw64(fr, cr)
-    e = float((ops.conv4x4s2_bf16x3_wrw(fr, cr, *shape).double() - r64).abs().max() / r64.abs().max())
-    print("%s bf16-representable operands: %.2e of the scale" % (cid, e))
-    assert e <= 1e-5, (cid, e)
+    run = lambda f, c: ops.conv4x4s2_bf16x3_wrw(f, c, *shape)
+    check_guarded(monkeypatch, run, (fine, coarse), ("fine", "coarse"), d, plan["ws"], cid)
+    check_out_slice(lambda o: ops.conv4x4s2_bf16x3_wrw(fine, coarse, *shape, out=o), d, cid)
+    check_bf16_representable(run, _wrw64, (fine, coarse), cid, scale="the scale")
 
 
 def test_every_tap_is_inside_its_own_band():
@@ -160,7 +125,7 @@ def test_refusals_write_nothing(what):
     fine = torch.zeros(B, Cf, 2 * nh, 2 * nw, device="cuda")
     coarse = torch.zeros(B, Kc, nh, nw, device="cuda")
     dw = torch.empty(Kc, Cf, 4, 4, device="cuda")
-    _bits(dw).fill_(0x7FC00DAD)
+    _bits(dw).fill_(NAN_BITS)
     keep = dw.clone()
     ws = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
     nbytes = ws.numel()
@@ -182,30 +147,6 @@ def test_refusals_write_nothing(what):
 
 
 # ---- through the modules ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def direct_math(request):
-    from deepinpainting_amd.models import hipconv
-    was = (hipconv._MATH["fp32"], hipconv._check_hook, torch.backends.cudnn.deterministic)
-
-    def restore():
-        hipconv.set_conv_math(fp32=was[0])
-        hipconv._check_hook = was[1]
-        torch.backends.cudnn.deterministic = was[2]
-    request.addfinalizer(restore)
-    torch.backends.cudnn.deterministic = True            # MIOpen: ask for solvers that repeat their bits, so that bits can be compared
-    return hipconv
-
-
-def _module_pass(hipconv, m, x, dy):
-    seen = {}
-    hipconv._check_hook = lambda kind, eng, geom, operands, result: seen.__setitem__(kind, eng)
-    xr = x.clone().requires_grad_(True)
-    y = hipconv.conv_nobias(m, xr)
-    dx, dw = torch.autograd.grad(y, (xr, m.weight), dy)
-    torch.cuda.synchronize()
-    return seen, y.detach(), dx, dw
-
-
 COARSE = 16                                                     # the coarse grid of the module test: the smallest the rule admits
 
 

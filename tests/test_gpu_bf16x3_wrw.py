@@ -19,7 +19,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import bf16x3_wrw_plan as X
-from guarded import Arena
+from bf16x3_harness import NAN_BITS, _bits, _module_pass, _same, check_bf16_representable, check_guarded, check_out_slice, draw
+from bf16x3_harness import _in_band as _in_band_of
+from bf16x3_harness import direct_math_deterministic  # noqa: F401  (the fixture `direct_math`)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,22 +29,10 @@ IPSR_ERR_INVALID, IPSR_ERR_UNSUPPORTED, IPSR_ERR_WORKSPACE = -1, -2, -3
 F32, BF16 = torch.float32, torch.bfloat16
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
 def _operands(B, Cin, Cout, H, W, seed):
     """(x, dy): normal draws times a per-channel power of two in 2^-6 .. 2^6."""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    x = torch.randn(B, Cin, H, W, device="cuda", generator=g)
-    x = x * torch.exp2(torch.randint(-6, 7, (1, Cin, 1, 1), device="cuda", generator=g).float())
-    dy = torch.randn(B, Cout, H, W, device="cuda", generator=g)
-    dy = dy * torch.exp2(torch.randint(-6, 7, (1, Cout, 1, 1), device="cuda", generator=g).float())
-    return x, dy
+    return draw(g, (B, Cin, H, W), 1), draw(g, (B, Cout, H, W), 1)
 
 
 def _wrw64(tr, x, dy):
@@ -58,10 +48,7 @@ def _band(tr, x, dy, d64):
 
 
 def _in_band(tag, d, d64, band):
-    err = (d.double() - d64).abs()
-    worst = float((err / band).max())
-    print("%s: max |err| / band %.3f, max |err| / max|dW64| %.2e" % (tag, worst, float(err.max() / d64.abs().max())))
-    assert torch.isfinite(d).all() and worst <= 1.0, (tag, worst)
+    _in_band_of(tag, d, d64, band, ref="dW64")
 
 
 _REF = {}
@@ -90,7 +77,6 @@ def test_split_bf16_weight_gradient(cid, monkeypatch):
     assert ops.conv3x3_bf16x3_wrw_supported(tr, B, Cin, H, W, Cout)
     assert L.ipsr_conv3x3_bf16x3_wrw_workspace_bytes(tr, B, Cin, H, W, Cout) == plan["ws"], (cid, plan)
     x, dy, d64, band = _case(cid)
-    x0, dy0 = x.clone(), dy.clone()
     wshape = (Cin, Cout, 3, 3) if tr else (Cout, Cin, 3, 3)
     d = ops.conv3x3_bf16x3_wrw(tr, x, dy, Cout)
     torch.cuda.synchronize()
@@ -98,31 +84,10 @@ def test_split_bf16_weight_gradient(cid, monkeypatch):
     _in_band(cid, d, d64, band)
     # a second call: the same bits
     assert _same(ops.conv3x3_bf16x3_wrw(tr, x, dy, Cout), d), "%s: two calls differ" % cid
-    # between guard bands, on a NaN-filled workspace of exactly the size asked for
-    arena = Arena(ws_fill="nan")
-    gx, gdy = arena.guarded_copy(x, "x"), arena.guarded_copy(dy, "dy")
-    with arena.installed(monkeypatch):
-        dg = ops.conv3x3_bf16x3_wrw(tr, gx, gdy, Cout)
-    torch.cuda.synchronize()
-    arena.check_guards()
-    assert _same(gx, x0) and _same(gdy, dy0) and _same(x, x0) and _same(dy, dy0), "an input was modified"
-    assert _same(dg, d), "%s: the guarded run differs" % cid
-    assert arena.workspaces and arena.workspaces[0][0] == plan["ws"]
-    # out= into the middle of a larger buffer (a gradient bucket slice): the same bits, the neighbours untouched
-    n, pad = d.numel(), 96
-    buf = torch.empty(n + 2 * pad, device="cuda")
-    _bits(buf).fill_(0x7FC00DAD)
-    keep = buf.clone()
-    got = ops.conv3x3_bf16x3_wrw(tr, x, dy, Cout, out=buf[pad:pad + n].view(wshape))
-    torch.cuda.synchronize()
-    assert got.data_ptr() == buf.data_ptr() + 4 * pad and _same(got, d)
-    assert _same(buf[:pad], keep[:pad]) and _same(buf[pad + n:], keep[pad + n:]), "%s: out='s neighbours were written" % cid
-    # bf16-representable operands: lo = 0, the products are exact, only the fp32 accumulation is left
-    xr, dyr = x.to(BF16).float(), dy.to(BF16).float()
-    r64 = _wrw64(tr, xr, dyr)
-    e = float((ops.conv3x3_bf16x3_wrw(tr, xr, dyr, Cout).double() - r64).abs().max() / r64.abs().max())
-    print("%s bf16-representable operands: %.2e of the scale" % (cid, e))
-    assert e <= 1e-5, (cid, e)
+    run = lambda a, b: ops.conv3x3_bf16x3_wrw(tr, a, b, Cout)
+    check_guarded(monkeypatch, run, (x, dy), ("x", "dy"), d, plan["ws"], cid)
+    check_out_slice(lambda o: ops.conv3x3_bf16x3_wrw(tr, x, dy, Cout, out=o), d, cid)
+    check_bf16_representable(run, lambda a, b: _wrw64(tr, a, b), (x, dy), cid, scale="the scale")
 
 
 def test_wrong_dtype_is_refused():
@@ -142,7 +107,7 @@ def test_refusals_write_nothing(what):
     x = torch.zeros(B, Cin, H, W, device="cuda")
     dy = torch.zeros(B, Cout, H, W, device="cuda")
     dw = torch.empty(Cout, Cin, 3, 3, device="cuda")
-    _bits(dw).fill_(0x7FC00DAD)
+    _bits(dw).fill_(NAN_BITS)
     keep = dw.clone()
     ws = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
     nbytes = ws.numel()
@@ -164,30 +129,6 @@ def test_refusals_write_nothing(what):
 
 
 # ---- through the modules ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def direct_math(request):
-    from deepinpainting_amd.models import hipconv
-    was = (hipconv._MATH["fp32"], hipconv._check_hook, torch.backends.cudnn.deterministic)
-
-    def restore():
-        hipconv.set_conv_math(fp32=was[0])
-        hipconv._check_hook = was[1]
-        torch.backends.cudnn.deterministic = was[2]
-    request.addfinalizer(restore)
-    torch.backends.cudnn.deterministic = True            # MIOpen: ask for solvers that repeat their bits, so that bits can be compared
-    return hipconv
-
-
-def _module_pass(hipconv, m, x, dy):
-    seen = {}
-    hipconv._check_hook = lambda kind, eng, geom, operands, result: seen.__setitem__(kind, eng)
-    xr = x.clone().requires_grad_(True)
-    y = hipconv.conv_nobias(m, xr)
-    dx, dw = torch.autograd.grad(y, (xr, m.weight), dy)
-    torch.cuda.synchronize()
-    return seen, y.detach(), dx, dw
-
-
 @pytest.mark.parametrize("mk", [lambda: nn.Conv2d(64, 64, 3, padding=1), lambda: nn.ConvTranspose2d(128, 64, 3, padding=1)], ids=["conv64", "convT128_64"])
 def test_modules_run_all_three_passes_when_asked(mk, direct_math):
     hipconv = direct_math

@@ -422,6 +422,27 @@ for _Kc, _Cf, _nh, _nw, _B in ((48, 32, 16, 16, 3), (200, 16, 32, 32, 1), (64, 6
         return res
 
 
+# the split-bf16 kernels of the k4 s2 p1 layers on fp32 tensors.  Data passes: one channel block / ragged produced channels; the widest grid;
+# the cut reduction (partials behind the packed planes)
+for _B, _Kc, _Cf, _nh, _nw in ((2, 48, 16, 16, 16), (1, 64, 32, 4, 128), (1, 128, 128, 16, 16)):
+    @case("bf16x3_s2_%d_%d_%dx%d_b%d" % (_Kc, _Cf, _nh, _nw, _B), ["ipsr_conv4x4s2_bf16x3"])
+    def _(mk, Kc=_Kc, Cf=_Cf, nh=_nh, nw=_nw, B=_B):
+        from deepinpainting_amd import ops
+        fine, coarse = mk("fine", rn(B, Cf, 2 * nh, 2 * nw, seed=1)), mk("coarse", rn(B, Kc, nh, nw, seed=2))
+        w = mk("w", rn(Kc, Cf, 4, 4, seed=3, scale=0.05))
+        a = (B, Kc, Cf, nh, nw)
+        return {"m0": ops.conv4x4s2_bf16x3(ops.S2_FINE_TO_COARSE, fine, w, *a), "m1": ops.conv4x4s2_bf16x3(ops.S2_COARSE_TO_FINE, coarse, w, *a)}
+
+
+# weight gradient: one ragged tile, one stage; the widest grid, several runs per image; two stages per workgroup (the ring wraps)
+for _B, _Kc, _Cf, _nh, _nw in ((1, 48, 16, 4, 16), (2, 64, 128, 3, 64), (2, 340, 380, 16, 16)):
+    @case("bf16x3_s2_wrw_%d_%d_%dx%d_b%d" % (_Kc, _Cf, _nh, _nw, _B), ["ipsr_conv4x4s2_bf16x3_wrw"])
+    def _(mk, Kc=_Kc, Cf=_Cf, nh=_nh, nw=_nw, B=_B):
+        from deepinpainting_amd import ops
+        fine, coarse = mk("fine", rn(B, Cf, 2 * nh, 2 * nw, seed=1)), mk("coarse", rn(B, Kc, nh, nw, seed=2))
+        return {"dw": ops.conv4x4s2_bf16x3_wrw(fine, coarse, B, Kc, Cf, nh, nw)}
+
+
 # ---- weight-gradient sinks: the gradient written straight into a slice of a bucket between two NaN neighbours, laid out as
 # dist.py lays a bucket out (256-byte slots) and at the tightest offset the entries accept (16 bytes)
 def _sink(mk, name, shape, pad_floats):
@@ -496,6 +517,7 @@ def test_every_launching_entry_has_a_row():
     missing = [n for n in _declared() if not n.endswith("_workspace_bytes") and n not in EXEMPT and ALIASES.get(n, n) not in covered]
     assert not missing, "entries without a guarded-memory case: %s" % missing
     assert set(ALIASES.values()) <= covered and not (EXEMPT | set(ALIASES)) - set(_declared())
+    assert len({c[0] for c in CASES}) == len(CASES), "two rows share an id"
 
 
 # outputs whose tail is capacity, not result: the backward's sparse index is sized by ipsr_bwd_index_ints (an upper bound) and filled
