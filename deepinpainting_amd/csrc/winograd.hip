@@ -1753,7 +1753,7 @@ int launch_winograd_s2(int mode, const void* a, const void* b2, void* out, int B
 // a handful of activations: MIOpen spends 45-150 us on each (layout transposes, zero fills, tiles made for large maps).
 // Here the weight tensor Wm = [R][Q] (R = its first channel dimension, Q = second channel dimension x taps, contiguous: Conv2d
 // [Cout][(Cin,t)], ConvTranspose2d [Cin][(Cout,t)]) is STREAMED ONCE from where it lies, 16 bytes per lane straight into
-// MFMA operands — no LDS, no packing — and the P = B*Ho*Wo <= 512 positions ride on the 32-wide N side of 32x32x2 MFMAs:
+// MFMA operands — no LDS, no packing — and the P = B*Ho*Wo <= 1024 positions ride on the 32-wide N side of 32x32x2 MFMAs:
 //   DATA (Conv2d backward-data, ConvTranspose2d forward)   Mcol[q][p] = sum_r Wm[r][q] * in[r][p],  then col2im over the taps
 //   FWD  (Conv2d forward, ConvTranspose2d backward-data)    y[r][p]    = sum_q Wm[r][q] * col(fine)[q][p]
 //   WRW  (weight gradient of either)                        dW[r][q]   = sum_p coarse[r][p] * col(fine)[q][p]   (native layout, one pass)

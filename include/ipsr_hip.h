@@ -243,9 +243,14 @@ int ipsr_bias_act_backward(const void* dy, const void* y, int act, float slope, 
  *   op 3  ConvTranspose2d bwd-data in = dy [B,Cout,Ho,Wo]   weight [Cin,Cout,k,k]   out = dx [B,Cin,H,W]
  * (Cin, H, W) always describe the module's INPUT; Ho = (H + 2*pad - dil*(k-1) - 1)/stride + 1 for Conv2d and
  * (H-1)*stride - 2*pad + dil*(k-1) + 1 for ConvTranspose2d (output_padding 0, groups 1, square kernels k <= 4).
- * Supported tap sets: 9 or 16 taps (k = 3, 4) with any stride for the direct forms (op 0, 3) and stride 1 or 2 for the
- * transposed forms (op 1, 2); the reduction channel count must be even for k = 3.  Anything else -> IPSR_ERR_UNSUPPORTED
- * (the Python wrapper then leaves that layer on MIOpen).  fp32, summation order fixed (deterministic, no atomics). */
+ * Supported tap sets: 4, 9 or 16 taps per launch.  The direct forms (op 0, 3) and the stride-1 transposed forms (op 1, 2) gather
+ * all k*k taps: k = 2, 3, 4 with any pad and dilation, and any stride for the direct forms (1, 2 and 3 are tested).  The stride-2
+ * transposed forms run one launch per output parity, whose taps are those of matching parity: with even dilation all k*k taps of
+ * k = 2, 3, 4 fall into one class (the rest of the output is zero); with odd dilation k = 4 gives 2 x 2 taps in each of the four
+ * classes, while k = 2, 3 leave a class with 1 or 2 taps and are refused, as is k = 1 and a transposed form with stride > 2.
+ * The reduction channel count (Cin for op 0, 2; Cout for op 1, 3) must be even for 9-tap launches and a multiple of 4 for 4-tap
+ * ones; the input tensor must be smaller than 2 GiB.  Anything else -> IPSR_ERR_UNSUPPORTED before any launch, workspace query 0 (the Python wrapper then leaves
+ * that layer on MIOpen).  tests/fp32_conv_plan.py restates the plan.  fp32, summation order fixed (deterministic, no atomics). */
 size_t ipsr_conv2d_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout, int k, int stride, int pad, int dil);
 int ipsr_conv2d(int op, const float* in, const float* weight, float* out, int B, int Cin, int H, int W, int Cout,
                 int k, int stride, int pad, int dil, void* ws, size_t ws_bytes, void* stream);

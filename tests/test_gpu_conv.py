@@ -46,7 +46,9 @@ def _rel(a, b):
 
 @pytest.mark.parametrize("geom", GEOMS, ids=lambda g: "%s_c%d_%dx%d_k%d_%ds%dp%dd%d" % (g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8]))
 def test_direct_implicit_gemm_vs_fp64(geom):
-    """conv_gemm.hip: forward and backward-data of every geometry within 2e-5 of fp64 (fp32 accumulation of <= 8192 terms)."""
+    """conv_gemm.hip: forward and backward-data of every geometry within 2e-5 of fp64 (fp32 accumulation of <= 8192 terms).
+    Which stage counts, splits, tiles and tap sets a shape reaches is stated and tested in tests/fp32_conv_plan.py and
+    tests/test_gpu_fp32_conv_variants.py; these are the nets' own geometries."""
     from deepinpainting_amd import ops
     kind, Cin, H, W, Cout, k, st, pad, dil = geom
     tr = kind == "convT"
@@ -230,7 +232,8 @@ def test_k4_s2_p1_polyphase_winograd_f5x5_2x2_vs_fp64(Kc, Cf, nh, nw, B):
 def test_smallmap_engine_vs_fp64(kind, Ci, Co, H, W, k, st, pad, dil, B):
     """ipsr_conv_smallmap: the inner levels of the U-Nets / netF (models/networks.py:220-259, 404-432, 510-515) — input gradient of
     a Conv2d, forward of a ConvTranspose2d and the weight gradient of either, with the weight tensor read in place as the GEMM
-    operand: within 2e-5 of fp64 on 1x1 ... 8x8 grids, k3 / k4, stride 1 / 2, dilated."""
+    operand: within 2e-5 of fp64 on 1x1 ... 8x8 grids, k3 / k4, stride 1 / 2, dilated.  Every launch variant of `sm_plan` (position
+    groups, slabs, short waves, odd P, the 1024-position limit) is in tests/fp32_conv_plan.py and tests/test_gpu_fp32_conv_variants.py."""
     from deepinpainting_amd import ops
     g = torch.Generator().manual_seed(Ci + 3 * H + k)
     tr = kind == "convT"
