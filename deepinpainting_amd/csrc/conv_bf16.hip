@@ -60,7 +60,8 @@ constexpr int CB_LDS_MAX = 160 * 1024;
 //   C2F  k4 s2 p1, coarse -> fine     (ConvTranspose2d forward, Conv2d input gradient) lane grid = COARSE input; a workgroup produces the
 //        fine rows of ONE row parity ey' and both column parities (two accumulator sets of 2 x 2 taps each: 8 taps per stage), raw / T as
 //        S1 on the coarse image; the epilogue interleaves the two column phases into whole fine rows.
-enum { CB_S1 = 0, CB_F2C = 1, CB_C2F = 2 };
+//   DF2C / DC2F  k4 s2 p3 d2 on fp32 tensors only (conv_bf16x3_s2_kernel below): see that kernel's header.
+enum { CB_S1 = 0, CB_F2C = 1, CB_C2F = 2, CB_DF2C = 3, CB_DC2F = 4 };
 
 struct CbGeom {
     int B, C, K;                // C reduction channels (multiple of 16), K produced channels
@@ -915,14 +916,29 @@ int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C
 // per tap 4 A + 2 B fragment reads for 6 MFMAs.  LDS: A[2] = 2 x 32 KB | T <= 48.5 KB (F2C at nw = 128: 8 planes x 3 rows x 129 positions).
 // Small maps: the reduction cut of cb_finish (cb_cut_reduction), fp32 partials behind the packed planes, cb_split_reduce_kernel<float>.
 // Supported: coarse width nw in {16, 32, 64, 128}, nh a multiple of 256 / nw, reduction channels a multiple of 16.
+//
+// The DILATED forms (k4 s2 p3 d2, netG's down convolution; modes 4 / 5 of ipsr_conv4x4s2_bf16x3).  y(oy, ox) reads x(2 oy - 3 + 2 r, 2 ox - 3 + 2 s):
+// odd rows and odd columns only, so with q(m, n) = x(2 m + 1, 2 n + 1) the layer is the 16-tap stride-1 correlation y(oy, ox) = sum w(r, s)
+// q(oy + r - 2, ox + s - 2) on the coarse grid: halo 2 in front, 1 behind.  Its input gradient is dq(m, n) = sum w(r, s) dy(m + 2 - r, n + 2 - s)
+// (halo 1 / 2), dx = dq on the odd / odd positions and zero everywhere else.  Sixteen taps of A (2 x 64 KB double-buffered) do not fit
+// beside T, so a channel block is two sub-stages of 8 taps, the weight-row pairs {0, 1} and {2, 3}, each on its own R + 1 rows:
+//   DF2C fine -> coarse: sub-stage e reads the fine rows 2 (y0 + i + 2 e - 2) + 1, i = 0 .. R (the even rows are never loaded); an item is 4
+//        floats of such a row of which the split store keeps the two ODD columns: ONE plane T[hi | lo][cg][R + 1][nw + 3], q column n at n + 2;
+//        tap (ri, s) of either sub-stage = row slot + ri, position + s.
+//   DC2F coarse -> fine: sub-stage e reads the coarse rows y0 + i + 1 - 2 e; T[hi | lo][cg][R + 1][nw + 3], column n at n + 1; tap (ri, s) = row
+//        slot + 1 - ri, position + 3 - s.  One accumulator set; the epilogue writes the WHOLE fine tile: (0, v) pairs on the odd fine rows
+//        and zero rows between them.  Under a reduction cut every run writes such a whole fine partial, so the ordered add needs nothing new.
+// Both share T between the sub-stages like F2C (rows outside the image written as zeros every stage); the halo columns keep the initial zeros.
+// LDS: A[2] = 2 x 32 KB | T <= 24.6 KB (nw = 128: 4 planes x 3 rows x 131 positions); items <= 384 (DF2C at nw = 128).
 constexpr int C2_K = 64, C2_A_BYTES = 2 * 8 * 2 * C2_K * 16;
 
 template <int MODE>
 __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const float* __restrict__ in, const uint4* __restrict__ Wp, size_t lo_plane,
                                                                       CbGeom g, float* __restrict__ out)
 {
-    static_assert(MODE == CB_F2C || MODE == CB_C2F, "form");
+    static_assert(MODE == CB_F2C || MODE == CB_C2F || MODE == CB_DF2C || MODE == CB_DC2F, "form");
     constexpr int KT = C2_K, NTAP = 8, NSET = MODE == CB_C2F ? 2 : 1, TPSET = NTAP / NSET;
+    constexpr bool SUB2 = MODE != CB_C2F;                      // two sub-stages per channel block, each with its own input rows
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | T
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -933,7 +949,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
     const int pt = L / per_pt, kps = L - pt * per_pt;
     const int split = kps % g.nsplit, kp = kps / g.nsplit;
     const int kt = kp % g.ktiles, phase = kp / g.ktiles;
-    const int s_lo = split * g.sps, s_hi = min(g.nstage, s_lo + g.sps);        // (F2C: sps is even, a run starts on sub-stage 0)
+    const int s_lo = split * g.sps, s_hi = min(g.nstage, s_lo + g.sps);        // (two sub-stages: sps is even, a run starts on sub-stage 0)
     const size_t HWi = (size_t)g.Hin * g.Win, HWo = (size_t)g.Hout * g.Wout;
     out += (size_t)split * g.B * g.K * HWo;
     const int tiles_per_img = g.Hl / g.R;
@@ -952,7 +968,8 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
     const size_t xstride = (size_t)CB_C * HWi;
     const int t_base = 2 * C2_A_BYTES, t_plane = g.t_bytes / 2;
     // F2C: float i of the item is fine column 4 seg + i = 2 j + ex -> plane ex, position j + ex (plane 1 starts at j = -1)
-    const int t_wr = t_base + (cg * g.NPOS + row * g.PW + (MODE == CB_F2C ? 2 * seg : 4 * seg + 1)) * 16;
+    // DF2C: only the odd columns 4 seg + i = 2 n + 1 are kept, n = 2 seg + (i >> 1) at position n + 2
+    const int t_wr = t_base + (cg * g.NPOS + row * g.PW + (MODE == CB_F2C ? 2 * seg : MODE == CB_DF2C ? 2 * seg + 2 : 4 * seg + 1)) * 16;
     const int t_ex = 2 * g.NPOS * 16;
     // A tile DMA: 2 planes x 16 pieces of 1 KiB, piece = wave + 8 j
     constexpr int PPP = NTAP * KT / 32, NPIECE = 2 * PPP, APW = NPIECE / 8;
@@ -981,17 +998,18 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
     f32x4 xr[8];
     auto load_x = [&](int stage) {
         if (item) {
-            const int cb = MODE == CB_F2C ? stage >> 1 : stage;
-            const float* src = ((MODE == CB_F2C && (stage & 1)) ? gxb : gxa) + (size_t)cb * xstride;
+            const int cb = SUB2 ? stage >> 1 : stage;
+            const float* src = ((SUB2 && (stage & 1)) ? gxb : gxa) + (size_t)cb * xstride;
 #pragma unroll
             for (int c = 0; c < 8; ++c) xr[c] = *reinterpret_cast<const f32x4*>(src + (size_t)c * HWi);
         }
     };
     auto split_store = [&](int stage) {                        // registers -> T (hi planes, lo planes)
         if (item) {
-            const bool inside = (MODE == CB_F2C && (stage & 1)) ? in_b : in_a;
+            const bool inside = (SUB2 && (stage & 1)) ? in_b : in_a;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
+                if (MODE == CB_DF2C && !(i & 1)) continue;     // the even columns are loaded and dropped
                 unsigned hi[8], lo[8];
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
@@ -1002,7 +1020,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
                 u32x4 vh, vl;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { vh[c] = hi[2 * c] | (hi[2 * c + 1] << 16); vl[c] = lo[2 * c] | (lo[2 * c + 1] << 16); }
-                const int at = t_wr + (MODE == CB_F2C ? (i & 1) * t_ex + ((i >> 1) + (i & 1)) * 16 : i * 16);
+                const int at = t_wr + (MODE == CB_F2C ? (i & 1) * t_ex + ((i >> 1) + (i & 1)) * 16 : MODE == CB_DF2C ? (i >> 1) * 16 : i * 16);
                 *reinterpret_cast<u32x4*>(lds + at) = vh;
                 *reinterpret_cast<u32x4*>(lds + at + t_plane) = vl;
             }
@@ -1026,7 +1044,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
         }
         const unsigned char* A = lds + cur * C2_A_BYTES + a_off;
         const unsigned char* T = lds + b_off;
-        const int* toff = g.tapoff[MODE == CB_F2C ? (s & 1) : phase];
+        const int* toff = g.tapoff[SUB2 ? (s & 1) : phase];
         // the tap pipeline of conv_bf16x3_kernel: the six fragments of tap t + 1 are read behind tap t's first multiplication
         bf16x8 fa[2][2][2], fb[2][2];                          // [set][plane][row tile], [set][plane]
         auto load_tap = [&](int t, int set) {
@@ -1076,6 +1094,19 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
                 const int k = kt * KT + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (k < g.K) *reinterpret_cast<float2*>(op + (size_t)k * HWo) = make_float2(acc[0][i][e], acc[NSET - 1][i][e]);
             }
+    } else if (MODE == CB_DC2F) {
+        // fine rows 2 py and 2 py + 1, fine columns 2 px and 2 px + 1: only (odd, odd) carries a value, the other three are zeros of the result
+        float* op = out + (size_t)b * g.K * HWo + (size_t)(2 * py) * g.Wout + 2 * px;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int k = kt * KT + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (k < g.K) {
+                    *reinterpret_cast<float2*>(op + (size_t)k * HWo) = make_float2(0.0f, 0.0f);
+                    *reinterpret_cast<float2*>(op + (size_t)k * HWo + g.Wout) = make_float2(0.0f, acc[0][i][e]);
+                }
+            }
     } else {
         float* op = out + (size_t)b * g.K * HWo + (size_t)py * g.Wout + px;
 #pragma unroll
@@ -1088,7 +1119,36 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
     }
 }
 
-// form 0: fine -> coarse (C = Cf reduced, K = Kc produced); 1: coarse -> fine.  The limits, before any launch.
+// the two dilated forms (k4 s2 p3 d2) on a lane grid already set: form 4 fine -> coarse, 5 coarse -> fine (conv_bf16x3_s2_kernel's header)
+static void c2_dil_form(int form, int nh, int nw, CbGeom* g)
+{
+    const bool f2c = form == 4;
+    g->Hin = f2c ? 2 * nh : nh; g->Win = f2c ? 2 * nw : nw;
+    g->Hout = f2c ? nh : 2 * nh; g->Wout = f2c ? nw : 2 * nw;
+    g->NR = g->R + 1; g->PW = nw + 3;
+    g->ymul = f2c ? 2 : 1; g->rowstep = g->ymul;
+    g->yoff[0] = f2c ? -3 : 1; g->yoff[1] = f2c ? 1 : -1;      // sub-stage e = weight rows {2 e, 2 e + 1}
+    g->nsub = 2; g->nphase = 1; g->ntap = 8;
+    g->NPOS = g->NR * g->PW;
+    for (int e = 0; e < 2; ++e)
+        for (int t = 0; t < 8; ++t) {
+            const int ri = t >> 2, sx = t & 3;
+            g->tapoff[e][t] = f2c ? ri * g->PW + sx : (1 - ri) * g->PW + (3 - sx);
+        }
+}
+
+// source taps of the dilated forms' packed images: sub-stage e, tap t = ri * 4 + s -> weight row 2 e + ri, column s (both forms)
+static CbPack c2_dil_pack()
+{
+    CbPack pk{};
+    pk.ntap = 8; pk.nsub = 2; pk.nphase = 1;
+    for (int e = 0; e < 2; ++e)
+        for (int t = 0; t < 8; ++t) pk.srctap[0][e][t] = (2 * e + (t >> 2)) * 4 + (t & 3);
+    return pk;
+}
+
+// form 0: fine -> coarse (C = Cf reduced, K = Kc produced); 1: coarse -> fine; 4 / 5: the same directions of the dilated layer.
+// The limits, before any launch.
 static int c2_geometry(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
 {
     const char* who = "split-bf16 direct 4x4 stride-2 conv";
@@ -1096,14 +1156,16 @@ static int c2_geometry(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
     if (nw != 16 && nw != 32 && nw != 64 && nw != 128) return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width %d (16 .. 128, a power of two)", who, nw);
     if (int rc = cb_lane_grid(nh, nw, CB_P, g, who)) return rc;
     g->B = B; g->C = C; g->K = K;
-    cb_s2_form(form, nh, nw, g);
+    if (form & 4) c2_dil_form(form, nh, nw, g);
+    else cb_s2_form(form, nh, nw, g);
+    const int planes = form == 0 ? 2 : 1;                      // column-phase planes of T (F2C only)
     g->kt = C2_K;
     g->ktiles = (K + C2_K - 1) / C2_K;
     g->ptiles = B * (g->Hl / g->R);
     g->nstage = (C / CB_C) * g->nsub;
     cb_cut_reduction(g);
     g->a_bytes = C2_A_BYTES;
-    g->t_bytes = (int)align_up((size_t)2 * g->nsub * 2 * g->NPOS * 16, 256);     // hi | lo, each [column phase][c group][positions]
+    g->t_bytes = (int)align_up((size_t)2 * planes * 2 * g->NPOS * 16, 256);      // hi | lo, each [column phase][c group][positions]
     g->raw_bytes = 0; g->raw1 = 0;
     if (2 * C2_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (g->Win / 4) > CB_THREADS)
         return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, g->Win);
@@ -1131,27 +1193,30 @@ static int c2_launch_kernel(const CbGeom& g, const float* in, const uint4* Wp, s
     return IPSR_OK;
 }
 
-// weight and forms as in launch_conv_bf16_s2; in / out fp32
+// weight and forms 0 / 1 as in launch_conv_bf16_s2, forms 4 / 5 the dilated layer (pad 3, dilation 2) in the same directions; in / out fp32
 int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out, int B, int Kc, int Cf, int nh, int nw, long skc, long scf,
                           void* ws, size_t ws_bytes, hipStream_t st)
 {
     CbGeom g;
-    const int C = form == 0 ? Cf : Kc, K = form == 0 ? Kc : Cf;
+    const bool f2c = !(form & 1);
+    const int C = f2c ? Cf : Kc, K = f2c ? Kc : Cf;
     if (int rc = c2_geometry(form, B, C, K, nh, nw, &g)) return rc;
     const size_t need = conv_bf16x3_s2_ws_bytes(form, B, C, K, nh, nw);
     if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 direct 4x4 stride-2 conv: workspace %zu < %zu", ws_bytes, need);
     uint4* zero_page = static_cast<uint4*>(ws);
     uint4* Wp = zero_page + 16;
     const size_t lo_plane = c2_pack_bytes(g) / 16;
-    CbPack pk = cb_s2_pack(form);
+    CbPack pk = (form & 4) ? c2_dil_pack() : cb_s2_pack(form);
     pk.kt = C2_K;
     cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * C2_K, 256), C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(
-        w, C, K, form == 0 ? scf : skc, form == 0 ? skc : scf, pk, Wp, zero_page, lo_plane);
+        w, C, K, f2c ? scf : skc, f2c ? skc : scf, pk, Wp, zero_page, lo_plane);
     if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
     float* dst = g.nsplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wp) + align_up(2 * c2_pack_bytes(g), 256)) : out;
-    const double outs = (double)B * g.Hout * g.Wout, taps = form == 0 ? 16.0 : 4.0;
+    // the dilated forms: 16 taps per coarse pixel whichever tensor is written
+    const double outs = (form & 4) ? (double)B * g.Hl * g.Wl : (double)B * g.Hout * g.Wout, taps = form == 1 ? 4.0 : 16.0;
     profile_mark_start(st, 4);
-    if (int rc = form == 0 ? c2_launch_kernel<CB_F2C>(g, in, Wp, lo_plane, dst, st) : c2_launch_kernel<CB_C2F>(g, in, Wp, lo_plane, dst, st)) return rc;
+    if (int rc = form == 0 ? c2_launch_kernel<CB_F2C>(g, in, Wp, lo_plane, dst, st) : form == 1 ? c2_launch_kernel<CB_C2F>(g, in, Wp, lo_plane, dst, st)
+               : form == 4 ? c2_launch_kernel<CB_DF2C>(g, in, Wp, lo_plane, dst, st) : c2_launch_kernel<CB_DC2F>(g, in, Wp, lo_plane, dst, st)) return rc;
     if (g.nsplit > 1) {
         if (int rc = check_launch("conv_bf16x3_s2_kernel")) return rc;
         const size_t n = (size_t)B * K * g.Hout * g.Wout;      // a multiple of 4: Wout is
@@ -2100,6 +2165,9 @@ static int cb_misaligned(const char* who, const char* what, std::initializer_lis
     return IPSR_OK;
 }
 
+// modes of ipsr_conv4x4s2_bf16x3: bit 0 = coarse -> fine, bit 2 = pad 3, dilation 2
+static bool c2_mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 4 || mode == 5; }
+
 extern "C" {
 
 size_t ipsr_conv3x3_bf16_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout)
@@ -2159,16 +2227,16 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
 
 size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
-    if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_workspace_bytes", mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return 0;
-    return conv_bf16x3_s2_ws_bytes(mode, B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
+    if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_workspace_bytes", c2_mode_ok(mode), {B, Kc, Cf, nh, nw})) return 0;
+    return conv_bf16x3_s2_ws_bytes(mode, B, (mode & 1) ? Kc : Cf, (mode & 1) ? Cf : Kc, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
                           void* ws, size_t ws_bytes, void* stream)
 {
     if (int rc = cb_null("ipsr_conv4x4s2_bf16x3", {in, weight, out, ws})) return rc;
-    if (!cb_dims_ok(mode == 0 || mode == 1, {B, Kc, Cf, nh, nw}))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: bad argument (mode %d: 0 fine -> coarse, 1 coarse -> fine)", mode);
+    if (!cb_dims_ok(c2_mode_ok(mode), {B, Kc, Cf, nh, nw}))
+        return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: bad argument (mode %d: 0 fine -> coarse, 1 coarse -> fine; 4, 5 the same with pad 3, dilation 2)", mode);
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3", "in / out / workspace", {ws, in, out})) return rc;
     return launch_conv_bf16x3_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }

@@ -59,6 +59,8 @@ class IPSR(BaseModel):
         # Under amp_bf16 the engines read / write bf16 activations and multiply split-bf16 operands (`conv_math_bf16`, default "bf16x3").
         from . import hipconv
         hipconv.set_conv_math(fp32=getattr(opt, 'conv_math', 'fp32'), bf16=getattr(opt, 'conv_math_bf16', 'bf16x3'))
+        # opt-in: netG's dilated down convolutions (forward / input gradient, fp32 activations) on the direct split-bf16 kernel
+        hipconv.set_direct_dilated(bool(getattr(opt, 'direct_dilated', False)))
         # conv-bias + InstanceNorm + activation in one HIP kernel each way (models/fused.py); False = plain torch modules
         networks.FusedSequential.enabled = bool(getattr(opt, 'fused_norm_act', True))
 

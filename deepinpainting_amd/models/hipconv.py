@@ -29,6 +29,8 @@ pass and what the engine needs; a new engine is one record there plus its rule i
   "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32=...)`, the four direct names of ops.DIRECT_PASSES): forward / input gradient on split-bf16 operands
+                                  — and, by a switch of its own (`set_direct_dilated`), forward / input gradient of netG's dilated down convolution
+                                  Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input, instead of "wino_dil"
   "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (the same names): the weight gradient as a pixel reduction on split-bf16 operands, two launches
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
@@ -65,6 +67,24 @@ def set_conv_math(fp32=None, bf16=None):
                 raise ValueError("conv math must be one of %s" % sorted(k for k in _ops.MATH_CODE if k))
             _MATH[key] = val
     _SEL.clear()           # `select` memoises without the arithmetic
+
+
+_DIRECT_DILATED = False    # opt-in: the dilated 4x4 stride-2 data passes of "wino_dil" on the direct split-bf16 kernel (`set_direct_dilated`)
+
+
+def set_direct_dilated(on):
+    """Opt-in, default off, independent of `set_conv_math`: under fp32 activations, forward and input gradient of the dilated down
+    convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" has go to the direct split-bf16 kernel ("bf16x3d",
+    ops.conv4x4s2_bf16x3 with ops.S2_DILATED) on every shape it takes.  Weight gradients, bf16 activations, forced engines and the
+    k4 s1 p1 layer stay where they are."""
+    global _DIRECT_DILATED
+    _DIRECT_DILATED = bool(on)
+    _SEL.clear()
+
+
+def direct_dilated():
+    """Whether `set_direct_dilated` is on."""
+    return _DIRECT_DILATED
 
 
 def _amp_bf16():
@@ -115,6 +135,10 @@ def _select_any(op, lay, bf16):
         if eng == "winograd" and ops.direct_moves(_MATH["fp32"], "k3_data") and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
             return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
         if ops.direct_moves(_MATH["fp32"], "s2_data") and _bf16x3_s2_wins(eng, op, lay):
+            return "bf16x3d"
+        if _DIRECT_DILATED and _bf16x3_dil_takes(eng, op, lay):
+            # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_dil_layers.txt, batch 8, vs "wino_dil", forward / input
+            # gradient): 64 @256 wins 2.16x / 2.61x, 128 @128 wins 1.55x / 1.72x, 512 @32 wins 1.47x / 1.30x, 256 @64 LOSES 0.82x / 0.93x
             return "bf16x3d"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
@@ -370,6 +394,29 @@ def _bf16x3_s2_wins(eng, op, lay):
     return ops.conv4x4s2_bf16x3_supported(_s2_mode(op), lay[1], *g)
 
 
+def _dil_geometry(lay):
+    """(Kc, Cf, nh, nw) of a Conv2d(k4 s2 p3 d2) layer on an even map in the coarse / fine terms of ipsr_conv4x4s2_bf16x3, or None."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    if transposed or not _is_dilated4(k, stride, pad, dil) or H % 2 or W % 2:
+        return None
+    return Cout, Cin, H // 2, W // 2
+
+
+def _dil_mode(op):
+    return ops.S2_DILATED | (ops.S2_FINE_TO_COARSE if op == ops.CONV_FWD else ops.S2_COARSE_TO_FINE)
+
+
+def _bf16x3_dil_takes(eng, op, lay):
+    """fp32 activations under `set_direct_dilated(True)`: the forward / input-gradient passes of the dilated down convolution that "wino_dil"
+    has go to the direct split-bf16 kernel wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.
+    Measured at batch 8 on the step's four shapes (profiles/direct_bf16x3_dil_layers.txt): 1.30-2.61x "wino_dil" on 64 @256, 128 @128 and
+    512 @32, 0.82x / 0.93x (a loss) on 256 @64; the switch moves all four, the step gains 1.5 %.  A forced engine is never overridden; netD's k4 s1 p1 and the weight gradient stay on "wino_dil"."""
+    if eng != "wino_dil" or _mode() != "auto" or op not in (ops.CONV_FWD, ops.CONV_BWD_DATA):
+        return False
+    g = _dil_geometry(lay)
+    return g is not None and ops.conv4x4s2_bf16x3_supported(_dil_mode(op), lay[1], *g)
+
+
 def _bf16x3_wrw_wins(eng, lay):
     """fp32 activations under the opt-in "direct_bf16x3_dw" / "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
     split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured at batch 8
@@ -463,9 +510,11 @@ def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
 
 
 def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
-    """fp32 activations on the direct split-bf16 kernels: the same two shapes."""
+    """fp32 activations on the direct split-bf16 kernels: the same two shapes, and the dilated down convolution."""
     if lay[6] == 3:
         return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], **_frozen_pack(w, param))
+    if _is_dilated4(*lay[6:]):
+        return ops.conv4x4s2_bf16x3(_dil_mode(op), inp, w, lay[1], *_dil_geometry(lay))
     return ops.conv4x4s2_bf16x3(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay))
 
 

@@ -657,10 +657,10 @@ def _conv4x4s2_direct(arith, mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype):
     who = "conv4x4s2_" + arith
     inp, = _direct_operands(arith, who, inp, "conv input")
     weight = _req(weight, torch.float32, "conv weight")
-    if mode not in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE):
+    if mode not in (_S2_X3_MODES if arith == "bf16x3" else _S2_MODES):
         raise ValueError("%s: mode %r" % (who, mode))
     fine, coarse = (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)
-    want_in, oshape = (fine, coarse) if mode == S2_FINE_TO_COARSE else (coarse, fine)
+    want_in, oshape = (fine, coarse) if mode & ~S2_DILATED == S2_FINE_TO_COARSE else (coarse, fine)
     if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
         raise RuntimeError("%s mode %d: input %s / weight %s do not match %s / %s" % (who, mode, tuple(inp.shape), tuple(weight.shape), want_in, (Kc, Cf, 4, 4)))
     L = _lib.lib()
@@ -739,13 +739,15 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
 
 
 def conv4x4s2_bf16x3_supported(mode, B, Kc, Cf, nh, nw):
-    return mode in (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE) and _lib.lib().ipsr_conv4x4s2_bf16x3_workspace_bytes(mode, B, Kc, Cf, nh, nw) > 0
+    return mode in _S2_X3_MODES and _lib.lib().ipsr_conv4x4s2_bf16x3_workspace_bytes(mode, B, Kc, Cf, nh, nw) > 0
 
 
 def conv4x4s2_bf16x3(mode, inp, weight, B, Kc, Cf, nh, nw):
     """The k4 s2 p1 layers on FP32 tensors as ONE direct implicit GEMM on the bf16 matrix cores with split operands (ipsr_conv4x4s2_bf16x3,
     csrc/conv_bf16.hip): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32 accumulation; fp32 in, fp32 out.  mode, shapes
-    and weight as in conv4x4s2_bf16."""
+    and weight as in conv4x4s2_bf16.  With S2_DILATED or-ed into the mode the layer is Conv2d(k4, stride 2, pad 3, dilation 2) in the same
+    terms: S2_DILATED | S2_FINE_TO_COARSE its forward, S2_DILATED | S2_COARSE_TO_FINE its input gradient (every element of the fine result
+    is written: the odd / odd quarter carries values, the rest is zero)."""
     return _conv4x4s2_direct("bf16x3", mode, inp, weight, B, Kc, Cf, nh, nw, torch.float32)
 
 
@@ -836,6 +838,9 @@ def conv4x4_dilated_winograd(mode, a, b, in_shape, Cout, out=None, geom=GEOM_K4_
 
 
 S2_FINE_TO_COARSE, S2_COARSE_TO_FINE, S2_WEIGHT_GRAD = 0, 1, 2
+S2_DILATED = 4          # or-ed into a data mode of conv4x4s2_bf16x3: pad 3, dilation 2 instead of pad 1
+_S2_MODES = (S2_FINE_TO_COARSE, S2_COARSE_TO_FINE)
+_S2_X3_MODES = _S2_MODES + (S2_DILATED | S2_FINE_TO_COARSE, S2_DILATED | S2_COARSE_TO_FINE)
 
 
 def s2_winograd_supported(mode, B, Kc, Cf, nh, nw):

@@ -488,7 +488,13 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
  * output <= 2^-16 of sum |x||w| plus the fp32 accumulation's.  mode and weight as above (an entry of its own: ipsr_conv4x4s2_bf16 takes any
  * non-zero out_bf16 as "bf16 out").  Supported: nw in {16, 32, 64, 128} in both modes, nh a multiple of 256 / nw, reduction channels (mode 0:
  * Cf, mode 1: Kc) a multiple of 16; anything else -> IPSR_ERR_UNSUPPORTED, checked before any launch.  The workspace query returns 0 where
- * the shape is unsupported, reason in ipsr_last_error(); `in`, `out`, `ws` must be 16-byte aligned; any other mode is IPSR_ERR_INVALID. */
+ * the shape is unsupported, reason in ipsr_last_error(); `in`, `out`, `ws` must be 16-byte aligned; any other mode is IPSR_ERR_INVALID.
+ * Modes 4 and 5 (bit 2 = "pad 3, dilation 2") are the same two directions of netG's DILATED down convolution Conv2d(C, C, k4, stride 2, pad 3,
+ * dilation 2) (models/networks.py:198) in the same terms: mode 4 fine -> coarse is its forward (reads the odd rows and odd columns of the
+ * fine tensor only: a 16-tap stride-1 correlation on that quarter), mode 5 coarse -> fine its input gradient (writes EVERY element of the
+ * fine tensor: values at the odd / odd positions, zeros elsewhere).  Same supported set, same refusals, same workspace layout (a cut
+ * reduction's partials are fine-sized in mode 5); ipsr_conv4x4s2_bf16 (bf16 tensors) has no such modes.  Added without an ABI version
+ * change (15): no signature changed, and the modes were IPSR_ERR_INVALID before. */
 size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
                           void* ws, size_t ws_bytes, void* stream);
