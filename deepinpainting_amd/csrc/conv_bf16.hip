@@ -417,15 +417,15 @@ static int cb_lane_grid(int Hl, int Wl, int ptile, CbGeom* g, const char* who)
     return IPSR_OK;
 }
 
-// (ktiles, nphase, ptiles, nsub set) -> nsplit, sps
-static void cb_cut_reduction(CbGeom* g)
+// The reduction cut of the three data-pass planners: fewer than 128 workgroups and >= 8 channel blocks -> up to four runs of whole channel
+// blocks (`nsub` stages each).  wgs = workgroups without a cut -> the number of runs and the stages of a run.
+static void cb_cut_reduction(int wgs, int nblocks, int nsub, int* nsplit, int* sps)
 {
-    const int wgs = g->ktiles * g->nphase * g->ptiles, nblocks = g->C / CB_C;
     int ns = 1;
     if (wgs < 128 && nblocks >= 8) ns = min(min(4, nblocks / 4), (256 + wgs - 1) / wgs);
-    const int bps = (nblocks + ns - 1) / max(ns, 1);      // channel blocks per run
-    g->nsplit = (nblocks + bps - 1) / bps;
-    g->sps = bps * g->nsub;
+    const int bps = (nblocks + ns - 1) / ns;              // channel blocks per run
+    *nsplit = (nblocks + bps - 1) / bps;
+    *sps = bps * nsub;
 }
 
 static int cb_finish(CbGeom* g, const char* who)
@@ -437,7 +437,7 @@ static int cb_finish(CbGeom* g, const char* who)
     g->nstage = (g->C / CB_C) * g->nsub;
     // Small maps leave the chip idle (a 16x16 map is ONE pixel tile per image: 64 workgroups at 512 produced channels and batch 16): the
     // reduction is cut into up to four runs of whole channel blocks, each run a workgroup of its own writing an fp32 partial.
-    cb_cut_reduction(g);
+    cb_cut_reduction(g->ktiles * g->nphase * g->ptiles, g->C / CB_C, g->nsub, &g->nsplit, &g->sps);
     const int planes = g->nsub;                               // F2C keeps the two column phases
     g->a_bytes = g->ntap * 2 * g->kt * 16;
     g->t_bytes = (int)align_up((size_t)planes * 2 * g->NPOS * 16, 256);
@@ -535,6 +535,34 @@ __global__ void __launch_bounds__(256) cb_split_reduce_kernel(const float* __res
     st4(out, i, a);
 }
 
+// Every kernel of this file may ask for up to CB_LDS_MAX of dynamic LDS.  The attribute belongs to the device the launch goes to: set per
+// launch, not once per process.
+static int cb_raise_lds(const void* kernel, const char* name)
+{
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
+    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "%s: hipFuncSetAttribute(dynamic LDS %d): %s", name, CB_LDS_MAX, hipGetErrorString(e));
+    return IPSR_OK;
+}
+
+// Where a data-pass kernel writes: `out`, or under a reduction cut the runs' fp32 partials behind the `pack_bytes` of packed weights at Wp
+static void* cb_run_dst(int nsplit, uint4* Wp, size_t pack_bytes, void* out)
+{
+    return nsplit > 1 ? reinterpret_cast<unsigned char*>(Wp) + align_up(pack_bytes, 256) : out;
+}
+
+// The tail of the three data launchers, behind the launch of `kernel` into cb_run_dst(): under a cut the ordered add of the partials `dst`
+// into the n elements of `out` (a multiple of 4: the output width is), the profile stop, the launch check.
+static int cb_launch_tail(const char* kernel, int nsplit, const void* dst, size_t n, void* out, int out_bf16, hipStream_t st, double work, double work2)
+{
+    if (nsplit > 1) {
+        if (int rc = check_launch(kernel)) return rc;
+        if (out_bf16) cb_split_reduce_kernel<bf16_t><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(static_cast<const float*>(dst), nsplit, n / 4, static_cast<bf16_t*>(out));
+        else cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(static_cast<const float*>(dst), nsplit, n / 4, static_cast<float*>(out));
+    }
+    profile_mark_stop(st, 4, work, work2);
+    return check_launch(nsplit > 1 ? "cb_split_reduce_kernel" : kernel);
+}
+
 size_t conv_bf16_ws_bytes(int B, int C, int K, int H, int W)
 {
     CbGeom g;
@@ -550,11 +578,20 @@ size_t conv_bf16_s2_ws_bytes(int form, int B, int C, int K, int nh, int nw)
 }
 
 template <int MODE, int KT, int P, typename TOUT>
-static void cb_launch_kernel(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
+static int cb_launch_kernel(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
 {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
+    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), "conv_bf16_kernel")) return rc;
     conv_bf16_kernel<MODE, KT, P, TOUT><<<grid, CB_THREADS, smem, st>>>(static_cast<const unsigned short*>(in), Wp, zero_page, g, static_cast<TOUT*>(out));
+    return IPSR_OK;
+}
+
+// the kernel instance of a plan: tile (g.kt x g.ptile) and output type
+template <int MODE, typename TOUT>
+static int cb_launch_tile(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
+{
+    if (g.kt == 64 && g.ptile == 2 * CB_P) return cb_launch_kernel<MODE, 64, 2 * CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
+    if (g.kt == 64) return cb_launch_kernel<MODE, 64, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
+    return cb_launch_kernel<MODE, 128, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
 }
 
 template <int MODE>
@@ -570,33 +607,13 @@ static int cb_launch(const CbGeom& g, CbPack pk, const void* in, const float* w,
     }
     const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
     const size_t smem = 2 * (size_t)(g.a_bytes + g.t_bytes) + (size_t)(g.raw1 ? 1 : 2) * g.raw_bytes;
-    void* final_out = out;
-    const int final_bf16 = out_bf16;
-    if (g.nsplit > 1) {                                       // the runs write fp32 partials behind the packed weights
-        const size_t pack_bytes = (size_t)g.ktiles * g.nphase * g.nstage * pk.ntap * 2 * g.kt * 16;
-        out = reinterpret_cast<unsigned char*>(Wp) + align_up(pack_bytes, 256);
-        out_bf16 = 0;
-    }
+    void* dst = cb_run_dst(g.nsplit, Wp, (size_t)g.ktiles * g.nphase * g.nstage * pk.ntap * 2 * g.kt * 16, out);
     profile_mark_start(st, 4);
-    if (g.kt == 64 && g.ptile == 2 * CB_P) {
-        if (out_bf16) cb_launch_kernel<MODE, 64, 2 * CB_P, bf16_t>(g, in, Wp, zero_page, out, grid, smem, st);
-        else cb_launch_kernel<MODE, 64, 2 * CB_P, float>(g, in, Wp, zero_page, out, grid, smem, st);
-    } else if (g.kt == 64) {
-        if (out_bf16) cb_launch_kernel<MODE, 64, CB_P, bf16_t>(g, in, Wp, zero_page, out, grid, smem, st);
-        else cb_launch_kernel<MODE, 64, CB_P, float>(g, in, Wp, zero_page, out, grid, smem, st);
-    } else {
-        if (out_bf16) cb_launch_kernel<MODE, 128, CB_P, bf16_t>(g, in, Wp, zero_page, out, grid, smem, st);
-        else cb_launch_kernel<MODE, 128, CB_P, float>(g, in, Wp, zero_page, out, grid, smem, st);
-    }
+    if (int rc = (out_bf16 && g.nsplit == 1) ? cb_launch_tile<MODE, bf16_t>(g, in, Wp, zero_page, dst, grid, smem, st)
+                                             : cb_launch_tile<MODE, float>(g, in, Wp, zero_page, dst, grid, smem, st)) return rc;
     const double outs = (double)g.B * g.Hout * g.Wout;
-    if (g.nsplit > 1) {
-        if (int rc = check_launch("conv_bf16_kernel")) return rc;
-        const size_t n = (size_t)g.B * g.K * g.Hout * g.Wout;          // a multiple of 4: Wout is
-        if (final_bf16) cb_split_reduce_kernel<bf16_t><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(static_cast<const float*>(out), g.nsplit, n / 4, static_cast<bf16_t*>(final_out));
-        else cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(static_cast<const float*>(out), g.nsplit, n / 4, static_cast<float*>(final_out));
-    }
-    profile_mark_stop(st, 4, 2.0 * taps_per_out * g.C * (double)(g.ktiles * g.kt) * outs, 2.0 * taps_per_out * g.C * (double)g.K * outs);
-    return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16_kernel");
+    return cb_launch_tail("conv_bf16_kernel", g.nsplit, dst, (size_t)g.B * g.K * g.Hout * g.Wout, out, out_bf16, st,
+                          2.0 * taps_per_out * g.C * (double)(g.ktiles * g.kt) * outs, 2.0 * taps_per_out * g.C * (double)g.K * outs);
 }
 
 // in [B,C,H,W] bf16, weight fp32 with element (c, k, tap) at w[c*sc + k*sk + tap] (taps flipped when `flip`), out [B,K,H,W] bf16 / fp32
@@ -843,12 +860,7 @@ static int cx_geometry(int B, int C, int K, int H, int W, CxGeom* g)
     g->ktiles = (K + CX_K - 1) / CX_K;
     g->ptiles = B * (H / g->R);
     g->nstage = C / CB_C;
-    // the bf16 kernel's rule for small maps: fewer than 128 workgroups and >= 8 channel blocks -> up to four runs of whole channel blocks
-    const int wgs = g->ktiles * g->ptiles;
-    int ns = 1;
-    if (wgs < 128 && g->nstage >= 8) ns = min(min(4, g->nstage / 4), (256 + wgs - 1) / wgs);
-    g->sps = (g->nstage + ns - 1) / ns;
-    g->nsplit = (g->nstage + g->sps - 1) / g->sps;
+    cb_cut_reduction(g->ktiles * g->ptiles, g->nstage, 1, &g->nsplit, &g->sps);
     g->t_bytes = (int)align_up((size_t)2 * 2 * g->NPOS * 16, 256);
     if (2 * CX_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (W / 4) > CB_THREADS)
         return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, W);
@@ -883,20 +895,14 @@ int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C
         cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * CX_K, 256), C / 8, 9), 256, 0, st>>>(w, C, K, sc, sk, pk, Wp, zero_page, lo_plane);
         if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
     }
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
-    float* dst = g.nsplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wp) + align_up(2 * cx_pack_bytes(g), 256)) : out;
+    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel), "conv_bf16x3_kernel")) return rc;
+    float* dst = static_cast<float*>(cb_run_dst(g.nsplit, Wp, 2 * cx_pack_bytes(g), out));
     const unsigned grid = (unsigned)(g.ktiles * g.ptiles * g.nsplit);
     const double outs = (double)B * H * W;
     profile_mark_start(st, 4);
     conv_bf16x3_kernel<<<grid, CB_THREADS, 2 * CX_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, dst);
-    if (g.nsplit > 1) {
-        if (int rc = check_launch("conv_bf16x3_kernel")) return rc;
-        const size_t n = (size_t)B * K * H * W;                // a multiple of 4: W is
-        cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(dst, g.nsplit, n / 4, out);
-    }
-    profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * C * (double)(g.ktiles * CX_K) * outs, 2.0 * 9.0 * C * (double)K * outs);
-    return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16x3_kernel");
+    return cb_launch_tail("conv_bf16x3_kernel", g.nsplit, dst, (size_t)B * K * H * W, out, 0, st,
+                          3.0 * 2.0 * 9.0 * C * (double)(g.ktiles * CX_K) * outs, 2.0 * 9.0 * C * (double)K * outs);
 }
 
 // =====================================================================================================================================
@@ -1163,7 +1169,7 @@ static int c2_geometry(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
     g->ktiles = (K + C2_K - 1) / C2_K;
     g->ptiles = B * (g->Hl / g->R);
     g->nstage = (C / CB_C) * g->nsub;
-    cb_cut_reduction(g);
+    cb_cut_reduction(g->ktiles * g->nphase * g->ptiles, C / CB_C, g->nsub, &g->nsplit, &g->sps);
     g->a_bytes = C2_A_BYTES;
     g->t_bytes = (int)align_up((size_t)2 * planes * 2 * g->NPOS * 16, 256);      // hi | lo, each [column phase][c group][positions]
     g->raw_bytes = 0; g->raw1 = 0;
@@ -1185,9 +1191,7 @@ size_t conv_bf16x3_s2_ws_bytes(int form, int B, int C, int K, int nh, int nw)
 template <int MODE>
 static int c2_launch_kernel(const CbGeom& g, const float* in, const uint4* Wp, size_t lo_plane, float* out, hipStream_t st)
 {
-    // the attribute belongs to the device the launch goes to: set per launch, not once per process
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
-    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "conv_bf16x3_s2_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", CB_LDS_MAX, hipGetErrorString(e));
+    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<MODE>), "conv_bf16x3_s2_kernel")) return rc;
     const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
     conv_bf16x3_s2_kernel<MODE><<<grid, CB_THREADS, 2 * C2_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, out);
     return IPSR_OK;
@@ -1211,19 +1215,14 @@ int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out,
     cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * C2_K, 256), C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(
         w, C, K, f2c ? scf : skc, f2c ? skc : scf, pk, Wp, zero_page, lo_plane);
     if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
-    float* dst = g.nsplit > 1 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wp) + align_up(2 * c2_pack_bytes(g), 256)) : out;
+    float* dst = static_cast<float*>(cb_run_dst(g.nsplit, Wp, 2 * c2_pack_bytes(g), out));
     // the dilated forms: 16 taps per coarse pixel whichever tensor is written
     const double outs = (form & 4) ? (double)B * g.Hl * g.Wl : (double)B * g.Hout * g.Wout, taps = form == 1 ? 4.0 : 16.0;
     profile_mark_start(st, 4);
     if (int rc = form == 0 ? c2_launch_kernel<CB_F2C>(g, in, Wp, lo_plane, dst, st) : form == 1 ? c2_launch_kernel<CB_C2F>(g, in, Wp, lo_plane, dst, st)
                : form == 4 ? c2_launch_kernel<CB_DF2C>(g, in, Wp, lo_plane, dst, st) : c2_launch_kernel<CB_DC2F>(g, in, Wp, lo_plane, dst, st)) return rc;
-    if (g.nsplit > 1) {
-        if (int rc = check_launch("conv_bf16x3_s2_kernel")) return rc;
-        const size_t n = (size_t)B * K * g.Hout * g.Wout;      // a multiple of 4: Wout is
-        cb_split_reduce_kernel<float><<<(unsigned)cdiv(n / 4, 256), 256, 0, st>>>(dst, g.nsplit, n / 4, out);
-    }
-    profile_mark_stop(st, 4, 3.0 * 2.0 * taps * C * (double)(g.ktiles * C2_K) * outs, 2.0 * taps * C * (double)K * outs);
-    return check_launch(g.nsplit > 1 ? "cb_split_reduce_kernel" : "conv_bf16x3_s2_kernel");
+    return cb_launch_tail("conv_bf16x3_s2_kernel", g.nsplit, dst, (size_t)B * K * g.Hout * g.Wout, out, 0, st,
+                          3.0 * 2.0 * taps * C * (double)(g.ktiles * C2_K) * outs, 2.0 * taps * C * (double)K * outs);
 }
 
 // =====================================================================================================================================
@@ -1240,28 +1239,55 @@ int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out,
 // rows): the a rows [128][128 px] double-buffered, the w rows in a ring of 2 RS + 2 image rows (a stage needs RS + 2, the next one's
 // RS new rows arrive meanwhile), both by LDS-DMA with the 16-byte chunks of a row XOR-swizzled / the row pitch odd in 16-byte slots so
 // that the 32 channels of a fragment read hit distinct banks.
-constexpr int WB_K = 128, WB_C = 64, WB_THREADS = 512, WB_PX = 128;
-constexpr int WB_A_BYTES = WB_K * WB_PX * 2;                 // 32 KB per buffer
-constexpr int WB_X_BYTES = 96 * 1024;                        // the w-row ring (largest: W = 16 -> 18 rows x 64 c x 5 slots x 16 B = 92 KB)
 
-struct WbGeom {
-    int B, Ka, Cb, H, W, wshift;
-    int RS, NSLOT, pitch;       // image rows per stage, ring rows (2 RS + 2), 16-byte slots per (row, channel): W / 8 + 3
+// The plan of all four weight-gradient kernels (this one, its split-bf16 form and the two k4 s2 p1 kernels further down; wrw_geometry).
+// The a operand is the one whose channels index dW's rows (3x3: see above; k4 s2: the coarse tensor), w the one read through the taps
+// (k4 s2: the fine tensor); H x W is the grid the reduction runs over (k4 s2: the coarse grid nh x nw, the fine tensor is 2H x 2W).
+struct WrwGeom {
+    int B, K, C, H, W, wshift;  // channels of a / of w; log2 W
+    int RS, NRING, pitch;       // grid rows per stage; ring entries (3x3: image rows, k4 s2: pairs of fine rows); 16-byte slots per (w row, channel)
     int stages_per_wg, nsplit;  // stages of RS rows a workgroup reduces; B * H / (RS * stages_per_wg) runs
     int ktiles, ctiles;
+    int ring_plane;             // bytes of the ring (split-bf16: of one of its two planes, hi | lo); read by the split-bf16 kernels only
 };
 
-__device__ __forceinline__ unsigned alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
+// What the four kernels differ in as far as the host is concerned: one row per kernel, read by wrw_geometry, wrw_ws_bytes and launch_wrw.
+// LDS of a launch = 2 x TK x PX x 2 bytes of a (bf16: two buffers; split: hi | lo) + the ring (bf16: one plane; split: two).
+enum { WRW_3X3 = 0, WRW_3X3_SPLIT = 1, WRW_S2 = 2, WRW_S2_SPLIT = 3 };
+struct WrwKind {
+    int TK, TC, NT, PX;         // tile: a channels x w channels; taps (= NT of cb_slab_reduce_kernel); pixels per stage
+    int ring_mul, ring_add;     // ring entries = ring_mul * RS + ring_add
+    int wscale, wmax;           // the w tensor per grid pixel, both ways (k4 s2: 2 = rows per ring entry, pitch of 2 W pixels); widest grid
+    int dma_add;                // bf16: one LDS-DMA round moves up to RS + dma_add ring entries, 5 slots per thread; split: -1, no DMA
+    bool split;                 // fp32 tensors, split-bf16 operands: two planes, no zero page, three MFMAs per product
+    const char *who, *width_fmt, *rows_fmt, *ring_fmt;      // the messages, as each planner has always worded them
+    const char *kernel, *reduce;                             // the names check_launch reports
+};
+constexpr WrwKind WRW_KINDS[4] = {
+    // TK  TC  NT   PX  ring   wscale wmax dma split
+    {128, 64,  9, 128, 2, 2,  1,    128,  0, false, "bf16 weight gradient",
+     "%s: image width %d (16, 32, 64 or 128)", "%s: %d rows are not a multiple of %d", "%s: the row ring of a %d-wide image does not fit the LDS plan",
+     "conv_bf16_wrw_kernel", "conv_bf16_wrw_reduce_kernel"},
+    {128, 32,  9, 128, 1, 2,  1,    128, -1, true, "split-bf16 weight gradient",
+     "%s: image width %d (16, 32, 64 or 128)", "%s: %d rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide image does not fit the LDS plan",
+     "conv_bf16x3_wrw_kernel", "conv_bf16_wrw_reduce_kernel"},
+    {128, 32, 16,  64, 2, 1,  2,     64,  1, false, "bf16 4x4 stride-2 weight gradient",
+     "%s: coarse width %d (16, 32 or 64)", "%s: %d coarse rows are not a multiple of %d", "%s: row ring of a %d-wide grid",
+     "conv_bf16_wrw_s2_kernel", "conv_bf16_wrw_s2_reduce_kernel"},
+    {128, 32, 16,  64, 1, 1,  2,     64, -1, true, "split-bf16 4x4 stride-2 weight gradient",
+     "%s: coarse width %d (16, 32 or 64)", "%s: %d coarse rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide grid does not fit the LDS plan",
+     "conv_bf16x3_wrw_s2_kernel", "conv_bf16_wrw_s2_reduce_kernel"},
+};
+constexpr int WB_K = WRW_KINDS[WRW_3X3].TK, WB_C = WRW_KINDS[WRW_3X3].TC, WB_PX = WRW_KINDS[WRW_3X3].PX, WB_THREADS = 512;
+constexpr int WB_A_BYTES = WB_K * WB_PX * 2;                 // 32 KB per buffer; the w-row ring gets the other 96 KB (largest: W = 16 -> 18 rows x 64 c
+                                                             // x 5 slots x 16 B = 92 KB)
 
-__global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsigned short* __restrict__ a, const unsigned short* __restrict__ w,
-                                                                      const uint4* __restrict__ zero_page, WbGeom g, float* __restrict__ slabs)
+// ---- what the four kernels share on the device ----
+struct WrwRun { int kt, ct, split, b, ylo; };               // tile, run, and the run's image and first grid row
+
+// workgroup -> (tile, run): the tiles of one run are neighbours
+__device__ __forceinline__ WrwRun wrw_decode(const WrwGeom& g)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | X ring
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wk = wave >> 1, wc = wave & 1;
-    const int r = lane & 31, h = lane >> 5;
-
     const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
     const int tiles = g.ktiles * g.ctiles;
     const int tile = L % tiles, split = L / tiles;
@@ -1269,6 +1295,64 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
     const int rows_per_wg = g.RS * g.stages_per_wg;
     const int runs_per_img = g.H / rows_per_wg;
     const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
+    return {kt, ct, split, b, ylo};
+}
+
+// The accumulator clear of the two split-bf16 kernels.  The two bf16 kernels keep theirs inline, and all four keep their slab store
+// (slab[split][t][ka][cb], rows by the element map of the 32 x 32 MFMA) inline: hoisted, either one makes hipcc lay the kernel out
+// differently (an inverted compare and branch, other register numbers) — the same work, but not the instruction stream that was measured.
+template <int N>
+__device__ __forceinline__ void wrw_clear(f32x16 (&acc)[N])
+{
+#pragma unroll
+    for (int t = 0; t < N; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+}
+
+__device__ __forceinline__ unsigned alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
+
+// 3x3: the three column taps of 8 pixels at X (a lane's aligned 16-byte chunk of a ring row): the chunk itself and, from it and the dword
+// before and after it, the windows one pixel to the left and to the right
+__device__ __forceinline__ void wrw_shifted(const unsigned char* X, u32x4* left, u32x4* ctr, u32x4* right)
+{
+    const u32x4 c4 = *reinterpret_cast<const u32x4*>(X);    // ext-vector load (see u32x4)
+    const unsigned prev = *reinterpret_cast<const unsigned*>(X - 4);
+    const unsigned next = *reinterpret_cast<const unsigned*>(X + 16);
+    const unsigned s0 = alignbit16(c4.x, prev), s1 = alignbit16(c4.y, c4.x), s2 = alignbit16(c4.z, c4.y), s3 = alignbit16(c4.w, c4.z),
+                   s4 = alignbit16(next, c4.w);
+    *ctr = c4; *left = u32x4{s0, s1, s2, s3}; *right = u32x4{s1, s2, s3, s4};
+}
+
+__device__ __forceinline__ unsigned pack_hi(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x07060302u); }   // {x.hi16, y.hi16}
+__device__ __forceinline__ unsigned pack_lo(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x05040100u); }   // {x.lo16, y.lo16}
+
+// k4 s2: the four column taps s of 8 coarse pixels from the 16 fine pixels at X (two aligned 16-byte chunks of a ring row) and the dword
+// before and after them: every other fine pixel, starting at fine column 2 ox - 1 + s
+__device__ __forceinline__ void wrw_pick_even_odd(const unsigned char* X, u32x4 (&f)[4])
+{
+    const u32x4 lo4 = *reinterpret_cast<const u32x4*>(X);
+    const u32x4 hi4 = *reinterpret_cast<const u32x4*>(X + 16);
+    const unsigned prev = *reinterpret_cast<const unsigned*>(X - 4);
+    const unsigned next = *reinterpret_cast<const unsigned*>(X + 32);
+    const unsigned d0 = lo4.x, d1 = lo4.y, d2 = lo4.z, d3 = lo4.w, d4 = hi4.x, d5 = hi4.y, d6 = hi4.z, d7 = hi4.w;
+    f[0] = u32x4{pack_hi(prev, d0), pack_hi(d1, d2), pack_hi(d3, d4), pack_hi(d5, d6)};
+    f[1] = u32x4{pack_lo(d0, d1), pack_lo(d2, d3), pack_lo(d4, d5), pack_lo(d6, d7)};
+    f[2] = u32x4{pack_hi(d0, d1), pack_hi(d2, d3), pack_hi(d4, d5), pack_hi(d6, d7)};
+    f[3] = u32x4{pack_lo(d1, d2), pack_lo(d3, d4), pack_lo(d5, d6), pack_lo(d7, next)};
+}
+
+__global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsigned short* __restrict__ a, const unsigned short* __restrict__ w,
+                                                                      const uint4* __restrict__ zero_page, WrwGeom g, float* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | X ring
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, wc = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
     const size_t HW = (size_t)g.H * g.W;
     const int cpr = g.W >> 3;                                // 16-byte chunks per image row
 
@@ -1280,9 +1364,9 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
         const int k = sigma >> 4, c8 = (sigma & 15) ^ (k & 15);
         const int rs = c8 / cpr, cx = c8 - rs * cpr;
         const int ka = kt * WB_K + k;
-        ga[j] = ka < g.Ka ? a + ((size_t)b * g.Ka + ka) * HW + (size_t)(ylo + rs) * g.W + cx * 8 : nullptr;
+        ga[j] = ka < g.K ? a + ((size_t)b * g.K + ka) * HW + (size_t)(ylo + rs) * g.W + cx * 8 : nullptr;
     }
-    // ---- w rows: ring slot of image row y = (y + 1) mod NSLOT; per (ring row, channel): [halo][W / 8 chunks][halo][pad] = `pitch` slots ----
+    // ---- w rows: ring slot of image row y = (y + 1) mod NRING; per (ring row, channel): [halo][W / 8 chunks][halo][pad] = `pitch` slots ----
     // a group of RS rows = RS * 64 * pitch slots; slot q = (row rr, channel c, slot sl); 64 * pitch is a multiple of 64, so the 64 lanes of
     // one DMA instruction never straddle rows: wave-uniform LDS base, per-lane source
     const int xslots = g.RS * WB_C * g.pitch;
@@ -1293,8 +1377,8 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
         const int qq = q < xslots ? q : 0;
         const int sl = qq % g.pitch, c = (qq / g.pitch) % WB_C;
         const int cb = ct * WB_C + c;
-        const bool data = sl >= 1 && sl <= cpr && cb < g.Cb;
-        gxw[j] = data ? w + ((size_t)b * g.Cb + cb) * HW + (sl - 1) * 8 : nullptr;
+        const bool data = sl >= 1 && sl <= cpr && cb < g.C;
+        gxw[j] = data ? w + ((size_t)b * g.C + cb) * HW + (sl - 1) * 8 : nullptr;
     }
     const int ring_row_slots = WB_C * g.pitch, ring_row_bytes = ring_row_slots * 16;
 
@@ -1319,8 +1403,8 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
             if (q0 < xslots) {
                 const int rr = q0 / ring_row_slots, within = q0 - rr * ring_row_slots;
                 const int y = y_first + rr;
-                int slot = (y + 1) % g.NSLOT;
-                if (slot < 0) slot += g.NSLOT;
+                int slot = (y + 1) % g.NRING;
+                if (slot < 0) slot += g.NRING;
                 const bool ok = gxw[j] != nullptr && (unsigned)y < (unsigned)g.H;
                 const void* src = ok ? static_cast<const void*>(gxw[j] + (size_t)y * g.W) : static_cast<const void*>(zero_page);
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + 2 * WB_A_BYTES + slot * ring_row_bytes + within * 16), 16, 0, 0);
@@ -1352,14 +1436,10 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
             const int rs = p0 >> g.wshift, px = (p0 & (g.W - 1)) + 8 * h;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                int slot = (y0 + rs + dy) % g.NSLOT;          // image row y0 + rs + dy - 1 lives in ring slot (y + 1) mod NSLOT
+                int slot = (y0 + rs + dy) % g.NRING;          // image row y0 + rs + dy - 1 lives in ring slot (y + 1) mod NRING
                 const unsigned char* X = lds + 2 * WB_A_BYTES + slot * ring_row_bytes + (bcol * g.pitch + 1 + (px >> 3)) * 16;
-                const u32x4 c4 = *reinterpret_cast<const u32x4*>(X);    // ext-vector load (see u32x4)
-                const unsigned prev = *reinterpret_cast<const unsigned*>(X - 4);
-                const unsigned next = *reinterpret_cast<const unsigned*>(X + 16);
-                const unsigned s0 = alignbit16(c4.x, prev), s1 = alignbit16(c4.y, c4.x), s2 = alignbit16(c4.z, c4.y), s3 = alignbit16(c4.w, c4.z),
-                               s4 = alignbit16(next, c4.w);
-                const uint4 left = make_uint4(s0, s1, s2, s3), right = make_uint4(s1, s2, s3, s4);
+                u32x4 left, c4, right;
+                wrw_shifted(X, &left, &c4, &right);
                 acc[dy * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, left), acc[dy * 3 + 0], 0, 0, 0);
                 acc[dy * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, c4), acc[dy * 3 + 1], 0, 0, 0);
                 acc[dy * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, right), acc[dy * 3 + 2], 0, 0, 0);
@@ -1370,59 +1450,15 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16_wrw_kernel(const unsi
     }
 
     // partial result: slab[split][t][ka][cb] (lanes along cb: coalesced)
-    const int Kap = g.ktiles * WB_K, Cbp = g.ctiles * WB_C;
-    float* out = slabs + (size_t)split * 9 * Kap * Cbp;
+    const int Kp = g.ktiles * WB_K, Cp = g.ctiles * WB_C;
+    float* out = slabs + (size_t)split * 9 * Kp * Cp;
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int ka = kt * WB_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            out[((size_t)t * Kap + ka) * Cbp + ct * WB_C + bcol] = acc[t][e];
+            out[((size_t)t * Kp + ka) * Cp + ct * WB_C + bcol] = acc[t][e];
         }
-}
-
-static int wb_geometry(int B, int Ka, int Cb, int H, int W, WbGeom* g)
-{
-    if (W != 16 && W != 32 && W != 64 && W != 128) return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: image width %d (16, 32, 64 or 128)", W);
-    const int RS = WB_PX / W;
-    if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: %d rows are not a multiple of %d", H, RS);
-    g->B = B; g->Ka = Ka; g->Cb = Cb; g->H = H; g->W = W;
-    g->wshift = cb_wshift(W);
-    g->RS = RS; g->NSLOT = 2 * RS + 2; g->pitch = W / 8 + 3;
-    g->ktiles = (Ka + WB_K - 1) / WB_K; g->ctiles = (Cb + WB_C - 1) / WB_C;
-    if (g->NSLOT * WB_C * g->pitch * 16 > WB_X_BYTES || RS * WB_C * g->pitch > 5 * WB_THREADS)
-        return fail(IPSR_ERR_UNSUPPORTED, "bf16 weight gradient: the row ring of a %d-wide image does not fit the LDS plan", W);
-    cb_cut_runs(g->ktiles * g->ctiles, B, H / RS, &g->stages_per_wg, &g->nsplit);
-    return IPSR_OK;
-}
-
-size_t conv_bf16_wrw_ws_bytes(int B, int Ka, int Cb, int H, int W)
-{
-    WbGeom g;
-    if (wb_geometry(B, Ka, Cb, H, W, &g) != IPSR_OK) return 0;
-    return 256 + (size_t)g.nsplit * 9 * g.ktiles * WB_K * g.ctiles * WB_C * 4;
-}
-
-// a [B,Ka,H,W], w [B,Cb,H,W] bf16 -> dW [Ka][Cb][3][3] fp32
-int launch_conv_bf16_wrw(const void* a, const void* w, float* dW, int B, int Ka, int Cb, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    WbGeom g;
-    if (int rc = wb_geometry(B, Ka, Cb, H, W, &g)) return rc;
-    const size_t need = conv_bf16_wrw_ws_bytes(B, Ka, Cb, H, W);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "bf16 weight gradient: workspace %zu < %zu", ws_bytes, need);
-    uint4* zero_page = static_cast<uint4*>(ws);
-    float* slabs = reinterpret_cast<float*>(zero_page + 16);
-    if (hipMemsetAsync(zero_page, 0, 64, st) != hipSuccess) return fail(IPSR_ERR_LAUNCH, "bf16 weight gradient: hipMemsetAsync failed");
-    const size_t smem = 2 * (size_t)WB_A_BYTES + (size_t)g.NSLOT * WB_C * g.pitch * 16;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_wrw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * WB_A_BYTES + WB_X_BYTES); attr = true; }
-    const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
-    profile_mark_start(st, 4);
-    conv_bf16_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
-    profile_mark_stop(st, 4, 2.0 * 9.0 * (double)(g.ktiles * WB_K) * (g.ctiles * WB_C) * B * H * W, 2.0 * 9.0 * (double)Ka * Cb * B * H * W);
-    if (int rc = check_launch("conv_bf16_wrw_kernel")) return rc;
-    cb_slab_reduce_kernel<9><<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WB_K, g.ctiles * WB_C, dW);
-    return check_launch("conv_bf16_wrw_reduce_kernel");
 }
 
 // =====================================================================================================================================
@@ -1445,16 +1481,8 @@ int launch_conv_bf16_wrw(const void* a, const void* w, float* dW, int B, int Ka,
 // LDS: a hi | a lo = 2 x 32 KB; ring hi | ring lo = 2 x (RS + 2) x 32 c x (W / 8 + 3) slots x 16 B:
 //      W = 16: 65536 + 51200 = 116736 B   W = 32: 65536 + 43008 = 108544 B   W = 64: 65536 + 45056 = 110592 B   W = 128: 65536 + 58368 = 123904 B
 // Supported: W in {16, 32, 64, 128}, H a multiple of 128 / W.  Deterministic: no atomics, every sum in a fixed order.
-constexpr int WX_K = 128, WX_C = 32, WX_PX = 128;
+constexpr int WX_K = WRW_KINDS[WRW_3X3_SPLIT].TK, WX_C = WRW_KINDS[WRW_3X3_SPLIT].TC, WX_PX = WRW_KINDS[WRW_3X3_SPLIT].PX;
 constexpr int WX_A_PLANE = WX_K * WX_PX * 2;                 // 32 KB per plane
-
-struct WxGeom {
-    int B, Ka, Cb, H, W, wshift;
-    int RS, NSLOT, pitch;       // image rows per stage, ring rows (RS + 2), 16-byte slots per (row, channel): W / 8 + 3
-    int stages_per_wg, nsplit;  // stages of RS rows a workgroup reduces; B * H / (RS * stages_per_wg) runs
-    int ktiles, ctiles;
-    int ring_plane;             // bytes of one plane of the ring
-};
 
 // 8 consecutive fp32 pixels -> their hi and lo bf16 images (16 bytes each)
 __device__ __forceinline__ void wx_split8(const f32x4& v0, const f32x4& v1, u32x4* hi, u32x4* lo)
@@ -1470,7 +1498,7 @@ __device__ __forceinline__ void wx_split8(const f32x4& v0, const f32x4& v1, u32x
     for (int i = 0; i < 4; ++i) { (*hi)[i] = h16[2 * i] | (h16[2 * i + 1] << 16); (*lo)[i] = l16[2 * i] | (l16[2 * i + 1] << 16); }
 }
 
-__global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const float* __restrict__ a, const float* __restrict__ w, WxGeom g,
+__global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const float* __restrict__ a, const float* __restrict__ w, WrwGeom g,
                                                                         float* __restrict__ slabs)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // a hi | a lo | ring hi | ring lo
@@ -1479,13 +1507,8 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
     const int wk = wave >> 1, wp = wave & 1;
     const int r = lane & 31, h = lane >> 5;
 
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const int tiles = g.ktiles * g.ctiles;
-    const int tile = L % tiles, split = L / tiles;
-    const int kt = tile % g.ktiles, ct = tile / g.ktiles;
-    const int rows_per_wg = g.RS * g.stages_per_wg;
-    const int runs_per_img = g.H / rows_per_wg;
-    const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
     const size_t HW = (size_t)g.H * g.W;
     const int cpr = g.W >> 3;                                // 16-byte bf16 chunks per image row
     unsigned char* const ring = lds + 2 * WX_A_PLANE;
@@ -1498,20 +1521,17 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int ka = kt * WX_K + k0 + 32 * j;
-        ga[j] = ka < g.Ka ? a + ((size_t)b * g.Ka + ka) * HW + (size_t)ylo * g.W + c8 * 8 : nullptr;
+        ga[j] = ka < g.K ? a + ((size_t)b * g.K + ka) * HW + (size_t)ylo * g.W + c8 * 8 : nullptr;
     }
     const int a_wr = ((k0 << 4) + (c8 ^ (k0 & 15))) * 16;    // + j * 8192
     // ---- w rows: a lane owns chunk c8 (row rr, chunk cx of the stage's RS new rows) of channel tid >> 4 -------------------------------------
     const int rr = c8 / cpr, cx = c8 - rr * cpr;
     const int cbw = ct * WX_C + k0;
-    const float* gw = cbw < g.Cb ? w + ((size_t)b * g.Cb + cbw) * HW + c8 * 8 : nullptr;
+    const float* gw = cbw < g.C ? w + ((size_t)b * g.C + cbw) * HW + c8 * 8 : nullptr;
     const int w_wr = (k0 * g.pitch + 1 + cx) * 16;
 
     f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+    wrw_clear(acc);
 
     f32x4 ar[8], wr[2];
 #pragma unroll
@@ -1542,7 +1562,7 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
             *reinterpret_cast<u32x4*>(lds + a_wr + j * 8192) = vh;
             *reinterpret_cast<u32x4*>(lds + WX_A_PLANE + a_wr + j * 8192) = vl;
         }
-        const int slot = (ylo + s * g.RS + 2 + rr) % g.NSLOT;                    // image row y lives in ring slot (y + 1) mod NSLOT
+        const int slot = (ylo + s * g.RS + 2 + rr) % g.NRING;                    // image row y lives in ring slot (y + 1) mod NRING
         wx_split8(wr[0], wr[1], &vh, &vl);
         *reinterpret_cast<u32x4*>(ring + slot * ring_row_bytes + w_wr) = vh;
         *reinterpret_cast<u32x4*>(ring + g.ring_plane + slot * ring_row_bytes + w_wr) = vl;
@@ -1556,11 +1576,11 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
         const int e = i / (WX_C * cpr), rem = i - e * (WX_C * cpr);
         const int c = rem / cpr, x8 = rem - c * cpr;
         const int y = ylo - 1 + e, cb = ct * WX_C + c;
-        if (cb < g.Cb && y >= 0) {                           // else: the zeros stay
-            const float* src = w + ((size_t)b * g.Cb + cb) * HW + (size_t)y * g.W + x8 * 8;
+        if (cb < g.C && y >= 0) {                            // else: the zeros stay
+            const float* src = w + ((size_t)b * g.C + cb) * HW + (size_t)y * g.W + x8 * 8;
             u32x4 vh, vl;
             wx_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), &vh, &vl);
-            const int off = ((y + 1) % g.NSLOT) * ring_row_bytes + (c * g.pitch + 1 + x8) * 16;
+            const int off = ((y + 1) % g.NRING) * ring_row_bytes + (c * g.pitch + 1 + x8) * 16;
             *reinterpret_cast<u32x4*>(ring + off) = vh;
             *reinterpret_cast<u32x4*>(ring + g.ring_plane + off) = vl;
         }
@@ -1582,19 +1602,11 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
             const int rs = p0 >> g.wshift, px = (p0 & (g.W - 1)) + 8 * h;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                const int slot = (y0 + rs + dy) % g.NSLOT;    // image row y0 + rs + dy - 1
+                const int slot = (y0 + rs + dy) % g.NRING;    // image row y0 + rs + dy - 1
                 const unsigned char* X = ring + slot * ring_row_bytes + (r * g.pitch + 1 + (px >> 3)) * 16;
                 u32x4 ctr[2], left[2], right[2];
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const unsigned char* Xp = X + pl * g.ring_plane;
-                    const u32x4 c4 = *reinterpret_cast<const u32x4*>(Xp);
-                    const unsigned prev = *reinterpret_cast<const unsigned*>(Xp - 4);
-                    const unsigned next = *reinterpret_cast<const unsigned*>(Xp + 16);
-                    const unsigned s0 = alignbit16(c4.x, prev), s1 = alignbit16(c4.y, c4.x), s2 = alignbit16(c4.z, c4.y), s3 = alignbit16(c4.w, c4.z),
-                                   s4 = alignbit16(next, c4.w);
-                    ctr[pl] = c4; left[pl] = u32x4{s0, s1, s2, s3}; right[pl] = u32x4{s1, s2, s3, s4};
-                }
+                for (int pl = 0; pl < 2; ++pl) wrw_shifted(X + pl * g.ring_plane, &left[pl], &ctr[pl], &right[pl]);
                 f32x16& a0 = acc[dy * 3 + 0];
                 f32x16& a1 = acc[dy * 3 + 1];
                 f32x16& a2 = acc[dy * 3 + 2];
@@ -1639,60 +1651,15 @@ __global__ void __launch_bounds__(WB_THREADS, 1) conv_bf16x3_wrw_kernel(const fl
     if (wp != 0) return;
 
     // partial result: slab[split][t][ka][cb] (lanes along cb: coalesced)
-    const int Kap = g.ktiles * WX_K, Cbp = g.ctiles * WX_C;
-    float* out = slabs + (size_t)split * 9 * Kap * Cbp;
+    const int Kp = g.ktiles * WX_K, Cp = g.ctiles * WX_C;
+    float* out = slabs + (size_t)split * 9 * Kp * Cp;
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int ka = kt * WX_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            out[((size_t)t * Kap + ka) * Cbp + ct * WX_C + r] = acc[t][e];
+            out[((size_t)t * Kp + ka) * Cp + ct * WX_C + r] = acc[t][e];
         }
-}
-
-static int wx_geometry(int B, int Ka, int Cb, int H, int W, WxGeom* g)
-{
-    const char* who = "split-bf16 weight gradient";
-    if (W != 16 && W != 32 && W != 64 && W != 128) return fail(IPSR_ERR_UNSUPPORTED, "%s: image width %d (16, 32, 64 or 128)", who, W);
-    const int RS = WX_PX / W;
-    if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a stage", who, H, RS);
-    g->B = B; g->Ka = Ka; g->Cb = Cb; g->H = H; g->W = W;
-    g->wshift = cb_wshift(W);
-    g->RS = RS; g->NSLOT = RS + 2; g->pitch = W / 8 + 3;
-    g->ktiles = (Ka + WX_K - 1) / WX_K; g->ctiles = (Cb + WX_C - 1) / WX_C;
-    g->ring_plane = g->NSLOT * WX_C * g->pitch * 16;
-    if (2 * WX_A_PLANE + 2 * g->ring_plane > CB_LDS_MAX)
-        return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide image does not fit the LDS plan", who, W);
-    cb_cut_runs(g->ktiles * g->ctiles, B, H / RS, &g->stages_per_wg, &g->nsplit);
-    return IPSR_OK;
-}
-
-// the partial slabs, nothing else
-size_t conv_bf16x3_wrw_ws_bytes(int B, int Ka, int Cb, int H, int W)
-{
-    WxGeom g;
-    if (wx_geometry(B, Ka, Cb, H, W, &g) != IPSR_OK) return 0;
-    return (size_t)g.nsplit * 9 * g.ktiles * WX_K * g.ctiles * WX_C * 4;
-}
-
-// a [B,Ka,H,W], w [B,Cb,H,W] fp32 -> dW [Ka][Cb][3][3] fp32
-int launch_conv_bf16x3_wrw(const float* a, const float* w, float* dW, int B, int Ka, int Cb, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    WxGeom g;
-    if (int rc = wx_geometry(B, Ka, Cb, H, W, &g)) return rc;
-    const size_t need = conv_bf16x3_wrw_ws_bytes(B, Ka, Cb, H, W);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 weight gradient: workspace %zu < %zu", ws_bytes, need);
-    float* slabs = static_cast<float*>(ws);
-    const size_t smem = 2 * (size_t)WX_A_PLANE + 2 * (size_t)g.ring_plane;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_wrw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
-    const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
-    profile_mark_start(st, 4);
-    conv_bf16x3_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(a, w, g, slabs);
-    profile_mark_stop(st, 4, 3.0 * 2.0 * 9.0 * (double)(g.ktiles * WX_K) * (g.ctiles * WX_C) * B * H * W, 2.0 * 9.0 * (double)Ka * Cb * B * H * W);
-    if (int rc = check_launch("conv_bf16x3_wrw_kernel")) return rc;
-    cb_slab_reduce_kernel<9><<<dim3(cdiv(Cb, 256), Ka), 256, 0, st>>>(slabs, g.nsplit, Ka, Cb, g.ktiles * WX_K, g.ctiles * WX_C, dW);
-    return check_launch("conv_bf16_wrw_reduce_kernel");
 }
 
 // =====================================================================================================================================
@@ -1705,20 +1672,12 @@ int launch_conv_bf16x3_wrw(const float* a, const float* w, float* dW, int B, int
 // pixels (RS = 64 / nw coarse rows); the fine rows live in a ring of 4 RS + 2 image rows handled in PAIRS (row 2 i - 1 and 2 i:
 // 64 x pitch slots, so a DMA instruction never straddles ring entries); runs of coarse rows are cut over workgroups, the partial
 // [t][kc][cf] slabs added in order by the second launch.
-constexpr int W2_K = 128, W2_C = 32, W2_PX = 64;
+// In WrwGeom's terms (both k4 s2 kernels): K = Kc, C = Cf, H x W = the coarse grid nh x nw, NRING = pairs of fine rows.
+constexpr int W2_K = WRW_KINDS[WRW_S2].TK, W2_C = WRW_KINDS[WRW_S2].TC, W2_PX = WRW_KINDS[WRW_S2].PX;
 constexpr int W2_A_BYTES = W2_K * W2_PX * 2;                 // 16 KB per buffer
 
-struct W2Geom {
-    int B, Kc, Cf, nh, nw, wshift;      // coarse grid nh x nw (fine 2nh x 2nw)
-    int RS, NPAIR, pitch;               // coarse rows per stage, ring entries (pairs of fine rows: 2 RS + 1), slots per (fine row, channel)
-    int stages_per_wg, nsplit, ktiles, ctiles;
-};
-
-__device__ __forceinline__ unsigned pack_hi(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x07060302u); }   // {x.hi16, y.hi16}
-__device__ __forceinline__ unsigned pack_lo(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x05040100u); }   // {x.lo16, y.lo16}
-
 __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned short* __restrict__ coarse, const unsigned short* __restrict__ fine,
-                                                                   const uint4* __restrict__ zero_page, W2Geom g, float* __restrict__ slabs)
+                                                                   const uint4* __restrict__ zero_page, WrwGeom g, float* __restrict__ slabs)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | fine-row ring
     const int tid = threadIdx.x;
@@ -1726,16 +1685,11 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
     const int wk = wave >> 1, rh = wave & 1;
     const int r = lane & 31, h = lane >> 5;
 
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const int tiles = g.ktiles * g.ctiles;
-    const int tile = L % tiles, split = L / tiles;
-    const int kt = tile % g.ktiles, ct = tile / g.ktiles;
-    const int rows_per_wg = g.RS * g.stages_per_wg;
-    const int runs_per_img = g.nh / rows_per_wg;
-    const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
-    const int Hf = 2 * g.nh, Wf = 2 * g.nw;
-    const size_t HWc = (size_t)g.nh * g.nw, HWf = (size_t)Hf * Wf;
-    const int cprc = g.nw >> 3;                              // 16-byte chunks per coarse row
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
+    const int Hf = 2 * g.H, Wf = 2 * g.W;
+    const size_t HWc = (size_t)g.H * g.W, HWf = (size_t)Hf * Wf;
+    const int cprc = g.W >> 3;                               // 16-byte chunks per coarse row
     const int cprf = Wf >> 3;                                // ... per fine row
 
     // ---- coarse rows: slot sigma = k * 8 + cs holds stage chunk c8 = cs ^ (k & 7) of channel k; c8 -> (coarse row rs, chunk cx) ----------
@@ -1746,9 +1700,9 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
         const int k = sigma >> 3, c8 = (sigma & 7) ^ (k & 7);
         const int rs = c8 / cprc, cx = c8 - rs * cprc;
         const int kc = kt * W2_K + k;
-        ga[j] = kc < g.Kc ? coarse + ((size_t)b * g.Kc + kc) * HWc + (size_t)(ylo + rs) * g.nw + cx * 8 : nullptr;
+        ga[j] = kc < g.K ? coarse + ((size_t)b * g.K + kc) * HWc + (size_t)(ylo + rs) * g.W + cx * 8 : nullptr;
     }
-    // ---- fine rows: ring entry of the row pair (2 i - 1, 2 i) = i mod NPAIR; per (row, channel): [halo][Wf / 8 chunks][halo][pad] ---------
+    // ---- fine rows: ring entry of the row pair (2 i - 1, 2 i) = i mod NRING; per (row, channel): [halo][Wf / 8 chunks][halo][pad] ---------
     const int pair_slots = 2 * W2_C * g.pitch;               // a multiple of 64
     const unsigned short* gf[5];
     int f_row[5];
@@ -1760,8 +1714,8 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
         const int c = rem / g.pitch, sl = rem - c * g.pitch;
         const int cf = ct * W2_C + c;
         f_row[j] = 2 * (q / pair_slots) + pr;                // fine row offset from the first row of the group
-        const bool data = sl >= 1 && sl <= cprf && cf < g.Cf;
-        gf[j] = data ? fine + ((size_t)b * g.Cf + cf) * HWf + (sl - 1) * 8 : nullptr;
+        const bool data = sl >= 1 && sl <= cprf && cf < g.C;
+        gf[j] = data ? fine + ((size_t)b * g.C + cf) * HWf + (sl - 1) * 8 : nullptr;
     }
     const int pair_bytes = pair_slots * 16;
 
@@ -1774,7 +1728,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
     auto dma_a = [&](int buf, int stage) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const void* src = ga[j] ? static_cast<const void*>(ga[j] + (size_t)stage * g.RS * g.nw) : static_cast<const void*>(zero_page);
+            const void* src = ga[j] ? static_cast<const void*>(ga[j] + (size_t)stage * g.RS * g.W) : static_cast<const void*>(zero_page);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + buf * W2_A_BYTES + (wave + 8 * j) * 1024), 16, 0, 0);
         }
     };
@@ -1786,8 +1740,8 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
             const int q0 = wave * 64 + 512 * j;              // uniform
             if (q0 < nslots) {
                 const int pp = q0 / pair_slots, within = q0 - pp * pair_slots;
-                int entry = (i0 + pp) % g.NPAIR;
-                if (entry < 0) entry += g.NPAIR;
+                int entry = (i0 + pp) % g.NRING;
+                if (entry < 0) entry += g.NRING;
                 const int yf = 2 * i0 - 1 + f_row[j];
                 const bool ok = gf[j] != nullptr && (unsigned)yf < (unsigned)Hf;
                 const void* src = ok ? static_cast<const void*>(gf[j] + (size_t)yf * Wf) : static_cast<const void*>(zero_page);
@@ -1817,26 +1771,17 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
             const int c8 = 2 * j + h;
             const bf16x8 fa = *reinterpret_cast<const bf16x8*>(A + ((a_row << 3) + (c8 ^ (a_row & 7))) * 16);
             const int p0 = 16 * j;
-            const int rs = p0 >> g.wshift, ox0 = (p0 & (g.nw - 1)) + 8 * h;
+            const int rs = p0 >> g.wshift, ox0 = (p0 & (g.W - 1)) + 8 * h;
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri) {
                 // fine row 2 (y0 + rs) - 1 + (2 rh + ri) = row (1 - ...) of a pair: row index u = 2 (y0 + rs) + 2 rh + ri  ->  pair u / 2, member u & 1
                 const int u = 2 * (y0 + rs) + 2 * rh + ri;    // = fine row + 1
-                const int entry = (u >> 1) % g.NPAIR;
+                const int entry = (u >> 1) % g.NRING;
                 const unsigned char* X = lds + 2 * W2_A_BYTES + entry * pair_bytes + (u & 1) * row_bytes + (r * g.pitch + 1 + (ox0 >> 2)) * 16;
-                const u32x4 lo4 = *reinterpret_cast<const u32x4*>(X);
-                const u32x4 hi4 = *reinterpret_cast<const u32x4*>(X + 16);
-                const unsigned prev = *reinterpret_cast<const unsigned*>(X - 4);
-                const unsigned next = *reinterpret_cast<const unsigned*>(X + 32);
-                const unsigned d0 = lo4.x, d1 = lo4.y, d2 = lo4.z, d3 = lo4.w, d4 = hi4.x, d5 = hi4.y, d6 = hi4.z, d7 = hi4.w;
-                const uint4 f0 = make_uint4(pack_hi(prev, d0), pack_hi(d1, d2), pack_hi(d3, d4), pack_hi(d5, d6));
-                const uint4 f1 = make_uint4(pack_lo(d0, d1), pack_lo(d2, d3), pack_lo(d4, d5), pack_lo(d6, d7));
-                const uint4 f2 = make_uint4(pack_hi(d0, d1), pack_hi(d2, d3), pack_hi(d4, d5), pack_hi(d6, d7));
-                const uint4 f3 = make_uint4(pack_lo(d1, d2), pack_lo(d3, d4), pack_lo(d5, d6), pack_lo(d7, next));
-                acc[ri * 4 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f0), acc[ri * 4 + 0], 0, 0, 0);
-                acc[ri * 4 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f1), acc[ri * 4 + 1], 0, 0, 0);
-                acc[ri * 4 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f2), acc[ri * 4 + 2], 0, 0, 0);
-                acc[ri * 4 + 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f3), acc[ri * 4 + 3], 0, 0, 0);
+                u32x4 f[4];                                  // [column tap]
+                wrw_pick_even_odd(X, f);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f[t]), acc[ri * 4 + t], 0, 0, 0);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1850,53 +1795,9 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_wrw_s2_kernel(const unsigned
     for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int kc = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            out[((size_t)(rh * 8 + t) * Kp + kc) * Cp + ct * W2_C + r] = acc[t][e];
+            const int ka = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)(rh * 8 + t) * Kp + ka) * Cp + ct * W2_C + r] = acc[t][e];
         }
-}
-
-static int w2_geometry(int B, int Kc, int Cf, int nh, int nw, W2Geom* g)
-{
-    if (nw != 16 && nw != 32 && nw != 64) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: coarse width %d (16, 32 or 64)", nw);
-    const int RS = W2_PX / nw;
-    if (nh % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: %d coarse rows are not a multiple of %d", nh, RS);
-    g->B = B; g->Kc = Kc; g->Cf = Cf; g->nh = nh; g->nw = nw;
-    g->wshift = cb_wshift(nw);
-    g->RS = RS; g->NPAIR = 2 * RS + 1; g->pitch = 2 * nw / 8 + 3;
-    g->ktiles = (Kc + W2_K - 1) / W2_K; g->ctiles = (Cf + W2_C - 1) / W2_C;
-    if ((RS + 1) * 2 * W2_C * g->pitch > 5 * 512) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: row ring of a %d-wide grid", nw);
-    cb_cut_runs(g->ktiles * g->ctiles, B, nh / RS, &g->stages_per_wg, &g->nsplit);
-    return IPSR_OK;
-}
-
-size_t conv_bf16_wrw_s2_ws_bytes(int B, int Kc, int Cf, int nh, int nw)
-{
-    W2Geom g;
-    if (w2_geometry(B, Kc, Cf, nh, nw, &g) != IPSR_OK) return 0;
-    return 256 + (size_t)g.nsplit * 16 * g.ktiles * W2_K * g.ctiles * W2_C * 4;
-}
-
-// fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw] bf16 -> dW [Kc][Cf][4][4] fp32
-int launch_conv_bf16_wrw_s2(const void* fine, const void* coarse, float* dW, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    W2Geom g;
-    if (int rc = w2_geometry(B, Kc, Cf, nh, nw, &g)) return rc;
-    const size_t need = conv_bf16_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "bf16 4x4 stride-2 weight gradient: workspace %zu < %zu", ws_bytes, need);
-    uint4* zero_page = static_cast<uint4*>(ws);
-    float* slabs = reinterpret_cast<float*>(zero_page + 16);
-    if (hipMemsetAsync(zero_page, 0, 64, st) != hipSuccess) return fail(IPSR_ERR_LAUNCH, "bf16 4x4 stride-2 weight gradient: hipMemsetAsync failed");
-    const size_t smem = 2 * (size_t)W2_A_BYTES + (size_t)g.NPAIR * 2 * W2_C * g.pitch * 16;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_wrw_s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX); attr = true; }
-    if (smem > (size_t)CB_LDS_MAX) return fail(IPSR_ERR_UNSUPPORTED, "bf16 4x4 stride-2 weight gradient: %zu bytes of LDS", smem);
-    const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
-    profile_mark_start(st, 4);
-    conv_bf16_wrw_s2_kernel<<<grid, 512, smem, st>>>(static_cast<const unsigned short*>(coarse), static_cast<const unsigned short*>(fine), zero_page, g, slabs);
-    profile_mark_stop(st, 4, 2.0 * 16.0 * (double)(g.ktiles * W2_K) * (g.ctiles * W2_C) * B * nh * nw, 2.0 * 16.0 * (double)Kc * Cf * B * nh * nw);
-    if (int rc = check_launch("conv_bf16_wrw_s2_kernel")) return rc;
-    cb_slab_reduce_kernel<16><<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
-    return check_launch("conv_bf16_wrw_s2_reduce_kernel");
 }
 
 // =====================================================================================================================================
@@ -1919,14 +1820,7 @@ int launch_conv_bf16_wrw_s2(const void* fine, const void* coarse, float* dW, int
 // nw = 128 is refused: a stage of 64 coarse pixels is half a coarse row, and a ring of whole fine rows costs 2 planes x 2 pairs x 2 rows x
 // 32 cf x 35 slots x 16 B = 143360 B + 32768 = 176128 B > 160 KB of LDS.
 // Supported: nw in {16, 32, 64}, nh a multiple of 64 / nw.  Deterministic: no atomics, every sum in a fixed order.
-struct X2Geom {
-    int B, Kc, Cf, nh, nw, wshift;
-    int RS, NPAIR, pitch;               // coarse rows per stage, ring entries (RS + 1 pairs of fine rows), slots per (fine row, channel)
-    int stages_per_wg, nsplit, ktiles, ctiles;
-    int ring_plane;                     // bytes of one plane (hi or lo) of the ring
-};
-
-__global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float* __restrict__ coarse, const float* __restrict__ fine, X2Geom g,
+__global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float* __restrict__ coarse, const float* __restrict__ fine, WrwGeom g,
                                                                      float* __restrict__ slabs)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // coarse hi | coarse lo | ring hi | ring lo
@@ -1935,15 +1829,10 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
     const int wk = wave >> 1, rh = wave & 1;
     const int r = lane & 31, h = lane >> 5;
 
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const int tiles = g.ktiles * g.ctiles;
-    const int tile = L % tiles, split = L / tiles;
-    const int kt = tile % g.ktiles, ct = tile / g.ktiles;
-    const int rows_per_wg = g.RS * g.stages_per_wg;
-    const int runs_per_img = g.nh / rows_per_wg;
-    const int b = split / runs_per_img, ylo = (split - b * runs_per_img) * rows_per_wg;
-    const int Hf = 2 * g.nh, Wf = 2 * g.nw;
-    const size_t HWc = (size_t)g.nh * g.nw, HWf = (size_t)Hf * Wf;
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
+    const int Hf = 2 * g.H, Wf = 2 * g.W;
+    const size_t HWc = (size_t)g.H * g.W, HWf = (size_t)Hf * Wf;
     const int cprf = Wf >> 3;                                // 8-pixel chunks per fine row
     unsigned char* const ring = lds + 2 * W2_A_BYTES;
     const int row_bytes = W2_C * g.pitch * 16;
@@ -1956,7 +1845,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int kc = kt * W2_K + k0 + 64 * j;
-        ga[j] = kc < g.Kc ? coarse + ((size_t)b * g.Kc + kc) * HWc + (size_t)ylo * g.nw + c8 * 8 : nullptr;
+        ga[j] = kc < g.K ? coarse + ((size_t)b * g.K + kc) * HWc + (size_t)ylo * g.W + c8 * 8 : nullptr;
     }
     const int a_wr = ((k0 << 3) + (c8 ^ (k0 & 7))) * 16;     // + j * 8192
     // ---- fine rows: the 2 RS new rows of a stage are 32 chunks per channel; a lane owns chunk fi = tid & 31 (row fr, chunk fx) of the
@@ -1968,16 +1857,13 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int cf = ct * W2_C + c0 + 16 * j;
-        fok[j] = cf < g.Cf;
-        gf[j] = fine + ((size_t)b * g.Cf + (fok[j] ? cf : g.Cf - 1)) * HWf + fi * 8;
+        fok[j] = cf < g.C;
+        gf[j] = fine + ((size_t)b * g.C + (fok[j] ? cf : g.C - 1)) * HWf + fi * 8;
     }
     const int f_wr = (c0 * g.pitch + 1 + fx) * 16;           // + j * 16 * pitch * 16
 
     f32x16 acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+    wrw_clear(acc);
 
     f32x4 ar[4], fw[4];
 #pragma unroll
@@ -2012,7 +1898,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
             *reinterpret_cast<u32x4*>(lds + W2_A_BYTES + a_wr + j * 8192) = vl;
         }
         const int u = 2 * (ylo + s * g.RS) + 2 + fr;          // fine row + 1: pair u >> 1, member u & 1
-        unsigned char* dst = ring + ((u >> 1) % g.NPAIR) * pair_bytes + (u & 1) * row_bytes + f_wr;
+        unsigned char* dst = ring + ((u >> 1) % g.NRING) * pair_bytes + (u & 1) * row_bytes + f_wr;
         const bool inside = u - 1 < Hf;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -2031,11 +1917,11 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
         const int m = i / (W2_C * cprf), rem = i - m * (W2_C * cprf);
         const int c = rem / cprf, x8 = rem - c * cprf;
         const int y = 2 * ylo - 1 + m, cf = ct * W2_C + c;
-        if (cf < g.Cf && y >= 0) {                           // else: the zeros stay
-            const float* src = fine + ((size_t)b * g.Cf + cf) * HWf + (size_t)y * Wf + x8 * 8;
+        if (cf < g.C && y >= 0) {                            // else: the zeros stay
+            const float* src = fine + ((size_t)b * g.C + cf) * HWf + (size_t)y * Wf + x8 * 8;
             u32x4 vh, vl;
             wx_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), &vh, &vl);
-            const int off = (ylo % g.NPAIR) * pair_bytes + m * row_bytes + (c * g.pitch + 1 + x8) * 16;
+            const int off = (ylo % g.NRING) * pair_bytes + m * row_bytes + (c * g.pitch + 1 + x8) * 16;
             *reinterpret_cast<u32x4*>(ring + off) = vh;
             *reinterpret_cast<u32x4*>(ring + g.ring_plane + off) = vl;
         }
@@ -2053,25 +1939,14 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
             const unsigned char* A = lds + ((a_row << 3) + (f8 ^ (a_row & 7))) * 16;
             const bf16x8 fah = *reinterpret_cast<const bf16x8*>(A), fal = *reinterpret_cast<const bf16x8*>(A + W2_A_BYTES);
             const int p0 = 16 * j;
-            const int rs = p0 >> g.wshift, ox0 = (p0 & (g.nw - 1)) + 8 * h;
+            const int rs = p0 >> g.wshift, ox0 = (p0 & (g.W - 1)) + 8 * h;
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri) {
                 const int u = 2 * (y0 + rs) + 2 * rh + ri;    // = fine row + 1 (tap row 2 rh + ri)
-                const unsigned char* X = ring + ((u >> 1) % g.NPAIR) * pair_bytes + (u & 1) * row_bytes + (r * g.pitch + 1 + (ox0 >> 2)) * 16;
+                const unsigned char* X = ring + ((u >> 1) % g.NRING) * pair_bytes + (u & 1) * row_bytes + (r * g.pitch + 1 + (ox0 >> 2)) * 16;
                 u32x4 f[2][4];                               // [plane][column tap]
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const unsigned char* Xp = X + pl * g.ring_plane;
-                    const u32x4 lo4 = *reinterpret_cast<const u32x4*>(Xp);
-                    const u32x4 hi4 = *reinterpret_cast<const u32x4*>(Xp + 16);
-                    const unsigned prev = *reinterpret_cast<const unsigned*>(Xp - 4);
-                    const unsigned next = *reinterpret_cast<const unsigned*>(Xp + 32);
-                    const unsigned d0 = lo4.x, d1 = lo4.y, d2 = lo4.z, d3 = lo4.w, d4 = hi4.x, d5 = hi4.y, d6 = hi4.z, d7 = hi4.w;
-                    f[pl][0] = u32x4{pack_hi(prev, d0), pack_hi(d1, d2), pack_hi(d3, d4), pack_hi(d5, d6)};
-                    f[pl][1] = u32x4{pack_lo(d0, d1), pack_lo(d2, d3), pack_lo(d4, d5), pack_lo(d6, d7)};
-                    f[pl][2] = u32x4{pack_hi(d0, d1), pack_hi(d2, d3), pack_hi(d4, d5), pack_hi(d6, d7)};
-                    f[pl][3] = u32x4{pack_lo(d1, d2), pack_lo(d3, d4), pack_lo(d5, d6), pack_lo(d7, next)};
-                }
+                for (int pl = 0; pl < 2; ++pl) wrw_pick_even_odd(X + pl * g.ring_plane, f[pl]);
                 // smallest terms first: lo(coarse) hi(fine), hi(coarse) lo(fine), hi hi; the four taps alternate so that no MFMA waits for its predecessor
 #pragma unroll
                 for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, f[0][t]), acc[ri * 4 + t], 0, 0, 0);
@@ -2095,55 +1970,78 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
     for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int kc = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            out[((size_t)(rh * 8 + t) * Kp + kc) * Cp + ct * W2_C + r] = acc[t][e];
+            const int ka = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)(rh * 8 + t) * Kp + ka) * Cp + ct * W2_C + r] = acc[t][e];
         }
 }
 
-static int x2_geometry(int B, int Kc, int Cf, int nh, int nw, X2Geom* g)
+// ---- the host side of the four weight-gradient kernels: one planner, one byte count, one launcher over WRW_KINDS ----
+static size_t wrw_lds_bytes(const WrwKind& k, const WrwGeom& g) { return 2 * (size_t)k.TK * k.PX * 2 + (k.split ? 2 : 1) * (size_t)g.ring_plane; }
+
+// The limits, before any launch (3x3: K = Ka, C = Cb, the image H x W; k4 s2: K = Kc, C = Cf, the coarse grid nh x nw).
+static int wrw_geometry(int kind, int B, int K, int C, int H, int W, WrwGeom* g)
 {
-    const char* who = "split-bf16 4x4 stride-2 weight gradient";
-    if (nw == 128)
-        return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width 128: the ring of whole fine rows for a half-row stage needs 176128 bytes of LDS (16, 32 or 64)", who);
-    if (nw != 16 && nw != 32 && nw != 64) return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width %d (16, 32 or 64)", who, nw);
-    const int RS = W2_PX / nw;
-    if (nh % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d coarse rows are not a multiple of the %d rows of a stage", who, nh, RS);
-    g->B = B; g->Kc = Kc; g->Cf = Cf; g->nh = nh; g->nw = nw;
-    g->wshift = cb_wshift(nw);
-    g->RS = RS; g->NPAIR = RS + 1; g->pitch = 2 * nw / 8 + 3;
-    g->ktiles = (Kc + W2_K - 1) / W2_K; g->ctiles = (Cf + W2_C - 1) / W2_C;
-    g->ring_plane = g->NPAIR * 2 * W2_C * g->pitch * 16;
-    if (2 * W2_A_BYTES + 2 * g->ring_plane > CB_LDS_MAX) return fail(IPSR_ERR_UNSUPPORTED, "%s: the row ring of a %d-wide grid does not fit the LDS plan", who, nw);
-    cb_cut_runs(g->ktiles * g->ctiles, B, nh / RS, &g->stages_per_wg, &g->nsplit);
+    const WrwKind& k = WRW_KINDS[kind];
+    if (kind == WRW_S2_SPLIT && W == 128)
+        return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width 128: the ring of whole fine rows for a half-row stage needs 176128 bytes of LDS (16, 32 or 64)", k.who);
+    if (W != 16 && W != 32 && W != 64 && W != k.wmax) return fail(IPSR_ERR_UNSUPPORTED, k.width_fmt, k.who, W);
+    const int RS = k.PX / W;
+    if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, k.rows_fmt, k.who, H, RS);
+    g->B = B; g->K = K; g->C = C; g->H = H; g->W = W;
+    g->wshift = cb_wshift(W);
+    g->RS = RS; g->NRING = k.ring_mul * RS + k.ring_add; g->pitch = k.wscale * W / 8 + 3;
+    g->ktiles = (K + k.TK - 1) / k.TK; g->ctiles = (C + k.TC - 1) / k.TC;
+    const int entry_slots = k.wscale * k.TC * g->pitch;       // 16-byte slots of a ring entry
+    g->ring_plane = g->NRING * entry_slots * 16;
+    if (wrw_lds_bytes(k, *g) > (size_t)CB_LDS_MAX || (k.dma_add >= 0 && (RS + k.dma_add) * entry_slots > 5 * WB_THREADS))
+        return fail(IPSR_ERR_UNSUPPORTED, k.ring_fmt, k.who, W);
+    cb_cut_runs(g->ktiles * g->ctiles, B, H / RS, &g->stages_per_wg, &g->nsplit);
     return IPSR_OK;
 }
 
-// the partial slabs, nothing else
-size_t conv_bf16x3_wrw_s2_ws_bytes(int B, int Kc, int Cf, int nh, int nw)
+// [bf16: the zero page |] the partial slabs
+static size_t wrw_ws_bytes(int kind, int B, int K, int C, int H, int W)
 {
-    X2Geom g;
-    if (x2_geometry(B, Kc, Cf, nh, nw, &g) != IPSR_OK) return 0;
-    return (size_t)g.nsplit * 16 * g.ktiles * W2_K * g.ctiles * W2_C * 4;
+    const WrwKind& k = WRW_KINDS[kind];
+    WrwGeom g;
+    if (wrw_geometry(kind, B, K, C, H, W, &g) != IPSR_OK) return 0;
+    return (k.split ? 0 : 256) + (size_t)g.nsplit * k.NT * g.ktiles * k.TK * g.ctiles * k.TC * 4;
 }
 
-// fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw] fp32 -> dW [Kc][Cf][4][4] fp32
-int launch_conv_bf16x3_wrw_s2(const float* fine, const float* coarse, float* dW, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, hipStream_t st)
+// a [B,K,H,W], w [B,C,wscale H,wscale W] (bf16, or fp32 for the split kinds) -> dW [K][C][NT] fp32
+template <int KIND>
+static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int C, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
 {
-    X2Geom g;
-    if (int rc = x2_geometry(B, Kc, Cf, nh, nw, &g)) return rc;
-    const size_t need = conv_bf16x3_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 4x4 stride-2 weight gradient: workspace %zu < %zu", ws_bytes, need);
-    float* slabs = static_cast<float*>(ws);
-    const size_t smem = 2 * (size_t)W2_A_BYTES + 2 * (size_t)g.ring_plane;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
-    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "conv_bf16x3_wrw_s2_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", CB_LDS_MAX, hipGetErrorString(e));
+    constexpr WrwKind k = WRW_KINDS[KIND];
+    WrwGeom g;
+    if (int rc = wrw_geometry(KIND, B, K, C, H, W, &g)) return rc;
+    const size_t need = wrw_ws_bytes(KIND, B, K, C, H, W);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "%s: workspace %zu < %zu", k.who, ws_bytes, need);
+    const uint4* zero_page = static_cast<const uint4*>(ws);   // bf16 kinds: what the LDS-DMA reads outside the image and past the channels
+    float* slabs = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + (k.split ? 0 : 256));
+    if (!k.split && hipMemsetAsync(ws, 0, 64, st) != hipSuccess) return fail(IPSR_ERR_LAUNCH, "%s: hipMemsetAsync failed", k.who);
     const unsigned grid = (unsigned)(g.ktiles * g.ctiles * g.nsplit);
+    const size_t smem = wrw_lds_bytes(k, g);
+    const void* kernel;
+    if constexpr (KIND == WRW_3X3) kernel = reinterpret_cast<const void*>(&conv_bf16_wrw_kernel);
+    else if constexpr (KIND == WRW_3X3_SPLIT) kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_kernel);
+    else if constexpr (KIND == WRW_S2) kernel = reinterpret_cast<const void*>(&conv_bf16_wrw_s2_kernel);
+    else kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel);
+    if (int rc = cb_raise_lds(kernel, k.kernel)) return rc;
     profile_mark_start(st, 4);
-    conv_bf16x3_wrw_s2_kernel<<<grid, 512, smem, st>>>(coarse, fine, g, slabs);
-    profile_mark_stop(st, 4, 3.0 * 2.0 * 16.0 * (double)(g.ktiles * W2_K) * (g.ctiles * W2_C) * B * nh * nw, 2.0 * 16.0 * (double)Kc * Cf * B * nh * nw);
-    if (int rc = check_launch("conv_bf16x3_wrw_s2_kernel")) return rc;
-    cb_slab_reduce_kernel<16><<<dim3(cdiv(Cf, 256), Kc), 256, 0, st>>>(slabs, g.nsplit, Kc, Cf, g.ktiles * W2_K, g.ctiles * W2_C, dW);
-    return check_launch("conv_bf16_wrw_s2_reduce_kernel");
+    if constexpr (KIND == WRW_3X3)
+        conv_bf16_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
+    else if constexpr (KIND == WRW_3X3_SPLIT)
+        conv_bf16x3_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    else if constexpr (KIND == WRW_S2)
+        conv_bf16_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
+    else
+        conv_bf16x3_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    const double px = (double)B * H * W;
+    profile_mark_stop(st, 4, (k.split ? 3.0 : 1.0) * 2.0 * k.NT * (double)(g.ktiles * k.TK) * (g.ctiles * k.TC) * px, 2.0 * k.NT * (double)K * C * px);
+    if (int rc = check_launch(k.kernel)) return rc;
+    cb_slab_reduce_kernel<k.NT><<<dim3(cdiv(C, 256), K), 256, 0, st>>>(slabs, g.nsplit, K, C, g.ktiles * k.TK, g.ctiles * k.TC, dW);
+    return check_launch(k.reduce);
 }
 
 }  // namespace ipsr
@@ -2244,7 +2142,7 @@ int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float*
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
 {
     if (!cb_dims_ok(true, {B, Kc, Cf, nh, nw})) return 0;
-    return conv_bf16_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
+    return wrw_ws_bytes(WRW_S2, B, Kc, Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
@@ -2252,13 +2150,13 @@ int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int
     if (int rc = cb_null("ipsr_conv4x4s2_bf16_wrw", {fine, coarse, dw, ws})) return rc;
     if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
-    return launch_conv_bf16_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    return launch_wrw<WRW_S2>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
 {
     if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes", true, {B, Kc, Cf, nh, nw})) return 0;
-    return conv_bf16x3_wrw_s2_ws_bytes(B, Kc, Cf, nh, nw);
+    return wrw_ws_bytes(WRW_S2_SPLIT, B, Kc, Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
@@ -2266,19 +2164,19 @@ int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw,
     if (int rc = cb_null("ipsr_conv4x4s2_bf16x3_wrw", {fine, coarse, dw, ws})) return rc;
     if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16x3_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
-    return launch_conv_bf16x3_wrw_s2(fine, coarse, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    return launch_wrw<WRW_S2_SPLIT>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)
 {
     if (!cb_dims_ok(true, {B, Cin, Cout, H, W})) return 0;
-    return transposed ? conv_bf16_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16_wrw_ws_bytes(B, Cout, Cin, H, W);
+    return transposed ? wrw_ws_bytes(WRW_3X3, B, Cin, Cout, H, W) : wrw_ws_bytes(WRW_3X3, B, Cout, Cin, H, W);
 }
 
 size_t ipsr_conv3x3_bf16x3_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)
 {
     if (cb_bad_dims("ipsr_conv3x3_bf16x3_wrw_workspace_bytes", true, {B, Cin, Cout, H, W})) return 0;
-    return transposed ? conv_bf16x3_wrw_ws_bytes(B, Cin, Cout, H, W) : conv_bf16x3_wrw_ws_bytes(B, Cout, Cin, H, W);
+    return transposed ? wrw_ws_bytes(WRW_3X3_SPLIT, B, Cin, Cout, H, W) : wrw_ws_bytes(WRW_3X3_SPLIT, B, Cout, Cin, H, W);
 }
 
 int ipsr_conv3x3_bf16_wrw(int form, const void* x, const void* dy, float* dw, int B, int Cin, int H, int W, int Cout,
@@ -2292,14 +2190,9 @@ int ipsr_conv3x3_bf16_wrw(int form, const void* x, const void* dy, float* dw, in
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool transposed = form & 1;
     // Conv2d: dW[co][ci][t] = sum dy[co][p] x[ci][p + t];  ConvTranspose2d: dW[ci][co][t] = sum x[ci][p] dy[co][p + t]
-    if (form >= 2) {
-        const float* xf = static_cast<const float*>(x);
-        const float* dyf = static_cast<const float*>(dy);
-        if (transposed) return launch_conv_bf16x3_wrw(xf, dyf, dw, B, Cin, Cout, H, W, ws, ws_bytes, st);
-        return launch_conv_bf16x3_wrw(dyf, xf, dw, B, Cout, Cin, H, W, ws, ws_bytes, st);
-    }
-    if (transposed) return launch_conv_bf16_wrw(x, dy, dw, B, Cin, Cout, H, W, ws, ws_bytes, st);
-    return launch_conv_bf16_wrw(dy, x, dw, B, Cout, Cin, H, W, ws, ws_bytes, st);
+    const auto launch = form >= 2 ? launch_wrw<WRW_3X3_SPLIT> : launch_wrw<WRW_3X3>;
+    if (transposed) return launch(x, dy, dw, B, Cin, Cout, H, W, ws, ws_bytes, st);
+    return launch(dy, x, dw, B, Cout, Cin, H, W, ws, ws_bytes, st);
 }
 
 }  // extern "C"

@@ -15,18 +15,18 @@ Weight-gradient plans: RS, groups (stages per image), spw0 (the fill-the-chip va
     (the `while (groups % spw)` loop ran), nsplit (slabs), ktiles, ctiles.
 """
 
-CB_K, CB_P, CB_C, CB_THREADS = 128, 256, 16, 512          # conv_bf16.hip:40
-CB_LDS_MAX = 160 * 1024                                   # :45
-WB_K, WB_C, WB_THREADS, WB_PX = 128, 64, 512, 128         # :595
-WB_X_BYTES = 96 * 1024                                    # :597
-W2_K, W2_C, W2_PX = 128, 32, 64                           # :820
+CB_K, CB_P, CB_C, CB_THREADS = 128, 256, 16, 512          # conv_bf16.hip: CB_K, CB_P, CB_C, CB_THREADS
+CB_LDS_MAX = 160 * 1024                                   # CB_LDS_MAX
+WB_K, WB_C, WB_THREADS, WB_PX = 128, 64, 512, 128         # WRW_KINDS[WRW_3X3] (TK, TC, PX), WB_THREADS
+WB_X_BYTES = 96 * 1024                                    # the ring's share: CB_LDS_MAX less the two a buffers
+W2_K, W2_C, W2_PX = 128, 32, 64                           # WRW_KINDS[WRW_S2] (TK, TC, PX)
 
 
-def cb_tr_max(ptile):                                     # :43
+def cb_tr_max(ptile):                                     # cb_tr_max
     return 6 if ptile == 256 else 10
 
 
-def cb_xj(ptile):                                         # :44
+def cb_xj(ptile):                                         # cb_xj
     return 3 if ptile == 256 else 5
 
 
@@ -39,7 +39,7 @@ def cdiv(a, b):
 
 
 def cb_lane_grid(Hl, Wl, ptile):
-    """:353-362 -> (R, None) or (None, message fragment)."""
+    """cb_lane_grid -> (R, None) or (None, message fragment)."""
     if Wl not in (16, 32, 64, 128, 256):
         return None, "grid width %d" % Wl
     R = ptile // Wl
@@ -49,37 +49,37 @@ def cb_lane_grid(Hl, Wl, ptile):
 
 
 def cb_finish(g):
-    """:364-390: k tile, the reduction cut, the LDS plan.  g holds B, C, K, Hl, R, Win, NR, PW, nsub, nphase, ntap, ptile."""
+    """cb_finish: k tile, the reduction cut, the LDS plan.  g holds B, C, K, Hl, R, Win, NR, PW, nsub, nphase, ntap, ptile."""
     g["NPOS"] = g["NR"] * g["PW"]
-    g["kt"] = 64 if g["K"] <= 64 else CB_K                                               # :367
+    g["kt"] = 64 if g["K"] <= 64 else CB_K                                               # cb_finish
     g["ktiles"] = cdiv(g["K"], g["kt"])
     g["tiles_per_img"] = g["Hl"] // g["R"]
-    g["ptiles"] = g["B"] * g["tiles_per_img"]                                            # :369
+    g["ptiles"] = g["B"] * g["tiles_per_img"]                                            # cb_finish
     g["nstage"] = (g["C"] // CB_C) * g["nsub"]
-    wgs, nblocks = g["ktiles"] * g["nphase"] * g["ptiles"], g["C"] // CB_C               # :374
+    wgs, nblocks = g["ktiles"] * g["nphase"] * g["ptiles"], g["C"] // CB_C               # cb_cut_reduction
     ns = 1
-    if wgs < 128 and nblocks >= 8:                                                       # :376
+    if wgs < 128 and nblocks >= 8:                                                       # cb_cut_reduction
         ns = min(min(4, nblocks // 4), cdiv(256, wgs))
-    bps = cdiv(nblocks, max(ns, 1))                                                      # :377
-    g["nsplit"] = cdiv(nblocks, bps)                                                     # :378
+    bps = cdiv(nblocks, max(ns, 1))                                                      # cb_cut_reduction
+    g["nsplit"] = cdiv(nblocks, bps)                                                     # cb_cut_reduction
     g["sps"] = bps * g["nsub"]
     g["wgs"], g["nblocks"], g["bps"] = wgs, nblocks, bps
     g["last_bps"] = nblocks - (g["nsplit"] - 1) * bps
     g["uneven"] = g["last_bps"] != bps
-    planes = g["nsub"]                                                                   # :381
+    planes = g["nsub"]                                                                   # cb_finish
     g["a_bytes"] = g["ntap"] * 2 * g["kt"] * 16
     g["t_bytes"] = align_up(planes * 2 * g["NPOS"] * 16, 256)
     g["raw_bytes"] = align_up(CB_C * g["NR"] * g["Win"] * 2, 1024)
-    g["raw1"] = 2 * (g["a_bytes"] + g["t_bytes"] + g["raw_bytes"]) > CB_LDS_MAX          # :385
+    g["raw1"] = 2 * (g["a_bytes"] + g["t_bytes"] + g["raw_bytes"]) > CB_LDS_MAX          # cb_finish
     g["lds"] = 2 * (g["a_bytes"] + g["t_bytes"]) + (1 if g["raw1"] else 2) * g["raw_bytes"]
     if g["lds"] > CB_LDS_MAX or 4 * g["NR"] * (g["Win"] // 16) > 32 * cb_tr_max(g["ptile"]) or \
-            CB_C * g["NR"] * (g["Win"] // 8) > cb_xj(g["ptile"]) * CB_THREADS:           # :386-387
+            CB_C * g["NR"] * (g["Win"] // 8) > cb_xj(g["ptile"]) * CB_THREADS:           # cb_finish
         return None, "a tile of %d rows x %d does not fit the LDS plan" % (g["NR"], g["Win"])
     return g, None
 
 
 def cb_geometry_p(B, C, K, H, W, ptile):
-    """:393-403, k3 s1 p1 at one tile size."""
+    """cb_geometry_p, k3 s1 p1 at one tile size."""
     if C % CB_C != 0:
         return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
     R, msg = cb_lane_grid(H, W, ptile)
@@ -90,7 +90,7 @@ def cb_geometry_p(B, C, K, H, W, ptile):
 
 
 def _two_tiles(K, geometry_p):
-    """:406-410 / :414-418: <= 64 produced channels try the 512-pixel tile first; any refusal falls back to 256, silently."""
+    """cb_geometry / cb_geometry_s2: <= 64 produced channels try the 512-pixel tile first; any refusal falls back to 256, silently."""
     p512 = None
     if K <= 64:
         g, msg = geometry_p(2 * CB_P)
@@ -105,13 +105,13 @@ def _two_tiles(K, geometry_p):
 
 
 def cb_geometry(B, C, K, H, W, why=False):
-    """:406-410: k3 s1 p1, C reduction channels -> K produced."""
+    """cb_geometry: k3 s1 p1, C reduction channels -> K produced."""
     g, msg = _two_tiles(K, lambda p: cb_geometry_p(B, C, K, H, W, p))
     return (g, msg) if why else g
 
 
 def cb_geometry_s2_p(form, B, C, K, nh, nw, ptile):
-    """:420-453, k4 s2 p1 at one tile size.  form 0: fine -> coarse (C = Cf, K = Kc); 1: coarse -> fine (C = Kc, K = Cf)."""
+    """cb_geometry_s2_p and cb_s2_form, k4 s2 p1 at one tile size.  form 0: fine -> coarse (C = Cf, K = Kc); 1: coarse -> fine (C = Kc, K = Cf)."""
     if C % CB_C != 0:
         return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
     R, msg = cb_lane_grid(nh, nw, ptile)
@@ -126,24 +126,24 @@ def cb_geometry_s2_p(form, B, C, K, nh, nw, ptile):
 
 
 def cb_geometry_s2(form, B, C, K, nh, nw, why=False):
-    """:414-418."""
+    """cb_geometry_s2."""
     g, msg = _two_tiles(K, lambda p: cb_geometry_s2_p(form, B, C, K, nh, nw, p))
     return (g, msg) if why else g
 
 
-def cb_partial_bytes(g):                                  # :456
+def cb_partial_bytes(g):                                  # cb_partial_bytes
     return align_up(g["nsplit"] * g["B"] * g["K"] * g["Hout"] * g["Wout"] * 4, 256) if g["nsplit"] > 1 else 0
 
 
 def cb_ws_bytes(g):
-    """:472-484: zero page + packed weights + fp32 partials of a cut reduction; 0 for a refused shape."""
+    """conv_bf16_ws_bytes / conv_bf16_s2_ws_bytes: zero page + packed weights + fp32 partials of a cut reduction; 0 for a refused shape."""
     if g is None:
         return 0
     return 256 + g["ktiles"] * g["nphase"] * g["nstage"] * g["ntap"] * 2 * g["kt"] * 16 + cb_partial_bytes(g)
 
 
 def _spw(tiles, B, groups):
-    """:771-777 / :998-1004: one round of one workgroup per CU, lowered until it divides the stages of an image."""
+    """cb_cut_runs: one round of one workgroup per CU, lowered until it divides the stages of an image."""
     spw0 = (tiles * B * groups + 255) // 256
     spw = min(max(spw0, 1), groups)
     lowered = groups % spw != 0
@@ -153,7 +153,7 @@ def _spw(tiles, B, groups):
 
 
 def wb_geometry(B, Ka, Cb, H, W, why=False):
-    """:758-779: k3 weight gradient dW[Ka][Cb][3][3]."""
+    """wrw_geometry on WRW_KINDS[WRW_3X3]: k3 weight gradient dW[Ka][Cb][3][3]."""
     def out(g, msg=None):
         return (g, msg) if why else g
     if W not in (16, 32, 64, 128):
@@ -163,7 +163,7 @@ def wb_geometry(B, Ka, Cb, H, W, why=False):
         return out(None, "%d rows are not a multiple of %d" % (H, RS))
     NSLOT, pitch = 2 * RS + 2, W // 8 + 3
     ktiles, ctiles = cdiv(Ka, WB_K), cdiv(Cb, WB_C)
-    if NSLOT * WB_C * pitch * 16 > WB_X_BYTES or RS * WB_C * pitch > 5 * WB_THREADS:     # :767 (never true for the four widths)
+    if NSLOT * WB_C * pitch * 16 > WB_X_BYTES or RS * WB_C * pitch > 5 * WB_THREADS:     # the fit check of wrw_geometry (never true for the four widths)
         return out(None, "the row ring")
     groups = H // RS
     spw0, spw, lowered = _spw(ktiles * ctiles, B, groups)
@@ -171,12 +171,12 @@ def wb_geometry(B, Ka, Cb, H, W, why=False):
                     ktiles=ktiles, ctiles=ctiles))
 
 
-def wb_ws_bytes(g):                                       # :781-786
+def wb_ws_bytes(g):                                       # wrw_ws_bytes
     return 0 if g is None else 256 + g["nsplit"] * 9 * g["ktiles"] * WB_K * g["ctiles"] * WB_C * 4
 
 
 def w2_geometry(B, Kc, Cf, nh, nw, why=False):
-    """:988-1006: k4 s2 p1 weight gradient dW[Kc][Cf][4][4]."""
+    """wrw_geometry on WRW_KINDS[WRW_S2]: k4 s2 p1 weight gradient dW[Kc][Cf][4][4]."""
     def out(g, msg=None):
         return (g, msg) if why else g
     if nw not in (16, 32, 64):
@@ -186,7 +186,7 @@ def w2_geometry(B, Kc, Cf, nh, nw, why=False):
         return out(None, "%d coarse rows are not a multiple of %d" % (nh, RS))
     pitch = 2 * nw // 8 + 3
     ktiles, ctiles = cdiv(Kc, W2_K), cdiv(Cf, W2_C)
-    if (RS + 1) * 2 * W2_C * pitch > 5 * 512:                                            # :997 (never true for the three widths)
+    if (RS + 1) * 2 * W2_C * pitch > 5 * 512:                                            # the fit check of wrw_geometry (never true for the three widths)
         return out(None, "row ring")
     groups = nh // RS
     spw0, spw, lowered = _spw(ktiles * ctiles, B, groups)
@@ -194,11 +194,11 @@ def w2_geometry(B, Kc, Cf, nh, nw, why=False):
                     ktiles=ktiles, ctiles=ctiles))
 
 
-def w2_ws_bytes(g):                                       # :1008-1013
+def w2_ws_bytes(g):                                       # wrw_ws_bytes
     return 0 if g is None else 256 + g["nsplit"] * 16 * g["ktiles"] * W2_K * g["ctiles"] * W2_C * 4
 
 
-# ---- the C entries' argument orders (conv_bf16.hip:1044-1049, :1074-1078, :1092-1096, :1108-1112) ------------------------------------
+# ---- the C entries' argument orders (conv_bf16.hip: ipsr_conv3x3_bf16_packed, ipsr_conv4x4s2_bf16, ipsr_conv4x4s2_bf16_wrw, ipsr_conv3x3_bf16_wrw) ------------------------------------
 def k3_plan(op, B, Cin, H, W, Cout, why=False):
     """ipsr_conv3x3_bf16: op 0 Conv2d forward, 1 its input gradient, 2 ConvTranspose2d forward, 3 its input gradient."""
     fwd = op in (0, 2)
@@ -368,65 +368,65 @@ def _multi(p):
 
 
 VARIANTS = (
-    ("S1 KT128 P256, 3 tiles per image (W 32)", ":134, :369", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["tiles_per_img"] == 3 and p["Wl"] == 32,
+    ("S1 KT128 P256, 3 tiles per image (W 32)", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["tiles_per_img"] == 3 and p["Wl"] == 32,
      (("k3_c64_24x32_k160_b3", "fwd"),)),
-    ("S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128", ":134, :369", lambda p: p["mode"] == "S1" and p["kt"] == 128 and _multi(p) and p["Wl"] in (64, 128),
+    ("S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and _multi(p) and p["Wl"] in (64, 128),
      (("k3_c64_12x64_k128_b2", "fwd"), ("k3_c32_10x128_k80_b1", "fwd"))),
-    ("S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image", ":406-410, :385", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["Wl"] == 256 and p["R"] == 1 and p["raw1"] and p["tiles_per_img"] == 6,
+    ("S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image", "cb_lane_grid, cb_finish raw1", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["Wl"] == 256 and p["R"] == 1 and p["raw1"] and p["tiles_per_img"] == 6,
      (("k3_c32_6x256_k144_b2", "fwd"),)),
-    ("S1 KT64 P512 at W 16, 3 tiles per image", ":408", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 16 and p["tiles_per_img"] == 3,
+    ("S1 KT64 P512 at W 16, 3 tiles per image", "cb_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 16 and p["tiles_per_img"] == 3,
      (("k3_c48_96x16_k32_b2", "fwd"), ("k3_c48_96x16_k32_b2", "dx"))),
-    ("S1 KT64 P512 at W 32, 3 tiles per image", ":408", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+    ("S1 KT64 P512 at W 32, 3 tiles per image", "cb_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 32 and p["tiles_per_img"] == 3,
      (("k3T_c32_48x32_k64_b1", "fwd"), ("k3T_c32_48x32_k64_b1", "dx"))),
-    ("S1 KT64, P512 refused by the rows -> P256", ":408, :358", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["p512"] == "rows",
+    ("S1 KT64, P512 refused by the rows -> P256", "cb_geometry, cb_lane_grid", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["p512"] == "rows",
      (("k3_c64_24x32_k160_b3", "dx"), ("k3_c64_12x64_k128_b2", "dx"), ("k3_c32_10x128_k80_b1", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
-    ("S1 KT64 P256, reduction cut in 2 / in 4", ":373-380", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] in (2, 4),
+    ("S1 KT64 P256, reduction cut in 2 / in 4", "cb_cut_reduction", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] in (2, 4),
      (("k3_c64_24x32_k160_b3", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
-    ("S1 KT64 P512, cut in 3 uneven (5 + 5 + 3 blocks)", ":373-380", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and (p["nsplit"], p["bps"], p["last_bps"]) == (3, 5, 3),
+    ("S1 KT64 P512, cut in 3 uneven (5 + 5 + 3 blocks)", "cb_cut_reduction", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and (p["nsplit"], p["bps"], p["last_bps"]) == (3, 5, 3),
      (("k3T_c208_32x16_k48_b1", "fwd"),)),
-    ("S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)", ":373-380, :385", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and (p["nsplit"], p["bps"], p["last_bps"]) == (2, 5, 4),
+    ("S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)", "cb_cut_reduction, cb_finish raw1", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and (p["nsplit"], p["bps"], p["last_bps"]) == (2, 5, 4),
      (("k3_c32_6x256_k144_b2", "dx"),)),
-    ("F2C KT64 P512 raw1 at nw 16", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 16,
+    ("F2C KT64 P512 raw1 at nw 16", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 16,
      (("s2_64_32_32x16_b2", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 32, 3 tiles per image", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+    ("F2C KT64 P512 raw1 at nw 32, 3 tiles per image", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 32 and p["tiles_per_img"] == 3,
      (("s2_48_32_48x32_b1", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 64, 3 tiles per image", ":414-418, :385", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 64 and p["tiles_per_img"] == 3,
+    ("F2C KT64 P512 raw1 at nw 64, 3 tiles per image", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 64 and p["tiles_per_img"] == 3,
      (("s2_16_16_24x64_b2", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)", ":414-418, :385-386", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 156672,
+    ("F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 156672,
      (("s2_48_16_4x128_b1", "f2c"), ("s2_32_80_4x128_b1", "f2c"))),
-    ("F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image", ":385-386", lambda p: p["mode"] == "F2C" and p["kt"] == 128 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 139776 and p["tiles_per_img"] == 3,
+    ("F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image", "cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 128 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 139776 and p["tiles_per_img"] == 3,
      (("s2_128_64_6x128_b1", "f2c"),)),
-    ("F2C cut in 2 uneven, a run = bps x nsub stages (10 + 8)", ":373-380", lambda p: p["mode"] == "F2C" and p["nsub"] == 2 and (p["nsplit"], p["sps"], p["last_bps"] * p["nsub"]) == (2, 10, 8),
+    ("F2C cut in 2 uneven, a run = bps x nsub stages (10 + 8)", "cb_cut_reduction", lambda p: p["mode"] == "F2C" and p["nsub"] == 2 and (p["nsplit"], p["sps"], p["last_bps"] * p["nsub"]) == (2, 10, 8),
      (("s2_128_144_16x16_b1", "f2c"),)),
-    ("F2C KT64 cut in 3 uneven", ":373-380", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
+    ("F2C KT64 cut in 3 uneven", "cb_cut_reduction", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
      (("s2_64_208_16x16_b1", "f2c"),)),
-    ("F2C 3 tiles per image (KT128)", ":134, :369", lambda p: p["mode"] == "F2C" and p["tiles_per_img"] == 3 and p["kt"] == 128,
+    ("F2C 3 tiles per image (KT128)", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "F2C" and p["tiles_per_img"] == 3 and p["kt"] == 128,
      (("s2_96_48_24x32_b2", "f2c"),)),
-    ("C2F KT64 P512 at nw 128", ":414-418", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 128,
+    ("C2F KT64 P512 at nw 128", "cb_geometry_s2", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 128,
      (("s2_48_16_4x128_b1", "c2f"),)),
-    ("C2F KT128 P256 at nw 128", ":414-418", lambda p: p["mode"] == "C2F" and p["kt"] == 128 and p["Wl"] == 128,
+    ("C2F KT128 P256 at nw 128", "cb_geometry_s2", lambda p: p["mode"] == "C2F" and p["kt"] == 128 and p["Wl"] == 128,
      (("s2_32_80_4x128_b1", "c2f"),)),
-    ("C2F KT64 P512 raw1 at nw 256", ":414-418, :385", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 256,
+    ("C2F KT64 P512 raw1 at nw 256", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 256,
      (("s2_16_16_2x256_b1", "c2f"),)),
-    ("C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image", ":414-418, :285-288", lambda p: p["mode"] == "C2F" and p["raw1"] and p["Wl"] == 256 and p["nstage"] == 3 and p["nsplit"] == 1 and p["tiles_per_img"] == 2,
+    ("C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image", "cb_geometry_s2, the raw1 stage loop", lambda p: p["mode"] == "C2F" and p["raw1"] and p["Wl"] == 256 and p["nstage"] == 3 and p["nsplit"] == 1 and p["tiles_per_img"] == 2,
      (("s2_48_16_4x256_b2", "c2f"),)),
-    ("C2F KT64 P256 (rows) cut in 2, 3 tiles per image", ":373-380", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] == 2 and p["tiles_per_img"] == 3,
+    ("C2F KT64 P256 (rows) cut in 2, 3 tiles per image", "cb_cut_reduction", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] == 2 and p["tiles_per_img"] == 3,
      (("s2_128_64_6x128_b1", "c2f"),)),
-    ("C2F KT64 cut in 3 uneven", ":373-380", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
+    ("C2F KT64 cut in 3 uneven", "cb_cut_reduction", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
      (("s2_208_64_16x16_b1", "c2f"),)),
-    ("C2F 3 tiles per image, both row phases", ":134, :369", lambda p: p["mode"] == "C2F" and p["tiles_per_img"] == 3 and p["nphase"] == 2,
+    ("C2F 3 tiles per image, both row phases", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "C2F" and p["tiles_per_img"] == 3 and p["nphase"] == 2,
      (("s2_96_48_24x32_b2", "c2f"), ("s2_48_32_48x32_b1", "c2f"))),
-    ("k3 weight gradient: groups 6 / 10 / 12 (not a power of two)", ":771", lambda p: "RS" in p and "Ka" in p and p["groups"] in (6, 10, 12),
+    ("k3 weight gradient: groups 6 / 10 / 12 (not a power of two)", "wrw_geometry", lambda p: "RS" in p and "Ka" in p and p["groups"] in (6, 10, 12),
      (("k3_c64_24x32_k160_b3", "dw"), ("k3_c32_10x128_k80_b1", "dw"), ("k3_c48_96x16_k32_b2", "dw"))),
-    ("k3 weight gradient: stages_per_wg lowered by the loop (4 -> 3), 1 < spw < groups", ":772-777", lambda p: "Ka" in p and p["lowered"] and 1 < p["spw"] < p["groups"],
+    ("k3 weight gradient: stages_per_wg lowered by the loop (4 -> 3), 1 < spw < groups", "cb_cut_runs", lambda p: "Ka" in p and p["lowered"] and 1 < p["spw"] < p["groups"],
      (("k3w_ka512_cb256_48x16_b9", "dw"),)),
-    ("k3 weight gradient: spw = groups, ONE slab", ":772-777", lambda p: "Ka" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
+    ("k3 weight gradient: spw = groups, ONE slab", "cb_cut_runs", lambda p: "Ka" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
      (("k3w_ka1024_cb1088_16x16_b1", "dw"),)),
-    ("k4 s2 weight gradient: groups 12 / 24 (not a power of two)", ":998", lambda p: "Kc" in p and p["groups"] in (12, 24),
+    ("k4 s2 weight gradient: groups 12 / 24 (not a power of two)", "wrw_geometry", lambda p: "Kc" in p and p["groups"] in (12, 24),
      (("s2_96_48_24x32_b2", "dw"), ("s2_48_32_48x32_b1", "dw"))),
-    ("k4 s2 weight gradient: spw = groups 12, one slab per image", ":998-1004", lambda p: "Kc" in p and p["spw"] == p["groups"] == 12 and p["nsplit"] == p["B"],
+    ("k4 s2 weight gradient: spw = groups 12, one slab per image", "cb_cut_runs", lambda p: "Kc" in p and p["spw"] == p["groups"] == 12 and p["nsplit"] == p["B"],
      (("s2w_512_512_24x32_b5", "dw"),)),
-    ("k4 s2 weight gradient: ONE slab", ":998-1004", lambda p: "Kc" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
+    ("k4 s2 weight gradient: ONE slab", "cb_cut_runs", lambda p: "Kc" in p and p["nsplit"] == 1 and p["spw"] == p["groups"] > 1,
      (("s2w_512_1056_8x16_b1", "dw"),)),
 )
 

@@ -1,4 +1,4 @@
-"""The launch plan of the split-bf16 weight gradient of the k4 s2 p1 layers on fp32 tensors (csrc/conv_bf16.hip, x2_geometry), restated in
+"""The launch plan of the split-bf16 weight gradient of the k4 s2 p1 layers on fp32 tensors (csrc/conv_bf16.hip, wrw_geometry on WRW_KINDS[WRW_S2_SPLIT]), restated in
 Python, and the GPU cases of tests/test_gpu_bf16x3_s2_wrw.py with the variant each must reach.  No GPU, no library:
 tests/test_bf16x3_s2_wrw_abi.py compares the library's workspace query against `ws` here.
 

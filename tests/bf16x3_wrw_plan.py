@@ -1,4 +1,4 @@
-"""The launch plan of the split-bf16 weight gradient on fp32 tensors (csrc/conv_bf16.hip, wx_geometry), restated in Python, and the GPU
+"""The launch plan of the split-bf16 weight gradient on fp32 tensors (csrc/conv_bf16.hip, wrw_geometry on WRW_KINDS[WRW_3X3_SPLIT]), restated in Python, and the GPU
 cases of tests/test_gpu_bf16x3_wrw.py with the variant each must reach.  No GPU, no library: tests/test_bf16x3_wrw_abi.py compares the
 library's workspace query against `ws` here.
 

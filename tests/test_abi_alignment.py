@@ -37,21 +37,22 @@ def _P(p, name, slot):
 # Offsets are the largest misalignment below the requirement that is still a whole element (4 bytes of fp32, 2 of bf16 -> we use
 # 4 or 8 bytes), so a refusal keyed on the element size alone would not pass.
 CASES = [
-    # conv_bf16.hip: A / input fragments are 16-byte reads (:706, :930); the bf16 tile leaves as uint4 rows (:347); the split
-    # reduction reads and stores 4-element vectors (:464-469)
+    # conv_bf16.hip: A / input fragments are 16-byte reads (load_x of conv_bf16x3_kernel and conv_bf16x3_s2_kernel, the LDS-DMA of
+    # conv_bf16_kernel); the bf16 tile leaves as uint4 rows (conv_bf16_kernel's epilogue); the split reduction reads and stores 4-element
+    # vectors (cb_split_reduce_kernel)
     ("ipsr_conv3x3_bf16_packed",
      lambda p: (0, _P(p, "in", 0), _P(p, "weight", 1), _P(p, "out", 2), 2, 32, 16, 16, 48, 1, 0, _P(p, "ws", 3), WS, None),
-     [("in", 8, "conv_bf16.hip:706 16-byte fragment reads"), ("out", 8, "conv_bf16.hip:347 uint4 store of the bf16 tile"),
-      ("out", 4, "conv_bf16.hip:347"), ("ws", 8, "packed weights read as uint4")]),
+     [("in", 8, "conv_bf16_kernel: 16-byte fragment reads"), ("out", 8, "conv_bf16_kernel epilogue: uint4 store of the bf16 tile"),
+      ("out", 4, "conv_bf16_kernel epilogue"), ("ws", 8, "packed weights read as uint4")]),
     ("ipsr_conv3x3_bf16",
      lambda p: (2, _P(p, "in", 0), _P(p, "weight", 1), _P(p, "out", 2), 2, 64, 32, 64, 48, 0, _P(p, "ws", 3), WS, None),
-     [("out", 8, "conv_bf16.hip:469 st4 of the split reduction (fp32 out)"), ("in", 4, "conv_bf16.hip:706")]),
+     [("out", 8, "cb_split_reduce_kernel: st4 of the split reduction (fp32 out)"), ("in", 4, "conv_bf16x3_kernel load_x")]),
     ("ipsr_conv4x4s2_bf16",
      lambda p: (0, _P(p, "in", 0), _P(p, "weight", 1), _P(p, "out", 2), 2, 48, 32, 16, 16, 1, _P(p, "ws", 3), WS, None),
-     [("out", 8, "conv_bf16.hip:347 uint4 store of the fine -> coarse bf16 tile"), ("in", 8, "conv_bf16.hip:930"), ("ws", 8, "packed weights")]),
+     [("out", 8, "conv_bf16_kernel epilogue: uint4 store of the fine -> coarse bf16 tile"), ("in", 8, "conv_bf16_kernel dma_x"), ("ws", 8, "packed weights")]),
     ("ipsr_conv4x4s2_bf16_wrw",
      lambda p: (_P(p, "fine", 0), _P(p, "coarse", 1), _P(p, "dw", 2), 2, 48, 32, 16, 16, _P(p, "ws", 3), WS, None),
-     [("fine", 8, "16-byte row reads"), ("coarse", 8, "16-byte row reads"), ("dw", 8, "conv_bf16.hip:983 float4 store")]),
+     [("fine", 8, "16-byte row reads"), ("coarse", 8, "16-byte row reads"), ("dw", 8, "cb_slab_reduce_kernel<16>: float4 store")]),
     ("ipsr_conv3x3_bf16_wrw",
      lambda p: (0, _P(p, "x", 0), _P(p, "dy", 1), _P(p, "dw", 2), 2, 32, 16, 16, 48, _P(p, "ws", 3), WS, None),
      [("x", 8, "16-byte fragment reads"), ("dy", 8, "16-byte fragment reads"), ("ws", 8, "workspace vectors")]),

@@ -79,7 +79,7 @@ def test_mirror_matches_the_library_on_every_op_and_case_shape(lib):
 
 
 def test_lds_arithmetic_against_the_figures_in_the_source():
-    """conv_bf16.hip:46-49: k3 at W <= 128: 2 x (36 + 16 + 16.3) KB; stride 2: 2 x (32 + 20 + 20.4); k3 at W = 256: 2 x 36 + 2 x 24.3 +
+    """conv_bf16.hip, the LDS plan under CB_LDS_MAX: k3 at W <= 128: 2 x (36 + 16 + 16.3) KB; stride 2: 2 x (32 + 20 + 20.4); k3 at W = 256: 2 x 36 + 2 x 24.3 +
     ONE raw buffer of 24 KB."""
     g = P.cb_geometry(16, 128, 128, 128, 128)
     assert (g["a_bytes"], g["raw_bytes"], g["raw1"]) == (36 * 1024, 16 * 1024, False) and 16 * 1024 < g["t_bytes"] < 17 * 1024
