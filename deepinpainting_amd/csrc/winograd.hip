@@ -1,6 +1,14 @@
-// winograd.hip — 3x3 stride-1 pad-1 convolutions (and their input gradients / the transposed twins) by Winograd
-// F(4x4, 3x3) on the fp32 matrix cores.
+// winograd.hip — the Winograd convolutions on the matrix cores.  Four families share the 36 GEMMs of the arithmetic stage
+// (wino_gemm_kernel / wino_gemm_split_kernel), one plan (WinoGemmPlan, wino_plan_gemm), one workspace rule (wino_ws_bytes), one
+// launch head (wino_launch_head) and one launcher of the GEMMs (launch_wino_gemm); each keeps its own transform kernels,
+// tile geometry and refusals:
+//   3x3 data passes      F(4x4, 3x3), k3 s1 p1 in the four roles       wino_plan     launch_winograd      (this comment, below)
+//   3x3 weight gradient  F(3x3, 4x4), reduction over the tiles         wino_wrw_plan launch_winograd_wrw  ("weight-gradient transforms")
+//   4x4 on 3x3 tiles     F(3x3, 4x4), k4 s2 p3 d2 and k4 s1 p1         dil_plan      launch_winograd_dil  ("The DILATED down convolution")
+//   4x4 stride 2         polyphase F(5x5, 2x2), k4 s2 p1               s2_plan       launch_winograd_s2   ("The 4x4 STRIDE-2 pad-1 layers")
+// The small-map convolutions, which are no Winograd algorithm, live in smallmap.hip.
 //
+// The 3x3 stride-1 pad-1 convolutions, their input gradients and the transposed twins, by F(4x4, 3x3).
 // Reference layers (models/vgg16.py:9-21 — all thirteen VGG convolutions; models/networks.py:220-243 — `downconv_3`
 // Conv2d(k3 s1 p1) and `upconv_3` ConvTranspose2d(k3 s1 p1) of every netG level): together the largest share of the
 // training step's time.  A direct fp32 implicit GEMM (conv_gemm.hip, ~100 TF) can at best tie MIOpen's F(2x2,3x3)
@@ -39,7 +47,7 @@ constexpr int WG_BM = 128, WG_BN = 128, WG_BK = 16, WG_NBUF = 4, WG_THREADS = 25
 // (M + (ks*36 + xi) * plane); the output transforms add the slabs of each xi in ascending order (deterministic).
 struct WinoSplit {
     int nsplit, sps, xi_split, nsplit_t, sps_t;
-    int nxi = 36;           // GEMMs in the launch (36 Winograd points; 1 for the plain GEMMs of the small-map convolutions)
+    int nxi = 36;           // GEMMs in the launch: always the 36 Winograd points (kept: it is part of the kernels' argument layout)
     __host__ __device__ int slabs() const { return xi_split >= nxi ? nsplit : (xi_split <= 0 ? nsplit_t : (nsplit > nsplit_t ? nsplit : nsplit_t)); }
     __host__ __device__ int of(int xi) const { return xi < xi_split ? nsplit : nsplit_t; }
     __host__ __device__ int head_xi() const { return xi_split < nxi ? xi_split : nxi; }
@@ -805,29 +813,10 @@ __global__ void __launch_bounds__(WG_THREADS, 2) wino_gemm_split_kernel(const un
     }
 }
 
-// launches the 36 GEMMs in the arithmetic `math`: 0 = fp32 operands on v_mfma_f32_32x32x2_f32; 2 / 3 = split bf16 operands
-// `useful`: the multiply-adds of the UNPADDED problem x 2 (rows / cols / reduction before rounding up to the tile sizes)
 // Rows (produced channels) of the GEMM operand U / of M as stored: a multiple of 128, or exactly 64 for the 64-channel layers in
 // fp32 arithmetic (wino_gemm_kernel<64>); math < 0 = "whatever arithmetic" for workspace sizing (the larger padding).
 static int wino_rows_padded(int K, int math) { return (math == 0 && K <= 64) ? 64 : (K + WG_BM - 1) / WG_BM * WG_BM; }
 static int wino_row_tiles(int Kp) { return Kp == 64 ? 1 : Kp / WG_BM; }
-
-static void launch_wino_gemm(int math, const void* A, const void* Bv, int red, int rows, int cols, const WinoSplit& sp, float* Mo, hipStream_t st,
-                             double useful = 0.0)
-{
-    const int kt = wino_row_tiles(rows), tt = cols / WG_BN;
-    const unsigned grid = sp.workgroups(kt * tt);
-    profile_mark_start(st, 3);
-    if (math == 2)
-        wino_gemm_split_kernel<2><<<grid, WG_THREADS, 0, st>>>(static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(Bv), red, rows, cols, kt, tt, sp, Mo);
-    else if (math == 3)
-        wino_gemm_split_kernel<3><<<grid, WG_THREADS, 0, st>>>(static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(Bv), red, rows, cols, kt, tt, sp, Mo);
-    else if (rows == 64)
-        wino_gemm_kernel<64><<<grid, WG_THREADS, 0, st>>>(static_cast<const float*>(A), static_cast<const float*>(Bv), red, rows, cols, kt, tt, sp, Mo);
-    else
-        wino_gemm_kernel<128><<<grid, WG_THREADS, 0, st>>>(static_cast<const float*>(A), static_cast<const float*>(Bv), red, rows, cols, kt, tt, sp, Mo);
-    profile_mark_stop(st, 3, 72.0 * red * rows * cols, useful);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // how to cut the reduction of the 36 GEMMs (measurements: tools/sweep_wino_split.py -> profiles/r02_sweep_wino_split.txt).
@@ -894,29 +883,95 @@ template <typename F> static inline void with_type(bool bf16, F&& f)
 }
 #define ELEM_T(tag) std::remove_pointer_t<decltype(tag)>
 
-struct WinoPlan { int TY, TX, T, Tp, Kp; WinoSplit sp; size_t u_floats, v_floats, m_floats, total_bytes; };
+// The arithmetic stage of every family: M[xi][rows][cols] = sum over red of A[xi][red][rows] * B[xi][red][cols] for the 36 points.
+// TY x TX tiles per image, T in all, Tp = T rounded up to WG_BN.  The data passes have cols = Tp and red = the reduction
+// channels; the weight gradients have cols = the channels rounded up to WG_BN and red = Tp.
+struct WinoGemmPlan { int TY, TX, T, Tp, rows, cols, red; WinoSplit sp; size_t a_floats, b_floats, m_floats, total_bytes; };
 
-static int wino_plan(int B, int C, int K, int H, int W, WinoPlan* p, int math)
+static int round_up_bn(int n) { return (n + WG_BN - 1) / WG_BN * WG_BN; }
+
+static void wino_plan_tiles(WinoGemmPlan* p, int B, int TY, int TX)
+{
+    p->TY = TY; p->TX = TX;
+    p->T = B * TY * TX;
+    p->Tp = round_up_bn(p->T);                 // as a reduction: a multiple of 16 (and of the 16-tile blocks)
+}
+
+// the GEMMs and the workspace (A, B, the slabs of M: 256-byte aligned slices) for `produced` channels x cols, reduced over red
+static void wino_plan_gemm(WinoGemmPlan* p, int produced, int cols, int red, int math)
+{
+    p->rows = wino_rows_padded(produced, math);
+    p->cols = cols;
+    p->red = red;
+    p->a_floats = (size_t)36 * red * p->rows * 3 / 2;          // room for three bf16 planes (the split arithmetic with NPL = 3)
+    p->b_floats = (size_t)36 * red * cols * 3 / 2;
+    const size_t m1 = (size_t)36 * p->rows * cols;
+    p->sp = wino_choose_split(36 * wino_row_tiles(p->rows) * (cols / WG_BN), red / WG_BK, m1 * 4);
+    p->m_floats = m1 * p->sp.slabs();
+    p->total_bytes = align_up(p->a_floats * 4, 256) + align_up(p->b_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
+}
+
+// workspace for whatever arithmetic the call will ask for: the larger of math -1 and math 0; 0 where the family refuses the shape
+template <typename F> static size_t wino_ws_bytes(F&& plan)
+{
+    WinoGemmPlan p, q;
+    if (plan(&p, -1) != IPSR_OK || plan(&q, 0) != IPSR_OK) return 0;
+    return p.total_bytes > q.total_bytes ? p.total_bytes : q.total_bytes;
+}
+
+// What a launcher does between its plan and its first kernel, in the order that decides which message a bad call gets:
+// workspace, the family's own check (the 3x3 epilogue), arithmetic (`arith_note`: the tail of that message).  Then the slices
+// of the workspace: the two operands and the slabs of M.
+struct WinoBufs { float *A, *B, *M; };
+static int no_check() { return IPSR_OK; }
+
+template <typename Check = int (*)()>
+static int wino_launch_head(const char* who, const char* arith_note, const WinoGemmPlan& p, const ConvArith& ar, void* ws, size_t ws_bytes,
+                            WinoBufs* b, Check family_check = no_check)
+{
+    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, p.total_bytes);
+    if (int rc = family_check()) return rc;
+    if (!arith_ok(ar)) return fail(IPSR_ERR_INVALID, "%s: arithmetic %d%s", who, ar.math, arith_note);
+    Carver cv(ws, ws_bytes);
+    b->A = cv.take<float>(p.a_floats);
+    b->B = cv.take<float>(p.b_floats);
+    b->M = cv.take<float>(p.m_floats);
+    return IPSR_OK;
+}
+
+static int wino_remap() { return !debug_option(1); }    // XCD-contiguous (channel, tile block) ranges; debug option 1 = off
+
+// launches the 36 GEMMs in the arithmetic `math`: 0 = fp32 operands on v_mfma_f32_32x32x2_f32; 2 / 3 = split bf16 operands
+// `useful`: the multiply-adds of the UNPADDED problem x 2 (rows / cols / reduction before rounding up to the tile sizes)
+static int launch_wino_gemm(int math, const WinoGemmPlan& p, const WinoBufs& b, hipStream_t st, double useful)
+{
+    const int kt = wino_row_tiles(p.rows), tt = p.cols / WG_BN;
+    const unsigned grid = p.sp.workgroups(kt * tt);
+    const unsigned short *As = reinterpret_cast<const unsigned short*>(b.A), *Bs = reinterpret_cast<const unsigned short*>(b.B);
+    profile_mark_start(st, 3);
+    if (math == 2)
+        wino_gemm_split_kernel<2><<<grid, WG_THREADS, 0, st>>>(As, Bs, p.red, p.rows, p.cols, kt, tt, p.sp, b.M);
+    else if (math == 3)
+        wino_gemm_split_kernel<3><<<grid, WG_THREADS, 0, st>>>(As, Bs, p.red, p.rows, p.cols, kt, tt, p.sp, b.M);
+    else if (p.rows == 64)
+        wino_gemm_kernel<64><<<grid, WG_THREADS, 0, st>>>(b.A, b.B, p.red, p.rows, p.cols, kt, tt, p.sp, b.M);
+    else
+        wino_gemm_kernel<128><<<grid, WG_THREADS, 0, st>>>(b.A, b.B, p.red, p.rows, p.cols, kt, tt, p.sp, b.M);
+    profile_mark_stop(st, 3, 72.0 * p.red * p.rows * p.cols, useful);
+    return check_launch("wino_gemm_kernel");
+}
+
+static int wino_plan(int B, int C, int K, int H, int W, WinoGemmPlan* p, int math)
 {
     if (C % WG_BK != 0) return fail(IPSR_ERR_UNSUPPORTED, "winograd: %d reduction channels are not a multiple of %d", C, WG_BK);
-    p->TY = (H + 3) / 4; p->TX = (W + 3) / 4;
-    p->T = B * p->TY * p->TX;
-    p->Tp = (p->T + WG_BN - 1) / WG_BN * WG_BN;
-    p->Kp = wino_rows_padded(K, math);
-    p->u_floats = (size_t)36 * C * p->Kp * 3 / 2;          // room for three bf16 planes (the split arithmetic with NPL = 3)
-    p->v_floats = (size_t)36 * C * p->Tp * 3 / 2;
-    const size_t m1 = (size_t)36 * p->Kp * p->Tp;
-    p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Tp / WG_BN), C / WG_BK, m1 * 4);
-    p->m_floats = m1 * p->sp.slabs();
-    p->total_bytes = align_up(p->u_floats * 4, 256) + align_up(p->v_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
+    wino_plan_tiles(p, B, (H + 3) / 4, (W + 3) / 4);
+    wino_plan_gemm(p, K, p->Tp, C, math);
     return IPSR_OK;
 }
 
 size_t winograd_ws_bytes(int B, int C, int K, int H, int W)
 {
-    WinoPlan p, q;                                    // whatever arithmetic the call will ask for
-    if (wino_plan(B, C, K, H, W, &p, -1) != IPSR_OK || wino_plan(B, C, K, H, W, &q, 0) != IPSR_OK) return 0;
-    return p.total_bytes > q.total_bytes ? p.total_bytes : q.total_bytes;
+    return wino_ws_bytes([&](WinoGemmPlan* p, int math) { return wino_plan(B, C, K, H, W, p, math); });
 }
 
 size_t winograd_filter_floats(int C, int K) { return (size_t)36 * C * ((K + WG_BM - 1) / WG_BM * WG_BM) * 3 / 2; }
@@ -928,91 +983,70 @@ int launch_winograd(const void* x, const float* w, void* y, int B, int C, int K,
                     void* ws, size_t ws_bytes, hipStream_t st, const float* bias = nullptr, int epilogue = 0,
                     float* u_cache = nullptr, int u_valid = 0, ConvArith ar = ConvArith{0, false, false})
 {
-    WinoPlan p;
+    WinoGemmPlan p;
+    WinoBufs m;
     if (int rc = wino_plan(B, C, K, H, W, &p, ar.math)) return rc;
-    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "winograd: workspace %zu < %zu", ws_bytes, p.total_bytes);
-    if (epilogue < 0 || epilogue > 2 || (epilogue == 2 && ((H | W) & 1)))
-        return fail(IPSR_ERR_INVALID, "winograd: epilogue %d on a %dx%d map", epilogue, H, W);
-    if (!arith_ok(ar)) return fail(IPSR_ERR_INVALID, "winograd: arithmetic %d (0 = fp32 MFMA, 2 / 3 = split bf16)", ar.math);
-    Carver cv(ws, ws_bytes);
-    float* U = cv.take<float>(p.u_floats);
-    float* V = cv.take<float>(p.v_floats);
-    float* Mo = cv.take<float>(p.m_floats);
-    if (u_cache) U = u_cache;
-    const int remap = !debug_option(1);          // XCD-contiguous (channel, tile block) ranges; debug option 1 = off
+    auto epilogue_ok = [&] {
+        if (epilogue < 0 || epilogue > 2 || (epilogue == 2 && ((H | W) & 1)))
+            return fail(IPSR_ERR_INVALID, "winograd: epilogue %d on a %dx%d map", epilogue, H, W);
+        return (int)IPSR_OK;
+    };
+    if (int rc = wino_launch_head("winograd", " (0 = fp32 MFMA, 2 / 3 = split bf16)", p, ar, ws, ws_bytes, &m, epilogue_ok)) return rc;
+    if (u_cache) m.A = u_cache;
+    const int remap = wino_remap();
     with_mode(ar.math, [&](auto M) {
         constexpr int MODE = decltype(M)::value;
-        if (!(u_cache && u_valid)) wino_filter_kernel<MODE><<<op_grid(false, MODE, p.Kp, C), 256, 0, st>>>(w, C, K, p.Kp, sc, sm, flip, U);
+        if (!(u_cache && u_valid)) wino_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, C), 256, 0, st>>>(w, C, K, p.rows, sc, sm, flip, m.A);
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_input_kernel<MODE, T><<<op_grid(false, MODE, p.Tp, C), 256, 0, st>>>(static_cast<const T*>(x), B, C, H, W, p.TY, p.TX, p.Tp, V, remap);
+            wino_input_kernel<MODE, T><<<op_grid(false, MODE, p.Tp, C), 256, 0, st>>>(static_cast<const T*>(x), B, C, H, W, p.TY, p.TX, p.Tp, m.B, remap);
         });
     });
     if (int rc = check_launch("wino_input_kernel")) return rc;
-    launch_wino_gemm(ar.math, U, V, C, p.Kp, p.Tp, p.sp, Mo, st, 72.0 * C * K * p.T);
-    if (int rc = check_launch("wino_gemm_kernel")) return rc;
+    if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * C * K * p.T)) return rc;
     const dim3 og(cdiv(p.T, 256), K);
     with_type(ar.out_bf16, [&](auto* tag) {
         using T = ELEM_T(tag);
         T* yo = static_cast<T*>(y);
-        if (epilogue == 2) wino_output_kernel<2, T><<<og, 256, 0, st>>>(Mo, p.sp, bias, B, K, p.Kp, H, W, p.TY, p.TX, p.Tp, yo, remap);
-        else if (epilogue == 1) wino_output_kernel<1, T><<<og, 256, 0, st>>>(Mo, p.sp, bias, B, K, p.Kp, H, W, p.TY, p.TX, p.Tp, yo, remap);
-        else wino_output_kernel<0, T><<<og, 256, 0, st>>>(Mo, p.sp, bias, B, K, p.Kp, H, W, p.TY, p.TX, p.Tp, yo, remap);
+        if (epilogue == 2) wino_output_kernel<2, T><<<og, 256, 0, st>>>(m.M, p.sp, bias, B, K, p.rows, H, W, p.TY, p.TX, p.Tp, yo, remap);
+        else if (epilogue == 1) wino_output_kernel<1, T><<<og, 256, 0, st>>>(m.M, p.sp, bias, B, K, p.rows, H, W, p.TY, p.TX, p.Tp, yo, remap);
+        else wino_output_kernel<0, T><<<og, 256, 0, st>>>(m.M, p.sp, bias, B, K, p.rows, H, W, p.TY, p.TX, p.Tp, yo, remap);
     });
     return check_launch("wino_output_kernel");
 }
 
-struct WinoWrwPlan { int TY, TX, T, Tp, Kp, Cp; WinoSplit sp; size_t e_floats, v_floats, m_floats, total_bytes; };
-
-static int wino_wrw_plan(int B, int K, int C, int H, int W, WinoWrwPlan* p, int math)
+static int wino_wrw_plan(int B, int K, int C, int H, int W, WinoGemmPlan* p, int math)      // refuses nothing
 {
-    p->TY = (H + 3) / 4; p->TX = (W + 3) / 4;
-    p->T = B * p->TY * p->TX;
-    p->Tp = (p->T + WG_BN - 1) / WG_BN * WG_BN;            // reduction of the GEMM: a multiple of 16 (and of the 16-tile blocks)
-    p->Kp = wino_rows_padded(K, math);
-    p->Cp = (C + WG_BN - 1) / WG_BN * WG_BN;
-    p->e_floats = (size_t)36 * p->Tp * p->Kp * 3 / 2;            // room for three bf16 planes
-    p->v_floats = (size_t)36 * p->Tp * p->Cp * 3 / 2;
-    const size_t m1 = (size_t)36 * p->Kp * p->Cp;
-    p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Cp / WG_BN), p->Tp / WG_BK, m1 * 4);
-    p->m_floats = m1 * p->sp.slabs();
-    p->total_bytes = align_up(p->e_floats * 4, 256) + align_up(p->v_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
+    wino_plan_tiles(p, B, (H + 3) / 4, (W + 3) / 4);
+    wino_plan_gemm(p, K, round_up_bn(C), p->Tp, math);
     return IPSR_OK;
 }
 
 size_t winograd_wrw_ws_bytes(int B, int K, int C, int H, int W)
 {
-    WinoWrwPlan p, q;
-    wino_wrw_plan(B, K, C, H, W, &p, -1);
-    wino_wrw_plan(B, K, C, H, W, &q, 0);
-    return p.total_bytes > q.total_bytes ? p.total_bytes : q.total_bytes;
+    return wino_ws_bytes([&](WinoGemmPlan* p, int math) { return wino_wrw_plan(B, K, C, H, W, p, math); });
 }
 
 // dW[K][C][3][3] = sum over tiles:  tile operand `et` [B,K,H,W] (4x4 tiles), window operand `dt` [B,C,H,W] (6x6 windows)
 int launch_winograd_wrw(const void* et, const void* dt, float* dW, int B, int K, int C, int H, int W, void* ws, size_t ws_bytes, hipStream_t st,
                         ConvArith ar = ConvArith{0, false, false})
 {
-    WinoWrwPlan p;
+    WinoGemmPlan p;
+    WinoBufs m;
     wino_wrw_plan(B, K, C, H, W, &p, ar.math);
-    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "winograd wrw: workspace %zu < %zu", ws_bytes, p.total_bytes);
-    if (!arith_ok(ar)) return fail(IPSR_ERR_INVALID, "winograd wrw: arithmetic %d", ar.math);
-    Carver cv(ws, ws_bytes);
-    float* Et = cv.take<float>(p.e_floats);
-    float* Vt = cv.take<float>(p.v_floats);
-    float* Mw = cv.take<float>(p.m_floats);
+    if (int rc = wino_launch_head("winograd wrw", "", p, ar, ws, ws_bytes, &m)) return rc;
     with_mode(ar.math, [&](auto M) {
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.Kp), 256, 0, st>>>(static_cast<const T*>(et), B, K, H, W, p.TY, p.TX, p.Tp, p.Kp, Et);
-            wino_wrw_window_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.Cp), 256, 0, st>>>(static_cast<const T*>(dt), B, C, H, W, p.TY, p.TX, p.Tp, p.Cp, Vt);
+            wino_wrw_tile_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(et), B, K, H, W, p.TY, p.TX, p.Tp, p.rows, m.A);
+            wino_wrw_window_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.cols), 256, 0, st>>>(static_cast<const T*>(dt), B, C, H, W, p.TY, p.TX, p.Tp, p.cols, m.B);
         });
     });
     if (int rc = check_launch("wino_wrw_window_kernel")) return rc;
     // M[xi][k][c] = sum_t Et[xi][t][k] * Vt[xi][t][c]: the same GEMM with the tiles as the reduction
-    launch_wino_gemm(ar.math, Et, Vt, p.Tp, p.Kp, p.Cp, p.sp, Mw, st, 72.0 * p.T * K * C);
-    if (int rc = check_launch("wino_gemm_kernel")) return rc;
-    wino_wrw_output_kernel<<<dim3(cdiv(C, 256), K), 256, 0, st>>>(Mw, p.sp, K, C, p.Kp, p.Cp, dW);
+    if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * K * C)) return rc;
+    wino_wrw_output_kernel<<<dim3(cdiv(C, 256), K), 256, 0, st>>>(m.M, p.sp, K, C, p.rows, p.cols, dW);
     return check_launch("wino_wrw_output_kernel");
 }
 
@@ -1194,57 +1228,43 @@ __global__ void __launch_bounds__(256) wino_wrw_output4_kernel(const float* __re
     for (int i = 0; i < 4; ++i) dst[i] = make_float4(o[i][0], o[i][1], o[i][2], o[i][3]);
 }
 
-struct DilPlan { int Ho, Wo, Gy, Gx, TY, TX, T, Tp, Kp, Cp; WinoSplit sp; size_t a_floats, b_floats, m_floats, total_bytes; };
+// Ho x Wo: the output extent; Gy x Gx: the extent the 3x3 tiles cover (the output, or dx of geometry 1 in mode 1)
+struct DilGrid { int Ho, Wo, Gy, Gx; };
+static DilGrid dil_grid(int geom, int mode, int H, int W)
+{
+    const int Ho = geom == 0 ? H / 2 : H - 1, Wo = geom == 0 ? W / 2 : W - 1;
+    return DilGrid{Ho, Wo, (geom == 1 && mode == 1) ? H : Ho, (geom == 1 && mode == 1) ? W : Wo};
+}
 
 // mode 0: forward (grid = output Ho x Wo, reduce C=Cin, produce K=Cout); 1: backward-data (geom 0: grid = H/2 x W/2 odd positions
 // of dx; geom 1: grid = H x W; reduce Cout, produce Cin); 2: weight gradient (tiles of dy, reduction over tiles).
 // geom 0: Conv2d(k4 s2 p3 d2), output H/2 x W/2.   geom 1: Conv2d(k4 s1 p1) — netD's fourth convolution, models/networks.py:483-489
 // — output (H-1) x (W-1): the same 4-tap stride-1 correlation, on the image itself (X[i] = x[i - 1]).
-static int dil_plan(int geom, int mode, int B, int Cin, int H, int W, int Cout, DilPlan* p, int math)
+static int dil_plan(int geom, int mode, int B, int Cin, int H, int W, int Cout, WinoGemmPlan* p, int math)
 {
     if (geom != 0 && geom != 1) return fail(IPSR_ERR_INVALID, "4x4 winograd: geometry %d", geom);
     if (geom == 0 && ((H | W) & 1)) return fail(IPSR_ERR_UNSUPPORTED, "dilated winograd: odd extent %dx%d", H, W);
     if (geom == 1 && (H < 4 || W < 4)) return fail(IPSR_ERR_UNSUPPORTED, "4x4 winograd: extent %dx%d below the kernel", H, W);
-    p->Ho = geom == 0 ? H / 2 : H - 1; p->Wo = geom == 0 ? W / 2 : W - 1;
-    p->Gy = (geom == 1 && mode == 1) ? H : p->Ho; p->Gx = (geom == 1 && mode == 1) ? W : p->Wo;
-    p->TY = (p->Gy + 2) / 3; p->TX = (p->Gx + 2) / 3;
-    p->T = B * p->TY * p->TX;
-    p->Tp = (p->T + WG_BN - 1) / WG_BN * WG_BN;
-    if (mode == 2) {
-        p->Kp = wino_rows_padded(Cout, math);
-        p->Cp = (Cin + WG_BN - 1) / WG_BN * WG_BN;
-        p->a_floats = (size_t)36 * p->Tp * p->Kp * 3 / 2;        // room for three bf16 planes (split arithmetic)
-        p->b_floats = (size_t)36 * p->Tp * p->Cp * 3 / 2;
-        const size_t m1 = (size_t)36 * p->Kp * p->Cp;
-        p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Cp / WG_BN), p->Tp / WG_BK, m1 * 4);
-        p->m_floats = m1 * p->sp.slabs();
-    } else {
-        const int red = mode == 0 ? Cin : Cout, prod = mode == 0 ? Cout : Cin;
-        if (red % WG_BK != 0) return fail(IPSR_ERR_UNSUPPORTED, "4x4 winograd: %d reduction channels are not a multiple of %d", red, WG_BK);
-        p->Kp = wino_rows_padded(prod, math);
-        p->Cp = red;
-        p->a_floats = (size_t)36 * red * p->Kp * 3 / 2;
-        p->b_floats = (size_t)36 * red * p->Tp * 3 / 2;
-        const size_t m1 = (size_t)36 * p->Kp * p->Tp;
-        p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Tp / WG_BN), red / WG_BK, m1 * 4);
-        p->m_floats = m1 * p->sp.slabs();
-    }
-    p->total_bytes = align_up(p->a_floats * 4, 256) + align_up(p->b_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
+    const DilGrid g = dil_grid(geom, mode, H, W);
+    wino_plan_tiles(p, B, (g.Gy + 2) / 3, (g.Gx + 2) / 3);
+    const int red = mode == 0 ? Cin : Cout;
+    if (mode != 2 && red % WG_BK != 0)
+        return fail(IPSR_ERR_UNSUPPORTED, "4x4 winograd: %d reduction channels are not a multiple of %d", red, WG_BK);
+    if (mode == 2) wino_plan_gemm(p, Cout, round_up_bn(Cin), p->Tp, math);
+    else wino_plan_gemm(p, mode == 0 ? Cout : Cin, p->Tp, red, math);
     return IPSR_OK;
 }
 
 size_t winograd_dil_ws_bytes(int geom, int mode, int B, int Cin, int H, int W, int Cout)
 {
-    DilPlan p, q;
-    if (dil_plan(geom, mode, B, Cin, H, W, Cout, &p, -1) != IPSR_OK || dil_plan(geom, mode, B, Cin, H, W, Cout, &q, 0) != IPSR_OK) return 0;
-    return p.total_bytes > q.total_bytes ? p.total_bytes : q.total_bytes;
+    return wino_ws_bytes([&](WinoGemmPlan* p, int math) { return dil_plan(geom, mode, B, Cin, H, W, Cout, p, math); });
 }
 
 template <bool TMAJOR, int MODE, typename T>
-static void launch_window3(int is, hipStream_t st, const T* x, int B, int C, int H, int W, int off, const DilPlan& p, int Cp, void* V)
+static void launch_window3(int is, hipStream_t st, const T* x, int B, int C, int H, int W, int off, const WinoGemmPlan& p, int Cp, void* V)
 {
     const dim3 grid = op_grid(TMAJOR, MODE, p.Tp, TMAJOR ? Cp : C);
-    const int remap = !debug_option(1);          // XCD-contiguous (channel, tile block) ranges; debug option 1 = off
+    const int remap = wino_remap();
     if (is == 2) wino_window_kernel<3, 2, TMAJOR, MODE, T><<<grid, 256, 0, st>>>(x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V, remap);
     else wino_window_kernel<3, 1, TMAJOR, MODE, T><<<grid, 256, 0, st>>>(x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V, remap);
 }
@@ -1253,16 +1273,13 @@ static void launch_window3(int is, hipStream_t st, const T* x, int B, int C, int
 int launch_winograd_dil(int geom, int mode, const void* a, const void* b2, void* out, int B, int Cin, int H, int W, int Cout,
                         void* ws, size_t ws_bytes, hipStream_t st, ConvArith ar = ConvArith{0, false, false})
 {
-    DilPlan p;
+    WinoGemmPlan p;
+    WinoBufs m;
     if (int rc = dil_plan(geom, mode, B, Cin, H, W, Cout, &p, ar.math)) return rc;
-    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "4x4 winograd: workspace %zu < %zu", ws_bytes, p.total_bytes);
-    if (!arith_ok(ar)) return fail(IPSR_ERR_INVALID, "4x4 winograd: arithmetic %d", ar.math);
-    const int Ho = p.Ho, Wo = p.Wo;
+    if (int rc = wino_launch_head("4x4 winograd", "", p, ar, ws, ws_bytes, &m)) return rc;
+    const DilGrid g = dil_grid(geom, mode, H, W);
+    const int Ho = g.Ho, Wo = g.Wo;
     const int xis = geom == 0 ? 2 : 1, xoff = geom == 0 ? -3 : -1;        // X[i] = x[xis * i + xoff]
-    Carver cv(ws, ws_bytes);
-    float* A = cv.take<float>(p.a_floats);
-    float* Bv = cv.take<float>(p.b_floats);
-    float* Mo = cv.take<float>(p.m_floats);
     if (mode == 0 || mode == 1) {
         // mode 0: a = x, b2 = w, out = y.   mode 1: a = dy, b2 = w, out = dx:
         //   geom 0: only the odd rows / columns receive gradient, dx[2q+1] = sum_r' w[3-r'] dy[q - 1 + r']
@@ -1274,21 +1291,20 @@ int launch_winograd_dil(int geom, int mode, const void* a, const void* b2, void*
         const float* w = static_cast<const float*>(b2);
         with_mode(ar.math, [&](auto M) {
             constexpr int MODE = decltype(M)::value;
-            if (mode == 0) wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.Kp, Cin), 256, 0, st>>>(w, Cin, Cout, p.Kp, 16, (long)Cin * 16, 0, A);
-            else wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.Kp, Cout), 256, 0, st>>>(w, Cout, Cin, p.Kp, (long)Cin * 16, 16, 1, A);
+            if (mode == 0) wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, Cin), 256, 0, st>>>(w, Cin, Cout, p.rows, 16, (long)Cin * 16, 0, m.A);
+            else wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, Cout), 256, 0, st>>>(w, Cout, Cin, p.rows, (long)Cin * 16, 16, 1, m.A);
             with_type(ar.in_bf16, [&](auto* tag) {
                 using T = ELEM_T(tag);
-                if (mode == 0) launch_window3<false, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, 0, Bv);
-                else launch_window3<false, MODE, T>(1, st, static_cast<const T*>(a), B, Cout, Ho, Wo, geom == 0 ? -1 : -2, p, 0, Bv);
+                if (mode == 0) launch_window3<false, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, 0, m.B);
+                else launch_window3<false, MODE, T>(1, st, static_cast<const T*>(a), B, Cout, Ho, Wo, geom == 0 ? -1 : -2, p, 0, m.B);
             });
         });
         if (int rc = check_launch("wino_window_kernel")) return rc;
-        launch_wino_gemm(ar.math, A, Bv, red, p.Kp, p.Tp, p.sp, Mo, st, 72.0 * red * prod * p.T);
-        if (int rc = check_launch("wino_gemm_kernel")) return rc;
+        if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * red * prod * p.T)) return rc;
         with_type(ar.out_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            if (mode == 0) wino3_output_kernel<T><<<dim3(cdiv(p.T, 256), prod), 256, 0, st>>>(Mo, p.sp, B, Cout, p.Kp, Ho, Wo, p.TY, p.TX, p.Tp, Ho, Wo, 1, 0, static_cast<T*>(out));
-            else wino3_output_kernel<T><<<dim3(cdiv(p.T, 256), prod), 256, 0, st>>>(Mo, p.sp, B, Cin, p.Kp, p.Gy, p.Gx, p.TY, p.TX, p.Tp, H, W,
+            if (mode == 0) wino3_output_kernel<T><<<dim3(cdiv(p.T, 256), prod), 256, 0, st>>>(m.M, p.sp, B, Cout, p.rows, Ho, Wo, p.TY, p.TX, p.Tp, Ho, Wo, 1, 0, static_cast<T*>(out));
+            else wino3_output_kernel<T><<<dim3(cdiv(p.T, 256), prod), 256, 0, st>>>(m.M, p.sp, B, Cin, p.rows, g.Gy, g.Gx, p.TY, p.TX, p.Tp, H, W,
                                                                                     geom == 0 ? 2 : 1, geom == 0 ? 1 : 0, static_cast<T*>(out));
         });
         return check_launch("wino3_output_kernel");
@@ -1298,14 +1314,13 @@ int launch_winograd_dil(int geom, int mode, const void* a, const void* b2, void*
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile3_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.Kp), 256, 0, st>>>(static_cast<const T*>(b2), B, Cout, Ho, Wo, p.TY, p.TX, p.Tp, p.Kp, A);
-            launch_window3<true, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, p.Cp, Bv);
+            wino_wrw_tile3_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(b2), B, Cout, Ho, Wo, p.TY, p.TX, p.Tp, p.rows, m.A);
+            launch_window3<true, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, p.cols, m.B);
         });
     });
     if (int rc = check_launch("wino_window_kernel")) return rc;
-    launch_wino_gemm(ar.math, A, Bv, p.Tp, p.Kp, p.Cp, p.sp, Mo, st, 72.0 * p.T * Cout * Cin);
-    if (int rc = check_launch("wino_gemm_kernel")) return rc;
-    wino_wrw_output4_kernel<<<dim3(cdiv(Cin, 256), Cout), 256, 0, st>>>(Mo, p.sp, Cout, Cin, p.Kp, p.Cp, static_cast<float*>(out));
+    if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * Cout * Cin)) return rc;
+    wino_wrw_output4_kernel<<<dim3(cdiv(Cin, 256), Cout), 256, 0, st>>>(m.M, p.sp, Cout, Cin, p.rows, p.cols, static_cast<float*>(out));
     return check_launch("wino_wrw_output4_kernel");
 }
 
@@ -1644,46 +1659,21 @@ __global__ void __launch_bounds__(256) wino_wrw_output2_kernel(const float* __re
         for (int b = 0; b < 2; ++b) dst[(2 * a + ey) * 4 + 2 * b + ex] = o[a][b];
 }
 
-struct S2Plan { int TY, TX, T, Tp, Kp, Cp, red; WinoSplit sp; size_t a_floats, b_floats, m_floats, total_bytes; };
-
-static int s2_plan(int mode, int B, int Kc, int Cf, int nh, int nw, S2Plan* p, int math)
+static int s2_plan(int mode, int B, int Kc, int Cf, int nh, int nw, WinoGemmPlan* p, int math)
 {
     if (mode < 0 || mode > 2) return fail(IPSR_ERR_INVALID, "4x4 stride-2 winograd: mode %d", mode);
-    p->TY = mode == 1 ? (nh + 5) / 5 : (nh + 4) / 5;
-    p->TX = mode == 1 ? (nw + 5) / 5 : (nw + 4) / 5;
-    p->T = B * p->TY * p->TX;
-    p->Tp = (p->T + WG_BN - 1) / WG_BN * WG_BN;
-    size_t m1;
-    if (mode == 2) {
-        p->Kp = wino_rows_padded(Kc, math);
-        p->Cp = (4 * Cf + WG_BN - 1) / WG_BN * WG_BN;
-        p->red = p->Tp;
-        p->a_floats = (size_t)36 * p->Tp * p->Kp * 3 / 2;
-        p->b_floats = (size_t)36 * p->Tp * p->Cp * 3 / 2;
-        m1 = (size_t)36 * p->Kp * p->Cp;
-        p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Cp / WG_BN), p->Tp / WG_BK, m1 * 4);
-    } else {
-        p->red = mode == 0 ? 4 * Cf : Kc;
-        if (p->red % WG_BK != 0)
-            return fail(IPSR_ERR_UNSUPPORTED, "4x4 stride-2 winograd: reduction length %d is not a multiple of %d", p->red, WG_BK);
-        const int prod = mode == 0 ? Kc : 4 * Cf;
-        p->Kp = wino_rows_padded(prod, math);
-        p->Cp = p->red;
-        p->a_floats = (size_t)36 * p->red * p->Kp * 3 / 2;
-        p->b_floats = (size_t)36 * p->red * p->Tp * 3 / 2;
-        m1 = (size_t)36 * p->Kp * p->Tp;
-        p->sp = wino_choose_split(36 * wino_row_tiles(p->Kp) * (p->Tp / WG_BN), p->red / WG_BK, m1 * 4);
-    }
-    p->m_floats = m1 * p->sp.slabs();
-    p->total_bytes = align_up(p->a_floats * 4, 256) + align_up(p->b_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
+    wino_plan_tiles(p, B, mode == 1 ? (nh + 5) / 5 : (nh + 4) / 5, mode == 1 ? (nw + 5) / 5 : (nw + 4) / 5);
+    const int red = mode == 0 ? 4 * Cf : Kc;
+    if (mode != 2 && red % WG_BK != 0)
+        return fail(IPSR_ERR_UNSUPPORTED, "4x4 stride-2 winograd: reduction length %d is not a multiple of %d", red, WG_BK);
+    if (mode == 2) wino_plan_gemm(p, Kc, round_up_bn(4 * Cf), p->Tp, math);
+    else wino_plan_gemm(p, mode == 0 ? Kc : 4 * Cf, p->Tp, red, math);
     return IPSR_OK;
 }
 
 size_t winograd_s2_ws_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
-    S2Plan p, q;
-    if (s2_plan(mode, B, Kc, Cf, nh, nw, &p, -1) != IPSR_OK || s2_plan(mode, B, Kc, Cf, nh, nw, &q, 0) != IPSR_OK) return 0;
-    return p.total_bytes > q.total_bytes ? p.total_bytes : q.total_bytes;
+    return wino_ws_bytes([&](WinoGemmPlan* p, int math) { return s2_plan(mode, B, Kc, Cf, nh, nw, p, math); });
 }
 
 // fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw], w / dW [Kc][Cf][4][4].
@@ -1691,43 +1681,38 @@ size_t winograd_s2_ws_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 int launch_winograd_s2(int mode, const void* a, const void* b2, void* out, int B, int Kc, int Cf, int nh, int nw,
                        void* ws, size_t ws_bytes, hipStream_t st, ConvArith ar = ConvArith{0, false, false})
 {
-    S2Plan p;
+    WinoGemmPlan p;
+    WinoBufs m;
     if (int rc = s2_plan(mode, B, Kc, Cf, nh, nw, &p, ar.math)) return rc;
-    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "4x4 stride-2 winograd: workspace %zu < %zu", ws_bytes, p.total_bytes);
-    if (!arith_ok(ar)) return fail(IPSR_ERR_INVALID, "4x4 stride-2 winograd: arithmetic %d", ar.math);
+    if (int rc = wino_launch_head("4x4 stride-2 winograd", "", p, ar, ws, ws_bytes, &m)) return rc;
     // the split filter transform stores whole 8-channel blocks per phase (form 0) / whole 32-column blocks per phase (form 1):
     // shapes it cannot express run the fp32 arithmetic instead (never less accurate)
-    if (ar.math && ((mode == 0 && Cf % 8 != 0) || (mode == 1 && (Cf % SPLIT_ROWS != 0 || p.Kp != 4 * Cf || Kc % 8 != 0)))) ar.math = 0;
-    Carver cv(ws, ws_bytes);
-    float* A = cv.take<float>(p.a_floats);
-    float* Bv = cv.take<float>(p.b_floats);
-    float* Mo = cv.take<float>(p.m_floats);
-    const int remap = !debug_option(1);          // XCD-contiguous (channel, tile block) ranges; debug option 1 = off
+    if (ar.math && ((mode == 0 && Cf % 8 != 0) || (mode == 1 && (Cf % SPLIT_ROWS != 0 || p.rows != 4 * Cf || Kc % 8 != 0)))) ar.math = 0;
+    const int remap = wino_remap();
     if (mode == 0 || mode == 1) {
         const float* w = static_cast<const float*>(b2);
         if (ar.math == 0) {
-            if (mode == 0) wino52_filter_kernel<<<dim3(cdiv(p.Kp, 256), Cf), 256, 0, st>>>(w, Kc, Cf, p.Kp, 0, A);
-            else wino52_filter_kernel<<<dim3(cdiv(Cf + (p.Kp - 4 * Cf), 256), Kc), 256, 0, st>>>(w, Kc, Cf, p.Kp, 1, A);
+            if (mode == 0) wino52_filter_kernel<<<dim3(cdiv(p.rows, 256), Cf), 256, 0, st>>>(w, Kc, Cf, p.rows, 0, m.A);
+            else wino52_filter_kernel<<<dim3(cdiv(Cf + (p.rows - 4 * Cf), 256), Kc), 256, 0, st>>>(w, Kc, Cf, p.rows, 1, m.A);
         } else {
-            const dim3 fg = mode == 0 ? dim3(p.Kp / SPLIT_ROWS, Cf / 8) : dim3(Cf / SPLIT_ROWS, Kc / 8);
-            if (ar.math == 2) wino52_filter_split_kernel<2><<<fg, 256, 0, st>>>(w, Kc, Cf, p.Kp, mode, reinterpret_cast<unsigned short*>(A));
-            else wino52_filter_split_kernel<3><<<fg, 256, 0, st>>>(w, Kc, Cf, p.Kp, mode, reinterpret_cast<unsigned short*>(A));
+            const dim3 fg = mode == 0 ? dim3(p.rows / SPLIT_ROWS, Cf / 8) : dim3(Cf / SPLIT_ROWS, Kc / 8);
+            if (ar.math == 2) wino52_filter_split_kernel<2><<<fg, 256, 0, st>>>(w, Kc, Cf, p.rows, mode, reinterpret_cast<unsigned short*>(m.A));
+            else wino52_filter_split_kernel<3><<<fg, 256, 0, st>>>(w, Kc, Cf, p.rows, mode, reinterpret_cast<unsigned short*>(m.A));
         }
         with_mode(ar.math, [&](auto M) {
             constexpr int MODE = decltype(M)::value;
             with_type(ar.in_bf16, [&](auto* tag) {
                 using T = ELEM_T(tag);
-                if (mode == 0) wino5_window_kernel<2, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, 0, Bv, remap);
-                else wino5_window_kernel<1, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Kc, nh, nw, 1, p.TY, p.TX, p.Tp, 0, Bv, remap);
+                if (mode == 0) wino5_window_kernel<2, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, 0, m.B, remap);
+                else wino5_window_kernel<1, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Kc, nh, nw, 1, p.TY, p.TX, p.Tp, 0, m.B, remap);
             });
         });
         if (int rc = check_launch("wino5_window_kernel")) return rc;
-        launch_wino_gemm(ar.math, A, Bv, p.red, p.Kp, p.Tp, p.sp, Mo, st, 72.0 * p.red * (mode == 0 ? Kc : 4 * Cf) * p.T);
-        if (int rc = check_launch("wino_gemm_kernel")) return rc;
+        if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.red * (mode == 0 ? Kc : 4 * Cf) * p.T)) return rc;
         with_type(ar.out_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            if (mode == 0) wino5_output_kernel<T><<<dim3(cdiv(p.T, 256), Kc), 256, 0, st>>>(Mo, p.sp, B, Kc, p.Kp, nh, nw, p.TY, p.TX, p.Tp, static_cast<T*>(out));
-            else wino5_output_rows_kernel<T><<<dim3(cdiv(p.T, W5R_TILES), Cf), 256, 0, st>>>(Mo, p.sp, B, Cf, p.Kp, nh, nw, p.TY, p.TX, p.Tp, static_cast<T*>(out));
+            if (mode == 0) wino5_output_kernel<T><<<dim3(cdiv(p.T, 256), Kc), 256, 0, st>>>(m.M, p.sp, B, Kc, p.rows, nh, nw, p.TY, p.TX, p.Tp, static_cast<T*>(out));
+            else wino5_output_rows_kernel<T><<<dim3(cdiv(p.T, W5R_TILES), Cf), 256, 0, st>>>(m.M, p.sp, B, Cf, p.rows, nh, nw, p.TY, p.TX, p.Tp, static_cast<T*>(out));
         });
         return check_launch("wino5_output_kernel");
     }
@@ -1736,387 +1721,14 @@ int launch_winograd_s2(int mode, const void* a, const void* b2, void* out, int B
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile5_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.Kp), 256, 0, st>>>(static_cast<const T*>(b2), B, Kc, nh, nw, p.TY, p.TX, p.Tp, p.Kp, A);
-            wino5_window_kernel<2, true, MODE, T><<<op_grid(true, MODE, p.Tp, p.Cp), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, p.Cp, Bv, 0);
+            wino_wrw_tile5_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(b2), B, Kc, nh, nw, p.TY, p.TX, p.Tp, p.rows, m.A);
+            wino5_window_kernel<2, true, MODE, T><<<op_grid(true, MODE, p.Tp, p.cols), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, p.cols, m.B, 0);
         });
     });
     if (int rc = check_launch("wino5_window_kernel")) return rc;
-    launch_wino_gemm(ar.math, A, Bv, p.Tp, p.Kp, p.Cp, p.sp, Mo, st, 72.0 * p.T * Kc * 4 * Cf);
-    if (int rc = check_launch("wino_gemm_kernel")) return rc;
-    wino_wrw_output2_kernel<<<dim3(cdiv(Cf, 256), Kc, 4), 256, 0, st>>>(Mo, p.sp, Kc, Cf, p.Kp, p.Cp, static_cast<float*>(out));
+    if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * Kc * 4 * Cf)) return rc;
+    wino_wrw_output2_kernel<<<dim3(cdiv(Cf, 256), Kc, 4), 256, 0, st>>>(m.M, p.sp, Kc, Cf, p.rows, p.cols, static_cast<float*>(out));
     return check_launch("wino_wrw_output2_kernel");
-}
-
-// ===================================================================================================
-// Small maps.  The inner levels of both U-Nets and netF (512-1024 channels on 8x8 ... 1x1: models/networks.py:220-259, 404-432,
-// 510-515) are ~85 convolution calls per training step whose arithmetic is a skinny GEMM between a 9-33 MB weight tensor and
-// a handful of activations: MIOpen spends 45-150 us on each (layout transposes, zero fills, tiles made for large maps).
-// Here the weight tensor Wm = [R][Q] (R = its first channel dimension, Q = second channel dimension x taps, contiguous: Conv2d
-// [Cout][(Cin,t)], ConvTranspose2d [Cin][(Cout,t)]) is STREAMED ONCE from where it lies, 16 bytes per lane straight into
-// MFMA operands — no LDS, no packing — and the P = B*Ho*Wo <= 1024 positions ride on the 32-wide N side of 32x32x2 MFMAs:
-//   DATA (Conv2d backward-data, ConvTranspose2d forward)   Mcol[q][p] = sum_r Wm[r][q] * in[r][p],  then col2im over the taps
-//   FWD  (Conv2d forward, ConvTranspose2d backward-data)    y[r][p]    = sum_q Wm[r][q] * col(fine)[q][p]
-//   WRW  (weight gradient of either)                        dW[r][q]   = sum_p coarse[r][p] * col(fine)[q][p]   (native layout, one pass)
-// p runs over the grid on R's side ("coarse": the conv's output side), "fine" is the grid on Q's side.  The row / column labels
-// of an MFMA tile are free, so a lane's float4 of four consecutive q feeds four MFMAs whose tiles are q = q0 + 4m + j: every
-// weight byte is fetched by exactly one coalesced 16-byte load.  The streams are bandwidth bound (16.8 MB in ~5 us); the
-// reduction is cut over workgroups into slabs that the tiny post-pass (col2im / layout) adds in order (deterministic).
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-
-__global__ void __launch_bounds__(256) sm_to_cn_kernel(const float* __restrict__ x, int B, int C, int HW, int Tp, float* __restrict__ out)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-    if (n >= Tp) return;
-    float v = 0.0f;
-    if (n < B * HW) { const int b = n / HW, p = n - b * HW; v = x[((size_t)b * C + c) * HW + p]; }
-    out[(size_t)c * Tp + n] = v;
-}
-
-__global__ void __launch_bounds__(256) sm_to_nc_kernel(const float* __restrict__ x, int B, int C, int HW, float* __restrict__ out)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;              // rows n >= B*HW are zero padding of the reduction
-    if (c >= C) return;
-    float v = 0.0f;
-    if (n < B * HW) { const int b = n / HW, p = n - b * HW; v = x[((size_t)b * C + c) * HW + p]; }
-    out[(size_t)n * C + c] = v;
-}
-
-__device__ __forceinline__ float sm_tap(const float* __restrict__ f, int B, int C, int Hf, int Wf, int Ho, int Wo, int k, int st, int pad, int dil,
-                                        int n, int col)
-{
-    if (n >= B * Ho * Wo) return 0.0f;
-    const int kk = k * k;
-    const int c = col / kk, t = col - c * kk, r = t / k, q = t - r * k;
-    const int b = n / (Ho * Wo), o = n - b * Ho * Wo, oy = o / Wo, ox = o - oy * Wo;
-    const int fy = oy * st - pad + r * dil, fx = ox * st - pad + q * dil;
-    return ((unsigned)fy < (unsigned)Hf && (unsigned)fx < (unsigned)Wf) ? f[(((size_t)b * C + c) * Hf + fy) * Wf + fx] : 0.0f;
-}
-
-// V[n][(c,t)] = fine[b][c][oy*s - pad + r*dil][ox*s - pad + q*dil]  (0 outside; rows n >= B*Ho*Wo zero)
-__global__ void __launch_bounds__(256) sm_im2col_nt_kernel(const float* __restrict__ f, int B, int C, int Hf, int Wf, int Ho, int Wo,
-                                                           int k, int st, int pad, int dil, float* __restrict__ out)
-{
-    const int col = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
-    const int ncol = C * k * k;
-    if (col >= ncol) return;
-    out[(size_t)n * ncol + col] = sm_tap(f, B, C, Hf, Wf, Ho, Wo, k, st, pad, dil, n, col);
-}
-
-// the same as [(c,t)][n] with row length Tp (columns n >= B*Ho*Wo zero)
-__global__ void __launch_bounds__(256) sm_im2col_cn_kernel(const float* __restrict__ f, int B, int C, int Hf, int Wf, int Ho, int Wo,
-                                                           int k, int st, int pad, int dil, int Tp, float* __restrict__ out)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x, col = blockIdx.y;
-    if (n >= Tp) return;
-    out[(size_t)col * Tp + n] = sm_tap(f, B, C, Hf, Wf, Ho, Wo, k, st, pad, dil, n, col);
-}
-
-// out[b][c][fy][fx] = sum_{slabs} sum_{(r,q): fy = oy*s - pad + r*dil, fx = ox*s - pad + q*dil} M[(c,t)][(b,oy,ox)]
-__global__ void __launch_bounds__(256) sm_col2im_kernel(const float* __restrict__ M, int nslab, size_t slab_stride, int B, int C, int Hf, int Wf,
-                                                        int Ho, int Wo, int k, int st, int pad, int dil, int Tp, float* __restrict__ out)
-{
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)B * C * Hf * Wf;
-    if (idx >= total) return;
-    const int fx = (int)(idx % Wf), fy = (int)((idx / Wf) % Hf), c = (int)((idx / ((size_t)Wf * Hf)) % C), b = (int)(idx / ((size_t)Wf * Hf * C));
-    float acc = 0.0f;
-    for (int r = 0; r < k; ++r) {
-        const int ny = fy + pad - r * dil;
-        if (ny < 0 || ny % st) continue;
-        const int oy = ny / st;
-        if (oy >= Ho) continue;
-        for (int q = 0; q < k; ++q) {
-            const int nx = fx + pad - q * dil;
-            if (nx < 0 || nx % st) continue;
-            const int ox = nx / st;
-            if (ox >= Wo) continue;
-            const size_t off = (size_t)(c * k * k + r * k + q) * Tp + ((size_t)b * Ho + oy) * Wo + ox;
-            for (int sl = 0; sl < nslab; ++sl) acc += M[(size_t)sl * slab_stride + off];
-        }
-    }
-    out[idx] = acc;
-}
-
-// out[b][r][o] = sum_{slabs} Y[slab][r][(b,o)]
-__global__ void __launch_bounds__(256) sm_sum_to_nchw_kernel(const float* __restrict__ Y, int nslab, size_t slab_stride, int B, int R, int HW, int Tp,
-                                                             float* __restrict__ out)
-{
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (size_t)B * R * HW) return;
-    const int o = (int)(idx % HW), r = (int)((idx / HW) % R), b = (int)(idx / ((size_t)HW * R));
-    const size_t off = (size_t)r * Tp + (size_t)b * HW + o;
-    float acc = 0.0f;
-    for (int sl = 0; sl < nslab; ++sl) acc += Y[(size_t)sl * slab_stride + off];
-    out[idx] = acc;
-}
-
-// In-workgroup reduction of the four waves' partial tiles (each wave took a quarter of the slab's reduction range): waves 1..3
-// park a tile in LDS, wave 0 adds them in order.  Deterministic; 4x fewer slabs for the same number of waves in flight.
-template <int NB>
-__device__ __forceinline__ void sm_reduce4(f32x16 (&acc)[NB], float* lds, int wave, int lane)
-{
-    if (wave > 0) {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) lds[(((wave - 1) * NB + nb) * 16 + e) * 64 + lane] = acc[nb][e];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int w = 0; w < 3; ++w)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[nb][e] += lds[((w * NB + nb) * 16 + e) * 64 + lane];
-    }
-    __syncthreads();
-}
-
-// DATA: one workgroup (4 waves) = 128 columns q of Wm x the rows of its slab (a quarter per wave) x NB position blocks.
-//   A (MFMA j, lane (m, h)) = Wm[r + h][q0 + 4m + j]   — component j of the lane's float4 at Wm[r + h][q0 + 4m]
-//   B (lane (n, h))         = in[r + h][n0 + 32 nb + n]
-// slab s = blockIdx.y: Mcol_s[q0 + 4*row + j][n] for the 32x32 tile rows `row` of MFMA j.
-template <int NB>
-__global__ void __launch_bounds__(256) sm_data_kernel(const float* __restrict__ Wm, const float* __restrict__ In, int R, int Q, int Tp, int rows_per_wave,
-                                                      float* __restrict__ Mcol)
-{
-    __shared__ float red[3 * NB * 16 * 64];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 31, h = lane >> 5;
-    const int q0 = blockIdx.x * 128, n0 = blockIdx.z * (32 * NB);
-    const int ra = min(R, (blockIdx.y * 4 + wave) * rows_per_wave), rb = min(R, ra + rows_per_wave);
-    f32x16 acc[4][NB];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[j][nb][e] = 0.0f;
-    const float* wp = Wm + (size_t)(ra + h) * Q + q0 + 4 * m;
-    const float* ip = In + (size_t)(ra + h) * Tp + n0 + m;
-    constexpr int U = NB == 1 ? 8 : (NB == 2 ? 4 : 2);     // row pairs in flight (8 KB of the weight stream per wave at NB = 1); bounded by the 4*NB accumulator tiles
-    for (int r = ra; r < rb; r += 2 * U) {
-        f32x4v a[U];
-        float bv[U][NB];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = r + 2 * u < rb;               // R and rows_per_wave are even: a pair is in or out as a whole
-            a[u] = ok ? *reinterpret_cast<const f32x4v*>(wp + (size_t)2 * u * Q) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) bv[u][nb] = ok ? ip[(size_t)2 * u * Tp + 32 * nb] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[j][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][j], bv[u][nb], acc[j][nb], 0, 0, 0);
-        wp += (size_t)2 * U * Q;
-        ip += (size_t)2 * U * Tp;
-    }
-    float* out = Mcol + (size_t)blockIdx.y * Q * Tp;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        sm_reduce4<NB>(acc[j], red, wave, lane);
-        if (wave == 0) {
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-                    out[(size_t)(q0 + 4 * row + j) * Tp + n0 + 32 * nb + m] = acc[j][nb][e];
-                }
-        }
-    }
-}
-
-// FWD: one workgroup (4 waves) = 32 rows r of Wm x the columns of its slab (a quarter per wave) x NB position blocks.
-//   A (MFMA j, lane (m, h)) = Wm[r0 + m][q + 4h + j]   — component j of the lane's float4 at Wm[r0 + m][q + 4h]
-//   B (MFMA j, lane (n, h)) = col[q + 4h + j][n0 + 32 nb + n]
-template <int NB>
-__global__ void __launch_bounds__(256) sm_fwd_kernel(const float* __restrict__ Wm, const float* __restrict__ Xc, int R, int Q, int Tp, int cols_per_wave,
-                                                     float* __restrict__ Y)
-{
-    __shared__ float red[3 * NB * 16 * 64];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 31, h = lane >> 5;
-    const int r0 = blockIdx.x * 32, n0 = blockIdx.z * (32 * NB);
-    const int qa = min(Q, (blockIdx.y * 4 + wave) * cols_per_wave), qb = min(Q, qa + cols_per_wave);
-    f32x16 acc[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[nb][e] = 0.0f;
-    const float* wp = Wm + (size_t)(r0 + m) * Q + qa + 4 * h;
-    const float* xp = Xc + (size_t)(qa + 4 * h) * Tp + n0 + m;
-    constexpr int U = 4;                                  // groups of 8 columns in flight
-    for (int q = qa; q < qb; q += 8 * U) {
-        f32x4v a[U];
-        float bv[U][4][NB];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = q + 8 * u < qb;               // Q and cols_per_wave are multiples of 8
-            a[u] = ok ? *reinterpret_cast<const f32x4v*>(wp + 8 * u) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) bv[u][j][nb] = ok ? xp[(size_t)(8 * u + j) * Tp + 32 * nb] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][j], bv[u][j][nb], acc[nb], 0, 0, 0);
-        wp += 8 * U;
-        xp += (size_t)8 * U * Tp;
-    }
-    sm_reduce4<NB>(acc, red, wave, lane);
-    if (wave == 0) {
-        float* out = Y + (size_t)blockIdx.y * R * Tp;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-                out[(size_t)(r0 + row) * Tp + n0 + 32 * nb + m] = acc[nb][e];
-            }
-    }
-}
-
-// WRW: one wave = the 32 x 128 block dW[r0 .. r0+31][q0 .. q0+127], reduction over all Pp (even, zero padded) positions.
-//   A (lane (m, h)) = Ct[p + h][r0 + m]                      coarse tensor as [p][r]
-//   B (MFMA j)      = component j of the float4 Vt[p + h][q0 + 4n]   im2col of the fine tensor as [p][(c,t)]  -> tile column n is q0 + 4n + j
-__global__ void __launch_bounds__(64) sm_wrw_kernel(const float* __restrict__ Ct, const float* __restrict__ Vt, int R, int Q, int Pp, float* __restrict__ dW)
-{
-    const int lane = threadIdx.x, m = lane & 31, h = lane >> 5;
-    const int q0 = blockIdx.x * 128, r0 = blockIdx.y * 32;
-    f32x16 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.0f;
-    const float* cp = Ct + (size_t)h * R + r0 + m;
-    const float* vp = Vt + (size_t)h * Q + q0 + 4 * m;
-    constexpr int U = 4;
-    for (int p = 0; p < Pp; p += 2 * U) {
-        float av[U];
-        f32x4v b[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = p + 2 * u < Pp;
-            av[u] = ok ? cp[(size_t)2 * u * R] : 0.0f;
-            b[u] = ok ? *reinterpret_cast<const f32x4v*>(vp + (size_t)2 * u * Q) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b[u][j], acc[j], 0, 0, 0);
-        cp += (size_t)2 * U * R;
-        vp += (size_t)2 * U * Q;
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-        *reinterpret_cast<f32x4v*>(dW + (size_t)(r0 + row) * Q + q0 + 4 * m) = f32x4v{acc[0][e], acc[1][e], acc[2][e], acc[3][e]};
-    }
-}
-
-struct SmPlan { int P, Tp, Pp, Q, nb, ngroups, nslab, per_slab; size_t a_floats, b_floats, m_floats, total_bytes; };
-
-// op 0 (DATA): in [B][R][Ho][Wo], W [R][Cq][k][k] -> out [B][Cq][Hf][Wf].   op 1 (WRW): coarse [B][R][Ho][Wo], fine [B][Cq][Hf][Wf]
-// -> dW [R][Cq][k][k].   op 2 (FWD): fine [B][Cq][Hf][Wf], W -> out [B][R][Ho][Wo].   (R = the weight's first channel dimension.)
-static int sm_plan(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf, int k, int st, int pad, int dil, SmPlan* p)
-{
-    if (op < 0 || op > 2) return fail(IPSR_ERR_INVALID, "small-map convolution: op %d", op);
-    if (k < 1 || k > 4 || st < 1 || st > 2 || dil < 1 || pad < 0) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: k%d s%d p%d d%d", k, st, pad, dil);
-    if (Ho != (Hf + 2 * pad - dil * (k - 1) - 1) / st + 1 || Wo != (Wf + 2 * pad - dil * (k - 1) - 1) / st + 1)
-        return fail(IPSR_ERR_INVALID, "small-map convolution: %dx%d is not the output grid of %dx%d under k%d s%d p%d d%d", Ho, Wo, Hf, Wf, k, st, pad, dil);
-    p->P = B * Ho * Wo;
-    p->Q = Cq * k * k;
-    if (p->Q % 128 != 0) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: %d x %d taps is not a multiple of 128", Cq, k * k);
-    if (R % 32 != 0) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: %d weight rows are not a multiple of 32", R);
-    if (p->P > 1024) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: %d positions (made for <= 1024)", p->P);
-    const int blocks = (p->P + 31) / 32;                           // 32-wide position blocks
-    p->nb = blocks >= 4 ? 4 : (blocks == 3 ? 4 : blocks);          // 1, 2 or 4 per wave
-    if (op == 0 && p->nb == 4) p->nb = 2;                          // DATA keeps 4 accumulator tiles per position block: 2 blocks fill the registers
-    p->ngroups = (blocks + p->nb - 1) / p->nb;
-    p->Tp = p->ngroups * p->nb * 32;
-    p->Pp = (p->P + 1) & ~1;
-    p->a_floats = p->b_floats = p->m_floats = 0;
-    p->nslab = 1; p->per_slab = 0;
-    // waves in flight ~ 1024 (one per SIMD) when the slab count allows it: a slab costs its write + its read in the post-pass, so it is
-    // capped where that traffic would pass half the weight stream
-    const size_t w_bytes = (size_t)R * p->Q * 4;
-    if (op == 0) {
-        const int qb = p->Q / 128;
-        const size_t slab_bytes = (size_t)p->Q * p->Tp * 4;
-        const int cap = (int)std::max<size_t>(1, w_bytes / slab_bytes);
-        int ns = std::max(1, std::min({R / 64, cap, (256 + qb * p->ngroups - 1) / (qb * p->ngroups)}));
-        p->per_slab = (((R + 4 * ns - 1) / (4 * ns)) + 1) & ~1;                      // rows per WAVE (even)
-        p->nslab = (R + 4 * p->per_slab - 1) / (4 * p->per_slab);
-        p->b_floats = (size_t)R * p->Tp;
-        p->m_floats = (size_t)p->nslab * p->Q * p->Tp;
-    } else if (op == 2) {
-        const int rb = R / 32;
-        const size_t slab_bytes = (size_t)R * p->Tp * 4;
-        const int cap = (int)std::max<size_t>(1, w_bytes / slab_bytes);
-        int ns = std::max(1, std::min({p->Q / 256, cap, (256 + rb * p->ngroups - 1) / (rb * p->ngroups)}));
-        p->per_slab = (((p->Q + 4 * ns - 1) / (4 * ns)) + 7) & ~7;                   // columns per WAVE (multiple of 8)
-        p->nslab = (p->Q + 4 * p->per_slab - 1) / (4 * p->per_slab);
-        p->b_floats = (size_t)p->Q * p->Tp;
-        p->m_floats = (size_t)p->nslab * R * p->Tp;
-    } else {
-        p->a_floats = (size_t)p->Pp * R;
-        p->b_floats = (size_t)p->Pp * p->Q;
-    }
-    p->total_bytes = align_up(p->a_floats * 4, 256) + align_up(p->b_floats * 4, 256) + align_up(p->m_floats * 4, 256) + 256;
-    return IPSR_OK;
-}
-
-size_t smallmap_ws_bytes(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf, int k, int st, int pad, int dil)
-{
-    SmPlan p;
-    if (sm_plan(op, B, R, Cq, Ho, Wo, Hf, Wf, k, st, pad, dil, &p) != IPSR_OK) return 0;
-    return p.total_bytes;
-}
-
-int launch_smallmap(int op, const float* a, const float* b2, float* out, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf,
-                    int k, int st_, int pad, int dil, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    SmPlan p;
-    if (int rc = sm_plan(op, B, R, Cq, Ho, Wo, Hf, Wf, k, st_, pad, dil, &p)) return rc;
-    if (ws_bytes < p.total_bytes) return fail(IPSR_ERR_WORKSPACE, "small-map convolution: workspace %zu < %zu", ws_bytes, p.total_bytes);
-    Carver cv(ws, ws_bytes);
-    float* A = cv.take<float>(p.a_floats);
-    float* Bv = cv.take<float>(p.b_floats);
-    float* Mo = cv.take<float>(p.m_floats);
-    if (op == 0) {          // a = in, b2 = W
-        sm_to_cn_kernel<<<dim3(cdiv(p.Tp, 256), R), 256, 0, st>>>(a, B, R, Ho * Wo, p.Tp, Bv);
-        const dim3 grid(p.Q / 128, p.nslab, p.ngroups);
-        if (p.nb == 1) sm_data_kernel<1><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else sm_data_kernel<2><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        if (int rc = check_launch("sm_data_kernel")) return rc;
-        const size_t total = (size_t)B * Cq * Hf * Wf;
-        sm_col2im_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Mo, p.nslab, (size_t)p.Q * p.Tp, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, out);
-        return check_launch("sm_col2im_kernel");
-    }
-    if (op == 2) {          // a = fine, b2 = W
-        sm_im2col_cn_kernel<<<dim3(cdiv(p.Tp, 256), p.Q), 256, 0, st>>>(a, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, Bv);
-        const dim3 grid(R / 32, p.nslab, p.ngroups);
-        if (p.nb == 1) sm_fwd_kernel<1><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else if (p.nb == 2) sm_fwd_kernel<2><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else sm_fwd_kernel<4><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        if (int rc = check_launch("sm_fwd_kernel")) return rc;
-        const size_t total = (size_t)B * R * Ho * Wo;
-        sm_sum_to_nchw_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Mo, p.nslab, (size_t)R * p.Tp, B, R, Ho * Wo, p.Tp, out);
-        return check_launch("sm_sum_to_nchw_kernel");
-    }
-    // op 1: a = coarse, b2 = fine
-    sm_to_nc_kernel<<<dim3(cdiv(R, 256), p.Pp), 256, 0, st>>>(a, B, R, Ho * Wo, A);
-    sm_im2col_nt_kernel<<<dim3(cdiv(p.Q, 256), p.Pp), 256, 0, st>>>(b2, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, Bv);
-    sm_wrw_kernel<<<dim3(p.Q / 128, R / 32), 64, 0, st>>>(A, Bv, R, p.Q, p.Pp, out);
-    return check_launch("sm_wrw_kernel");
 }
 
 }  // namespace ipsr
@@ -2265,23 +1877,6 @@ int ipsr_conv4x4s2_winograd(int mode, const float* a, const float* b, float* out
                             void* ws, size_t ws_bytes, void* stream)
 {
     return ipsr_conv4x4s2_winograd_mp(mode, a, b, out, B, Kc, Cf, nh, nw, 0, 0, ws, ws_bytes, stream);
-}
-
-size_t ipsr_conv_smallmap_workspace_bytes(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf, int k, int stride, int pad, int dil)
-{
-    if (B < 1 || R < 1 || Cq < 1 || Ho < 1 || Wo < 1 || Hf < 1 || Wf < 1) return 0;
-    return smallmap_ws_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil);
-}
-
-int ipsr_conv_smallmap(int op, const float* a, const float* b, float* out, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf,
-                       int k, int stride, int pad, int dil, void* ws, size_t ws_bytes, void* stream)
-{
-    if (!a || !b || !out || !ws) return fail(IPSR_ERR_INVALID, "ipsr_conv_smallmap: null pointer");
-    if (B < 1 || R < 1 || Cq < 1 || Ho < 1 || Wo < 1 || Hf < 1 || Wf < 1) return fail(IPSR_ERR_INVALID, "ipsr_conv_smallmap: bad argument");
-    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u) || (reinterpret_cast<uintptr_t>(a) & 15u) ||
-        (reinterpret_cast<uintptr_t>(b) & 15u))
-        return fail(IPSR_ERR_INVALID, "ipsr_conv_smallmap: operands / workspace must be 16-byte aligned");
-    return launch_smallmap(op, a, b, out, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_winograd_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)

@@ -1,4 +1,4 @@
-"""The two fp32 matrix-core launchers restated in Python: `sm_plan` of csrc/winograd.hip (ipsr_conv_smallmap) and `make_plan` /
+"""The two fp32 matrix-core launchers restated in Python: `sm_plan` of csrc/smallmap.hip (ipsr_conv_smallmap) and `make_plan` /
 `choose_split` / `launch_conv_gemm` of csrc/conv_gemm.hip (ipsr_conv2d) — which kernel instantiation, grid, slab or split a shape reaches.
 
 A plain module (like thin_conv_plan.py, bf16_conv_plan.py, guarded.py).  tests/test_fp32_conv_plan.py ties it to the built library
@@ -29,7 +29,7 @@ def c_div(a, b):
 
 
 def conv_out_dim(op, n, k, stride, pad, dil):
-    """conv_gemm.hip:478-482 (`conv_out_dim`) and winograd.hip:2033.  Where the window overhangs the padded input by less than the
+    """conv_gemm.hip:478-482 (`conv_out_dim`) and the grid check of `sm_plan` (smallmap.hip).  Where the window overhangs the padded input by less than the
     stride (span in -stride + 1 .. -1, e.g. k4 s2 p1 on a 1 x 1 map) C's division answers 1 where floor answers 0: both entry points
     serve that shape as one output position whose window is cut by the (bounds-checked) taps.  torch refuses such a module call, so the
     nets never get there; the mirror restates the library as it is."""
@@ -40,7 +40,7 @@ def conv_out_dim(op, n, k, stride, pad, dil):
 
 # ---- ipsr_conv_smallmap ----------------------------------------------------------------------------------------------------------------
 def _waves(total, per, nslab):
-    """The reduction ranges [a, b) of the 4 * nslab waves (winograd.hip:1888, :1944): wave w of slab s starts at min(total, (4 s + w) per)."""
+    """The reduction ranges [a, b) of the 4 * nslab waves (smallmap.hip: `ra` / `rb` of sm_data_kernel, `qa` / `qb` of sm_fwd_kernel): wave w of slab s starts at min(total, (4 s + w) per)."""
     out = []
     for i in range(4 * nslab):
         a = min(total, i * per)
@@ -50,33 +50,33 @@ def _waves(total, per, nslab):
 
 def _wave_facts(waves, per, group):
     """Short waves (range cut by the end of the reduction), idle ones (`ra == rb`), and whether some live wave's range is no multiple of
-    the unroll group, i.e. the `ok` guard of a partly filled group fires (winograd.hip:1904, :1958, :2007)."""
+    the unroll group, i.e. the `ok` guard of a partly filled group fires (smallmap.hip: sm_data_kernel, sm_fwd_kernel, sm_wrw_kernel)."""
     lens = [b - a for a, b in waves]
     return dict(short_waves=sum(1 for n in lens if 0 < n < per), idle_waves=sum(1 for n in lens if n == 0),
                 partial_group=any(n % group for n in lens if n), full_groups=any(n >= group for n in lens), group=group)
 
 
 def sm_plan(op, B, R, Cq, Ho, Wo, Hf, Wf, k, st, pad, dil):
-    """winograd.hip:2270-2274 (the entry's argument check) and :2029-2075 (`sm_plan`); the kernel and grid of :2094-2119."""
+    """smallmap.hip: the argument check of ipsr_conv_smallmap_workspace_bytes and `sm_plan`; the kernel and grid of `launch_smallmap`."""
     if min(B, R, Cq, Ho, Wo, Hf, Wf) < 1 or op not in (SM_DATA, SM_WRW, SM_FWD):
         return None
-    if k < 1 or k > 4 or st < 1 or st > 2 or dil < 1 or pad < 0:                          # :2032
+    if k < 1 or k > 4 or st < 1 or st > 2 or dil < 1 or pad < 0:                          # sm_plan: k, stride, dilation, pad
         return None
-    if Ho != conv_out_dim(CONV_FWD, Hf, k, st, pad, dil) or Wo != conv_out_dim(CONV_FWD, Wf, k, st, pad, dil):      # :2033-2034
+    if Ho != conv_out_dim(CONV_FWD, Hf, k, st, pad, dil) or Wo != conv_out_dim(CONV_FWD, Wf, k, st, pad, dil):      # sm_plan: the output grid
         return None
     P, Q = B * Ho * Wo, Cq * k * k
-    if Q % 128 != 0 or R % 32 != 0 or P > 1024:                                           # :2037-2039
+    if Q % 128 != 0 or R % 32 != 0 or P > 1024:                                           # sm_plan: Q, R, P
         return None
     blocks = cdiv(P, 32)
-    nb = 4 if blocks >= 3 else blocks                                                     # :2041
-    if op == SM_DATA and nb == 4:                                                         # :2042
+    nb = 4 if blocks >= 3 else blocks                                                     # sm_plan: nb
+    if op == SM_DATA and nb == 4:                                                         # sm_plan: nb of op 0
         nb = 2
     ngroups = cdiv(blocks, nb)
     Tp, Pp = ngroups * nb * 32, (P + 1) & ~1
     a_floats = b_floats = m_floats = 0
     nslab, per_slab = 1, 0
     w_bytes = R * Q * 4
-    if op == SM_DATA:                                                                     # :2051-2059
+    if op == SM_DATA:                                                                     # sm_plan: op 0
         qb = Q // 128
         cap = max(1, w_bytes // (Q * Tp * 4))
         ns = max(1, min(R // 64, cap, (256 + qb * ngroups - 1) // (qb * ngroups)))
@@ -85,8 +85,8 @@ def sm_plan(op, B, R, Cq, Ho, Wo, Hf, Wf, k, st, pad, dil):
         b_floats, m_floats = R * Tp, nslab * Q * Tp
         kernel, grid = "sm_data_kernel<%d>" % nb, (Q // 128, nslab, ngroups)
         waves = _waves(R, per_slab, nslab)
-        facts = _wave_facts(waves, per_slab, 2 * {1: 8, 2: 4, 4: 2}[nb])                 # :1898
-    elif op == SM_FWD:                                                                    # :2060-2068
+        facts = _wave_facts(waves, per_slab, 2 * {1: 8, 2: 4, 4: 2}[nb])                 # U of sm_data_kernel
+    elif op == SM_FWD:                                                                    # sm_plan: op 2
         rb = R // 32
         cap = max(1, w_bytes // (R * Tp * 4))
         ns = max(1, min(Q // 256, cap, (256 + rb * ngroups - 1) // (rb * ngroups)))
@@ -95,12 +95,12 @@ def sm_plan(op, B, R, Cq, Ho, Wo, Hf, Wf, k, st, pad, dil):
         b_floats, m_floats = Q * Tp, nslab * R * Tp
         kernel, grid = "sm_fwd_kernel<%d>" % nb, (R // 32, nslab, ngroups)
         waves = _waves(Q, per_slab, nslab)
-        facts = _wave_facts(waves, per_slab, 32)                                          # :1952
-    else:                                                                                 # :2070-2071
+        facts = _wave_facts(waves, per_slab, 32)                                          # U of sm_fwd_kernel
+    else:                                                                                 # sm_plan: op 1
         a_floats, b_floats = Pp * R, Pp * Q
         kernel, grid = "sm_wrw_kernel", (Q // 128, R // 32, 1)
         waves = [(0, Pp)]
-        facts = _wave_facts(waves, Pp, 8)                                                 # :2001-2002
+        facts = _wave_facts(waves, Pp, 8)                                                 # sm_wrw_kernel
     ws = align_up(a_floats * 4, 256) + align_up(b_floats * 4, 256) + align_up(m_floats * 4, 256) + 256
     return dict(op=op, kernel=kernel, grid=grid, P=P, Q=Q, R=R, blocks=blocks, nb=nb, ngroups=ngroups, Tp=Tp, Pp=Pp, nslab=nslab, per_slab=per_slab,
                 waves=waves, zero_blocks=Tp // 32 - blocks, padded_columns=Tp - P, zero_row=Pp - P, ws=ws, **facts)
@@ -395,37 +395,37 @@ def _stages(NT, n):
     return _cg(lambda c, p: c["NT"] == NT and c["ksplit"] == 1 and c["nstage"] == n)
 
 
-_W, _G = "winograd.hip", "conv_gemm.hip"
+_S, _G = "smallmap.hip", "conv_gemm.hip"
 VARIANTS = (
-    ("sm_data_kernel<1>", _W + ":2041, :2097", _sm(D, nb=1), ("conv8_224_6x6_k4s2_b1:data", "conv24_32_8x8_k4s2_b1:data")),
-    ("sm_data_kernel<2>, one group", _W + ":2041-2042, :2098", _sm(D, nb=2, ngroups=1), ("conv32_160_5x5_k4s1_b3:data",)),
-    ("sm_data_kernel<2>: blockIdx.z > 0, the last group half zero blocks", _W + ":2043, :1887", lambda p: _sm(D, nb=2)(p) and p["ngroups"] >= 2 and p["zero_blocks"] == 1,
+    ("sm_data_kernel<1>", _S + ": sm_plan nb, launch_smallmap", _sm(D, nb=1), ("conv8_224_6x6_k4s2_b1:data", "conv24_32_8x8_k4s2_b1:data")),
+    ("sm_data_kernel<2>, one group", _S + ": sm_plan nb (DATA), launch_smallmap", _sm(D, nb=2, ngroups=1), ("conv32_160_5x5_k4s1_b3:data",)),
+    ("sm_data_kernel<2>: blockIdx.z > 0, the last group half zero blocks", _S + ": sm_plan ngroups, sm_data_kernel", lambda p: _sm(D, nb=2)(p) and p["ngroups"] >= 2 and p["zero_blocks"] == 1,
      ("conv8_32_12x12_k4s2_b2:data", "conv8_32_20x20_k4s2_b2:data")),
-    ("sm_data_kernel<2>: blockIdx.z > 0, a ragged last block", _W + ":2043, :1887", lambda p: _sm(D, nb=2)(p) and p["ngroups"] >= 2 and p["P"] % 32 != 0,
+    ("sm_data_kernel<2>: blockIdx.z > 0, a ragged last block", _S + ": sm_plan ngroups, sm_data_kernel", lambda p: _sm(D, nb=2)(p) and p["ngroups"] >= 2 and p["P"] % 32 != 0,
      ("conv8_32_18x14_k4s2_b2:data", "conv8_32_12x12_k4s2_b2:data")),
-    ("sm_data_kernel<2>: 16 groups at the limit of 1024 positions", _W + ":2039", _sm(D, P=1024, ngroups=16), ("conv8_64_32x32_k4s2_b4:data",)),
-    ("sm_data_kernel: three slabs, a short wave (4 of 20 rows)", _W + ":2055-2057, :1888", lambda p: _sm(D, nslab=3, per_slab=20, short_waves=1)(p),
+    ("sm_data_kernel<2>: 16 groups at the limit of 1024 positions", _S + ": sm_plan, P > 1024", _sm(D, P=1024, ngroups=16), ("conv8_64_32x32_k4s2_b4:data",)),
+    ("sm_data_kernel: three slabs, a short wave (4 of 20 rows)", _S + ": sm_plan slabs, sm_data_kernel", lambda p: _sm(D, nslab=3, per_slab=20, short_waves=1)(p),
      ("conv8_224_6x6_k4s2_b1:data", "convT224_8_3x3_k4s2_b1:data")),
-    ("sm_data_kernel<1>: a full unroll group and a partly filled one", _W + ":1898-1904", lambda p: _sm(D, nb=1, partial_group=True, full_groups=True)(p),
+    ("sm_data_kernel<1>: a full unroll group and a partly filled one", _S + ": sm_data_kernel unroll loop", lambda p: _sm(D, nb=1, partial_group=True, full_groups=True)(p),
      ("conv128_96_3x3_k3s1_b1:data", "conv8_224_6x6_k4s2_b1:data")),
-    ("sm_data_kernel<1>: half an unroll group only", _W + ":1898-1904", _sm(D, nb=1, per_slab=8, full_groups=False), ("conv24_32_8x8_k4s2_b1:data", "conv120_32_8x8_k4s2_b1:data")),
-    ("sm_data_kernel<2>: a partly filled unroll group", _W + ":1898-1904", _sm(D, nb=2, partial_group=True), ("conv32_160_5x5_k4s1_b3:data",)),
-    ("sm_fwd_kernel<1>", _W + ":2041, :2107", _sm(FW, nb=1), ("conv8_224_6x6_k4s2_b1:fwd", "conv24_32_8x8_k4s2_b1:fwd")),
-    ("sm_fwd_kernel<2>", _W + ":2041, :2108", _sm(FW, nb=2), ("conv32_160_5x5_k4s1_b3:fwd",)),
-    ("sm_fwd_kernel<4> with one all-zero block (three position blocks)", _W + ":2041, :2109", _sm(FW, nb=4, blocks=3, zero_blocks=1), ("conv8_32_12x12_k4s2_b2:fwd",)),
-    ("sm_fwd_kernel<4> with a ragged last block", _W + ":2041, :2109", _sm(FW, nb=4, blocks=4, padded_columns=2), ("conv8_32_18x14_k4s2_b2:fwd",)),
-    ("sm_fwd_kernel<4>: blockIdx.z > 0", _W + ":2043, :1943", lambda p: _sm(FW, nb=4)(p) and p["ngroups"] >= 2, ("conv8_32_20x20_k4s2_b2:fwd", "conv8_64_32x32_k4s2_b4:fwd")),
-    ("sm_fwd_kernel<4>: 8 groups at the limit of 1024 positions", _W + ":2039", _sm(FW, P=1024, ngroups=8), ("conv8_64_32x32_k4s2_b4:fwd",)),
-    ("sm_fwd_kernel: four slabs of 72 columns (two groups and one 8-column step over)", _W + ":2064-2066, :1958", _sm(FW, per_slab=72, nslab=4, partial_group=True),
+    ("sm_data_kernel<1>: half an unroll group only", _S + ": sm_data_kernel unroll loop", _sm(D, nb=1, per_slab=8, full_groups=False), ("conv24_32_8x8_k4s2_b1:data", "conv120_32_8x8_k4s2_b1:data")),
+    ("sm_data_kernel<2>: a partly filled unroll group", _S + ": sm_data_kernel unroll loop", _sm(D, nb=2, partial_group=True), ("conv32_160_5x5_k4s1_b3:data",)),
+    ("sm_fwd_kernel<1>", _S + ": sm_plan nb, launch_smallmap", _sm(FW, nb=1), ("conv8_224_6x6_k4s2_b1:fwd", "conv24_32_8x8_k4s2_b1:fwd")),
+    ("sm_fwd_kernel<2>", _S + ": sm_plan nb, launch_smallmap", _sm(FW, nb=2), ("conv32_160_5x5_k4s1_b3:fwd",)),
+    ("sm_fwd_kernel<4> with one all-zero block (three position blocks)", _S + ": sm_plan nb, launch_smallmap", _sm(FW, nb=4, blocks=3, zero_blocks=1), ("conv8_32_12x12_k4s2_b2:fwd",)),
+    ("sm_fwd_kernel<4> with a ragged last block", _S + ": sm_plan nb, launch_smallmap", _sm(FW, nb=4, blocks=4, padded_columns=2), ("conv8_32_18x14_k4s2_b2:fwd",)),
+    ("sm_fwd_kernel<4>: blockIdx.z > 0", _S + ": sm_plan ngroups, sm_fwd_kernel", lambda p: _sm(FW, nb=4)(p) and p["ngroups"] >= 2, ("conv8_32_20x20_k4s2_b2:fwd", "conv8_64_32x32_k4s2_b4:fwd")),
+    ("sm_fwd_kernel<4>: 8 groups at the limit of 1024 positions", _S + ": sm_plan, P > 1024", _sm(FW, P=1024, ngroups=8), ("conv8_64_32x32_k4s2_b4:fwd",)),
+    ("sm_fwd_kernel: four slabs of 72 columns (two groups and one 8-column step over)", _S + ": sm_plan slabs, sm_fwd_kernel `ok`", _sm(FW, per_slab=72, nslab=4, partial_group=True),
      ("conv128_96_3x3_k3s1_b1:fwd",)),
-    ("sm_fwd_kernel: a short wave and an idle wave (`qa == qb`)", _W + ":2064-2066, :1944", lambda p: _sm(FW)(p) and p["short_waves"] >= 1 and p["idle_waves"] >= 1,
+    ("sm_fwd_kernel: a short wave and an idle wave (`qa == qb`)", _S + ": sm_plan slabs, sm_fwd_kernel", lambda p: _sm(FW)(p) and p["short_waves"] >= 1 and p["idle_waves"] >= 1,
      ("conv120_32_8x8_k4s2_b1:fwd",)),
-    ("sm_wrw_kernel: odd P, the zero row of Pp is read", _W + ":2045, :2116", lambda p: _sm(WG)(p) and p["zero_row"] == 1,
+    ("sm_wrw_kernel: odd P, the zero row of Pp is read", _S + ": sm_plan Pp, launch_smallmap", lambda p: _sm(WG)(p) and p["zero_row"] == 1,
      ("conv8_224_6x6_k4s2_b1:wrw", "convT224_8_3x3_k4s2_b1:wrw", "conv128_96_3x3_k3s1_b1:wrw")),
-    ("sm_wrw_kernel: a partly filled unroll group (Pp % 8 != 0)", _W + ":2001-2007", _sm(WG, partial_group=True),
+    ("sm_wrw_kernel: a partly filled unroll group (Pp % 8 != 0)", _S + ": sm_wrw_kernel unroll loop", _sm(WG, partial_group=True),
      ("conv8_224_6x6_k4s2_b1:wrw", "conv8_32_18x14_k4s2_b2:wrw")),
-    ("sm_wrw_kernel: 1024 positions", _W + ":2039", _sm(WG, Pp=1024), ("conv8_64_32x32_k4s2_b4:wrw",)),
-    ("sm_wrw_kernel: more than one block on x and y", _W + ":2118", lambda p: _sm(WG)(p) and p["grid"][0] >= 2 and p["grid"][1] >= 2,
+    ("sm_wrw_kernel: 1024 positions", _S + ": sm_plan, P > 1024", _sm(WG, Pp=1024), ("conv8_64_32x32_k4s2_b4:wrw",)),
+    ("sm_wrw_kernel: more than one block on x and y", _S + ": launch_smallmap, op 1 grid", lambda p: _sm(WG)(p) and p["grid"][0] >= 2 and p["grid"][1] >= 2,
      ("conv128_96_3x3_k3s1_b1:wrw", "conv32_160_5x5_k4s1_b3:wrw")),
     ("conv_gemm_kernel<9>: 1 stage", _G + ":180-184", _stages(9, 1), ("conv2_9x7_c5_k3_b1:fwd", "convT30_5x6_c2_k3_b2:bwd")),
     ("conv_gemm_kernel<9>: 2 stages", _G + ":181", _stages(9, 2), ("conv4_9x7_c6_k3_b2:fwd", "conv4_13x11_c6_k3s3_b2:fwd")),

@@ -56,26 +56,26 @@ CASES = [
     ("ipsr_conv3x3_bf16_wrw",
      lambda p: (0, _P(p, "x", 0), _P(p, "dy", 1), _P(p, "dw", 2), 2, 32, 16, 16, 48, _P(p, "ws", 3), WS, None),
      [("x", 8, "16-byte fragment reads"), ("dy", 8, "16-byte fragment reads"), ("ws", 8, "workspace vectors")]),
-    # winograd.hip: wino_input_kernel reads a window's inner four columns as one ld4 (:298) when W % 4 == 0; the tile output stores
-    # st4 (:400); the polyphase filter transforms read each 4x4 weight as four float4 (:1389, :1432); the k4 weight gradients store
-    # float4 (:1192)
+    # winograd.hip: wino_input_kernel reads a window's inner four columns as one ld4 when W % 4 == 0; the tile output stores
+    # st4 (wino_output_kernel); the polyphase filter transforms read each 4x4 weight as four float4 (wino52_filter_kernel,
+    # wino52_filter_split_kernel); the k4 weight gradients store float4 (wino_wrw_output4_kernel)
     ("ipsr_conv3x3_winograd_mp",
      lambda p: (0, _P(p, "in", 0), _P(p, "weight", 1), None, 0, _P(p, "filter_cache", 4), 0, _P(p, "out", 2), 2, 32, 16, 16, 48, 0, 0,
                 _P(p, "ws", 3), WS, None),
-     [("in", 8, "winograd.hip:298 ld4 of fp32 activations"), ("out", 8, "winograd.hip:400 st4"), ("filter_cache", 8, "transformed filter vectors"),
+     [("in", 8, "wino_input_kernel: ld4 of fp32 activations"), ("out", 8, "wino_output_kernel: st4"), ("filter_cache", 8, "transformed filter vectors"),
       ("ws", 8, "workspace vectors")]),
     ("ipsr_conv3x3_winograd_mp",              # bf16 activations in (io = 1): a vector is 8 bytes
      lambda p: (1, _P(p, "in", 0), _P(p, "weight", 1), None, 0, None, 0, _P(p, "out", 2), 2, 32, 16, 16, 48, 0, 1, _P(p, "ws", 3), WS, None),
-     [("in", 4, "winograd.hip:298 ld4 of bf16 activations (8 bytes)")]),
+     [("in", 4, "wino_input_kernel: ld4 of bf16 activations (8 bytes)")]),
     ("ipsr_conv4x4s2_winograd_mp",
      lambda p: (0, _P(p, "a", 0), _P(p, "b", 1), _P(p, "out", 2), 2, 32, 16, 8, 8, 0, 0, _P(p, "ws", 3), WS, None),
-     [("b", 8, "winograd.hip:1389 float4 reads of the weight"), ("b", 4, "winograd.hip:1389"), ("out", 8, "output vectors"), ("ws", 8, "workspace")]),
+     [("b", 8, "wino52_filter_kernel: float4 reads of the weight"), ("b", 4, "wino52_filter_kernel"), ("out", 8, "output vectors"), ("ws", 8, "workspace")]),
     ("ipsr_conv4x4s2_winograd_mp",            # coarse -> fine under the split-bf16 arithmetic: the split filter transform
      lambda p: (1, _P(p, "a", 0), _P(p, "b", 1), _P(p, "out", 2), 2, 32, 16, 8, 8, 2, 0, _P(p, "ws", 3), WS, None),
-     [("b", 8, "winograd.hip:1432 float4 reads of the weight")]),
+     [("b", 8, "wino52_filter_split_kernel: float4 reads of the weight")]),
     ("ipsr_conv4x4_winograd_mp",
      lambda p: (0, 2, _P(p, "a", 0), _P(p, "b", 1), _P(p, "out", 2), 2, 32, 16, 16, 48, 0, 0, _P(p, "ws", 3), WS, None),
-     [("out", 8, "winograd.hip:1192 float4 store of the weight gradient"), ("ws", 8, "workspace")]),
+     [("out", 8, "wino_wrw_output4_kernel: float4 store of the weight gradient"), ("ws", 8, "workspace")]),
     ("ipsr_conv_smallmap",
      lambda p: (2, _P(p, "a", 0), _P(p, "b", 1), _P(p, "out", 2), 2, 128, 128, 4, 4, 8, 8, 4, 2, 1, 1, _P(p, "ws", 3), WS, None),
      [("a", 8, "operand vectors"), ("b", 8, "the weight read in place as a GEMM operand"), ("out", 8, "output vectors")]),

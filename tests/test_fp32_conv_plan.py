@@ -1,4 +1,4 @@
-"""tests/fp32_conv_plan.py (the Python restatement of `sm_plan` of csrc/winograd.hip and of `make_plan` / `choose_split` /
+"""tests/fp32_conv_plan.py (the Python restatement of `sm_plan` of csrc/smallmap.hip and of `make_plan` / `choose_split` /
 `launch_conv_gemm` of csrc/conv_gemm.hip) against the built library, without a GPU.
 
 The two workspace queries are host functions of the shape, 0 exactly where the entry point refuses:

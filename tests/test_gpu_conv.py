@@ -629,7 +629,7 @@ def test_split_bf16_winograd_arithmetic_all_families(math, io_bf16):
 #   thin        rounded: csrc/thin_conv.hip:47 / :98 (thin_rb when a side is bf16) rounded: csrc/thin_conv.hip:64 / :126
 #   thin_mfma   (weight gradient: does not read the weights)                      rounded: csrc/thin_conv.hip:355 (f2bf2); `_thin_mfma_wrw`
 #   winograd, wino_dil, wino_s2 (bf16x3)
-#               split, not rounded: csrc/winograd.hip:123-126 (hi + lo bf16)      split as well; the weight gradient reads x cast to
+#               split, not rounded: csrc/winograd.hip: store_split (hi + lo)      split as well; the weight gradient reads x cast to
 #                                                                                 dy's dtype (`_run_wrw`, `_ENGINES[...].wrw_x_as_dy`)
 #   one, smallmap   fp32 weights                                                  exact fp32 copies (`_run_data` / `_run_wrw`,
 #                                                                                 `_ENGINES[...].fp32_copies`)

@@ -1,5 +1,5 @@
 """The two fp32 matrix-core convolution engines in every launch variant, against torch in fp64 on the GPU: ipsr_conv_smallmap (the
-`sm_*` kernels of csrc/winograd.hip, planned by `sm_plan`) and ipsr_conv2d (csrc/conv_gemm.hip, planned by `make_plan` / `choose_split`).
+`sm_*` kernels of csrc/smallmap.hip, planned by `sm_plan`) and ipsr_conv2d (csrc/conv_gemm.hip, planned by `make_plan` / `choose_split`).
 
 Every case goes through `ops.conv_smallmap` / `ops.conv2d`.  tests/fp32_conv_plan.py restates the two launchers and holds the case
 tables; tests/test_fp32_conv_plan.py proves without a GPU that the tables reach every row below, and each test here asserts its own
@@ -7,74 +7,74 @@ rows again (`P.check_case`) before it compares numbers.  A case id names the mod
 batch); the pass after the colon is data | wrw | fwd of ipsr_conv_smallmap, or fwd | bwd (the module's forward / input gradient) of
 ipsr_conv2d.
 
-  variant                                                                                       selected at                    case id:pass
-  --------------------------------------------------------------------------------------------  -----------------------------  ----------------------------------------
-  sm_data_kernel<1>                                                                             winograd.hip:2041, :2097       conv8_224_6x6_k4s2_b1:data, conv24_32_8x8_k4s2_b1:data
-  sm_data_kernel<2>, one group                                                                  winograd.hip:2041-2042, :2098  conv32_160_5x5_k4s1_b3:data
-  sm_data_kernel<2>: blockIdx.z > 0, the last group half zero blocks                            winograd.hip:2043, :1887       conv8_32_12x12_k4s2_b2:data, conv8_32_20x20_k4s2_b2:data
-  sm_data_kernel<2>: blockIdx.z > 0, a ragged last block                                        winograd.hip:2043, :1887       conv8_32_18x14_k4s2_b2:data, conv8_32_12x12_k4s2_b2:data
-  sm_data_kernel<2>: 16 groups at the limit of 1024 positions                                   winograd.hip:2039              conv8_64_32x32_k4s2_b4:data
-  sm_data_kernel: three slabs, a short wave (4 of 20 rows)                                      winograd.hip:2055-2057, :1888  conv8_224_6x6_k4s2_b1:data, convT224_8_3x3_k4s2_b1:data
-  sm_data_kernel<1>: a full unroll group and a partly filled one                                winograd.hip:1898-1904         conv128_96_3x3_k3s1_b1:data, conv8_224_6x6_k4s2_b1:data
-  sm_data_kernel<1>: half an unroll group only                                                  winograd.hip:1898-1904         conv24_32_8x8_k4s2_b1:data, conv120_32_8x8_k4s2_b1:data
-  sm_data_kernel<2>: a partly filled unroll group                                               winograd.hip:1898-1904         conv32_160_5x5_k4s1_b3:data
-  sm_fwd_kernel<1>                                                                              winograd.hip:2041, :2107       conv8_224_6x6_k4s2_b1:fwd, conv24_32_8x8_k4s2_b1:fwd
-  sm_fwd_kernel<2>                                                                              winograd.hip:2041, :2108       conv32_160_5x5_k4s1_b3:fwd
-  sm_fwd_kernel<4> with one all-zero block (three position blocks)                              winograd.hip:2041, :2109       conv8_32_12x12_k4s2_b2:fwd
-  sm_fwd_kernel<4> with a ragged last block                                                     winograd.hip:2041, :2109       conv8_32_18x14_k4s2_b2:fwd
-  sm_fwd_kernel<4>: blockIdx.z > 0                                                              winograd.hip:2043, :1943       conv8_32_20x20_k4s2_b2:fwd, conv8_64_32x32_k4s2_b4:fwd
-  sm_fwd_kernel<4>: 8 groups at the limit of 1024 positions                                     winograd.hip:2039              conv8_64_32x32_k4s2_b4:fwd
-  sm_fwd_kernel: four slabs of 72 columns (two groups and one 8-column step over)               winograd.hip:2064-2066, :1958  conv128_96_3x3_k3s1_b1:fwd
-  sm_fwd_kernel: a short wave and an idle wave (`qa == qb`)                                     winograd.hip:2064-2066, :1944  conv120_32_8x8_k4s2_b1:fwd
-  sm_wrw_kernel: odd P, the zero row of Pp is read                                              winograd.hip:2045, :2116       conv8_224_6x6_k4s2_b1:wrw, convT224_8_3x3_k4s2_b1:wrw
-                                                                                                                               conv128_96_3x3_k3s1_b1:wrw
-  sm_wrw_kernel: a partly filled unroll group (Pp % 8 != 0)                                     winograd.hip:2001-2007         conv8_224_6x6_k4s2_b1:wrw, conv8_32_18x14_k4s2_b2:wrw
-  sm_wrw_kernel: 1024 positions                                                                 winograd.hip:2039              conv8_64_32x32_k4s2_b4:wrw
-  sm_wrw_kernel: more than one block on x and y                                                 winograd.hip:2118              conv128_96_3x3_k3s1_b1:wrw, conv32_160_5x5_k4s1_b3:wrw
-  conv_gemm_kernel<9>: 1 stage                                                                  conv_gemm.hip:180-184          conv2_9x7_c5_k3_b1:fwd, convT30_5x6_c2_k3_b2:bwd
-  conv_gemm_kernel<9>: 2 stages                                                                 conv_gemm.hip:181              conv4_9x7_c6_k3_b2:fwd, conv4_13x11_c6_k3s3_b2:fwd
-  conv_gemm_kernel<9>: 3 stages                                                                 conv_gemm.hip:182              conv6_11x13_c10_k3_b3:fwd, conv4_9x7_c6_k3_b2:bwd
-  conv_gemm_kernel<9>: 5 stages, the ring wraps                                                 conv_gemm.hip:156, :193        conv10_5x6_c30_k3_b1:fwd, conv6_11x13_c10_k3_b3:bwd
-  conv_gemm_kernel<9>: 15 stages                                                                conv_gemm.hip:334              conv10_5x6_c30_k3_b1:bwd, convT30_5x6_c2_k3_b2:fwd
-  conv_gemm_kernel<16>: 1 stage                                                                 conv_gemm.hip:180-184          conv1_12x10_c4_k4s2_b2:fwd, convT20_6x4_c1_k4s2_b1:bwd
-  conv_gemm_kernel<16>: 2 stages                                                                conv_gemm.hip:181              conv2_12x10_c8_k4s2_b1:fwd, convT12_3x5_c2_k4s2_b3:bwd
-  conv_gemm_kernel<16>: 3 stages                                                                conv_gemm.hip:182              conv3_9x11_c12_k4s2_b3:fwd, convT4_4x6_c3_k4s2_b1:bwd
-  conv_gemm_kernel<16>: 5 stages, the ring wraps                                                conv_gemm.hip:156, :193        conv5_8x8_c20_k4s2_b1:fwd, convT8_5x3_c5_k4s2_b2:bwd
-  conv_gemm_kernel<16>: 15 stages                                                               conv_gemm.hip:334              conv15_6x6_c60_k4s2_b1:fwd
-  conv_gemm_kernel<4>: 1 stage                                                                  conv_gemm.hip:180-184          conv1_12x10_c4_k4s2_b2:bwd, convT4_4x6_c3_k4s2_b1:fwd
-  conv_gemm_kernel<4>: 2 stages                                                                 conv_gemm.hip:181              conv2_12x10_c8_k4s2_b1:bwd, convT8_5x3_c5_k4s2_b2:fwd
-  conv_gemm_kernel<4>: 3 stages                                                                 conv_gemm.hip:182              conv3_9x11_c12_k4s2_b3:bwd, convT12_3x5_c2_k4s2_b3:fwd
-  conv_gemm_kernel<4>: 5 stages, the ring wraps                                                 conv_gemm.hip:156, :193        conv5_8x8_c20_k4s2_b1:bwd, convT20_6x4_c1_k4s2_b1:fwd
-  conv_gemm_kernel<4>: 15 stages                                                                conv_gemm.hip:334              conv15_6x6_c60_k4s2_b1:bwd, convT60_2x3_c4_k4s2_b2:fwd
-  split-K: two even splits of 8 stages                                                          conv_gemm.hip:334-336, :231    conv32_6x5_c136_k3_b2:fwd
-  split-K: a short last split of 2 stages (`ns > 2` false)                                      conv_gemm.hip:142, :182        conv130_9x13_c70_k3_b3:fwd
-  split-K: a short last split of 1 stage (`ns > 1` false), 16 splits                            conv_gemm.hip:142, :181        conv17_5x5_c136_k4s1_b1:bwd
-  split-K on the 16-tap kernel, last split one stage short                                      conv_gemm.hip:335-336          conv17_5x5_c136_k4s1_b1:fwd
-  two m tiles, the second with 8 live rows                                                      conv_gemm.hip:349, :238, :250  conv32_6x5_c136_k3_b2:fwd, conv17_5x5_c136_k4s1_b1:fwd
-                                                                                                                               conv4_24x23_c136_k3_b3:fwd
-  two m tiles and split-K: partial tiles of the second m tile                                   conv_gemm.hip:232-238          conv32_6x5_c136_k3_b2:fwd, conv17_5x5_c136_k4s1_b1:fwd
-  one pixel tile partly filled                                                                  conv_gemm.hip:127, :230        conv2_9x7_c5_k3_b1:fwd, conv4_9x7_c6_k3_b2:fwd
-  several pixel tiles, a ragged last one                                                        conv_gemm.hip:127, :230        conv6_11x13_c10_k3_b3:fwd, conv4_24x23_c136_k3_b3:fwd
-                                                                                                                               conv130_9x13_c70_k3_b3:fwd
-  a grid that is no multiple of 8 workgroups, above 8 (xcd_remap)                               ipsr_common.h:46-52            conv4_24x23_c136_k3_b3:fwd
-  parity classes: odd output extents, four different grids                                      conv_gemm.hip:366              conv4_21x19_c8_k4s2_b2:bwd, conv3_9x11_c12_k4s2_b3:bwd
-                                                                                                                               conv8_15x13_c4_k4s2p1d3_b2:bwd
-  parity classes without taps: need_zero, one 16-tap class                                      conv_gemm.hip:367, :411-412    conv3_12x10_c5_k4s2p3d2_b2:bwd, conv3_2x2_c5_k4s2p3d2_b3:bwd
-  the dilated input gradient on the 2 x 2 map                                                   conv_gemm.hip:366-367          conv3_2x2_c5_k4s2p3d2_b3:bwd
-  k = 2 on the direct forms: a 4-tap gather, stride 1 and 2, op 0 and op 3                      conv_gemm.hip:317, :355, :419  conv4_9x8_c8_k2s1_b2:fwd, conv8_9x8_c6_k2s2p1_b1:fwd
-                                                                                                                               convT6_5x4_c12_k2s2_b2:bwd, conv4_9x8_c8_k2s2p1d2_b1:fwd
-  k = 2 on the stride-1 transposed form (op 1)                                                  conv_gemm.hip:353, :423        conv4_9x8_c8_k2s1_b2:bwd
-  k = 2, 3 with dilation 2 on the stride-2 transposed form: all taps in one parity class        conv_gemm.hip:363-367          conv6_9x8_c4_k3s2p2d2_b2:bwd, conv4_9x8_c8_k2s2p1d2_b1:bwd
-  stride 3 on the direct forms, k3 and k4, op 0 and op 3                                        conv_gemm.hip:421, :130        conv4_13x11_c6_k3s3_b2:fwd, conv3_13x11_c6_k4s3p2_b1:fwd
-                                                                                                                               convT6_4x5_c3_k4s3_b2:bwd
-  dilation 3 on the stride-2 transposed forms: two taps per parity, offsets a step of -3 apart  conv_gemm.hip:325, :435-436    conv8_15x13_c4_k4s2p1d3_b2:bwd, convT8_4x3_c4_k4s2p1d3_b1:fwd
-  refused: 1088 positions, all three ops                                                        winograd.hip:2039              conv8_32_32x34_k4s2_b4
-  refused: k3 s2 transposed: one or two taps in a parity class                                  conv_gemm.hip:373              conv4_8x8_c4_k3s2_bwd, convT4_4x4_c4_k3s2_fwd
-  refused: k = 1: one tap                                                                       conv_gemm.hip:373              conv4_6x6_c4_k1
-  refused: k3: odd reduction channels                                                           conv_gemm.hip:376              conv3_6x6_c4_k3_odd, conv4_6x6_c3_k3_odd
-  refused: 4-tap classes: reduction channels no multiple of 4                                   conv_gemm.hip:376              convT6_4x4_c4_k4s2_mod4, conv4_8x8_c6_k4s2_mod4
-  refused: k2 direct: reduction channels no multiple of 4                                       conv_gemm.hip:376              conv6_9x8_c6_k2_mod4
-  refused: stride 3 transposed                                                                  conv_gemm.hip:358              conv4_13x11_c4_k4s3_bwd, convT4_4x5_c4_k4s3_fwd
+  variant                                                                                       selected at                                       case id:pass
+  --------------------------------------------------------------------------------------------  ------------------------------------------------  ----------------------------------------
+  sm_data_kernel<1>                                                                             smallmap.hip: sm_plan nb, launch_smallmap         conv8_224_6x6_k4s2_b1:data, conv24_32_8x8_k4s2_b1:data
+  sm_data_kernel<2>, one group                                                                  smallmap.hip: sm_plan nb (DATA), launch_smallmap  conv32_160_5x5_k4s1_b3:data
+  sm_data_kernel<2>: blockIdx.z > 0, the last group half zero blocks                            smallmap.hip: sm_plan ngroups, sm_data_kernel     conv8_32_12x12_k4s2_b2:data, conv8_32_20x20_k4s2_b2:data
+  sm_data_kernel<2>: blockIdx.z > 0, a ragged last block                                        smallmap.hip: sm_plan ngroups, sm_data_kernel     conv8_32_18x14_k4s2_b2:data, conv8_32_12x12_k4s2_b2:data
+  sm_data_kernel<2>: 16 groups at the limit of 1024 positions                                   smallmap.hip: sm_plan, P > 1024                   conv8_64_32x32_k4s2_b4:data
+  sm_data_kernel: three slabs, a short wave (4 of 20 rows)                                      smallmap.hip: sm_plan slabs, sm_data_kernel       conv8_224_6x6_k4s2_b1:data, convT224_8_3x3_k4s2_b1:data
+  sm_data_kernel<1>: a full unroll group and a partly filled one                                smallmap.hip: sm_data_kernel unroll loop          conv128_96_3x3_k3s1_b1:data, conv8_224_6x6_k4s2_b1:data
+  sm_data_kernel<1>: half an unroll group only                                                  smallmap.hip: sm_data_kernel unroll loop          conv24_32_8x8_k4s2_b1:data, conv120_32_8x8_k4s2_b1:data
+  sm_data_kernel<2>: a partly filled unroll group                                               smallmap.hip: sm_data_kernel unroll loop          conv32_160_5x5_k4s1_b3:data
+  sm_fwd_kernel<1>                                                                              smallmap.hip: sm_plan nb, launch_smallmap         conv8_224_6x6_k4s2_b1:fwd, conv24_32_8x8_k4s2_b1:fwd
+  sm_fwd_kernel<2>                                                                              smallmap.hip: sm_plan nb, launch_smallmap         conv32_160_5x5_k4s1_b3:fwd
+  sm_fwd_kernel<4> with one all-zero block (three position blocks)                              smallmap.hip: sm_plan nb, launch_smallmap         conv8_32_12x12_k4s2_b2:fwd
+  sm_fwd_kernel<4> with a ragged last block                                                     smallmap.hip: sm_plan nb, launch_smallmap         conv8_32_18x14_k4s2_b2:fwd
+  sm_fwd_kernel<4>: blockIdx.z > 0                                                              smallmap.hip: sm_plan ngroups, sm_fwd_kernel      conv8_32_20x20_k4s2_b2:fwd, conv8_64_32x32_k4s2_b4:fwd
+  sm_fwd_kernel<4>: 8 groups at the limit of 1024 positions                                     smallmap.hip: sm_plan, P > 1024                   conv8_64_32x32_k4s2_b4:fwd
+  sm_fwd_kernel: four slabs of 72 columns (two groups and one 8-column step over)               smallmap.hip: sm_plan slabs, sm_fwd_kernel `ok`   conv128_96_3x3_k3s1_b1:fwd
+  sm_fwd_kernel: a short wave and an idle wave (`qa == qb`)                                     smallmap.hip: sm_plan slabs, sm_fwd_kernel        conv120_32_8x8_k4s2_b1:fwd
+  sm_wrw_kernel: odd P, the zero row of Pp is read                                              smallmap.hip: sm_plan Pp, launch_smallmap         conv8_224_6x6_k4s2_b1:wrw, convT224_8_3x3_k4s2_b1:wrw
+                                                                                                                                                  conv128_96_3x3_k3s1_b1:wrw
+  sm_wrw_kernel: a partly filled unroll group (Pp % 8 != 0)                                     smallmap.hip: sm_wrw_kernel unroll loop           conv8_224_6x6_k4s2_b1:wrw, conv8_32_18x14_k4s2_b2:wrw
+  sm_wrw_kernel: 1024 positions                                                                 smallmap.hip: sm_plan, P > 1024                   conv8_64_32x32_k4s2_b4:wrw
+  sm_wrw_kernel: more than one block on x and y                                                 smallmap.hip: launch_smallmap, op 1 grid          conv128_96_3x3_k3s1_b1:wrw, conv32_160_5x5_k4s1_b3:wrw
+  conv_gemm_kernel<9>: 1 stage                                                                  conv_gemm.hip:180-184                             conv2_9x7_c5_k3_b1:fwd, convT30_5x6_c2_k3_b2:bwd
+  conv_gemm_kernel<9>: 2 stages                                                                 conv_gemm.hip:181                                 conv4_9x7_c6_k3_b2:fwd, conv4_13x11_c6_k3s3_b2:fwd
+  conv_gemm_kernel<9>: 3 stages                                                                 conv_gemm.hip:182                                 conv6_11x13_c10_k3_b3:fwd, conv4_9x7_c6_k3_b2:bwd
+  conv_gemm_kernel<9>: 5 stages, the ring wraps                                                 conv_gemm.hip:156, :193                           conv10_5x6_c30_k3_b1:fwd, conv6_11x13_c10_k3_b3:bwd
+  conv_gemm_kernel<9>: 15 stages                                                                conv_gemm.hip:334                                 conv10_5x6_c30_k3_b1:bwd, convT30_5x6_c2_k3_b2:fwd
+  conv_gemm_kernel<16>: 1 stage                                                                 conv_gemm.hip:180-184                             conv1_12x10_c4_k4s2_b2:fwd, convT20_6x4_c1_k4s2_b1:bwd
+  conv_gemm_kernel<16>: 2 stages                                                                conv_gemm.hip:181                                 conv2_12x10_c8_k4s2_b1:fwd, convT12_3x5_c2_k4s2_b3:bwd
+  conv_gemm_kernel<16>: 3 stages                                                                conv_gemm.hip:182                                 conv3_9x11_c12_k4s2_b3:fwd, convT4_4x6_c3_k4s2_b1:bwd
+  conv_gemm_kernel<16>: 5 stages, the ring wraps                                                conv_gemm.hip:156, :193                           conv5_8x8_c20_k4s2_b1:fwd, convT8_5x3_c5_k4s2_b2:bwd
+  conv_gemm_kernel<16>: 15 stages                                                               conv_gemm.hip:334                                 conv15_6x6_c60_k4s2_b1:fwd
+  conv_gemm_kernel<4>: 1 stage                                                                  conv_gemm.hip:180-184                             conv1_12x10_c4_k4s2_b2:bwd, convT4_4x6_c3_k4s2_b1:fwd
+  conv_gemm_kernel<4>: 2 stages                                                                 conv_gemm.hip:181                                 conv2_12x10_c8_k4s2_b1:bwd, convT8_5x3_c5_k4s2_b2:fwd
+  conv_gemm_kernel<4>: 3 stages                                                                 conv_gemm.hip:182                                 conv3_9x11_c12_k4s2_b3:bwd, convT12_3x5_c2_k4s2_b3:fwd
+  conv_gemm_kernel<4>: 5 stages, the ring wraps                                                 conv_gemm.hip:156, :193                           conv5_8x8_c20_k4s2_b1:bwd, convT20_6x4_c1_k4s2_b1:fwd
+  conv_gemm_kernel<4>: 15 stages                                                                conv_gemm.hip:334                                 conv15_6x6_c60_k4s2_b1:bwd, convT60_2x3_c4_k4s2_b2:fwd
+  split-K: two even splits of 8 stages                                                          conv_gemm.hip:334-336, :231                       conv32_6x5_c136_k3_b2:fwd
+  split-K: a short last split of 2 stages (`ns > 2` false)                                      conv_gemm.hip:142, :182                           conv130_9x13_c70_k3_b3:fwd
+  split-K: a short last split of 1 stage (`ns > 1` false), 16 splits                            conv_gemm.hip:142, :181                           conv17_5x5_c136_k4s1_b1:bwd
+  split-K on the 16-tap kernel, last split one stage short                                      conv_gemm.hip:335-336                             conv17_5x5_c136_k4s1_b1:fwd
+  two m tiles, the second with 8 live rows                                                      conv_gemm.hip:349, :238, :250                     conv32_6x5_c136_k3_b2:fwd, conv17_5x5_c136_k4s1_b1:fwd
+                                                                                                                                                  conv4_24x23_c136_k3_b3:fwd
+  two m tiles and split-K: partial tiles of the second m tile                                   conv_gemm.hip:232-238                             conv32_6x5_c136_k3_b2:fwd, conv17_5x5_c136_k4s1_b1:fwd
+  one pixel tile partly filled                                                                  conv_gemm.hip:127, :230                           conv2_9x7_c5_k3_b1:fwd, conv4_9x7_c6_k3_b2:fwd
+  several pixel tiles, a ragged last one                                                        conv_gemm.hip:127, :230                           conv6_11x13_c10_k3_b3:fwd, conv4_24x23_c136_k3_b3:fwd
+                                                                                                                                                  conv130_9x13_c70_k3_b3:fwd
+  a grid that is no multiple of 8 workgroups, above 8 (xcd_remap)                               ipsr_common.h:46-52                               conv4_24x23_c136_k3_b3:fwd
+  parity classes: odd output extents, four different grids                                      conv_gemm.hip:366                                 conv4_21x19_c8_k4s2_b2:bwd, conv3_9x11_c12_k4s2_b3:bwd
+                                                                                                                                                  conv8_15x13_c4_k4s2p1d3_b2:bwd
+  parity classes without taps: need_zero, one 16-tap class                                      conv_gemm.hip:367, :411-412                       conv3_12x10_c5_k4s2p3d2_b2:bwd, conv3_2x2_c5_k4s2p3d2_b3:bwd
+  the dilated input gradient on the 2 x 2 map                                                   conv_gemm.hip:366-367                             conv3_2x2_c5_k4s2p3d2_b3:bwd
+  k = 2 on the direct forms: a 4-tap gather, stride 1 and 2, op 0 and op 3                      conv_gemm.hip:317, :355, :419                     conv4_9x8_c8_k2s1_b2:fwd, conv8_9x8_c6_k2s2p1_b1:fwd
+                                                                                                                                                  convT6_5x4_c12_k2s2_b2:bwd, conv4_9x8_c8_k2s2p1d2_b1:fwd
+  k = 2 on the stride-1 transposed form (op 1)                                                  conv_gemm.hip:353, :423                           conv4_9x8_c8_k2s1_b2:bwd
+  k = 2, 3 with dilation 2 on the stride-2 transposed form: all taps in one parity class        conv_gemm.hip:363-367                             conv6_9x8_c4_k3s2p2d2_b2:bwd, conv4_9x8_c8_k2s2p1d2_b1:bwd
+  stride 3 on the direct forms, k3 and k4, op 0 and op 3                                        conv_gemm.hip:421, :130                           conv4_13x11_c6_k3s3_b2:fwd, conv3_13x11_c6_k4s3p2_b1:fwd
+                                                                                                                                                  convT6_4x5_c3_k4s3_b2:bwd
+  dilation 3 on the stride-2 transposed forms: two taps per parity, offsets a step of -3 apart  conv_gemm.hip:325, :435-436                       conv8_15x13_c4_k4s2p1d3_b2:bwd, convT8_4x3_c4_k4s2p1d3_b1:fwd
+  refused: 1088 positions, all three ops                                                        smallmap.hip: sm_plan, P > 1024                   conv8_32_32x34_k4s2_b4
+  refused: k3 s2 transposed: one or two taps in a parity class                                  conv_gemm.hip:373                                 conv4_8x8_c4_k3s2_bwd, convT4_4x4_c4_k3s2_fwd
+  refused: k = 1: one tap                                                                       conv_gemm.hip:373                                 conv4_6x6_c4_k1
+  refused: k3: odd reduction channels                                                           conv_gemm.hip:376                                 conv3_6x6_c4_k3_odd, conv4_6x6_c3_k3_odd
+  refused: 4-tap classes: reduction channels no multiple of 4                                   conv_gemm.hip:376                                 convT6_4x4_c4_k4s2_mod4, conv4_8x8_c6_k4s2_mod4
+  refused: k2 direct: reduction channels no multiple of 4                                       conv_gemm.hip:376                                 conv6_9x8_c6_k2_mod4
+  refused: stride 3 transposed                                                                  conv_gemm.hip:358                                 conv4_13x11_c4_k4s3_bwd, convT4_4x5_c4_k4s3_fwd
 
 Not reached, with the reason: an idle wave (`ra == rb`) in sm_data_kernel.  Within the 224 channels these cases keep to, `sm_plan`
 cannot produce one (test_fp32_conv_plan.py::test_no_data_wave_is_idle_within_the_case_limits enumerates it; the first R that has one

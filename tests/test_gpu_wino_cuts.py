@@ -1,10 +1,10 @@
 """Every Winograd reduction cut, on every planner and pass, against fp64.
 
 The 36 GEMMs of a Winograd convolution may cut their reduction over workgroups; the output transforms then add the slabs of each
-point (wino_load_sum, WinoSplit::of / slabs: csrc/winograd.hip:40-75).  wino_choose_split (:844-878) picks the cut with a timing
+point (wino_load_sum, WinoSplit::of / slabs in csrc/winograd.hip).  wino_choose_split picks the cut with a timing
 model, so the cuts today's layers land on are an accident of that model.  Here ipsr_debug_force_wino_split forces each cut form on
 every planner (its workspace queries included) and ipsr_wino_gemm_split confirms, before each numeric check, that the force took
-effect at that pass's stage count (the chooser ignores a force larger than the stage count, :849).
+effect at that pass's stage count (the chooser ignores a force larger than the stage count).
 
   cut form (force nsplit, xi_split, nsplit_t)         ranges at S stages                 case
   --------------------------------------------------  ---------------------------------  -----------------------------------
@@ -17,16 +17,14 @@ effect at that pass's stage count (the chooser ignores a force larger than the s
   head / tail, xi_split 35     (2, 35, S)             tail finer than the head           cut "ht35_fine_tail"
   (test_every_cut_form_is_reached asserts that the passes below meet an even and an uneven uniform cut and both head/tail orders.)
 
-  planner / pass                                   split chosen at       test id (family), passes
+  planner / pass (the split of each is chosen in wino_plan_gemm, called by)         test id (family), passes
   -----------------------------------------------  --------------------  ---------------------------------------------------
-  3x3 Conv2d / ConvTranspose2d fwd, input grad     winograd.hip:909      k3_conv*, k3_convT*: fwd, bwd_data
-  3x3 weight gradient                              winograd.hip:977      k3_conv*, k3_convT*: wrw
-  k4 s2 p3 d2 (geometry 0), k4 s1 p1 (geometry 1)  winograd.hip:1219 (wrw), :1229 (fwd, bwd_data)
-                                                                         dil_g0*, dil_g1*: mode 0, 1, 2
-  k4 s2 p1 polyphase F(5x5, 2x2)                   winograd.hip:1664 (wrw), :1675 (modes 0, 1)
-                                                                         s2*: mode 0, 1, 2
+  3x3 Conv2d / ConvTranspose2d fwd, input grad     wino_plan             k3_conv*, k3_convT*: fwd, bwd_data
+  3x3 weight gradient                              wino_wrw_plan         k3_conv*, k3_convT*: wrw
+  k4 s2 p3 d2 (geometry 0), k4 s1 p1 (geometry 1)  dil_plan              dil_g0*, dil_g1*: mode 0, 1, 2
+  k4 s2 p1 polyphase F(5x5, 2x2)                   s2_plan               s2*: mode 0, 1, 2
 
-  arithmetic                                       GEMM kernel (launch_wino_gemm, winograd.hip:815-829)      tests
+  arithmetic                                       GEMM kernel (launch_wino_gemm)                            tests
   -----------------------------------------------  --------------------------------------------------------  ------------------------
   fp32, <= 64 produced channels                    wino_gemm_kernel<64>                                      *-narrow-fp32 (fwd, wrw)
   fp32, > 64 produced channels                     wino_gemm_kernel<128>                                     *-wide-fp32, narrow bwd
@@ -48,7 +46,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-# shapes at which the automatic rule takes each of its branches (winograd.hip:854-876): uncut, head/tail, uniform
+# shapes at which the automatic rule takes each of its branches (wino_choose_split): uncut, head/tail, uniform
 AUTO_PROBES = [(128, 128, 256), (512, 512, 512), (256, 512, 1024), (256, 2048, 256), (128, 128, 8192)]
 
 
@@ -82,7 +80,7 @@ def cdiv(a, b):
 
 
 def forced_split(S, a, x, b):
-    """What wino_choose_split returns under force (a, x, b) at S stages (winograd.hip:848-853)."""
+    """What wino_choose_split returns under force (a, x, b) at S stages (the force branch of wino_choose_split in winograd.hip)."""
     pa, pb = cdiv(S, a), cdiv(S, b)
     return (cdiv(S, pa), pa, x, cdiv(S, pb), pb)
 
@@ -99,7 +97,7 @@ def ranges(S, n, per):
 
 
 def rows_padded(K, math):
-    """wino_rows_padded (winograd.hip:812): the <64> tile for fp32 arithmetic on <= 64 produced channels."""
+    """wino_rows_padded (winograd.hip): the <64> tile for fp32 arithmetic on <= 64 produced channels."""
     return 64 if (math == "fp32" and K <= 64) else cdiv(K, 128) * 128
 
 
@@ -110,7 +108,7 @@ def gemm_kernel(prod, math):
 
 
 def wrw_stages(T):
-    """Weight-gradient planners: the reduction runs over Tp = roundup(T, 128) tiles in stages of 16 (:972-977, :1219, :1664)."""
+    """Weight-gradient planners: the reduction runs over Tp = roundup(T, 128) tiles in stages of 16 (wino_plan_tiles; red = Tp in wino_wrw_plan, dil_plan and s2_plan)."""
     return cdiv(T, 128) * 128 // 16
 
 
@@ -158,7 +156,7 @@ def family_passes(family, shape, io_bf16, seed):
         xr, wr = x64.clone().requires_grad_(True), w64.clone().requires_grad_(True)
         y64 = F.conv2d(xr, wr, None, st_, pad, dil)
         dx64, dw64 = torch.autograd.grad(y64, (xr, wr), dy64)
-        T = B * cdiv(Ho, 3) * cdiv(Wo, 3)                                                    # dil_plan, winograd.hip:1208-1211
+        T = B * cdiv(Ho, 3) * cdiv(Wo, 3)                                                    # dil_plan (winograd.hip)
         call = ops.conv4x4_dilated_winograd
         passes += [("mode0", Cin // 16, Cout, lambda m: call(0, x, w, (B, Cin, H, W), Cout, geom=geom, math=m), y64.detach(), True),
                    ("mode1", Cout // 16, Cin, lambda m: call(1, dy, w, (B, Cin, H, W), Cout, geom=geom, math=m), dx64, True),
@@ -170,7 +168,7 @@ def family_passes(family, shape, io_bf16, seed):
         fr, wr = f64.clone().requires_grad_(True), w64.clone().requires_grad_(True)
         y64 = F.conv2d(fr, wr, None, 2, 1)
         dx64, dw64 = torch.autograd.grad(y64, (fr, wr), c64)
-        T = B * cdiv(nh, 5) * cdiv(nw, 5)                                                    # s2_plan, winograd.hip:1649-1651
+        T = B * cdiv(nh, 5) * cdiv(nw, 5)                                                    # s2_plan (winograd.hip)
         call = ops.conv4x4s2_winograd
         passes += [("mode0", 4 * Cf // 16, Kc, lambda m: call(ops.S2_FINE_TO_COARSE, fine, w, B, Kc, Cf, nh, nw, math=m), y64.detach(), True),
                    ("mode1", Kc // 16, 4 * Cf, lambda m: call(ops.S2_COARSE_TO_FINE, coarse, w, B, Kc, Cf, nh, nw, math=m), dx64, True),

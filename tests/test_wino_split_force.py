@@ -1,7 +1,7 @@
 """The Winograd cut override and its query on the host (no GPU needed: the library loads with every GPU hidden).
 
 ipsr_debug_force_wino_split(nsplit, xi_split, nsplit_t) replaces wino_choose_split's rule for every following call
-(csrc/winograd.hip:848-853, :2128-2134); ipsr_wino_gemm_split reports the cut (:2136-2143).  tests/test_gpu_wino_cuts.py relies on
+(wino_choose_split and the entry itself in csrc/winograd.hip); ipsr_wino_gemm_split reports the cut.  tests/test_gpu_wino_cuts.py relies on
 both: a force must round-trip through the query, an out-of-range force must be refused with IPSR_ERR_INVALID (and leave the
 previous state in place), and (0, 0, 0) must restore the automatic rule exactly.
 """
