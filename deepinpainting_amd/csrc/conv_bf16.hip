@@ -40,6 +40,7 @@ typedef __attribute__((address_space(3))) s16x4* lds_s4_t;
 // LDS reads that run beside an LDS-DMA use ext-vector types: a HIP_vector_type (uint4) load is a struct copy that reaches the back end
 // without alias metadata, and hipcc then drains the DMA queue (s_waitcnt vmcnt(0)) in front of it — the prefetch stops overlapping.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CB_K = 128, CB_P = 256, CB_C = 16, CB_THREADS = 512, CB_MAXTAP = 9;
 // per-thread loop bounds of a stage, by pixels per tile (256 / 512): transposition blocks (4 channels x 16 pixels) per 16-lane group, and
@@ -1240,7 +1241,8 @@ int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out,
 // RS new rows arrive meanwhile), both by LDS-DMA with the 16-byte chunks of a row XOR-swizzled / the row pitch odd in 16-byte slots so
 // that the 32 channels of a fragment read hit distinct banks.
 
-// The plan of all four weight-gradient kernels (this one, its split-bf16 form and the two k4 s2 p1 kernels further down; wrw_geometry).
+// The plan of all five weight-gradient kernels (this one, its split-bf16 form, the two k4 s2 p1 kernels and the dilated k4 s2 kernel further
+// down; wrw_geometry).
 // The a operand is the one whose channels index dW's rows (3x3: see above; k4 s2: the coarse tensor), w the one read through the taps
 // (k4 s2: the fine tensor); H x W is the grid the reduction runs over (k4 s2: the coarse grid nh x nw, the fine tensor is 2H x 2W).
 struct WrwGeom {
@@ -1251,19 +1253,20 @@ struct WrwGeom {
     int ring_plane;             // bytes of the ring (split-bf16: of one of its two planes, hi | lo); read by the split-bf16 kernels only
 };
 
-// What the four kernels differ in as far as the host is concerned: one row per kernel, read by wrw_geometry, wrw_ws_bytes and launch_wrw.
+// What the five kernels differ in as far as the host is concerned: one row per kernel, read by wrw_geometry, wrw_ws_bytes and launch_wrw.
 // LDS of a launch = 2 x TK x PX x 2 bytes of a (bf16: two buffers; split: hi | lo) + the ring (bf16: one plane; split: two).
-enum { WRW_3X3 = 0, WRW_3X3_SPLIT = 1, WRW_S2 = 2, WRW_S2_SPLIT = 3 };
+enum { WRW_3X3 = 0, WRW_3X3_SPLIT = 1, WRW_S2 = 2, WRW_S2_SPLIT = 3, WRW_DIL_SPLIT = 4 };
 struct WrwKind {
     int TK, TC, NT, PX;         // tile: a channels x w channels; taps (= NT of cb_slab_reduce_kernel); pixels per stage
     int ring_mul, ring_add;     // ring entries = ring_mul * RS + ring_add
-    int wscale, wmax;           // the w tensor per grid pixel, both ways (k4 s2: 2 = rows per ring entry, pitch of 2 W pixels); widest grid
+    int wscale, wmax;           // a ring entry per grid row, both ways (k4 s2: 2 = rows per ring entry, pitch of 2 W pixels; dilated: 1, the
+                                // ring holds the sampled rows q); widest grid
     int dma_add;                // bf16: one LDS-DMA round moves up to RS + dma_add ring entries, 5 slots per thread; split: -1, no DMA
     bool split;                 // fp32 tensors, split-bf16 operands: two planes, no zero page, three MFMAs per product
     const char *who, *width_fmt, *rows_fmt, *ring_fmt;      // the messages, as each planner has always worded them
     const char *kernel, *reduce;                             // the names check_launch reports
 };
-constexpr WrwKind WRW_KINDS[4] = {
+constexpr WrwKind WRW_KINDS[5] = {
     // TK  TC  NT   PX  ring   wscale wmax dma split
     {128, 64,  9, 128, 2, 2,  1,    128,  0, false, "bf16 weight gradient",
      "%s: image width %d (16, 32, 64 or 128)", "%s: %d rows are not a multiple of %d", "%s: the row ring of a %d-wide image does not fit the LDS plan",
@@ -1277,12 +1280,15 @@ constexpr WrwKind WRW_KINDS[4] = {
     {128, 32, 16,  64, 1, 1,  2,     64, -1, true, "split-bf16 4x4 stride-2 weight gradient",
      "%s: coarse width %d (16, 32 or 64)", "%s: %d coarse rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide grid does not fit the LDS plan",
      "conv_bf16x3_wrw_s2_kernel", "conv_bf16_wrw_s2_reduce_kernel"},
+    {128, 32, 16,  64, 1, 3,  1,    128, -1, true, "split-bf16 dilated 4x4 stride-2 weight gradient",
+     "%s: coarse width %d (16, 32, 64 or 128)", "%s: %d coarse rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide grid does not fit the LDS plan",
+     "conv_bf16x3_wrw_dil_kernel", "conv_bf16_wrw_dil_reduce_kernel"},
 };
 constexpr int WB_K = WRW_KINDS[WRW_3X3].TK, WB_C = WRW_KINDS[WRW_3X3].TC, WB_PX = WRW_KINDS[WRW_3X3].PX, WB_THREADS = 512;
 constexpr int WB_A_BYTES = WB_K * WB_PX * 2;                 // 32 KB per buffer; the w-row ring gets the other 96 KB (largest: W = 16 -> 18 rows x 64 c
                                                              // x 5 slots x 16 B = 92 KB)
 
-// ---- what the four kernels share on the device ----
+// ---- what the five kernels share on the device ----
 struct WrwRun { int kt, ct, split, b, ylo; };               // tile, run, and the run's image and first grid row
 
 // workgroup -> (tile, run): the tiles of one run are neighbours
@@ -1975,7 +1981,213 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_s2_kernel(const float*
         }
 }
 
-// ---- the host side of the four weight-gradient kernels: one planner, one byte count, one launcher over WRW_KINDS ----
+// =====================================================================================================================================
+// Weight gradient of the dilated down convolution Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) on FP32 tensors with split-bf16 operands
+// (ipsr_conv4x4s2_bf16x3_dil_wrw; the opt-in switch set_direct_dilated_dw of the fp32 nets).  With q(m, n) = fine(2 m + 1, 2 n + 1) the
+// layer is a 16-tap stride-1 correlation on the coarse grid (the derivation of the dilated data passes above), so
+//      dW[kc][cf][r][s] = sum_{b, oy, ox}  coarse[b][kc][oy][ox] * q[b][cf][oy + r - 2][ox + s - 2]            (q zero outside nh x nw)
+// with a halo of 2 in front and 1 behind, in rows and columns; only odd fine rows and odd fine columns are ever read.
+// Operands and products as in conv_bf16x3_wrw_kernel (hi + lo, lo*hi + hi*lo + hi*hi, smallest first).  Tile, wave layout (4 kc x 2 row-tap
+// pairs), stage (64 coarse pixels), run cut and slab reduction are conv_bf16x3_wrw_s2_kernel's; the fragments are conv_bf16x3_wrw_kernel's:
+// unit-stride 16-byte reads of a ring of whole q rows, the column taps s = 0..3 as the shifts -2, -1, 0, +1 of the aligned chunk and its
+// neighbouring dwords (wrw_shifted plus the window two pixels to the left, which needs no alignbit).
+//   * q is sampled at split time: a thread loads 8 consecutive floats of an odd fine row (two 16-byte loads), keeps the 4 odd ones, and
+//     stores 8 bytes into the hi and the lo plane — no de-interleave on the read side.  512 threads x 8 floats = the 256 q chunks of a stage;
+//   * q row y lives in ring slot (y + 2) mod NRING; a stage reads rows y0 - 2 .. y0 + RS, so NRING = RS + 3 and the next stage's RS new
+//     rows replace the RS oldest.  Rows above the image are the ring's initial zeros (only the first stages of a run at ylo = 0 read them);
+//     rows below it are zeros STORED by the stage that would load them (the slot held data a stage earlier), from a load of row nh - 1, so
+//     that the loads stay unconditional; channels past Cf likewise.  The halo slots of every (row, channel) are zeroed once, never written;
+//   * nw = 128 (WIDE): a stage is half a q row.  The ring is 4 whole rows, a new row (two 8-float loads per thread) arrives every second
+//     stage, after the second half of the row above has been multiplied.  In WrwGeom's terms RS = 1 and stages_per_wg counts ROWS.
+// LDS: coarse hi | lo = 2 x 16 KB; ring hi | lo = 2 x (RS + 3) rows x 32 cf x (nw / 8 + 3) slots x 16 B:
+//      nw = 16: 32768 + 35840 = 68608 B    nw = 32: 32768 + 35840 = 68608 B    nw = 64: 32768 + 45056 = 77824 B    nw = 128: 32768 + 77824 = 110592 B
+// Supported: nw in {16, 32, 64, 128}, nh a multiple of max(1, 64 / nw).  Deterministic: no atomics, every sum in a fixed order.
+
+// 8 consecutive fp32 pixels of an odd fine row -> the hi and lo bf16 images (8 bytes each) of the 4 odd ones
+__device__ __forceinline__ void wd_split4_odd(const f32x4& v0, const f32x4& v1, u32x2* hi, u32x2* lo)
+{
+    unsigned h16[4], l16[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float v = i < 2 ? v0[2 * i + 1] : v1[2 * i - 3];
+        h16[i] = __builtin_bit_cast(unsigned short, (__bf16)v);
+        l16[i] = __builtin_bit_cast(unsigned short, (__bf16)(v - __uint_as_float(h16[i] << 16)));
+    }
+    *hi = u32x2{h16[0] | (h16[1] << 16), h16[2] | (h16[3] << 16)};
+    *lo = u32x2{l16[0] | (l16[1] << 16), l16[2] | (l16[3] << 16)};
+}
+
+// the four column taps s of 8 coarse pixels at X (a lane's aligned 16-byte chunk of a ring row): the windows starting at ox - 2 + s
+__device__ __forceinline__ void wd_taps(const unsigned char* X, u32x4 (&f)[4])
+{
+    wrw_shifted(X, &f[1], &f[2], &f[3]);
+    const unsigned prev = *reinterpret_cast<const unsigned*>(X - 4);
+    f[0] = u32x4{prev, f[2].x, f[2].y, f[2].z};
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_dil_kernel(const float* __restrict__ coarse, const float* __restrict__ fine, WrwGeom g,
+                                                                      float* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // coarse hi | coarse lo | ring hi | ring lo
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, rh = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
+    const int Wf = 2 * g.W;
+    const size_t HWc = (size_t)g.H * g.W, HWf = 4 * HWc;
+    const int hpr = g.W >> 2;                                // 4-pixel half chunks per q row
+    unsigned char* const ring = lds + 2 * W2_A_BYTES;
+    const int row_bytes = W2_C * g.pitch * 16;
+
+    // ---- coarse rows: as in conv_bf16x3_wrw_s2_kernel ---------------------------------------------------------------------------------------
+    const int c8 = tid & 7, k0 = tid >> 3;
+    const float* ga[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int kc = kt * W2_K + k0 + 64 * j;
+        ga[j] = kc < g.K ? coarse + ((size_t)b * g.K + kc) * HWc + (size_t)ylo * g.W + c8 * 8 : nullptr;
+    }
+    const int a_wr = ((k0 << 3) + (c8 ^ (k0 & 7))) * 16;     // + j * 8192
+    // ---- q rows: the new rows of a stage (WIDE: of a row) are 16 (32) half chunks per channel; a lane owns half chunk (tid & 15) + 16 j
+    // (row fr, half chunk fx) of channel tid >> 4 -----------------------------------------------------------------------------------------
+    constexpr int NQ = WIDE ? 2 : 1;
+    const int c0 = tid >> 4;
+    const bool fok = ct * W2_C + c0 < g.C;                   // channels past Cf: a valid address (the last channel), zeros are stored
+    const float* gq = fine + ((size_t)b * g.C + (fok ? ct * W2_C + c0 : g.C - 1)) * HWf + Wf;        // q row 0 = fine row 1
+    int fr[NQ], fx[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int hi = (tid & 15) + 16 * j;
+        fr[j] = hi >> (g.wshift - 2); fx[j] = hi & (hpr - 1);
+    }
+    const int q_wr = (c0 * g.pitch + 1) * 16;                // + fx * 8
+
+    f32x16 acc[8];
+    wrw_clear(acc);
+
+    f32x4 ar[4], fw[2 * NQ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ar[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};           // channels past Kc stay zeros
+    // step st: its 64 coarse pixels
+    auto load_a = [&](int st) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (ga[j]) {
+                const float* src = ga[j] + (size_t)st * W2_PX;
+                ar[2 * j] = *reinterpret_cast<const f32x4*>(src);
+                ar[2 * j + 1] = *reinterpret_cast<const f32x4*>(src + 4);
+            }
+    };
+    auto store_a = [&]() {
+        u32x4 vh, vl;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            wx_split8(ar[2 * j], ar[2 * j + 1], &vh, &vl);
+            *reinterpret_cast<u32x4*>(lds + a_wr + j * 8192) = vh;
+            *reinterpret_cast<u32x4*>(lds + W2_A_BYTES + a_wr + j * 8192) = vl;
+        }
+    };
+    // unit u (a stage; WIDE: a row): the q rows y0 + 1 .. y0 + RS, what it reads beyond the rows of unit u - 1.  Unconditional loads: a row
+    // below the image reads row nh - 1 instead and store_q stores zeros for it
+    auto load_q = [&](int u) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int y = ylo + u * g.RS + 1 + fr[j];
+            const float* src = gq + (size_t)(y < g.H ? y : g.H - 1) * (2 * Wf) + fx[j] * 8;
+            fw[2 * j] = *reinterpret_cast<const f32x4*>(src);
+            fw[2 * j + 1] = *reinterpret_cast<const f32x4*>(src + 4);
+        }
+    };
+    auto store_q = [&](int u) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int y = ylo + u * g.RS + 1 + fr[j];
+            u32x2 vh, vl;
+            wd_split4_odd(fw[2 * j], fw[2 * j + 1], &vh, &vl);
+            if (!(y < g.H && fok)) vh = vl = u32x2{0u, 0u};                      // row below the image / channel past Cf
+            unsigned char* dst = ring + ((y + 2) % g.NRING) * row_bytes + q_wr + fx[j] * 8;
+            *reinterpret_cast<u32x2*>(dst) = vh;
+            *reinterpret_cast<u32x2*>(dst + g.ring_plane) = vl;
+        }
+    };
+
+    // prologue: the ring starts as zeros (halo slots and the rows above the image keep them); rows ylo - 2 .. ylo, then unit 0
+    for (int i = tid; i < 2 * g.ring_plane / 16; i += 512) *reinterpret_cast<u32x4*>(ring + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    load_a(0);
+    load_q(0);
+    __syncthreads();
+    for (int i = tid; i < 3 * W2_C * hpr; i += 512) {
+        const int m = i / (W2_C * hpr), rem = i - m * (W2_C * hpr);
+        const int c = rem / hpr, x4 = rem - c * hpr;
+        const int y = ylo - 2 + m, cf = ct * W2_C + c;
+        if (cf < g.C && y >= 0) {                            // else: the zeros stay
+            const float* src = fine + ((size_t)b * g.C + cf) * HWf + (size_t)(2 * y + 1) * Wf + x4 * 8;
+            u32x2 vh, vl;
+            wd_split4_odd(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), &vh, &vl);
+            const int off = ((y + 2) % g.NRING) * row_bytes + (c * g.pitch + 1) * 16 + x4 * 8;
+            *reinterpret_cast<u32x2*>(ring + off) = vh;
+            *reinterpret_cast<u32x2*>(ring + g.ring_plane + off) = vl;
+        }
+    }
+    store_a();
+    store_q(0);
+    __syncthreads();
+
+    const int a_row = wk * 32 + r;
+    const int nsteps = WIDE ? 2 * g.stages_per_wg : g.stages_per_wg;
+    for (int st = 0; st < nsteps; ++st) {
+        const int y0 = ylo + (WIDE ? st >> 1 : st * g.RS);
+        const bool more = st + 1 < nsteps, new_rows = more && (!WIDE || (st & 1));
+        if (more) load_a(st + 1);                             // consumed behind this step's multiplications
+        if (new_rows) load_q(WIDE ? (st + 1) >> 1 : st + 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                         // k-steps of 16 coarse pixels
+            const int f8 = 2 * j + h;
+            const unsigned char* A = lds + ((a_row << 3) + (f8 ^ (a_row & 7))) * 16;
+            const bf16x8 fah = *reinterpret_cast<const bf16x8*>(A), fal = *reinterpret_cast<const bf16x8*>(A + W2_A_BYTES);
+            const int p0 = 16 * j + (WIDE ? 64 * (st & 1) : 0);
+            const int rs = WIDE ? 0 : p0 >> g.wshift, ox0 = (p0 & (g.W - 1)) + 8 * h;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const int slot = (y0 + rs + 2 * rh + ri) % g.NRING;             // q row y0 + rs + (tap row 2 rh + ri) - 2
+                const unsigned char* X = ring + slot * row_bytes + (r * g.pitch + 1 + (ox0 >> 3)) * 16;
+                u32x4 f[2][4];                               // [plane][column tap]
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) wd_taps(X + pl * g.ring_plane, f[pl]);
+                // smallest terms first: lo(coarse) hi(q), hi(coarse) lo(q), hi hi; the four taps alternate so that no MFMA waits for its predecessor
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal, __builtin_bit_cast(bf16x8, f[0][t]), acc[ri * 4 + t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, f[1][t]), acc[ri * 4 + t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah, __builtin_bit_cast(bf16x8, f[0][t]), acc[ri * 4 + t], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                       // every wave is done reading this step
+        if (more) {
+            store_a();
+            if (new_rows) store_q(WIDE ? (st + 1) >> 1 : st + 1);
+            __syncthreads();
+        }
+    }
+
+    // partial result: slab[split][t = r * 4 + s][kc][cf] (lanes along cf)
+    const int Kp = g.ktiles * W2_K, Cp = g.ctiles * W2_C;
+    float* out = slabs + (size_t)split * 16 * Kp * Cp;
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ka = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)(rh * 8 + t) * Kp + ka) * Cp + ct * W2_C + r] = acc[t][e];
+        }
+}
+
+// ---- the host side of the five weight-gradient kernels: one planner, one byte count, one launcher over WRW_KINDS ----
 static size_t wrw_lds_bytes(const WrwKind& k, const WrwGeom& g) { return 2 * (size_t)k.TK * k.PX * 2 + (k.split ? 2 : 1) * (size_t)g.ring_plane; }
 
 // The limits, before any launch (3x3: K = Ka, C = Cb, the image H x W; k4 s2: K = Kc, C = Cf, the coarse grid nh x nw).
@@ -1985,7 +2197,7 @@ static int wrw_geometry(int kind, int B, int K, int C, int H, int W, WrwGeom* g)
     if (kind == WRW_S2_SPLIT && W == 128)
         return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width 128: the ring of whole fine rows for a half-row stage needs 176128 bytes of LDS (16, 32 or 64)", k.who);
     if (W != 16 && W != 32 && W != 64 && W != k.wmax) return fail(IPSR_ERR_UNSUPPORTED, k.width_fmt, k.who, W);
-    const int RS = k.PX / W;
+    const int RS = k.PX >= W ? k.PX / W : 1;                  // the dilated kernel at W = 128: a stage is half a row, the cut is by rows
     if (H % RS != 0) return fail(IPSR_ERR_UNSUPPORTED, k.rows_fmt, k.who, H, RS);
     g->B = B; g->K = K; g->C = C; g->H = H; g->W = W;
     g->wshift = cb_wshift(W);
@@ -2008,7 +2220,7 @@ static size_t wrw_ws_bytes(int kind, int B, int K, int C, int H, int W)
     return (k.split ? 0 : 256) + (size_t)g.nsplit * k.NT * g.ktiles * k.TK * g.ctiles * k.TC * 4;
 }
 
-// a [B,K,H,W], w [B,C,wscale H,wscale W] (bf16, or fp32 for the split kinds) -> dW [K][C][NT] fp32
+// a [B,K,H,W], w [B,C,wscale H,wscale W] (dilated: [B,C,2H,2W]) (bf16, or fp32 for the split kinds) -> dW [K][C][NT] fp32
 template <int KIND>
 static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int C, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
 {
@@ -2026,7 +2238,8 @@ static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int
     if constexpr (KIND == WRW_3X3) kernel = reinterpret_cast<const void*>(&conv_bf16_wrw_kernel);
     else if constexpr (KIND == WRW_3X3_SPLIT) kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_kernel);
     else if constexpr (KIND == WRW_S2) kernel = reinterpret_cast<const void*>(&conv_bf16_wrw_s2_kernel);
-    else kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel);
+    else if constexpr (KIND == WRW_S2_SPLIT) kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel);
+    else kernel = W == 128 ? reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<true>) : reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<false>);
     if (int rc = cb_raise_lds(kernel, k.kernel)) return rc;
     profile_mark_start(st, 4);
     if constexpr (KIND == WRW_3X3)
@@ -2035,8 +2248,12 @@ static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int
         conv_bf16x3_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
     else if constexpr (KIND == WRW_S2)
         conv_bf16_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
-    else
+    else if constexpr (KIND == WRW_S2_SPLIT)
         conv_bf16x3_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    else if (W == 128)
+        conv_bf16x3_wrw_dil_kernel<true><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    else
+        conv_bf16x3_wrw_dil_kernel<false><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
     const double px = (double)B * H * W;
     profile_mark_stop(st, 4, (k.split ? 3.0 : 1.0) * 2.0 * k.NT * (double)(g.ktiles * k.TK) * (g.ctiles * k.TC) * px, 2.0 * k.NT * (double)K * C * px);
     if (int rc = check_launch(k.kernel)) return rc;
@@ -2165,6 +2382,20 @@ int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw,
     if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16x3_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
     return launch_wrw<WRW_S2_SPLIT>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t ipsr_conv4x4s2_bf16x3_dil_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
+{
+    if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_dil_wrw_workspace_bytes", true, {B, Kc, Cf, nh, nw})) return 0;
+    return wrw_ws_bytes(WRW_DIL_SPLIT, B, Kc, Cf, nh, nw);
+}
+
+int ipsr_conv4x4s2_bf16x3_dil_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
+{
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16x3_dil_wrw", {fine, coarse, dw, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16x3_dil_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3_dil_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
+    return launch_wrw<WRW_DIL_SPLIT>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)

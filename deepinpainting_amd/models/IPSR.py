@@ -61,6 +61,8 @@ class IPSR(BaseModel):
         hipconv.set_conv_math(fp32=getattr(opt, 'conv_math', 'fp32'), bf16=getattr(opt, 'conv_math_bf16', 'bf16x3'))
         # opt-in: netG's dilated down convolutions (forward / input gradient, fp32 activations) on the direct split-bf16 kernel
         hipconv.set_direct_dilated(bool(getattr(opt, 'direct_dilated', False)))
+        # opt-in, a switch of its own: their weight gradient on the direct split-bf16 kernel
+        hipconv.set_direct_dilated_dw(bool(getattr(opt, 'direct_dilated_dw', False)))
         # conv-bias + InstanceNorm + activation in one HIP kernel each way (models/fused.py); False = plain torch modules
         networks.FusedSequential.enabled = bool(getattr(opt, 'fused_norm_act', True))
 

@@ -32,6 +32,8 @@ pass and what the engine needs; a new engine is one record there plus its rule i
                                   — and, by a switch of its own (`set_direct_dilated`), forward / input gradient of netG's dilated down convolution
                                   Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input, instead of "wino_dil"
   "bf16x3w"   csrc/conv_bf16.hip  fp32 activations, opt-in (the same names): the weight gradient as a pixel reduction on split-bf16 operands, two launches
+                                  — and, by a switch of its own (`set_direct_dilated_dw`), the weight gradient of the dilated down convolution as
+                                  the same reduction over the odd / odd quarter of the input, instead of "wino_dil"
   "miopen"    torch               everything else
 Weight gradients: Winograd F(3x3,4x4) (csrc/winograd.hip) for the 3x3 stride-1 layers with >= 256 channels on 16x16..64x64
 maps (2.0-2.4x MIOpen), MIOpen otherwise (`select_wrw`).
@@ -85,6 +87,24 @@ def set_direct_dilated(on):
 def direct_dilated():
     """Whether `set_direct_dilated` is on."""
     return _DIRECT_DILATED
+
+
+_DIRECT_DILATED_DW = False # opt-in: the dilated 4x4 stride-2 weight gradient of "wino_dil" on the direct split-bf16 kernel (`set_direct_dilated_dw`)
+
+
+def set_direct_dilated_dw(on):
+    """Opt-in, default off, independent of `set_conv_math` and of `set_direct_dilated`: under fp32 activations, the weight gradient of the
+    dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" has goes to the direct split-bf16 kernel ("bf16x3w",
+    ops.conv4x4s2_bf16x3_dil_wrw) on every shape it takes (`_bf16x3_dil_wrw_takes`).  The data passes, bf16 activations, forced engines,
+    the k4 s1 p1 layer and "smallmap" grids stay where they are."""
+    global _DIRECT_DILATED_DW
+    _DIRECT_DILATED_DW = bool(on)
+    _SEL.clear()
+
+
+def direct_dilated_dw():
+    """Whether `set_direct_dilated_dw` is on."""
+    return _DIRECT_DILATED_DW
 
 
 def _amp_bf16():
@@ -354,6 +374,8 @@ def _select_wrw_any(lay, bf16):
             return "bf16x3w"
         if ops.direct_moves(_MATH["fp32"], "s2_wrw") and _bf16x3_s2_wrw_wins(eng, lay):
             return "bf16x3w"
+        if _DIRECT_DILATED_DW and _bf16x3_dil_wrw_takes(eng, lay):
+            return "bf16x3w"
         return eng
     if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
         return eng
@@ -415,6 +437,26 @@ def _bf16x3_dil_takes(eng, op, lay):
         return False
     g = _dil_geometry(lay)
     return g is not None and ops.conv4x4s2_bf16x3_supported(_dil_mode(op), lay[1], *g)
+
+
+# MIOpen's one dilated weight gradient of the step, netG's outermost 64 -> 64 @256x256 (coarse grid 128 wide), as (Kc, Cf, nh, nw)
+_DIL_WRW_MIOPEN_ROW = (64, 64, 128, 128)
+
+
+def _bf16x3_dil_wrw_takes(eng, lay):
+    """fp32 activations under `set_direct_dilated_dw(True)`: the weight gradients of the dilated down convolution that "wino_dil" has go to
+    the direct split-bf16 kernel (ops.conv4x4s2_bf16x3_dil_wrw) wherever it takes the shape (coarse grids 16 .. 128 wide) — every such
+    shape, won or lost.  Measured at batch 8 on the step's shapes (profiles/direct_bf16x3_dil_wrw_layers.txt): 1.84x "wino_dil" on 128 @128
+    (0.079 vs 0.146 ms), 1.30x on 256 @64, 1.13x on 512 @32, the ranges apart in every row.  Of MIOpen's rows exactly one moves, at any batch
+    though only batch 8 was measured: 64 -> 64 @256x256, where the kernel's slowest round (0.1412 ms) is faster than MIOpen's fastest
+    (0.2164 ms), 1.68x on the medians.  The step gains 0.8-1.0 %.  A forced engine is never overridden; netD's k4 s1 p1, "smallmap" grids and
+    bf16 activations stay where they are."""
+    if eng not in ("wino_dil", "miopen") or _mode() != "auto":
+        return False
+    g = _dil_geometry(lay)
+    if g is None or (eng == "miopen" and g != _DIL_WRW_MIOPEN_ROW):
+        return False
+    return ops.conv4x4s2_bf16x3_dil_wrw_supported(lay[1], *g)
 
 
 def _bf16x3_wrw_wins(eng, lay):
@@ -527,6 +569,8 @@ def _bf16d_wrw(x, dy, lay, math, sink):
 def _bf16x3w_wrw(x, dy, lay, math, sink):
     if lay[6] == 3:
         return ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink)
+    if _is_dilated4(*lay[6:]):
+        return ops.conv4x4s2_bf16x3_dil_wrw(x, dy, lay[1], *_dil_geometry(lay), out=sink)      # Conv2d only: (fine, coarse) = (x, dy)
     return ops.conv4x4s2_bf16x3_wrw(*_fine_coarse(x, dy, lay), out=sink)
 
 

@@ -585,7 +585,7 @@ def conv3x3_winograd(op, inp, weight, in_shape, Cout, bias=None, epilogue=None, 
 
 def _direct_operands(arith, who, *named):
     """The activation operands (tensor, name, ...) of a direct pass: all bf16 under "bf16", all fp32 under "bf16x3"."""
-    if arith == "bf16x3":
+    if arith.startswith("bf16x3"):
         return [_req(t, torch.float32, name) for t, name in zip(named[::2], named[1::2])]
     acts = [_act(t, name) for t, name in zip(named[::2], named[1::2])]
     if not all(bf for _, bf in acts):
@@ -770,6 +770,17 @@ def conv4x4s2_bf16x3_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     matrix cores with split operands (ipsr_conv4x4s2_bf16x3_wrw): every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32
     accumulation, the split in the kernel; `out`: optional contiguous fp32 destination (a gradient bucket slice)."""
     return _conv4x4s2_direct_wrw("bf16x3", fine, coarse, B, Kc, Cf, nh, nw, out)
+
+
+def conv4x4s2_bf16x3_dil_wrw_supported(B, Kc, Cf, nh, nw):
+    return _lib.lib().ipsr_conv4x4s2_bf16x3_dil_wrw_workspace_bytes(B, Kc, Cf, nh, nw) > 0
+
+
+def conv4x4s2_bf16x3_dil_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
+    """Weight gradient [Kc,Cf,4,4] (fp32) of Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) from its FP32 input fine [B,Cf,2nh,2nw] and
+    output gradient coarse [B,Kc,nh,nw] on the bf16 matrix cores with split operands (ipsr_conv4x4s2_bf16x3_dil_wrw); arithmetic and `out`
+    as in conv4x4s2_bf16x3_wrw."""
+    return _conv4x4s2_direct_wrw("bf16x3_dil", fine, coarse, B, Kc, Cf, nh, nw, out)
 
 
 def conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):

@@ -516,6 +516,18 @@ int ipsr_conv4x4s2_bf16_wrw(const void* fine, const void* coarse, float* dw, int
 size_t ipsr_conv4x4s2_bf16x3_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
                               void* ws, size_t ws_bytes, void* stream);
+/* the weight gradient of the DILATED layer Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) on FP32 tensors with split-bf16 operands (the
+ * opt-in switch set_direct_dilated_dw of the fp32 nets): fine [B,Cf,2nh,2nw] = the layer's input, coarse [B,Kc,nh,nw] = its output gradient,
+ * fp32 NCHW -> dw [Kc][Cf][4][4] fp32.  With q(m, n) = fine(2 m + 1, 2 n + 1),
+ *        dw[kc][cf][r][s] = sum_{b,oy,ox} coarse[b][kc][oy][ox] * q[b][cf][oy + r - 2][ox + s - 2]           (q zero outside nh x nw);
+ * only odd fine rows and odd fine columns are read.  Arithmetic, launches, determinism and error bound as ipsr_conv4x4s2_bf16x3_wrw.
+ * Supported: nw in {16, 32, 64, 128}, nh a multiple of max(1, 64 / nw), any Kc, Cf, B >= 1; anything else -> IPSR_ERR_UNSUPPORTED, checked
+ * before any launch and before anything is written.  The workspace query returns 0 where the shape is unsupported, reason in
+ * ipsr_last_error(); a short workspace is IPSR_ERR_WORKSPACE; fine, coarse, dw and ws must be 16-byte aligned.  Added without an ABI
+ * version change (15): entries are added, none changes. */
+size_t ipsr_conv4x4s2_bf16x3_dil_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
+int ipsr_conv4x4s2_bf16x3_dil_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
+                                  void* ws, size_t ws_bytes, void* stream);
 /* their weight gradient: x [B,Cin,H,W], dy [B,Cout,H,W] -> dw fp32 in the module's layout.  The reduction over pixels is cut over
  * workgroups; the partial results are added in a fixed order by a second launch (deterministic).  W in {16, 32, 64, 128}, H a multiple
  * of 128 / W.  form:

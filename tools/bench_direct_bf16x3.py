@@ -18,11 +18,15 @@
            gradient (ops.conv4x4s2_bf16x3 with ops.S2_DILATED, engine "bf16x3d" under hipconv.set_direct_dilated(True)): the new kernel
            against the engine `select` answers for the shape with the switch off, same process, same rounds; err = max |y - y64| / max |y64|
            against the fp64 convolution (first two images).
+  dilwrw   the weight gradient of the same dilated layers (ops.conv4x4s2_bf16x3_dil_wrw, engine "bf16x3w" under
+           hipconv.set_direct_dilated_dw(True)): the new kernel against the engine `select_wrw` answers for the shape with the switch off,
+           same process, same rounds; err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the whole batch.
   steps    the whole fp32 training step of bench.py (its model, batch and step function) under conv_math "fp32", "direct_bf16x3",
            "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw" and "bf16x3" in ONE process, alternated over `--rounds` rounds
-           (`--maths` narrows the list), each with hipconv.set_direct_dilated off and on (two columns; `--dilated off` / `on` keeps one).
+           (`--maths` narrows the list), each with hipconv.set_direct_dilated off and on (two columns; `--dilated off` / `on` keeps one) and,
+           with `--dilated-dw both`, with hipconv.set_direct_dilated_dw off and on as further columns (default: off only).
 
-    python tools/bench_direct_bf16x3.py [--what layers wrw s2 s2wrw dil steps] [--out profiles/direct_bf16x3_layers.txt]
+    python tools/bench_direct_bf16x3.py [--what layers wrw s2 s2wrw dil dilwrw steps] [--out profiles/direct_bf16x3_layers.txt]
 """
 import argparse
 import os
@@ -288,7 +292,52 @@ def dil(B, iters, rounds, emit):
                   min(ms["today"]), max(ms["today"]), err["today"], md["today"] / md["direct"], verdict))
 
 
-def steps(B, ksteps, rounds, emit, maths=None, dilated=(False, True)):
+def dilwrw(B, iters, rounds, emit):
+    from deepinpainting_amd.models import hipconv
+    g = torch.Generator(device="cuda").manual_seed(10)
+    hipconv.set_conv_math(fp32="fp32")
+    hipconv.set_direct_dilated_dw(False)
+    emit("k4 s2 p3 d2 weight gradient, batch %d, fp32 NCHW operands, dW fp32; ms = device time per call (HIP events, %d calls per burst, median of %d "
+         "alternated rounds, [min..max]); TF = useful flop / time" % (B, iters, rounds))
+    emit("err = max |dW - dW64| / max |dW64| against the fp64 weight gradient of the unrounded operands; today = the engine select_wrw answers with the switch off")
+    emit("wins = the kernel's slowest round is faster than today's fastest round; loses = the reverse; ties = the ranges overlap")
+    emit("%-22s %-5s | %-40s | %-44s | %s" % ("layer", "pass", "direct bf16x3  ms [min..max]  TF   err", "today's engine  ms [min..max]  err", "today / direct"))
+    for C, H in DIL_LAYERS:
+        n = H // 2
+        lay = (False, B, C, H, H, C, 4, 2, 3, 2)
+        w = torch.zeros(C, C, 4, 4, device="cuda")
+        x = torch.randn(B, C, H, H, device="cuda", generator=g)
+        dy = torch.randn(B, C, n, n, device="cuda", generator=g)
+        flops = 2.0 * 16 * C * C * B * n * n
+        label = "conv %4d->%-4d @%-3d   %-5s" % (C, C, H, "wrw")
+        today = hipconv.select_wrw(False, B, C, H, H, C, 4, 2, 3, 2)
+        if not ops.conv4x4s2_bf16x3_dil_wrw_supported(B, C, C, n, n):
+            emit("%s | unsupported (today: %s)" % (label, today))
+            continue
+        if today != "miopen":
+            base = lambda: hipconv._run_wrw(today, x, dy, w, lay, "fp32")
+        else:
+            base = lambda: torch.ops.aten.convolution_backward(dy, x, w, None, [2, 2], [3, 3], [2, 2], False, [0, 0], 1, [False, True, False])[1]
+        ref = torch.ops.aten.convolution_backward(dy.double(), x.double(), w.double(), None, [2, 2], [3, 3], [2, 2], False, [0, 0], 1, [False, True, False])[1]
+        engines = [("direct", lambda: ops.conv4x4s2_bf16x3_dil_wrw(x, dy, B, C, C, n, n)), ("today", base)]
+        err, ms = {}, {k: [] for k, _ in engines}
+        for k, fn in engines:
+            for _ in range(3):
+                y = fn()
+            err[k] = float((y.double() - ref).abs().max() / ref.abs().max())
+        del ref
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, fn in engines:
+                ms[k].append(burst_ms(fn, iters))
+        md = {k: statistics.median(v) for k, v in ms.items()}
+        verdict = "wins" if max(ms["direct"]) < min(ms["today"]) else "loses" if min(ms["direct"]) > max(ms["today"]) else "ties"
+        emit("%s | %7.4f [%6.4f..%6.4f] %6.1f %.1e | %-9s %7.4f [%6.4f..%6.4f] %.1e | %.2fx %s" %
+             (label, md["direct"], min(ms["direct"]), max(ms["direct"]), flops / md["direct"] / 1e9, err["direct"], today, md["today"],
+              min(ms["today"]), max(ms["today"]), err["today"], md["today"] / md["direct"], verdict))
+
+
+def steps(B, ksteps, rounds, emit, maths=None, dilated=(False, True), dilated_dw=(False,)):
     from deepinpainting_amd.models import hipconv
     from deepinpainting_amd.models.models import create_model
     from deepinpainting_amd.options import Option
@@ -299,12 +348,13 @@ def steps(B, ksteps, rounds, emit, maths=None, dilated=(False, True)):
     model = bench.quiet(create_model, opt)
     img, mask, ref = bench.synthetic_batch(device, B, 1234)
     maths = tuple(maths) if maths else ("fp32", "direct_bf16x3", "direct_bf16x3_dw", "direct_bf16x3_s2", "direct_bf16x3_s2_dw", "bf16x3")
-    variants = [(m, d) for m in maths for d in dilated]
+    variants = [(m, d, dw) for m in maths for d in dilated for dw in dilated_dw]
     rate = {v: [] for v in variants}
 
     def use(v):
         hipconv.set_conv_math(fp32=v[0])
         hipconv.set_direct_dilated(v[1])
+        hipconv.set_direct_dilated_dw(v[2])
     try:
         for v in variants:                                     # every variant's shapes warmed before any is timed
             use(v)
@@ -322,21 +372,24 @@ def steps(B, ksteps, rounds, emit, maths=None, dilated=(False, True)):
                 torch.cuda.synchronize()
                 rate[v].append(B * ksteps / (time.perf_counter() - t0))
     finally:
-        use(("fp32", False))
+        use(("fp32", False, False))
     emit("whole fp32 training step (bench.py's model and step, batch %d, eager, one process): images/s over %d steps, %d alternated rounds" % (B, ksteps, rounds))
-    emit("  one column per setting of hipconv.set_direct_dilated: median (rounds)")
+    emit("  one column per setting of hipconv.set_direct_dilated%s: median (rounds)" % (" / set_direct_dilated_dw" if len(dilated_dw) > 1 else ""))
+    onoff = lambda b: "on" if b else "off"
     for m in maths:
-        emit("  conv_math %-19s %s" % (m, "   ".join("dilated %-3s median %7.1f (%s)" % ("on" if d else "off", statistics.median(rate[(m, d)]),
-                                                                                  " ".join("%.1f" % r for r in rate[(m, d)])) for d in dilated)))
+        emit("  conv_math %-19s %s" % (m, "   ".join("dilated %-3s%s median %7.1f (%s)" % (
+            onoff(d), " dw %-3s" % onoff(dw) if len(dilated_dw) > 1 else "", statistics.median(rate[(m, d, dw)]), " ".join("%.1f" % r for r in rate[(m, d, dw)]))
+            for d in dilated for dw in dilated_dw)))
     losses = {k: float(v) for k, v in model.get_current_errors().items()}
     emit("  losses after the last step finite: %s" % all(v == v and abs(v) != float("inf") for v in losses.values()))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "s2", "s2wrw", "dil", "steps"))
+    ap.add_argument("--what", nargs="+", default=["layers", "steps"], choices=("layers", "wrw", "s2", "s2wrw", "dil", "dilwrw", "steps"))
     ap.add_argument("--maths", nargs="+", default=None, help="the arithmetics of the step table (default: all six)")
     ap.add_argument("--dilated", choices=("both", "off", "on"), default="both", help="the step table's columns: hipconv.set_direct_dilated off, on or both")
+    ap.add_argument("--dilated-dw", choices=("off", "both", "on"), default="off", help="the step table's columns: hipconv.set_direct_dilated_dw off, on or both")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
@@ -363,8 +416,11 @@ def main():
         s2wrw(a.batch, a.iters, a.rounds, emit)
     if "dil" in a.what:
         dil(a.batch, a.iters, a.rounds, emit)
+    if "dilwrw" in a.what:
+        dilwrw(a.batch, a.iters, a.rounds, emit)
     if "steps" in a.what:
-        steps(a.batch, a.steps, a.rounds, emit, a.maths, {"both": (False, True), "off": (False,), "on": (True,)}[a.dilated])
+        cols = {"both": (False, True), "off": (False,), "on": (True,)}
+        steps(a.batch, a.steps, a.rounds, emit, a.maths, cols[a.dilated], cols[a.dilated_dw])
 
 
 if __name__ == "__main__":
