@@ -19,6 +19,8 @@ void profile_mark_start(hipStream_t st, int region = 0);
 void profile_mark_stop(hipStream_t st, int region = 0, double work = 0.0, double work2 = 0.0);
 
 // tuning switches (ipsr_debug_set_option in ipsr_hip.h): A/B aids, every key defaults to the shipped behaviour
+//   1  winograd.hip: transform kernels without the XCD remap of their block ids
+//   2  winograd.hip: the independent transforms of a convolution as two launches instead of one paired launch
 int debug_option(int key);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

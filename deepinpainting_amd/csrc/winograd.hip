@@ -17,10 +17,11 @@
 //
 //      Y = A^T [ (G g G^T) (.) (B^T d B) ] A          per 4x4 output tile, summed over input channels
 //
-// Non-fused, four launches (all operands of the multiply stage are then plain reduction-major matrices):
-//   wino_filter_kernel   U[xi][c][k] = (G g G^T)[xi]                 from the weight tensor in any of the four roles
+// Non-fused, four stages in three launches (all operands of the multiply stage are then plain reduction-major matrices; the two
+// transforms do not depend on each other and share one launch: wino_pair_kernel, "transform bodies and their launches"):
+//   WinoFilter           U[xi][c][k] = (G g G^T)[xi]                 from the weight tensor in any of the four roles
 //                        (Conv2d / ConvTranspose2d, forward / backward-data: index strides + tap flip, as in conv_gemm.hip)
-//   wino_input_kernel    V[xi][c][t] = (B^T d B)[xi]                 d = 6x6 input window of tile t = (b, ty, tx), zero padded
+//   WinoInput            V[xi][c][t] = (B^T d B)[xi]                 d = 6x6 input window of tile t = (b, ty, tx), zero padded
 //   wino_gemm_kernel     M[xi][k][t] = sum_c U[xi][c][k] * V[xi][c][t]   36 independent GEMMs; both operands are [C][*]
 //                        with the reduction outermost — exactly the layout the correlation kernel streams by LDS-DMA, so
 //                        this is that kernel's pipeline (128x128 tile, 4-slot DMA ring, 32x32x2 fp32 MFMA) without the arg-max
@@ -194,10 +195,10 @@ template <bool TMAJOR, int MODE> constexpr int op_smem_bytes()
 }
 
 template <bool TMAJOR, int MODE>
-__device__ __forceinline__ OpIdx op_index(bool remap)
+__device__ __forceinline__ OpIdx op_index(unsigned bx, unsigned by)
 {
     OpIdx ix;
-    remap2d(remap, ix.bx, ix.by);
+    ix.bx = bx; ix.by = by;
     const int tid = threadIdx.x;
     if (!TMAJOR && MODE == 0) { ix.pk = 0; ix.rl = 0; ix.t = ix.bx * 256 + tid; ix.c = ix.by; }
     else if (!TMAJOR) { ix.pk = tid >> 5; ix.rl = tid & 31; ix.t = ix.bx * SPLIT_ROWS + ix.rl; ix.c = ix.by * 8 + ix.pk; }
@@ -235,24 +236,128 @@ __device__ __forceinline__ void op_emit(unsigned char* smem, const float (&v)[6]
     }
 }
 
-// U[xi][c][k], k < Kp (zero beyond K), from W[c*sc + k*sm + r*3 + s] (flip: r -> 2-r, s -> 2-s)
-// MODE 0: fp32 planes U[xi][c][k].  MODE 2 / 3: split bf16, Us[xi][plane][c/8][k][8] (grid = (Kp/32, C/8)).
-template <int MODE>
-__global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restrict__ W, int C, int K, int Kp, long sc, long sm, int flip,
-                                                          void* __restrict__ Uout)
+// ---- transform bodies and their launches ------------------------------------------------------------------------------------------
+// Every operand-producing transform is a BODY: a struct that holds the kernel's arguments, says how much LDS it wants (SMEM) and
+// runs one workgroup at the block coordinates it is handed.  wino_one_kernel launches one body on its own 2-D grid;
+// wino_pair_kernel launches the two bodies of a convolution that do not depend on each other (filter || input or window transform
+// of the data passes, tile || window transform of the weight gradients) as ONE 1-D grid: linear ids [0, n0) are the blocks of the
+// first part, [n0, n0 + n1) those of the second.  The branch is uniform per workgroup, so the barriers inside the bodies stay
+// legal; LDS and registers are the larger of the two.  The first part is the long, XCD-remapped transform (it sees the linear
+// ids it sees alone), the second the short one, which fills the last round.  `swap`: the first part is body B (weight gradients:
+// the operand with more blocks goes first).  Debug option 2 puts every site back on two launches (launch_pair).
+template <typename BODY>
+__global__ void __launch_bounds__(256) wino_one_kernel(const BODY body, int remap)
 {
-    __shared__ __attribute__((aligned(16))) unsigned short stage[MODE > 0 ? split_stage_elems<MODE ? MODE : 1>() : 8];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[BODY::SMEM];
+    unsigned bx, by;
+    remap2d(remap != 0, bx, by);
+    body(smem, bx, by);
+}
+
+// WAVES: waves per SIMD the kernel must keep (the occupancy of the long transform alone, where the short body alone would take a
+// register more than that allows).  The empty asm statements keep the compiler from sinking the two bodies' look-alike stores into
+// one tail, which made the registers of the pair the SUM of the two bodies' (88 instead of 52 for the 3x3 data passes).
+template <typename BODY_A, typename BODY_B, int WAVES = 1>
+__global__ void __launch_bounds__(256, WAVES) wino_pair_kernel(const BODY_A a, unsigned ax, const BODY_B b, unsigned bxn, unsigned n0, int swap, int remap)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[BODY_A::SMEM > BODY_B::SMEM ? BODY_A::SMEM : BODY_B::SMEM];
+    unsigned id = blockIdx.x;
+    const bool first = id < n0;
+    if (first) { if (remap) id = xcd_remap(id, n0); }
+    else id -= n0;
+    if (first != (swap != 0)) {
+        const unsigned y = id / ax;
+        a(smem, id - y * ax, y);
+        asm volatile("; end of part A" ::: "memory");
+    } else {
+        const unsigned y = id / bxn;
+        b(smem, id - y * bxn, y);
+        asm volatile("; end of part B" ::: "memory");
+    }
+}
+
+static int wino_paired() { return !debug_option(2); }   // one launch per pair of independent transforms; debug option 2 = two launches
+
+// the stand-alone launches, in the order they always had: the short transform in front of the long one
+template <typename BODY_A, typename BODY_B>
+static void launch_two(hipStream_t st, const BODY_A& first, dim3 ga, int remap, const BODY_B& second, dim3 gb)
+{
+    wino_one_kernel<BODY_B><<<gb, 256, 0, st>>>(second, 0);
+    wino_one_kernel<BODY_A><<<ga, 256, 0, st>>>(first, remap);
+}
+
+// `first` (the long transform; XCD-remapped when `remap`) and `second` on the stream in one launch.  `second_live` false:
+// `first` alone.
+template <int WAVES = 1, typename BODY_A, typename BODY_B>
+static void launch_pair(hipStream_t st, const BODY_A& first, dim3 ga, int remap, const BODY_B& second, dim3 gb, bool second_live = true)
+{
+    if (!second_live) { wino_one_kernel<BODY_A><<<ga, 256, 0, st>>>(first, remap); return; }
+    if (!wino_paired()) return launch_two(st, first, ga, remap, second, gb);
+    const unsigned na = ga.x * ga.y, nb = gb.x * gb.y;
+    wino_pair_kernel<BODY_A, BODY_B, WAVES><<<na + nb, 256, 0, st>>>(first, ga.x, second, gb.x, na, 0, remap);
+}
+
+// weight gradients: tile operand `a` and window operand `b`, neither remapped; the one with more blocks goes first.
+// tile_may_lead false (split bf16 x6: the tile bodies keep 8 waves per SIMD alone, the pair has the window body's 7): a call whose
+// tile operand is the longer one stays on two launches.  So does a call whose SHORTER operand has more than WRW_PAIR_MAX_SHORT
+// blocks: both are then long streaming kernels with nothing to hide behind each other, and the one measured (64 -> 64 @ 256^2,
+// batch 8: 8192 + 16384 blocks) was 1.9 % slower paired, where 128 -> 128 @ 128^2 (4096 + 4096) gained 2.6 %
+// (profiles/wino_paired_launch_layers.txt).
+constexpr unsigned WRW_PAIR_MAX_SHORT = 4096;
+template <typename BODY_A, typename BODY_B>
+static void launch_pair_wrw(hipStream_t st, const BODY_A& a, dim3 ga, const BODY_B& b, dim3 gb, bool tile_may_lead)
+{
+    const unsigned na = ga.x * ga.y, nb = gb.x * gb.y;
+    if (!wino_paired() || (na > nb && !tile_may_lead) || (na < nb ? na : nb) > WRW_PAIR_MAX_SHORT) {
+        wino_one_kernel<BODY_A><<<ga, 256, 0, st>>>(a, 0);
+        wino_one_kernel<BODY_B><<<gb, 256, 0, st>>>(b, 0);
+        return;
+    }
+    const int swap = nb > na;
+    wino_pair_kernel<BODY_A, BODY_B><<<na + nb, 256, 0, st>>>(a, ga.x, b, gb.x, swap ? nb : na, swap, 0);
+}
+
+// U[xi][c][k], k < Kp (zero beyond K), from W[c*sc + k*sm + r*3 + s] (flip: r -> 2-r, s -> 2-s)
+// MODE 0: fp32 planes U[xi][c][k] (grid = (Kp/256, C)).  MODE 2 / 3: split bf16, Us[xi][plane][c/8][k][8] (grid = (Kp/32, C/8)).
+// MODE 0 with sm == 9 (the produced channel is the weight tensor's inner index: Conv2d backward-data, ConvTranspose2d forward):
+// the workgroup's taps are ONE run of 9 x 256 floats, which crosses LDS so that the global reads are whole 256-byte wave accesses
+// instead of nine reads at a 36-byte lane pitch (4.3x the weights fetched, profiles/r03_wino_hbm_traffic.csv); pitch 9 is odd,
+// hence free of bank conflicts.  With sc == 9 the 36-byte runs of a workgroup lie a whole filter row apart and are read directly.
+template <int MODE>
+struct WinoFilter {
+    const float* W; int C, K, Kp; long sc, sm; int flip; void* Uout;
+    static constexpr int SMEM = MODE > 0 ? split_stage_elems<MODE ? MODE : 1>() * 2 : 256 * 9 * 4;
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    unsigned short* stage = reinterpret_cast<unsigned short*>(smem);
     int k, c;
-    if (MODE > 0) { k = blockIdx.x * SPLIT_ROWS + (threadIdx.x & 31); c = blockIdx.y * 8 + (threadIdx.x >> 5); }
-    else { k = blockIdx.x * 256 + threadIdx.x; c = blockIdx.y; if (k >= Kp) return; }
+    if (MODE > 0) { k = bx * SPLIT_ROWS + (threadIdx.x & 31); c = by * 8 + (threadIdx.x >> 5); }
+    else { k = bx * 256 + threadIdx.x; c = by; }
     float g[3][3];
+    if (MODE == 0 && sm == 9) {
+        float* taps = reinterpret_cast<float*>(smem);
+        const int k0 = bx * 256, n = (K - k0 < 256 ? K - k0 : 256) * 9;
+        const float* src = W + (long)c * sc + (long)k0 * 9;
+        for (int i = threadIdx.x; i < n; i += 256) taps[i] = src[i];
+        __syncthreads();
+        if (k >= Kp) return;
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            const int rr = flip ? 2 - r : r, ss = flip ? 2 - s : s;
-            g[r][s] = k < K ? W[(long)c * sc + (long)k * sm + rr * 3 + ss] : 0.0f;
-        }
+            for (int s = 0; s < 3; ++s) {
+                const int rr = flip ? 2 - r : r, ss = flip ? 2 - s : s;
+                g[r][s] = k < K ? taps[threadIdx.x * 9 + rr * 3 + ss] : 0.0f;
+            }
+    } else {
+        if (MODE == 0 && k >= Kp) return;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const int rr = flip ? 2 - r : r, ss = flip ? 2 - s : s;
+                g[r][s] = k < K ? W[(long)c * sc + (long)k * sm + rr * 3 + ss] : 0.0f;
+            }
+    }
     float t[6][3], u[6][6];
 #pragma unroll
     for (int s = 0; s < 3; ++s) {                 // columns: t[:,s] = G g[:,s]
@@ -265,27 +370,28 @@ __global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_g(t[i], u[i]);          // rows: u[i,:] = G t[i,:]
     if (MODE > 0) {
-        store_split<MODE ? MODE : 1>(stage, u, threadIdx.x >> 5, threadIdx.x & 31, static_cast<unsigned short*>(Uout), C / 8, Kp, blockIdx.y,
-                                     (size_t)blockIdx.x * SPLIT_ROWS);
+        store_split<MODE ? MODE : 1>(stage, u, threadIdx.x >> 5, threadIdx.x & 31, static_cast<unsigned short*>(Uout), C / 8, Kp, by,
+                                     (size_t)bx * SPLIT_ROWS);
         return;
     }
-    float* U = static_cast<float*>(Uout);
+    float* __restrict__ U = static_cast<float*>(Uout);
     const size_t plane = (size_t)C * Kp;
 #pragma unroll
     for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int j = 0; j < 6; ++j) U[(size_t)(i * 6 + j) * plane + (size_t)c * Kp + k] = u[i][j];
-}
+    }
+};
 
 // MODE 0: fp32 planes V[xi][c][t].  MODE 2 / 3: split bf16, Vs[xi][plane][c/8][t][8] (grid = (Tp/32, C/8)).  TIN: float, or
 // unsigned short = bf16 activations (BASELINE config 5).
 template <int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_input_kernel(const TIN* __restrict__ x, int B, int C, int H, int Wd, int TY, int TX, int Tp,
-                                                         void* __restrict__ Vout, int remap)
-{
-    __shared__ __attribute__((aligned(16))) unsigned short stage[MODE > 0 ? split_stage_elems<MODE ? MODE : 1>() : 8];
-    unsigned bx, by;
-    remap2d(remap != 0, bx, by);
+struct WinoInput {
+    const TIN* x; int B, C, H, Wd, TY, TX, Tp; void* Vout;
+    static constexpr int SMEM = MODE > 0 ? split_stage_elems<MODE ? MODE : 1>() * 2 : 16;
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    unsigned short* stage = reinterpret_cast<unsigned short*>(smem);
     int t, c;
     if (MODE > 0) { t = bx * SPLIT_ROWS + (threadIdx.x & 31); c = by * 8 + (threadIdx.x >> 5); }
     else { t = bx * 256 + threadIdx.x; c = by; if (t >= Tp) return; }
@@ -342,13 +448,14 @@ __global__ void __launch_bounds__(256) wino_input_kernel(const TIN* __restrict__
                                      (size_t)bx * SPLIT_ROWS);
         return;
     }
-    float* V = static_cast<float*>(Vout);
+    float* __restrict__ V = static_cast<float*>(Vout);
     const size_t plane = (size_t)C * Tp;
 #pragma unroll
     for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int j = 0; j < 6; ++j) V[(size_t)(i * 6 + j) * plane + (size_t)c * Tp + t] = v[i][j];
-}
+    }
+};
 
 // y[b][k][4ty+i][4tx+j] = (A^T M A)[i][j], M = the sum of the GEMM's `nsplit` partial results (ascending: deterministic).
 // EPI: 0 plain; 1 = + bias[k], ReLU; 2 = + bias[k], ReLU, 2x2 max-pool (y is then [B,K,H/2,W/2]) — the VGG16 chain
@@ -434,11 +541,12 @@ __device__ __forceinline__ void wino_store_tmajor(float (*stage)[16][17], const 
 
 // window operand (x for Conv2d, dy for ConvTranspose2d):  Vt[xi][t][c] = (B^T d B)[xi], zero for t >= T or c >= C
 template <int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_wrw_window_kernel(const TIN* __restrict__ x, int B, int C, int H, int Wd, int TY, int TX,
-                                                              int Tp, int Cp, void* __restrict__ Vt)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<true, MODE>()];
-    const OpIdx ix = op_index<true, MODE>(false);
+struct WinoWrwWindow {
+    const TIN* x; int B, C, H, Wd, TY, TX, Tp, Cp; void* Vt;
+    static constexpr int SMEM = op_smem_bytes<true, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<true, MODE>(bx, by);
     const int t = ix.t, c = ix.c, T = B * TY * TX;
     float d[6][6];
     const bool live = t < T && c < C;
@@ -468,15 +576,17 @@ __global__ void __launch_bounds__(256) wino_wrw_window_kernel(const TIN* __restr
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_bt(w[i], v[i]);
     op_emit<true, MODE>(smem, v, ix, Vt, Cp, Tp);
-}
+    }
+};
 
 // tile operand (dy for Conv2d, x for ConvTranspose2d):  Et[xi][t][k] = (G' e G'^T)[xi], e = the 4x4 tile, zero beyond T / K
 template <int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_wrw_tile_kernel(const TIN* __restrict__ dy, int B, int K, int H, int Wd, int TY, int TX,
-                                                            int Tp, int Kp, void* __restrict__ Et)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<true, MODE>()];
-    const OpIdx ix = op_index<true, MODE>(false);
+struct WinoWrwTile {
+    const TIN* dy; int B, K, H, Wd, TY, TX, Tp, Kp; void* Et;
+    static constexpr int SMEM = op_smem_bytes<true, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<true, MODE>(bx, by);
     const int t = ix.t, k = ix.c, T = B * TY * TX;
     const bool live = t < T && k < K;
     int b = 0, ty = 0, tx = 0;
@@ -502,7 +612,8 @@ __global__ void __launch_bounds__(256) wino_wrw_tile_kernel(const TIN* __restric
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_g4(w[i], v[i]);
     op_emit<true, MODE>(smem, v, ix, Et, Kp, Tp);
-}
+    }
+};
 
 // dW[k][c][r][s] = (A'^T Mw[:][k][c] A')[r][s]
 __global__ void __launch_bounds__(256) wino_wrw_output_kernel(const float* __restrict__ Mw, WinoSplit split, int K, int C, int Kp, int Cp,
@@ -996,13 +1107,13 @@ int launch_winograd(const void* x, const float* w, void* y, int B, int C, int K,
     const int remap = wino_remap();
     with_mode(ar.math, [&](auto M) {
         constexpr int MODE = decltype(M)::value;
-        if (!(u_cache && u_valid)) wino_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, C), 256, 0, st>>>(w, C, K, p.rows, sc, sm, flip, m.A);
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_input_kernel<MODE, T><<<op_grid(false, MODE, p.Tp, C), 256, 0, st>>>(static_cast<const T*>(x), B, C, H, W, p.TY, p.TX, p.Tp, m.B, remap);
+            launch_pair(st, WinoInput<MODE, T>{static_cast<const T*>(x), B, C, H, W, p.TY, p.TX, p.Tp, m.B}, op_grid(false, MODE, p.Tp, C), remap,
+                        WinoFilter<MODE>{w, C, K, p.rows, sc, sm, flip, m.A}, op_grid(false, MODE, p.rows, C), !(u_cache && u_valid));
         });
     });
-    if (int rc = check_launch("wino_input_kernel")) return rc;
+    if (int rc = check_launch("wino_pair_kernel<WinoInput, WinoFilter>")) return rc;
     if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * C * K * p.T)) return rc;
     const dim3 og(cdiv(p.T, 256), K);
     with_type(ar.out_bf16, [&](auto* tag) {
@@ -1039,11 +1150,12 @@ int launch_winograd_wrw(const void* et, const void* dt, float* dW, int B, int K,
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(et), B, K, H, W, p.TY, p.TX, p.Tp, p.rows, m.A);
-            wino_wrw_window_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.cols), 256, 0, st>>>(static_cast<const T*>(dt), B, C, H, W, p.TY, p.TX, p.Tp, p.cols, m.B);
+            launch_pair_wrw(st, WinoWrwTile<MODE, T>{static_cast<const T*>(et), B, K, H, W, p.TY, p.TX, p.Tp, p.rows, m.A}, op_grid(true, MODE, p.Tp, p.rows),
+                            WinoWrwWindow<MODE, T>{static_cast<const T*>(dt), B, C, H, W, p.TY, p.TX, p.Tp, p.cols, m.B}, op_grid(true, MODE, p.Tp, p.cols),
+                            MODE != 3);
         });
     });
-    if (int rc = check_launch("wino_wrw_window_kernel")) return rc;
+    if (int rc = check_launch("wino_pair_kernel<WinoWrwTile, WinoWrwWindow>")) return rc;
     // M[xi][k][c] = sum_t Et[xi][t][k] * Vt[xi][t][c]: the same GEMM with the tiles as the reduction
     if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * K * C)) return rc;
     wino_wrw_output_kernel<<<dim3(cdiv(C, 256), K), 256, 0, st>>>(m.M, p.sp, K, C, p.rows, p.cols, dW);
@@ -1067,11 +1179,12 @@ int launch_winograd_wrw(const void* et, const void* dt, float* dW, int B, int K,
 // generic window transform: V[xi][c][t] (TMAJOR = false) or V[xi][t][c] (true) of windows at origin OS*t read as
 // x[c][IS*(origin + i) + off]
 template <int OS, int IS, bool TMAJOR, int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_window_kernel(const TIN* __restrict__ x, int B, int C, int H, int Wd, int off, int TY, int TX,
-                                                          int Tp, int Cp, void* __restrict__ V, int remap)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<TMAJOR, MODE>()];
-    const OpIdx ix = op_index<TMAJOR, MODE>(!TMAJOR && remap != 0);
+struct WinoWindow {
+    const TIN* x; int B, C, H, Wd, off, TY, TX, Tp, Cp; void* V;
+    static constexpr int SMEM = op_smem_bytes<TMAJOR, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<TMAJOR, MODE>(bx, by);
     const int t = ix.t, c = ix.c;
     if (!TMAJOR && MODE == 0 && t >= Tp) return;
     const int T = B * TY * TX;
@@ -1102,25 +1215,45 @@ __global__ void __launch_bounds__(256) wino_window_kernel(const TIN* __restrict_
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_bt(w[i], v[i]);
     op_emit<TMAJOR, MODE>(smem, v, ix, V, TMAJOR ? Cp : C, Tp);
-}
+    }
+};
 
 // U[xi][c][k] = (G' g G'^T)[xi] for 4x4 taps: W[c*sc + k*sm + r*4 + s] (flip: r -> 3-r, s -> 3-s)
+// MODE 0 with sm == 16 (backward-data): the workgroup's taps are one run of 16 x 256 floats and cross LDS like WinoFilter's
+// (pitch 17: the lanes' 64-byte rows would otherwise all start in the same bank).
 template <int MODE>
-__global__ void __launch_bounds__(256) wino4_filter_kernel(const float* __restrict__ W, int C, int K, int Kp, long sc, long sm, int flip,
-                                                           void* __restrict__ U)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<false, MODE>()];
-    const OpIdx ix = op_index<false, MODE>(false);
+struct Wino4Filter {
+    const float* W; int C, K, Kp; long sc, sm; int flip; void* U;
+    static constexpr int SMEM = MODE > 0 ? op_smem_bytes<false, MODE>() : 256 * 17 * 4;
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<false, MODE>(bx, by);
     const int k = ix.t, c = ix.c;
-    if (MODE == 0 && k >= Kp) return;
     float g[4][4];
+    if (MODE == 0 && sm == 16) {
+        float* taps = reinterpret_cast<float*>(smem);
+        const int k0 = bx * 256, n = (K - k0 < 256 ? K - k0 : 256) * 16;
+        const float* src = W + (long)c * sc + (long)k0 * 16;
+        for (int i = threadIdx.x; i < n; i += 256) taps[(i >> 4) * 17 + (i & 15)] = src[i];
+        __syncthreads();
+        if (k >= Kp) return;
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-            const int rr = flip ? 3 - r : r, ss = flip ? 3 - s2 : s2;
-            g[r][s2] = k < K ? W[(long)c * sc + (long)k * sm + rr * 4 + ss] : 0.0f;
-        }
+            for (int s2 = 0; s2 < 4; ++s2) {
+                const int rr = flip ? 3 - r : r, ss = flip ? 3 - s2 : s2;
+                g[r][s2] = k < K ? taps[threadIdx.x * 17 + rr * 4 + ss] : 0.0f;
+            }
+    } else {
+        if (MODE == 0 && k >= Kp) return;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int s2 = 0; s2 < 4; ++s2) {
+                const int rr = flip ? 3 - r : r, ss = flip ? 3 - s2 : s2;
+                g[r][s2] = k < K ? W[(long)c * sc + (long)k * sm + rr * 4 + ss] : 0.0f;
+            }
+    }
     float t[6][4], u[6][6];
 #pragma unroll
     for (int s2 = 0; s2 < 4; ++s2) {
@@ -1133,7 +1266,8 @@ __global__ void __launch_bounds__(256) wino4_filter_kernel(const float* __restri
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_g4(t[i], u[i]);
     op_emit<false, MODE>(smem, u, ix, U, C, Kp);
-}
+    }
+};
 
 // y[b][k][os*(3ty+i)+oo][os*(3tx+j)+oo] = (A'^T M A')[i][j] for 3ty+i < Ho, 3tx+j < Wo  (y is [B,K,Hy,Wy])
 template <typename TOUT>
@@ -1171,11 +1305,12 @@ __global__ void __launch_bounds__(256) wino3_output_kernel(const float* __restri
 
 // weight gradient: 3x3 tiles of dy -> Et[xi][t][k] = (G e G^T)[xi]
 template <int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_wrw_tile3_kernel(const TIN* __restrict__ dy, int B, int K, int Ho, int Wo, int TY, int TX,
-                                                             int Tp, int Kp, void* __restrict__ Et)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<true, MODE>()];
-    const OpIdx ix = op_index<true, MODE>(false);
+struct WinoWrwTile3 {
+    const TIN* dy; int B, K, Ho, Wo, TY, TX, Tp, Kp; void* Et;
+    static constexpr int SMEM = op_smem_bytes<true, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<true, MODE>(bx, by);
     const int t = ix.t, k = ix.c, T = B * TY * TX;
     const bool live = t < T && k < K;
     int b = 0, ty = 0, tx = 0;
@@ -1201,7 +1336,8 @@ __global__ void __launch_bounds__(256) wino_wrw_tile3_kernel(const TIN* __restri
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_g(w[i], v[i]);
     op_emit<true, MODE>(smem, v, ix, Et, Kp, Tp);
-}
+    }
+};
 
 // dW[k][c][r][s] (4x4) = (A^T Mw[:][k][c] A)[r][s]
 __global__ void __launch_bounds__(256) wino_wrw_output4_kernel(const float* __restrict__ Mw, WinoSplit split, int K, int C, int Kp, int Cp,
@@ -1260,13 +1396,13 @@ size_t winograd_dil_ws_bytes(int geom, int mode, int B, int Cin, int H, int W, i
     return wino_ws_bytes([&](WinoGemmPlan* p, int math) { return dil_plan(geom, mode, B, Cin, H, W, Cout, p, math); });
 }
 
-template <bool TMAJOR, int MODE, typename T>
-static void launch_window3(int is, hipStream_t st, const T* x, int B, int C, int H, int W, int off, const WinoGemmPlan& p, int Cp, void* V)
+// hands f the window body of the 3x3-tile family for the input stride `is` (2: the dilated layer's sub-sampled image) and its grid
+template <bool TMAJOR, int MODE, typename T, typename F>
+static void with_window3(int is, const T* x, int B, int C, int H, int W, int off, const WinoGemmPlan& p, int Cp, void* V, F&& f)
 {
     const dim3 grid = op_grid(TMAJOR, MODE, p.Tp, TMAJOR ? Cp : C);
-    const int remap = wino_remap();
-    if (is == 2) wino_window_kernel<3, 2, TMAJOR, MODE, T><<<grid, 256, 0, st>>>(x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V, remap);
-    else wino_window_kernel<3, 1, TMAJOR, MODE, T><<<grid, 256, 0, st>>>(x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V, remap);
+    if (is == 2) f(WinoWindow<3, 2, TMAJOR, MODE, T>{x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V}, grid);
+    else f(WinoWindow<3, 1, TMAJOR, MODE, T>{x, B, C, H, W, off, p.TY, p.TX, p.Tp, Cp, V}, grid);
 }
 
 // x [B,Cin,H,W], w [Cout,Cin,4,4], y / dy [B,Cout,Ho,Wo]
@@ -1291,15 +1427,17 @@ int launch_winograd_dil(int geom, int mode, const void* a, const void* b2, void*
         const float* w = static_cast<const float*>(b2);
         with_mode(ar.math, [&](auto M) {
             constexpr int MODE = decltype(M)::value;
-            if (mode == 0) wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, Cin), 256, 0, st>>>(w, Cin, Cout, p.rows, 16, (long)Cin * 16, 0, m.A);
-            else wino4_filter_kernel<MODE><<<op_grid(false, MODE, p.rows, Cout), 256, 0, st>>>(w, Cout, Cin, p.rows, (long)Cin * 16, 16, 1, m.A);
+            const Wino4Filter<MODE> filt = mode == 0 ? Wino4Filter<MODE>{w, Cin, Cout, p.rows, 16, (long)Cin * 16, 0, m.A}
+                                                     : Wino4Filter<MODE>{w, Cout, Cin, p.rows, (long)Cin * 16, 16, 1, m.A};
+            const dim3 fgrid = op_grid(false, MODE, p.rows, red);
             with_type(ar.in_bf16, [&](auto* tag) {
                 using T = ELEM_T(tag);
-                if (mode == 0) launch_window3<false, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, 0, m.B);
-                else launch_window3<false, MODE, T>(1, st, static_cast<const T*>(a), B, Cout, Ho, Wo, geom == 0 ? -1 : -2, p, 0, m.B);
+                auto go = [&](const auto& win, dim3 grid) { launch_pair(st, win, grid, wino_remap(), filt, fgrid); };
+                if (mode == 0) with_window3<false, MODE, T>(xis, static_cast<const T*>(a), B, Cin, H, W, xoff, p, 0, m.B, go);
+                else with_window3<false, MODE, T>(1, static_cast<const T*>(a), B, Cout, Ho, Wo, geom == 0 ? -1 : -2, p, 0, m.B, go);
             });
         });
-        if (int rc = check_launch("wino_window_kernel")) return rc;
+        if (int rc = check_launch("wino_pair_kernel<WinoWindow, Wino4Filter>")) return rc;
         if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * red * prod * p.T)) return rc;
         with_type(ar.out_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
@@ -1314,11 +1452,13 @@ int launch_winograd_dil(int geom, int mode, const void* a, const void* b2, void*
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile3_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(b2), B, Cout, Ho, Wo, p.TY, p.TX, p.Tp, p.rows, m.A);
-            launch_window3<true, MODE, T>(xis, st, static_cast<const T*>(a), B, Cin, H, W, xoff, p, p.cols, m.B);
+            const WinoWrwTile3<MODE, T> tile{static_cast<const T*>(b2), B, Cout, Ho, Wo, p.TY, p.TX, p.Tp, p.rows, m.A};
+            with_window3<true, MODE, T>(xis, static_cast<const T*>(a), B, Cin, H, W, xoff, p, p.cols, m.B, [&](const auto& win, dim3 grid) {
+                launch_pair_wrw(st, tile, op_grid(true, MODE, p.Tp, p.rows), win, grid, MODE != 3);
+            });
         });
     });
-    if (int rc = check_launch("wino_window_kernel")) return rc;
+    if (int rc = check_launch("wino_pair_kernel<WinoWrwTile3, WinoWindow>")) return rc;
     if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * Cout * Cin)) return rc;
     wino_wrw_output4_kernel<<<dim3(cdiv(Cin, 256), Cout), 256, 0, st>>>(m.M, p.sp, Cout, Cin, p.rows, p.cols, static_cast<float*>(out));
     return check_launch("wino_wrw_output4_kernel");
@@ -1380,9 +1520,13 @@ __device__ __forceinline__ void wino_at2(const float m[6], float y[2])       // 
 //   form 1 (mode 1): reduction row r = kc,              produced column q = (phase, cf) of 4*Cf; g[a][b] = w[3-ey-2a][3-ex-2b]
 // One thread per (kc, cf): its 16 taps are one 64-byte read, the four phases' 4 x 36 numbers go out with the q index
 // fastest across the threads (form 0: kc, form 1: cf), i.e. coalesced.  Columns q in [Q, Qp) are zero-filled by the same threads.
-__global__ void __launch_bounds__(256) wino52_filter_kernel(const float* __restrict__ W, int Kc, int Cf, int Qp, int form, float* __restrict__ U)
-{
-    const int fast = blockIdx.x * 256 + threadIdx.x, slow = blockIdx.y;
+struct Wino52Filter {
+    const float* W; int Kc, Cf, Qp, form; float* Uout;
+    static constexpr int SMEM = 16;
+    __device__ __forceinline__ void operator()(unsigned char*, unsigned bx, unsigned by) const
+    {
+    float* __restrict__ U = Uout;
+    const int fast = bx * 256 + threadIdx.x, slow = by;
     const int nfast = form == 0 ? Kc : Cf;
     const int R = form == 0 ? 4 * Cf : Kc, Q = form == 0 ? Kc : 4 * Cf;
     const size_t plane = (size_t)R * Qp;
@@ -1429,19 +1573,22 @@ __global__ void __launch_bounds__(256) wino52_filter_kernel(const float* __restr
 #pragma unroll
             for (int j = 0; j < 6; ++j) U[(size_t)(i * 6 + j) * plane + r * Qp + q] = u[i][j];
     }
-}
+    }
+};
 
 // split-bf16 twin (see store_split): workgroup = 8 reduction indices x 32 columns of (kc, cf) pairs, the four phases stored one after
 // the other.  form 0: reduction (ph, cf) -> blocks of 8 cf, columns kc (grid (Qp/32, Cf/8), padding columns are zero);
 // form 1: reduction kc -> blocks of 8 kc, columns (ph, cf) (grid (Cf/32, Kc/8); host requires Cf % 32 == 0 and Qp == 4*Cf).
 template <int NPL>
-__global__ void __launch_bounds__(256) wino52_filter_split_kernel(const float* __restrict__ W, int Kc, int Cf, int Qp, int form,
-                                                                  unsigned short* __restrict__ U)
-{
-    __shared__ __attribute__((aligned(16))) unsigned short stage[split_stage_elems<NPL>()];
+struct Wino52FilterSplit {
+    const float* W; int Kc, Cf, Qp, form; unsigned short* U;
+    static constexpr int SMEM = split_stage_elems<NPL>() * 2;
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    unsigned short* stage = reinterpret_cast<unsigned short*>(smem);
     const int pk = threadIdx.x >> 5, rl = threadIdx.x & 31;
-    const int kc = form == 0 ? blockIdx.x * SPLIT_ROWS + rl : blockIdx.y * 8 + pk;
-    const int cf = form == 0 ? blockIdx.y * 8 + pk : blockIdx.x * SPLIT_ROWS + rl;
+    const int kc = form == 0 ? bx * SPLIT_ROWS + rl : by * 8 + pk;
+    const int cf = form == 0 ? by * 8 + pk : bx * SPLIT_ROWS + rl;
     const bool live = kc < Kc && cf < Cf;
     float w[4][4];
     const float4* wp = reinterpret_cast<const float4*>(W + ((size_t)(live ? kc : 0) * Cf + (live ? cf : 0)) * 16);
@@ -1469,21 +1616,23 @@ __global__ void __launch_bounds__(256) wino52_filter_split_kernel(const float* _
         }
 #pragma unroll
         for (int i = 0; i < 6; ++i) wino_g2(t[i], u[i]);
-        if (form == 0) store_split<NPL>(stage, u, pk, rl, U, (size_t)4 * Cf / 8, Qp, (size_t)ph * Cf / 8 + blockIdx.y, (size_t)blockIdx.x * SPLIT_ROWS);
-        else store_split<NPL>(stage, u, pk, rl, U, (size_t)Kc / 8, Qp, blockIdx.y, (size_t)ph * Cf + (size_t)blockIdx.x * SPLIT_ROWS);
+        if (form == 0) store_split<NPL>(stage, u, pk, rl, U, (size_t)4 * Cf / 8, Qp, (size_t)ph * Cf / 8 + by, (size_t)bx * SPLIT_ROWS);
+        else store_split<NPL>(stage, u, pk, rl, U, (size_t)Kc / 8, Qp, by, (size_t)ph * Cf + (size_t)bx * SPLIT_ROWS);
     }
-}
+    }
+};
 
 // windows at tile stride 5: V[xi][cc][t] (TMAJOR = false) or V[xi][t][cc] (true), cc = (phase, c) of nphase*C.
 //   nphase = 4, IS = 2: P_e[5t + i] = x[2(5t+i) + e], e = (ey-1, ex-1)  (modes 0 and 2, x = the fine tensor)
 //   nphase = 1, IS = 1: x[5t + i - 1]                                    (mode 1, x = the coarse tensor)
 template <int IS, bool TMAJOR, int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino5_window_kernel(const TIN* __restrict__ x, int B, int C, int H, int Wd, int nphase, int TY, int TX,
-                                                           int Tp, int Cp, void* __restrict__ V, int remap)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<TMAJOR, MODE>()];
+struct Wino5Window {
+    const TIN* x; int B, C, H, Wd, nphase, TY, TX, Tp, Cp; void* V;
+    static constexpr int SMEM = op_smem_bytes<TMAJOR, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
     const int Ctot = nphase * C;
-    const OpIdx ix = op_index<TMAJOR, MODE>(!TMAJOR && remap != 0);
+    const OpIdx ix = op_index<TMAJOR, MODE>(bx, by);
     const int t = ix.t, cc = ix.c;
     if (!TMAJOR && MODE == 0 && t >= Tp) return;
     const int T = B * TY * TX;
@@ -1515,7 +1664,8 @@ __global__ void __launch_bounds__(256) wino5_window_kernel(const TIN* __restrict
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_bt(w[i], v[i]);
     op_emit<TMAJOR, MODE>(smem, v, ix, V, TMAJOR ? Cp : Ctot, Tp);
-}
+    }
+};
 
 __device__ __forceinline__ void wino_at5_2d(const float m[6][6], float o[5][5])
 {
@@ -1602,11 +1752,12 @@ __global__ void __launch_bounds__(256) wino5_output_rows_kernel(const float* __r
 
 // mode 2: 5x5 tiles of the coarse tensor -> Et[xi][t][k] = (G5 e G5^T)[xi]
 template <int MODE, typename TIN>
-__global__ void __launch_bounds__(256) wino_wrw_tile5_kernel(const TIN* __restrict__ dy, int B, int K, int Ho, int Wo, int TY, int TX,
-                                                             int Tp, int Kp, void* __restrict__ Et)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[op_smem_bytes<true, MODE>()];
-    const OpIdx ix = op_index<true, MODE>(false);
+struct WinoWrwTile5 {
+    const TIN* dy; int B, K, Ho, Wo, TY, TX, Tp, Kp; void* Et;
+    static constexpr int SMEM = op_smem_bytes<true, MODE>();
+    __device__ __forceinline__ void operator()(unsigned char* smem, unsigned bx, unsigned by) const
+    {
+    const OpIdx ix = op_index<true, MODE>(bx, by);
     const int t = ix.t, k = ix.c, T = B * TY * TX;
     const bool live = t < T && k < K;
     int b = 0, ty = 0, tx = 0;
@@ -1632,7 +1783,8 @@ __global__ void __launch_bounds__(256) wino_wrw_tile5_kernel(const TIN* __restri
 #pragma unroll
     for (int i = 0; i < 6; ++i) wino_g5(w[i], v[i]);
     op_emit<true, MODE>(smem, v, ix, Et, Kp, Tp);
-}
+    }
+};
 
 // mode 2: dW[kc][cf][2a+ey][2b+ex] = (A2^T Mw[:][kc][(ph, cf)] A2)[a][b]; one phase per blockIdx.z
 __global__ void __launch_bounds__(256) wino_wrw_output2_kernel(const float* __restrict__ Mw, WinoSplit split, int Kc, int Cf, int Kp, int Cp,
@@ -1691,23 +1843,30 @@ int launch_winograd_s2(int mode, const void* a, const void* b2, void* out, int B
     const int remap = wino_remap();
     if (mode == 0 || mode == 1) {
         const float* w = static_cast<const float*>(b2);
-        if (ar.math == 0) {
-            if (mode == 0) wino52_filter_kernel<<<dim3(cdiv(p.rows, 256), Cf), 256, 0, st>>>(w, Kc, Cf, p.rows, 0, m.A);
-            else wino52_filter_kernel<<<dim3(cdiv(Cf + (p.rows - 4 * Cf), 256), Kc), 256, 0, st>>>(w, Kc, Cf, p.rows, 1, m.A);
-        } else {
-            const dim3 fg = mode == 0 ? dim3(p.rows / SPLIT_ROWS, Cf / 8) : dim3(Cf / SPLIT_ROWS, Kc / 8);
-            if (ar.math == 2) wino52_filter_split_kernel<2><<<fg, 256, 0, st>>>(w, Kc, Cf, p.rows, mode, reinterpret_cast<unsigned short*>(m.A));
-            else wino52_filter_split_kernel<3><<<fg, 256, 0, st>>>(w, Kc, Cf, p.rows, mode, reinterpret_cast<unsigned short*>(m.A));
-        }
         with_mode(ar.math, [&](auto M) {
             constexpr int MODE = decltype(M)::value;
             with_type(ar.in_bf16, [&](auto* tag) {
                 using T = ELEM_T(tag);
-                if (mode == 0) wino5_window_kernel<2, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, 0, m.B, remap);
-                else wino5_window_kernel<1, false, MODE, T><<<op_grid(false, MODE, p.Tp, p.red), 256, 0, st>>>(static_cast<const T*>(a), B, Kc, nh, nw, 1, p.TY, p.TX, p.Tp, 0, m.B, remap);
+                const dim3 wgrid = op_grid(false, MODE, p.Tp, p.red);
+                // fp32: paired, at the window transform's own 8 waves per SIMD (the filter body alone takes 65 registers).  Split
+                // arithmetics: Wino52FilterSplit takes 106-116 registers (4 waves) against the window transform's 54-67 (7-8), so
+                // that pair would halve the long transform's occupancy: two launches.
+                auto go = [&](const auto& filt, dim3 fgrid) {
+                    auto pair = [&](const auto& win) {
+                        if constexpr (MODE == 0) launch_pair<8>(st, win, wgrid, remap, filt, fgrid);
+                        else launch_two(st, win, wgrid, remap, filt, fgrid);
+                    };
+                    if (mode == 0) pair(Wino5Window<2, false, MODE, T>{static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, 0, m.B});
+                    else pair(Wino5Window<1, false, MODE, T>{static_cast<const T*>(a), B, Kc, nh, nw, 1, p.TY, p.TX, p.Tp, 0, m.B});
+                };
+                if constexpr (MODE == 0)
+                    go(Wino52Filter{w, Kc, Cf, p.rows, mode, m.A}, mode == 0 ? dim3(cdiv(p.rows, 256), Cf) : dim3(cdiv(Cf + (p.rows - 4 * Cf), 256), Kc));
+                else
+                    go(Wino52FilterSplit<MODE>{w, Kc, Cf, p.rows, mode, reinterpret_cast<unsigned short*>(m.A)},
+                       mode == 0 ? dim3(p.rows / SPLIT_ROWS, Cf / 8) : dim3(Cf / SPLIT_ROWS, Kc / 8));
             });
         });
-        if (int rc = check_launch("wino5_window_kernel")) return rc;
+        if (int rc = check_launch("wino_pair_kernel<Wino5Window, Wino52Filter>")) return rc;
         if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.red * (mode == 0 ? Kc : 4 * Cf) * p.T)) return rc;
         with_type(ar.out_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
@@ -1721,11 +1880,12 @@ int launch_winograd_s2(int mode, const void* a, const void* b2, void* out, int B
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
             using T = ELEM_T(tag);
-            wino_wrw_tile5_kernel<MODE, T><<<op_grid(true, MODE, p.Tp, p.rows), 256, 0, st>>>(static_cast<const T*>(b2), B, Kc, nh, nw, p.TY, p.TX, p.Tp, p.rows, m.A);
-            wino5_window_kernel<2, true, MODE, T><<<op_grid(true, MODE, p.Tp, p.cols), 256, 0, st>>>(static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, p.cols, m.B, 0);
+            launch_pair_wrw(st, WinoWrwTile5<MODE, T>{static_cast<const T*>(b2), B, Kc, nh, nw, p.TY, p.TX, p.Tp, p.rows, m.A}, op_grid(true, MODE, p.Tp, p.rows),
+                            Wino5Window<2, true, MODE, T>{static_cast<const T*>(a), B, Cf, 2 * nh, 2 * nw, 4, p.TY, p.TX, p.Tp, p.cols, m.B}, op_grid(true, MODE, p.Tp, p.cols),
+                            MODE != 3);
         });
     });
-    if (int rc = check_launch("wino5_window_kernel")) return rc;
+    if (int rc = check_launch("wino_pair_kernel<WinoWrwTile5, Wino5Window>")) return rc;
     if (int rc = launch_wino_gemm(ar.math, p, m, st, 72.0 * p.T * Kc * 4 * Cf)) return rc;
     wino_wrw_output2_kernel<<<dim3(cdiv(Cf, 256), Kc, 4), 256, 0, st>>>(m.M, p.sp, Kc, Cf, p.rows, p.cols, static_cast<float*>(out));
     return check_launch("wino_wrw_output2_kernel");
@@ -1779,7 +1939,7 @@ int ipsr_conv3x3_winograd_mp(int op, const void* in, const float* weight, const 
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_winograd: out / workspace / filter_cache must be 16-byte aligned");
     ConvArith ar;
     if (int rc = arith_from("ipsr_conv3x3_winograd_mp", math, io, &ar)) return rc;
-    // in: wino_input_kernel reads each window's inner four columns as one 4-element vector (16 bytes of fp32, 8 of bf16)
+    // in: WinoInput reads each window's inner four columns as one 4-element vector (16 bytes of fp32, 8 of bf16)
     if (reinterpret_cast<uintptr_t>(in) & (ar.in_bf16 ? 7u : 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_winograd: in must be aligned to four elements");
     hipStream_t st = static_cast<hipStream_t>(stream);
