@@ -21,6 +21,9 @@ void profile_mark_stop(hipStream_t st, int region = 0, double work = 0.0, double
 // tuning switches (ipsr_debug_set_option in ipsr_hip.h): A/B aids, every key defaults to the shipped behaviour
 //   1  winograd.hip: transform kernels without the XCD remap of their block ids
 //   2  winograd.hip: the independent transforms of a convolution as two launches instead of one paired launch
+//   3  smallmap.hip: 1 = the small operands laid out in the workspace by pre-pass launches ("staged") in every call, 2 = gathered in
+//      the main kernels in every call (the default gathers except in the weight gradient above 32 positions)
+//   4  smallmap.hip: col2im by the looping kernel (one load per term, in turn) instead of the one that issues its loads up front
 int debug_option(int key);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -11,6 +11,16 @@
 // of an MFMA tile are free, so a lane's float4 of four consecutive q feeds four MFMAs whose tiles are q = q0 + 4m + j: every
 // weight byte is fetched by exactly one coalesced 16-byte load.  The streams are bandwidth bound (16.8 MB in ~5 us); the
 // reduction is cut over workgroups into slabs that the tiny post-pass (col2im / layout) adds in order (deterministic).
+//
+// The small operand (in, col(fine), coarse) is GATHERED by the main kernels from the NCHW tensor itself: its position (b, oy, ox)
+// or its (channel, tap) is a lane's own for the whole loop, the tensors are 64 KB - 1 MB and sit in L2, and a position >= P, a tap
+// outside the map or the padding row of Pp is a load the hardware drops (see "operands of the main kernels").  The pre-pass kernels
+// (sm_to_cn, sm_im2col_cn, sm_to_nc, sm_im2col_nt) that lay the same values out as images in the workspace remain — "staged": the
+// weight gradient above 32 positions (sm_staged), and everything under ipsr_debug_set_option(3, 1); the values fed to the
+// MFMAs are the same numbers in the same order either way, so the results are the same bits.  The plan and the workspace size do
+// not depend on the form: gathered calls leave the image slices of the workspace unused.
+// Each stream is software-pipelined over three register sets (sm_stream): two groups of loads are in flight beyond the one whose
+// MFMAs run.
 #include <algorithm>
 
 #include "ipsr_common.h"
@@ -94,6 +104,41 @@ __global__ void __launch_bounds__(256) sm_col2im_kernel(const float* __restrict_
     out[idx] = acc;
 }
 
+// The same sums in the same order with every load issued before the first add: all K x K taps x up to SL slabs of a thread are
+// independent buffer loads (a tap that reaches no position and a slab >= nslab are dropped by the descriptor's bounds check and add
+// +0.0f, which changes no bit), where the loop above waits an L2 round trip per term.
+template <int K, int SL>
+__global__ void __launch_bounds__(256) sm_col2im_wide_kernel(const float* __restrict__ M, int nslab, unsigned slab_bytes, unsigned m_bytes, int B, int C, int Hf, int Wf,
+                                                             int Ho, int Wo, int st, int pad, int dil, int Tp, float* __restrict__ out)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t total = (size_t)B * C * Hf * Wf;
+    if (idx >= total) return;
+    const int fx = (int)(idx % Wf), fy = (int)((idx / Wf) % Hf), c = (int)((idx / ((size_t)Wf * Hf)) % C), b = (int)(idx / ((size_t)Wf * Hf * C));
+    const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(M), 0, (int)m_bytes, 0x00020000);
+    float v[K * K][SL];
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int ny = fy + pad - r * dil, oy = ny / st;
+        const bool yok = ny >= 0 && ny % st == 0 && oy < Ho;
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const int nx = fx + pad - q * dil, ox = nx / st;
+            const bool ok = yok && nx >= 0 && nx % st == 0 && ox < Wo;
+            const unsigned off = (unsigned)((c * K * K + r * K + q) * Tp + (b * Ho + oy) * Wo + ox) * 4u;
+#pragma unroll
+            for (int sl = 0; sl < SL; ++sl)
+                v[r * K + q][sl] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mrs, (ok && sl < nslab) ? off + (unsigned)sl * slab_bytes : 0x80000000u, 0, 0));
+        }
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < K * K; ++t)
+#pragma unroll
+        for (int sl = 0; sl < SL; ++sl) acc += v[t][sl];
+    out[idx] = acc;
+}
+
 // out[b][r][o] = sum_{slabs} Y[slab][r][(b,o)]
 __global__ void __launch_bounds__(256) sm_sum_to_nchw_kernel(const float* __restrict__ Y, int nslab, size_t slab_stride, int B, int R, int HW, int Tp,
                                                              float* __restrict__ out)
@@ -130,18 +175,112 @@ __device__ __forceinline__ void sm_reduce4(f32x16 (&acc)[NB], float* lds, int wa
     __syncthreads();
 }
 
+// ---- operands of the main kernels ------------------------------------------------------------------------------------------------------
+// Every load of a main kernel goes through a buffer descriptor that covers exactly the tensor it reads (all operands are below 2 GiB:
+// launch_smallmap checks), with a 32-bit byte offset.  A load that is predicated off — a partly filled or empty group, a prefetch
+// past the wave's range, a position >= P, a tap outside the map — has bit 31 of its offset set (sm_off), which is past every
+// descriptor: the hardware drops it (no memory access) and the destination reads +0.0f, the value the pre-passes write for the
+// same element.  No load is under a branch, so the loads of a group sit in one basic block and the compiler's wait counts let group
+// g's MFMAs start while the groups after it are in flight.
+constexpr unsigned SM_OFF = 0x80000000u;
+__device__ __forceinline__ unsigned sm_off(unsigned off, unsigned on) { return off | (((on & 1u) - 1u) & SM_OFF); }     // on = 1: off, on = 0: dropped
+__device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t sm_rsrc(const float* p, unsigned bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float sm_ld(__amdgpu_buffer_rsrc_t rs, unsigned off) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0)); }
+__device__ __forceinline__ f32x4v sm_ld4(__amdgpu_buffer_rsrc_t rs, unsigned off)
+{
+    return __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+}
+
+// the convolution's geometry, for the kernels that gather from the NCHW tensors: coarse [B][R][Ho][Wo], fine [B][C][Hf][Wf]
+struct SmGeo { int P, R, C, Ho, Wo, Hf, Wf, k, st, pad, dil; };
+
+// One position p = (b, oy, ox) of the coarse grid as the taps see it: the byte offset of fine[b][0][oy*s - pad][ox*s - pad] (modulo
+// 2^32: the corner may lie outside the tensor, the taps that are loaded do not) and which kernel rows r / columns s fall inside the
+// map (bit r of ymask, bit s of xmask).  A position >= P has no row inside.
+struct SmPos {
+    unsigned base, ymask, xmask;
+    SmPos() = default;
+    __device__ __forceinline__ SmPos(const SmGeo& g, int p)
+    {
+        const int HW = g.Ho * g.Wo, b = p / HW, o = p - b * HW, oy = o / g.Wo, ox = o - oy * g.Wo;
+        const int iy0 = oy * g.st - g.pad, ix0 = ox * g.st - g.pad;
+        base = (unsigned)((b * g.C * g.Hf + iy0) * g.Wf + ix0) * 4u;
+        ymask = xmask = 0;
+        for (int t = 0; t < g.k; ++t) {
+            ymask |= (unsigned)(p < g.P && (unsigned)(iy0 + t * g.dil) < (unsigned)g.Hf) << t;
+            xmask |= (unsigned)((unsigned)(ix0 + t * g.dil) < (unsigned)g.Wf) << t;
+        }
+    }
+};
+
+// Byte offset of col(fine)[q][p] — tap t = q % K^2 = (r, s) of channel c = q / K^2 at position `pos` — dropped where the tap falls
+// outside the map (the zero sm_tap returns) or `on` is 0.
+template <int K>
+__device__ __forceinline__ unsigned sm_tap_off(const SmGeo& g, const SmPos& pos, unsigned q, unsigned on)
+{
+    const unsigned c = q / (K * K), t = q - c * (K * K), r = t / K, s = t - r * K;
+    return sm_off(pos.base + (c * g.Hf * g.Wf + r * g.dil * g.Wf + s * g.dil) * 4u, (pos.ymask >> r) & (pos.xmask >> s) & on);
+}
+
+// The software pipeline of the three streams.  A group is G loads of 16 weight bytes per lane with the small-operand values that go
+// with them; `load(set, g)` issues group g into a register set (a group past the wave's range loads nothing: every offset is
+// SM_OFF), `mma(set)` runs its MFMAs.  Three sets rotate, so two groups beyond the one being consumed are in flight: 3 * G * 16 =
+// 192 B per lane, 48 KiB per CU at one workgroup per CU, of weights alone.  The MFMAs run in group order, as a plain loop would.
+// The instruction scheduler may not move anything across SM_KEEP_ORDER: without it, it sinks each load to its first use to save
+// registers and the prefetch is gone.  Every set is either consumed unconditionally or carried round the loop, so that no load can be
+// sunk into a conditional block either.
+#define SM_KEEP_ORDER() __builtin_amdgcn_sched_barrier(0)
+
+template <class Set, class Load, class Mma>
+__device__ __forceinline__ void sm_stream(int ngroups, Load load, Mma mma)
+{
+    Set s0, s1, s2;
+    load(s0, 0);
+    load(s1, 1);
+    int g = 0;
+    if (ngroups >= 3) do {            // a bottom-tested loop: as a `for`, the sets were copied at the loop head, behind a wait for every load
+        load(s2, g + 2);
+        SM_KEEP_ORDER();
+        mma(s0);
+        SM_KEEP_ORDER();
+        load(s0, g + 3);
+        SM_KEEP_ORDER();
+        mma(s1);
+        SM_KEEP_ORDER();
+        load(s1, g + 4);
+        SM_KEEP_ORDER();
+        mma(s2);
+        SM_KEEP_ORDER();
+        g += 3;
+    } while (g + 3 <= ngroups);
+    if (g < ngroups) mma(s0);
+    if (g + 1 < ngroups) mma(s1);
+}
+
+// group depth: 4 as in the single-buffered loops these kernels had; 2 where four position blocks' accumulators and operands fill the registers
+template <int NB> struct SmDepth { static constexpr int G = NB == 4 ? 2 : 4; };
+
 // DATA: one workgroup (4 waves) = 128 columns q of Wm x the rows of its slab (a quarter per wave) x NB position blocks.
 //   A (MFMA j, lane (m, h)) = Wm[r + h][q0 + 4m + j]   — component j of the lane's float4 at Wm[r + h][q0 + 4m]
 //   B (lane (n, h))         = in[r + h][n0 + 32 nb + n]
 // slab s = blockIdx.y: Mcol_s[q0 + 4*row + j][n] for the 32x32 tile rows `row` of MFMA j.
+// in[r][n]: HW == 0: the [R][Tp] image sm_to_cn_kernel laid out at In;  HW > 0: In is the NCHW tensor, in[r][n] = In[(b*R + r)*HW + o]
+// for n = b*HW + o < P and zero for the padding columns — (b, o) is the lane's own for the whole loop, only r advances.
 template <int NB>
 __global__ void __launch_bounds__(256) sm_data_kernel(const float* __restrict__ Wm, const float* __restrict__ In, int R, int Q, int Tp, int rows_per_wave,
-                                                      float* __restrict__ Mcol)
+                                                      int P, int HW, float* __restrict__ Mcol)
 {
     __shared__ float red[3 * NB * 16 * 64];
+    constexpr int G = SmDepth<NB>::G;                      // row pairs per group
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 128, n0 = blockIdx.z * (32 * NB);
     const int ra = min(R, (blockIdx.y * 4 + wave) * rows_per_wave), rb = min(R, ra + rows_per_wave);
+    const __amdgpu_buffer_rsrc_t wrs = sm_rsrc(Wm, (unsigned)R * Q * 4u), irs = sm_rsrc(In, (unsigned)R * (HW ? P : Tp) * 4u);
     f32x16 acc[4][NB];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -149,28 +288,33 @@ __global__ void __launch_bounds__(256) sm_data_kernel(const float* __restrict__ 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[j][nb][e] = 0.0f;
-    const float* wp = Wm + (size_t)(ra + h) * Q + q0 + 4 * m;
-    const float* ip = In + (size_t)(ra + h) * Tp + n0 + m;
-    constexpr int U = NB == 1 ? 8 : (NB == 2 ? 4 : 2);     // row pairs in flight (8 KB of the weight stream per wave at NB = 1); bounded by the 4*NB accumulator tiles
-    for (int r = ra; r < rb; r += 2 * U) {
-        f32x4v a[U];
-        float bv[U][NB];
+    const unsigned wlane = (unsigned)(h * Q + q0 + 4 * m) * 4u, wrow = (unsigned)Q * 4u, irow = (unsigned)(HW ? HW : Tp) * 4u;
+    unsigned icol[NB];                                     // the lane's position in row 0 of `in`
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = r + 2 * u < rb;               // R and rows_per_wave are even: a pair is in or out as a whole
-            a[u] = ok ? *reinterpret_cast<const f32x4v*>(wp + (size_t)2 * u * Q) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int nb = 0; nb < NB; ++nb) {
+        const int n = n0 + 32 * nb + m;
+        icol[nb] = !HW ? (unsigned)n * 4u : (n < P ? (unsigned)((n / HW) * R * HW + n % HW) * 4u : SM_OFF);
+    }
+    struct Set { f32x4v a[G]; float bv[G][NB]; };
+    auto load = [&](Set& s, int grp) {
+        const int r = ra + grp * 2 * G;
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) bv[u][nb] = ok ? ip[(size_t)2 * u * Tp + 32 * nb] : 0.0f;
+        for (int u = 0; u < G; ++u) {
+            const unsigned ok = r + 2 * u < rb;           // R and rows_per_wave are even: a pair is in or out as a whole
+            s.a[u] = sm_ld4(wrs, sm_off(wlane + (unsigned)(r + 2 * u) * wrow, ok));
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) s.bv[u][nb] = sm_ld(irs, sm_off(icol[nb] + (unsigned)(r + 2 * u + h) * irow, ok) | (icol[nb] & SM_OFF));
         }
+    };
+    auto mma = [&](const Set& s) {
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < G; ++u)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[j][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][j], bv[u][nb], acc[j][nb], 0, 0, 0);
-        wp += (size_t)2 * U * Q;
-        ip += (size_t)2 * U * Tp;
-    }
+                for (int nb = 0; nb < NB; ++nb) acc[j][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(s.a[u][j], s.bv[u][nb], acc[j][nb], 0, 0, 0);
+    };
+    sm_stream<Set>(cdiv_dev(rb - ra, 2 * G), load, mma);
     float* out = Mcol + (size_t)blockIdx.y * Q * Tp;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -190,43 +334,53 @@ __global__ void __launch_bounds__(256) sm_data_kernel(const float* __restrict__ 
 // FWD: one workgroup (4 waves) = 32 rows r of Wm x the columns of its slab (a quarter per wave) x NB position blocks.
 //   A (MFMA j, lane (m, h)) = Wm[r0 + m][q + 4h + j]   — component j of the lane's float4 at Wm[r0 + m][q + 4h]
 //   B (MFMA j, lane (n, h)) = col[q + 4h + j][n0 + 32 nb + n]
-template <int NB>
-__global__ void __launch_bounds__(256) sm_fwd_kernel(const float* __restrict__ Wm, const float* __restrict__ Xc, int R, int Q, int Tp, int cols_per_wave,
-                                                     float* __restrict__ Y)
+// col[q][n]: K == 0: the [Q][Tp] image sm_im2col_cn_kernel laid out at X;  K > 0: X is the fine NCHW tensor and col[q][n] its tap
+// (sm_tap_off) — (b, oy, ox) is the lane's own for the whole loop, (c, tap) follows q.
+template <int NB, int K>
+__global__ void __launch_bounds__(256) sm_fwd_kernel(const float* __restrict__ Wm, const float* __restrict__ X, int R, int Q, int Tp, int cols_per_wave,
+                                                     SmGeo g, float* __restrict__ Y)
 {
     __shared__ float red[3 * NB * 16 * 64];
+    constexpr int G = SmDepth<NB>::G, KS = K ? K : 1;      // groups of 8 columns per pipeline group
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * 32, n0 = blockIdx.z * (32 * NB);
     const int qa = min(Q, (blockIdx.y * 4 + wave) * cols_per_wave), qb = min(Q, qa + cols_per_wave);
+    const __amdgpu_buffer_rsrc_t wrs = sm_rsrc(Wm, (unsigned)R * Q * 4u);
+    const __amdgpu_buffer_rsrc_t xrs = sm_rsrc(X, (K ? (unsigned)(g.P / (g.Ho * g.Wo)) * g.C * g.Hf * g.Wf : (unsigned)Q * Tp) * 4u);
     f32x16 acc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[nb][e] = 0.0f;
-    const float* wp = Wm + (size_t)(r0 + m) * Q + qa + 4 * h;
-    const float* xp = Xc + (size_t)(qa + 4 * h) * Tp + n0 + m;
-    constexpr int U = 4;                                  // groups of 8 columns in flight
-    for (int q = qa; q < qb; q += 8 * U) {
-        f32x4v a[U];
-        float bv[U][4][NB];
+    const unsigned wlane = (unsigned)((r0 + m) * Q + 4 * h) * 4u;
+    SmPos pos[NB];                                         // the lane's positions (unused by the staged form)
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = q + 8 * u < qb;               // Q and cols_per_wave are multiples of 8
-            a[u] = ok ? *reinterpret_cast<const f32x4v*>(wp + 8 * u) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int nb = 0; nb < NB; ++nb) pos[nb] = SmPos(g, n0 + 32 * nb + m);
+    struct Set { f32x4v a[G]; float bv[G][4][NB]; };
+    auto load = [&](Set& s, int grp) {
+        const int q = qa + grp * 8 * G;
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            const unsigned ok = q + 8 * u < qb;           // Q and cols_per_wave are multiples of 8
+            s.a[u] = sm_ld4(wrs, sm_off(wlane + (unsigned)(q + 8 * u) * 4u, ok));
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) bv[u][j][nb] = ok ? xp[(size_t)(8 * u + j) * Tp + 32 * nb] : 0.0f;
+                for (int nb = 0; nb < NB; ++nb) {
+                    const unsigned qq = (unsigned)(q + 8 * u + 4 * h + j);
+                    s.bv[u][j][nb] = sm_ld(xrs, K ? sm_tap_off<KS>(g, pos[nb], qq, ok) : sm_off((qq * Tp + n0 + 32 * nb + m) * 4u, ok));
+                }
         }
+    };
+    auto mma = [&](const Set& s) {
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < G; ++u)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][j], bv[u][j][nb], acc[nb], 0, 0, 0);
-        wp += 8 * U;
-        xp += (size_t)8 * U * Tp;
-    }
+                for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(s.a[u][j], s.bv[u][j][nb], acc[nb], 0, 0, 0);
+    };
+    sm_stream<Set>(cdiv_dev(qb - qa, 8 * G), load, mma);
     sm_reduce4<NB>(acc, red, wave, lane);
     if (wave == 0) {
         float* out = Y + (size_t)blockIdx.y * R * Tp;
@@ -243,39 +397,82 @@ __global__ void __launch_bounds__(256) sm_fwd_kernel(const float* __restrict__ W
 // WRW: one wave = the 32 x 128 block dW[r0 .. r0+31][q0 .. q0+127], reduction over all Pp (even, zero padded) positions.
 //   A (lane (m, h)) = Ct[p + h][r0 + m]                      coarse tensor as [p][r]
 //   B (MFMA j)      = component j of the float4 Vt[p + h][q0 + 4n]   im2col of the fine tensor as [p][(c,t)]  -> tile column n is q0 + 4n + j
-__global__ void __launch_bounds__(64) sm_wrw_kernel(const float* __restrict__ Ct, const float* __restrict__ Vt, int R, int Q, int Pp, float* __restrict__ dW)
+// K == 0: Ct / Vt are the images sm_to_nc_kernel / sm_im2col_nt_kernel laid out.  K > 0: they are the NCHW tensors: Ct[p][r] =
+// coarse[(b*R + r)*Ho*Wo + o], and the lane's four Vt values are four taps of position p.  q0 + 4n + j is the lane's own for the
+// whole loop: its (c, tap) is taken apart once, per component (for K = 3 four consecutive q cross a kernel row and a channel).  p
+// advances, and what a position contributes to an address — SmPos and its offset in `coarse` — is tabulated in LDS first (<= 1024
+// positions; entry Pp stands for every position past the end), so the loop adds and compares only.
+template <int K>
+__global__ void __launch_bounds__(64) sm_wrw_kernel(const float* __restrict__ Ct, const float* __restrict__ Vt, int R, int Q, int Pp, SmGeo g, float* __restrict__ dW)
 {
+    constexpr int G = 4, KS = K ? K : 1;                   // position pairs per group
+    __shared__ uint4 tab[K ? 1025 : 1];                    // (byte offset in coarse, SmPos) of every position
     const int lane = threadIdx.x, m = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 128, r0 = blockIdx.y * 32;
+    const int HW = g.Ho * g.Wo;
+    const __amdgpu_buffer_rsrc_t crs = sm_rsrc(Ct, (unsigned)(K ? g.P : Pp) * R * 4u);
+    const __amdgpu_buffer_rsrc_t vrs = sm_rsrc(Vt, (K ? (unsigned)(g.P / HW) * g.C * g.Hf * g.Wf : (unsigned)Pp * Q) * 4u);
     f32x16 acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.0f;
-    const float* cp = Ct + (size_t)h * R + r0 + m;
-    const float* vp = Vt + (size_t)h * Q + q0 + 4 * m;
-    constexpr int U = 4;
-    for (int p = 0; p < Pp; p += 2 * U) {
-        float av[U];
-        f32x4v b[U];
+    unsigned tr[4], ts[4], toff[4];                        // the lane's four (c, tap): kernel row, column, byte offset from a position's corner
+    const unsigned rlane = (unsigned)((r0 + m) * HW) * 4u;
+    if constexpr (K != 0) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const bool ok = p + 2 * u < Pp;
-            av[u] = ok ? cp[(size_t)2 * u * R] : 0.0f;
-            b[u] = ok ? *reinterpret_cast<const f32x4v*>(vp + (size_t)2 * u * Q) : f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = 0; j < 4; ++j) {
+            const unsigned q = q0 + 4 * m + j, c = q / (KS * KS), t = q - c * (KS * KS);
+            tr[j] = t / KS; ts[j] = t - tr[j] * KS; toff[j] = (c * g.Hf * g.Wf + tr[j] * g.dil * g.Wf + ts[j] * g.dil) * 4u;
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], b[u][j], acc[j], 0, 0, 0);
-        cp += (size_t)2 * U * R;
-        vp += (size_t)2 * U * Q;
+        for (int p = lane; p <= Pp; p += 64) {
+            const SmPos pos(g, p);
+            const int b = p / HW;
+            tab[p] = make_uint4(p < g.P ? (unsigned)(b * R * HW + p - b * HW) * 4u : SM_OFF, pos.base, pos.ymask, pos.xmask);
+        }
+        __syncthreads();
     }
+    struct Set { float av[G]; f32x4v b[G]; };
+    auto load = [&](Set& s, int grp) {
+        const int p = grp * 2 * G;
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            const int pp = p + 2 * u + h;
+            if constexpr (K == 0) {
+                const unsigned ok = p + 2 * u < Pp;
+                s.av[u] = sm_ld(crs, sm_off((unsigned)(pp * R + r0 + m) * 4u, ok));
+                s.b[u] = sm_ld4(vrs, sm_off((unsigned)(pp * Q + q0 + 4 * m) * 4u, ok));
+            } else {
+                const uint4 e = tab[min(pp, Pp)];          // the same for the 32 lanes of a half-wave
+                s.av[u] = sm_ld(crs, e.x + rlane);         // SM_OFF + rlane stays past the descriptor
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s.b[u][j] = sm_ld(vrs, sm_off(e.y + toff[j], (e.z >> tr[j]) & (e.w >> ts[j])));
+            }
+        }
+    };
+    auto mma = [&](const Set& s) {
+#pragma unroll
+        for (int u = 0; u < G; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(s.av[u], s.b[u][j], acc[j], 0, 0, 0);
+    };
+    sm_stream<Set>(cdiv_dev(Pp, 2 * G), load, mma);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
         *reinterpret_cast<f32x4v*>(dW + (size_t)(r0 + row) * Q + q0 + 4 * m) = f32x4v{acc[0][e], acc[1][e], acc[2][e], acc[3][e]};
     }
+}
+
+// Which form a call takes.  Gathering wins wherever it was measured on the forward / data passes (<= 32 positions in the training
+// step) and on the weight gradient up to 32 positions; from 128 positions up the weight gradient's four scalar tap loads per lane
+// and position pair cost more than its two pre-pass launches, and it stays staged (profiles/smallmap_stream_layers.txt).
+// Debug option 3 (A/B, the bit comparison of tests/test_gpu_smallmap_stream.py): 1 = staged everywhere, 2 = gathered everywhere.
+constexpr int SM_WRW_GATHER_MAX_POS = 32;
+static bool sm_staged(int op, int P)
+{
+    const int forced = debug_option(3);
+    return forced == 1 || (forced != 2 && op == 1 && P > SM_WRW_GATHER_MAX_POS);
 }
 
 struct SmPlan { int P, Tp, Pp, Q, nb, ngroups, nslab, per_slab; size_t a_floats, b_floats, m_floats, total_bytes; };
@@ -347,31 +544,65 @@ int launch_smallmap(int op, const float* a, const float* b2, float* out, int B, 
     float* A = cv.take<float>(p.a_floats);
     float* Bv = cv.take<float>(p.b_floats);
     float* Mo = cv.take<float>(p.m_floats);
+    // the main kernels address every operand by 32-bit byte offsets below SM_OFF
+    const size_t largest = 4 * std::max({(size_t)R * p.Q, (size_t)B * Cq * Hf * Wf, (size_t)R * p.Tp, (size_t)p.Q * p.Tp, (size_t)p.Pp * p.Q});
+    if (largest >= SM_OFF) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: an operand of %zu bytes (made for < 2 GiB)", largest);
+    const bool staged = sm_staged(op, p.P);
+    const SmGeo g = {p.P, R, Cq, Ho, Wo, Hf, Wf, k, st_, pad, dil};
     if (op == 0) {          // a = in, b2 = W
-        sm_to_cn_kernel<<<dim3(cdiv(p.Tp, 256), R), 256, 0, st>>>(a, B, R, Ho * Wo, p.Tp, Bv);
+        if (staged) sm_to_cn_kernel<<<dim3(cdiv(p.Tp, 256), R), 256, 0, st>>>(a, B, R, Ho * Wo, p.Tp, Bv);
+        const float* in = staged ? Bv : a;
+        const int HW = staged ? 0 : Ho * Wo;
         const dim3 grid(p.Q / 128, p.nslab, p.ngroups);
-        if (p.nb == 1) sm_data_kernel<1><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else sm_data_kernel<2><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
+        if (p.nb == 1) sm_data_kernel<1><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
+        else sm_data_kernel<2><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
         if (int rc = check_launch("sm_data_kernel")) return rc;
         const size_t total = (size_t)B * Cq * Hf * Wf;
-        sm_col2im_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Mo, p.nslab, (size_t)p.Q * p.Tp, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, out);
+        const unsigned cgrid = (unsigned)((total + 255) / 256);
+        const size_t slab_bytes = (size_t)p.Q * p.Tp * 4, m_bytes = slab_bytes * p.nslab;
+        const bool wide = !debug_option(4) && m_bytes < SM_OFF && (k == 3 || k == 4) && p.nslab <= 8;      // debug option 4 = the looping kernel
+        if (wide && k == 3) sm_col2im_wide_kernel<3, 8><<<cgrid, 256, 0, st>>>(Mo, p.nslab, (unsigned)slab_bytes, (unsigned)m_bytes, B, Cq, Hf, Wf, Ho, Wo, st_, pad, dil, p.Tp, out);
+        else if (wide && p.nslab <= 4) sm_col2im_wide_kernel<4, 4><<<cgrid, 256, 0, st>>>(Mo, p.nslab, (unsigned)slab_bytes, (unsigned)m_bytes, B, Cq, Hf, Wf, Ho, Wo, st_, pad, dil, p.Tp, out);
+        else if (wide) sm_col2im_wide_kernel<4, 8><<<cgrid, 256, 0, st>>>(Mo, p.nslab, (unsigned)slab_bytes, (unsigned)m_bytes, B, Cq, Hf, Wf, Ho, Wo, st_, pad, dil, p.Tp, out);
+        else sm_col2im_kernel<<<cgrid, 256, 0, st>>>(Mo, p.nslab, (size_t)p.Q * p.Tp, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, out);
         return check_launch("sm_col2im_kernel");
     }
+    const int K = staged ? 0 : k;                                  // the kernels' template argument: 0 = the staged images
     if (op == 2) {          // a = fine, b2 = W
-        sm_im2col_cn_kernel<<<dim3(cdiv(p.Tp, 256), p.Q), 256, 0, st>>>(a, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, Bv);
+        if (staged) sm_im2col_cn_kernel<<<dim3(cdiv(p.Tp, 256), p.Q), 256, 0, st>>>(a, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, Bv);
+        const float* x = staged ? Bv : a;
         const dim3 grid(R / 32, p.nslab, p.ngroups);
-        if (p.nb == 1) sm_fwd_kernel<1><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else if (p.nb == 2) sm_fwd_kernel<2><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
-        else sm_fwd_kernel<4><<<grid, 256, 0, st>>>(b2, Bv, R, p.Q, p.Tp, p.per_slab, Mo);
+#define SM_FWD_K(NB)                                                                                                                                   \
+    switch (K) {                                                                                                                                       \
+    case 0: sm_fwd_kernel<NB, 0><<<grid, 256, 0, st>>>(b2, x, R, p.Q, p.Tp, p.per_slab, g, Mo); break;                                                 \
+    case 1: sm_fwd_kernel<NB, 1><<<grid, 256, 0, st>>>(b2, x, R, p.Q, p.Tp, p.per_slab, g, Mo); break;                                                 \
+    case 2: sm_fwd_kernel<NB, 2><<<grid, 256, 0, st>>>(b2, x, R, p.Q, p.Tp, p.per_slab, g, Mo); break;                                                 \
+    case 3: sm_fwd_kernel<NB, 3><<<grid, 256, 0, st>>>(b2, x, R, p.Q, p.Tp, p.per_slab, g, Mo); break;                                                 \
+    default: sm_fwd_kernel<NB, 4><<<grid, 256, 0, st>>>(b2, x, R, p.Q, p.Tp, p.per_slab, g, Mo); break;                                                \
+    }
+        if (p.nb == 1) { SM_FWD_K(1) }
+        else if (p.nb == 2) { SM_FWD_K(2) }
+        else { SM_FWD_K(4) }
+#undef SM_FWD_K
         if (int rc = check_launch("sm_fwd_kernel")) return rc;
         const size_t total = (size_t)B * R * Ho * Wo;
         sm_sum_to_nchw_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Mo, p.nslab, (size_t)R * p.Tp, B, R, Ho * Wo, p.Tp, out);
         return check_launch("sm_sum_to_nchw_kernel");
     }
     // op 1: a = coarse, b2 = fine
-    sm_to_nc_kernel<<<dim3(cdiv(R, 256), p.Pp), 256, 0, st>>>(a, B, R, Ho * Wo, A);
-    sm_im2col_nt_kernel<<<dim3(cdiv(p.Q, 256), p.Pp), 256, 0, st>>>(b2, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, Bv);
-    sm_wrw_kernel<<<dim3(p.Q / 128, R / 32), 64, 0, st>>>(A, Bv, R, p.Q, p.Pp, out);
+    if (staged) {
+        sm_to_nc_kernel<<<dim3(cdiv(R, 256), p.Pp), 256, 0, st>>>(a, B, R, Ho * Wo, A);
+        sm_im2col_nt_kernel<<<dim3(cdiv(p.Q, 256), p.Pp), 256, 0, st>>>(b2, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, Bv);
+    }
+    const float *ct = staged ? A : a, *vt = staged ? Bv : b2;
+    const dim3 grid(p.Q / 128, R / 32);
+    switch (K) {
+    case 0: sm_wrw_kernel<0><<<grid, 64, 0, st>>>(ct, vt, R, p.Q, p.Pp, g, out); break;
+    case 1: sm_wrw_kernel<1><<<grid, 64, 0, st>>>(ct, vt, R, p.Q, p.Pp, g, out); break;
+    case 2: sm_wrw_kernel<2><<<grid, 64, 0, st>>>(ct, vt, R, p.Q, p.Pp, g, out); break;
+    case 3: sm_wrw_kernel<3><<<grid, 64, 0, st>>>(ct, vt, R, p.Q, p.Pp, g, out); break;
+    default: sm_wrw_kernel<4><<<grid, 64, 0, st>>>(ct, vt, R, p.Q, p.Pp, g, out); break;
+    }
     return check_launch("sm_wrw_kernel");
 }
 
