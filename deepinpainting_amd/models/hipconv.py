@@ -239,8 +239,8 @@ def _select(op, lay):
         # 64-row tile also the outermost 64 -> 64 @256x256 level (0.171 / 0.193 vs 0.230 / 0.261 ms, profiles/r03_hipconv_k3.txt)
         return "wino_dil"
     if mode == "auto" and _is_k4s1(k, stride, pad, dil) and op in (ops.CONV_FWD, ops.CONV_BWD_DATA) \
-            and cred % 16 == 0 and min(Cin, Cout) >= 128 and 16 <= H <= 128:
-        return "wino_dil"        # netD's 4x4 stride-1 convolution: the same F(3x3,4x4) pipeline on the image itself
+            and cred % 16 == 0 and min(Cin, Cout) >= 128 and 16 <= H <= 128 and W >= 4:
+        return "wino_dil"        # netD's 4x4 stride-1 convolution: the same F(3x3,4x4) pipeline on the image itself (which refuses extents below the kernel)
     if mode == "auto" and op == ops.CONV_FWD and Cout == 1 and Cin >= 64 and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil):
         return "one"             # netD's last layer (512 -> 1): a single pass over the input, 15 vs 80-143 us
     if mode == "auto" and _thin_wins(op, lay):
@@ -255,7 +255,8 @@ def _select(op, lay):
     # 64 -> 64 @256x256 (VGG conv1_2, forward and input gradient) 0.311 vs MIOpen's 0.378 ms
     if wino_ok and H * W >= 256 and min(cred, kout) >= 64 and (max(cred, kout) >= 128 or kout == 64):
         return "winograd"
-    if k == 4 and stride == 2 and dil == 2 and op == ops.CONV_BWD_DATA and Cin >= 128 and 16 <= H <= 128:
+    if k == 4 and stride == 2 and dil == 2 and op == ops.CONV_BWD_DATA and Cin >= 128 and 16 <= H <= 128 \
+            and ops.conv2d_supported(op, B, Cin, H, W, Cout, k, stride, pad, dil):
         return "direct"          # dilated 4x4 stride-2 input gradient: 8-12 % faster than MIOpen's f3x2_dilation2 + transposes
     return "miopen"
 
@@ -495,7 +496,7 @@ def _select_wrw(lay):
     if mode == "auto" and not transposed and _is_dilated4(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 32 <= H <= 128 \
             and H % 2 == 0 and W % 2 == 0:
         return "wino_dil"
-    if mode == "auto" and not transposed and _is_k4s1(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 16 <= H <= 128:
+    if mode == "auto" and not transposed and _is_k4s1(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 16 <= H <= 128 and W >= 4:
         return "wino_dil"
     if mode == "auto":
         g = _s2_geometry(lay)
