@@ -4,7 +4,10 @@ nn.ConvTranspose2d modules whose parameters, names and state_dict keys are untou
 
 One engine per (operation, geometry), chosen by `select()` / `select_wrw()` from measurements on MI355X at the step's shapes
 (tools/bench_hipconv.py -> profiles/r02_hipconv_*.txt).  The engines are the records of `_ENGINES` below — the call that runs each
-pass and what the engine needs; a new engine is one record there plus its rule in `_select` / `_select_wrw`:
+pass, the support query that says which layers the engine accepts (`takes`), and what the engine needs.  A new engine is one record
+there (its passes, its `takes`, its flags) plus its rule in `_select` / `_select_wrw`; a new direct split-bf16 opt-in is one row of
+`_DIRECT_OPT_INS`.  A rule asks the record before it answers, and a last guard in `_select_any` / `_select_wrw_any` turns any answer its
+engine does not take into "miopen": no rule, and no forced mode, can hand an engine a layer it raises on.
 
   "winograd"  csrc/winograd.hip   k3 s1 p1 forward / backward-data of Conv2d and ConvTranspose2d, F(4x4,3x3) on fp32 MFMA:
                                   2.0-2.4x MIOpen's F(2x2,3x3) assembly from 16x16 maps and 128 channels up
@@ -18,7 +21,7 @@ pass and what the engine needs; a new engine is one record there plus its rule i
   "thin_f2m"  csrc/thin_conv.hip  Conv2d 3 -> K, k4 s2 p1, forward under bf16 activations: the window gather on the bf16 matrix cores, one launch
   "thin_mfma" csrc/thin_conv.hip  weight gradient of the layers with 3 or 6 channels on the narrow side (k3 s1 p1, k4 s2 p1) under bf16
                                   activations: the pixel reduction on the bf16 matrix cores straight from NCHW, two launches
-  "smallmap"  csrc/winograd.hip   the innermost levels: the weight tensor streamed once, 16 bytes per lane straight into MFMA operands —
+  "smallmap"  csrc/smallmap.hip   the innermost levels: the weight tensor streamed once, 16 bytes per lane straight into MFMA operands —
                                   weight gradients of the 4x4 stride-2 layers up to 256 positions per batch (dW written in its native
                                   layout), forward and input gradient of the 3x3 / 4x4 layers up to 32 positions
   "direct"    csrc/conv_gemm.hip  one-launch implicit GEMM, NCHW in/out (every k3/k4, stride 1/2, dilated and transposed
@@ -48,7 +51,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import _lib, ops
 from .. import dist as ipsr_dist
 
 _FORCE = None          # test hook: overrides the environment
@@ -86,7 +89,7 @@ def set_direct_dilated(on):
 
 def direct_dilated():
     """Whether `set_direct_dilated` is on."""
-    return _DIRECT_DILATED
+    return "dil_data" in _direct_passes_on()
 
 
 _DIRECT_DILATED_DW = False # opt-in: the dilated 4x4 stride-2 weight gradient of "wino_dil" on the direct split-bf16 kernel (`set_direct_dilated_dw`)
@@ -95,8 +98,8 @@ _DIRECT_DILATED_DW = False # opt-in: the dilated 4x4 stride-2 weight gradient of
 def set_direct_dilated_dw(on):
     """Opt-in, default off, independent of `set_conv_math` and of `set_direct_dilated`: under fp32 activations, the weight gradient of the
     dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" has goes to the direct split-bf16 kernel ("bf16x3w",
-    ops.conv4x4s2_bf16x3_dil_wrw) on every shape it takes (`_bf16x3_dil_wrw_takes`).  The data passes, bf16 activations, forced engines,
-    the k4 s1 p1 layer and "smallmap" grids stay where they are."""
+    ops.conv4x4s2_bf16x3_dil_wrw) on every shape it takes (the "dil_wrw" row of `_DIRECT_OPT_INS`).  The data passes, bf16 activations,
+    forced engines, the k4 s1 p1 layer and "smallmap" grids stay where they are."""
     global _DIRECT_DILATED_DW
     _DIRECT_DILATED_DW = bool(on)
     _SEL.clear()
@@ -104,7 +107,18 @@ def set_direct_dilated_dw(on):
 
 def direct_dilated_dw():
     """Whether `set_direct_dilated_dw` is on."""
-    return _DIRECT_DILATED_DW
+    return "dil_wrw" in _direct_passes_on()
+
+
+def _direct_passes_on():
+    """-> the keys of `_DIRECT_OPT_INS` that are switched on: the passes the fp32 arithmetic name moves (ops.DIRECT_PASSES), "dil_data" under
+    `set_direct_dilated`, "dil_wrw" under `set_direct_dilated_dw`.  The one place the three kinds of switch are read."""
+    on = ops.DIRECT_PASSES.get(_MATH["fp32"], frozenset())
+    if _DIRECT_DILATED:
+        on = on | {"dil_data"}
+    if _DIRECT_DILATED_DW:
+        on = on | {"dil_wrw"}
+    return on
 
 
 def _amp_bf16():
@@ -152,25 +166,20 @@ def _select_any(op, lay, bf16):
     eng = _select(op, lay)
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if not bf16:
-        if eng == "winograd" and ops.direct_moves(_MATH["fp32"], "k3_data") and _mode() == "auto" and ops.conv3x3_bf16x3_supported(op, B, Cin, H, W, Cout):
-            return "bf16x3d"         # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
-        if ops.direct_moves(_MATH["fp32"], "s2_data") and _bf16x3_s2_wins(eng, op, lay):
-            return "bf16x3d"
-        if _DIRECT_DILATED and _bf16x3_dil_takes(eng, op, lay):
-            # opt-in: every shape the kernel takes, won or lost (profiles/direct_bf16x3_dil_layers.txt, batch 8, vs "wino_dil", forward / input
-            # gradient): 64 @256 wins 2.16x / 2.61x, 128 @128 wins 1.55x / 1.72x, 512 @32 wins 1.47x / 1.30x, 256 @64 LOSES 0.82x / 0.93x
-            return "bf16x3d"
-        return eng
-    if _bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies:
-        return eng
-    if _mode() == "auto" and _thin_wins(op, lay, True):
-        return "thin"            # the vector-ALU stream kernels read / write bf16 tensors themselves (ipsr_conv3x3_thin_io)
-    if _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and op == ops.CONV_FWD and Cin == 3 and (k, stride, pad, dil) == (4, 2, 1, 1) and H * W >= 4096 \
-            and ops.thin_f2m_mfma_supported(op, B, Cin, H, W, Cout, k, stride):
-        # the first Conv2d of netP / netD (3 -> 64, k4 s2): the window gather on the matrix cores, 0.041-0.045 vs MIOpen's 0.059 ms and one
-        # launch instead of four (profiles/r04_thin_bf16.txt; for the 3x3 thin layers the vector-ALU kernels and MIOpen stay ahead or level)
-        return "thin_f2m"
-    return _bf16_direct(op, lay)
+        eng = _direct_opt_in("data", eng, op, lay)
+    elif not (_bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies):
+        if _mode() == "auto" and _thin_wins(op, lay, True):
+            eng = "thin"         # the vector-ALU stream kernels read / write bf16 tensors themselves (ipsr_conv3x3_thin_io)
+        elif _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and op == ops.CONV_FWD and Cin == 3 and (k, stride, pad, dil) == (4, 2, 1, 1) and H * W >= 4096 \
+                and engine_takes("thin_f2m", "data", op, lay, True):
+            # the first Conv2d of netP / netD (3 -> 64, k4 s2): the window gather on the matrix cores, 0.041-0.045 vs MIOpen's 0.059 ms and one
+            # launch instead of four (profiles/r04_thin_bf16.txt; for the 3x3 thin layers the vector-ALU kernels and MIOpen stay ahead or level)
+            eng = "thin_f2m"
+        else:
+            eng = _bf16_direct(op, lay)
+    # the final guard: the rules and forced modes that probe nothing ("winograd", "wino_dil", IPSR_CONV_ENGINE=winograd) answer "miopen"
+    # where their engine refuses the layer, instead of raising in `conv_nobias` on a layer torch computes
+    return eng if engine_takes(eng, "data", op, lay, bf16) else "miopen"
 
 
 def _bf16_direct(op, lay):
@@ -181,12 +190,12 @@ def _bf16_direct(op, lay):
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if _env("IPSR_BF16_ENGINES", "") == "none" or _mode() in ("miopen", "winograd", "direct"):
         return "miopen"
-    if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 256 and ops.conv3x3_bf16_supported(op, B, Cin, H, W, Cout):
+    if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 256 and engine_takes("bf16d", "data", op, lay, True):
         return "bf16d"           # 16x16 maps too since the reduction is cut over workgroups there (0.041-0.063 vs 0.056-0.081 split-Winograd, 0.070-0.122 MIOpen)
     # (measured and not kept: the small-map engine on fp32 copies for the innermost levels beyond 32 positions per batch — 708 images/s at
     # 32, 706 at 64, 696 at 256, 658 at 1024: MIOpen's tiny bf16 convolutions cost 45-60 us per CALL but far less device time)
     g = _s2_geometry(lay)
-    if g is not None and ops.conv4x4s2_bf16_supported(_s2_mode(op), B, *g):
+    if g is not None and engine_takes("bf16d", "data", op, lay, True):
         # the 4x4 stride-2 family (profiles/r04_conv_bf16_layers.txt, batch 16): 1.3-2x MIOpen wherever the launch has enough tiles;
         # a 16x16 coarse grid gives one pixel tile per image (64 workgroups at 512 channels) and MIOpen ties or wins
         Kc, Cf, nh, nw = g
@@ -232,7 +241,7 @@ def _select(op, lay):
     if mode == "winograd":
         return "winograd" if wino_ok else "miopen"
     if mode == "direct":
-        return "direct" if ops.conv2d_supported(op, B, Cin, H, W, Cout, k, stride, pad, dil) else "miopen"
+        return "direct" if engine_takes("direct", "data", op, lay, False) else "miopen"
     if mode == "auto" and _is_dilated4(k, stride, pad, dil) and op in (ops.CONV_FWD, ops.CONV_BWD_DATA) \
             and cred % 16 == 0 and min(Cin, Cout) >= 64 and 32 <= H <= 256 and H % 2 == 0 and W % 2 == 0:
         # netG's dilated down convolution: F(3x3,4x4), 1.4-2.0x MIOpen (profiles/r02_hipconv_k3_v3.txt); since the GEMM has a
@@ -241,7 +250,7 @@ def _select(op, lay):
     if mode == "auto" and _is_k4s1(k, stride, pad, dil) and op in (ops.CONV_FWD, ops.CONV_BWD_DATA) \
             and cred % 16 == 0 and min(Cin, Cout) >= 128 and 16 <= H <= 128 and W >= 4:
         return "wino_dil"        # netD's 4x4 stride-1 convolution: the same F(3x3,4x4) pipeline on the image itself (which refuses extents below the kernel)
-    if mode == "auto" and op == ops.CONV_FWD and Cout == 1 and Cin >= 64 and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil):
+    if mode == "auto" and op == ops.CONV_FWD and Cout == 1 and Cin >= 64 and engine_takes("one", "data", op, lay, False):
         return "one"             # netD's last layer (512 -> 1): a single pass over the input, 15 vs 80-143 us
     if mode == "auto" and _thin_wins(op, lay):
         return "thin"            # 3/6-channel side at full resolution: one pass over the wide tensor on the vector ALUs
@@ -249,14 +258,14 @@ def _select(op, lay):
         return "smallmap"        # innermost levels (<= 32 positions per batch): the weight tensor streamed once into MFMA operands
     if mode == "auto":
         g = _s2_geometry(lay)
-        if g is not None and _s2_wins(g, _s2_mode(op), B) and ops.s2_winograd_supported(_s2_mode(op), B, *g):
+        if g is not None and _s2_wins(g, _s2_mode(op), B) and engine_takes("wino_s2", "data", op, lay, False):
             return "wino_s2"     # 4x4 stride-2 layers: polyphase Winograd F(5x5,2x2)
     # auto: measured rules (MI355X, batch 8; profiles/r03_hipconv_k3.txt).  64 produced channels run on the GEMM's 64-row tile:
     # 64 -> 64 @256x256 (VGG conv1_2, forward and input gradient) 0.311 vs MIOpen's 0.378 ms
     if wino_ok and H * W >= 256 and min(cred, kout) >= 64 and (max(cred, kout) >= 128 or kout == 64):
         return "winograd"
     if k == 4 and stride == 2 and dil == 2 and op == ops.CONV_BWD_DATA and Cin >= 128 and 16 <= H <= 128 \
-            and ops.conv2d_supported(op, B, Cin, H, W, Cout, k, stride, pad, dil):
+            and engine_takes("direct", "data", op, lay, False):
         return "direct"          # dilated 4x4 stride-2 input gradient: 8-12 % faster than MIOpen's f3x2_dilation2 + transposes
     return "miopen"
 
@@ -314,7 +323,7 @@ def _thin_wins(op, lay, bf16=False):
     if _env("IPSR_NO_THIN", "0") == "1":           # A/B switch
         return False
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
-    if not (k == 3 and stride == 1 and pad == 1 and dil == 1) or H * W < 4096 or not ops.thin_supported(op, Cin, H, W, Cout):
+    if not (k == 3 and stride == 1 and pad == 1 and dil == 1) or H * W < 4096 or not engine_takes("thin", "data", op, lay, bf16):
         return False
     fwd = op in (ops.CONV_FWD, ops.CONVT_FWD)
     i, o = (Cin, Cout) if fwd else (Cout, Cin)
@@ -335,7 +344,7 @@ def _smallmap_data_wins(op, lay):
     if _env("IPSR_NO_SMALLMAP", "0") == "1" or k not in (3, 4) or min(Cin, Cout) < 256:
         return False
     g = _smallmap_geometry(lay)
-    return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= int(_env("IPSR_SMALLMAP_MAX_POS", "32")) and ops.smallmap_supported(_smallmap_op(op), *g)
+    return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= int(_env("IPSR_SMALLMAP_MAX_POS", "32")) and engine_takes("smallmap", "data", op, lay, False)
 
 
 def _smallmap_wrw_wins(lay):
@@ -345,7 +354,7 @@ def _smallmap_wrw_wins(lay):
     if k != 4 or stride != 2 or _env("IPSR_NO_SMALLMAP", "0") == "1":        # the switch is for A/B timing
         return False
     g = _smallmap_geometry(lay)
-    return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= 256 and min(Cin, Cout) >= 256 and ops.smallmap_supported(ops.SM_WRW, *g)
+    return g[3] >= 1 and g[4] >= 1 and g[0] * g[3] * g[4] <= 256 and min(Cin, Cout) >= 256 and engine_takes("smallmap", "wrw", None, lay, False)
 
 
 def _is_k4s1(k, stride, pad, dil):
@@ -366,26 +375,17 @@ def _select_wrw_any(lay, bf16):
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     eng = _select_wrw(lay)
     thin = _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and pad == 1 and dil == 1 and (k, stride) in ((3, 1), (4, 2)) and H * W >= 4096 \
-        and ops.thin_wrw_mfma_supported(transposed, B, Cin, H, W, Cout, k, stride)
+        and engine_takes("thin_mfma", "wrw", None, lay, bf16)
     if not bf16:
         # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
-        if thin and eng == "miopen":
-            return "thin_mfma"
-        if ops.direct_moves(_MATH["fp32"], "k3_wrw") and _bf16x3_wrw_wins(eng, lay):
-            return "bf16x3w"
-        if ops.direct_moves(_MATH["fp32"], "s2_wrw") and _bf16x3_s2_wrw_wins(eng, lay):
-            return "bf16x3w"
-        if _DIRECT_DILATED_DW and _bf16x3_dil_wrw_takes(eng, lay):
-            return "bf16x3w"
-        return eng
-    if _bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies:
-        return eng
-    if thin:
+        eng = "thin_mfma" if thin and eng == "miopen" else _direct_opt_in("wrw", eng, None, lay)
+    elif not (_bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies):
         # 3 / 6 channels on the narrow side: the pixel reduction on the bf16 matrix cores straight from NCHW (profiles/r04_thin_bf16.txt, batch 16:
         # 3 -> 64 k4 s2 0.033 vs MIOpen's 0.057 ms, ConvT 128 -> 3 k3 0.152 vs 0.202, k4 s2 0.052 vs 0.063, 6 -> 64 0.118 vs 0.125 — and 2
         # launches instead of MIOpen's 5-6)
-        return "thin_mfma"
-    return _bf16_direct_wrw(lay)
+        eng = "thin_mfma" if thin else _bf16_direct_wrw(lay)
+    # the final guard, as in `_select_any`: "winograd", "wino_dil" and "wino_s2" weight gradients are answered without a probe
+    return eng if engine_takes(eng, "wrw", None, lay, bf16) else "miopen"
 
 
 def _bf16_direct_wrw(lay):
@@ -394,27 +394,12 @@ def _bf16_direct_wrw(lay):
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     if _env("IPSR_BF16_ENGINES", "") == "none" or _mode() in ("miopen", "winograd", "direct"):
         return "miopen"
-    if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and ops.conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):
+    if k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and engine_takes("bf16d", "wrw", None, lay, True):
         return "bf16d"
     g = _s2_geometry(lay)
-    if g is not None and g[3] >= 32 and ((g[0] + 127) // 128) * ((g[1] + 31) // 32) >= 4 and ops.conv4x4s2_bf16_wrw_supported(B, *g):
+    if g is not None and g[3] >= 32 and ((g[0] + 127) // 128) * ((g[1] + 31) // 32) >= 4 and engine_takes("bf16d", "wrw", None, lay, True):
         return "bf16d"           # 1.2-1.4x MIOpen from four 128 x 32 output tiles up on coarse grids >= 32 wide; 16-wide grids and single tiles lose
     return "miopen"
-
-
-def _bf16x3_s2_wins(eng, op, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct
-    split-bf16 kernel (ops.conv4x4s2_bf16x3) where it takes the shape.  Measured at batch 8 on every such row of the step
-    (profiles/direct_bf16x3_s2_layers.txt): 1.23-2.51x "wino_s2" (0.037-0.106 vs 0.079-0.197 ms), every row's slowest round of the kernel faster than
-    the fastest of "wino_s2", no row loses — so the rule is every "wino_s2" data pass the kernel takes; other batches and channel counts inside it were not measured.
-    Of MIOpen's k4 s2 p1 rows the kernel takes one in the step, netG's outermost ConvTranspose2d 64 -> 64 @128 input gradient (0.072 vs
-    0.197 ms, 2.72x): that shape moves too, at any batch though only batch 8 was measured; nothing else of MIOpen's does.  A forced engine is never overridden."""
-    if eng not in ("wino_s2", "miopen") or _mode() != "auto":
-        return False
-    g = _s2_geometry(lay)
-    if g is None or (eng == "miopen" and not (_s2_mode(op) == ops.S2_FINE_TO_COARSE and g == (64, 64, 128, 128))):
-        return False
-    return ops.conv4x4s2_bf16x3_supported(_s2_mode(op), lay[1], *g)
 
 
 def _dil_geometry(lay):
@@ -429,69 +414,75 @@ def _dil_mode(op):
     return ops.S2_DILATED | (ops.S2_FINE_TO_COARSE if op == ops.CONV_FWD else ops.S2_COARSE_TO_FINE)
 
 
-def _bf16x3_dil_takes(eng, op, lay):
-    """fp32 activations under `set_direct_dilated(True)`: the forward / input-gradient passes of the dilated down convolution that "wino_dil"
-    has go to the direct split-bf16 kernel wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.
-    Measured at batch 8 on the step's four shapes (profiles/direct_bf16x3_dil_layers.txt): 1.30-2.61x "wino_dil" on 64 @256, 128 @128 and
-    512 @32, 0.82x / 0.93x (a loss) on 256 @64; the switch moves all four, the step gains 1.5 %.  A forced engine is never overridden; netD's k4 s1 p1 and the weight gradient stay on "wino_dil"."""
-    if eng != "wino_dil" or _mode() != "auto" or op not in (ops.CONV_FWD, ops.CONV_BWD_DATA):
-        return False
-    g = _dil_geometry(lay)
-    return g is not None and ops.conv4x4s2_bf16x3_supported(_dil_mode(op), lay[1], *g)
-
-
 # MIOpen's one dilated weight gradient of the step, netG's outermost 64 -> 64 @256x256 (coarse grid 128 wide), as (Kc, Cf, nh, nw)
 _DIL_WRW_MIOPEN_ROW = (64, 64, 128, 128)
 
 
-def _bf16x3_dil_wrw_takes(eng, lay):
-    """fp32 activations under `set_direct_dilated_dw(True)`: the weight gradients of the dilated down convolution that "wino_dil" has go to
-    the direct split-bf16 kernel (ops.conv4x4s2_bf16x3_dil_wrw) wherever it takes the shape (coarse grids 16 .. 128 wide) — every such
-    shape, won or lost.  Measured at batch 8 on the step's shapes (profiles/direct_bf16x3_dil_wrw_layers.txt): 1.84x "wino_dil" on 128 @128
-    (0.079 vs 0.146 ms), 1.30x on 256 @64, 1.13x on 512 @32, the ranges apart in every row.  Of MIOpen's rows exactly one moves, at any batch
-    though only batch 8 was measured: 64 -> 64 @256x256, where the kernel's slowest round (0.1412 ms) is faster than MIOpen's fastest
-    (0.2164 ms), 1.68x on the medians.  The step gains 0.8-1.0 %.  A forced engine is never overridden; netD's k4 s1 p1, "smallmap" grids and
-    bf16 activations stay where they are."""
-    if eng not in ("wino_dil", "miopen") or _mode() != "auto":
-        return False
-    g = _dil_geometry(lay)
-    if g is None or (eng == "miopen" and g != _DIL_WRW_MIOPEN_ROW):
-        return False
-    return ops.conv4x4s2_bf16x3_dil_wrw_supported(lay[1], *g)
+# ---- the direct split-bf16 opt-ins for fp32 activations: one row per pass a switch moves to "bf16x3d" / "bf16x3w" ---------------------------
+# key:      what switches the row on (`_direct_passes_on`): a pass name of ops.DIRECT_PASSES, or "dil_data" / "dil_wrw" for the two booleans
+# replaces: the base answers (`_select` / `_select_wrw`) the row may replace;  when(base, op, lay): what else must hold (op None for "wrw")
+# `_direct_opt_in` adds what every row shares: mode "auto" only (a forced engine is never overridden), and the engine must take the layer.
+_DirectOptIn = namedtuple("_DirectOptIn", "key kind engine replaces when")
+_DIRECT_OPT_INS = (
+    # the k3 s1 p1 forward / input gradient of "winograd": every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
+    _DirectOptIn("k3_data", "data", "bf16x3d", ("winograd",), lambda base, op, lay: True),
+    # "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct split-bf16
+    # kernel (ops.conv4x4s2_bf16x3) where it takes the shape.  Measured at batch 8 on every such row of the step
+    # (profiles/direct_bf16x3_s2_layers.txt): 1.23-2.51x "wino_s2" (0.037-0.106 vs 0.079-0.197 ms), every row's slowest round of the kernel
+    # faster than the fastest of "wino_s2", no row loses — so the rule is every "wino_s2" data pass the kernel takes; other batches and
+    # channel counts inside it were not measured.  Of MIOpen's k4 s2 p1 rows the kernel takes one in the step, netG's outermost
+    # ConvTranspose2d 64 -> 64 @128 input gradient (0.072 vs 0.197 ms, 2.72x): that shape moves too, at any batch though only batch 8 was
+    # measured; nothing else of MIOpen's does.
+    _DirectOptIn("s2_data", "data", "bf16x3d", ("wino_s2", "miopen"), lambda base, op, lay: _s2_geometry(lay) is not None and (
+        base != "miopen" or (_s2_mode(op) == ops.S2_FINE_TO_COARSE and _s2_geometry(lay) == (64, 64, 128, 128)))),
+    # `set_direct_dilated(True)`: the forward / input-gradient passes of the dilated down convolution that "wino_dil" has go to the direct
+    # split-bf16 kernel wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.  Measured at batch 8 on the
+    # step's four shapes (profiles/direct_bf16x3_dil_layers.txt, vs "wino_dil", forward / input gradient): 64 @256 wins 2.16x / 2.61x,
+    # 128 @128 wins 1.55x / 1.72x, 512 @32 wins 1.47x / 1.30x, 256 @64 LOSES 0.82x / 0.93x; the switch moves all four, the step gains 1.5 %.
+    # netD's k4 s1 p1 and the weight gradient stay on "wino_dil".
+    _DirectOptIn("dil_data", "data", "bf16x3d", ("wino_dil",),
+                 lambda base, op, lay: op in (ops.CONV_FWD, ops.CONV_BWD_DATA) and _dil_geometry(lay) is not None),
+    # "direct_bf16x3_dw" / "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to
+    # the direct split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured
+    # at batch 8 (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient
+    # on 256 -> 256 / 512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer
+    # multiplications and its transforms are small there), so maps below 64x64 with >= 512 channels on both sides stay where they are.
+    _DirectOptIn("k3_wrw", "wrw", "bf16x3w", ("winograd", "miopen"), lambda base, op, lay: lay[6:] == (3, 1, 1, 1) and lay[3] * lay[4] >= 1024
+                 and not (lay[3] * lay[4] < 4096 and min(lay[2], lay[5]) >= 512)),
+    # "direct_bf16x3_s2_dw": the k4 s2 p1 weight gradients that "wino_s2" has go to the direct split-bf16 kernel (ops.conv4x4s2_bf16x3_wrw)
+    # where it takes the shape (coarse grids 16, 32 or 64 wide).  Measured at batch 8 on every such row of the step
+    # (profiles/direct_bf16x3_s2_wrw_layers.txt): 1.21-1.87x "wino_s2" (0.050-0.091 vs 0.079-0.145 ms), every row's slowest round of the
+    # kernel faster than the fastest of "wino_s2" (the closest: Conv2d 64 -> 128 on a 64-wide coarse grid, 0.0823 vs 0.0947), no row loses —
+    # so the rule is every "wino_s2" weight gradient the kernel takes; other batches and the channel counts / grids `_s2_wins` admits beyond
+    # the step's were not measured.  MIOpen's rows ("thin_mfma"'s 3-channel ends, netG's outermost 64 -> 64 on a 128-wide coarse grid, which
+    # the kernel refuses), "smallmap", "one", the dilated family and grids below 16 wide stay where they are.
+    _DirectOptIn("s2_wrw", "wrw", "bf16x3w", ("wino_s2",), lambda base, op, lay: _s2_geometry(lay) is not None),
+    # `set_direct_dilated_dw(True)`: the weight gradients of the dilated down convolution that "wino_dil" has go to the direct split-bf16
+    # kernel (ops.conv4x4s2_bf16x3_dil_wrw) wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.
+    # Measured at batch 8 on the step's shapes (profiles/direct_bf16x3_dil_wrw_layers.txt): 1.84x "wino_dil" on 128 @128 (0.079 vs
+    # 0.146 ms), 1.30x on 256 @64, 1.13x on 512 @32, the ranges apart in every row.  Of MIOpen's rows exactly one moves, at any batch though
+    # only batch 8 was measured: 64 -> 64 @256x256, where the kernel's slowest round (0.1412 ms) is faster than MIOpen's fastest
+    # (0.2164 ms), 1.68x on the medians.  The step gains 0.8-1.0 %.  netD's k4 s1 p1, "smallmap" grids and bf16 activations stay where they are.
+    _DirectOptIn("dil_wrw", "wrw", "bf16x3w", ("wino_dil", "miopen"), lambda base, op, lay: _dil_geometry(lay) is not None and (
+        base != "miopen" or _dil_geometry(lay) == _DIL_WRW_MIOPEN_ROW)),
+)
 
 
-def _bf16x3_wrw_wins(eng, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_dw" / "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to the direct
-    split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured at batch 8
-    (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient on 256 -> 256 /
-    512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer multiplications and its
-    transforms are small there), so maps below 64x64 with >= 512 channels on both sides stay where they are."""
-    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
-    if eng not in ("winograd", "miopen") or _mode() != "auto":
-        return False
-    if H * W < 4096 and min(Cin, Cout) >= 512:
-        return False
-    return k == 3 and stride == 1 and pad == 1 and dil == 1 and H * W >= 1024 and ops.conv3x3_bf16x3_wrw_supported(transposed, B, Cin, H, W, Cout)
-
-
-def _bf16x3_s2_wrw_wins(eng, lay):
-    """fp32 activations under the opt-in "direct_bf16x3_s2_dw": the k4 s2 p1 weight gradients that "wino_s2" has go to the direct split-bf16
-    kernel (ops.conv4x4s2_bf16x3_wrw) where it takes the shape (coarse grids 16, 32 or 64 wide).  Measured at batch 8 on every such row of the step
-    (profiles/direct_bf16x3_s2_wrw_layers.txt): 1.21-1.87x "wino_s2" (0.050-0.091 vs 0.079-0.145 ms), every row's slowest round of the kernel
-    faster than the fastest of "wino_s2" (the closest: Conv2d 64 -> 128 on a 64-wide coarse grid, 0.0823 vs 0.0947), no row loses — so the rule is
-    every "wino_s2" weight gradient the kernel takes; other batches and the channel counts / grids `_s2_wins` admits beyond the step's were not measured.
-    A forced engine is never overridden; MIOpen's rows ("thin_mfma"'s 3-channel ends, netG's outermost 64 -> 64 on a 128-wide coarse grid,
-    which the kernel refuses), "smallmap", "one", the dilated family and grids below 16 wide stay where they are."""
-    if eng != "wino_s2" or _mode() != "auto":
-        return False
-    g = _s2_geometry(lay)
-    return g is not None and ops.conv4x4s2_bf16x3_wrw_supported(lay[1], *g)
+def _direct_opt_in(kind, base, op, lay):
+    """fp32 activations: -> the engine of the first row of `_DIRECT_OPT_INS` that moves this pass off its base answer, else `base`."""
+    if _mode() != "auto":
+        return base
+    on = _direct_passes_on()
+    for row in _DIRECT_OPT_INS:
+        if row.kind == kind and row.key in on and base in row.replaces and row.when(base, op, lay) and engine_takes(row.engine, kind, op, lay, False):
+            return row.engine
+    return base
 
 
 def _select_wrw(lay):
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     mode = _mode()
-    if mode == "auto" and not transposed and Cout == 1 and Cin >= 64 and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil):
+    if mode == "auto" and not transposed and Cout == 1 and Cin >= 64 and engine_takes("one", "wrw", None, lay, False):
         return "one"
     if mode == "auto" and not transposed and _is_dilated4(k, stride, pad, dil) and min(Cin, Cout) >= 128 and 32 <= H <= 128 \
             and H % 2 == 0 and W % 2 == 0:
@@ -520,14 +511,24 @@ def _select_wrw(lay):
 # data:  (op, inp, w, lay, math, out_dtype, param) -> y / dx: forward (inp = x) and input gradient (inp = dy) share the call
 # wrw:   (x, dy, lay, math, sink) -> dW (fp32, the module's layout); None: the engine has no such pass
 #        ("miopen" has neither: it runs through _miopen_forward / _miopen_backward).  lay[1:5] = (B, Cin, H, W), lay[5] = Cout, lay[6:] = (k, stride, pad, dil)
-# bf16_io:     reads / writes bf16 activation tensors in competition with MIOpen's bf16 kernels: the engines `_bf16_wins` rules on (the thin
+# takes: (kind, op, lay, bf16) -> whether the engine accepts this pass of this layer: kind "data" (op = the ops.* code of the forward / input-
+#        gradient pass) or "wrw" (op ignored); bf16 = the activations are bf16.  The support query of the entry point the `data` / `wrw` call
+#        reaches, with the arguments that call builds; False for a pass the engine has not, or a geometry its call cannot express.  Ask
+#        through `engine_takes`.  (tests/dispatch_envelope.py restates the mapping on its own.)
+# bf16_io:    reads / writes bf16 activation tensors in competition with MIOpen's bf16 kernels: the engines `_bf16_wins` rules on (the thin
 #              engines read bf16 too, by rules of their own in `_select_any` / `_select_wrw_any`)
 # fp32_copies: an fp32 engine whose operands are small next to its weight stream / single pass (the innermost levels, netD's one-channel
 #              head): under bf16 activations it runs on fp32 copies of the activations (a cast of a few hundred KB) instead of falling
 #              back to MIOpen's transposes + 40-160 us kernels
 # sink:        data parallel: may write the weight gradient straight into its slice of the armed gradient bucket (dist.py)
 # wrw_x_as_dy: a weight gradient that reads both operands in one dtype: x is cast to dy's
-_Engine = namedtuple("_Engine", "data wrw bf16_io fp32_copies sink wrw_x_as_dy", defaults=(None, None, False, False, False, False))
+_Engine = namedtuple("_Engine", "data wrw takes bf16_io fp32_copies sink wrw_x_as_dy", defaults=(None, None, None, False, False, False, False))
+_K3 = (3, 1, 1, 1)         # (k, stride, pad, dil)
+
+
+def engine_takes(eng, kind, op, lay, bf16):
+    """Whether the engine accepts one pass of one layer (`_Engine.takes`); "miopen" takes everything."""
+    return eng == "miopen" or bool(_ENGINES[eng].takes(kind, op, lay, bf16))
 
 
 def _frozen_pack(w, param):
@@ -543,36 +544,77 @@ def _fine_coarse(x, dy, lay):
     return ((dy, x) if lay[0] else (x, dy)) + (lay[1],) + _s2_geometry(lay)
 
 
+def _direct_case(lay, x3):
+    """-> (case, g): which entry point of csrc/conv_bf16.hip a layer reaches on the direct bf16 (x3 False) / split-bf16 (x3 True) engines —
+    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, split-bf16 only, g = `_dil_geometry`) — or
+    (None, None) where their calls cannot express the layer.  The run calls and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" all branch on it."""
+    if lay[6:] == _K3:
+        return "k3", None
+    dilated = x3 and _is_dilated4(*lay[6:])
+    g = _dil_geometry(lay) if dilated else _s2_geometry(lay)
+    return (None if g is None else "dil" if dilated else "s2"), g
+
+
+def _direct_mode(case, op):
+    return _dil_mode(op) if case == "dil" else _s2_mode(op)
+
+
 def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
     """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form."""
     if inp.dtype != torch.bfloat16:
         inp = inp.to(torch.bfloat16)
-    if lay[6] == 3:
+    case, g = _direct_case(lay, False)
+    if case == "k3":
         return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, **_frozen_pack(w, param))
-    return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), out_dtype=out_dtype)
-
-
-def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
-    """fp32 activations on the direct split-bf16 kernels: the same two shapes, and the dilated down convolution."""
-    if lay[6] == 3:
-        return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], **_frozen_pack(w, param))
-    if _is_dilated4(*lay[6:]):
-        return ops.conv4x4s2_bf16x3(_dil_mode(op), inp, w, lay[1], *_dil_geometry(lay))
-    return ops.conv4x4s2_bf16x3(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay))
+    return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *g, out_dtype=out_dtype)
 
 
 def _bf16d_wrw(x, dy, lay, math, sink):
-    if lay[6] == 3:
+    if _direct_case(lay, False)[0] == "k3":
         return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
     return ops.conv4x4s2_bf16_wrw(*_fine_coarse(x, dy, lay), out=sink)
 
 
+def _bf16d_takes(kind, op, lay, bf16):
+    case, g = _direct_case(lay, False)
+    if not bf16 or case is None:             # reads bf16 activations
+        return False
+    if case == "k3":
+        return ops.conv3x3_bf16_supported(op, *lay[1:6]) if kind == "data" else ops.conv3x3_bf16_wrw_supported(*lay[:6])
+    return ops.conv4x4s2_bf16_supported(_s2_mode(op), lay[1], *g) if kind == "data" else ops.conv4x4s2_bf16_wrw_supported(lay[1], *g)
+
+
+def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
+    """fp32 activations on the direct split-bf16 kernels: the same two shapes, and the dilated down convolution."""
+    case, g = _direct_case(lay, True)
+    if case == "k3":
+        return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], **_frozen_pack(w, param))
+    return ops.conv4x4s2_bf16x3(_direct_mode(case, op), inp, w, lay[1], *g)
+
+
+def _bf16x3d_takes(kind, op, lay, bf16):
+    case, g = _direct_case(lay, True)
+    if kind != "data" or bf16 or case is None:       # reads fp32 activations
+        return False
+    return ops.conv3x3_bf16x3_supported(op, *lay[1:6]) if case == "k3" else ops.conv4x4s2_bf16x3_supported(_direct_mode(case, op), lay[1], *g)
+
+
 def _bf16x3w_wrw(x, dy, lay, math, sink):
-    if lay[6] == 3:
+    case, g = _direct_case(lay, True)
+    if case == "k3":
         return ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink)
-    if _is_dilated4(*lay[6:]):
-        return ops.conv4x4s2_bf16x3_dil_wrw(x, dy, lay[1], *_dil_geometry(lay), out=sink)      # Conv2d only: (fine, coarse) = (x, dy)
+    if case == "dil":
+        return ops.conv4x4s2_bf16x3_dil_wrw(x, dy, lay[1], *g, out=sink)      # Conv2d only: (fine, coarse) = (x, dy)
     return ops.conv4x4s2_bf16x3_wrw(*_fine_coarse(x, dy, lay), out=sink)
+
+
+def _bf16x3w_takes(kind, op, lay, bf16):
+    case, g = _direct_case(lay, True)
+    if kind != "wrw" or bf16 or case is None:
+        return False
+    if case == "k3":
+        return ops.conv3x3_bf16x3_wrw_supported(*lay[:6])
+    return (ops.conv4x4s2_bf16x3_dil_wrw_supported if case == "dil" else ops.conv4x4s2_bf16x3_wrw_supported)(lay[1], *g)
 
 
 def _thin_mfma_wrw(x, dy, lay, math, sink):
@@ -581,35 +623,69 @@ def _thin_mfma_wrw(x, dy, lay, math, sink):
     return ops.conv_thin_wrw_mfma(lay[0], x, dy, lay[6], lay[7], out=sink)
 
 
+def _winograd_takes(kind, op, lay, bf16):
+    if lay[6:] != _K3:
+        return False
+    if kind == "data":
+        return ops.winograd_supported(op, *lay[1:6])
+    return _lib.lib().ipsr_conv3x3_winograd_wrw_workspace_bytes(int(lay[0]), *lay[1:6]) > 0      # (ops has no *_supported for it)
+
+
+def _wino_dil_mode(kind, op):
+    """Mode of ops.conv4x4_dilated_winograd: 0 forward, 1 input gradient, 2 weight gradient."""
+    return 2 if kind == "wrw" else int(op != ops.CONV_FWD)
+
+
+def _wino_dil_takes(kind, op, lay, bf16):
+    g = ops.conv4x4_geometry(*lay[6:])
+    return g is not None and not lay[0] and ops.dilated_winograd_supported(_wino_dil_mode(kind, op), *lay[1:6], geom=g)
+
+
+def _wino_s2_takes(kind, op, lay, bf16):
+    g = _s2_geometry(lay)
+    return g is not None and ops.s2_winograd_supported(_s2_mode(op) if kind == "data" else ops.S2_WEIGHT_GRAD, lay[1], *g)
+
+
 _ENGINES = {
     "winograd": _Engine(
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_winograd(op, inp, w, lay[1:5], lay[5], math=math, out_dtype=out_dtype),
         lambda x, dy, lay, math, sink: ops.conv3x3_winograd_wrw(lay[0], x, dy, lay[5], out=sink, math=math),
-        bf16_io=True, sink=True, wrw_x_as_dy=True),
-    "wino_dil": _Engine(         # mode 0 forward, 1 input gradient, 2 weight gradient
+        _winograd_takes, bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "wino_dil": _Engine(
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv4x4_dilated_winograd(
-            int(op != ops.CONV_FWD), inp, w, lay[1:5], lay[5], geom=ops.conv4x4_geometry(*lay[6:]), math=math, out_dtype=out_dtype),
-        lambda x, dy, lay, math, sink: ops.conv4x4_dilated_winograd(2, x, dy, lay[1:5], lay[5], out=sink, geom=ops.conv4x4_geometry(*lay[6:]), math=math),
-        bf16_io=True, sink=True, wrw_x_as_dy=True),
+            _wino_dil_mode("data", op), inp, w, lay[1:5], lay[5], geom=ops.conv4x4_geometry(*lay[6:]), math=math, out_dtype=out_dtype),
+        lambda x, dy, lay, math, sink: ops.conv4x4_dilated_winograd(
+            _wino_dil_mode("wrw", None), x, dy, lay[1:5], lay[5], out=sink, geom=ops.conv4x4_geometry(*lay[6:]), math=math),
+        _wino_dil_takes, bf16_io=True, sink=True, wrw_x_as_dy=True),
     "wino_s2": _Engine(          # the weight gradient takes (fine, coarse)
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv4x4s2_winograd(_s2_mode(op), inp, w, lay[1], *_s2_geometry(lay), math=math, out_dtype=out_dtype),
         lambda x, dy, lay, math, sink: ops.conv4x4s2_winograd(ops.S2_WEIGHT_GRAD, *_fine_coarse(x, dy, lay), out=sink, math=math),
-        bf16_io=True, sink=True, wrw_x_as_dy=True),
-    "thin": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_thin(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype)),
-    "thin_f2m": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv_thin_f2m_mfma(op, inp, w, lay[1:5], lay[5], lay[6], lay[7], out_dtype=out_dtype)),
-    "thin_mfma": _Engine(None, _thin_mfma_wrw, sink=True),
+        _wino_s2_takes, bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "thin": _Engine(
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv3x3_thin(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype),
+        takes=lambda kind, op, lay, bf16: kind == "data" and lay[6:] == _K3 and ops.thin_supported(op, *lay[2:6])),
+    "thin_f2m": _Engine(
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv_thin_f2m_mfma(op, inp, w, lay[1:5], lay[5], lay[6], lay[7], out_dtype=out_dtype),
+        takes=lambda kind, op, lay, bf16: kind == "data" and lay[8:] == (1, 1) and ops.thin_f2m_mfma_supported(op, *lay[1:8])),
+    "thin_mfma": _Engine(
+        None, _thin_mfma_wrw, sink=True,
+        takes=lambda kind, op, lay, bf16: kind == "wrw" and lay[8:] == (1, 1) and ops.thin_wrw_mfma_supported(*lay[:8])),
     "smallmap": _Engine(         # the weight gradient takes (coarse, fine)
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv_smallmap(_smallmap_op(op), inp, w, *_smallmap_geometry(lay)),
         lambda x, dy, lay, math, sink: ops.conv_smallmap(ops.SM_WRW, *((x, dy) if lay[0] else (dy, x)), *_smallmap_geometry(lay), out=sink),
+        lambda kind, op, lay, bf16: ops.smallmap_supported(_smallmap_op(op) if kind == "data" else ops.SM_WRW, *_smallmap_geometry(lay)),
         fp32_copies=True, sink=True),
-    "direct": _Engine(lambda op, inp, w, lay, math, out_dtype, param: ops.conv2d(op, inp, w, lay[1:5], *lay[5:])),
-    "one": _Engine(
+    "direct": _Engine(
+        lambda op, inp, w, lay, math, out_dtype, param: ops.conv2d(op, inp, w, lay[1:5], *lay[5:]),
+        takes=lambda kind, op, lay, bf16: kind == "data" and ops.conv2d_supported(op, *lay[1:])),
+    "one": _Engine(              # Conv2d forward and weight gradient only
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv_to_one(inp, w, lay[8]),
         lambda x, dy, lay, math, sink: ops.conv_to_one_wrw(x, dy, lay[6], lay[8], out=sink),
+        lambda kind, op, lay, bf16: not lay[0] and lay[5] == 1 and (kind == "wrw" or op == ops.CONV_FWD) and ops.conv_to_one_supported(*lay[1:5], *lay[6:]),
         fp32_copies=True, sink=True),
-    "bf16d": _Engine(_bf16d_data, _bf16d_wrw, bf16_io=True, sink=True, wrw_x_as_dy=True),
-    "bf16x3d": _Engine(_bf16x3d_data),
-    "bf16x3w": _Engine(None, _bf16x3w_wrw, sink=True),
+    "bf16d": _Engine(_bf16d_data, _bf16d_wrw, _bf16d_takes, bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "bf16x3d": _Engine(_bf16x3d_data, takes=_bf16x3d_takes),
+    "bf16x3w": _Engine(None, _bf16x3w_wrw, _bf16x3w_takes, sink=True),
     "miopen": _Engine(),
 }
 
@@ -728,17 +804,23 @@ def conv_math(bf16):
     return _MATH["bf16" if bf16 else "fp32"]
 
 
+def _engines_of(lay, bf16, dx=True, dw=True):
+    """-> the engines of (forward, input gradient, weight gradient) of one layer; a gradient nobody needs (dx / dw False) is not asked for
+    and reads "miopen"."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if transposed else (ops.CONV_FWD, ops.CONV_BWD_DATA)
+    return (select(fop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16),
+            select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if dx else "miopen",
+            select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if dw else "miopen")
+
+
 def any_engine(m, x):
     """True when at least one pass of m(x) would run on a HIP engine (so the caller should split the bias off and come through
     conv_nobias); False = all three passes are MIOpen's and the plain module call loses nothing."""
     lb = _layer_of(m, x, m.weight)
     if lb is None:
         return False
-    (transposed, B, Cin, H, W, Cout, k, stride, pad, dil), bf16 = lb
-    fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if transposed else (ops.CONV_FWD, ops.CONV_BWD_DATA)
-    return select(fop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) != "miopen" \
-        or select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) != "miopen" \
-        or select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) != "miopen"
+    return _engines_of(*lb) != ("miopen",) * 3
 
 
 def conv_nobias(m, x, weight=None):
@@ -749,20 +831,16 @@ def conv_nobias(m, x, weight=None):
     lb = _layer_of(m, x, w)
     if lb is not None:
         lay, bf16 = lb
-        transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
-        op = ops.CONVT_FWD if transposed else ops.CONV_FWD
         act = torch.bfloat16 if bf16 else torch.float32
         math = _MATH["bf16" if bf16 else "fp32"]
-        eng = select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
-        if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
+        grad = torch.is_grad_enabled()
+        engs = _engines_of(lay, bf16, grad and x.requires_grad, grad and w.requires_grad)
+        if grad and (x.requires_grad or w.requires_grad):
             # the backward may use a HIP engine even where the forward stays on MIOpen
-            bop = ops.CONVT_BWD_DATA if transposed else ops.CONV_BWD_DATA
-            beng = select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if x.requires_grad else "miopen"
-            weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if w.requires_grad else "miopen"
-            if eng != "miopen" or beng != "miopen" or weng != "miopen":
-                return _HipConv.apply(x, w, lay, eng, math, act)
-        elif eng != "miopen":
-            return _run_data(eng, op, x.contiguous(), w.detach(), lay, math, act, param=w)
+            if engs != ("miopen",) * 3:
+                return _HipConv.apply(x, w, lay, engs[0], math, act)
+        elif engs[0] != "miopen":
+            return _run_data(engs[0], ops.CONVT_FWD if lay[0] else ops.CONV_FWD, x.contiguous(), w.detach(), lay, math, act, param=w)
     if isinstance(m, nn.ConvTranspose2d):
         return F.conv_transpose2d(x, w, None, m.stride, m.padding, m.output_padding, m.groups, m.dilation)
     return F.conv2d(x, w, None, m.stride, m.padding, m.dilation, m.groups)

@@ -456,9 +456,9 @@ CONV_FWD, CONV_BWD_DATA, CONVT_FWD, CONVT_BWD_DATA = 0, 1, 2, 3
 # and the dispatcher (models/hipconv.py) moves the passes named here to the DIRECT kernels on split-bf16 operands (csrc/conv_bf16.hip:
 # every operand hi + lo, every product lo*hi + hi*lo + hi*hi, fp32 accumulation, error ~6e-6), wherever the kernel takes the shape:
 #   "k3_data"  forward / input gradient of the k3 s1 p1 layers that "winograd" has               -> conv3x3_bf16x3      (engine "bf16x3d")
-#   "k3_wrw"   weight gradient of the k3 s1 p1 layers that hipconv._bf16x3_wrw_wins names      -> conv3x3_bf16x3_wrw  (engine "bf16x3w")
-#   "s2_data"  forward / input gradient of the k4 s2 p1 layers that hipconv._bf16x3_s2_wins names -> conv4x4s2_bf16x3   (engine "bf16x3d")
-#   "s2_wrw"   weight gradient of the k4 s2 p1 layers that hipconv._bf16x3_s2_wrw_wins names   -> conv4x4s2_bf16x3_wrw (engine "bf16x3w")
+#   "k3_wrw"   weight gradient of the k3 s1 p1 layers of that row of hipconv._DIRECT_OPT_INS     -> conv3x3_bf16x3_wrw  (engine "bf16x3w")
+#   "s2_data"  forward / input gradient of the k4 s2 p1 layers of that row                       -> conv4x4s2_bf16x3   (engine "bf16x3d")
+#   "s2_wrw"   weight gradient of the k4 s2 p1 layers of that row                                -> conv4x4s2_bf16x3_wrw (engine "bf16x3w")
 # Each name moves what the one before it moves, plus one more pass.  This table is the one place that says so.
 DIRECT_PASSES = {
     "direct_bf16x3": frozenset({"k3_data"}),

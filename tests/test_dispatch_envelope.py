@@ -1,13 +1,21 @@
 """The dispatcher of models/hipconv.py at the edges of what its rules admit — host logic and workspace probes only, no kernel is launched.
 
 The rules were measured on square maps at batch 8 / 16, and several bound H alone, or H * W alone, and channel counts from below only: they
-hand the engines elongated maps, one-row and one-column maps and other batches.  Three checks:
+hand the engines elongated maps, one-row and one-column maps and other batches.  The checks:
+  * every answer of the sweep is the recorded one (digests per block, tests/golden/dispatch_envelope_digests.json);
+  * `hipconv.engine_takes`, what the rules and the final guard ask, equals the independent restatement `dispatch_envelope.takes`; an engine
+    whose record refuses is never answered; the three kinds of direct opt-in switch build one set;
   * no answer of `select` / `select_wrw` over a grid with H != W is one the chosen engine's own support query refuses (such a layer would
     raise NotImplementedError in `conv_nobias` although torch computes it);
   * every row of tests/dispatch_envelope.py's corner table still reaches the engines it names (tests/test_gpu_dispatch_envelope.py runs
     those rows against fp64: a row whose answer moved to MIOpen would compare MIOpen with fp64 and pass);
   * the table covers every (engine, pass kind) the grid observes, in both orientations and at batches 1 and 3.
 """
+import hashlib
+import json
+import os
+from collections import namedtuple
+
 import pytest
 
 import dispatch_envelope as de
@@ -40,16 +48,41 @@ def built():
     return _lib
 
 
+# ---- every answer of the sweep, pinned by digest ---------------------------------------------------------------------------------------
+# tests/golden/dispatch_envelope_digests.json holds one SHA-256 and one answer count per block of the sweep, block = (setting, dtype, batch,
+# geometry): the digest of the block's answers, "miopen" included, one character each (the engine's index in `DIGEST_ENGINES`, base 36), in
+# the order the sweep walks — channels x H x W x Conv2d / ConvTranspose2d x (forward, input gradient, weight gradient), shapes torch refuses
+# left out.  tests/golden/engine_selection.json.gz pins square maps under the default arithmetic; this pins the elongated maps and the opt-in
+# arithmetics.  A pull request that re-routes or widens an engine regenerates the file
+# (IPSR_REGENERATE_DISPATCH_DIGESTS=1 python -m pytest tests/test_dispatch_envelope.py -k recorded_digests) and shows which blocks moved; one
+# that only restructures the rules must never regenerate it from the restructured code.
+DIGEST_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispatch_envelope_digests.json")
+DIGEST_ENGINES = ["miopen", "winograd", "wino_dil", "wino_s2", "thin", "thin_f2m", "thin_mfma", "smallmap", "direct", "one", "bf16d", "bf16x3d", "bf16x3w"]
+_DIGITS = "0123456789abcdefghijklmnopqrstuvwxyz"
+
+Sweep = namedtuple("Sweep", "refused seen blocks disagree")
+
+
+def _block_key(setting, bf16, B, geom):
+    return "%s/%s/b%d/k%ds%dp%dd%d" % ((setting, "bf16" if bf16 else "fp32", B) + tuple(geom))
+
+
 @pytest.fixture(scope="module")
-def sweep(built):
-    """-> (refused, seen): the answers the chosen engine's own support query refuses, as (setting, engine, kind, op, lay, bf16), and the
-    {(engine, kind): count} of every answer other than "miopen", over settings x dtypes x batches x geometries x channels x H x W x the three
-    passes of Conv2d and of ConvTranspose2d, on the shapes torch accepts."""
+def swept(built):
+    """-> Sweep over settings x dtypes x batches x geometries x channels x H x W x the three passes of Conv2d and of ConvTranspose2d, on the
+    shapes torch accepts:
+      refused   the answers the chosen engine's own support query (`de.takes`) refuses, as (setting, engine, kind, op, lay, bf16)
+      seen      {(engine, kind): count} of every answer other than "miopen"
+      blocks    {block key: (SHA-256 of the block's answers, their count)}, see `DIGEST_FIXTURE`
+      disagree  the answers on which `hipconv.engine_takes` and `de.takes` differ, as `refused` (None under a hipconv.py from before the engine
+                records had `takes`: the digests can be checked against such a file, nothing else here can)"""
     from deepinpainting_amd import ops
     from deepinpainting_amd.models import hipconv
     assert sorted(n for n, _, sw, _, _ in SETTINGS if sw != "default") == sorted(ops.DIRECT_PASSES)
+    code = {e: _DIGITS[i] for i, e in enumerate(DIGEST_ENGINES)}
+    engine_takes = getattr(hipconv, "engine_takes", None)
     mp = pytest.MonkeyPatch()
-    refused, seen, points = [], {}, 0
+    refused, seen, points, blocks, disagree = [], {}, 0, {}, None if engine_takes is None else []
     try:
         mp.setattr(hipconv, "_FORCE", None)
         for name, env, sw, dtypes, channels in SETTINGS:
@@ -62,6 +95,7 @@ def sweep(built):
                 for bf16 in dtypes:
                     for B in BATCHES:
                         for geom in GEOMS:
+                            chars = []
                             for Cin, Cout in channels:
                                 for H in EXTENTS:
                                     for W in EXTENTS:
@@ -71,17 +105,67 @@ def sweep(built):
                                                 continue
                                             for eng, (kind, op) in zip(de.answers(hipconv, lay, bf16), de.passes(lay)):
                                                 points += 1
+                                                chars.append(code[eng])
                                                 if eng == "miopen":
                                                     continue
                                                 seen[(eng, kind)] = seen.get((eng, kind), 0) + 1
-                                                if not de.takes(eng, kind, op, lay, bf16):
+                                                took = de.takes(eng, kind, op, lay, bf16)
+                                                if not took:
                                                     refused.append((name, eng, kind, op, lay, bf16))
+                                                if engine_takes is not None and engine_takes(eng, kind, op, lay, bf16) != took:
+                                                    disagree.append((name, eng, kind, op, lay, bf16))
+                            blocks[_block_key(name, bf16, B, geom)] = (hashlib.sha256("".join(chars).encode("ascii")).hexdigest(), len(chars))
                     hipconv._SEL.clear()             # the memo of a finished dtype is dead weight
     finally:
         mp.undo()
         hipconv.reload_env()
     print("dispatcher sweep: %d answers, %d on a HIP engine, %d refused" % (points, sum(seen.values()), len(refused)))
-    return refused, seen
+    return Sweep(refused, seen, blocks, disagree)
+
+
+@pytest.fixture(scope="module")
+def sweep(swept):
+    """-> (refused, seen) of `swept`."""
+    return swept.refused, swept.seen
+
+
+def test_sweep_answers_match_the_recorded_digests(swept):
+    """Every answer of the sweep, "miopen" included, is the one recorded: per block (setting, dtype, batch, geometry) the digest and the count
+    of the answers equal the fixture's.  `test_no_selection_is_refused_by_its_engine` checks that answers are taken, not what they are;
+    this pins what they are, on elongated maps and under every opt-in arithmetic."""
+    if os.environ.get("IPSR_REGENERATE_DISPATCH_DIGESTS") == "1":
+        doc = {"engines": DIGEST_ENGINES, "extents": EXTENTS, "order": "per block: channels x H x W x (Conv2d, ConvTranspose2d) x (forward, input gradient, "
+               "weight gradient), shapes torch refuses left out; one base-36 digit per answer, its index in `engines`",
+               "blocks": {key: {"sha256": sha, "answers": n} for key, (sha, n) in swept.blocks.items()}}
+        with open(DIGEST_FIXTURE, "w") as f:
+            json.dump(doc, f, sort_keys=True, indent=0)
+            f.write("\n")
+    with open(DIGEST_FIXTURE) as f:
+        doc = json.load(f)
+    assert doc["engines"] == DIGEST_ENGINES and doc["extents"] == EXTENTS
+    want = {key: (b["sha256"], b["answers"]) for key, b in doc["blocks"].items()}
+    assert sorted(want) == sorted(swept.blocks), (sorted(set(want) - set(swept.blocks)), sorted(set(swept.blocks) - set(want)))
+    moved = sorted(key for key in want if want[key] != swept.blocks[key])
+    assert not moved, "%d of %d blocks moved (block: recorded count -> now): %s" % (
+        len(moved), len(want), ", ".join("%s: %d -> %d" % (k, want[k][1], swept.blocks[k][1]) for k in moved))
+    assert sum(n for _, n in want.values()) > 1000000 and len(want) >= 300
+
+
+def test_engine_takes_is_the_independent_restatement(swept, hipconv):
+    """`hipconv.engine_takes` — the `takes` of the engine records, what the rules and the final guard ask — equals `de.takes`, the restatement
+    by geometry in tests/dispatch_envelope.py: for the answered engine at every point of the sweep, and for every engine x the three passes on
+    every row of the corner table, with the row's dtype and with the other one.  "miopen" takes everything."""
+    assert swept.disagree == [], "%d sweep answers, first: %s" % (len(swept.disagree), swept.disagree[:6])
+    differ = []
+    for row in de.ROWS:
+        with de.switches(hipconv, row.switches):
+            for bf16 in (row.bf16, not row.bf16):
+                for kind, op in de.passes(row.lay):
+                    assert hipconv.engine_takes("miopen", kind, op, row.lay, bf16) is True
+                    for eng in hipconv._ENGINES:
+                        if eng != "miopen" and hipconv.engine_takes(eng, kind, op, row.lay, bf16) != de.takes(eng, kind, op, row.lay, bf16):
+                            differ.append((row.id, eng, kind, op, bf16))
+    assert not differ, differ
 
 
 def test_no_selection_is_refused_by_its_engine(sweep):
@@ -123,6 +207,56 @@ def test_envelope_rows_reach_the_engines_they_name(hipconv):
     assert len(set(r.id for r in de.ROWS)) == len(de.ROWS)
     k4s1_below = [r for r in de.ROWS if r.geom == de.K4S1 and (r.cin, r.cout, r.H, r.W, r.B) == (128, 128, 16, 3, 1)]
     assert len(k4s1_below) == 1 and k4s1_below[0].engines == ("miopen",) * 3
+
+
+def test_an_engine_that_refuses_is_never_answered(hipconv):
+    """The final guard of `_select_any` / `_select_wrw_any`: with one record's `takes` answering False, no pass of any row of the corner table
+    is answered with that engine — it goes to "miopen" or to a later rule's engine — and the passes of the other engines stay.  "winograd" and
+    "wino_dil" are the engines whose rules probe nothing, "wino_s2" probes for its data passes only, "smallmap" probes in its rule."""
+    for refused in ("winograd", "wino_dil", "wino_s2", "smallmap"):
+        rows = [r for r in de.ROWS if refused in r.engines]
+        assert rows, refused
+        for patched in (True, False):            # then with the record put back: the rows answer their engines again
+            with pytest.MonkeyPatch.context() as mp:
+                if patched:
+                    mp.setitem(hipconv._ENGINES, refused, hipconv._ENGINES[refused]._replace(takes=lambda kind, op, lay, bf16: False))
+                hipconv._SEL.clear()
+                try:
+                    for row in rows:
+                        with de.switches(hipconv, row.switches):
+                            got = de.answers(hipconv, row.lay, row.bf16)
+                        assert not patched or refused not in got, (refused, row.id, got)
+                        assert all(g == e for g, e in zip(got, row.engines) if not patched or e != refused), (refused, row.id, got)
+                finally:
+                    hipconv._SEL.clear()
+
+
+def test_direct_switches_build_one_set(hipconv):
+    """`_direct_passes_on` over the 2 x 2 x 5 settings of the two dilated booleans and the fp32 arithmetic: the passes of ops.DIRECT_PASSES
+    for the name plus "dil_data" / "dil_wrw" for the booleans, and the public getters read the same set.  The direct names stay refused for
+    bf16 activations."""
+    from deepinpainting_amd import ops
+    was = (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw())
+    try:
+        for math in ["fp32"] + sorted(ops.DIRECT_PASSES):
+            for dil in (False, True):
+                for dil_dw in (False, True):
+                    hipconv.set_conv_math(fp32=math)
+                    hipconv.set_direct_dilated(dil)
+                    hipconv.set_direct_dilated_dw(dil_dw)
+                    want = set(ops.DIRECT_PASSES.get(math, ())) | ({"dil_data"} if dil else set()) | ({"dil_wrw"} if dil_dw else set())
+                    assert set(hipconv._direct_passes_on()) == want, (math, dil, dil_dw)
+                    assert (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw()) == (math, dil, dil_dw)
+                    assert all(ops.direct_moves(math, key) == (key in want) for key in ("k3_data", "k3_wrw", "s2_data", "s2_wrw"))
+        assert set(r.key for r in hipconv._DIRECT_OPT_INS) == set().union(*ops.DIRECT_PASSES.values()) | {"dil_data", "dil_wrw"}
+        for name in ops.DIRECT_PASSES:
+            with pytest.raises(ValueError):
+                hipconv.set_conv_math(bf16=name)
+        assert hipconv._MATH["bf16"] not in ops.DIRECT_PASSES
+    finally:
+        hipconv.set_conv_math(fp32=was[0])
+        hipconv.set_direct_dilated(was[1])
+        hipconv.set_direct_dilated_dw(was[2])
 
 
 # (engine, kind) whose rule admits one orientation only, and why
