@@ -255,7 +255,7 @@ class IPSR(BaseModel):
         self.loss_IPSR = self.criterionGAN(self.real_B, self.fake_B, False)
 
     def get_loss(self):
-        self.loss_valid = (self.criterionL1(self.fake_B, self.real_B) + self.criterionL1(self.fake_P, self.real_B)) * self.opt.lambda_A
+        self.loss_valid = networks.l1_pair_loss(self.fake_B, self.fake_P, self.real_B, self.opt.lambda_A, self.criterionL1)
         return OrderedDict([('GAN', self.loss_valid.data.item())])
 
     def _disc_is_per_sample(self):
@@ -290,15 +290,21 @@ class IPSR(BaseModel):
                 nb = fake_AB.size(0)
                 both = self.netD(torch.cat((fake_AB.detach(), real_AB), 0)).float()
                 self.pred_fake, self.pred_real = both[:nb], both[nb:]
-                both = self.netF(torch.cat((self.gt_latent_fake.relu3_3.detach(), self.gt_latent_real.relu3_3), 0)).float()
-                self.pred_fake_F, self.pred_real_F = both[:nb], both[nb:]
+                both_F = self.netF(torch.cat((self.gt_latent_fake.relu3_3.detach(), self.gt_latent_real.relu3_3), 0)).float()
+                self.pred_fake_F, self.pred_real_F = both_F[:nb], both_F[nb:]
             else:
+                both = both_F = None
                 self.pred_fake = self.netD(fake_AB.detach()).float()
                 self.pred_real = self.netD(real_AB).float()
                 self.pred_fake_F = self.netF(self.gt_latent_fake.relu3_3.detach()).float()
                 self.pred_real_F = self.netF(self.gt_latent_real.relu3_3).float()
-        self.loss_D_fake = self.criterionGAN(self.pred_fake, self.pred_real, True)
-        self.loss_F_fake = self.criterionGAN(self.pred_fake_F, self.pred_real_F, True)
+        if both is not None:
+            # the batched predictions go to the loss whole: one gradient tensor each instead of two zero-filled halves and their sum
+            self.loss_D_fake = self.criterionGAN.batched(both, nb, True)
+            self.loss_F_fake = self.criterionGAN.batched(both_F, nb, True)
+        else:
+            self.loss_D_fake = self.criterionGAN(self.pred_fake, self.pred_real, True)
+            self.loss_F_fake = self.criterionGAN(self.pred_fake_F, self.pred_real_F, True)
 
         self.loss_D = self.loss_D_fake * 0.5 + self.loss_F_fake * 0.5
         if self._reducer_D is not None:
@@ -329,7 +335,7 @@ class IPSR(BaseModel):
             pred_real_F = self.netF(self.gt_latent_real.relu3_3).float()
 
         self.loss_G_GAN = self.criterionGAN(pred_fake, pred_real, False) + self.criterionGAN(pred_fake_f, pred_real_F, False)
-        self.loss_G_L1 = (self.criterionL1(self.fake_B, self.real_B) + self.criterionL1(self.fake_P, self.real_B)) * self.opt.lambda_A
+        self.loss_G_L1 = networks.l1_pair_loss(self.fake_B, self.fake_P, self.real_B, self.opt.lambda_A, self.criterionL1)
         self.loss_G = self.loss_G_L1 + self.loss_G_GAN * self.opt.gan_weight
 
         self.ng_loss_value = 0

@@ -14,13 +14,16 @@ The convolutions run on PyTorch-ROCm (MIOpen); the patch-attention layer and the
 the IPSR block are the hand-written HIP path (IPSR_model / InnerCos / InnerCos2).
 """
 import functools
+import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 from torch.nn import init
 from torch.optim import lr_scheduler
 
+from .. import _lib, ops
 from .IPSR_model import IPSR_model
 from .InnerCos import InnerCos
 from .InnerCos2 import InnerCos2
@@ -154,11 +157,108 @@ class GANLoss(nn.Module):
         return cur
 
     def __call__(self, y_pred_fake, y_pred, target_is_real):
-        t = self.get_target_tensor(y_pred_fake, target_is_real)
         sign = 1.0 if target_is_real else -1.0
+        if _fused_route(y_pred_fake, y_pred):
+            return _RaGANLoss.apply(y_pred_fake, y_pred, sign * self.real_label)
+        t = self.get_target_tensor(y_pred_fake, target_is_real)
         a = torch.mean((y_pred - torch.mean(y_pred_fake) - sign * t) ** 2)
         b = torch.mean((y_pred_fake - torch.mean(y_pred) + sign * t) ** 2)
         return (a + b) / 2
+
+    def batched(self, both, nb, target_is_real):
+        """The loss of both[:nb] (fake) against both[nb:] (real), the two halves of one batched prediction: on the fused route its
+        gradient is written as ONE tensor, where autograd would zero-fill two and add them."""
+        if 0 < nb < both.size(0) and _fused_route(both) and both.requires_grad and torch.is_grad_enabled():
+            return _RaGANLossBatched.apply(both, nb, (1.0 if target_is_real else -1.0) * self.real_label)
+        return self(both[:nb], both[nb:], target_is_real)
+
+
+# ----------------------------------------------------------------------------------------------------
+# the fused loss heads (csrc/loss_head.hip): value and gradients in one launch, the backward one multiply by the incoming scalar
+# ----------------------------------------------------------------------------------------------------
+_FUSED = None          # None: read IPSR_NO_FUSED_LOSS at the next use
+
+
+def set_fused_losses(on):
+    """True / False: the loss heads (GANLoss, l1_pair_loss) of CUDA fp32 contiguous tensors run as one HIP launch each / as PyTorch
+    expressions (A/B runs, tests).  None: back to the environment's choice (IPSR_NO_FUSED_LOSS=1 turns them off), read at the next use."""
+    global _FUSED
+    _FUSED = None if on is None else bool(on)
+
+
+def fused_losses():
+    global _FUSED
+    if _FUSED is None:
+        _FUSED = os.environ.get("IPSR_NO_FUSED_LOSS", "0") != "1"
+    return _FUSED
+
+
+def _fused_route(*tensors):
+    """CUDA fp32 contiguous tensors on the current device, the switch on and the library built; everything else (the CPU twin, other
+    dtypes, strided views) keeps the PyTorch expression."""
+    if not fused_losses():
+        return False
+    for t in tensors:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() > 0 and t.device.index == torch._C._cuda_getDevice()):
+            return False
+    return os.path.exists(_lib.LIB_PATH)
+
+
+class _RaGANLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fake, real, s):
+        loss, ctx.gf, ctx.gr = ops.ragan_loss(fake, real, s, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        gf, gr = ctx.gf, ctx.gr
+        if gf is None and gr is None:
+            return None, None, None
+        if gf is None:
+            return None, ops.loss_grad_scale(grad_loss, gr)[0], None
+        gf, gr = ops.loss_grad_scale(grad_loss, gf, gr)
+        return gf, gr, None
+
+
+class _RaGANLossBatched(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, both, nb, s):
+        loss, g = ops.ragan_loss(both[:nb], both[nb:], s, joined=True)
+        ctx.g, ctx.shape = g, both.shape
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        return ops.loss_grad_scale(grad_loss, ctx.g)[0].view(ctx.shape), None, None
+
+
+class _L1PairLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a1, a2, target, scale):
+        loss, ctx.g1, ctx.g2 = ops.l1_pair_loss(a1, a2, target, scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        g1, g2 = ctx.g1, ctx.g2
+        if g1 is None and g2 is None:
+            return None, None, None, None
+        if g1 is None:
+            return None, ops.loss_grad_scale(grad_loss, g2)[0], None, None
+        g1, g2 = ops.loss_grad_scale(grad_loss, g1, g2)
+        return g1, g2, None, None
+
+
+def l1_pair_loss(a1, a2, target, scale, criterion=F.l1_loss):
+    """(criterion(a1, target) + criterion(a2, target)) * scale — the two L1 terms of the generator loss.  `target` takes no gradient."""
+    if _fused_route(a1, a2, target) and a1.shape == target.shape and a2.shape == target.shape and not target.requires_grad \
+            and (criterion is F.l1_loss or (type(criterion) is nn.L1Loss and criterion.reduction == 'mean')):
+        return _L1PairLoss.apply(a1, a2, target, float(scale))
+    return (criterion(a1, target) + criterion(a2, target)) * scale
 
 
 # ----------------------------------------------------------------------------------------------------

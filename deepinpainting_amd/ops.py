@@ -1138,3 +1138,68 @@ def innercos_loss_backward(x, cuse, mask_f32, target, strength, grad_loss):
                                                  float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
                "innercos_loss_backward")
     return gx
+
+
+# ---- loss heads (csrc/loss_head.hip): the value and the gradients for a unit incoming gradient in one launch
+def _count(n, what):
+    if not 0 < n < 2 ** 31:
+        raise RuntimeError("%s: %d elements (the entry takes 1 .. 2^31 - 1)" % (what, n))
+    return n
+
+
+def ragan_loss(fake, real, s, want_fake=True, want_real=True, joined=False):
+    """The relativistic-average LSGAN loss 1/2 [mean((real - mean(fake) - s)^2) + mean((fake - mean(real) + s)^2)] of two fp32
+    predictions (any shapes, the sizes may differ) -> (loss [], d loss / d fake or None, d loss / d real or None), the gradients shaped
+    like their inputs.  `joined`: both gradients are wanted as ONE flat buffer [n_fake + n_real] (fake first) -> (loss, buffer): the
+    gradient of a batched prediction whose halves `fake` and `real` are."""
+    fake, real = _req(fake, torch.float32, "fake"), _req(real, torch.float32, "real")
+    nf, nr = _count(fake.numel(), "fake"), _count(real.numel(), "real")
+    _count(nf + nr, "fake + real")
+    dev = fake.device
+    loss = _empty((), dtype=torch.float32, device=dev)
+    if joined:
+        both = _empty((nf + nr,), dtype=torch.float32, device=dev)
+        gf, gr = both[:nf], both[nf:]
+    else:
+        gf = _empty(fake.shape, dtype=torch.float32, device=dev) if want_fake else None
+        gr = _empty(real.shape, dtype=torch.float32, device=dev) if want_real else None
+    _lib.check(_lib.lib().ipsr_ragan_loss(fake.data_ptr(), nf, real.data_ptr(), nr, float(s), loss.data_ptr(),
+                                          gf.data_ptr() if gf is not None else None, gr.data_ptr() if gr is not None else None, _stream()),
+               "ipsr_ragan_loss")
+    return (loss, both) if joined else (loss, gf, gr)
+
+
+def l1_pair_loss(a1, a2, target, scale, want1=True, want2=True):
+    """scale * (mean|a1 - target| + mean|a2 - target|) of three fp32 tensors of one shape -> (loss [], g1 or None, g2 or None) with
+    g = (scale / n) * sign(a - target), written in the same pass."""
+    a1, a2, target = _req(a1, torch.float32, "a1"), _req(a2, torch.float32, "a2"), _req(target, torch.float32, "target")
+    if a1.shape != target.shape or a2.shape != target.shape:
+        raise RuntimeError("l1_pair_loss: shapes %s / %s / %s differ" % (tuple(a1.shape), tuple(a2.shape), tuple(target.shape)))
+    n, dev = _count(target.numel(), "target"), target.device
+    loss = _empty((), dtype=torch.float32, device=dev)
+    g1 = _empty(a1.shape, dtype=torch.float32, device=dev) if want1 else None
+    g2 = _empty(a2.shape, dtype=torch.float32, device=dev) if want2 else None
+    L = _lib.lib()
+    ws = _workspace(L.ipsr_l1_pair_loss_workspace_bytes(n), dev)
+    _lib.check(L.ipsr_l1_pair_loss(a1.data_ptr(), a2.data_ptr(), target.data_ptr(), n, float(scale), loss.data_ptr(),
+                                   g1.data_ptr() if g1 is not None else None, g2.data_ptr() if g2 is not None else None,
+                                   ws.data_ptr(), ws.numel(), _stream()), "ipsr_l1_pair_loss")
+    return loss, g1, g2
+
+
+def loss_grad_scale(grad_loss, g1, g2=None):
+    """The backward of the loss heads: g * grad_loss for one or two saved gradients in one launch; grad_loss is a one-element fp32
+    tensor on the device and stays there."""
+    gl = _req(grad_loss.reshape(1), torch.float32, "grad_loss")
+    g1 = _req(g1, torch.float32, "g1")
+    _count(g1.numel(), "g1")
+    o1 = _empty(g1.shape, dtype=torch.float32, device=g1.device)
+    o2 = None
+    if g2 is not None:
+        g2 = _req(g2, torch.float32, "g2")
+        _count(g2.numel(), "g2")
+        o2 = _empty(g2.shape, dtype=torch.float32, device=g2.device)
+    _lib.check(_lib.lib().ipsr_loss_grad_scale(gl.data_ptr(), g1.data_ptr(), o1.data_ptr(), g1.numel(),
+                                               g2.data_ptr() if g2 is not None else None, o2.data_ptr() if o2 is not None else None,
+                                               g2.numel() if g2 is not None else 0, _stream()), "ipsr_loss_grad_scale")
+    return o1, o2

@@ -400,6 +400,27 @@ int innercos_loss_backward(const float* x, int B, int Cx, int Cuse, int N, const
                            const float* target, float strength, const float* grad_loss /*[1]*/,
                            float* grad_x /*[B,Cx,N]*/, void* stream);
 
+/* ---- loss heads: value and gradients in one launch (csrc/loss_head.hip) -----------------------------
+ * The relativistic-average LSGAN loss of models/networks.py GANLoss, with s = sign * label:
+ *     loss = 1/2 [ mean((real - mean(fake) - s)^2) + mean((fake - mean(real) + s)^2) ]
+ * fake [n_fake], real [n_real] fp32 (the sizes may differ) -> loss [1] on the device and, where the pointer is not NULL,
+ * grad_fake [n_fake] / grad_real [n_real] = d loss / d input for a unit incoming gradient.  One launch of a few workgroups that share
+ * nothing (each sums both inputs whole, then writes its share of the gradients), every sum in fp64 in a fixed order: two calls give the
+ * same bits.  16-byte aligned operands are read and written as 4-element vectors, others element by element. */
+int ipsr_ragan_loss(const float* fake, int n_fake, const float* real, int n_real, float s, float* loss /*[1]*/,
+                    float* grad_fake /*[n_fake] or NULL*/, float* grad_real /*[n_real] or NULL*/, void* stream);
+/* Two L1 terms that share their target: loss = scale * (mean|a1 - t| + mean|a2 - t|) over n elements each, and in the same pass, where
+ * the pointer is not NULL, g1 / g2 = (scale / n) * sign(a - t) (sign(0) = 0).  Block partials in fp64 (workspace, 8-byte aligned, of
+ * ipsr_l1_pair_loss_workspace_bytes(n)), folded in a fixed order by a second small launch.  16-byte aligned operands are read and
+ * written as 4-element vectors, others element by element. */
+size_t ipsr_l1_pair_loss_workspace_bytes(int n);
+int ipsr_l1_pair_loss(const float* a1, const float* a2, const float* t, int n, float scale, float* loss /*[1]*/,
+                      float* g1 /*[n] or NULL*/, float* g2 /*[n] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+/* Their backward: out = g * (*gscale), gscale one fp32 ON THE DEVICE (the incoming gradient of the loss; never read by the host), for
+ * one saved gradient (n2 = 0) or two in one launch.  Added with the two entries above without an ABI version change (15). */
+int ipsr_loss_grad_scale(const float* gscale /*[1]*/, const float* g1, float* out1, int n1, const float* g2, float* out2, int n2,
+                         void* stream);
+
 /* ---- measurement hook (bench.py) -----------------------------------------------------------------
  * Opt-in: when enabled, three kinds of regions are bracketed by a pair of HIP events recorded on the SAME stream the
  * work is launched on:
