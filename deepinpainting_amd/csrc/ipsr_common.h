@@ -24,6 +24,9 @@ void profile_mark_stop(hipStream_t st, int region = 0, double work = 0.0, double
 //   3  smallmap.hip: 1 = the small operands laid out in the workspace by pre-pass launches ("staged") in every call, 2 = gathered in
 //      the main kernels in every call (the default gathers except in the weight gradient above 32 positions)
 //   4  smallmap.hip: col2im by the looping kernel (one load per term, in turn) instead of the one that issues its loads up front
+//   5  smallmap.hip: the tiled flag of `op` (IPSR_SMALLMAP_TILED) is ignored: such calls run the streaming kernels
+//   6  smallmap.hip: > 0 = the number of splits of the tiled regime's reduction (the plan's own choice otherwise); set it before the
+//      workspace query, which follows it
 int debug_option(int key);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -21,6 +21,8 @@
 // not depend on the form: gathered calls leave the image slices of the workspace unused.
 // Each stream is software-pipelined over three register sets (sm_stream): two groups of loads are in flight beyond the one whose
 // MFMAs run.
+// A second regime, asked for by a flag bit of `op` (SM_TILED), runs DATA and FWD from 33 positions up as LDS-tiled split-K GEMMs on the same
+// weights in place (sm_tiled_kernel, "the tiled regime" below): from 256 positions up it is ahead of the streams.
 #include <algorithm>
 
 #include "ipsr_common.h"
@@ -464,6 +466,166 @@ __global__ void __launch_bounds__(64) sm_wrw_kernel(const float* __restrict__ Ct
     }
 }
 
+// ---- the tiled regime (op | SM_TILED): 33 .. 1024 positions -------------------------------------------------------------------------------
+// From 128 positions up DATA and FWD are real GEMMs, and a stream that reloads every small-operand value per lane and MFMA and reads the
+// weights once per 128 positions is bound by its loads.  Here both are the LDS-tiled fp32-MFMA GEMM of conv_gemm.hip: 256 threads, a
+// 128 (rows of the result) x 128 (positions) tile, 2 x 2 sub-tiles of 32 x 32 per wave, 16-deep stages double-buffered in LDS (32 KiB: up to
+// four workgroups per CU), one barrier per stage.  The weights are still read where they lie:
+//   DATA  Mcol[q][p] = sum_r Wm[r][q] * in[r][p]     Wm is reduction-major with q contiguous — the [red][rows] LDS image itself: its rows go
+//                                                     HBM -> LDS by 16-byte DMA, one stage ahead (R % 32 == 0, Q % 128 == 0: every piece is whole)
+//   FWD   Y[r][p]    = sum_q Wm[r][q] * col[q][p]    Wm's rows are reduction-contiguous: a thread's float4 is four reduction steps of one row,
+//                                                     loaded one stage ahead (range-checked: rows >= R read zero) and scattered into the same image
+// The small operand is gathered from the NCHW tensor through registers into LDS once per workgroup and stage — a thread owns one position for
+// the whole loop and eight of the stage's sixteen reduction rows — by the offsets of the streaming kernels (SmPos / sm_tap_off: bit 31 set =
+// dropped by the descriptor, reads +0.0f).  The reduction is cut over workgroups (SmPlan::nslab splits of per_slab stages); every split writes
+// its own partial tile [rows][Tp], and the post-passes of the streaming regime add them in order.
+typedef const __attribute__((address_space(1))) void* sm_gptr_t;
+typedef __attribute__((address_space(3))) void* sm_lptr_t;
+constexpr int SMT_BM = 128, SMT_BN = 128, SMT_BK = 16, SMT_NBUF = 2, SMT_SLOT = 2 * SMT_BK * SMT_BM;
+
+template <bool FWD, int K>
+__global__ void __launch_bounds__(256, 4) sm_tiled_kernel(const float* __restrict__ Wm, const float* __restrict__ X, int R, int Q, int Tp, int m_tiles,
+                                                          int ksplit, int stages_per_split, int nstage, SmGeo g, float* __restrict__ part)
+{
+    __shared__ __attribute__((aligned(16))) float lds[SMT_NBUF * SMT_SLOT];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
+    const int M = FWD ? R : Q;                                // rows of the result
+
+    // m-tiles fastest (they share the gathered operand), then the splits, then the position tiles
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    const int mt = L % m_tiles, ks = (L / m_tiles) % ksplit, nt = L / (m_tiles * ksplit);
+    const int m0 = mt * SMT_BM, n0 = nt * SMT_BN;
+    const int s_lo = ks * stages_per_split;
+    const int ns = min(nstage, s_lo + stages_per_split) - s_lo;            // stages of this workgroup (>= 1)
+
+    // ---- the small operand: this thread's position, rows jj + 8*gpar of every stage
+    const int gpar = wave >> 1, gn = n0 + (tid & 127);
+    const int HW = g.Ho * g.Wo;
+    const __amdgpu_buffer_rsrc_t xrs = sm_rsrc(X, (unsigned)(g.P / HW) * (FWD ? g.C * g.Hf * g.Wf : R * HW) * 4u);
+    const SmPos pos(g, gn);                                   // FWD: the taps of this position
+    const unsigned icol = gn < g.P ? (unsigned)((gn / HW) * R * HW + gn % HW) * 4u : SM_OFF;      // DATA: the position in row 0 of `in`
+    float breg[8];
+    auto gather = [&](int s) {
+        const unsigned row0 = (unsigned)((s_lo + s) * SMT_BK + 8 * gpar);                       // wave-uniform
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj)
+            breg[jj] = sm_ld(xrs, FWD ? sm_tap_off<K>(g, pos, row0 + jj, 1u) : icol + (row0 + jj) * (unsigned)HW * 4u);
+    };
+    auto store_b = [&](int s) {
+        float* bt = lds + (s & (SMT_NBUF - 1)) * SMT_SLOT + SMT_BK * SMT_BM + (tid & 127);
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) bt[(jj + 8 * gpar) * SMT_BM] = breg[jj];
+    };
+
+    // ---- the weights.  DATA: DMA pieces of two rows x 128 columns, piece q of a stage belongs to wave q % 4
+    const int dma_row = lane >> 5, dma_col = (lane & 31) * 4;
+    const float* wbase = Wm + (size_t)s_lo * SMT_BK * Q + m0 + dma_col;
+    auto dma_piece = [&](int s, int q) {
+        const int slot = (s & (SMT_NBUF - 1)) * SMT_SLOT + q * 2 * SMT_BM;
+        const float* src = wbase + ((size_t)s * SMT_BK + 2 * q + dma_row) * Q;
+        __builtin_amdgcn_global_load_lds((sm_gptr_t)src, (sm_lptr_t)&lds[slot], 16, 0, 0);
+    };
+    auto dma_stage = [&](int s) {
+        dma_piece(s, wave);
+        dma_piece(s, wave + 4);
+    };
+    // FWD: float4 i of a thread = row (tid + 256 i) / 4 of the tile, reduction steps 4 kc .. 4 kc + 3 of the stage, kc = tid % 4
+    const __amdgpu_buffer_rsrc_t wrs = sm_rsrc(Wm, (unsigned)R * Q * 4u);
+    const int arow = tid >> 2, akc = tid & 3;
+    unsigned aoff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = m0 + arow + 64 * i;
+        aoff[i] = sm_off((unsigned)(min(row, R - 1) * Q + s_lo * SMT_BK + 4 * akc) * 4u, row < R);
+    }
+    f32x4v areg[2];
+    auto load_a = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) areg[i] = sm_ld4(wrs, aoff[i] + (unsigned)(s * SMT_BK) * 4u);
+    };
+    auto store_a = [&](int s) {
+        float* at = lds + (s & (SMT_NBUF - 1)) * SMT_SLOT + 4 * akc * SMT_BM + arow;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) at[j * SMT_BM + 64 * i] = areg[i][j];
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+
+    // ---- prologue: stage 0 in LDS
+    if constexpr (FWD) load_a(0);
+    else dma_stage(0);
+    gather(0);
+    if constexpr (FWD) store_a(0);
+    store_b(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    for (int s = 0; s < ns; ++s) {
+        const int cur = s & (SMT_NBUF - 1);
+        const bool more = s + 1 < ns;
+        if (more) {                                           // stage s+1: lands under this stage's MFMAs
+            if constexpr (FWD) load_a(s + 1);
+            gather(s + 1);
+        }
+        const float* ta = lds + cur * SMT_SLOT + h * SMT_BM + wm * 32 + r;
+        const float* tb = lds + cur * SMT_SLOT + SMT_BK * SMT_BM + h * SMT_BM + wn * 32 + r;
+        float fa0[3], fa1[3], fb0[3], fb1[3];
+        fa0[0] = ta[0]; fa1[0] = ta[64]; fb0[0] = tb[0]; fb1[0] = tb[64];
+#pragma unroll
+        for (int kk = 0; kk < SMT_BK / 2; ++kk) {
+            const int cs = kk % 3, nx = (kk + 1) % 3;
+            if (kk + 1 < SMT_BK / 2) {
+                const int ro = (kk + 1) * 2 * SMT_BM;
+                fa0[nx] = ta[ro]; fa1[nx] = ta[ro + 64]; fb0[nx] = tb[ro]; fb1[nx] = tb[ro + 64];
+            }
+            // DATA: this wave's two weight pieces of stage s+1, into the other slot (last read in stage s-1, before the barrier)
+            if (!FWD && more && kk < 2) dma_piece(s + 1, wave + 4 * kk);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[cs], fb0[cs], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa0[cs], fb1[cs], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[cs], fb0[cs], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[cs], fb1[cs], acc[1][1], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // Stage s+1 must be whole in LDS before anyone crosses the barrier: the registers loaded at the top of this stage and the pieces
+        // issued in its first two k-steps, a stage of MFMAs ago.  A counted wait that leaves pieces of later stages in flight is not to be
+        // had here: before a store to LDS the compiler waits for every LDS DMA in flight (it cannot tell the slots apart), so a deeper ring
+        // bought nothing and two slots it is.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (more) {
+            if constexpr (FWD) store_a(s + 1);
+            store_b(s + 1);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    }
+
+    // ---- this split's partial tile: [M][Tp], lane = position column, 16 rows per sub-tile in registers (n0 + 127 < Tp)
+    float* dst = part + (size_t)ks * M * Tp;
+#pragma unroll
+    for (int jn = 0; jn < 2; ++jn) {
+        const int n = n0 + wn * 32 + jn * 64 + r;
+#pragma unroll
+        for (int im = 0; im < 2; ++im) {
+            const int mb = m0 + wm * 32 + im * 64;            // M % 32 == 0: a sub-tile's 32 rows are inside or outside as a whole (wave-uniform)
+            if (mb >= M) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) dst[(size_t)(mb + (e & 3) + 8 * (e >> 2) + 4 * h) * Tp + n] = acc[im][jn][e];
+        }
+    }
+}
+
 // Which form a call takes.  Gathering wins wherever it was measured on the forward / data passes (<= 32 positions in the training
 // step) and on the weight gradient up to 32 positions; from 128 positions up the weight gradient's four scalar tap loads per lane
 // and position pair cost more than its two pre-pass launches, and it stays staged (profiles/smallmap_stream_layers.txt).
@@ -475,13 +637,25 @@ static bool sm_staged(int op, int P)
     return forced == 1 || (forced != 2 && op == 1 && P > SM_WRW_GATHER_MAX_POS);
 }
 
-struct SmPlan { int P, Tp, Pp, Q, nb, ngroups, nslab, per_slab; size_t a_floats, b_floats, m_floats, total_bytes; };
+// The flag bit of `op` that asks for the tiled regime (ipsr_hip.h).  It changes DATA and FWD with k = 3 | 4 from SM_TILED_MIN_POS positions up; the
+// weight gradient, other kernel sizes and fewer positions (where the streams win: one position block, nothing to share) run as without it.
+// Debug option 5 (A/B): the flag is ignored.
+constexpr int SM_TILED = 16, SM_TILED_MIN_POS = 33;
+static bool sm_tiled(int op, int flags, int k, int P)
+{
+    return (flags & SM_TILED) && !debug_option(5) && (op == 0 || op == 2) && (k == 3 || k == 4) && P >= SM_TILED_MIN_POS;
+}
+
+// tiled: nslab = the splits of the reduction, per_slab = 16-deep stages per split, m_tiles x ngroups = the 128 x 128 tiles
+struct SmPlan { int P, Tp, Pp, Q, nb, ngroups, nslab, per_slab, m_tiles, nstage; bool tiled; size_t a_floats, b_floats, m_floats, total_bytes; };
 
 // op 0 (DATA): in [B][R][Ho][Wo], W [R][Cq][k][k] -> out [B][Cq][Hf][Wf].   op 1 (WRW): coarse [B][R][Ho][Wo], fine [B][Cq][Hf][Wf]
 // -> dW [R][Cq][k][k].   op 2 (FWD): fine [B][Cq][Hf][Wf], W -> out [B][R][Ho][Wo].   (R = the weight's first channel dimension.)
 static int sm_plan(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf, int k, int st, int pad, int dil, SmPlan* p)
 {
-    if (op < 0 || op > 2) return fail(IPSR_ERR_INVALID, "small-map convolution: op %d", op);
+    const int flags = op & ~3;
+    op &= 3;
+    if ((flags & ~SM_TILED) || op > 2) return fail(IPSR_ERR_INVALID, "small-map convolution: op %d", op | flags);
     if (k < 1 || k > 4 || st < 1 || st > 2 || dil < 1 || pad < 0) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: k%d s%d p%d d%d", k, st, pad, dil);
     if (Ho != (Hf + 2 * pad - dil * (k - 1) - 1) / st + 1 || Wo != (Wf + 2 * pad - dil * (k - 1) - 1) / st + 1)
         return fail(IPSR_ERR_INVALID, "small-map convolution: %dx%d is not the output grid of %dx%d under k%d s%d p%d d%d", Ho, Wo, Hf, Wf, k, st, pad, dil);
@@ -498,6 +672,27 @@ static int sm_plan(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf,
     p->Pp = (p->P + 1) & ~1;
     p->a_floats = p->b_floats = p->m_floats = 0;
     p->nslab = 1; p->per_slab = 0;
+    p->m_tiles = p->nstage = 0;
+    p->tiled = sm_tiled(op, flags, k, p->P);
+    if (p->tiled) {
+        // About 2 workgroups per CU and at least 8 stages per split (the pipeline's prologue).  What a split costs is its partial tile, written
+        // and read back once: FWD's is R x Tp, small next to its reduction, and 32 splits were the best or level with it on every step shape
+        // from 128 to 1024 positions; DATA's is Q x Tp, k*k times the result, and more than 4 splits lost everywhere
+        // (profiles/smallmap_tiled_layers.txt, the sweep).
+        const int M = op == 0 ? p->Q : R, red = op == 0 ? R : p->Q;
+        p->ngroups = (p->P + SMT_BN - 1) / SMT_BN;
+        p->Tp = p->ngroups * SMT_BN;
+        p->m_tiles = (M + SMT_BM - 1) / SMT_BM;
+        p->nstage = red / SMT_BK;
+        const int tiles = p->m_tiles * p->ngroups;
+        int ks = std::max(1, std::min({op == 0 ? 4 : 32, p->nstage / 8, (512 + tiles - 1) / tiles}));
+        if (debug_option(6) > 0) ks = std::min(debug_option(6), p->nstage);          // A/B: a split count of the caller's
+        p->per_slab = (p->nstage + ks - 1) / ks;
+        p->nslab = (p->nstage + p->per_slab - 1) / p->per_slab;
+        p->m_floats = (size_t)p->nslab * M * p->Tp;
+        p->total_bytes = align_up(p->m_floats * 4, 256) + 768;
+        return IPSR_OK;
+    }
     // waves in flight ~ 1024 (one per SIMD) when the slab count allows it: a slab costs its write + its read in the post-pass, so it is
     // capped where that traffic would pass half the weight stream
     const size_t w_bytes = (size_t)R * p->Q * 4;
@@ -547,16 +742,23 @@ int launch_smallmap(int op, const float* a, const float* b2, float* out, int B, 
     // the main kernels address every operand by 32-bit byte offsets below SM_OFF
     const size_t largest = 4 * std::max({(size_t)R * p.Q, (size_t)B * Cq * Hf * Wf, (size_t)R * p.Tp, (size_t)p.Q * p.Tp, (size_t)p.Pp * p.Q});
     if (largest >= SM_OFF) return fail(IPSR_ERR_UNSUPPORTED, "small-map convolution: an operand of %zu bytes (made for < 2 GiB)", largest);
+    op &= 3;
     const bool staged = sm_staged(op, p.P);
     const SmGeo g = {p.P, R, Cq, Ho, Wo, Hf, Wf, k, st_, pad, dil};
+    const unsigned tgrid = (unsigned)(p.m_tiles * p.nslab * p.ngroups);
     if (op == 0) {          // a = in, b2 = W
-        if (staged) sm_to_cn_kernel<<<dim3(cdiv(p.Tp, 256), R), 256, 0, st>>>(a, B, R, Ho * Wo, p.Tp, Bv);
-        const float* in = staged ? Bv : a;
-        const int HW = staged ? 0 : Ho * Wo;
-        const dim3 grid(p.Q / 128, p.nslab, p.ngroups);
-        if (p.nb == 1) sm_data_kernel<1><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
-        else sm_data_kernel<2><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
-        if (int rc = check_launch("sm_data_kernel")) return rc;
+        if (p.tiled) {
+            sm_tiled_kernel<false, 4><<<tgrid, 256, 0, st>>>(b2, a, R, p.Q, p.Tp, p.m_tiles, p.nslab, p.per_slab, p.nstage, g, Mo);
+            if (int rc = check_launch("sm_tiled_kernel")) return rc;
+        } else {
+            if (staged) sm_to_cn_kernel<<<dim3(cdiv(p.Tp, 256), R), 256, 0, st>>>(a, B, R, Ho * Wo, p.Tp, Bv);
+            const float* in = staged ? Bv : a;
+            const int HW = staged ? 0 : Ho * Wo;
+            const dim3 grid(p.Q / 128, p.nslab, p.ngroups);
+            if (p.nb == 1) sm_data_kernel<1><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
+            else sm_data_kernel<2><<<grid, 256, 0, st>>>(b2, in, R, p.Q, p.Tp, p.per_slab, p.P, HW, Mo);
+            if (int rc = check_launch("sm_data_kernel")) return rc;
+        }
         const size_t total = (size_t)B * Cq * Hf * Wf;
         const unsigned cgrid = (unsigned)((total + 255) / 256);
         const size_t slab_bytes = (size_t)p.Q * p.Tp * 4, m_bytes = slab_bytes * p.nslab;
@@ -568,6 +770,14 @@ int launch_smallmap(int op, const float* a, const float* b2, float* out, int B, 
         return check_launch("sm_col2im_kernel");
     }
     const int K = staged ? 0 : k;                                  // the kernels' template argument: 0 = the staged images
+    if (op == 2 && p.tiled) {
+        if (k == 3) sm_tiled_kernel<true, 3><<<tgrid, 256, 0, st>>>(b2, a, R, p.Q, p.Tp, p.m_tiles, p.nslab, p.per_slab, p.nstage, g, Mo);
+        else sm_tiled_kernel<true, 4><<<tgrid, 256, 0, st>>>(b2, a, R, p.Q, p.Tp, p.m_tiles, p.nslab, p.per_slab, p.nstage, g, Mo);
+        if (int rc = check_launch("sm_tiled_kernel")) return rc;
+        const size_t total = (size_t)B * R * Ho * Wo;
+        sm_sum_to_nchw_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Mo, p.nslab, (size_t)R * p.Tp, B, R, Ho * Wo, p.Tp, out);
+        return check_launch("sm_sum_to_nchw_kernel");
+    }
     if (op == 2) {          // a = fine, b2 = W
         if (staged) sm_im2col_cn_kernel<<<dim3(cdiv(p.Tp, 256), p.Q), 256, 0, st>>>(a, B, Cq, Hf, Wf, Ho, Wo, k, st_, pad, dil, p.Tp, Bv);
         const float* x = staged ? Bv : a;

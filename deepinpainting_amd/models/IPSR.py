@@ -112,6 +112,15 @@ class IPSR(BaseModel):
             self.netF = networks.define_D(opt.input_nc, opt.ndf, opt.which_model_netF, opt.n_layers_D, opt.norm,
                                           use_sigmoid, opt.init_type, self.gpu_ids, opt.init_gain)
 
+        # The small-map engine's tiled regime takes MIOpen's forward / input-gradient passes of the 512 / 1024-channel layers on 4x4 .. 16x16
+        # maps (models/hipconv.py `_reached`): the reach travels on the modules, not in a process global, so `hipconv.select` answers other
+        # callers as before.  fp32 activations only (under amp_bf16 the wider reach was measured to lose); 0 = off.
+        reach = 0 if self.amp_bf16 else int(getattr(opt, 'smallmap_reach', 1024))
+        for net in (self.netG, self.netP) + ((self.netD, self.netF) if self.isTrain else ()):
+            for mod in net.modules():
+                if isinstance(mod, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+                    mod.smallmap_reach = reach or None
+
         if not self.isTrain or opt.continue_train:
             print('Loading pre-trained network!')
             self.load_network(self.netG, 'G', opt.which_epoch)

@@ -23,7 +23,12 @@ engine does not take into "miopen": no rule, and no forced mode, can hand an eng
                                   activations: the pixel reduction on the bf16 matrix cores straight from NCHW, two launches
   "smallmap"  csrc/smallmap.hip   the innermost levels: the weight tensor streamed once, 16 bytes per lane straight into MFMA operands —
                                   weight gradients of the 4x4 stride-2 layers up to 256 positions per batch (dW written in its native
-                                  layout), forward and input gradient of the 3x3 / 4x4 layers up to 32 positions
+                                  layout), forward and input gradient of the 3x3 / 4x4 layers up to 32 positions.  For a caller that sets a
+                                  reach (`select(..., reach=)`, the trainer's `opt.smallmap_reach`): forward and input gradient of the
+                                  512 / 1024-channel 4x4 stride-2 layers (pad 1 and the dilated pad 3) on 4x4 .. 16x16 maps (128 .. 1024
+                                  positions per batch) that MIOpen had and loses (`_reach_regime`): the 4x4 maps (128 positions) on the
+                                  streaming kernels, the 8x8 / 16x16 maps as LDS-tiled split-K GEMMs on the weights in place (the engine's
+                                  tiled regime).  The 3x3 layers and every weight gradient of those levels stay on MIOpen.
   "direct"    csrc/conv_gemm.hip  one-launch implicit GEMM, NCHW in/out (every k3/k4, stride 1/2, dilated and transposed
                                   geometry of the nets, forward and backward-data): at parity with MIOpen (~100 TF), used
                                   where it measured >= 7 % faster
@@ -149,15 +154,96 @@ def _mode():
     return _FORCE or _env("IPSR_CONV_ENGINE", "auto")
 
 
-def select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
+def select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False, reach=None):
     """-> the engine for one convolution call.  (Cin, H, W) = the module's input, as in ipsr_conv2d.  Memoised per (mode, shape):
     the rules query the library (workspace probes), ~150 convolution calls per training step ask.
-    bf16: the activations are bf16 tensors — only the Winograd engines read / write those; every other shape takes MIOpen."""
+    bf16: the activations are bf16 tensors — only the Winograd engines read / write those; every other shape takes MIOpen.
+    reach: the caller's reach of the small-map engine's tiled regime in positions per batch (`_reached`); None or 0 = none."""
     key = (0, _FORCE, op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
     eng = _SEL.get(key)
     if eng is None:
         eng = _SEL[key] = _select_any(op, (op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA), B, Cin, H, W, Cout, k, stride, pad, dil), bf16)
-    return eng
+    return _reached("data", key, eng, op, bf16, reach) if reach else eng
+
+
+# The reach.  "smallmap" beyond the chain's own rules — its tiled regime (ops.conv_smallmap(..., tiled=True)) and the streaming kernels on the
+# 4x4 levels — is no rule of the chain: a caller asks for it, per module, by the
+# number of positions per batch up to which it wants MIOpen's passes of the 3x3 / 4x4 layers with >= 256 channels moved to "smallmap" — the
+# trainer stamps `opt.smallmap_reach` on the conv modules of its nets as the attribute `smallmap_reach`, `conv_nobias` reads it.  It is applied
+# to the FINAL answer of the chain and moves "miopen" only: never a pass another engine has, no bf16 activations (the wider reach lost there,
+# `_bf16_direct`), no forced engine, not under IPSR_NO_SMALLMAP=1.  Inside the reach `_reach_regime` says which passes move, and to which of
+# the engine's two regimes.
+
+
+def _reach_regime(kind, op, lay):
+    """-> "stream" | "tiled" | None: the regime of "smallmap" that beats MIOpen on this pass, by the rule of profiles/smallmap_tiled_layers.txt
+    (the engine's median below MIOpen's minimum by more than MIOpen's spread), measured at the step's shapes — 512 / 1024 channels, batch 8
+    and netF's batch 16 — and applied to the position counts between them:
+      forward / input gradient   the k4 layers (stride 2, pad 1 and the dilated pad 3):
+                                 33 .. 128 positions: the streaming kernels (every row, 1.1-2.7x MIOpen; the tiled GEMM has one position
+                                 tile there and nothing to share);  129 .. 256: SM_FWD tiled, SM_DATA streaming;  257 .. 512: tiled
+                                 (1.05-1.4x), except SM_FWD with 1024 weight rows (netP's ConvTranspose2d 1024 -> 512 @8 input gradient:
+                                 91 us against MIOpen's 96.7-102.6, level by the rule);  513 .. 1024: SM_FWD tiled (1.3x).  SM_DATA at
+                                 1024 positions was measured on one pass only, netF's batch-16 input gradient @16 (102 us against
+                                 MIOpen's 170), which the chain gives to "wino_s2": nothing of MIOpen's was measured there, none moves
+                                 k3 stays.  At 512 positions its rows are level or lose.  At 128 positions the streaming kernels win all
+                                 four rows by 6-12 us a call, the smallest gains of the table (~40 us a step) — but MIOpen's 3x3 kernels on
+                                 those maps are what makes a batch-2 step differ between identical runs, and tests/test_gpu_loss_head.py
+                                 takes its tolerance from that difference: without them the step repeats bit for bit and the tolerance
+                                 falls below what the loss heads' own rounding moves netG's gradient by (5.5e-5 of its norm).  They move
+                                 with a change that can re-derive that tolerance.
+      weight gradient            none moves.  The engine has no tiled weight gradient; the streaming kernel loses from 512 positions up (k4 s2
+                                 beyond the chain's own 256 included) and is ahead only on the 3x3 layers at 32 positions (3x) and at 128 with
+                                 <= 512 channels (1.4x).  Those two stay as well: MIOpen's 3x3 weight gradient there is a transform
+                                 algorithm whose own error is several times the bound of an fp32 fma chain (and nonzero where the exact
+                                 value is zero), so the in-step comparison with MIOpen that guards every pass moved here
+                                 (tests/test_gpu_smallmap_reach_step.py) cannot hold for them, though the kernel is within 0.4 of that
+                                 bound against float64."""
+    transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+    g = _smallmap_geometry(lay)
+    pos = g[0] * g[3] * g[4] if g[3] >= 1 and g[4] >= 1 else 0
+    if pos < 1:
+        return None
+    if kind == "wrw":
+        return None
+    if pos <= 32:
+        return None              # the chain's own rule (`_smallmap_data_wins`)
+    if k != 4:
+        return None
+    if pos <= 128:
+        return "stream"
+    fwd = _smallmap_op(op) == ops.SM_FWD
+    if pos <= 256:
+        return "tiled" if fwd else "stream"
+    if pos <= 512:
+        return None if fwd and g[1] > 512 else "tiled"
+    return "tiled" if fwd else None
+
+
+def _reached(kind, key, eng, op, bf16, reach):
+    """-> "smallmap" where the pass of `key` (the memo key of `select` / `select_wrw`), answered `eng` by the chain, is inside `reach`."""
+    if eng != "miopen" or bf16:
+        return eng
+    rkey = key + (int(reach),)
+    hit = _SEL.get(rkey)
+    if hit is None:
+        lay = ((op in (ops.CONVT_FWD, ops.CONVT_BWD_DATA),) if kind == "data" else ()) + key[3 if kind == "data" else 2:-1]
+        transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
+        g = _smallmap_geometry(lay)
+        regime = _reach_regime(kind, op, lay)
+        ok = _mode() == "auto" and _env("IPSR_NO_SMALLMAP", "0") != "1" and regime is not None and k in (3, 4) and min(Cin, Cout) >= 256 \
+            and g[0] * g[3] * g[4] <= int(reach) and bool(_ENGINES["smallmap"].takes(kind, op, lay, False, tiled=regime == "tiled"))
+        hit = _SEL[rkey] = "smallmap" if ok else eng
+    return hit
+
+
+def _via_reach(kind, op, lay, bf16, reach):
+    """Whether this pass runs on "smallmap" only because of the caller's reach, and in the tiled regime: those calls carry `tiled=True`."""
+    if not reach or _reach_regime(kind, op, lay) != "tiled":
+        return False
+    if kind == "data":
+        return select(op, *lay[1:], bf16) != "smallmap" and select(op, *lay[1:], bf16, reach=reach) == "smallmap"
+    return select_wrw(*lay, bf16) != "smallmap" and select_wrw(*lay, bf16, reach=reach) == "smallmap"
 
 
 # Below `select` / `select_wrw` a layer travels as ONE tuple, `lay` = (transposed, B, Cin, H, W, Cout, k, stride, pad, dil): (Cin, H, W) =
@@ -361,14 +447,15 @@ def _is_k4s1(k, stride, pad, dil):
     return k == 4 and stride == 1 and pad == 1 and dil == 1
 
 
-def select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False):
+def select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16=False, reach=None):
     """-> the engine for the weight gradient of one layer (profiles/r02_hipconv_k3_wrw.txt: F(3x3,4x4) is 2.0-2.4x
-    MIOpen from 256 channels up on maps of 16x16..64x64; on larger maps its tile-major transforms lose to MIOpen)."""
+    MIOpen from 256 channels up on maps of 16x16..64x64; on larger maps its tile-major transforms lose to MIOpen).
+    reach: as in `select`."""
     key = (1, _FORCE, transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
     eng = _SEL.get(key)
     if eng is None:
         eng = _SEL[key] = _select_wrw_any((transposed, B, Cin, H, W, Cout, k, stride, pad, dil), bf16)
-    return eng
+    return _reached("wrw", key, eng, None, bf16, reach) if reach else eng
 
 
 def _select_wrw_any(lay, bf16):
@@ -670,10 +757,12 @@ _ENGINES = {
     "thin_mfma": _Engine(
         None, _thin_mfma_wrw, sink=True,
         takes=lambda kind, op, lay, bf16: kind == "wrw" and lay[8:] == (1, 1) and ops.thin_wrw_mfma_supported(*lay[:8])),
-    "smallmap": _Engine(         # the weight gradient takes (coarse, fine)
-        lambda op, inp, w, lay, math, out_dtype, param: ops.conv_smallmap(_smallmap_op(op), inp, w, *_smallmap_geometry(lay)),
-        lambda x, dy, lay, math, sink: ops.conv_smallmap(ops.SM_WRW, *((x, dy) if lay[0] else (dy, x)), *_smallmap_geometry(lay), out=sink),
-        lambda kind, op, lay, bf16: ops.smallmap_supported(_smallmap_op(op) if kind == "data" else ops.SM_WRW, *_smallmap_geometry(lay)),
+    "smallmap": _Engine(         # the weight gradient takes (coarse, fine); tiled: the pass was admitted through the caller's reach
+        lambda op, inp, w, lay, math, out_dtype, param, tiled=False: ops.conv_smallmap(_smallmap_op(op), inp, w, *_smallmap_geometry(lay), tiled=tiled),
+        lambda x, dy, lay, math, sink, tiled=False: ops.conv_smallmap(ops.SM_WRW, *((x, dy) if lay[0] else (dy, x)), *_smallmap_geometry(lay), out=sink,
+                                                                       tiled=tiled),
+        lambda kind, op, lay, bf16, tiled=False: ops.smallmap_supported(_smallmap_op(op) if kind == "data" else ops.SM_WRW, *_smallmap_geometry(lay),
+                                                                         tiled=tiled),
         fp32_copies=True, sink=True),
     "direct": _Engine(
         lambda op, inp, w, lay, math, out_dtype, param: ops.conv2d(op, inp, w, lay[1:5], *lay[5:]),
@@ -690,23 +779,24 @@ _ENGINES = {
 }
 
 
-def _run_data(eng, op, inp, w, lay, math, out_dtype, param=None):
-    """Forward (inp = x) or input gradient (inp = dy) of one layer on a HIP engine; `inp` contiguous."""
+def _run_data(eng, op, inp, w, lay, math, out_dtype, param=None, tiled=False):
+    """Forward (inp = x) or input gradient (inp = dy) of one layer on a HIP engine; `inp` contiguous.  tiled: `_via_reach` ("smallmap" only)."""
     e = _ENGINES[eng]
+    kw = {"tiled": True} if tiled else {}
     if e.fp32_copies:
-        return e.data(op, inp.float(), w, lay, math, torch.float32, param).to(out_dtype)
-    return e.data(op, inp, w, lay, math, out_dtype, param)
+        return e.data(op, inp.float(), w, lay, math, torch.float32, param, **kw).to(out_dtype)
+    return e.data(op, inp, w, lay, math, out_dtype, param, **kw)
 
 
-def _run_wrw(eng, x, dy, w, lay, math):
-    """Weight gradient of one layer on a HIP engine (fp32, the module's layout); x, dy contiguous."""
+def _run_wrw(eng, x, dy, w, lay, math, tiled=False):
+    """Weight gradient of one layer on a HIP engine (fp32, the module's layout); x, dy contiguous.  tiled: as in `_run_data`."""
     e = _ENGINES[eng]
     sink = ipsr_dist.grad_sink_for(w.data_ptr(), w.shape) if e.sink else None
     if e.fp32_copies:
         x, dy = x.float(), dy.float()
     elif e.wrw_x_as_dy and x.dtype != dy.dtype:
         x = x.to(dy.dtype)
-    return e.wrw(x, dy, lay, math, sink)
+    return e.wrw(x, dy, lay, math, sink, **({"tiled": True} if tiled else {}))
 
 
 def _miopen_forward(x, w, transposed, stride, pad, dil):
@@ -728,16 +818,17 @@ class _HipConv(torch.autograd.Function):
     (MIOpen where none is faster).  `math` = the Winograd engines' arithmetic, `act` = dtype of the activation tensors produced."""
 
     @staticmethod
-    def forward(ctx, x, w, lay, eng_fwd, math, act):
+    def forward(ctx, x, w, lay, eng_fwd, math, act, reach=None):
         transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
         xc = x.contiguous()
         if eng_fwd == "miopen":
             y = _miopen_forward(xc, w, transposed, stride, pad, dil)
         else:
-            y = _run_data(eng_fwd, ops.CONVT_FWD if transposed else ops.CONV_FWD, xc, w, lay, math, act)
+            fop = ops.CONVT_FWD if transposed else ops.CONV_FWD
+            y = _run_data(eng_fwd, fop, xc, w, lay, math, act, tiled=eng_fwd == "smallmap" and _via_reach("data", fop, lay, act == torch.bfloat16, reach))
         ctx.save_for_backward(xc, w)
         ctx.lay, ctx.geom = lay, (transposed, k, stride, pad, dil, Cout)
-        ctx.math, ctx.bf16 = math, act == torch.bfloat16
+        ctx.math, ctx.bf16, ctx.reach = math, act == torch.bfloat16, reach
         if _check_hook is not None:
             _check_hook("forward", eng_fwd, ctx.geom, (xc, w), y)
         return y
@@ -745,7 +836,7 @@ class _HipConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        lay, math, bf16 = ctx.lay, ctx.math, ctx.bf16
+        lay, math, bf16, reach = ctx.lay, ctx.math, ctx.bf16, ctx.reach
         transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
         dy = dy.contiguous()
         if bf16 and dy.dtype != torch.bfloat16:
@@ -753,24 +844,24 @@ class _HipConv(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             op = ops.CONVT_BWD_DATA if transposed else ops.CONV_BWD_DATA
-            eng = select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
+            eng = select(op, B, Cin, H, W, Cout, k, stride, pad, dil, bf16, reach=reach)
             if eng == "miopen":
                 dx = _miopen_backward(dy, x, w, transposed, stride, pad, dil, [True, False, False])[0]
                 if dx.dtype != x.dtype:
                     dx = dx.to(x.dtype)
             else:
-                dx = _run_data(eng, op, dy, w, lay, math, x.dtype)
+                dx = _run_data(eng, op, dy, w, lay, math, x.dtype, tiled=eng == "smallmap" and _via_reach("data", op, lay, bf16, reach))
             if _check_hook is not None:
                 _check_hook("input_grad", eng, ctx.geom, (dy, x, w), dx)
         if ctx.needs_input_grad[1]:
-            weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16)
+            weng = select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16, reach=reach)
             if weng == "miopen":
                 dw = _miopen_backward(dy, x, w, transposed, stride, pad, dil, [False, True, False])[1]
             else:
-                dw = _run_wrw(weng, x, dy, w, lay, math)
+                dw = _run_wrw(weng, x, dy, w, lay, math, tiled=weng == "smallmap" and _via_reach("wrw", None, lay, bf16, reach))
             if _check_hook is not None:
                 _check_hook("weight_grad", weng, ctx.geom, (dy, x, w), dw)
-        return dx, dw, None, None, None, None
+        return dx, dw, None, None, None, None, None
 
 
 def _geometry(m):
@@ -804,14 +895,14 @@ def conv_math(bf16):
     return _MATH["bf16" if bf16 else "fp32"]
 
 
-def _engines_of(lay, bf16, dx=True, dw=True):
+def _engines_of(lay, bf16, dx=True, dw=True, reach=None):
     """-> the engines of (forward, input gradient, weight gradient) of one layer; a gradient nobody needs (dx / dw False) is not asked for
-    and reads "miopen"."""
+    and reads "miopen".  reach: the module's `smallmap_reach` (`select`)."""
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
     fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if transposed else (ops.CONV_FWD, ops.CONV_BWD_DATA)
-    return (select(fop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16),
-            select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if dx else "miopen",
-            select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16) if dw else "miopen")
+    return (select(fop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16, reach=reach),
+            select(bop, B, Cin, H, W, Cout, k, stride, pad, dil, bf16, reach=reach) if dx else "miopen",
+            select_wrw(transposed, B, Cin, H, W, Cout, k, stride, pad, dil, bf16, reach=reach) if dw else "miopen")
 
 
 def any_engine(m, x):
@@ -820,7 +911,7 @@ def any_engine(m, x):
     lb = _layer_of(m, x, m.weight)
     if lb is None:
         return False
-    return _engines_of(*lb) != ("miopen",) * 3
+    return _engines_of(*lb, reach=getattr(m, "smallmap_reach", None)) != ("miopen",) * 3
 
 
 def conv_nobias(m, x, weight=None):
@@ -834,13 +925,16 @@ def conv_nobias(m, x, weight=None):
         act = torch.bfloat16 if bf16 else torch.float32
         math = _MATH["bf16" if bf16 else "fp32"]
         grad = torch.is_grad_enabled()
-        engs = _engines_of(lay, bf16, grad and x.requires_grad, grad and w.requires_grad)
+        reach = getattr(m, "smallmap_reach", None)       # stamped by the trainer (models/IPSR.py); a bare module has none
+        engs = _engines_of(lay, bf16, grad and x.requires_grad, grad and w.requires_grad, reach)
         if grad and (x.requires_grad or w.requires_grad):
             # the backward may use a HIP engine even where the forward stays on MIOpen
             if engs != ("miopen",) * 3:
-                return _HipConv.apply(x, w, lay, engs[0], math, act)
+                return _HipConv.apply(x, w, lay, engs[0], math, act, reach)
         elif engs[0] != "miopen":
-            return _run_data(engs[0], ops.CONVT_FWD if lay[0] else ops.CONV_FWD, x.contiguous(), w.detach(), lay, math, act, param=w)
+            fop = ops.CONVT_FWD if lay[0] else ops.CONV_FWD
+            return _run_data(engs[0], fop, x.contiguous(), w.detach(), lay, math, act, param=w,
+                             tiled=engs[0] == "smallmap" and _via_reach("data", fop, lay, bf16, reach))
     if isinstance(m, nn.ConvTranspose2d):
         return F.conv_transpose2d(x, w, None, m.stride, m.padding, m.output_padding, m.groups, m.dilation)
     return F.conv2d(x, w, None, m.stride, m.padding, m.dilation, m.groups)

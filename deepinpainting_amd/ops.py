@@ -1052,15 +1052,19 @@ def conv_thin_wrw_mfma(transposed, x, dy, k, stride, out=None):
 SM_DATA, SM_WRW, SM_FWD = 0, 1, 2
 
 
-def smallmap_supported(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil):
-    return _lib.lib().ipsr_conv_smallmap_workspace_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil) > 0
+SM_TILED = 16           # flag bit of `op` (IPSR_SMALLMAP_TILED): the LDS-tiled GEMMs for SM_DATA / SM_FWD above 32 positions
 
 
-def conv_smallmap(op, a, b, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, out=None):
+def smallmap_supported(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, tiled=False):
+    return _lib.lib().ipsr_conv_smallmap_workspace_bytes(op | (SM_TILED if tiled else 0), B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil) > 0
+
+
+def conv_smallmap(op, a, b, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, out=None, tiled=False):
     """Small-map convolutions with the weight tensor [R,Cq,k,k] as the GEMM operand in place (ipsr_conv_smallmap):
     op SM_DATA: a = in [B,R,Ho,Wo], b = weight -> [B,Cq,Hf,Wf] (Conv2d backward-data / ConvTranspose2d forward);
     op SM_WRW:  a = coarse [B,R,Ho,Wo], b = fine [B,Cq,Hf,Wf] -> dW [R,Cq,k,k];
-    op SM_FWD:  a = fine [B,Cq,Hf,Wf], b = weight -> [B,R,Ho,Wo] (Conv2d forward / ConvTranspose2d backward-data)."""
+    op SM_FWD:  a = fine [B,Cq,Hf,Wf], b = weight -> [B,R,Ho,Wo] (Conv2d forward / ConvTranspose2d backward-data).
+    tiled: the call carries SM_TILED (the regime for 33 .. 1024 positions; the weight gradient has none and runs as without it)."""
     a = _req(a, torch.float32, "operand a")
     b = _req(b, torch.float32, "operand b")
     coarse, fine, wsh = (B, R, Ho, Wo), (B, Cq, Hf, Wf), (R, Cq, k, k)
@@ -1069,6 +1073,7 @@ def conv_smallmap(op, a, b, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil, out=N
         raise RuntimeError("conv_smallmap op %d: operands %s / %s do not match %s / %s" % (op, tuple(a.shape), tuple(b.shape), want[0], want[1]))
     out = _result(out, want[2], torch.float32, a.device, "conv_smallmap")
     L = _lib.lib()
+    op |= SM_TILED if tiled else 0
     ws = _probed_workspace(L, L.ipsr_conv_smallmap_workspace_bytes(op, B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil), a.device,
                            "ipsr_conv_smallmap: op %d R=%d Cq=%d %dx%d -> %dx%d k%d s%d p%d d%d", (op, R, Cq, Hf, Wf, Ho, Wo, k, stride, pad, dil))
     _lib.check(L.ipsr_conv_smallmap(op, a.data_ptr(), b.data_ptr(), out.data_ptr(), B, R, Cq, Ho, Wo, Hf, Wf, k, stride, pad, dil,

@@ -59,5 +59,7 @@ class Option(object):
         self.lr_policy = 'lambda'
         self.lr_decay_iters = 50
         self.isTrain = True
+        self.smallmap_reach = 1024     # not the reference's: positions per batch up to which the small-map engine's tiled GEMMs take MIOpen's
+                                       # passes of the 512 / 1024-channel layers (models/hipconv.py `select(..., reach=)`); 0 = off
         for k, v in overrides.items():
             setattr(self, k, v)

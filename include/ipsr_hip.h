@@ -323,7 +323,13 @@ int ipsr_conv4x4s2_winograd(int mode, const float* a, const float* b, float* out
  *   op 0  a = in [B,R,Ho,Wo]       b = weight        out = [B,Cq,Hf,Wf]    Conv2d backward-data / ConvTranspose2d forward
  *   op 1  a = coarse [B,R,Ho,Wo]   b = fine [B,Cq,Hf,Wf]   out = dW [R,Cq,k,k]   weight gradient of either module
  *   op 2  a = fine [B,Cq,Hf,Wf]    b = weight        out = [B,R,Ho,Wo]     Conv2d forward / ConvTranspose2d backward-data
- * R % 32 == 0, Cq*k*k % 128 == 0, B*Ho*Wo <= 1024. */
+ * R % 32 == 0, Cq*k*k % 128 == 0, B*Ho*Wo <= 1024.
+ * op | IPSR_SMALLMAP_TILED asks for the tiled regime: ops 0 and 2 with k = 3 or 4 and more than 32 positions run as an LDS-tiled
+ * split-K GEMM (128 x 128 tiles, the weights still read in place) instead of the streaming kernels, which win below that; the
+ * sums are ordered and repeat bit for bit, but are not the streaming kernels' bits.  Every other call (op 1, other k, <= 32
+ * positions) runs as without the flag.  The workspace size depends on the flag: ask with the `op` the call will pass.  Added without an
+ * ABI version change (15): a library without the flag refuses such an `op` (IPSR_ERR_INVALID, workspace 0). */
+#define IPSR_SMALLMAP_TILED 16
 size_t ipsr_conv_smallmap_workspace_bytes(int op, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf, int k, int stride, int pad, int dil);
 int ipsr_conv_smallmap(int op, const float* a, const float* b, float* out, int B, int R, int Cq, int Ho, int Wo, int Hf, int Wf,
                        int k, int stride, int pad, int dil, void* ws, size_t ws_bytes, void* stream);

@@ -17,6 +17,14 @@ divided by `--inner`.  The spread is max - min over the rounds.  A row counts as
 minimum by more than the parent's spread, as slower when it is above the parent's maximum by more than that spread, else level.
 
     python tools/ab_smallmap.py --parent-lib _ab/parent/deepinpainting_amd/libipsr_hip.so > smallmap_stream_layers.txt
+
+`--tiled`: the table of the tiled regime instead (profiles/smallmap_tiled_layers.txt) — the 512 / 1024-channel layers of netG, netP and
+netF on 2x2 .. 16x16 maps that MIOpen has without a reach (TILED_LAYERS), every pass: MIOpen through torch (its layout transposes and
+fills included) against the streaming kernels (`tiled=False`) and the tiled regime (`tiled=True`; the weight gradient has none), the
+three alternating within every round.  A pass moves when the median of the engine's best form is below MIOpen's minimum by more than
+MIOpen's spread.
+
+    python tools/ab_smallmap.py --tiled > smallmap_tiled_layers.txt
 """
 import argparse
 import collections
@@ -107,6 +115,81 @@ def timed(fn, iters, inner):
     return statistics.median(ts)
 
 
+# (net, module, Cin, Cout, (k, stride, pad, dil), input extent, batch)
+TILED_LAYERS = (
+    ("netP/F", "conv", 512, 512, (4, 2, 1, 1), 16, 8), ("netP/F", "conv", 512, 512, (4, 2, 1, 1), 8, 8),
+    ("netF", "conv", 512, 512, (4, 2, 1, 1), 16, 16), ("netF", "conv", 512, 512, (4, 2, 1, 1), 8, 16),
+    ("netP", "convT", 1024, 512, (4, 2, 1, 1), 4, 8), ("netP", "convT", 1024, 512, (4, 2, 1, 1), 8, 8),
+    ("netG", "conv", 512, 512, (4, 2, 3, 2), 16, 8), ("netG", "conv", 512, 512, (4, 2, 3, 2), 8, 8),
+    ("netG", "conv", 512, 512, (3, 1, 1, 1), 8, 8), ("netG", "conv", 512, 512, (3, 1, 1, 1), 4, 8), ("netG", "conv", 512, 512, (3, 1, 1, 1), 2, 8),
+    ("netG", "convT", 1024, 512, (3, 1, 1, 1), 2, 8), ("netG", "convT", 1024, 512, (3, 1, 1, 1), 4, 8), ("netG", "convT", 1024, 512, (3, 1, 1, 1), 8, 8),
+    ("netG", "convT", 512, 512, (4, 2, 1, 1), 4, 8), ("netG", "convT", 512, 512, (4, 2, 1, 1), 8, 8),
+)
+
+
+def tiled_table(a):
+    import torch.nn.functional as F
+    print("# the small-map engine against MIOpen through torch, device us per call: median of %d alternating rounds (each the median of %d event "
+          "pairs around %d calls), fp32" % (a.rounds, a.iters, a.inner))
+    print("# pass: fwd / dx / dw of the module; base = the dispatcher's answer without a reach; P = positions; verdict: the engine's better form "
+          "against MIOpen (moves: its median < MIOpen's minimum - MIOpen's spread)")
+    print("%-7s %-28s %-4s %-9s %5s %9s %9s %9s %9s %9s %9s %9s  %s" % ("net", "layer", "pass", "base", "P", "miopen", "m.min", "m.spread", "stream",
+                                                                        "s.spread", "tiled", "t.spread", "verdict"))
+    tot = collections.Counter()
+    for net, kind, Cin, Cout, geom, H, B in TILED_LAYERS:
+        tr = kind == "convT"
+        k, stride, pad, dil = geom
+        lay = (tr, B, Cin, H, H, Cout) + geom
+        g = hipconv._smallmap_geometry(lay)
+        x = torch.randn(B, Cin, H, H, device="cuda")
+        w = torch.randn((Cin, Cout, k, k) if tr else (Cout, Cin, k, k), device="cuda") * 0.05
+        y = hipconv._miopen_forward(x, w, tr, stride, pad, dil)
+        dy = torch.randn_like(y)
+        for name in ("fwd", "dx", "dw"):
+            if name == "dw":
+                base = hipconv.select_wrw(*lay)
+                sm_op, ops_ab = ops.SM_WRW, ((x, dy) if tr else (dy, x))
+                mi = lambda: hipconv._miopen_backward(dy, x, w, tr, stride, pad, dil, [False, True, False])
+            else:
+                op = {("fwd", False): ops.CONV_FWD, ("dx", False): ops.CONV_BWD_DATA, ("fwd", True): ops.CONVT_FWD, ("dx", True): ops.CONVT_BWD_DATA}[name, tr]
+                base = hipconv.select(op, *lay[1:])
+                sm_op, ops_ab = hipconv._smallmap_op(op), ((x, w) if name == "fwd" else (dy, w))
+                mi = (lambda: hipconv._miopen_forward(x, w, tr, stride, pad, dil)) if name == "fwd" else \
+                    (lambda: hipconv._miopen_backward(dy, x, w, tr, stride, pad, dil, [True, False, False]))
+            variants = {"miopen": mi}
+            if ops.smallmap_supported(sm_op, *g):
+                variants["stream"] = lambda: ops.conv_smallmap(sm_op, *ops_ab, *g)
+            if name != "dw" and ops.smallmap_supported(sm_op, *g, tiled=True):
+                variants["tiled"] = lambda: ops.conv_smallmap(sm_op, *ops_ab, *g, tiled=True)
+            t = {v: [] for v in variants}
+            for _ in range(a.rounds):
+                for v, fn in variants.items():
+                    t[v].append(timed(fn, a.iters, a.inner))
+            sweep = ""
+            if "tiled" in variants and a.sweep:          # the tiled regime under a forced number of splits (debug option 6)
+                L = _lib.lib()
+                try:
+                    for ks in (int(v) for v in a.sweep.split(",")):
+                        _lib.check(L.ipsr_debug_set_option(6, ks), "ipsr_debug_set_option")
+                        sweep += "  ks%d=%.2f" % (ks, timed(variants["tiled"], a.iters, a.inner))
+                finally:
+                    L.ipsr_debug_set_option(6, 0)
+            med = {v: statistics.median(r) for v, r in t.items()}
+            spread = {v: max(r) - min(r) for v, r in t.items()}
+            ours = min((v for v in med if v != "miopen"), key=med.get, default=None)
+            verdict = "-"
+            if ours is not None:
+                verdict = ("moves (%s)" % ours) if med[ours] < min(t["miopen"]) - spread["miopen"] else \
+                    "loses" if med[ours] > max(t["miopen"]) + spread["miopen"] else "level"
+            f = lambda d, v: "%.2f" % d[v] if v in d else "-"
+            print("%-7s %-28s %-4s %-9s %5d %9s %9.2f %9s %9s %9s %9s %9s  %s" % (
+                net, "%s %d->%d k%d s%d p%d d%d @%d B%d" % ((kind, Cin, Cout) + geom + (H, B)), name, base, g[0] * g[3] * g[4], f(med, "miopen"),
+                min(t["miopen"]), f(spread, "miopen"), f(med, "stream"), f(spread, "stream"), f(med, "tiled"), f(spread, "tiled"), verdict + sweep), flush=True)
+            for v in med:
+                tot[v] += med[v]
+    print("# sum of the medians over the rows that have the column, us: " + ", ".join("%s %.1f" % (v, tot[v]) for v in tot))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -114,7 +197,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--parent-lib", default=None, help="libipsr_hip.so of the parent commit, built in another directory")
+    ap.add_argument("--tiled", action="store_true", help="the table of the tiled regime against MIOpen and the streaming kernels")
+    ap.add_argument("--sweep", default="", help="with --tiled: also time the tiled regime under these split counts, e.g. 8,16,32")
     a = ap.parse_args()
+    if a.tiled:
+        return tiled_table(a)
     L = _lib.lib()
     parent = load_parent(a.parent_lib) if a.parent_lib else None
     shapes = step_shapes(a.batch)
