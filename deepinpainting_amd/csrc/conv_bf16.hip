@@ -48,7 +48,7 @@ constexpr int CB_K = 128, CB_P = 256, CB_C = 16, CB_THREADS = 512, CB_MAXTAP = 9
 constexpr int cb_tr_max(int ptile) { return ptile == 256 ? 6 : 10; }
 constexpr int cb_xj(int ptile) { return ptile == 256 ? 3 : 5; }
 constexpr int CB_LDS_MAX = 160 * 1024;
-// LDS plan (per geometry, cb_finish): A[2] | T[2] | raw[2 or 1].  A stage = ntap x 4 KB ([tap][c group][128 k][8 c] bf16), raw = [16 c][raw
+// LDS plan (per geometry, data_geometry): A[2] | T[2] | raw[2 or 1].  A stage = ntap x 4 KB ([tap][c group][128 k][8 c] bf16), raw = [16 c][raw
 // rows][input width] bf16, T = [planes][2 c groups][positions][8 c].  k3 at W <= 128: 2 x (36 + 16 + 16.3) KB; stride 2: 2 x (32 + 20 + 20.4);
 // k3 at W = 256 (one image row per tile): 2 x 36 + 2 x 24.3 + ONE raw buffer of 24 KB — the transposition then follows the stage's
 // multiplications instead of running beside them (`raw1`).
@@ -407,18 +407,7 @@ __global__ void __launch_bounds__(256) cb_slab_reduce_kernel(const float* __rest
     }
 }
 
-static int cb_lane_grid(int Hl, int Wl, int ptile, CbGeom* g, const char* who)
-{
-    if (Wl != 16 && Wl != 32 && Wl != 64 && Wl != 128 && Wl != 256) return fail(IPSR_ERR_UNSUPPORTED, "%s: grid width %d (16 .. 256, a power of two)", who, Wl);
-    const int R = ptile / Wl;
-    g->ptile = ptile;
-    if (Hl % R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", who, Hl, R);
-    g->Hl = Hl; g->Wl = Wl; g->R = R;
-    g->wshift = cb_wshift(Wl);
-    return IPSR_OK;
-}
-
-// The reduction cut of the three data-pass planners: fewer than 128 workgroups and >= 8 channel blocks -> up to four runs of whole channel
+// The reduction cut of the data-pass planner (data_geometry): fewer than 128 workgroups and >= 8 channel blocks -> up to four runs of whole channel
 // blocks (`nsub` stages each).  wgs = workgroups without a cut -> the number of runs and the stages of a run.
 static void cb_cut_reduction(int wgs, int nblocks, int nsub, int* nsplit, int* sps)
 {
@@ -427,96 +416,6 @@ static void cb_cut_reduction(int wgs, int nblocks, int nsub, int* nsplit, int* s
     const int bps = (nblocks + ns - 1) / ns;              // channel blocks per run
     *nsplit = (nblocks + bps - 1) / bps;
     *sps = bps * nsub;
-}
-
-static int cb_finish(CbGeom* g, const char* who)
-{
-    g->NPOS = g->NR * g->PW;
-    g->kt = g->K <= 64 ? 64 : CB_K;
-    g->ktiles = (g->K + g->kt - 1) / g->kt;
-    g->ptiles = g->B * (g->Hl / g->R);
-    g->nstage = (g->C / CB_C) * g->nsub;
-    // Small maps leave the chip idle (a 16x16 map is ONE pixel tile per image: 64 workgroups at 512 produced channels and batch 16): the
-    // reduction is cut into up to four runs of whole channel blocks, each run a workgroup of its own writing an fp32 partial.
-    cb_cut_reduction(g->ktiles * g->nphase * g->ptiles, g->C / CB_C, g->nsub, &g->nsplit, &g->sps);
-    const int planes = g->nsub;                               // F2C keeps the two column phases
-    g->a_bytes = g->ntap * 2 * g->kt * 16;
-    g->t_bytes = (int)align_up((size_t)planes * 2 * g->NPOS * 16, 256);
-    g->raw_bytes = (int)align_up((size_t)CB_C * g->NR * g->Win * 2, 1024);
-    g->raw1 = 2 * (g->a_bytes + g->t_bytes + g->raw_bytes) > CB_LDS_MAX;
-    if (2 * (g->a_bytes + g->t_bytes) + (g->raw1 ? 1 : 2) * g->raw_bytes > CB_LDS_MAX || 4 * g->NR * (g->Win / 16) > 32 * cb_tr_max(g->ptile) ||
-        CB_C * g->NR * (g->Win / 8) > cb_xj(g->ptile) * CB_THREADS)
-        return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, g->Win);
-    return IPSR_OK;
-}
-
-// k3 s1 p1
-static int cb_geometry_p(int B, int C, int K, int H, int W, int ptile, CbGeom* g)
-{
-    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 direct conv: %d reduction channels are not a multiple of %d", C, CB_C);
-    if (int rc = cb_lane_grid(H, W, ptile, g, "bf16 direct conv")) return rc;
-    g->B = B; g->C = C; g->K = K; g->Hin = H; g->Win = W; g->Hout = H; g->Wout = W;
-    g->NR = g->R + 2; g->PW = W + 2;
-    g->ymul = 1; g->rowstep = 1; g->yoff[0] = -1; g->yoff[1] = -1;
-    g->nsub = 1; g->nphase = 1; g->ntap = 9;
-    for (int t = 0; t < 9; ++t) g->tapoff[0][t] = g->tapoff[1][t] = (t / 3) * g->PW + (t % 3);
-    return cb_finish(g, "bf16 direct conv");
-}
-
-// <= 64 produced channels: the 512-pixel tile where the map and the LDS plan allow it, else 256
-static int cb_geometry(int B, int C, int K, int H, int W, CbGeom* g)
-{
-    if (K <= 64 && cb_geometry_p(B, C, K, H, W, 2 * CB_P, g) == IPSR_OK) return IPSR_OK;
-    return cb_geometry_p(B, C, K, H, W, CB_P, g);
-}
-
-static int cb_geometry_s2_p(int form, int B, int C, int K, int nh, int nw, int ptile, CbGeom* g);
-// k4 s2 p1: fine [.,Cf,2nh,2nw], coarse [.,Kc,nh,nw].  form 0: fine -> coarse (C = Cf reduced, K = Kc produced); 1: coarse -> fine
-static int cb_geometry_s2(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
-{
-    if (K <= 64 && cb_geometry_s2_p(form, B, C, K, nh, nw, 2 * CB_P, g) == IPSR_OK) return IPSR_OK;
-    return cb_geometry_s2_p(form, B, C, K, nh, nw, CB_P, g);
-}
-
-// the two k4 s2 p1 forms on a lane grid already set (cb_lane_grid): tensors, halo rows, row maps, tap offsets
-static void cb_s2_form(int form, int nh, int nw, CbGeom* g)
-{
-    if (form == 0) {
-        g->Hin = 2 * nh; g->Win = 2 * nw; g->Hout = nh; g->Wout = nw;
-        g->NR = g->R + 1; g->PW = nw + 1;
-        g->ymul = 2; g->rowstep = 2; g->yoff[0] = 0; g->yoff[1] = -1;       // sub-stage e = input row parity: rows 2 (y0 + i) + e - 2 e
-        g->nsub = 2; g->nphase = 1; g->ntap = 8;
-        g->NPOS = g->NR * g->PW;
-        // tap t = ri * 4 + s of sub-stage e: r = e ? {0, 2}[ri] : {1, 3}[ri]; input row 2 oy - 1 + r = 2 (oy + drow - (e ? 1 : 0)) + e  ->  drow = ri
-        // column 2 ox - 1 + s: s even -> odd column (plane 1, j = ox - 1 + s / 2, stored at j + 1), s odd -> even column (plane 0, j = ox + s / 2)
-        for (int e = 0; e < 2; ++e)
-            for (int t = 0; t < 8; ++t) {
-                const int ri = t >> 2, sx = t & 3, ex = (sx & 1) ? 0 : 1, dcol = sx >> 1;
-                g->tapoff[e][t] = ex * 2 * g->NPOS + ri * g->PW + dcol;
-            }
-    } else {
-        g->Hin = nh; g->Win = nw; g->Hout = 2 * nh; g->Wout = 2 * nw;
-        g->NR = g->R + 2; g->PW = nw + 2;
-        g->ymul = 1; g->rowstep = 1; g->yoff[0] = -1; g->yoff[1] = -1;
-        g->nsub = 1; g->nphase = 2; g->ntap = 8;
-        g->NPOS = g->NR * g->PW;
-        // row phase ey' (workgroup), column phase ex' (accumulator set), taps (ai, bi): fine row 2 i + ey' takes coarse rows
-        // ey' = 0: {i (r = 1), i - 1 (r = 3)};  ey' = 1: {i + 1 (r = 0), i (r = 2)}  ->  raw row (i - y0) + 1 + d, d = ey' - ai
-        for (int ey = 0; ey < 2; ++ey)
-            for (int t = 0; t < 8; ++t) {
-                const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
-                g->tapoff[ey][t] = (1 + ey - ai) * g->PW + (1 + ex - bi);
-            }
-    }
-}
-
-static int cb_geometry_s2_p(int form, int B, int C, int K, int nh, int nw, int ptile, CbGeom* g)
-{
-    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "bf16 direct 4x4 stride-2 conv: %d reduction channels are not a multiple of %d", C, CB_C);
-    if (int rc = cb_lane_grid(nh, nw, ptile, g, "bf16 direct 4x4 stride-2 conv")) return rc;
-    g->B = B; g->C = C; g->K = K;
-    cb_s2_form(form, nh, nw, g);
-    return cb_finish(g, "bf16 direct 4x4 stride-2 conv");
 }
 
 // fp32 partials of a split reduction, behind the packed weights
@@ -551,7 +450,7 @@ static void* cb_run_dst(int nsplit, uint4* Wp, size_t pack_bytes, void* out)
     return nsplit > 1 ? reinterpret_cast<unsigned char*>(Wp) + align_up(pack_bytes, 256) : out;
 }
 
-// The tail of the three data launchers, behind the launch of `kernel` into cb_run_dst(): under a cut the ordered add of the partials `dst`
+// The tail of launch_data, behind the launch of `kernel` into cb_run_dst(): under a cut the ordered add of the partials `dst`
 // into the n elements of `out` (a multiple of 4: the output width is), the profile stop, the launch check.
 static int cb_launch_tail(const char* kernel, int nsplit, const void* dst, size_t n, void* out, int out_bf16, hipStream_t st, double work, double work2)
 {
@@ -562,112 +461,6 @@ static int cb_launch_tail(const char* kernel, int nsplit, const void* dst, size_
     }
     profile_mark_stop(st, 4, work, work2);
     return check_launch(nsplit > 1 ? "cb_split_reduce_kernel" : kernel);
-}
-
-size_t conv_bf16_ws_bytes(int B, int C, int K, int H, int W)
-{
-    CbGeom g;
-    if (cb_geometry(B, C, K, H, W, &g) != IPSR_OK) return 0;
-    return 256 + (size_t)g.ktiles * g.nstage * 9 * 2 * g.kt * 16 + cb_partial_bytes(g);
-}
-
-size_t conv_bf16_s2_ws_bytes(int form, int B, int C, int K, int nh, int nw)
-{
-    CbGeom g;
-    if (cb_geometry_s2(form, B, C, K, nh, nw, &g) != IPSR_OK) return 0;
-    return 256 + (size_t)g.ktiles * g.nphase * g.nstage * 8 * 2 * g.kt * 16 + cb_partial_bytes(g);
-}
-
-template <int MODE, int KT, int P, typename TOUT>
-static int cb_launch_kernel(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
-{
-    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), "conv_bf16_kernel")) return rc;
-    conv_bf16_kernel<MODE, KT, P, TOUT><<<grid, CB_THREADS, smem, st>>>(static_cast<const unsigned short*>(in), Wp, zero_page, g, static_cast<TOUT*>(out));
-    return IPSR_OK;
-}
-
-// the kernel instance of a plan: tile (g.kt x g.ptile) and output type
-template <int MODE, typename TOUT>
-static int cb_launch_tile(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
-{
-    if (g.kt == 64 && g.ptile == 2 * CB_P) return cb_launch_kernel<MODE, 64, 2 * CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
-    if (g.kt == 64) return cb_launch_kernel<MODE, 64, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
-    return cb_launch_kernel<MODE, 128, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
-}
-
-template <int MODE>
-static int cb_launch(const CbGeom& g, CbPack pk, const void* in, const float* w, void* out, long sc, long sk, int out_bf16, void* ws,
-                     hipStream_t st, double taps_per_out, int pack_valid = 0)
-{
-    uint4* zero_page = static_cast<uint4*>(ws);
-    uint4* Wp = zero_page + 16;
-    pk.kt = g.kt;
-    if (!pack_valid) {
-        cb_pack_weights_kernel<false><<<dim3(cdiv(g.ktiles * g.kt, 256), g.C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(w, g.C, g.K, sc, sk, pk, Wp, zero_page, 0);
-        if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
-    }
-    const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
-    const size_t smem = 2 * (size_t)(g.a_bytes + g.t_bytes) + (size_t)(g.raw1 ? 1 : 2) * g.raw_bytes;
-    void* dst = cb_run_dst(g.nsplit, Wp, (size_t)g.ktiles * g.nphase * g.nstage * pk.ntap * 2 * g.kt * 16, out);
-    profile_mark_start(st, 4);
-    if (int rc = (out_bf16 && g.nsplit == 1) ? cb_launch_tile<MODE, bf16_t>(g, in, Wp, zero_page, dst, grid, smem, st)
-                                             : cb_launch_tile<MODE, float>(g, in, Wp, zero_page, dst, grid, smem, st)) return rc;
-    const double outs = (double)g.B * g.Hout * g.Wout;
-    return cb_launch_tail("conv_bf16_kernel", g.nsplit, dst, (size_t)g.B * g.K * g.Hout * g.Wout, out, out_bf16, st,
-                          2.0 * taps_per_out * g.C * (double)(g.ktiles * g.kt) * outs, 2.0 * taps_per_out * g.C * (double)g.K * outs);
-}
-
-// in [B,C,H,W] bf16, weight fp32 with element (c, k, tap) at w[c*sc + k*sk + tap] (taps flipped when `flip`), out [B,K,H,W] bf16 / fp32
-int launch_conv_bf16(const void* in, const float* w, void* out, int B, int C, int K, int H, int W, long sc, long sk, int flip, int out_bf16,
-                     void* ws, size_t ws_bytes, hipStream_t st, int pack_valid = 0)
-{
-    CbGeom g;
-    if (int rc = cb_geometry(B, C, K, H, W, &g)) return rc;
-    const size_t need = conv_bf16_ws_bytes(B, C, K, H, W);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "bf16 direct conv: workspace %zu < %zu", ws_bytes, need);
-    CbPack pk{};
-    pk.ntap = 9; pk.nsub = 1; pk.nphase = 1;
-    for (int t = 0; t < 9; ++t) pk.srctap[0][0][t] = flip ? 8 - t : t;
-    return cb_launch<CB_S1>(g, pk, in, w, out, sc, sk, out_bf16, ws, st, 9.0, pack_valid);
-}
-
-// source taps of the packed images of the two k4 s2 p1 forms: srctap[phase][sub][t] = r * 4 + s of the module's 4x4 kernel
-static CbPack cb_s2_pack(int form)
-{
-    CbPack pk{};
-    pk.ntap = 8;
-    if (form == 0) {
-        pk.nsub = 2; pk.nphase = 1;
-        for (int e = 0; e < 2; ++e)
-            for (int t = 0; t < 8; ++t) {
-                const int ri = t >> 2, sx = t & 3, rr = e ? 2 * ri : 2 * ri + 1;
-                pk.srctap[0][e][t] = rr * 4 + sx;
-            }
-        return pk;
-    }
-    pk.nsub = 1; pk.nphase = 2;
-    for (int ey = 0; ey < 2; ++ey)
-        for (int t = 0; t < 8; ++t) {
-            const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
-            const int rr = ey == 0 ? (ai ? 3 : 1) : (ai ? 2 : 0), ss = ex == 0 ? (bi ? 3 : 1) : (bi ? 2 : 0);
-            pk.srctap[ey][0][t] = rr * 4 + ss;
-        }
-    return pk;
-}
-
-// k4 s2 p1.  weight [Kc][Cf][4][4]: element (coarse channel kc, fine channel cf, r, s) at w[kc * skc + cf * scf + r * 4 + s].
-// form 0 (fine -> coarse): in = fine [B,Cf,2nh,2nw], out = coarse [B,Kc,nh,nw].   form 1 (coarse -> fine): in = coarse, out = fine.
-int launch_conv_bf16_s2(int form, const void* in, const float* w, void* out, int B, int Kc, int Cf, int nh, int nw, long skc, long scf,
-                        int out_bf16, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    CbGeom g;
-    const int C = form == 0 ? Cf : Kc, K = form == 0 ? Kc : Cf;
-    if (int rc = cb_geometry_s2(form, B, C, K, nh, nw, &g)) return rc;
-    const size_t need = conv_bf16_s2_ws_bytes(form, B, C, K, nh, nw);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "bf16 direct 4x4 stride-2 conv: workspace %zu < %zu", ws_bytes, need);
-    const CbPack pk = cb_s2_pack(form);
-    if (form == 0) return cb_launch<CB_F2C>(g, pk, in, w, out, scf, skc, out_bf16, ws, st, 16.0);
-    return cb_launch<CB_C2F>(g, pk, in, w, out, skc, scf, out_bf16, ws, st, 4.0);
 }
 
 // =====================================================================================================================================
@@ -690,6 +483,9 @@ int launch_conv_bf16_s2(int form, const void* in, const float* w, void* out, int
 // Supported: W in {16 .. 256} a power of two, H a multiple of 256 / W, reduction channels a multiple of 16.
 constexpr int CX_K = 64, CX_A_BYTES = 2 * 9 * 2 * CX_K * 16;
 
+// This kernel's arguments: the fields of the shared plan (CbGeom, data_geometry) that it reads, packed by launch_data.  On the whole CbGeom
+// the fields are no longer contiguous (a longer scalar prologue, same registers) and 7 of the step's 12 k3 passes measured 1.4 - 2.9 % slower,
+// the three builds in one process on the same buffers (profiles/conv_bf16_data_refactor_ab.txt).
 struct CxGeom {
     int B, C, K, H, W, wshift;
     int R, NR, PW, NPOS;        // image rows per tile, rows with halo, padded width, positions per (plane, c group)
@@ -847,68 +643,9 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_kernel(const float*
         }
 }
 
-static int cx_geometry(int B, int C, int K, int H, int W, CxGeom* g)
-{
-    const char* who = "split-bf16 direct conv";
-    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d reduction channels are not a multiple of %d", who, C, CB_C);
-    if (W != 16 && W != 32 && W != 64 && W != 128 && W != 256) return fail(IPSR_ERR_UNSUPPORTED, "%s: width %d (16 .. 256, a power of two)", who, W);
-    g->R = CB_P / W;
-    if (H % g->R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", who, H, g->R);
-    g->B = B; g->C = C; g->K = K; g->H = H; g->W = W;
-    g->wshift = cb_wshift(W);
-    g->NR = g->R + 2; g->PW = W + 2; g->NPOS = g->NR * g->PW;
-    for (int t = 0; t < 9; ++t) g->tapoff[t] = (t / 3) * g->PW + (t % 3);
-    g->ktiles = (K + CX_K - 1) / CX_K;
-    g->ptiles = B * (H / g->R);
-    g->nstage = C / CB_C;
-    cb_cut_reduction(g->ktiles * g->ptiles, g->nstage, 1, &g->nsplit, &g->sps);
-    g->t_bytes = (int)align_up((size_t)2 * 2 * g->NPOS * 16, 256);
-    if (2 * CX_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (W / 4) > CB_THREADS)
-        return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, W);
-    return IPSR_OK;
-}
-
-static size_t cx_pack_bytes(const CxGeom& g) { return (size_t)g.ktiles * g.nstage * 9 * 2 * CX_K * 16; }      // one plane
-
-// zero page | hi plane | lo plane | fp32 partials of a split reduction
-size_t conv_bf16x3_ws_bytes(int B, int C, int K, int H, int W)
-{
-    CxGeom g;
-    if (cx_geometry(B, C, K, H, W, &g) != IPSR_OK) return 0;
-    return 256 + align_up(2 * cx_pack_bytes(g), 256) + (g.nsplit > 1 ? align_up((size_t)g.nsplit * B * K * H * W * sizeof(float), 256) : 0);
-}
-
-// in [B,C,H,W] fp32, weight as in launch_conv_bf16, out [B,K,H,W] fp32
-int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C, int K, int H, int W, long sc, long sk, int flip,
-                       void* ws, size_t ws_bytes, hipStream_t st, int pack_valid)
-{
-    CxGeom g;
-    if (int rc = cx_geometry(B, C, K, H, W, &g)) return rc;
-    const size_t need = conv_bf16x3_ws_bytes(B, C, K, H, W);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 direct conv: workspace %zu < %zu", ws_bytes, need);
-    uint4* zero_page = static_cast<uint4*>(ws);
-    uint4* Wp = zero_page + 16;
-    const size_t lo_plane = cx_pack_bytes(g) / 16;
-    if (!pack_valid) {
-        CbPack pk{};
-        pk.ntap = 9; pk.nsub = 1; pk.nphase = 1; pk.kt = CX_K;
-        for (int t = 0; t < 9; ++t) pk.srctap[0][0][t] = flip ? 8 - t : t;
-        cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * CX_K, 256), C / 8, 9), 256, 0, st>>>(w, C, K, sc, sk, pk, Wp, zero_page, lo_plane);
-        if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
-    }
-    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel), "conv_bf16x3_kernel")) return rc;
-    float* dst = static_cast<float*>(cb_run_dst(g.nsplit, Wp, 2 * cx_pack_bytes(g), out));
-    const unsigned grid = (unsigned)(g.ktiles * g.ptiles * g.nsplit);
-    const double outs = (double)B * H * W;
-    profile_mark_start(st, 4);
-    conv_bf16x3_kernel<<<grid, CB_THREADS, 2 * CX_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, dst);
-    return cb_launch_tail("conv_bf16x3_kernel", g.nsplit, dst, (size_t)B * K * H * W, out, 0, st,
-                          3.0 * 2.0 * 9.0 * C * (double)(g.ktiles * CX_K) * outs, 2.0 * 9.0 * C * (double)K * outs);
-}
-
 // =====================================================================================================================================
 // The k4 s2 p1 forms (F2C / C2F above) on FP32 tensors with the same split-bf16 operands ("direct_bf16x3_s2", ipsr_conv4x4s2_bf16x3):
-// conv_bf16x3_kernel's structure on the geometry, tap maps and source-tap tables of the bf16 stride-2 kernel (cb_s2_form, cb_s2_pack).
+// conv_bf16x3_kernel's structure on the geometry, tap maps and source-tap tables of the bf16 stride-2 kernel (data_form, data_pack).
 //   * weights: cb_pack_weights_kernel<true> writes the hi and lo planes of Wp[kt][phase][cb][sub][t][cg][64 k][8 c]; a stage's A tile is
 //     2 x 16 KB by LDS-DMA, double-buffered;
 //   * activations: global -> registers -> split -> T, one item (c group, input row, 4 floats) per thread, 8 channels each.
@@ -921,7 +658,7 @@ int launch_conv_bf16x3(const float* in, const float* w, float* out, int B, int C
 //     zeros every stage (conv_bf16x3_kernel's "they keep T's zeros" does not hold here); only the halo columns keep their initial zeros.
 // Workgroup = 512 threads = 8 waves (1 x 8), tile 64 channels x 256 lane-grid pixels, a wave owns 64 x 32 (C2F: twice, the column parities):
 // per tap 4 A + 2 B fragment reads for 6 MFMAs.  LDS: A[2] = 2 x 32 KB | T <= 48.5 KB (F2C at nw = 128: 8 planes x 3 rows x 129 positions).
-// Small maps: the reduction cut of cb_finish (cb_cut_reduction), fp32 partials behind the packed planes, cb_split_reduce_kernel<float>.
+// Small maps: the reduction cut of data_geometry (cb_cut_reduction), fp32 partials behind the packed planes, cb_split_reduce_kernel<float>.
 // Supported: coarse width nw in {16, 32, 64, 128}, nh a multiple of 256 / nw, reduction channels a multiple of 16.
 //
 // The DILATED forms (k4 s2 p3 d2, netG's down convolution; modes 4 / 5 of ipsr_conv4x4s2_bf16x3).  y(oy, ox) reads x(2 oy - 3 + 2 r, 2 ox - 3 + 2 s):
@@ -1126,104 +863,210 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
     }
 }
 
-// the two dilated forms (k4 s2 p3 d2) on a lane grid already set: form 4 fine -> coarse, 5 coarse -> fine (conv_bf16x3_s2_kernel's header)
-static void c2_dil_form(int form, int nh, int nw, CbGeom* g)
+// ---- the host side of the four data-pass kernels: one planner, one byte count, one launcher over DATA_KINDS x DATA_FORMS ----
+// What the kernels differ in as far as the host is concerned: one row per kernel, read by data_geometry, data_ws_bytes and launch_data.
+// All four run on the one plan CbGeom (conv_bf16x3_kernel on the part of it that it reads, CxGeom).
+// `split` decides the rest of the plan: bf16 tensors (conv_bf16_kernel) get the tile 128 x 256, or 64 produced channels x 512 / 256 pixels when
+// K <= 64, LDS = A[2] | T[2] | raw[2 or 1], and a stage has to fit the transposition and DMA loops (cb_tr_max, cb_xj); fp32 tensors on split-bf16
+// operands get the tile 64 x 256, two packed planes (hi | lo), LDS = A[2] | T (hi | lo), and one activation item (c group, row, 4 floats) per thread.
+enum { DATA_K3 = 0, DATA_S2 = 1, DATA_K3_SPLIT = 2, DATA_S2_SPLIT = 3 };
+struct DataKind {
+    bool split;
+    int wmax;                           // widest lane grid
+    const char *who, *width_fmt;        // the messages, as each planner has always worded them
+    const char* kernel;                 // the name check_launch reports
+};
+constexpr DataKind DATA_KINDS[4] = {
+    {false, 256, "bf16 direct conv", "%s: grid width %d (16 .. 256, a power of two)", "conv_bf16_kernel"},
+    {false, 256, "bf16 direct 4x4 stride-2 conv", "%s: grid width %d (16 .. 256, a power of two)", "conv_bf16_kernel"},
+    {true, 256, "split-bf16 direct conv", "%s: width %d (16 .. 256, a power of two)", "conv_bf16x3_kernel"},
+    {true, 128, "split-bf16 direct 4x4 stride-2 conv", "%s: coarse width %d (16 .. 128, a power of two)", "conv_bf16x3_s2_kernel"},
+};
+
+// What a form (CB_S1 .. CB_DC2F) fixes on any grid: which tensor is the fine one (2 Hl x 2 Wl), sub-stages per channel block, row phases, taps per
+// stage, column-phase planes of T, and for the profile marks the taps per counted pixel (`coarse`: per lane-grid pixel whichever tensor is written).
+struct DataForm { bool fine_in, fine_out; int nsub, nphase, ntap, planes; double taps; bool coarse; };
+constexpr DataForm DATA_FORMS[5] = {
+    {false, false, 1, 1, 9, 1,  9.0, false},        // S1
+    {true,  false, 2, 1, 8, 2, 16.0, false},        // F2C: T keeps the two column phases
+    {false, true,  1, 2, 8, 1,  4.0, false},        // C2F
+    {true,  false, 2, 1, 8, 1, 16.0, true},         // DF2C
+    {false, true,  2, 1, 8, 1, 16.0, true},         // DC2F
+};
+
+// A form on a lane grid already set (Hl x Wl, R rows per tile): tensors, halo rows, row map, tap offsets
+static void data_form(int form, CbGeom* g)
 {
-    const bool f2c = form == 4;
-    g->Hin = f2c ? 2 * nh : nh; g->Win = f2c ? 2 * nw : nw;
-    g->Hout = f2c ? nh : 2 * nh; g->Wout = f2c ? nw : 2 * nw;
-    g->NR = g->R + 1; g->PW = nw + 3;
-    g->ymul = f2c ? 2 : 1; g->rowstep = g->ymul;
-    g->yoff[0] = f2c ? -3 : 1; g->yoff[1] = f2c ? 1 : -1;      // sub-stage e = weight rows {2 e, 2 e + 1}
-    g->nsub = 2; g->nphase = 1; g->ntap = 8;
+    const DataForm& f = DATA_FORMS[form];
+    const int nh = g->Hl, nw = g->Wl;
+    g->Hin = f.fine_in ? 2 * nh : nh; g->Win = f.fine_in ? 2 * nw : nw;
+    g->Hout = f.fine_out ? 2 * nh : nh; g->Wout = f.fine_out ? 2 * nw : nw;
+    g->nsub = f.nsub; g->nphase = f.nphase; g->ntap = f.ntap;
+    g->ymul = g->rowstep = f.fine_in ? 2 : 1;
+    if (form == CB_S1 || form == CB_C2F) {
+        g->NR = g->R + 2; g->PW = nw + 2; g->yoff[0] = g->yoff[1] = -1;
+    } else if (form == CB_F2C) {
+        g->NR = g->R + 1; g->PW = nw + 1; g->yoff[0] = 0; g->yoff[1] = -1;                  // sub-stage e = input row parity: rows 2 (y0 + i) + e - 2 e
+    } else {
+        g->NR = g->R + 1; g->PW = nw + 3;                                                   // sub-stage e = weight rows {2 e, 2 e + 1}
+        g->yoff[0] = form == CB_DF2C ? -3 : 1; g->yoff[1] = form == CB_DF2C ? 1 : -1;
+    }
     g->NPOS = g->NR * g->PW;
+    // tapoff[e][t], e = sub-stage (F2C, dilated) or row phase (C2F):
+    //   F2C   tap t = ri * 4 + s of sub-stage e: r = e ? {0, 2}[ri] : {1, 3}[ri]; input row 2 oy - 1 + r = 2 (oy + drow - (e ? 1 : 0)) + e  ->  drow = ri;
+    //         column 2 ox - 1 + s: s even -> odd column (plane 1, j = ox - 1 + s / 2, stored at j + 1), s odd -> even column (plane 0, j = ox + s / 2)
+    //   C2F   row phase ey' (workgroup), column phase ex' (accumulator set), taps (ai, bi): fine row 2 i + ey' takes coarse rows
+    //         ey' = 0: {i (r = 1), i - 1 (r = 3)};  ey' = 1: {i + 1 (r = 0), i (r = 2)}  ->  raw row (i - y0) + 1 + d, d = ey' - ai
+    //   dilated  tap (ri, s): conv_bf16x3_s2_kernel's header
     for (int e = 0; e < 2; ++e)
-        for (int t = 0; t < 8; ++t) {
+        for (int t = 0; t < f.ntap; ++t) {
             const int ri = t >> 2, sx = t & 3;
-            g->tapoff[e][t] = f2c ? ri * g->PW + sx : (1 - ri) * g->PW + (3 - sx);
+            const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
+            g->tapoff[e][t] = form == CB_S1 ? (t / 3) * g->PW + (t % 3)
+                            : form == CB_F2C ? ((sx & 1) ? 0 : 1) * 2 * g->NPOS + ri * g->PW + (sx >> 1)
+                            : form == CB_C2F ? (1 + e - ai) * g->PW + (1 + ex - bi)
+                            : form == CB_DF2C ? ri * g->PW + sx : (1 - ri) * g->PW + (3 - sx);
         }
 }
 
-// source taps of the dilated forms' packed images: sub-stage e, tap t = ri * 4 + s -> weight row 2 e + ri, column s (both forms)
-static CbPack c2_dil_pack()
+// Source taps of a form's packed image: srctap[phase][sub][t] = the tap of the module's kernel (S1: 3x3, flipped when `flip`; else r * 4 + s of its 4x4)
+static CbPack data_pack(int form, int flip, int kt)
 {
+    const DataForm& f = DATA_FORMS[form];
     CbPack pk{};
-    pk.ntap = 8; pk.nsub = 2; pk.nphase = 1;
-    for (int e = 0; e < 2; ++e)
-        for (int t = 0; t < 8; ++t) pk.srctap[0][e][t] = (2 * e + (t >> 2)) * 4 + (t & 3);
+    pk.ntap = f.ntap; pk.nsub = f.nsub; pk.nphase = f.nphase; pk.kt = kt;
+    for (int phase = 0; phase < f.nphase; ++phase)
+        for (int sub = 0; sub < f.nsub; ++sub)
+            for (int t = 0; t < f.ntap; ++t) {
+                const int ri = t >> 2, sx = t & 3;
+                const int ex = t >> 2, ai = (t >> 1) & 1, bi = t & 1;
+                pk.srctap[phase][sub][t] = form == CB_S1 ? (flip ? 8 - t : t)
+                                         : form == CB_F2C ? (sub ? 2 * ri : 2 * ri + 1) * 4 + sx
+                                         : form == CB_C2F ? (1 - phase + 2 * ai) * 4 + (1 - ex + 2 * bi)
+                                         : (2 * sub + ri) * 4 + sx;                         // both dilated forms: weight row 2 e + ri, column s
+            }
     return pk;
 }
 
-// form 0: fine -> coarse (C = Cf reduced, K = Kc produced); 1: coarse -> fine; 4 / 5: the same directions of the dilated layer.
-// The limits, before any launch.
-static int c2_geometry(int form, int B, int C, int K, int nh, int nw, CbGeom* g)
+static size_t data_lds_bytes(const DataKind& k, const CbGeom& g)
 {
-    const char* who = "split-bf16 direct 4x4 stride-2 conv";
-    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d reduction channels are not a multiple of %d", who, C, CB_C);
-    if (nw != 16 && nw != 32 && nw != 64 && nw != 128) return fail(IPSR_ERR_UNSUPPORTED, "%s: coarse width %d (16 .. 128, a power of two)", who, nw);
-    if (int rc = cb_lane_grid(nh, nw, CB_P, g, who)) return rc;
-    g->B = B; g->C = C; g->K = K;
-    if (form & 4) c2_dil_form(form, nh, nw, g);
-    else cb_s2_form(form, nh, nw, g);
-    const int planes = form == 0 ? 2 : 1;                      // column-phase planes of T (F2C only)
-    g->kt = C2_K;
-    g->ktiles = (K + C2_K - 1) / C2_K;
-    g->ptiles = B * (g->Hl / g->R);
-    g->nstage = (C / CB_C) * g->nsub;
-    cb_cut_reduction(g->ktiles * g->nphase * g->ptiles, C / CB_C, g->nsub, &g->nsplit, &g->sps);
-    g->a_bytes = C2_A_BYTES;
-    g->t_bytes = (int)align_up((size_t)2 * planes * 2 * g->NPOS * 16, 256);      // hi | lo, each [column phase][c group][positions]
-    g->raw_bytes = 0; g->raw1 = 0;
-    if (2 * C2_A_BYTES + g->t_bytes > CB_LDS_MAX || 2 * g->NR * (g->Win / 4) > CB_THREADS)
-        return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", who, g->NR, g->Win);
+    return 2 * (size_t)g.a_bytes + (k.split ? 1 : 2) * (size_t)g.t_bytes + (g.raw1 ? 1 : 2) * (size_t)g.raw_bytes;
+}
+
+// The limits, before any launch.  C reduction channels -> K produced; Hl x Wl = the lane grid (S1: the image; k4 s2: the coarse grid nh x nw, the fine
+// tensor is [., ., 2nh, 2nw]).
+static int data_geometry(int kind, int form, int B, int C, int K, int Hl, int Wl, CbGeom* g)
+{
+    const DataKind& k = DATA_KINDS[kind];
+    if (C % CB_C != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d reduction channels are not a multiple of %d", k.who, C, CB_C);
+    if (Wl != 16 && Wl != 32 && Wl != 64 && Wl != 128 && Wl != k.wmax) return fail(IPSR_ERR_UNSUPPORTED, k.width_fmt, k.who, Wl);
+    g->B = B; g->C = C; g->K = K; g->Hl = Hl; g->Wl = Wl;
+    g->wshift = cb_wshift(Wl);
+    g->kt = k.split || K <= 64 ? 64 : CB_K;
+    g->ktiles = (K + g->kt - 1) / g->kt;
+    const auto tile = [&](int ptile) -> int {
+        g->ptile = ptile; g->R = ptile / Wl;
+        if (Hl % g->R != 0) return fail(IPSR_ERR_UNSUPPORTED, "%s: %d rows are not a multiple of the %d rows of a tile", k.who, Hl, g->R);
+        data_form(form, g);
+        g->ptiles = B * (Hl / g->R);
+        g->nstage = (C / CB_C) * g->nsub;
+        // Small maps leave the chip idle (a 16x16 map is ONE pixel tile per image: 64 workgroups at 512 produced channels and batch 16): the
+        // reduction is cut into up to four runs of whole channel blocks, each run a workgroup of its own writing an fp32 partial.
+        cb_cut_reduction(g->ktiles * g->nphase * g->ptiles, C / CB_C, g->nsub, &g->nsplit, &g->sps);
+        const int nplane = k.split ? 2 : 1;                       // hi | lo
+        g->a_bytes = nplane * g->ntap * 2 * g->kt * 16;
+        g->t_bytes = (int)align_up((size_t)nplane * DATA_FORMS[form].planes * 2 * g->NPOS * 16, 256);
+        g->raw_bytes = k.split ? 0 : (int)align_up((size_t)CB_C * g->NR * g->Win * 2, 1024);
+        g->raw1 = !k.split && 2 * (g->a_bytes + g->t_bytes + g->raw_bytes) > CB_LDS_MAX;
+        const bool fits = k.split ? 2 * g->NR * (g->Win / 4) <= CB_THREADS
+                                  : 4 * g->NR * (g->Win / 16) <= 32 * cb_tr_max(ptile) && CB_C * g->NR * (g->Win / 8) <= cb_xj(ptile) * CB_THREADS;
+        if (data_lds_bytes(k, *g) > (size_t)CB_LDS_MAX || !fits)
+            return fail(IPSR_ERR_UNSUPPORTED, "%s: a tile of %d rows x %d does not fit the LDS plan", k.who, g->NR, g->Win);
+        return IPSR_OK;
+    };
+    // bf16, <= 64 produced channels: the 512-pixel tile where the map and the LDS plan allow it, else 256
+    if (!k.split && K <= 64 && tile(2 * CB_P) == IPSR_OK) return IPSR_OK;
+    return tile(CB_P);
+}
+
+static size_t data_pack_bytes(const CbGeom& g) { return (size_t)g.ktiles * g.nphase * g.nstage * g.ntap * 2 * g.kt * 16; }      // one plane
+
+// zero page | packed weights (split: hi plane | lo plane) | fp32 partials of a split reduction
+static size_t data_ws_bytes(const DataKind& k, const CbGeom& g) { return 256 + align_up((k.split ? 2 : 1) * data_pack_bytes(g), 256) + cb_partial_bytes(g); }
+
+// the workspace queries: 0 for a refused shape
+static size_t data_ws_query(int kind, int form, int B, int C, int K, int Hl, int Wl)
+{
+    CbGeom g;
+    return data_geometry(kind, form, B, C, K, Hl, Wl, &g) == IPSR_OK ? data_ws_bytes(DATA_KINDS[kind], g) : 0;
+}
+
+template <int MODE, int KT, int P, typename TOUT>
+static int cb_launch_kernel(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
+{
+    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), "conv_bf16_kernel")) return rc;
+    conv_bf16_kernel<MODE, KT, P, TOUT><<<grid, CB_THREADS, smem, st>>>(static_cast<const unsigned short*>(in), Wp, zero_page, g, static_cast<TOUT*>(out));
     return IPSR_OK;
 }
 
-static size_t c2_pack_bytes(const CbGeom& g) { return (size_t)g.ktiles * g.nphase * g.nstage * 8 * 2 * C2_K * 16; }      // one plane
-
-// zero page | hi plane | lo plane | fp32 partials of a split reduction
-size_t conv_bf16x3_s2_ws_bytes(int form, int B, int C, int K, int nh, int nw)
+// the bf16 kernel instance of a plan: tile (g.kt x g.ptile) and output type
+template <int MODE, typename TOUT>
+static int cb_launch_tile(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
 {
-    CbGeom g;
-    if (c2_geometry(form, B, C, K, nh, nw, &g) != IPSR_OK) return 0;
-    return 256 + align_up(2 * c2_pack_bytes(g), 256) + cb_partial_bytes(g);
+    if (g.kt == 64 && g.ptile == 2 * CB_P) return cb_launch_kernel<MODE, 64, 2 * CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
+    if (g.kt == 64) return cb_launch_kernel<MODE, 64, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
+    return cb_launch_kernel<MODE, 128, CB_P, TOUT>(g, in, Wp, zero_page, out, grid, smem, st);
 }
 
-template <int MODE>
-static int c2_launch_kernel(const CbGeom& g, const float* in, const uint4* Wp, size_t lo_plane, float* out, hipStream_t st)
+// in [B,C,Hin,Win] (bf16; the split kinds: fp32), weight fp32 with element (c, k, tap) at w[c*sc + k*sk + tap] (S1: taps flipped when `flip`),
+// out [B,K,Hout,Wout] bf16 / fp32 (the split kinds: fp32).  pack_valid (S1 only): ws already holds this weight's packed image.
+template <int KIND, int FORM>
+static int launch_data(const void* in, const float* w, void* out, int B, int C, int K, int Hl, int Wl, long sc, long sk, int flip, int out_bf16,
+                       void* ws, size_t ws_bytes, hipStream_t st, int pack_valid = 0)
 {
-    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<MODE>), "conv_bf16x3_s2_kernel")) return rc;
-    const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
-    conv_bf16x3_s2_kernel<MODE><<<grid, CB_THREADS, 2 * C2_A_BYTES + g.t_bytes, st>>>(in, Wp, lo_plane, g, out);
-    return IPSR_OK;
-}
-
-// weight and forms 0 / 1 as in launch_conv_bf16_s2, forms 4 / 5 the dilated layer (pad 3, dilation 2) in the same directions; in / out fp32
-int launch_conv_bf16x3_s2(int form, const float* in, const float* w, float* out, int B, int Kc, int Cf, int nh, int nw, long skc, long scf,
-                          void* ws, size_t ws_bytes, hipStream_t st)
-{
+    constexpr DataKind k = DATA_KINDS[KIND];
+    constexpr DataForm f = DATA_FORMS[FORM];
+    static_assert((FORM == CB_S1) == (KIND == DATA_K3 || KIND == DATA_K3_SPLIT) && (FORM < CB_DF2C || KIND == DATA_S2_SPLIT), "no kernel of this kind has the form");
     CbGeom g;
-    const bool f2c = !(form & 1);
-    const int C = f2c ? Cf : Kc, K = f2c ? Kc : Cf;
-    if (int rc = c2_geometry(form, B, C, K, nh, nw, &g)) return rc;
-    const size_t need = conv_bf16x3_s2_ws_bytes(form, B, C, K, nh, nw);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "split-bf16 direct 4x4 stride-2 conv: workspace %zu < %zu", ws_bytes, need);
+    if (int rc = data_geometry(KIND, FORM, B, C, K, Hl, Wl, &g)) return rc;
+    const size_t need = data_ws_bytes(k, g);
+    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "%s: workspace %zu < %zu", k.who, ws_bytes, need);
     uint4* zero_page = static_cast<uint4*>(ws);
     uint4* Wp = zero_page + 16;
-    const size_t lo_plane = c2_pack_bytes(g) / 16;
-    CbPack pk = (form & 4) ? c2_dil_pack() : cb_s2_pack(form);
-    pk.kt = C2_K;
-    cb_pack_weights_kernel<true><<<dim3(cdiv(g.ktiles * C2_K, 256), C / 8, pk.ntap * pk.nsub * pk.nphase), 256, 0, st>>>(
-        w, C, K, f2c ? scf : skc, f2c ? skc : scf, pk, Wp, zero_page, lo_plane);
-    if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
-    float* dst = static_cast<float*>(cb_run_dst(g.nsplit, Wp, 2 * c2_pack_bytes(g), out));
-    // the dilated forms: 16 taps per coarse pixel whichever tensor is written
-    const double outs = (form & 4) ? (double)B * g.Hl * g.Wl : (double)B * g.Hout * g.Wout, taps = form == 1 ? 4.0 : 16.0;
+    const size_t pack = data_pack_bytes(g), lo_plane = k.split ? pack / 16 : 0;
+    if (!pack_valid) {
+        cb_pack_weights_kernel<k.split><<<dim3(cdiv(g.ktiles * g.kt, 256), C / 8, f.ntap * f.nsub * f.nphase), 256, 0, st>>>(
+            w, C, K, sc, sk, data_pack(FORM, flip, g.kt), Wp, zero_page, lo_plane);
+        if (int rc = check_launch("cb_pack_weights_kernel")) return rc;
+    }
+    const unsigned grid = (unsigned)(g.ktiles * g.nphase * g.ptiles * g.nsplit);
+    const size_t smem = data_lds_bytes(k, g);
+    void* dst = cb_run_dst(g.nsplit, Wp, (k.split ? 2 : 1) * pack, out);
     profile_mark_start(st, 4);
-    if (int rc = form == 0 ? c2_launch_kernel<CB_F2C>(g, in, Wp, lo_plane, dst, st) : form == 1 ? c2_launch_kernel<CB_C2F>(g, in, Wp, lo_plane, dst, st)
-               : form == 4 ? c2_launch_kernel<CB_DF2C>(g, in, Wp, lo_plane, dst, st) : c2_launch_kernel<CB_DC2F>(g, in, Wp, lo_plane, dst, st)) return rc;
-    return cb_launch_tail("conv_bf16x3_s2_kernel", g.nsplit, dst, (size_t)B * K * g.Hout * g.Wout, out, 0, st,
-                          3.0 * 2.0 * taps * C * (double)(g.ktiles * C2_K) * outs, 2.0 * taps * C * (double)K * outs);
+    if constexpr (!k.split) {
+        if (int rc = (out_bf16 && g.nsplit == 1) ? cb_launch_tile<FORM, bf16_t>(g, in, Wp, zero_page, dst, grid, smem, st)
+                                                 : cb_launch_tile<FORM, float>(g, in, Wp, zero_page, dst, grid, smem, st)) return rc;
+    } else if constexpr (KIND == DATA_K3_SPLIT) {
+        if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel), k.kernel)) return rc;
+        CxGeom x{B, C, K, Hl, Wl, g.wshift, g.R, g.NR, g.PW, g.NPOS, g.ktiles, g.ptiles, g.nstage, g.nsplit, g.sps, g.t_bytes, {}};
+        for (int t = 0; t < 9; ++t) x.tapoff[t] = g.tapoff[0][t];
+        conv_bf16x3_kernel<<<grid, CB_THREADS, smem, st>>>(static_cast<const float*>(in), Wp, lo_plane, x, static_cast<float*>(dst));
+    } else {
+        if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<FORM>), k.kernel)) return rc;
+        conv_bf16x3_s2_kernel<FORM><<<grid, CB_THREADS, smem, st>>>(static_cast<const float*>(in), Wp, lo_plane, g, static_cast<float*>(dst));
+    }
+    const double outs = f.coarse ? (double)B * Hl * Wl : (double)B * g.Hout * g.Wout;
+    return cb_launch_tail(k.kernel, g.nsplit, dst, (size_t)B * K * g.Hout * g.Wout, out, out_bf16, st,
+                          (k.split ? 3.0 : 1.0) * 2.0 * f.taps * C * (double)(g.ktiles * g.kt) * outs, 2.0 * f.taps * C * (double)K * outs);
+}
+
+// The k4 s2 entries' operands: weight [Kc][Cf][4][4], fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw]; a form that reads the fine tensor reduces Cf
+template <int KIND, int FORM>
+static int launch_data_s2(const void* in, const float* w, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16, void* ws, size_t ws_bytes, hipStream_t st)
+{
+    constexpr bool f2c = DATA_FORMS[FORM].fine_in;
+    const long skc = (long)Cf * 16, scf = 16;
+    return launch_data<KIND, FORM>(in, w, out, B, f2c ? Cf : Kc, f2c ? Kc : Cf, nh, nw, f2c ? scf : skc, f2c ? skc : scf, 0, out_bf16, ws, ws_bytes, st);
 }
 
 // =====================================================================================================================================
@@ -2280,8 +2123,9 @@ static int cb_misaligned(const char* who, const char* what, std::initializer_lis
     return IPSR_OK;
 }
 
-// modes of ipsr_conv4x4s2_bf16x3: bit 0 = coarse -> fine, bit 2 = pad 3, dilation 2
+// modes of the k4 s2 entries: bit 0 = coarse -> fine, bit 2 = pad 3, dilation 2 (ipsr_conv4x4s2_bf16x3 only) -> the form
 static bool c2_mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 4 || mode == 5; }
+static int c2_form(int mode) { return ((mode & 4) ? CB_DF2C : CB_F2C) + (mode & 1); }
 
 extern "C" {
 
@@ -2289,14 +2133,14 @@ size_t ipsr_conv3x3_bf16_workspace_bytes(int op, int B, int Cin, int H, int W, i
 {
     if (!cb_dims_ok(op >= 0 && op <= 3, {B, Cin, Cout, H, W})) return 0;
     const bool fwd = op == 0 || op == 2;
-    return conv_bf16_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
+    return data_ws_query(DATA_K3, CB_S1, B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
 
 size_t ipsr_conv3x3_bf16x3_workspace_bytes(int op, int B, int Cin, int H, int W, int Cout)
 {
     if (cb_bad_dims("ipsr_conv3x3_bf16x3_workspace_bytes", op >= 0 && op <= 3, {B, Cin, Cout, H, W})) return 0;
     const bool fwd = op == 0 || op == 2;
-    return conv_bf16x3_ws_bytes(B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
+    return data_ws_query(DATA_K3_SPLIT, CB_S1, B, fwd ? Cin : Cout, fwd ? Cout : Cin, H, W);
 }
 
 int ipsr_conv3x3_bf16(int op, const void* in, const float* weight, void* out, int B, int Cin, int H, int W, int Cout, int io,
@@ -2319,15 +2163,14 @@ int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* 
     const long wc = (long)(op < 2 ? Cin : Cout) * 9;           // stride of the weight's first dimension
     const long sc = (op == 0 || op == 3) ? 9 : wc, sk = (op == 0 || op == 3) ? wc : 9;
     const int flip = op == 1 || op == 2;
-    if (io == 2)
-        return launch_conv_bf16x3(static_cast<const float*>(in), weight, static_cast<float*>(out), B, C, K, H, W, sc, sk, flip, ws, ws_bytes, st, pack_valid);
-    return launch_conv_bf16(in, weight, out, B, C, K, H, W, sc, sk, flip, io, ws, ws_bytes, st, pack_valid);
+    if (io == 2) return launch_data<DATA_K3_SPLIT, CB_S1>(in, weight, out, B, C, K, H, W, sc, sk, flip, 0, ws, ws_bytes, st, pack_valid);
+    return launch_data<DATA_K3, CB_S1>(in, weight, out, B, C, K, H, W, sc, sk, flip, io, ws, ws_bytes, st, pack_valid);
 }
 
 size_t ipsr_conv4x4s2_bf16_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
     if (!cb_dims_ok(mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return 0;
-    return conv_bf16_s2_ws_bytes(mode, B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
+    return data_ws_query(DATA_S2, c2_form(mode), B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
@@ -2337,13 +2180,14 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
     if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16", mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return rc;
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16", "in / out / workspace", {ws, in, out})) return rc;
     // weight [Kc][Cf][4][4] in both modules (Conv2d: [Cout][Cin], ConvTranspose2d: [Cin][Cout]), as in ipsr_conv4x4s2_winograd
-    return launch_conv_bf16_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    const auto launch = mode == 0 ? launch_data_s2<DATA_S2, CB_F2C> : launch_data_s2<DATA_S2, CB_C2F>;
+    return launch(in, weight, out, B, Kc, Cf, nh, nw, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16x3_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
 {
     if (cb_bad_dims("ipsr_conv4x4s2_bf16x3_workspace_bytes", c2_mode_ok(mode), {B, Kc, Cf, nh, nw})) return 0;
-    return conv_bf16x3_s2_ws_bytes(mode, B, (mode & 1) ? Kc : Cf, (mode & 1) ? Cf : Kc, nh, nw);
+    return data_ws_query(DATA_S2_SPLIT, c2_form(mode), B, (mode & 1) ? Kc : Cf, (mode & 1) ? Cf : Kc, nh, nw);
 }
 
 int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float* out, int B, int Kc, int Cf, int nh, int nw,
@@ -2353,7 +2197,9 @@ int ipsr_conv4x4s2_bf16x3(int mode, const float* in, const float* weight, float*
     if (!cb_dims_ok(c2_mode_ok(mode), {B, Kc, Cf, nh, nw}))
         return fail(IPSR_ERR_INVALID, "ipsr_conv4x4s2_bf16x3: bad argument (mode %d: 0 fine -> coarse, 1 coarse -> fine; 4, 5 the same with pad 3, dilation 2)", mode);
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3", "in / out / workspace", {ws, in, out})) return rc;
-    return launch_conv_bf16x3_s2(mode, in, weight, out, B, Kc, Cf, nh, nw, (long)Cf * 16, 16, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    const auto launch = mode == 0 ? launch_data_s2<DATA_S2_SPLIT, CB_F2C> : mode == 1 ? launch_data_s2<DATA_S2_SPLIT, CB_C2F>
+                      : mode == 4 ? launch_data_s2<DATA_S2_SPLIT, CB_DF2C> : launch_data_s2<DATA_S2_SPLIT, CB_DC2F>;
+    return launch(in, weight, out, B, Kc, Cf, nh, nw, 0, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv4x4s2_bf16_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)

@@ -1,16 +1,18 @@
 """The launch planners of csrc/conv_bf16.hip restated in Python: which kernel instantiation and LDS plan a shape reaches.
 
-A plain module (like golden_cases.py, guarded.py).  tests/test_bf16_conv_plan.py ties it to the built library through the four
+A plain module (like golden_cases.py, guarded.py).  tests/test_bf16_conv_plan.py ties it to the built library through the
 `*_workspace_bytes` queries (kt, ktiles, nstage and nsplit all show in the byte count), tests/test_gpu_bf16_conv_variants.py
 asserts through it the variant every case reaches before it compares numbers.  Each function names the lines it mirrors; integer
 arithmetic is C's (all operands non-negative, so `//` is the same division).
 
 A plan is a dict, `None` = the shape is refused (IPSR_ERR_UNSUPPORTED).  Forward / input-gradient plans:
-    mode "S1" | "F2C" | "C2F", kt (128 | 64), ptile (256 | 512), R (lane-grid rows per tile), tiles_per_img, ptiles, ktiles, nphase,
+    mode "S1" | "F2C" | "C2F" | "DF2C" | "DC2F", kt (128 | 64), ptile (256 | 512), R (lane-grid rows per tile), tiles_per_img, ptiles, ktiles, nphase,
     nsub, nstage, ntap, raw1, lds (bytes of dynamic LDS), nblocks (16-channel blocks of the reduction), nsplit (runs), bps (blocks per
     run), last_bps (blocks of the last run), uneven (last run shorter), wgs (workgroups before the cut), p512 ("taken", or why a
     <= 64-channel layer did not get the 512-pixel tile: "rows" | "lds"; None above 64 channels), Wl (lane-grid width), Hout, Wout,
-    B, C, K.  With `why=True` a planner returns (plan, message fragment of the refusal).
+    B, C, K; split (fp32 tensors, split-bf16 operands: kt 64, ptile 256, no raw buffers), items (their activation items per stage).
+    One planner, data_geometry(kind, form, ...), serves the four kernels; cb_geometry / cb_geometry_s2 are its bf16 kinds.  With
+    `why=True` a planner returns (plan, message fragment of the refusal).
 Weight-gradient plans: RS, groups (stages per image), spw0 (the fill-the-chip value before clamping), spw (stages_per_wg), lowered
     (the `while (groups % spw)` loop ran), nsplit (slabs), ktiles, ctiles.
 """
@@ -38,108 +40,113 @@ def cdiv(a, b):
     return (a + b - 1) // b
 
 
-def cb_lane_grid(Hl, Wl, ptile):
-    """cb_lane_grid -> (R, None) or (None, message fragment)."""
-    if Wl not in (16, 32, 64, 128, 256):
-        return None, "grid width %d" % Wl
-    R = ptile // Wl
-    if Hl % R != 0:
-        return None, "%d rows are not a multiple of the %d rows of a tile" % (Hl, R)
-    return R, None
+# ---- the forward / input-gradient planner: data_geometry over DATA_KINDS x DATA_FORMS -----------------------------------------------
+# kind: (split, widest lane grid, the width message's fragment)                                                       # DATA_KINDS
+DATA_KINDS = {"k3": (False, 256, "grid width %d"), "s2": (False, 256, "grid width %d"),
+              "k3_split": (True, 256, "width %d"), "s2_split": (True, 128, "coarse width %d")}
+# form: (fine_in, fine_out, nsub, nphase, ntap, column-phase planes of T)                                             # DATA_FORMS
+DATA_FORMS = {"S1": (False, False, 1, 1, 9, 1), "F2C": (True, False, 2, 1, 8, 2), "C2F": (False, True, 1, 2, 8, 1),
+              "DF2C": (True, False, 2, 1, 8, 1), "DC2F": (False, True, 2, 1, 8, 1)}
+S2_FORMS = {0: "F2C", 1: "C2F", 4: "DF2C", 5: "DC2F"}      # modes of the k4 s2 entries (c2_form)
 
 
-def cb_finish(g):
-    """cb_finish: k tile, the reduction cut, the LDS plan.  g holds B, C, K, Hl, R, Win, NR, PW, nsub, nphase, ntap, ptile."""
-    g["NPOS"] = g["NR"] * g["PW"]
-    g["kt"] = 64 if g["K"] <= 64 else CB_K                                               # cb_finish
-    g["ktiles"] = cdiv(g["K"], g["kt"])
-    g["tiles_per_img"] = g["Hl"] // g["R"]
-    g["ptiles"] = g["B"] * g["tiles_per_img"]                                            # cb_finish
-    g["nstage"] = (g["C"] // CB_C) * g["nsub"]
-    wgs, nblocks = g["ktiles"] * g["nphase"] * g["ptiles"], g["C"] // CB_C               # cb_cut_reduction
-    ns = 1
-    if wgs < 128 and nblocks >= 8:                                                       # cb_cut_reduction
-        ns = min(min(4, nblocks // 4), cdiv(256, wgs))
-    bps = cdiv(nblocks, max(ns, 1))                                                      # cb_cut_reduction
-    g["nsplit"] = cdiv(nblocks, bps)                                                     # cb_cut_reduction
-    g["sps"] = bps * g["nsub"]
-    g["wgs"], g["nblocks"], g["bps"] = wgs, nblocks, bps
-    g["last_bps"] = nblocks - (g["nsplit"] - 1) * bps
-    g["uneven"] = g["last_bps"] != bps
-    planes = g["nsub"]                                                                   # cb_finish
-    g["a_bytes"] = g["ntap"] * 2 * g["kt"] * 16
-    g["t_bytes"] = align_up(planes * 2 * g["NPOS"] * 16, 256)
-    g["raw_bytes"] = align_up(CB_C * g["NR"] * g["Win"] * 2, 1024)
-    g["raw1"] = 2 * (g["a_bytes"] + g["t_bytes"] + g["raw_bytes"]) > CB_LDS_MAX          # cb_finish
-    g["lds"] = 2 * (g["a_bytes"] + g["t_bytes"]) + (1 if g["raw1"] else 2) * g["raw_bytes"]
-    if g["lds"] > CB_LDS_MAX or 4 * g["NR"] * (g["Win"] // 16) > 32 * cb_tr_max(g["ptile"]) or \
-            CB_C * g["NR"] * (g["Win"] // 8) > cb_xj(g["ptile"]) * CB_THREADS:           # cb_finish
-        return None, "a tile of %d rows x %d does not fit the LDS plan" % (g["NR"], g["Win"])
-    return g, None
+def data_form(form, g):
+    """data_form: tensors and halo of a form on the lane grid g[Hl] x g[Wl] with g[R] rows per tile."""
+    fine_in, fine_out, nsub, nphase, ntap, planes = DATA_FORMS[form]
+    nh, nw, R = g["Hl"], g["Wl"], g["R"]
+    NR, PW = (R + 2, nw + 2) if form in ("S1", "C2F") else (R + 1, nw + 1) if form == "F2C" else (R + 1, nw + 3)
+    g.update(mode=form, Hin=2 * nh if fine_in else nh, Win=2 * nw if fine_in else nw, Hout=2 * nh if fine_out else nh,
+             Wout=2 * nw if fine_out else nw, nsub=nsub, nphase=nphase, ntap=ntap, planes=planes, NR=NR, PW=PW, NPOS=NR * PW)
 
 
-def cb_geometry_p(B, C, K, H, W, ptile):
-    """cb_geometry_p, k3 s1 p1 at one tile size."""
+def data_geometry(kind, form, B, C, K, Hl, Wl, why=False):
+    """data_geometry: C reduction channels -> K produced on the lane grid Hl x Wl (S1: the image; k4 s2: the coarse grid)."""
+    split, wmax, width_msg = DATA_KINDS[kind]
+
+    def out(g, msg=None):
+        return (g, msg) if why else g
     if C % CB_C != 0:
-        return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
-    R, msg = cb_lane_grid(H, W, ptile)
-    if R is None:
-        return None, msg
-    g = dict(mode="S1", B=B, C=C, K=K, Hl=H, Wl=W, R=R, ptile=ptile, Hin=H, Win=W, Hout=H, Wout=W, NR=R + 2, PW=W + 2, nsub=1, nphase=1, ntap=9)
-    return cb_finish(g)
+        return out(None, "%d reduction channels are not a multiple of %d" % (C, CB_C))
+    if Wl not in (16, 32, 64, 128, wmax):
+        return out(None, width_msg % Wl)
+    kt = 64 if split or K <= 64 else CB_K
 
+    def tile(ptile):
+        R = ptile // Wl
+        if Hl % R != 0:
+            return None, "%d rows are not a multiple of the %d rows of a tile" % (Hl, R)
+        g = dict(B=B, C=C, K=K, Hl=Hl, Wl=Wl, R=R, ptile=ptile, kt=kt, ktiles=cdiv(K, kt), split=split)
+        data_form(form, g)
+        g["tiles_per_img"] = Hl // R
+        g["ptiles"] = B * g["tiles_per_img"]
+        g["nstage"] = (C // CB_C) * g["nsub"]
+        wgs, nblocks = g["ktiles"] * g["nphase"] * g["ptiles"], C // CB_C                    # cb_cut_reduction
+        ns = 1
+        if wgs < 128 and nblocks >= 8:                                                       # cb_cut_reduction
+            ns = min(min(4, nblocks // 4), cdiv(256, wgs))
+        bps = cdiv(nblocks, max(ns, 1))                                                      # cb_cut_reduction
+        g["nsplit"] = cdiv(nblocks, bps)                                                     # cb_cut_reduction
+        g["sps"] = bps * g["nsub"]
+        g["wgs"], g["nblocks"], g["bps"] = wgs, nblocks, bps
+        g["last_bps"] = nblocks - (g["nsplit"] - 1) * bps
+        g["uneven"] = g["last_bps"] != bps
+        nplane = 2 if split else 1                                                           # hi | lo
+        g["a_bytes"] = nplane * g["ntap"] * 2 * kt * 16
+        g["t_bytes"] = align_up(nplane * g["planes"] * 2 * g["NPOS"] * 16, 256)
+        g["raw_bytes"] = 0 if split else align_up(CB_C * g["NR"] * g["Win"] * 2, 1024)
+        g["raw1"] = not split and 2 * (g["a_bytes"] + g["t_bytes"] + g["raw_bytes"]) > CB_LDS_MAX
+        g["lds"] = 2 * g["a_bytes"] + (1 if split else 2) * g["t_bytes"] + (1 if g["raw1"] else 2) * g["raw_bytes"]    # data_lds_bytes
+        g["items"] = 2 * g["NR"] * (g["Win"] // 4)                                           # split: activation items, one per thread
+        if split:
+            fits = g["items"] <= CB_THREADS
+        else:
+            fits = 4 * g["NR"] * (g["Win"] // 16) <= 32 * cb_tr_max(ptile) and CB_C * g["NR"] * (g["Win"] // 8) <= cb_xj(ptile) * CB_THREADS
+        if g["lds"] > CB_LDS_MAX or not fits:
+            return None, "a tile of %d rows x %d does not fit the LDS plan" % (g["NR"], g["Win"])
+        return g, None
 
-def _two_tiles(K, geometry_p):
-    """cb_geometry / cb_geometry_s2: <= 64 produced channels try the 512-pixel tile first; any refusal falls back to 256, silently."""
+    # bf16, <= 64 produced channels: the 512-pixel tile first; any refusal falls back to 256, silently
     p512 = None
-    if K <= 64:
-        g, msg = geometry_p(2 * CB_P)
+    if not split and K <= 64:
+        g, msg = tile(2 * CB_P)
         if g is not None:
             g["p512"] = "taken"
-            return g, None
+            return out(g)
         p512 = "rows" if "rows" in msg else ("lds" if "LDS" in msg else "other")
-    g, msg = geometry_p(CB_P)
+    g, msg = tile(CB_P)
     if g is not None:
         g["p512"] = p512
-    return g, msg
+    return out(g, msg)
 
 
 def cb_geometry(B, C, K, H, W, why=False):
-    """cb_geometry: k3 s1 p1, C reduction channels -> K produced."""
-    g, msg = _two_tiles(K, lambda p: cb_geometry_p(B, C, K, H, W, p))
-    return (g, msg) if why else g
-
-
-def cb_geometry_s2_p(form, B, C, K, nh, nw, ptile):
-    """cb_geometry_s2_p and cb_s2_form, k4 s2 p1 at one tile size.  form 0: fine -> coarse (C = Cf, K = Kc); 1: coarse -> fine (C = Kc, K = Cf)."""
-    if C % CB_C != 0:
-        return None, "%d reduction channels are not a multiple of %d" % (C, CB_C)
-    R, msg = cb_lane_grid(nh, nw, ptile)
-    if R is None:
-        return None, msg
-    g = dict(B=B, C=C, K=K, Hl=nh, Wl=nw, R=R, ptile=ptile, ntap=8)
-    if form == 0:
-        g.update(mode="F2C", Hin=2 * nh, Win=2 * nw, Hout=nh, Wout=nw, NR=R + 1, PW=nw + 1, nsub=2, nphase=1)
-    else:
-        g.update(mode="C2F", Hin=nh, Win=nw, Hout=2 * nh, Wout=2 * nw, NR=R + 2, PW=nw + 2, nsub=1, nphase=2)
-    return cb_finish(g)
+    """data_geometry(DATA_K3, CB_S1): k3 s1 p1 on bf16 tensors, C reduction channels -> K produced."""
+    return data_geometry("k3", "S1", B, C, K, H, W, why)
 
 
 def cb_geometry_s2(form, B, C, K, nh, nw, why=False):
-    """cb_geometry_s2."""
-    g, msg = _two_tiles(K, lambda p: cb_geometry_s2_p(form, B, C, K, nh, nw, p))
-    return (g, msg) if why else g
+    """data_geometry(DATA_S2, .): k4 s2 p1 on bf16 tensors.  form 0: fine -> coarse (C = Cf, K = Kc); 1: coarse -> fine (C = Kc, K = Cf)."""
+    return data_geometry("s2", S2_FORMS[form], B, C, K, nh, nw, why)
 
 
 def cb_partial_bytes(g):                                  # cb_partial_bytes
     return align_up(g["nsplit"] * g["B"] * g["K"] * g["Hout"] * g["Wout"] * 4, 256) if g["nsplit"] > 1 else 0
 
 
-def cb_ws_bytes(g):
-    """conv_bf16_ws_bytes / conv_bf16_s2_ws_bytes: zero page + packed weights + fp32 partials of a cut reduction; 0 for a refused shape."""
+def data_ws_bytes(g):
+    """data_ws_bytes: zero page + packed weights (split: two planes) + fp32 partials of a cut reduction; 0 for a refused shape."""
     if g is None:
         return 0
-    return 256 + g["ktiles"] * g["nphase"] * g["nstage"] * g["ntap"] * 2 * g["kt"] * 16 + cb_partial_bytes(g)
+    pack = g["ktiles"] * g["nphase"] * g["nstage"] * g["ntap"] * 2 * g["kt"] * 16           # data_pack_bytes: one plane
+    return 256 + align_up((2 if g["split"] else 1) * pack, 256) + cb_partial_bytes(g)
+
+
+def split_plan(kind, form, B, C, K, Hl, Wl):
+    """The plan of a split-bf16 kind as tests/test_gpu_bf16x3_conv.py, bf16x3_s2_plan.py and bf16x3_dil_plan.py hand it out; None = refused."""
+    g = data_geometry(kind, form, B, C, K, Hl, Wl)
+    if g is None:
+        return None
+    return dict(g, ragged_k=K % 64 != 0, ws=data_ws_bytes(g))
 
 
 def _spw(tiles, B, groups):
@@ -219,11 +226,11 @@ def s2_wrw_plan(B, Kc, Cf, nh, nw, why=False):
 
 
 def k3_ws(op, B, Cin, H, W, Cout):
-    return cb_ws_bytes(k3_plan(op, B, Cin, H, W, Cout))
+    return data_ws_bytes(k3_plan(op, B, Cin, H, W, Cout))
 
 
 def s2_ws(mode, B, Kc, Cf, nh, nw):
-    return cb_ws_bytes(s2_plan(mode, B, Kc, Cf, nh, nw))
+    return data_ws_bytes(s2_plan(mode, B, Kc, Cf, nh, nw))
 
 
 def k3_wrw_ws(transposed, B, Cin, H, W, Cout):
@@ -368,53 +375,53 @@ def _multi(p):
 
 
 VARIANTS = (
-    ("S1 KT128 P256, 3 tiles per image (W 32)", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["tiles_per_img"] == 3 and p["Wl"] == 32,
+    ("S1 KT128 P256, 3 tiles per image (W 32)", "tiles_per_img, data_geometry ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["tiles_per_img"] == 3 and p["Wl"] == 32,
      (("k3_c64_24x32_k160_b3", "fwd"),)),
-    ("S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and _multi(p) and p["Wl"] in (64, 128),
+    ("S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128", "tiles_per_img, data_geometry ptiles", lambda p: p["mode"] == "S1" and p["kt"] == 128 and _multi(p) and p["Wl"] in (64, 128),
      (("k3_c64_12x64_k128_b2", "fwd"), ("k3_c32_10x128_k80_b1", "fwd"))),
-    ("S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image", "cb_lane_grid, cb_finish raw1", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["Wl"] == 256 and p["R"] == 1 and p["raw1"] and p["tiles_per_img"] == 6,
+    ("S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image", "data_geometry rows, raw1", lambda p: p["mode"] == "S1" and p["kt"] == 128 and p["Wl"] == 256 and p["R"] == 1 and p["raw1"] and p["tiles_per_img"] == 6,
      (("k3_c32_6x256_k144_b2", "fwd"),)),
-    ("S1 KT64 P512 at W 16, 3 tiles per image", "cb_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 16 and p["tiles_per_img"] == 3,
+    ("S1 KT64 P512 at W 16, 3 tiles per image", "data_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 16 and p["tiles_per_img"] == 3,
      (("k3_c48_96x16_k32_b2", "fwd"), ("k3_c48_96x16_k32_b2", "dx"))),
-    ("S1 KT64 P512 at W 32, 3 tiles per image", "cb_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+    ("S1 KT64 P512 at W 32, 3 tiles per image", "data_geometry", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 32 and p["tiles_per_img"] == 3,
      (("k3T_c32_48x32_k64_b1", "fwd"), ("k3T_c32_48x32_k64_b1", "dx"))),
-    ("S1 KT64, P512 refused by the rows -> P256", "cb_geometry, cb_lane_grid", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["p512"] == "rows",
+    ("S1 KT64, P512 refused by the rows -> P256", "data_geometry 512 -> 256", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["p512"] == "rows",
      (("k3_c64_24x32_k160_b3", "dx"), ("k3_c64_12x64_k128_b2", "dx"), ("k3_c32_10x128_k80_b1", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
     ("S1 KT64 P256, reduction cut in 2 / in 4", "cb_cut_reduction", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] in (2, 4),
      (("k3_c64_24x32_k160_b3", "dx"), ("k3_c256_16x16_k64_b1", "fwd"))),
     ("S1 KT64 P512, cut in 3 uneven (5 + 5 + 3 blocks)", "cb_cut_reduction", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and (p["nsplit"], p["bps"], p["last_bps"]) == (3, 5, 3),
      (("k3T_c208_32x16_k48_b1", "fwd"),)),
-    ("S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)", "cb_cut_reduction, cb_finish raw1", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and (p["nsplit"], p["bps"], p["last_bps"]) == (2, 5, 4),
+    ("S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)", "cb_cut_reduction, data_geometry raw1", lambda p: p["mode"] == "S1" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and (p["nsplit"], p["bps"], p["last_bps"]) == (2, 5, 4),
      (("k3_c32_6x256_k144_b2", "dx"),)),
-    ("F2C KT64 P512 raw1 at nw 16", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 16,
+    ("F2C KT64 P512 raw1 at nw 16", "data_geometry raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 16,
      (("s2_64_32_32x16_b2", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 32, 3 tiles per image", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 32 and p["tiles_per_img"] == 3,
+    ("F2C KT64 P512 raw1 at nw 32, 3 tiles per image", "data_geometry raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 32 and p["tiles_per_img"] == 3,
      (("s2_48_32_48x32_b1", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 64, 3 tiles per image", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 64 and p["tiles_per_img"] == 3,
+    ("F2C KT64 P512 raw1 at nw 64, 3 tiles per image", "data_geometry raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 64 and p["tiles_per_img"] == 3,
      (("s2_16_16_24x64_b2", "f2c"),)),
-    ("F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 156672,
+    ("F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)", "data_geometry raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 156672,
      (("s2_48_16_4x128_b1", "f2c"), ("s2_32_80_4x128_b1", "f2c"))),
-    ("F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image", "cb_finish raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 128 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 139776 and p["tiles_per_img"] == 3,
+    ("F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image", "data_geometry raw1", lambda p: p["mode"] == "F2C" and p["kt"] == 128 and p["raw1"] and p["Wl"] == 128 and p["lds"] == 139776 and p["tiles_per_img"] == 3,
      (("s2_128_64_6x128_b1", "f2c"),)),
     ("F2C cut in 2 uneven, a run = bps x nsub stages (10 + 8)", "cb_cut_reduction", lambda p: p["mode"] == "F2C" and p["nsub"] == 2 and (p["nsplit"], p["sps"], p["last_bps"] * p["nsub"]) == (2, 10, 8),
      (("s2_128_144_16x16_b1", "f2c"),)),
     ("F2C KT64 cut in 3 uneven", "cb_cut_reduction", lambda p: p["mode"] == "F2C" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
      (("s2_64_208_16x16_b1", "f2c"),)),
-    ("F2C 3 tiles per image (KT128)", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "F2C" and p["tiles_per_img"] == 3 and p["kt"] == 128,
+    ("F2C 3 tiles per image (KT128)", "tiles_per_img, data_geometry ptiles", lambda p: p["mode"] == "F2C" and p["tiles_per_img"] == 3 and p["kt"] == 128,
      (("s2_96_48_24x32_b2", "f2c"),)),
-    ("C2F KT64 P512 at nw 128", "cb_geometry_s2", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 128,
+    ("C2F KT64 P512 at nw 128", "data_geometry", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["Wl"] == 128,
      (("s2_48_16_4x128_b1", "c2f"),)),
-    ("C2F KT128 P256 at nw 128", "cb_geometry_s2", lambda p: p["mode"] == "C2F" and p["kt"] == 128 and p["Wl"] == 128,
+    ("C2F KT128 P256 at nw 128", "data_geometry", lambda p: p["mode"] == "C2F" and p["kt"] == 128 and p["Wl"] == 128,
      (("s2_32_80_4x128_b1", "c2f"),)),
-    ("C2F KT64 P512 raw1 at nw 256", "cb_geometry_s2, cb_finish raw1", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 256,
+    ("C2F KT64 P512 raw1 at nw 256", "data_geometry raw1", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 512 and p["raw1"] and p["Wl"] == 256,
      (("s2_16_16_2x256_b1", "c2f"),)),
-    ("C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image", "cb_geometry_s2, the raw1 stage loop", lambda p: p["mode"] == "C2F" and p["raw1"] and p["Wl"] == 256 and p["nstage"] == 3 and p["nsplit"] == 1 and p["tiles_per_img"] == 2,
+    ("C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image", "data_geometry, the raw1 stage loop", lambda p: p["mode"] == "C2F" and p["raw1"] and p["Wl"] == 256 and p["nstage"] == 3 and p["nsplit"] == 1 and p["tiles_per_img"] == 2,
      (("s2_48_16_4x256_b2", "c2f"),)),
     ("C2F KT64 P256 (rows) cut in 2, 3 tiles per image", "cb_cut_reduction", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["ptile"] == 256 and p["nsplit"] == 2 and p["tiles_per_img"] == 3,
      (("s2_128_64_6x128_b1", "c2f"),)),
     ("C2F KT64 cut in 3 uneven", "cb_cut_reduction", lambda p: p["mode"] == "C2F" and p["kt"] == 64 and p["nsplit"] == 3 and p["uneven"],
      (("s2_208_64_16x16_b1", "c2f"),)),
-    ("C2F 3 tiles per image, both row phases", "tiles_per_img, cb_finish ptiles", lambda p: p["mode"] == "C2F" and p["tiles_per_img"] == 3 and p["nphase"] == 2,
+    ("C2F 3 tiles per image, both row phases", "tiles_per_img, data_geometry ptiles", lambda p: p["mode"] == "C2F" and p["tiles_per_img"] == 3 and p["nphase"] == 2,
      (("s2_96_48_24x32_b2", "c2f"), ("s2_48_32_48x32_b1", "c2f"))),
     ("k3 weight gradient: groups 6 / 10 / 12 (not a power of two)", "wrw_geometry", lambda p: "RS" in p and "Ka" in p and p["groups"] in (6, 10, 12),
      (("k3_c64_24x32_k160_b3", "dw"), ("k3_c32_10x128_k80_b1", "dw"), ("k3_c48_96x16_k32_b2", "dw"))),

@@ -1,6 +1,6 @@
 """The launch plan of the split-bf16 direct kernel for the DILATED 4x4 stride-2 layer Conv2d(k4, stride 2, pad 3, dilation 2) on fp32 tensors
-(csrc/conv_bf16.hip, c2_geometry / c2_dil_form), restated in Python, and the cases of tests/test_gpu_bf16x3_dil.py with the variant each
-must reach.  No GPU, no library: tests/test_bf16x3_dil_abi.py compares the library's workspace query against `ws` here.
+(csrc/conv_bf16.hip, data_geometry / data_form on DATA_S2_SPLIT), restated in Python (tests/bf16_conv_plan.py), and the cases of
+tests/test_gpu_bf16x3_dil.py with the variant each must reach.  No GPU, no library: tests/test_bf16x3_dil_abi.py compares the library's workspace query against `ws` here.
 
 Shapes are (B, Kc, Cf, nh, nw): fine [B,Cf,2nh,2nw] (x / dx), coarse [B,Kc,nh,nw] (y / dy), weight [Kc,Cf,4,4].  mode 4 = fine -> coarse
 (the forward: reduces Cf, produces Kc), mode 5 = coarse -> fine (the input gradient: reduces Kc, produces Cf).  Both run on the coarse lane
@@ -9,10 +9,7 @@ grid, tile = 64 produced channels x 256 coarse pixels = R = 256 / nw coarse rows
 loads items of 4 floats from rows 2 nw wide and keeps the two odd columns; mode 5 writes the whole fine result, so under a reduction cut
 its partials are fine-sized.
 """
-
-
-def _align(v, a):
-    return (v + a - 1) // a * a
+import bf16_conv_plan as P
 
 
 def plan(mode, B, Kc, Cf, nh, nw):
@@ -20,27 +17,8 @@ def plan(mode, B, Kc, Cf, nh, nw):
     if mode not in (4, 5) or min(B, Kc, Cf, nh, nw) < 1:
         return None
     C, K = (Cf, Kc) if mode == 4 else (Kc, Cf)                    # reduction / produced channels
-    if C % 16 or nw not in (16, 32, 64, 128) or nh % (256 // nw):
-        return None
-    R = 256 // nw
-    nsub = 2
-    NR, PW, Win = R + 1, nw + 3, (2 * nw if mode == 4 else nw)
-    ktiles, ptiles, nblocks = (K + 63) // 64, B * (nh // R), C // 16
-    nstage = nblocks * nsub
-    wgs, ns = ktiles * ptiles, 1
-    if wgs < 128 and nblocks >= 8:
-        ns = min(4, nblocks // 4, (256 + wgs - 1) // wgs)
-    bps = (nblocks + ns - 1) // ns
-    nsplit = (nblocks + bps - 1) // bps
-    t_bytes = _align(2 * 2 * NR * PW * 16, 256)                   # hi | lo, two channel groups, ONE column plane
-    lds, items = 2 * 32768 + t_bytes, 2 * NR * (Win // 4)
-    if lds > 160 * 1024 or items > 512:
-        return None
-    Hout, Wout = (nh, nw) if mode == 4 else (2 * nh, 2 * nw)
-    pack = ktiles * nstage * 8 * 2 * 64 * 16                      # one plane
-    ws = 256 + _align(2 * pack, 256) + (_align(nsplit * B * K * Hout * Wout * 4, 256) if nsplit > 1 else 0)
-    return dict(R=R, NR=NR, PW=PW, ktiles=ktiles, tiles_per_img=nh // R, ptiles=ptiles, nstage=nstage, nsplit=nsplit, sps=bps * nsub, lds=lds,
-                t_bytes=t_bytes, items=items, ragged_k=K % 64 != 0, ws=ws)
+    p = P.split_plan("s2_split", P.S2_FORMS[mode], B, C, K, nh, nw)
+    return p and {k: p[k] for k in ("R", "NR", "PW", "ktiles", "tiles_per_img", "ptiles", "nstage", "nsplit", "sps", "lds", "t_bytes", "items", "ragged_k", "ws")}
 
 
 # id: ((B, Kc, Cf, nh, nw), {mode: the plan fields the case is there for})

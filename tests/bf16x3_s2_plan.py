@@ -1,5 +1,6 @@
-"""The launch plan of the split-bf16 direct kernel for the k4 s2 p1 layers on fp32 tensors (csrc/conv_bf16.hip, c2_geometry), restated in
-Python, and the cases of tests/test_gpu_bf16x3_s2.py with the variant each must reach.  No GPU, no library: tests/test_bf16x3_s2_abi.py
+"""The launch plan of the split-bf16 direct kernel for the k4 s2 p1 layers on fp32 tensors (csrc/conv_bf16.hip, data_geometry on DATA_S2_SPLIT), restated in
+Python
+(tests/bf16_conv_plan.py), and the cases of tests/test_gpu_bf16x3_s2.py with the variant each must reach.  No GPU, no library: tests/test_bf16x3_s2_abi.py
 compares the library's workspace query against `ws` here.
 
 Shapes are (B, Kc, Cf, nh, nw): fine [B,Cf,2nh,2nw], coarse [B,Kc,nh,nw], weight [Kc,Cf,4,4].  mode 0 = fine -> coarse (reduces Cf, produces
@@ -7,10 +8,7 @@ Kc, two sub-stages per 16-channel block: one per input row parity), mode 1 = coa
 output row parity).  The lane grid is the coarse one in both: tile = 64 produced channels x 256 coarse pixels = R = 256 / nw coarse rows.
 The plan has ONE k tile (64 rows) and ONE pixel tile (256): what varies is how many of each a launch has, the stage count and the cut.
 """
-
-
-def _align(v, a):
-    return (v + a - 1) // a * a
+import bf16_conv_plan as P
 
 
 def plan(mode, B, Kc, Cf, nh, nw):
@@ -18,27 +16,8 @@ def plan(mode, B, Kc, Cf, nh, nw):
     if mode not in (0, 1) or min(B, Kc, Cf, nh, nw) < 1:
         return None
     C, K = (Cf, Kc) if mode == 0 else (Kc, Cf)                    # reduction / produced channels
-    if C % 16 or nw not in (16, 32, 64, 128) or nh % (256 // nw):
-        return None
-    R = 256 // nw
-    nsub, nphase = (2, 1) if mode == 0 else (1, 2)
-    NR, PW, Win = (R + 1, nw + 1, 2 * nw) if mode == 0 else (R + 2, nw + 2, nw)
-    ktiles, ptiles, nblocks = (K + 63) // 64, B * (nh // R), C // 16
-    nstage = nblocks * nsub
-    wgs, ns = ktiles * nphase * ptiles, 1
-    if wgs < 128 and nblocks >= 8:
-        ns = min(4, nblocks // 4, (256 + wgs - 1) // wgs)
-    bps = (nblocks + ns - 1) // ns
-    nsplit = (nblocks + bps - 1) // bps
-    t_bytes = _align(2 * nsub * 2 * NR * PW * 16, 256)
-    lds, items = 2 * 32768 + t_bytes, 2 * NR * (Win // 4)
-    if lds > 160 * 1024 or items > 512:
-        return None
-    Hout, Wout = (nh, nw) if mode == 0 else (2 * nh, 2 * nw)
-    pack = ktiles * nphase * nstage * 8 * 2 * 64 * 16             # one plane
-    ws = 256 + _align(2 * pack, 256) + (_align(nsplit * B * K * Hout * Wout * 4, 256) if nsplit > 1 else 0)
-    return dict(R=R, NR=NR, ktiles=ktiles, tiles_per_img=nh // R, ptiles=ptiles, nstage=nstage, nsplit=nsplit, sps=bps * nsub, lds=lds, items=items,
-                ragged_k=K % 64 != 0, ws=ws)
+    p = P.split_plan("s2_split", P.S2_FORMS[mode], B, C, K, nh, nw)
+    return p and {k: p[k] for k in ("R", "NR", "ktiles", "tiles_per_img", "ptiles", "nstage", "nsplit", "sps", "lds", "items", "ragged_k", "ws")}
 
 
 # id: ((B, Kc, Cf, nh, nw), {mode: the plan fields the case is there for})

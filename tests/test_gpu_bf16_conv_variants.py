@@ -8,38 +8,38 @@ and once more here), the plan each of its passes reaches, then compares with fp6
 
   variant                                                                              selected in                              case id(s)
   -----------------------------------------------------------------------------------  ---------------------------------------- ----------------------------
-  S1 KT128 P256, 3 tiles per image (W 32)                                              tiles_per_img, cb_finish ptiles          k3_c64_24x32_k160_b3
-  S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128                                   tiles_per_img, cb_finish ptiles          k3_c64_12x64_k128_b2, k3_c32_10x128_k80_b1
-  S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image                    cb_lane_grid, cb_finish raw1             k3_c32_6x256_k144_b2
-  S1 KT64 P512 at W 16, 3 tiles per image                                              cb_geometry                              k3_c48_96x16_k32_b2
-  S1 KT64 P512 at W 32, 3 tiles per image                                              cb_geometry                              k3T_c32_48x32_k64_b1
-  S1 KT64, P512 refused by the rows -> P256                                            cb_geometry, cb_lane_grid                k3_c64_24x32_k160_b3, k3_c64_12x64_k128_b2, k3_c32_10x128_k80_b1, k3_c256_16x16_k64_b1
+  S1 KT128 P256, 3 tiles per image (W 32)                                              tiles_per_img, data_geometry ptiles      k3_c64_24x32_k160_b3
+  S1 KT128 P256, 3 / 5 tiles per image at W 64 / 128                                   tiles_per_img, data_geometry ptiles      k3_c64_12x64_k128_b2, k3_c32_10x128_k80_b1
+  S1 KT128 P256 at W 256: one row per tile, raw1, 6 tiles per image                    data_geometry rows, raw1                 k3_c32_6x256_k144_b2
+  S1 KT64 P512 at W 16, 3 tiles per image                                              data_geometry                            k3_c48_96x16_k32_b2
+  S1 KT64 P512 at W 32, 3 tiles per image                                              data_geometry                            k3T_c32_48x32_k64_b1
+  S1 KT64, P512 refused by the rows -> P256                                            data_geometry 512 -> 256                 k3_c64_24x32_k160_b3, k3_c64_12x64_k128_b2, k3_c32_10x128_k80_b1, k3_c256_16x16_k64_b1
   S1 KT64 P256, reduction cut in 2 / in 4                                              cb_cut_reduction                         k3_c64_24x32_k160_b3, k3_c256_16x16_k64_b1
   S1 KT64 P512, cut in 3 uneven (5 + 5 + 3 blocks)                                     cb_cut_reduction                         k3T_c208_32x16_k48_b1
-  S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)                            cb_cut_reduction, cb_finish raw1         k3_c32_6x256_k144_b2
-  F2C KT64 P512 raw1 at nw 16                                                          cb_geometry_s2, cb_finish raw1           s2_64_32_32x16_b2
-  F2C KT64 P512 raw1 at nw 32, 3 tiles per image                                       cb_geometry_s2, cb_finish raw1           s2_48_32_48x32_b1
-  F2C KT64 P512 raw1 at nw 64, 3 tiles per image                                       cb_geometry_s2, cb_finish raw1           s2_16_16_24x64_b2
-  F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)                                         cb_geometry_s2, cb_finish raw1           s2_48_16_4x128_b1, s2_32_80_4x128_b1
-  F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image                     cb_finish raw1                           s2_128_64_6x128_b1
+  S1 KT64 P512 raw1 (W 256), cut in 2 uneven (5 + 4 blocks)                            cb_cut_reduction, data_geometry raw1     k3_c32_6x256_k144_b2
+  F2C KT64 P512 raw1 at nw 16                                                          data_geometry raw1                       s2_64_32_32x16_b2
+  F2C KT64 P512 raw1 at nw 32, 3 tiles per image                                       data_geometry raw1                       s2_48_32_48x32_b1
+  F2C KT64 P512 raw1 at nw 64, 3 tiles per image                                       data_geometry raw1                       s2_16_16_24x64_b2
+  F2C KT64 P512 raw1 at nw 128 (LDS 156 672 B)                                         data_geometry raw1                       s2_48_16_4x128_b1, s2_32_80_4x128_b1
+  F2C KT128 P256 raw1 at nw 128 (LDS 139 776 B), 3 tiles per image                     data_geometry raw1                       s2_128_64_6x128_b1
   F2C cut in 2 uneven, a run = bps x nsub stages (10 + 8)                              cb_cut_reduction                         s2_128_144_16x16_b1
   F2C KT64 cut in 3 uneven                                                             cb_cut_reduction                         s2_64_208_16x16_b1
-  F2C 3 tiles per image (KT128)                                                        tiles_per_img, cb_finish ptiles          s2_96_48_24x32_b2
-  C2F KT64 P512 at nw 128                                                              cb_geometry_s2                           s2_48_16_4x128_b1
-  C2F KT128 P256 at nw 128                                                             cb_geometry_s2                           s2_32_80_4x128_b1
-  C2F KT64 P512 raw1 at nw 256                                                         cb_geometry_s2, cb_finish raw1           s2_16_16_2x256_b1
-  C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image                        cb_geometry_s2, the raw1 stage loop      s2_48_16_4x256_b2
+  F2C 3 tiles per image (KT128)                                                        tiles_per_img, data_geometry ptiles      s2_96_48_24x32_b2
+  C2F KT64 P512 at nw 128                                                              data_geometry                            s2_48_16_4x128_b1
+  C2F KT128 P256 at nw 128                                                             data_geometry                            s2_32_80_4x128_b1
+  C2F KT64 P512 raw1 at nw 256                                                         data_geometry raw1                       s2_16_16_2x256_b1
+  C2F KT64 P512 raw1 at nw 256 over 3 stages, 2 tiles per image                        data_geometry, the raw1 stage loop       s2_48_16_4x256_b2
   C2F KT64 P256 (rows) cut in 2, 3 tiles per image                                     cb_cut_reduction                         s2_128_64_6x128_b1
   C2F KT64 cut in 3 uneven                                                             cb_cut_reduction                         s2_208_64_16x16_b1
-  C2F 3 tiles per image, both row phases                                               tiles_per_img, cb_finish ptiles          s2_96_48_24x32_b2, s2_48_32_48x32_b1
+  C2F 3 tiles per image, both row phases                                               tiles_per_img, data_geometry ptiles      s2_96_48_24x32_b2, s2_48_32_48x32_b1
   k3 weight gradient: groups 6 / 10 / 12 (not a power of two)                          wrw_geometry                             k3_c64_24x32_k160_b3, k3_c32_10x128_k80_b1, k3_c48_96x16_k32_b2
   k3 weight gradient: stages_per_wg lowered by the loop (4 -> 3), 1 < spw < groups     cb_cut_runs                              k3w_ka512_cb256_48x16_b9
   k3 weight gradient: spw = groups, ONE slab                                           cb_cut_runs                              k3w_ka1024_cb1088_16x16_b1
   k4 s2 weight gradient: groups 12 / 24 (not a power of two)                           wrw_geometry                             s2_96_48_24x32_b2, s2_48_32_48x32_b1
   k4 s2 weight gradient: spw = groups 12, one slab per image                           cb_cut_runs                              s2w_512_512_24x32_b5
   k4 s2 weight gradient: ONE slab                                                      cb_cut_runs                              s2w_512_1056_8x16_b1
-  refusals: W 24, C % 16, rows % R, F2C nw 256, wrw W 256, s2 wrw nw 128               cb_lane_grid, cb_geometry_p, cb_finish,  refuse_* (and the `dw` / `f2c` passes the
-                                                                                       wrw_geometry                             case tables mark refused)
+  refusals: W 24, C % 16, rows % R, F2C nw 256, wrw W 256, s2 wrw nw 128               data_geometry, wrw_geometry              refuse_* (and the `dw` / `f2c` passes the
+                                                                                                                                case tables mark refused)
 (The 512-pixel tile is never turned down by its LDS plan on a width the form accepts, only by the rows: test_bf16_conv_plan.py.)
 
 Reference and bounds are those of test_direct_bf16_conv_all_passes / test_direct_bf16_stride2_family (tests/test_gpu_conv.py):
@@ -143,8 +143,8 @@ def _k3_library_agrees(ops, tr, B, Cin, H, W, Cout, plans):
     L = _lib.lib()
     fop, bop = (ops.CONVT_FWD, ops.CONVT_BWD_DATA) if tr else (ops.CONV_FWD, ops.CONV_BWD_DATA)
     if "fwd" in plans:
-        assert L.ipsr_conv3x3_bf16_workspace_bytes(fop, B, Cin, H, W, Cout) == P.cb_ws_bytes(plans["fwd"])
-        assert L.ipsr_conv3x3_bf16_workspace_bytes(bop, B, Cin, H, W, Cout) == P.cb_ws_bytes(plans["dx"])
+        assert L.ipsr_conv3x3_bf16_workspace_bytes(fop, B, Cin, H, W, Cout) == P.data_ws_bytes(plans["fwd"])
+        assert L.ipsr_conv3x3_bf16_workspace_bytes(bop, B, Cin, H, W, Cout) == P.data_ws_bytes(plans["dx"])
     assert L.ipsr_conv3x3_bf16_wrw_workspace_bytes(int(tr), B, Cin, H, W, Cout) == P.wb_ws_bytes(plans["dw"])
 
 
@@ -239,8 +239,8 @@ def _s2_library_agrees(B, Kc, Cf, nh, nw, plans):
     from deepinpainting_amd import _lib
     L = _lib.lib()
     if "f2c" in plans:
-        assert L.ipsr_conv4x4s2_bf16_workspace_bytes(0, B, Kc, Cf, nh, nw) == P.cb_ws_bytes(plans["f2c"])
-        assert L.ipsr_conv4x4s2_bf16_workspace_bytes(1, B, Kc, Cf, nh, nw) == P.cb_ws_bytes(plans["c2f"])
+        assert L.ipsr_conv4x4s2_bf16_workspace_bytes(0, B, Kc, Cf, nh, nw) == P.data_ws_bytes(plans["f2c"])
+        assert L.ipsr_conv4x4s2_bf16_workspace_bytes(1, B, Kc, Cf, nh, nw) == P.data_ws_bytes(plans["c2f"])
     assert L.ipsr_conv4x4s2_bf16_wrw_workspace_bytes(B, Kc, Cf, nh, nw) == P.w2_ws_bytes(plans["dw"])
 
 

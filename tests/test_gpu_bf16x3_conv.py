@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import bf16_conv_plan as P
 from bf16x3_harness import NAN_BITS, _bits, _in_band, _module_pass, _same, check_bf16_representable, check_guarded, direct_math, draw  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -40,24 +41,11 @@ SHAPES = {
 }
 
 
-def _align(v, a):
-    return (v + a - 1) // a * a
-
-
 def x3_plan(op, B, Cin, H, W, Cout):
-    """The launch plan of csrc/conv_bf16.hip's cx_geometry, restated: None where it refuses."""
+    """The launch plan of csrc/conv_bf16.hip's data_geometry on DATA_K3_SPLIT, restated (tests/bf16_conv_plan.py): None where it refuses."""
     C, K = (Cin, Cout) if op in (0, 2) else (Cout, Cin)
-    if C % 16 or W not in (16, 32, 64, 128, 256) or H % (256 // W):
-        return None
-    R = 256 // W
-    ktiles, ptiles, nstage = (K + 63) // 64, B * (H // R), C // 16
-    wgs, ns = ktiles * ptiles, 1
-    if wgs < 128 and nstage >= 8:
-        ns = min(4, nstage // 4, (256 + wgs - 1) // wgs)
-    sps = (nstage + ns - 1) // ns
-    nsplit = (nstage + sps - 1) // sps
-    ws = 256 + _align(2 * ktiles * nstage * 9 * 2 * 64 * 16, 256) + (_align(nsplit * B * K * H * W * 4, 256) if nsplit > 1 else 0)
-    return dict(nsplit=nsplit, sps=sps, ktiles=ktiles, tiles_per_img=H // R, nstage=nstage, ws=ws)
+    p = P.split_plan("k3_split", "S1", B, C, K, H, W)
+    return p and {k: p[k] for k in ("nsplit", "sps", "ktiles", "tiles_per_img", "nstage", "ws")}
 
 
 def _operands(op, B, Cin, Cout, H, W, seed):
