@@ -655,7 +655,7 @@ def test_patch_layer_vs_oracle_bit_exact_and_vs_reference(ops, name):
     assert np.abs(f.attn_rows.cpu().numpy() - d["attn_rows"]).max() <= ATOL
 
 
-@pytest.mark.parametrize("B,C,h,w,p,seed", [(2, 16, 10, 14, 3, 1),      # K = 144: fast correlation path on a ragged grid
+@pytest.mark.parametrize("B,C,h,w,p,seed", [(2, 16, 10, 14, 3, 1),      # K = 144; h*w = 140: the generic WRITE_S correlation under the stencil
                                             (1, 512, 10, 10, 3, 2),     # K = 4608: the config-4 patch length (wide recurrence)
                                             (2, 20, 9, 9, 2, 3),        # K = 80, C not a multiple of 8: generic kernels
                                             (1, 128, 14, 14, 3, 4),     # K = 1152 (3 lane chunks), N' = 144 > 128: two k-tiles
