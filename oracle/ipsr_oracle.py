@@ -145,6 +145,52 @@ def forward(x, ref, mask_point_idx, patch=1, stride=1):
     return Forward(out, ind, vmax, attn[:, :M], bidx)
 
 
+INDEX_SENTINEL = -0x5A5A5A5B      # what forward_masks leaves in the bwd_index slots the library does not define
+
+
+def forward_masks(x, ref, mpi_rows, counts, Mcap, patch=1, want_attn=True):
+    """Twin of ipsr_forward_masks (include/ipsr_hip.h), in Python over `forward`: sample b is the batch-of-one layer on the
+    first counts[b] entries of its index row, laid out by the capacity Mcap.
+      mpi_rows  [Mcap] (one index shared by the batch) or [B,Mcap]; entries past counts[b] are never read
+      counts    [B], clamped to [0, Mcap] as the kernels do
+    -> Forward with attn_rows [B,Mcap,N'] (rows >= counts[b] zero; None when want_attn is false) and bwd_index
+    [B, bwd_index_ints(N', Mcap)]: offA | entA (N' - counts[b] entries) | offB | entB_q at 3N'+2 | entB_w at
+    3N'+2 + Mcap(Mcap+1)/2, offB[N'] entries each; every other slot holds INDEX_SENTINEL.  `backward` / `backward_patch`
+    read this layout with M = Mcap."""
+    x, ref = _f32(x), _f32(ref)
+    B, C, h, w = x.shape
+    N = (h - patch + 1) * (w - patch + 1)
+    Mcap = int(Mcap)
+    rows = np.asarray(mpi_rows)
+    if rows.ndim == 1:
+        rows = np.broadcast_to(rows, (B, rows.shape[0]))
+    if rows.shape != (B, Mcap) or not 1 <= Mcap <= N:
+        raise ValueError("forward_masks: mpi_rows %s does not fit B=%d, Mcap=%d, N=%d" % (rows.shape, B, Mcap, N))
+    counts = np.clip(np.asarray(counts, np.int64).reshape(-1), 0, Mcap)
+    if counts.shape[0] != B:
+        raise ValueError("forward_masks: counts must be [B]")
+    capB = Mcap * (Mcap + 1) // 2
+    out = np.empty_like(x)
+    ind = np.empty((B, N), np.int32)
+    vmax = np.empty((B, N), np.float32)
+    attn = np.zeros((B, Mcap, N), np.float32) if want_attn else None
+    bidx = np.full((B, bwd_index_ints(N, Mcap)), INDEX_SENTINEL, np.int32)
+    for b in range(B):
+        m = int(counts[b])
+        f = forward(x[b:b + 1], ref[b:b + 1], rows[b, :m], patch=patch)
+        out[b], ind[b], vmax[b] = f.out[0], f.ind[0], f.vmax[0]
+        if want_attn:
+            attn[b, :m] = f.attn_rows[0]
+        one, capb = f.bwd_index[0], m * (m + 1) // 2
+        nb = int(one[3 * N + 1])                                   # offB[N]
+        bidx[b, :N + 1] = one[:N + 1]
+        bidx[b, N + 1:2 * N + 1 - m] = one[N + 1:2 * N + 1 - m]
+        bidx[b, 2 * N + 1:3 * N + 2] = one[2 * N + 1:3 * N + 2]
+        bidx[b, 3 * N + 2:3 * N + 2 + nb] = one[3 * N + 2:3 * N + 2 + nb]
+        bidx[b, 3 * N + 2 + capB:3 * N + 2 + capB + nb] = one[3 * N + 2 + capb:3 * N + 2 + capb + nb]
+    return Forward(out, ind, vmax, attn, bidx)
+
+
 def unfold(x, patch):
     """x [B,C,h,w] -> [B, C*p*p, N'] (rows k = (c*p+dy)*p+dx)."""
     x = _f32(x)

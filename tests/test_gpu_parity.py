@@ -276,6 +276,23 @@ def used_index(bwd_index, N, M):
     return out
 
 
+def used_index_cap(bwd_index, N, counts, Mcap):
+    """`used_index` for the capacity layout of ipsr_forward_masks: sample b has N - counts[b] one-hot entries (counts clamped to
+    [0, Mcap]) and its survivor weights start capB = Mcap(Mcap+1)/2 words behind the survivor positions."""
+    bi = bwd_index if isinstance(bwd_index, np.ndarray) else bwd_index.cpu().numpy()
+    capB = Mcap * (Mcap + 1) // 2
+    out = []
+    for row, m in zip(bi, counts):
+        m = min(max(int(m), 0), Mcap)
+        offA, entA = row[:N + 1], row[N + 1:2 * N + 1]
+        offB = row[2 * N + 1:3 * N + 2]
+        nb = int(offB[N])
+        entBq = row[3 * N + 2:3 * N + 2 + nb]
+        entBw = row[3 * N + 2 + capB:3 * N + 2 + capB + nb]
+        out.append(np.concatenate([offA, entA[:N - m], offB, entBq, entBw]))
+    return out
+
+
 def assert_index_equal(a, b, N, M):
     for x, y in zip(used_index(a, N, M), used_index(b, N, M)):
         np.testing.assert_array_equal(x, y)
