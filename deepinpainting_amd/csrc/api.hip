@@ -82,8 +82,7 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 struct FwdPlan {
     int N, Cp, Mc;
-    int K, ld;         // patch length C*p*p and the row stride of the correlation operands: N, or for the bf16 correlation with
-                       // p > 1 (operands: the raw [C][h*w] features) h*w rounded up to 128
+    int K;             // patch length C*p*p
     size_t total;
 };
 
@@ -99,7 +98,6 @@ static FwdPlan plan_forward(int B, int C, int h, int w, int M, int patch, size_t
     p.K = C * patch * patch;
     p.N = (h - patch + 1) * (w - patch + 1);
     const bool win_bf16 = patch > 1 && corr_bf16;
-    p.ld = win_bf16 ? (h * w + 127) & ~127 : p.N;
     p.Cp = (p.K + 7) & ~7;
     p.Mc = M > 0 ? (M + 31) & ~31 : 32;
     const size_t Mx = M > 0 ? M : 1;
@@ -107,14 +105,14 @@ static FwdPlan plan_forward(int B, int C, int h, int w, int M, int patch, size_t
     const size_t hw = (size_t)h * w;
     // patch > 1 (shifted-sum form): WS_XN = the 1x1 correlation matrix R [B][hw][hw]; WS_XU = the per-position norms n1 [B][hw];
     // WS_CORR = partials of the 1x1 correlation launch; WS_RU = partials of the window arg-max.  Nothing is unfolded but xT.
-    // patch > 1 with the bf16 correlation: R from the bf16 kernel, WS_CORR = its partials and the two packed [C/8][ld][8] bf16
-    // copies of the raw features.
-    sz[WS_XN] = patch > 1 ? (size_t)B * hw * hw * 4 : (size_t)B * p.K * p.ld * 4;
+    // patch > 1 with the bf16 correlation: R from the bf16 kernel, WS_CORR = its partials and the two packed bf16 copies of the
+    // raw features (corr_R_bf16_ws_bytes).
+    sz[WS_XN] = patch > 1 ? (size_t)B * hw * hw * 4 : (size_t)B * p.K * p.N * 4;
     sz[WS_XT] = (size_t)B * p.N * p.Cp * 4;
     sz[WS_INV] = (size_t)B * p.N * 4;
-    if (win_bf16) sz[WS_CORR] = corr_argmax_bf16_ws_bytes(B, C, (int)hw, p.ld);
+    if (win_bf16) sz[WS_CORR] = corr_R_bf16_ws_bytes(B, C, (int)hw);
     else if (patch > 1) sz[WS_CORR] = corr_argmax_ws_bytes(B, C, (int)hw);
-    else sz[WS_CORR] = corr_bf16 ? corr_argmax_bf16_ws_bytes(B, p.K, p.N, p.ld) : corr_argmax_ws_bytes(B, p.K, p.N);
+    else sz[WS_CORR] = corr_bf16 ? corr_argmax_bf16_ws_bytes(B, p.K, p.N) : corr_argmax_ws_bytes(B, p.K, p.N);
     sz[WS_XU] = patch > 1 ? (size_t)B * hw * 4 : 0;
     sz[WS_RU] = patch > 1 ? window_corr_ws_bytes(B, p.N) : 0;
     sz[WS_OU] = patch > 1 ? (size_t)B * p.K * p.N * 4 : 0;
@@ -283,9 +281,9 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
     size_t sz[WS_COUNT];
     const FwdPlan p = plan_forward(B, C, h, w, M, patch, sz, corr_bf16);
     // the layer's limits are refused here, before the first launch: a refused call leaves every output untouched
-    if (corr_bf16 && patch > 1 && !corr_bf16_supported(C, p.ld))
+    if (corr_bf16 && patch > 1 && !corr_R_bf16_supported(C))
         return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C %% 64 == 0 for shift_sz > 1 (got C=%d)", C);
-    if (corr_bf16 && patch == 1 && !corr_bf16_supported(p.K, p.ld))
+    if (corr_bf16 && patch == 1 && !corr_bf16_supported(p.K, p.N))
         return fail(IPSR_ERR_UNSUPPORTED, "ipsr_forward_bf16corr: the bf16 correlation needs C %% 64 == 0 and N %% 128 == 0 for shift_sz = 1 (got %d, %d)", p.K, p.N);
     if (int rc = attention_limits(p.Cp, p.N, M, p.Mc)) return rc;
     if (ws_bytes < p.total) return fail(IPSR_ERR_WORKSPACE, "ipsr_forward: workspace %zu < %zu", ws_bytes, p.total);
@@ -314,16 +312,16 @@ static int forward_impl(const float* x, const float* ref, const int32_t* mask_po
             if (int rc = launch_corr_R_bf16(x, ref, B, C, h * w, R, slice[WS_CORR], sz[WS_CORR], st)) return rc;
         } else {
             CorrPartials unused;
-            if (int rc = launch_corr_argmax(x, ref, B, C, h * w, nullptr, nullptr, R, slice[WS_CORR], sz[WS_CORR], st, &unused, 0)) return rc;
+            if (int rc = launch_corr_argmax(x, ref, B, C, h * w, nullptr, nullptr, R, slice[WS_CORR], sz[WS_CORR], st, &unused)) return rc;
         }
         if (int rc = launch_window_corr_argmax(R, inv, B, h, w, patch, slice[WS_RU], sz[WS_RU], st, &a.part)) return rc;
         outs = reinterpret_cast<float*>(slice[WS_OU]);
     } else {
-        if (int rc = launch_patch_normalize(x, B, p.K, p.N, xn, xT, p.Cp, inv, st, p.ld, p.ld)) return rc;
+        if (int rc = launch_patch_normalize(x, B, p.K, p.N, xn, xT, p.Cp, inv, st)) return rc;
         if (corr_bf16) {
-            if (int rc = launch_corr_argmax_bf16(xn, ref, B, p.K, p.N, ind, vmax, slice[WS_CORR], sz[WS_CORR], st, &a.part, p.ld)) return rc;
+            if (int rc = launch_corr_argmax_bf16(xn, ref, B, p.K, p.N, ind, vmax, slice[WS_CORR], sz[WS_CORR], st, &a.part)) return rc;
         } else {
-            if (int rc = launch_corr_argmax(xn, ref, B, p.K, p.N, ind, vmax, nullptr, slice[WS_CORR], sz[WS_CORR], st, &a.part, p.ld)) return rc;
+            if (int rc = launch_corr_argmax(xn, ref, B, p.K, p.N, ind, vmax, nullptr, slice[WS_CORR], sz[WS_CORR], st, &a.part)) return rc;
         }
     }
     a.xT = xT; a.inv = inv; a.ind = ind; a.vmax = vmax; a.mpi = mask_point_idx;

@@ -26,6 +26,15 @@
 // Grid: (sample, q-tile, k-split) with an XCD-aware remap so that all workgroups of a sample — which
 // share its xn and ref tiles — sit on one XCD's L2.  k-splits keep >= 2 workgroups per CU busy at the
 // batch-8 / N=1024 size; their partial (max, argmax) are merged by a tiny second kernel.
+//
+// Layout of the file.  Three correlation kernels: generic (any C and N, every access guarded), fast (whole tiles), bf16; template
+// flags are <RAGGED, WRITE_S>, in that order, where a kernel has them.  Operands are [C][N]: the kernels' row stride argument ld is
+// N, except that the bf16 R entry pads its packed rows to whole tiles.  Each kernel carries its own copy of the workgroup decode,
+// the start rule, the per-k-tile fold and the final merge: shared __forceinline__ helpers for them were built and measured, and
+// not taken (profiles/corr_argmax_refactor_ab.txt: they change the compiled kernels, for two of the three also the registers).
+// The order rule itself is one function each, takes_over / better in ipsr_common.h.  On the host one plan (corr_plan,
+// window_plan) feeds both the byte counts and the launchers, finish_argmax is the one tail, and the two bf16 entries share
+// launch_bf16.
 #include "ipsr_common.h"
 
 namespace ipsr {
@@ -48,7 +57,8 @@ __device__ unsigned long long g_probe[2 * 8192];
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-template <bool FAST, bool WRITE_S>
+// Generic kernel: any C and N, every load and store guarded.
+template <bool WRITE_S>
 __global__ void __launch_bounds__(NTHREADS, 2)
 corr_argmax_kernel(const float* __restrict__ xn, const float* __restrict__ ref, int C, int N, int ld,
                    int qtiles, int ksplit, int ktiles, int kt_per_wg,
@@ -101,20 +111,15 @@ corr_argmax_kernel(const float* __restrict__ xn, const float* __restrict__ ref, 
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int c = c0 + ld_row + 8 * i;
-                if (FAST) {
-                    ra[i] = *reinterpret_cast<const float4*>(A + (size_t)c * ld + k0 + ld_c4);
-                    rb[i] = *reinterpret_cast<const float4*>(R + (size_t)c * ld + q0 + ld_c4);
-                } else {
-                    float va[4], vb[4];
+                float va[4], vb[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int kc = k0 + ld_c4 + e, qc = q0 + ld_c4 + e;
-                        va[e] = (c < C && kc < N) ? A[(size_t)c * ld + kc] : 0.0f;
-                        vb[e] = (c < C && qc < N) ? R[(size_t)c * ld + qc] : 0.0f;
-                    }
-                    ra[i] = make_float4(va[0], va[1], va[2], va[3]);
-                    rb[i] = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                for (int e = 0; e < 4; ++e) {
+                    const int kc = k0 + ld_c4 + e, qc = q0 + ld_c4 + e;
+                    va[e] = (c < C && kc < N) ? A[(size_t)c * ld + kc] : 0.0f;
+                    vb[e] = (c < C && qc < N) ? R[(size_t)c * ld + qc] : 0.0f;
                 }
+                ra[i] = make_float4(va[0], va[1], va[2], va[3]);
+                rb[i] = make_float4(vb[0], vb[1], vb[2], vb[3]);
             }
         };
         auto sstore = [&](int buf) {
@@ -157,9 +162,9 @@ corr_argmax_kernel(const float* __restrict__ xn, const float* __restrict__ ref, 
                 for (int e = 0; e < 16; ++e) {
                     const int k = k0 + wm * 64 + im * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                     const float v = acc[im][jn][e];
-                    if (FAST || k < N) {
+                    if (k < N) {
                         if (takes_over(v, best[jn])) { best[jn] = v; bidx[jn] = k; }
-                        if (WRITE_S) { if (FAST || q < N) S_out[((size_t)b * N + k) * N + q] = v; }
+                        if (WRITE_S) { if (q < N) S_out[((size_t)b * N + k) * N + q] = v; }
                     }
                 }
             }
@@ -211,10 +216,7 @@ corr_argmax_kernel(const float* __restrict__ xn, const float* __restrict__ ref, 
 //     k-step are 256 bytes apart in LDS = ONE ds_read2st64_b32 with immediate offsets each, i.e. 2 LDS instructions
 //     and no address arithmetic per 4 MFMAs; three fragment register sets in rotation, the reads of k-step kk+1
 //     pinned in front of the MFMAs of kk.
-//
-// RAGGED: the operands are [C][ld] with ld a multiple of 128 and the columns [N, ld) zero (shift_sz > 1 window grids);
-// patches k >= N are kept out of the arg-max and columns q >= N are not stored.
-template <bool WRITE_S, bool RAGGED>
+template <bool WRITE_S>
 __global__ void __launch_bounds__(NTHREADS, 2)
 corr_argmax_fast_kernel(const float* __restrict__ xn, const float* __restrict__ ref, int C, int N, int ld,
                         int qtiles, int ksplit, int ktiles, int kt_per_wg,
@@ -245,7 +247,6 @@ corr_argmax_fast_kernel(const float* __restrict__ xn, const float* __restrict__ 
     // start from the first row this lane will see, value -inf (see the generic kernel)
     float best[2] = {-INFINITY, -INFINITY};
     int bidx[2] = {kt_lo * BM + wm * 32 + 4 * h, kt_lo * BM + wm * 32 + 4 * h};
-    if (RAGGED && bidx[0] >= N) bidx[0] = bidx[1] = kt_lo * BM;
 
     // LDS-DMA: a stage = 2 operands x FBK rows x 512 B = 2*FBK/2 = 16 pieces of 1 KiB (2 rows); wave w owns row
     // pairs w and w+4 of A and of B -> NP = 4 pieces per wave per stage.  Lane -> (row parity, 16-byte column).
@@ -343,10 +344,8 @@ corr_argmax_fast_kernel(const float* __restrict__ xn, const float* __restrict__ 
                 for (int e = 0; e < 16; ++e) {
                     const int k = k0 + wm * 32 + im * 64 + (e & 3) + 8 * (e >> 2) + 4 * h;
                     const float v = acc[im][jn][e];
-                    if (!RAGGED || k < N) {
-                        if (takes_over(v, best[jn])) { best[jn] = v; bidx[jn] = k; }
-                        if (WRITE_S) { if (!RAGGED || q < N) S_out[((size_t)b * N + k) * N + q] = v; }
-                    }
+                    if (takes_over(v, best[jn])) { best[jn] = v; bidx[jn] = k; }
+                    if (WRITE_S) S_out[((size_t)b * N + k) * N + q] = v;
                 }
             }
         }
@@ -377,10 +376,8 @@ corr_argmax_fast_kernel(const float* __restrict__ xn, const float* __restrict__ 
             const int oi = red_i[(wn * 2 + jn) * 32 + r];
             if (better(ov, oi, best[jn], bidx[jn])) { best[jn] = ov; bidx[jn] = oi; }
             const int q = q0 + wn * 32 + jn * 64 + r;
-            if (!RAGGED || q < N) {
-                pval[((size_t)b * ksplit + ks) * N + q] = best[jn];
-                pidx[((size_t)b * ksplit + ks) * N + q] = bidx[jn];
-            }
+            pval[((size_t)b * ksplit + ks) * N + q] = best[jn];
+            pidx[((size_t)b * ksplit + ks) * N + q] = bidx[jn];
         }
     }
 }
@@ -425,6 +422,8 @@ __global__ void __launch_bounds__(256) pack_bf16_k8_kernel(const float* __restri
     dst[((size_t)b * C8 + g) * ld + n] = o;
 }
 
+// RAGGED: the packed operands have a row stride ld > N, a multiple of 128, with the columns [N, ld) zero (shift_sz > 1: N = h*w);
+// patches k >= N are kept out of the arg-max and columns q >= N are not stored.
 // WRITE_S: also store every correlation S_out[b][k][q] (N x N; the 1x1 correlation R of the shift_sz > 1 path)
 template <bool RAGGED, bool WRITE_S>
 __global__ void __launch_bounds__(NTHREADS, 2)
@@ -567,49 +566,6 @@ __global__ void __launch_bounds__(256) window_corr_argmax_kernel(const float* __
     pidx[((size_t)b * ksplit + ks) * Np + q] = bidx;
 }
 
-__global__ void argmax_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx, int B, int N, int ksplit,
-                                    int32_t* __restrict__ ind, float* __restrict__ vmax);
-
-// partial buffers of the window arg-max: [B][ksplit][N'] values + indices
-static void window_plan(int B, int Np, int* ksplit, int* kper)
-{
-    const int qblocks = cdiv(Np, 256) * B;
-    int ks = 1;
-    while (qblocks * ks < 1024 && ks < 64 && cdiv(Np, ks * 2) >= 32) ks *= 2;
-    *kper = cdiv(Np, ks);
-    *ksplit = cdiv(Np, *kper);
-}
-
-size_t window_corr_ws_bytes(int B, int Np)
-{
-    int ks, kper;
-    window_plan(B, Np, &ks, &kper);
-    return 2 * align_up((size_t)B * ks * Np * 4, 256) + 2 * align_up((size_t)B * Np * 4, 256) + 256;
-}
-
-int launch_window_corr_argmax(const float* R, const float* inv, int B, int h, int w, int patch, void* ws, size_t ws_bytes, hipStream_t st,
-                              CorrPartials* partials)
-{
-    const int nW = w - patch + 1, Np = (h - patch + 1) * nW;
-    int ks, kper;
-    window_plan(B, Np, &ks, &kper);
-    if (ws_bytes < window_corr_ws_bytes(B, Np)) return fail(IPSR_ERR_WORKSPACE, "window correlation: workspace %zu < %zu", ws_bytes, window_corr_ws_bytes(B, Np));
-    Carver cv(ws, ws_bytes);
-    float* pval = cv.take<float>((size_t)B * ks * Np);
-    int32_t* pidx = cv.take<int32_t>((size_t)B * ks * Np);
-    float* mval = cv.take<float>((size_t)B * Np);
-    int32_t* midx = cv.take<int32_t>((size_t)B * Np);
-    window_corr_argmax_kernel<<<dim3(cdiv(Np, 256), ks, B), 256, 0, st>>>(R, inv, h * w, w, nW, Np, patch, ks, kper, pval, pidx);
-    if (int rc = check_launch("window_corr_argmax_kernel")) return rc;
-    // fold the k-splits here, once: the stage kernel's consumers (one merge per 32x32 gather tile over K = C*p*p channels)
-    // would otherwise re-fold the same 16 partials thousands of times
-    argmax_merge_kernel<<<cdiv(B * Np, 256), 256, 0, st>>>(pval, pidx, B, Np, ks, midx, mval);
-    partials->pval = mval;
-    partials->pidx = midx;
-    partials->ksplit = 1;
-    return check_launch("argmax_merge_kernel");
-}
-
 // merge the k-split partials in ascending k order
 __global__ void __launch_bounds__(256) argmax_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
                                                            int B, int N, int ksplit, int32_t* __restrict__ ind,
@@ -629,122 +585,175 @@ __global__ void __launch_bounds__(256) argmax_merge_kernel(const float* __restri
     vmax[i] = bv;
 }
 
-static void plan(int B, int N, int* qtiles, int* ktiles, int* ksplit, int* kt_per_wg)
+// The one tail of the launchers: hand the k-split partials to the caller (its consumer folds them: merged_argmax), or fold them
+// here into ind / vmax.
+static int finish_argmax(float* pval, int32_t* pidx, int B, int N, int ksplit, int32_t* ind, float* vmax, hipStream_t st,
+                         CorrPartials* partials)
 {
-    *qtiles = cdiv(N, BN);
-    *ktiles = cdiv(N, BM);
+    if (partials) {
+        partials->pval = pval;
+        partials->pidx = pidx;
+        partials->ksplit = ksplit;
+        return IPSR_OK;
+    }
+    argmax_merge_kernel<<<cdiv(B * N, 256), 256, 0, st>>>(pval, pidx, B, N, ksplit, ind, vmax);
+    return check_launch("argmax_merge_kernel");
+}
+
+// A launcher's workspace: the partial values and indices [B][ksplit][N], then two more arrays of `extra_bytes` each (the merged
+// values and indices of the window arg-max; the packed operands of the bf16 path).  Every size is a multiple of 256 bytes.  The
+// byte count and the carve are both read off this, so they cannot drift apart.
+struct WsLayout {
+    size_t part_bytes, extra_bytes;
+    size_t total() const { return 2 * part_bytes + 2 * extra_bytes + 256; }
+    float* pval(void* ws) const { return reinterpret_cast<float*>(ws); }
+    int32_t* pidx(void* ws) const { return reinterpret_cast<int32_t*>(static_cast<char*>(ws) + part_bytes); }
+    template <typename T>
+    T* extra(void* ws, int i) const { return reinterpret_cast<T*>(static_cast<char*>(ws) + 2 * part_bytes + i * extra_bytes); }
+};
+
+struct WindowPlan : WsLayout {
+    int ksplit, kper;
+};
+
+static WindowPlan window_plan(int B, int Np)
+{
+    WindowPlan p;
+    const int qblocks = cdiv(Np, 256) * B;
+    int ks = 1;
+    while (qblocks * ks < 1024 && ks < 64 && cdiv(Np, ks * 2) >= 32) ks *= 2;
+    p.kper = cdiv(Np, ks);
+    p.ksplit = cdiv(Np, p.kper);
+    p.part_bytes = align_up((size_t)B * p.ksplit * Np * 4, 256);
+    p.extra_bytes = align_up((size_t)B * Np * 4, 256);
+    return p;
+}
+
+size_t window_corr_ws_bytes(int B, int Np) { return window_plan(B, Np).total(); }
+
+int launch_window_corr_argmax(const float* R, const float* inv, int B, int h, int w, int patch, void* ws, size_t ws_bytes, hipStream_t st,
+                              CorrPartials* partials)
+{
+    const int nW = w - patch + 1, Np = (h - patch + 1) * nW;
+    const WindowPlan p = window_plan(B, Np);
+    if (ws_bytes < p.total()) return fail(IPSR_ERR_WORKSPACE, "window correlation: workspace %zu < %zu", ws_bytes, p.total());
+    float* pval = p.pval(ws);
+    int32_t* pidx = p.pidx(ws);
+    float* mval = p.extra<float>(ws, 0);
+    int32_t* midx = p.extra<int32_t>(ws, 1);
+    window_corr_argmax_kernel<<<dim3(cdiv(Np, 256), p.ksplit, B), 256, 0, st>>>(R, inv, h * w, w, nW, Np, patch, p.ksplit, p.kper, pval, pidx);
+    if (int rc = check_launch("window_corr_argmax_kernel")) return rc;
+    // fold the k-splits here, once: the stage kernel's consumers (one merge per 32x32 gather tile over K = C*p*p channels)
+    // would otherwise re-fold the same 16 partials thousands of times
+    if (int rc = finish_argmax(pval, pidx, B, Np, p.ksplit, midx, mval, st, nullptr)) return rc;
+    return finish_argmax(mval, midx, B, Np, 1, nullptr, nullptr, st, partials);
+}
+
+struct CorrPlan : WsLayout {
+    int qtiles, ktiles, ksplit, kt_per_wg;
+};
+
+// C8 channel groups packed with row stride ld: the bf16 path's two operands ([C/8][ld][8] bf16 each); 0 on the fp32 path
+static CorrPlan corr_plan(int B, int N, int C8 = 0, int ld = 0)
+{
+    CorrPlan p;
+    p.qtiles = cdiv(N, BN);
+    p.ktiles = cdiv(N, BM);
     // The chip runs 512 workgroups at a time (256 CUs x 2).  Pick the k-tiles per workgroup that minimises
     // (rounds of 512 workgroups) x (k-tiles per workgroup + a fixed per-workgroup cost of about a quarter tile); on
     // ties the larger one (fewer partials).  N=1024, B=8: 8 splits of 1 tile (512 workgroups).  The 3x3-patch window
     // grid N'=3844, B=4: 31 q-tiles x 4 splits of 8,8,8,7 tiles = 496 workgroups in ONE round (5 splits of 7 would be
     // 620 workgroups = two rounds, the second one a fifth full).
-    const int base = B * *qtiles;
+    const int base = B * p.qtiles;
     long best_cost = -1;
-    int best = *ktiles;
-    for (int kpw = *ktiles; kpw >= 1; --kpw) {
-        const int ks = cdiv(*ktiles, kpw);
+    int best = p.ktiles;
+    for (int kpw = p.ktiles; kpw >= 1; --kpw) {
+        const int ks = cdiv(p.ktiles, kpw);
         const long rounds = cdiv(base * ks, 512);
         const long cost = rounds * (4L * kpw + 1);
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = kpw; }
     }
-    *kt_per_wg = best;
-    *ksplit = cdiv(*ktiles, best);
-}
-
-// bf16 path: the packed operands ([C/8][ld][8] bf16 each) live in the workspace behind the partials
-static size_t bf16_pack_bytes(int B, int C, int ld) { return align_up((size_t)B * ((C + 7) / 8) * ld * 16, 256); }
-
-bool corr_bf16_supported(int C, int ld) { return C % (16 * PF) == 0 && ld % BM == 0; }
-
-size_t corr_argmax_bf16_ws_bytes(int B, int C, int N, int ld)
-{
-    if (ld <= 0) ld = N;
-    return corr_argmax_ws_bytes(B, C, N) + 2 * bf16_pack_bytes(B, C, ld);
+    p.kt_per_wg = best;
+    p.ksplit = cdiv(p.ktiles, best);
+    p.part_bytes = align_up((size_t)B * p.ksplit * N * 4, 256);
+    p.extra_bytes = align_up((size_t)B * C8 * ld * 16, 256);
+    return p;
 }
 
 size_t corr_argmax_ws_bytes(int B, int C, int N)
 {
     (void)C;
-    int qt, kt, ks, kpw;
-    plan(B, N, &qt, &kt, &ks, &kpw);
-    return 2 * align_up((size_t)B * ks * N * 4, 256) + 256;
+    return corr_plan(B, N).total();
 }
 
 int launch_corr_argmax(const float* xn, const float* ref, int B, int C, int N, int32_t* ind, float* vmax,
-                       float* S_out, void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials, int ld)
+                       float* S_out, void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials)
 {
-    if (ld <= 0) ld = N;
-    int qt, kt, ks, kpw;
-    plan(B, N, &qt, &kt, &ks, &kpw);
-    if (ws_bytes < corr_argmax_ws_bytes(B, C, N))
-        return fail(IPSR_ERR_WORKSPACE, "ipsr_corr_argmax: workspace %zu < %zu", ws_bytes, corr_argmax_ws_bytes(B, C, N));
-    Carver cv(ws, ws_bytes);
-    float* pval = cv.take<float>((size_t)B * ks * N);
-    int32_t* pidx = cv.take<int32_t>((size_t)B * ks * N);
-    // fast path: whole 128-column tiles in memory (ld), whole 16-channel stages, 16-byte aligned rows
-    const bool fast = (ld % BM == 0) && (ld >= qt * BN) && (C % FBK == 0) &&
-                      ((reinterpret_cast<uintptr_t>(xn) | reinterpret_cast<uintptr_t>(ref)) & 15u) == 0;
-    const int grid = B * qt * ks;
+    const CorrPlan p = corr_plan(B, N);
+    if (ws_bytes < p.total()) return fail(IPSR_ERR_WORKSPACE, "ipsr_corr_argmax: workspace %zu < %zu", ws_bytes, p.total());
+    float* pval = p.pval(ws);
+    int32_t* pidx = p.pidx(ws);
+    // fast path: whole 128-column tiles, whole 16-channel stages, 16-byte aligned rows
+    const bool fast = (N % BM == 0) && (C % FBK == 0) && ((reinterpret_cast<uintptr_t>(xn) | reinterpret_cast<uintptr_t>(ref)) & 15u) == 0;
+    const int grid = B * p.qtiles * p.ksplit;
+    // the kernels' row stride argument ld is N
     profile_mark_start(st);
-    if (fast && ld == N) {
-        if (S_out) corr_argmax_fast_kernel<true, false><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
-        else corr_argmax_fast_kernel<false, false><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
-    } else if (fast) {
-        if (S_out) corr_argmax_fast_kernel<true, true><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
-        else corr_argmax_fast_kernel<false, true><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
+    if (fast) {
+        if (S_out) corr_argmax_fast_kernel<true><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, N, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
+        else corr_argmax_fast_kernel<false><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, N, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
     } else {
-        if (S_out) corr_argmax_kernel<false, true><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
-        else corr_argmax_kernel<false, false><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, ld, qt, ks, kt, kpw, S_out, pval, pidx);
+        if (S_out) corr_argmax_kernel<true><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, N, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
+        else corr_argmax_kernel<false><<<grid, NTHREADS, 0, st>>>(xn, ref, C, N, N, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
     }
     profile_mark_stop(st);
     if (int rc = check_launch("corr_argmax_kernel")) return rc;
-    if (partials) {
-        partials->pval = pval;
-        partials->pidx = pidx;
-        partials->ksplit = ks;
-        return IPSR_OK;
-    }
-    argmax_merge_kernel<<<cdiv(B * N, 256), 256, 0, st>>>(pval, pidx, B, N, ks, ind, vmax);
-    return check_launch("argmax_merge_kernel");
+    return finish_argmax(pval, pidx, B, N, p.ksplit, ind, vmax, st, partials);
+}
+
+// ---- bf16 path: the packed operands live in the workspace behind the partials ----
+// the arg-max entry takes whole tiles only (row stride N); the R entry pads the packed rows to whole tiles itself
+bool corr_bf16_supported(int C, int N) { return C % (16 * PF) == 0 && N % BM == 0; }
+bool corr_R_bf16_supported(int C) { return C % (16 * PF) == 0; }
+static int padded_stride(int N) { return cdiv(N, BM) * BM; }
+
+static CorrPlan bf16_plan(int B, int C, int N, int ld) { return corr_plan(B, N, (C + 7) / 8, ld); }
+
+size_t corr_argmax_bf16_ws_bytes(int B, int C, int N) { return bf16_plan(B, C, N, N).total(); }
+size_t corr_R_bf16_ws_bytes(int B, int C, int N) { return bf16_plan(B, C, N, padded_stride(N)).total(); }
+
+// Both bf16 entries behind their own support rule: pack xn / ref ([C][N] fp32) to bf16 with row stride ld (a multiple of 128, zero
+// columns past N), run the kernel, then the tail.  S_out == NULL: the arg-max entry (ld == N).
+static int launch_bf16(const char* who, const float* xn, const float* ref, int B, int C, int N, int ld, float* S_out, int32_t* ind, float* vmax,
+                       void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials)
+{
+    const int C8 = C / 8;
+    const CorrPlan p = bf16_plan(B, C, N, ld);
+    if (ws_bytes < p.total()) return fail(IPSR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, p.total());
+    float* pval = p.pval(ws);
+    int32_t* pidx = p.pidx(ws);
+    uint4* xp = p.extra<uint4>(ws, 0);
+    uint4* rp = p.extra<uint4>(ws, 1);
+    const dim3 pg(cdiv(ld, 256), C8, B);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(xn, C, N, N, ld, C8, xp);
+    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, N, N, ld, C8, rp);
+    if (int rc = check_launch("pack_bf16_k8_kernel")) return rc;
+    const int grid = B * p.qtiles * p.ksplit;
+    profile_mark_start(st);
+    if (!S_out) corr_argmax_bf16_kernel<false, false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
+    else if (ld == N) corr_argmax_bf16_kernel<false, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
+    else corr_argmax_bf16_kernel<true, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, p.qtiles, p.ksplit, p.ktiles, p.kt_per_wg, S_out, pval, pidx);
+    profile_mark_stop(st);
+    if (int rc = check_launch("corr_argmax_bf16_kernel")) return rc;
+    return finish_argmax(pval, pidx, B, N, p.ksplit, ind, vmax, st, partials);
 }
 
 // bf16 MFMA variant of launch_corr_argmax: xn / ref are the SAME fp32 operands; they are packed to bf16 here.
 int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int N, int32_t* ind, float* vmax,
-                            void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials, int ld)
+                            void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials)
 {
-    if (ld <= 0) ld = N;
-    if (!corr_bf16_supported(C, ld))
-        return fail(IPSR_ERR_UNSUPPORTED, "bf16 correlation: needs C %% %d == 0 and a row stride that is a multiple of %d (got C=%d, ld=%d)",
-                    16 * PF, BM, C, ld);
-    int qt, kt, ks, kpw;
-    plan(B, N, &qt, &kt, &ks, &kpw);
-    if (ld < qt * BN) return fail(IPSR_ERR_UNSUPPORTED, "bf16 correlation: row stride %d < %d", ld, qt * BN);
-    if (ws_bytes < corr_argmax_bf16_ws_bytes(B, C, N, ld))
-        return fail(IPSR_ERR_WORKSPACE, "ipsr_corr_argmax_bf16: workspace %zu < %zu", ws_bytes, corr_argmax_bf16_ws_bytes(B, C, N, ld));
-    Carver cv(ws, ws_bytes);
-    float* pval = cv.take<float>((size_t)B * ks * N);
-    int32_t* pidx = cv.take<int32_t>((size_t)B * ks * N);
-    const int C8 = C / 8;
-    uint4* xp = cv.take<uint4>((size_t)B * C8 * ld);
-    uint4* rp = cv.take<uint4>((size_t)B * C8 * ld);
-    const dim3 pg(cdiv(ld, 256), C8, B);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(xn, C, ld, ld, ld, C8, xp);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, ld, ld, ld, C8, rp);
-    if (int rc = check_launch("pack_bf16_k8_kernel")) return rc;
-    const int grid = B * qt * ks;
-    profile_mark_start(st);
-    if (ld == N) corr_argmax_bf16_kernel<false, false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, nullptr, pval, pidx);
-    else corr_argmax_bf16_kernel<true, false><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, nullptr, pval, pidx);
-    profile_mark_stop(st);
-    if (int rc = check_launch("corr_argmax_bf16_kernel")) return rc;
-    if (partials) {
-        partials->pval = pval;
-        partials->pidx = pidx;
-        partials->ksplit = ks;
-        return IPSR_OK;
-    }
-    argmax_merge_kernel<<<cdiv(B * N, 256), 256, 0, st>>>(pval, pidx, B, N, ks, ind, vmax);
-    return check_launch("argmax_merge_kernel");
+    if (!corr_bf16_supported(C, N))
+        return fail(IPSR_ERR_UNSUPPORTED, "bf16 correlation: needs C %% %d == 0 and N %% %d == 0 (got C=%d, N=%d)", 16 * PF, BM, C, N);
+    return launch_bf16("ipsr_corr_argmax_bf16", xn, ref, B, C, N, N, nullptr, ind, vmax, ws, ws_bytes, st, partials);
 }
 
 // shift_sz > 1 on the bf16 kernel: the 1x1 correlation R = x^T ref [B][N][N] (N = h*w) of the shifted-sum form, on the RAW
@@ -755,29 +764,9 @@ int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int
 // than the fp32 R + stencil at BASELINE config 4: DESIGN.md 5.4.)
 int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, float* R, void* ws, size_t ws_bytes, hipStream_t st)
 {
-    const int ld = cdiv(N, BM) * BM;
-    if (!corr_bf16_supported(C, ld))
-        return fail(IPSR_ERR_UNSUPPORTED, "bf16 window correlation: needs C %% %d == 0 (got %d)", 16 * PF, C);
-    int qt, kt, ks, kpw;
-    plan(B, N, &qt, &kt, &ks, &kpw);
-    if (ws_bytes < corr_argmax_bf16_ws_bytes(B, C, N, ld))
-        return fail(IPSR_ERR_WORKSPACE, "bf16 window correlation: workspace %zu < %zu", ws_bytes, corr_argmax_bf16_ws_bytes(B, C, N, ld));
-    Carver cv(ws, ws_bytes);
-    float* pval = cv.take<float>((size_t)B * ks * N);
-    int32_t* pidx = cv.take<int32_t>((size_t)B * ks * N);
-    const int C8 = C / 8;
-    uint4* xp = cv.take<uint4>((size_t)B * C8 * ld);
-    uint4* rp = cv.take<uint4>((size_t)B * C8 * ld);
-    const dim3 pg(cdiv(ld, 256), C8, B);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(x, C, N, N, ld, C8, xp);
-    pack_bf16_k8_kernel<<<pg, 256, 0, st>>>(ref, C, N, N, ld, C8, rp);
-    if (int rc = check_launch("pack_bf16_k8_kernel")) return rc;
-    const int grid = B * qt * ks;
-    profile_mark_start(st);
-    if (ld == N) corr_argmax_bf16_kernel<false, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, R, pval, pidx);
-    else corr_argmax_bf16_kernel<true, true><<<grid, NTHREADS, 0, st>>>(xp, rp, C8, N, ld, qt, ks, kt, kpw, R, pval, pidx);
-    profile_mark_stop(st);
-    return check_launch("corr_argmax_bf16_kernel");
+    if (!corr_R_bf16_supported(C)) return fail(IPSR_ERR_UNSUPPORTED, "bf16 window correlation: needs C %% %d == 0 (got %d)", 16 * PF, C);
+    CorrPartials unused;
+    return launch_bf16("bf16 window correlation", x, ref, B, C, N, padded_stride(N), R, nullptr, nullptr, ws, ws_bytes, st, &unused);
 }
 
 }  // namespace ipsr

@@ -164,20 +164,23 @@ size_t window_corr_ws_bytes(int B, int Np);
 int launch_window_corr_argmax(const float* R, const float* inv, int B, int h, int w, int patch, void* ws, size_t ws_bytes, hipStream_t st,
                               CorrPartials* partials);
 size_t corr_argmax_ws_bytes(int B, int C, int N);
-// ld: row stride of xn and ref (0 = N).  ld > N: operands zero-padded to whole 128-column tiles, patches k >= N are
-// excluded from the arg-max.
+// xn, ref: [B][C][N], rows N apart.  S_out != NULL: every correlation is stored as well ([B][N][N]).
 // partials != NULL: skip the merge kernel and hand the k-split partials to the caller (ind/vmax are then written by the
 // consumer that merges them: the attention stage kernel)
 int launch_corr_argmax(const float* xn, const float* ref, int B, int C, int N, int32_t* ind, float* vmax,
-                       float* S_out, void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials = nullptr, int ld = 0);
+                       float* S_out, void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials = nullptr);
 
-// bf16-MFMA variant (opt-in): same fp32 operands, packed to bf16 inside; needs corr_bf16_supported(C, ld)
-bool corr_bf16_supported(int C, int ld);
-size_t corr_argmax_bf16_ws_bytes(int B, int C, int N, int ld = 0);
+// bf16-MFMA variant (opt-in): same fp32 operands, packed to bf16 inside; needs corr_bf16_supported(C, N): C % 64 == 0 and whole
+// 128-column tiles (N % 128 == 0)
+bool corr_bf16_supported(int C, int N);
+size_t corr_argmax_bf16_ws_bytes(int B, int C, int N);
 int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int N, int32_t* ind, float* vmax,
-                            void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials = nullptr, int ld = 0);
+                            void* ws, size_t ws_bytes, hipStream_t st, CorrPartials* partials = nullptr);
 // shift_sz > 1 on the bf16 kernel: the 1x1 correlation R [B][N][N] of the raw features x, ref [B][C][N] (operands rounded to
-// bf16), for launch_window_corr_argmax; workspace corr_argmax_bf16_ws_bytes(B, C, N, roundup(N, 128)), needs C % 64 == 0
+// bf16), for launch_window_corr_argmax.  Any N (the packed rows are padded to whole tiles inside); needs
+// corr_R_bf16_supported(C): C % 64 == 0; workspace corr_R_bf16_ws_bytes(B, C, N)
+bool corr_R_bf16_supported(int C);
+size_t corr_R_bf16_ws_bytes(int B, int C, int N);
 int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, float* R, void* ws, size_t ws_bytes, hipStream_t st);
 
 // conv_gemm.hip — implicit-GEMM convolutions on the fp32 matrix cores (see the file header)

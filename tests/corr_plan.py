@@ -3,19 +3,19 @@ restated in Python: which kernel instantiation, k-split plan and grid a shape re
 
 A plain module (like thin_conv_plan.py).  tests/test_corr_plan.py ties it to the built library through the workspace queries and
 proves that the case tables below reach every row of the variant table; tests/test_gpu_corr_variants.py runs the tables.  Each
-function names the lines it mirrors; integer arithmetic is C's (all operands non-negative, so `//` is the same division).
+function names the function or kernel it mirrors; integer arithmetic is C's (all operands non-negative, so `//` is the same division).
 
 What reading the launchers shows, and the sweep of tests/test_corr_plan.py confirms through the byte counts:
   * `window_plan` never launches an empty k-slice.  Its doubling loop may ask for more slices than `kper`-long pieces fit into N'
-    (N' = 1985 .. 2016 at B = 1: 64 asked, kper 32), but the count it returns is recomputed as ceil(N' / kper) (:580): 63 slices, the
+    (N' = 1985 .. 2016 at B = 1: 64 asked, kper 32), but the count it returns is recomputed as ceil(N' / kper): 63 slices, the
     last one 16 windows long.  The case `win_empty_last_slice` keeps its shape (N' = 2000): it is the trimmed plan, not an empty
     slice, and `(-inf, k_lo)` with k_lo >= N' is never written.
-  * two instantiations of the file cannot be selected: see UNREACHABLE.
+  * every instantiation of the file can be selected by a call: UNREACHABLE is empty.
 """
 
-BM = BN = 128                                             # corr_argmax.hip:35-36
-FBK = 16                                                  # :38
-PF = 4                                                    # :404
+BM = BN = 128                                             # corr_argmax.hip: BM, BN
+FBK = 16                                                  # FBK
+PF = 4                                                    # PF
 IC_MAX_BLOCKS, IC_FUSED_BLOCKS = 4096, 512                # innercos.hip:15, :155
 IC_BWD_BLOCKS, IC_BWD_THREADS = 2048, 256                 # innercos.hip:169-172
 
@@ -30,8 +30,8 @@ def cdiv(a, b):
 
 # ---- the correlation ----------------------------------------------------------------------------------------------------------------
 def corr_plan(B, N):
-    """corr_argmax.hip:632-652 (`plan`) -> (qtiles, ktiles, ksplit, kt_per_wg, k-tiles of the last split).  A workgroup walks
-    `kt_per_wg` k-tiles of 128 patches; the last split's `kt_hi = min(ktiles, ...)` (:81, :244, :451) cuts it short when uneven."""
+    """corr_argmax.hip `corr_plan` -> (qtiles, ktiles, ksplit, kt_per_wg, k-tiles of the last split).  A workgroup walks
+    `kt_per_wg` k-tiles of 128 patches; the last split's `kt_hi = min(ktiles, ...)` (each kernel's decode) cuts it short when uneven."""
     qtiles, ktiles = cdiv(N, BN), cdiv(N, BM)
     base = B * qtiles
     best_cost, best = -1, ktiles
@@ -45,25 +45,26 @@ def corr_plan(B, N):
 
 
 def corr_ws(B, C, N):
-    """:665-671 (`corr_argmax_ws_bytes`): the [B][ksplit][N] partial values and indices."""
+    """`corr_argmax_ws_bytes` (`WsLayout::total` of `corr_plan`): the [B][ksplit][N] partial values and indices."""
     return 2 * align_up(B * corr_plan(B, N)[2] * N * 4, 256) + 256
 
 
 def corr_bf16_ws(B, C, N, ld=0):
-    """:655-663: the partials, then the two packed [C/8][ld][8] bf16 operands."""
+    """`bf16_plan`: the partials, then the two packed [C/8][ld][8] bf16 operands.  ld = N: `corr_argmax_bf16_ws_bytes` (the arg-max
+    entry); ld = N rounded up to 128: `corr_R_bf16_ws_bytes` (the window path's R entry)."""
     if ld <= 0:
         ld = N
     return corr_ws(B, C, N) + 2 * align_up(B * ((C + 7) // 8) * ld * 16, 256)
 
 
 def corr_bf16_supported(C, ld):
-    """:657."""
+    """`corr_bf16_supported` with ld = N (the arg-max entry); with ld = N rounded up to 128 it is `corr_R_bf16_supported`, C alone."""
     return C % (16 * PF) == 0 and ld % BM == 0
 
 
 def corr_variant(C, N, want_S):
-    """:685-698 with ld == N, the only stride a caller passes (api.hip:253, :317, :326).  The alignment term is always true behind
-    the entry points' own 16-byte check (api.hip:252, :281)."""
+    """`launch_corr_argmax`.  The alignment term is always true behind the entry points' own 16-byte check (`ipsr_corr_argmax`,
+    `forward_impl`)."""
     fast = N % BM == 0 and C % FBK == 0
     return ("fast" if fast else "generic"), bool(want_S)
 
@@ -71,17 +72,17 @@ def corr_variant(C, N, want_S):
 def corr_kernel_name(C, N, want_S):
     kind, S = corr_variant(C, N, want_S)
     s = "true" if S else "false"
-    return "corr_argmax_fast_kernel<%s,false>" % s if kind == "fast" else "corr_argmax_kernel<false,%s>" % s
+    return "corr_argmax_fast_kernel<%s>" % s if kind == "fast" else "corr_argmax_kernel<%s>" % s
 
 
 def fast_stages(C):
-    """LDS stages of the fast kernel (:243); its ring has 4 slots, 3 stages in flight (:39, :287)."""
+    """LDS stages of the fast kernel (`nstage`); its ring has 4 slots, 3 stages in flight (FNBUF, AHEAD)."""
     return C // FBK
 
 
 # ---- the window arg-max of shift_sz > 1 ------------------------------------------------------------------------------------------
 def window_split_sought(B, Np):
-    """The doubling loop of `window_plan` alone (:576-578): the power of two it stops at."""
+    """The doubling loop of `window_plan` alone: the power of two it stops at."""
     qblocks = cdiv(Np, 256) * B
     ks = 1
     while qblocks * ks < 1024 and ks < 64 and cdiv(Np, ks * 2) >= 32:
@@ -90,8 +91,8 @@ def window_split_sought(B, Np):
 
 
 def window_plan(B, Np):
-    """:574-581 -> (slices launched, kper, non-empty slices, length of the last non-empty one).  A slice s covers windows
-    [s kper, min(N', (s + 1) kper)) (:547) and is empty when s kper >= N'."""
+    """`window_plan` -> (slices launched, kper, non-empty slices, length of the last non-empty one).  A slice s covers windows
+    [s kper, min(N', (s + 1) kper)) (`window_corr_argmax_kernel`) and is empty when s kper >= N'."""
     kper = cdiv(Np, window_split_sought(B, Np))
     launched = cdiv(Np, kper)
     non_empty = sum(1 for s in range(launched) if s * kper < Np)
@@ -99,29 +100,29 @@ def window_plan(B, Np):
 
 
 def window_ws(B, Np):
-    """:583-588: the partials of every launched slice, then the merged values and indices."""
+    """`window_corr_ws_bytes` (`WsLayout::total` of `window_plan`): the partials of every launched slice, then the merged values and
+    indices."""
     ks = window_plan(B, Np)[0]
     return 2 * align_up(B * ks * Np * 4, 256) + 2 * align_up(B * Np * 4, 256) + 256
 
 
 def forward_ws(B, C, h, w, M, patch, corr_bf16):
-    """api.hip:96-133 (`plan_forward`): the total of the layer's fifteen workspace slices.  `window_plan` is visible from the host
+    """api.hip `plan_forward`: the total of the layer's fifteen workspace slices.  `window_plan` is visible from the host
     only through the WS_RU slice of this sum."""
     K = C * patch * patch
     N = (h - patch + 1) * (w - patch + 1)
     hw = h * w
     win_bf16 = patch > 1 and corr_bf16
-    ld = (hw + 127) & ~127 if win_bf16 else N
     Cp = (K + 7) & ~7
     Mc = (M + 31) & ~31 if M > 0 else 32
     Mx = M if M > 0 else 1
     if win_bf16:
-        corr = corr_bf16_ws(B, C, hw, ld)
+        corr = corr_bf16_ws(B, C, hw, cdiv(hw, BM) * BM)                                  # corr_R_bf16_ws_bytes
     elif patch > 1:
         corr = corr_ws(B, C, hw)
     else:
-        corr = corr_bf16_ws(B, K, N, ld) if corr_bf16 else corr_ws(B, K, N)
-    sz = [B * hw * hw * 4 if patch > 1 else B * K * ld * 4,                               # WS_XN
+        corr = corr_bf16_ws(B, K, N) if corr_bf16 else corr_ws(B, K, N)
+    sz = [B * hw * hw * 4 if patch > 1 else B * K * N * 4,                                # WS_XN
           B * N * Cp * 4,                                                                 # WS_XT
           B * N * 4,                                                                      # WS_INV
           corr,                                                                           # WS_CORR
@@ -298,28 +299,24 @@ def check_case(cid):
 # ---- the instantiations of corr_argmax.hip ----------------------------------------------------------------------------------------
 # (instantiation, selected at, case ids).  `case_plan(cid)["kernels"]` must hold the instantiation for each of its case ids.
 REACHABLE = (
-    ("corr_argmax_fast_kernel<false,false>", "corr_argmax.hip:689, :691",
+    ("corr_argmax_fast_kernel<false>", "launch_corr_argmax",
      ("fast_ring_exact", "fast_ring_wraps", "fast_kpw2_uneven", "fast_kpw3_uneven", "fast_kpw4_four_splits", "layer_kpw2_in_consumer_merge")),
-    ("corr_argmax_fast_kernel<true,false>", "corr_argmax.hip:689-690", ("fast_one_tile", "fast_two_stages", "fast_kpw2_even", "win_p2")),
-    ("corr_argmax_kernel<false,false>", "corr_argmax.hip:695, :697",
+    ("corr_argmax_fast_kernel<true>", "launch_corr_argmax", ("fast_one_tile", "fast_two_stages", "fast_kpw2_even", "win_p2")),
+    ("corr_argmax_kernel<false>", "launch_corr_argmax",
      ("generic_n_ragged_negative", "generic_kpw2_uneven", "generic_kpw3_uneven", "generic_kpw4")),
-    ("corr_argmax_kernel<false,true>", "corr_argmax.hip:695-696",
+    ("corr_argmax_kernel<true>", "launch_corr_argmax",
      ("generic_single", "generic_tiny", "generic_c_ragged_full_tiles", "generic_kpw2_even", "win_one_slice", "win_two_slices_short_last",
       "win_16_slices", "win_batch_limited", "win_empty_last_slice")),
-    ("pack_bf16_k8_kernel", "corr_argmax.hip:731-732, :772-773", ("bf16_one_tile", "bf16_kpw2_uneven", "win_bf16_full_tiles", "win_bf16_ragged")),
-    ("corr_argmax_bf16_kernel<false,false>", "corr_argmax.hip:736", ("bf16_one_tile", "bf16_kpw2_uneven")),
-    ("corr_argmax_bf16_kernel<false,true>", "corr_argmax.hip:777", ("win_bf16_full_tiles",)),
-    ("corr_argmax_bf16_kernel<true,true>", "corr_argmax.hip:778", ("win_bf16_ragged",)),
-    ("window_corr_argmax_kernel", "corr_argmax.hip:602", tuple(WINDOW_CASES)),
-    ("argmax_merge_kernel", "corr_argmax.hip:606, :707, :746", ("fast_kpw4_four_splits", "generic_kpw2_even", "bf16_kpw2_uneven", "win_16_slices")),
+    ("pack_bf16_k8_kernel", "launch_bf16", ("bf16_one_tile", "bf16_kpw2_uneven", "win_bf16_full_tiles", "win_bf16_ragged")),
+    ("corr_argmax_bf16_kernel<false,false>", "launch_bf16 (launch_corr_argmax_bf16)", ("bf16_one_tile", "bf16_kpw2_uneven")),
+    ("corr_argmax_bf16_kernel<false,true>", "launch_bf16 (launch_corr_R_bf16)", ("win_bf16_full_tiles",)),
+    ("corr_argmax_bf16_kernel<true,true>", "launch_bf16 (launch_corr_R_bf16)", ("win_bf16_ragged",)),
+    ("window_corr_argmax_kernel", "launch_window_corr_argmax", tuple(WINDOW_CASES)),
+    ("argmax_merge_kernel", "finish_argmax", ("fast_kpw4_four_splits", "generic_kpw2_even", "bf16_kpw2_uneven", "win_16_slices")),
 )
-# (instantiation, why no call selects it)
-UNREACHABLE = (
-    ("corr_argmax_fast_kernel<*,true> (RAGGED)", "corr_argmax.hip:692-694 needs ld != N; launch_corr_argmax is only called with ld == N or 0 "
-     "(api.hip:253 ipsr_corr_argmax, :317 ld 0, :326 p.ld == p.N at patch 1)"),
-    ("corr_argmax_bf16_kernel<true,false> (RAGGED)", "corr_argmax.hip:737 needs ld != N; launch_corr_argmax_bf16 is only called with ld == N or 0 "
-     "(api.hip:324 p.ld == p.N at patch 1, :392 ipsr_corr_argmax_bf16)"),
-)
+# (instantiation, why no call selects it): none.  The row stride that selected the RAGGED fast kernels and the RAGGED bf16 kernel
+# without WRITE_S is gone from the launchers, and those instantiations with it.
+UNREACHABLE = ()
 
 
 # ---- plan-level rows of the variant table: (variant, selected at, predicate on a plan, case ids) -----------------------------------
@@ -332,32 +329,32 @@ def _ic(**want):
 
 
 EDGES = (
-    ("fast kernel: 1 / 2 LDS stages (fewer than the 3 in flight)", "corr_argmax.hip:291-297", lambda p: p["kind"] == "fast" and p["stages"] in (1, 2) and "want_S" in p,
+    ("fast kernel: 1 / 2 LDS stages (fewer than the 3 in flight)", "corr_argmax_fast_kernel: prologue", lambda p: p["kind"] == "fast" and p["stages"] in (1, 2) and "want_S" in p,
      ("fast_one_tile", "fast_two_stages")),
-    ("fast kernel: 3 and 5 stages (at and past the 4-slot ring)", "corr_argmax.hip:300-331", lambda p: p["kind"] == "fast" and p["stages"] in (3, 5),
+    ("fast kernel: 3 and 5 stages (at and past the 4-slot ring)", "corr_argmax_fast_kernel: stage loop", lambda p: p["kind"] == "fast" and p["stages"] in (3, 5),
      ("fast_ring_exact", "fast_ring_wraps")),
-    ("fast kernel: kt_per_wg == 1", "corr_argmax.hip:644-651", _split("fast", lambda ks, kpw, last: kpw == 1),
+    ("fast kernel: kt_per_wg == 1", "corr_plan", _split("fast", lambda ks, kpw, last: kpw == 1),
      ("fast_one_tile", "fast_two_stages", "fast_ring_exact", "fast_ring_wraps")),
-    ("fast kernel: kt_per_wg >= 2, even last split", "corr_argmax.hip:244, :258, :333", _split("fast", lambda ks, kpw, last: kpw >= 2 and last == kpw),
+    ("fast kernel: kt_per_wg >= 2, even last split", "corr_argmax_fast_kernel: kt_hi, k-tile loop", _split("fast", lambda ks, kpw, last: kpw >= 2 and last == kpw),
      ("fast_kpw2_even", "layer_kpw2_in_consumer_merge")),
-    ("fast kernel: kt_per_wg >= 2, uneven last split", "corr_argmax.hip:244", _split("fast", lambda ks, kpw, last: kpw >= 2 and last < kpw),
+    ("fast kernel: kt_per_wg >= 2, uneven last split", "corr_argmax_fast_kernel: kt_hi", _split("fast", lambda ks, kpw, last: kpw >= 2 and last < kpw),
      ("fast_kpw2_uneven", "fast_kpw3_uneven", "fast_kpw4_four_splits")),
-    ("generic kernel: kt_per_wg == 1", "corr_argmax.hip:644-651", _split("generic", lambda ks, kpw, last: kpw == 1),
+    ("generic kernel: kt_per_wg == 1", "corr_plan", _split("generic", lambda ks, kpw, last: kpw == 1),
      ("generic_single", "generic_tiny", "generic_c_ragged_full_tiles", "generic_n_ragged_negative")),
-    ("generic kernel: kt_per_wg >= 2, even last split", "corr_argmax.hip:81, :88", _split("generic", lambda ks, kpw, last: kpw >= 2 and last == kpw),
+    ("generic kernel: kt_per_wg >= 2, even last split", "corr_argmax_kernel: kt_hi, k-tile loop", _split("generic", lambda ks, kpw, last: kpw >= 2 and last == kpw),
      ("generic_kpw2_even",)),
-    ("generic kernel: kt_per_wg >= 2, uneven last split", "corr_argmax.hip:81", _split("generic", lambda ks, kpw, last: kpw >= 2 and last < kpw),
+    ("generic kernel: kt_per_wg >= 2, uneven last split", "corr_argmax_kernel: kt_hi", _split("generic", lambda ks, kpw, last: kpw >= 2 and last < kpw),
      ("generic_kpw2_uneven", "generic_kpw3_uneven", "generic_kpw4")),
-    ("bf16 kernel: kt_per_wg >= 2, uneven last split", "corr_argmax.hip:451, :458", _split("bf16", lambda ks, kpw, last: kpw >= 2 and last < kpw),
+    ("bf16 kernel: kt_per_wg >= 2, uneven last split", "corr_argmax_bf16_kernel: kt_hi, k-tile loop", _split("bf16", lambda ks, kpw, last: kpw >= 2 and last < kpw),
      ("bf16_kpw2_uneven",)),
-    ("in-consumer merge of the partials (merged_argmax)", "ipsr_common.h:93-102, api.hip:326", lambda p: p.get("in_consumer_merge", False),
+    ("in-consumer merge of the partials (merged_argmax)", "merged_argmax, forward_impl", lambda p: p.get("in_consumer_merge", False),
      ("layer_kpw2_in_consumer_merge",)),
-    ("window plan: one slice", "corr_argmax.hip:578", lambda p: p["kind"] == "window" and p["window"][0] == 1, ("win_one_slice",)),
-    ("window plan: every slice sought is launched, short last one", "corr_argmax.hip:579-580", lambda p: p["kind"] == "window" and 1 < p["window"][0] == p["sought"] and p["window"][3] < p["window"][1],
+    ("window plan: one slice", "window_plan", lambda p: p["kind"] == "window" and p["window"][0] == 1, ("win_one_slice",)),
+    ("window plan: every slice sought is launched, short last one", "window_plan", lambda p: p["kind"] == "window" and 1 < p["window"][0] == p["sought"] and p["window"][3] < p["window"][1],
      ("win_two_slices_short_last", "win_p2", "win_16_slices", "win_batch_limited", "win_bf16_full_tiles", "win_bf16_ragged")),
-    ("window plan: split limited by the batch (8 < 16 slices)", "corr_argmax.hip:576-578", lambda p: p["kind"] == "window" and p["Np"] == 900 and p["window"][0] == 8,
+    ("window plan: split limited by the batch (8 < 16 slices)", "window_plan", lambda p: p["kind"] == "window" and p["Np"] == 900 and p["window"][0] == 8,
      ("win_batch_limited",)),
-    ("window plan: 64 slices sought, 63 launched (none empty)", "corr_argmax.hip:580", lambda p: p["kind"] == "window" and p["window"][0] < p["sought"] and p["window"][2] == p["window"][0],
+    ("window plan: 64 slices sought, 63 launched (none empty)", "window_plan", lambda p: p["kind"] == "window" and p["window"][0] < p["sought"] and p["window"][2] == p["window"][0],
      ("win_empty_last_slice",)),
     ("innercos_fused_kernel: scalar path (N % 4 != 0)", "innercos.hip:51, :70-77", _ic(vector=False), ("ic_scalar_small", "ic_rpb2_ragged_scalar")),
     ("innercos_fused_kernel: vector path", "innercos.hip:51-68", _ic(vector=True), ("ic_vector_cx_wider", "ic_rpb2_ragged_vector", "ic_bwd_grid_stride")),

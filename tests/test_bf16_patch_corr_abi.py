@@ -14,6 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IPSR_ERR_UNSUPPORTED = -2
+IPSR_ERR_WORKSPACE = -3
 
 # (B, C, h, w, M, patch, stride) -> (ipsr_forward_workspace_bytes, ipsr_forward_bf16corr_workspace_bytes or None = changed)
 RECORDED = {
@@ -62,7 +63,8 @@ def test_bf16_window_query_covers_the_packed_operands(built, B, C, h, w, M, p):
 
 
 def _child():
-    """Runs with every GPU hidden: the C = 24, p = 3 bf16 call (C not a multiple of 64) on fake device pointers."""
+    """Runs with every GPU hidden, on fake device pointers: the C = 24, p = 3 bf16 call (C not a multiple of 64), and what the bf16
+    arg-max entry (whole 128-column tiles only) and the p = 1 bf16 layer refuse."""
     sys.path.insert(0, ROOT)
     from deepinpainting_amd import _lib
     L = _lib.lib()
@@ -73,7 +75,13 @@ def _child():
             ("forward_bf16corr", lambda: L.ipsr_forward_bf16corr(ptr[0], ptr[1], ptr[2], 10, 2, 24, 16, 16, 3, 1, ptr[3], ptr[4], ptr[5],
                                                                   None, ptr[6], ptr[7], 1 << 40, None)),
             ("forward_masks", lambda: L.ipsr_forward_masks(ptr[0], ptr[1], ptr[2], 0, ptr[6], 10, 2, 24, 16, 16, 3, 1, ptr[3], ptr[4],
-                                                            ptr[5], None, None, ptr[7], 1 << 40, None, 1))):
+                                                            ptr[5], None, None, ptr[7], 1 << 40, None, 1)),
+            ("corr_bf16_n100", lambda: L.ipsr_corr_argmax_bf16(ptr[0], ptr[1], 1, 64, 100, ptr[4], ptr[5], ptr[7], 1 << 40, None)),
+            ("corr_bf16_c32", lambda: L.ipsr_corr_argmax_bf16(ptr[0], ptr[1], 1, 32, 128, ptr[4], ptr[5], ptr[7], 1 << 40, None)),
+            ("corr_bf16_ws_short", lambda: L.ipsr_corr_argmax_bf16(ptr[0], ptr[1], 1, 64, 128, ptr[4], ptr[5], ptr[7],
+                                                                    L.ipsr_corr_argmax_bf16_workspace_bytes(1, 64, 128) - 1, None)),
+            ("forward_bf16corr_p1_n100", lambda: L.ipsr_forward_bf16corr(ptr[0], ptr[1], ptr[2], 10, 1, 64, 10, 10, 1, 1, ptr[3], ptr[4],
+                                                                          ptr[5], None, ptr[6], ptr[7], 1 << 40, None))):
         rc = args()
         out[name] = (rc, L.ipsr_last_error().decode("utf-8", "replace"))
     print(json.dumps(out))
@@ -92,6 +100,30 @@ def test_c_not_multiple_of_64_is_refused_before_any_hip_call(refusals, entry):
     rc, msg = refusals[entry]
     assert rc == IPSR_ERR_UNSUPPORTED, (rc, msg)
     assert "C % 64" in msg and "shift_sz > 1" in msg and "C=24" in msg, msg
+
+
+def test_bf16_argmax_entry_refuses_ragged_n_before_any_hip_call(refusals):
+    """(B, C, N) = (1, 64, 100): the arg-max entry takes whole 128-column tiles only (the ragged kernel belongs to the R entry)."""
+    rc, msg = refusals["corr_bf16_n100"]
+    assert rc == IPSR_ERR_UNSUPPORTED, (rc, msg)
+    assert "100" in msg, msg
+
+
+def test_bf16_argmax_entry_refuses_c_not_multiple_of_64_before_any_hip_call(refusals):
+    rc, msg = refusals["corr_bf16_c32"]
+    assert rc == IPSR_ERR_UNSUPPORTED, (rc, msg)
+    assert "32" in msg, msg
+
+
+def test_bf16_argmax_entry_refuses_a_workspace_one_byte_short(refusals):
+    rc, msg = refusals["corr_bf16_ws_short"]
+    assert rc == IPSR_ERR_WORKSPACE, (rc, msg)
+
+
+def test_bf16_layer_at_patch_1_refuses_ragged_n_before_any_hip_call(refusals):
+    """patch = 1, C = 64, 10 x 10: N = 100 is no multiple of 128."""
+    rc, msg = refusals["forward_bf16corr_p1_n100"]
+    assert rc == IPSR_ERR_UNSUPPORTED, (rc, msg)
 
 
 if __name__ == "__main__" and sys.argv[1:] == ["--child"]:

@@ -5,57 +5,53 @@ Every case goes through the `ops` wrappers.  tests/corr_plan.py restates the lau
 tests/test_corr_plan.py proves without a GPU that the restatement gives the library's byte counts and that the tables reach every
 row below, and each test here asserts its own row again (`P.check_case`) before it compares numbers.
 
-  variant                                                                  selected at                        case ids
-  -----------------------------------------------------------------------  ---------------------------------  ----------------------------------------
-  corr_argmax_fast_kernel<false,false>                                     corr_argmax.hip:689, :691          fast_ring_exact, fast_ring_wraps, fast_kpw2_uneven
-                                                                                                              fast_kpw3_uneven, fast_kpw4_four_splits, layer_kpw2_in_consumer_merge
-  corr_argmax_fast_kernel<true,false>                                      corr_argmax.hip:689-690            fast_one_tile, fast_two_stages, fast_kpw2_even
-                                                                                                              win_p2
-  corr_argmax_kernel<false,false>                                          corr_argmax.hip:695, :697          generic_n_ragged_negative, generic_kpw2_uneven, generic_kpw3_uneven
-                                                                                                              generic_kpw4
-  corr_argmax_kernel<false,true>                                           corr_argmax.hip:695-696            generic_single, generic_tiny, generic_c_ragged_full_tiles
-                                                                                                              generic_kpw2_even, win_one_slice, win_two_slices_short_last
-                                                                                                              win_16_slices, win_batch_limited, win_empty_last_slice
-  pack_bf16_k8_kernel                                                      corr_argmax.hip:731-732, :772-773  bf16_one_tile, bf16_kpw2_uneven, win_bf16_full_tiles
-                                                                                                              win_bf16_ragged
-  corr_argmax_bf16_kernel<false,false>                                     corr_argmax.hip:736                bf16_one_tile, bf16_kpw2_uneven
-  corr_argmax_bf16_kernel<false,true>                                      corr_argmax.hip:777                win_bf16_full_tiles
-  corr_argmax_bf16_kernel<true,true>                                       corr_argmax.hip:778                win_bf16_ragged
-  window_corr_argmax_kernel                                                corr_argmax.hip:602                win_one_slice, win_two_slices_short_last, win_p2
-                                                                                                              win_16_slices, win_batch_limited, win_empty_last_slice
-                                                                                                              win_bf16_full_tiles, win_bf16_ragged
-  argmax_merge_kernel                                                      corr_argmax.hip:606, :707, :746    fast_kpw4_four_splits, generic_kpw2_even, bf16_kpw2_uneven
-                                                                                                              win_16_slices
-  fast kernel: 1 / 2 LDS stages (fewer than the 3 in flight)               corr_argmax.hip:291-297            fast_one_tile, fast_two_stages
-  fast kernel: 3 and 5 stages (at and past the 4-slot ring)                corr_argmax.hip:300-331            fast_ring_exact, fast_ring_wraps
-  fast kernel: kt_per_wg == 1                                              corr_argmax.hip:644-651            fast_one_tile, fast_two_stages, fast_ring_exact
-                                                                                                              fast_ring_wraps
-  fast kernel: kt_per_wg >= 2, even last split                             corr_argmax.hip:244, :258, :333    fast_kpw2_even, layer_kpw2_in_consumer_merge
-  fast kernel: kt_per_wg >= 2, uneven last split                           corr_argmax.hip:244                fast_kpw2_uneven, fast_kpw3_uneven, fast_kpw4_four_splits
-  generic kernel: kt_per_wg == 1                                           corr_argmax.hip:644-651            generic_single, generic_tiny, generic_c_ragged_full_tiles
-                                                                                                              generic_n_ragged_negative
-  generic kernel: kt_per_wg >= 2, even last split                          corr_argmax.hip:81, :88            generic_kpw2_even
-  generic kernel: kt_per_wg >= 2, uneven last split                        corr_argmax.hip:81                 generic_kpw2_uneven, generic_kpw3_uneven, generic_kpw4
-  bf16 kernel: kt_per_wg >= 2, uneven last split                           corr_argmax.hip:451, :458          bf16_kpw2_uneven
-  in-consumer merge of the partials (merged_argmax)                        ipsr_common.h:93-102, api.hip:326  layer_kpw2_in_consumer_merge
-  window plan: one slice                                                   corr_argmax.hip:578                win_one_slice
-  window plan: every slice sought is launched, short last one              corr_argmax.hip:579-580            win_two_slices_short_last, win_p2, win_16_slices
-                                                                                                              win_batch_limited, win_bf16_full_tiles, win_bf16_ragged
-  window plan: split limited by the batch (8 < 16 slices)                  corr_argmax.hip:576-578            win_batch_limited
-  window plan: 64 slices sought, 63 launched (none empty)                  corr_argmax.hip:580                win_empty_last_slice
-  innercos_fused_kernel: scalar path (N % 4 != 0)                          innercos.hip:51, :70-77            ic_scalar_small, ic_rpb2_ragged_scalar
-  innercos_fused_kernel: vector path                                       innercos.hip:51-68                 ic_vector_cx_wider, ic_rpb2_ragged_vector, ic_bwd_grid_stride
-  innercos_fused_kernel: two launches, 2 rows per block, last block 1 row  innercos.hip:138-140, :50          ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
-  innercos_fused_kernel: one launch, 9 rows per block                      innercos.hip:154-156               ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
-  innercos_backward_kernel: Cx > Cuse (zero-filled channels)               innercos.hip:118-123               ic_vector_cx_wider, ic_rpb2_ragged_scalar, ic_bwd_grid_stride
-  innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)       innercos.hip:112-114, :168-170     ic_bwd_grid_stride
-  index_prep_kernel: patch > 1, stride 2, threshold > 1                    mask_ops.hip:88-92, :118           ip_p2_s1_t2, ip_p3_s2_t1, ip_p3_s1_t9
-                                                                                                              ip_p4_s2_t16, ip_p2_s2_t4, ip_40x40_p3_s1_t5
-  index_prep_kernel: two 1024-chunks                                       mask_ops.hip:84                    ip_40x40_p3_s1_t5
-  unreachable: corr_argmax_fast_kernel<*,true> (RAGGED)
-      corr_argmax.hip:692-694 needs ld != N; launch_corr_argmax is only called with ld == N or 0 (api.hip:253 ipsr_corr_argmax, :317 ld 0, :326 p.ld == p.N at patch 1)
-  unreachable: corr_argmax_bf16_kernel<true,false> (RAGGED)
-      corr_argmax.hip:737 needs ld != N; launch_corr_argmax_bf16 is only called with ld == N or 0 (api.hip:324 p.ld == p.N at patch 1, :392 ipsr_corr_argmax_bf16)
+  variant                                                                  selected at                                  case ids
+  -----------------------------------------------------------------------  -------------------------------------------  ----------------------------------------
+  corr_argmax_fast_kernel<false>                                           launch_corr_argmax                           fast_ring_exact, fast_ring_wraps, fast_kpw2_uneven
+                                                                                                                        fast_kpw3_uneven, fast_kpw4_four_splits, layer_kpw2_in_consumer_merge
+  corr_argmax_fast_kernel<true>                                            launch_corr_argmax                           fast_one_tile, fast_two_stages, fast_kpw2_even
+                                                                                                                        win_p2
+  corr_argmax_kernel<false>                                                launch_corr_argmax                           generic_n_ragged_negative, generic_kpw2_uneven, generic_kpw3_uneven
+                                                                                                                        generic_kpw4
+  corr_argmax_kernel<true>                                                 launch_corr_argmax                           generic_single, generic_tiny, generic_c_ragged_full_tiles
+                                                                                                                        generic_kpw2_even, win_one_slice, win_two_slices_short_last
+                                                                                                                        win_16_slices, win_batch_limited, win_empty_last_slice
+  pack_bf16_k8_kernel                                                      launch_bf16                                  bf16_one_tile, bf16_kpw2_uneven, win_bf16_full_tiles
+                                                                                                                        win_bf16_ragged
+  corr_argmax_bf16_kernel<false,false>                                     launch_bf16 (launch_corr_argmax_bf16)        bf16_one_tile, bf16_kpw2_uneven
+  corr_argmax_bf16_kernel<false,true>                                      launch_bf16 (launch_corr_R_bf16)             win_bf16_full_tiles
+  corr_argmax_bf16_kernel<true,true>                                       launch_bf16 (launch_corr_R_bf16)             win_bf16_ragged
+  window_corr_argmax_kernel                                                launch_window_corr_argmax                    win_one_slice, win_two_slices_short_last, win_p2
+                                                                                                                        win_16_slices, win_batch_limited, win_empty_last_slice
+                                                                                                                        win_bf16_full_tiles, win_bf16_ragged
+  argmax_merge_kernel                                                      finish_argmax                                fast_kpw4_four_splits, generic_kpw2_even, bf16_kpw2_uneven
+                                                                                                                        win_16_slices
+  fast kernel: 1 / 2 LDS stages (fewer than the 3 in flight)               corr_argmax_fast_kernel: prologue            fast_one_tile, fast_two_stages
+  fast kernel: 3 and 5 stages (at and past the 4-slot ring)                corr_argmax_fast_kernel: stage loop          fast_ring_exact, fast_ring_wraps
+  fast kernel: kt_per_wg == 1                                              corr_plan                                    fast_one_tile, fast_two_stages, fast_ring_exact
+                                                                                                                        fast_ring_wraps
+  fast kernel: kt_per_wg >= 2, even last split                             corr_argmax_fast_kernel: kt_hi, k-tile loop  fast_kpw2_even, layer_kpw2_in_consumer_merge
+  fast kernel: kt_per_wg >= 2, uneven last split                           corr_argmax_fast_kernel: kt_hi               fast_kpw2_uneven, fast_kpw3_uneven, fast_kpw4_four_splits
+  generic kernel: kt_per_wg == 1                                           corr_plan                                    generic_single, generic_tiny, generic_c_ragged_full_tiles
+                                                                                                                        generic_n_ragged_negative
+  generic kernel: kt_per_wg >= 2, even last split                          corr_argmax_kernel: kt_hi, k-tile loop       generic_kpw2_even
+  generic kernel: kt_per_wg >= 2, uneven last split                        corr_argmax_kernel: kt_hi                    generic_kpw2_uneven, generic_kpw3_uneven, generic_kpw4
+  bf16 kernel: kt_per_wg >= 2, uneven last split                           corr_argmax_bf16_kernel: kt_hi, k-tile loop  bf16_kpw2_uneven
+  in-consumer merge of the partials (merged_argmax)                        merged_argmax, forward_impl                  layer_kpw2_in_consumer_merge
+  window plan: one slice                                                   window_plan                                  win_one_slice
+  window plan: every slice sought is launched, short last one              window_plan                                  win_two_slices_short_last, win_p2, win_16_slices
+                                                                                                                        win_batch_limited, win_bf16_full_tiles, win_bf16_ragged
+  window plan: split limited by the batch (8 < 16 slices)                  window_plan                                  win_batch_limited
+  window plan: 64 slices sought, 63 launched (none empty)                  window_plan                                  win_empty_last_slice
+  innercos_fused_kernel: scalar path (N % 4 != 0)                          innercos.hip:51, :70-77                      ic_scalar_small, ic_rpb2_ragged_scalar
+  innercos_fused_kernel: vector path                                       innercos.hip:51-68                           ic_vector_cx_wider, ic_rpb2_ragged_vector, ic_bwd_grid_stride
+  innercos_fused_kernel: two launches, 2 rows per block, last block 1 row  innercos.hip:138-140, :50                    ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
+  innercos_fused_kernel: one launch, 9 rows per block                      innercos.hip:154-156                         ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
+  innercos_backward_kernel: Cx > Cuse (zero-filled channels)               innercos.hip:118-123                         ic_vector_cx_wider, ic_rpb2_ragged_scalar, ic_bwd_grid_stride
+  innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)       innercos.hip:112-114, :168-170               ic_bwd_grid_stride
+  index_prep_kernel: patch > 1, stride 2, threshold > 1                    mask_ops.hip:88-92, :118                     ip_p2_s1_t2, ip_p3_s2_t1, ip_p3_s1_t9
+                                                                                                                        ip_p4_s2_t16, ip_p2_s2_t4, ip_40x40_p3_s1_t5
+  index_prep_kernel: two 1024-chunks                                       mask_ops.hip:84                              ip_40x40_p3_s1_t5
 
 The reference everywhere is `oracle.ipsr_oracle`, and every compared output is equal bit for bit: the fp32 matrix-core
 instruction is one fmaf chain over ascending channels, which is what the oracle writes.  The bf16 cases (added so that every
