@@ -437,7 +437,7 @@ def cat_relu_backward(grad_out, out, C1, skip_half_only=False):
 
 
 def bias_relu_pool2(x, bias):
-    """max_pool2d(relu(x + bias[c]), 2, 2) of a contiguous fp32 [B,C,H,W] tensor in one pass."""
+    """max_pool2d(relu(x + bias[c]), 2, 2) of a contiguous fp32 / bf16 [B,C,H,W] tensor in one pass (an odd last row / column is dropped)."""
     x, bf = _act(x, "x")
     B, C, H, W = x.shape
     y = _empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
