@@ -61,7 +61,10 @@ constexpr int CB_LDS_MAX = 160 * 1024;
 //   C2F  k4 s2 p1, coarse -> fine     (ConvTranspose2d forward, Conv2d input gradient) lane grid = COARSE input; a workgroup produces the
 //        fine rows of ONE row parity ey' and both column parities (two accumulator sets of 2 x 2 taps each: 8 taps per stage), raw / T as
 //        S1 on the coarse image; the epilogue interleaves the two column phases into whole fine rows.
-//   DF2C / DC2F  k4 s2 p3 d2 on fp32 tensors only (conv_bf16x3_s2_kernel below): see that kernel's header.
+//   DF2C / DC2F  k4 s2 p3 d2 (ipsr_conv4x4s2_bf16_dil; on fp32 tensors conv_bf16x3_s2_kernel below, whose header has the geometry): a channel
+//        block = two sub-stages of 8 taps, each on its own R + 1 rows, ONE plane T = [cg][R + 1][Wl + 3].  DF2C: lane grid = coarse output, raw tile =
+//        the R + 1 ODD fine rows of the sub-stage at full fine width, the transposition stores the odd columns only.  DC2F: lane grid = coarse
+//        input, raw / T on the coarse image, one accumulator set; the epilogue writes the whole fine tile ((0, v) pairs on the odd rows, zero rows).
 enum { CB_S1 = 0, CB_F2C = 1, CB_C2F = 2, CB_DF2C = 3, CB_DC2F = 4 };
 
 struct CbGeom {
@@ -127,6 +130,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
     constexpr int NTAP = MODE == CB_S1 ? 9 : 8;
     constexpr int NSET = MODE == CB_C2F ? 2 : 1;               // accumulator sets (C2F: the two column phases of the fine output)
     constexpr int TPSET = NTAP / NSET;
+    constexpr bool SUB2 = MODE == CB_F2C || MODE == CB_DF2C || MODE == CB_DC2F;  // two sub-stages per channel block, each with its own input rows
     // P = pixels per tile: 256 under 128 produced channels; under 64 it is 512 where the map has the rows for it — a wave owns 64 x 64
     // either way (4 fragment reads per 4 MFMAs; on a 64 x 256 tile it is 64 x 32: 3 reads per 2 MFMAs = 192 B/clk/CU of the LDS's 256)
     static_assert((KT == 128 && P == 256) || (KT == 64 && (P == 256 || P == 512)), "tile");
@@ -153,7 +157,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
     // raw tile DMA: chunk q (16 bytes = 8 pixels) = (c, row, seg), LDS image linear in q; per sub-stage its own row set
     const int segs = g.Win >> 3, nchunk = CB_C * g.NR * segs;
     constexpr int XJ = cb_xj(P);
-    const unsigned short* gx[XJ][MODE == CB_F2C ? 2 : 1];
+    const unsigned short* gx[XJ][SUB2 ? 2 : 1];
     bool xlive[XJ];
 #pragma unroll
     for (int j = 0; j < XJ; ++j) {
@@ -162,7 +166,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
         const int qq = xlive[j] ? q : 0;
         const int seg = qq % segs, row = (qq / segs) % g.NR, c = qq / (segs * g.NR);
 #pragma unroll
-        for (int e = 0; e < (MODE == CB_F2C ? 2 : 1); ++e) {
+        for (int e = 0; e < (SUB2 ? 2 : 1); ++e) {
             const int y = g.ymul * y0 + g.yoff[e] + g.rowstep * row;
             const bool inside = (unsigned)y < (unsigned)g.Hin;
             gx[j][e] = inside ? in + (((size_t)b * g.C + c) * g.Hin + y) * g.Win + seg * 8 : nullptr;
@@ -185,10 +189,14 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
         const int x = cb16 * 16 + li;
         int pos;
         if (MODE == CB_F2C) { const int ex = x & 1; pos = (ex * 2 + (cq >> 1)) * g.NPOS + row * g.PW + (x >> 1) + ex; }      // x = 2 j + ex; plane 1 starts at j = -1
+        else if (MODE == CB_DF2C) pos = (cq >> 1) * g.NPOS + row * g.PW + (x >> 1) + 2;    // x = 2 n + 1 -> q column n at n + 2; the even x are not stored (tr_keep)
         else pos = (cq >> 1) * g.NPOS + row * g.PW + x + 1;
         tr_wr[j] = (pos * 8 + (cq & 1) * 4) * 2;
     }
     const int ntr = (nblk + 31) / 32;
+    // DF2C: the raw rows carry every fine column, T takes the odd ones only: the lanes that hold an even column read (the transposing read wants
+    // the whole 16-lane group) and store nothing
+    const bool tr_keep = MODE != CB_DF2C || (li & 1);
     const int t_base = 2 * g.a_bytes, raw_base = t_base + 2 * g.t_bytes;
     // fragments: A rows wm*64 + {0,32} + r; B lane-grid pixels wn*64 + {0,32} + r
     const int a_off = (h * KT + wm * 64 + r) * 16;
@@ -219,11 +227,11 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
         }
     };
     auto dma_x = [&](int buf, int stage) {
-        const int cb = MODE == CB_F2C ? stage >> 1 : stage, e = MODE == CB_F2C ? stage & 1 : 0;
+        const int cb = SUB2 ? stage >> 1 : stage, e = SUB2 ? stage & 1 : 0;
 #pragma unroll
         for (int j = 0; j < XJ; ++j) {
             if (xlive[j]) {
-                const unsigned short* base = (MODE == CB_F2C && e) ? gx[j][MODE == CB_F2C ? 1 : 0] : gx[j][0];
+                const unsigned short* base = (SUB2 && e) ? gx[j][SUB2 ? 1 : 0] : gx[j][0];
                 const void* src = base ? static_cast<const void*>(base + (size_t)cb * xstride) : static_cast<const void*>(zero_page);
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + raw_base + buf * g.raw_bytes + (wave * 64 + CB_THREADS * j) * 16), 16, 0, 0);
             }
@@ -238,10 +246,13 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
             if (j < ntr) v[j] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(raw + tr_rd[j]));
 #pragma unroll
         for (int j = 0; j < CB_TR_MAX; ++j)
-            if (j < ntr) *reinterpret_cast<s16x4*>(T + tr_wr[j]) = v[j];
+            if (j < ntr && tr_keep) *reinterpret_cast<s16x4*>(T + tr_wr[j]) = v[j];
     };
 
-    // both T images start as zeros: the halo columns are never written (tiles span the full image width)
+    // both T images start as zeros: the halo columns are never written (tiles span the full image width).
+    // The dilated forms keep T double-buffered like F2C (2 x 21 KB at most, DF2C at nw = 128 on the 512-pixel tile; the largest plan is 153 KB):
+    // a transposition writes ALL R + 1 row slots of its buffer, the rows outside the image from the zero page, so a slot that lies outside the
+    // image for one sub-stage and inside it for the other never keeps the other's row — nothing is rewritten apart from the transposition itself.
     for (int i = tid; i < 2 * (g.t_bytes / 16); i += CB_THREADS)
         *reinterpret_cast<uint4*>(lds + t_base + i * 16) = make_uint4(0u, 0u, 0u, 0u);
     // prologue: A[0], raw[0] <- stage 0; raw[1] <- stage 1 (two raw buffers)
@@ -266,7 +277,7 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
         }
         const unsigned char* A = lds + cur * g.a_bytes + a_off;
         const unsigned char* T = lds + t_base + cur * g.t_bytes;
-        const int* toff = g.tapoff[MODE == CB_F2C ? (s & 1) : (MODE == CB_C2F ? phase : 0)];
+        const int* toff = g.tapoff[SUB2 ? (s & 1) : (MODE == CB_C2F ? phase : 0)];     // (two sub-stages: sps is even, a run starts on sub-stage 0)
         // software pipeline over the taps: the fragments of tap t + 1 are read while tap t multiplies (two register sets); the
         // sched_group_barriers pin that order — left alone the compiler issues a tap's reads right before its own multiplications and
         // every tap waits out the LDS latency (s_waitcnt lgkmcnt(0) in front of 4 MFMAs)
@@ -327,6 +338,19 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
                         }
                     }
                 }
+        } else if (MODE == CB_DC2F) {
+            // fine row 2 py + 1, fine columns 2 px and 2 px + 1: (0, v), one 4- / 8-byte store; the even fine rows follow below
+            TOUT* op = out + (size_t)b * g.K * HWo + (size_t)(2 * py + 1) * g.Wout + 2 * px;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int k = kt * KT + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (k < g.K) {
+                        if (sizeof(TOUT) == 2) *reinterpret_cast<unsigned*>(op + (size_t)k * HWo) = (unsigned)f2bf(acc[0][i][j][e]) << 16;
+                        else *reinterpret_cast<float2*>(op + (size_t)k * HWo) = make_float2(0.0f, acc[0][i][j][e]);
+                    }
+                }
         } else if (sizeof(TOUT) == 2) {
             // bf16 output: through LDS (free after the last stage's barrier) as [k][P pixels], so that the tile leaves as 16-byte rows
             // instead of 64 two-byte stores per lane
@@ -350,7 +374,17 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16_kernel(const unsigned
                 }
         }
     }
-    if (MODE != CB_C2F && sizeof(TOUT) == 2) {
+    if (MODE == CB_DC2F) {
+        // the even fine rows 2 (y0 + i), i < R, of the tile's channels: whole rows of +0 as 16-byte vectors
+        const int rchunks = g.Wout * (int)sizeof(TOUT) / 16, nz = KT * g.R * rchunks;
+        for (int z = tid; z < nz; z += CB_THREADS) {
+            const int seg = z % rchunks, i = (z / rchunks) % g.R, k = kt * KT + z / (rchunks * g.R);
+            if (k < g.K) {
+                TOUT* op = out + ((size_t)b * g.K + k) * HWo + (size_t)(2 * (y0 + i)) * g.Wout;
+                reinterpret_cast<uint4*>(op)[seg] = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+    } else if (MODE != CB_C2F && sizeof(TOUT) == 2) {
         __syncthreads();
         const uint4* L4 = reinterpret_cast<const uint4*>(lds);
 #pragma unroll
@@ -869,18 +903,21 @@ __global__ void __launch_bounds__(CB_THREADS, 1) conv_bf16x3_s2_kernel(const flo
 // `split` decides the rest of the plan: bf16 tensors (conv_bf16_kernel) get the tile 128 x 256, or 64 produced channels x 512 / 256 pixels when
 // K <= 64, LDS = A[2] | T[2] | raw[2 or 1], and a stage has to fit the transposition and DMA loops (cb_tr_max, cb_xj); fp32 tensors on split-bf16
 // operands get the tile 64 x 256, two packed planes (hi | lo), LDS = A[2] | T (hi | lo), and one activation item (c group, row, 4 floats) per thread.
-enum { DATA_K3 = 0, DATA_S2 = 1, DATA_K3_SPLIT = 2, DATA_S2_SPLIT = 3 };
+enum { DATA_K3 = 0, DATA_S2 = 1, DATA_K3_SPLIT = 2, DATA_S2_SPLIT = 3, DATA_S2_DIL = 4 };
 struct DataKind {
     bool split;
     int wmax;                           // widest lane grid
     const char *who, *width_fmt;        // the messages, as each planner has always worded them
     const char* kernel;                 // the name check_launch reports
 };
-constexpr DataKind DATA_KINDS[4] = {
+constexpr DataKind DATA_KINDS[5] = {
     {false, 256, "bf16 direct conv", "%s: grid width %d (16 .. 256, a power of two)", "conv_bf16_kernel"},
     {false, 256, "bf16 direct 4x4 stride-2 conv", "%s: grid width %d (16 .. 256, a power of two)", "conv_bf16_kernel"},
     {true, 256, "split-bf16 direct conv", "%s: width %d (16 .. 256, a power of two)", "conv_bf16x3_kernel"},
     {true, 128, "split-bf16 direct 4x4 stride-2 conv", "%s: coarse width %d (16 .. 128, a power of two)", "conv_bf16x3_s2_kernel"},
+    // the dilated forms on bf16 tensors: DATA_S2's plan on the coarse widths whose stage fits the loop bounds (DF2C at nw = 128 fills them: 192
+    // transposition blocks and 1536 raw chunks at 256 pixels, 320 and 2560 at 512); two raw buffers always fit (<= 153 KB), `raw1` never comes up
+    {false, 128, "bf16 direct dilated 4x4 stride-2 conv", "%s: coarse width %d (16 .. 128, a power of two)", "conv_bf16_kernel"},
 };
 
 // What a form (CB_S1 .. CB_DC2F) fixes on any grid: which tensor is the fine one (2 Hl x 2 Wl), sub-stages per channel block, row phases, taps per
@@ -1026,7 +1063,8 @@ static int launch_data(const void* in, const float* w, void* out, int B, int C, 
 {
     constexpr DataKind k = DATA_KINDS[KIND];
     constexpr DataForm f = DATA_FORMS[FORM];
-    static_assert((FORM == CB_S1) == (KIND == DATA_K3 || KIND == DATA_K3_SPLIT) && (FORM < CB_DF2C || KIND == DATA_S2_SPLIT), "no kernel of this kind has the form");
+    static_assert((FORM == CB_S1) == (KIND == DATA_K3 || KIND == DATA_K3_SPLIT) && (FORM < CB_DF2C || KIND == DATA_S2_SPLIT || KIND == DATA_S2_DIL) &&
+                  (KIND != DATA_S2_DIL || FORM >= CB_DF2C), "no kernel of this kind has the form");
     CbGeom g;
     if (int rc = data_geometry(KIND, FORM, B, C, K, Hl, Wl, &g)) return rc;
     const size_t need = data_ws_bytes(k, g);
@@ -2123,7 +2161,8 @@ static int cb_misaligned(const char* who, const char* what, std::initializer_lis
     return IPSR_OK;
 }
 
-// modes of the k4 s2 entries: bit 0 = coarse -> fine, bit 2 = pad 3, dilation 2 (ipsr_conv4x4s2_bf16x3 only) -> the form
+// modes of the k4 s2 entries: bit 0 = coarse -> fine, bit 2 = pad 3, dilation 2 (ipsr_conv4x4s2_bf16x3 only; ipsr_conv4x4s2_bf16_dil is the
+// dilated layer on bf16 tensors with modes 0 / 1) -> the form
 static bool c2_mode_ok(int mode) { return mode == 0 || mode == 1 || mode == 4 || mode == 5; }
 static int c2_form(int mode) { return ((mode & 4) ? CB_DF2C : CB_F2C) + (mode & 1); }
 
@@ -2181,6 +2220,22 @@ int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16", "in / out / workspace", {ws, in, out})) return rc;
     // weight [Kc][Cf][4][4] in both modules (Conv2d: [Cout][Cin], ConvTranspose2d: [Cin][Cout]), as in ipsr_conv4x4s2_winograd
     const auto launch = mode == 0 ? launch_data_s2<DATA_S2, CB_F2C> : launch_data_s2<DATA_S2, CB_C2F>;
+    return launch(in, weight, out, B, Kc, Cf, nh, nw, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t ipsr_conv4x4s2_bf16_dil_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw)
+{
+    if (!cb_dims_ok(mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return 0;
+    return data_ws_query(DATA_S2_DIL, c2_form(mode | 4), B, mode == 0 ? Cf : Kc, mode == 0 ? Kc : Cf, nh, nw);
+}
+
+int ipsr_conv4x4s2_bf16_dil(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
+                            void* ws, size_t ws_bytes, void* stream)
+{
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16_dil", {in, weight, out, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16_dil", mode == 0 || mode == 1, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16_dil", "in / out / workspace", {ws, in, out})) return rc;
+    const auto launch = mode == 0 ? launch_data_s2<DATA_S2_DIL, CB_DF2C> : launch_data_s2<DATA_S2_DIL, CB_DC2F>;
     return launch(in, weight, out, B, Kc, Cf, nh, nw, out_bf16, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 

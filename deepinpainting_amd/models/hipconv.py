@@ -36,6 +36,9 @@ engine does not take into "miopen": no rule, and no forced mode, can hand an eng
                                   gradient as one pass over the input
   "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
+                                  — and, by a switch of its own (`set_direct_dilated_bf16`), forward / input gradient of netG's dilated down
+                                  convolution Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input
+                                  (ops.conv4x4s2_bf16_dil), instead of "wino_dil" / MIOpen; its weight gradient stays where it is
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32=...)`, the four direct names of ops.DIRECT_PASSES): forward / input gradient on split-bf16 operands
                                   — and, by a switch of its own (`set_direct_dilated`), forward / input gradient of netG's dilated down convolution
                                   Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input, instead of "wino_dil"
@@ -113,6 +116,24 @@ def set_direct_dilated_dw(on):
 def direct_dilated_dw():
     """Whether `set_direct_dilated_dw` is on."""
     return "dil_wrw" in _direct_passes_on()
+
+
+_DIRECT_DILATED_BF16 = False   # opt-in: the dilated 4x4 stride-2 data passes under bf16 activations on the direct bf16 kernel (`set_direct_dilated_bf16`)
+
+
+def set_direct_dilated_bf16(on):
+    """Opt-in, default off, independent of `set_conv_math`, `set_direct_dilated` and `set_direct_dilated_dw`: under bf16 activations, forward
+    and input gradient of the dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" or MIOpen has go to the direct
+    bf16 kernel ("bf16d", ops.conv4x4s2_bf16_dil) on every shape it takes (`_dilated_bf16_opt_in`).  Weight gradients, fp32 activations, forced
+    engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
+    global _DIRECT_DILATED_BF16
+    _DIRECT_DILATED_BF16 = bool(on)
+    _SEL.clear()
+
+
+def direct_dilated_bf16():
+    """Whether `set_direct_dilated_bf16` is on."""
+    return _DIRECT_DILATED_BF16
 
 
 def _direct_passes_on():
@@ -263,6 +284,8 @@ def _select_any(op, lay, bf16):
             eng = "thin_f2m"
         else:
             eng = _bf16_direct(op, lay)
+    if bf16:
+        eng = _dilated_bf16_opt_in(eng, op, lay)
     # the final guard: the rules and forced modes that probe nothing ("winograd", "wino_dil", IPSR_CONV_ENGINE=winograd) answer "miopen"
     # where their engine refuses the layer, instead of raising in `conv_nobias` on a layer torch computes
     return eng if engine_takes(eng, "data", op, lay, bf16) else "miopen"
@@ -291,6 +314,23 @@ def _bf16_direct(op, lay):
             return "bf16d" if nw >= 32 and ((Kc + 127) // 128) * B * nh * nw // 256 >= 128 else "miopen"
         return "bf16d"
     return "miopen"
+
+
+def _dilated_bf16_opt_in(base, op, lay):
+    """bf16 activations under `set_direct_dilated_bf16(True)`: the forward / input-gradient passes of the dilated down convolution that the
+    chain answers "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) go to the direct bf16 kernel
+    wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated` follows for
+    fp32.  Mode "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids, the weight gradient and netD's k4 s1 p1 stay.
+    Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_layers.txt, forward / input gradient):
+    64 -> 64 @256 against MIOpen 1.93x / 2.53x (0.077 / 0.073 vs 0.149 / 0.186 ms), 128 -> 128 @128 against MIOpen 1.75x / 2.47x, 256 -> 256 @64
+    against "wino_dil" 0.93x (LOSES, 0.086 vs 0.081 ms) / 1.13x, 512 -> 512 @32 against "wino_dil" 1.05x / 0.84x (LOSES, 0.091 vs 0.076 ms); every
+    row's ranges apart.  The switch moves all eight passes; the config-5 step rate goes from 821.3 to 834.4 images/s (+1.6 %, five alternated
+    rounds, the ranges apart).  Other batches and channel counts inside the kernel's limits were not measured."""
+    if not _DIRECT_DILATED_BF16 or _mode() != "auto" or _env("IPSR_BF16_ENGINES", "") != "" or base not in ("wino_dil", "miopen"):
+        return base
+    if op in (ops.CONV_FWD, ops.CONV_BWD_DATA) and _dil_geometry(lay) is not None and engine_takes("bf16d", "data", op, lay, True):
+        return "bf16d"
+    return base
 
 
 def _bf16_wins(eng, Cin, H, W, Cout, wrw=False):
@@ -633,11 +673,12 @@ def _fine_coarse(x, dy, lay):
 
 def _direct_case(lay, x3):
     """-> (case, g): which entry point of csrc/conv_bf16.hip a layer reaches on the direct bf16 (x3 False) / split-bf16 (x3 True) engines —
-    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, split-bf16 only, g = `_dil_geometry`) — or
-    (None, None) where their calls cannot express the layer.  The run calls and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" all branch on it."""
+    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, g = `_dil_geometry`; on the bf16 engine its data
+    passes only, and only while `set_direct_dilated_bf16` is on) — or (None, None) where their calls cannot express the layer.  The run calls
+    and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" all branch on it."""
     if lay[6:] == _K3:
         return "k3", None
-    dilated = x3 and _is_dilated4(*lay[6:])
+    dilated = (x3 or _DIRECT_DILATED_BF16) and _is_dilated4(*lay[6:])
     g = _dil_geometry(lay) if dilated else _s2_geometry(lay)
     return (None if g is None else "dil" if dilated else "s2"), g
 
@@ -647,12 +688,15 @@ def _direct_mode(case, op):
 
 
 def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
-    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 in its coarse / fine form."""
+    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 / the dilated k4 s2 p3 d2 in their coarse /
+    fine form."""
     if inp.dtype != torch.bfloat16:
         inp = inp.to(torch.bfloat16)
     case, g = _direct_case(lay, False)
     if case == "k3":
         return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, **_frozen_pack(w, param))
+    if case == "dil":
+        return ops.conv4x4s2_bf16_dil(_dil_mode(op) & ~ops.S2_DILATED, inp, w, lay[1], *g, out_dtype=out_dtype)
     return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *g, out_dtype=out_dtype)
 
 
@@ -668,6 +712,8 @@ def _bf16d_takes(kind, op, lay, bf16):
         return False
     if case == "k3":
         return ops.conv3x3_bf16_supported(op, *lay[1:6]) if kind == "data" else ops.conv3x3_bf16_wrw_supported(*lay[:6])
+    if case == "dil":                        # no weight gradient: it stays on "wino_dil" / MIOpen
+        return kind == "data" and ops.conv4x4s2_bf16_dil_supported(_dil_mode(op) & ~ops.S2_DILATED, lay[1], *g)
     return ops.conv4x4s2_bf16_supported(_s2_mode(op), lay[1], *g) if kind == "data" else ops.conv4x4s2_bf16_wrw_supported(lay[1], *g)
 
 

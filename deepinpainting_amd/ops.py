@@ -659,6 +659,8 @@ def _conv4x4s2_direct(arith, mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype):
     weight = _req(weight, torch.float32, "conv weight")
     if mode not in (_S2_X3_MODES if arith == "bf16x3" else _S2_MODES):
         raise ValueError("%s: mode %r" % (who, mode))
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("%s writes bf16 or fp32, not %s" % (who, out_dtype))
     fine, coarse = (B, Cf, 2 * nh, 2 * nw), (B, Kc, nh, nw)
     want_in, oshape = (fine, coarse) if mode & ~S2_DILATED == S2_FINE_TO_COARSE else (coarse, fine)
     if tuple(inp.shape) != want_in or tuple(weight.shape) != (Kc, Cf, 4, 4):
@@ -736,6 +738,18 @@ def conv4x4s2_bf16(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat1
     conv4x4s2_winograd: mode S2_FINE_TO_COARSE: inp = fine [B,Cf,2nh,2nw] -> coarse [B,Kc,nh,nw]; S2_COARSE_TO_FINE: the reverse.
     weight [Kc,Cf,4,4] fp32 (Conv2d: [Cout,Cin]; ConvTranspose2d: [Cin,Cout])."""
     return _conv4x4s2_direct("bf16", mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype)
+
+
+def conv4x4s2_bf16_dil_supported(mode, B, Kc, Cf, nh, nw):
+    return mode in _S2_MODES and _lib.lib().ipsr_conv4x4s2_bf16_dil_workspace_bytes(mode, B, Kc, Cf, nh, nw) > 0
+
+
+def conv4x4s2_bf16_dil(mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype=torch.bfloat16):
+    """Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) on bf16 tensors as ONE direct implicit GEMM on the bf16 matrix cores
+    (ipsr_conv4x4s2_bf16_dil), in the terms of conv4x4s2_bf16: S2_FINE_TO_COARSE its forward (inp = fine [B,Cf,2nh,2nw] -> coarse
+    [B,Kc,nh,nw]; only the odd rows and odd columns of `inp` are used), S2_COARSE_TO_FINE its input gradient (every element of the fine
+    result is written: the odd / odd quarter carries values, the rest is +0).  weight [Kc,Cf,4,4] fp32; bf16 or fp32 out."""
+    return _conv4x4s2_direct("bf16_dil", mode, inp, weight, B, Kc, Cf, nh, nw, out_dtype)
 
 
 def conv4x4s2_bf16x3_supported(mode, B, Kc, Cf, nh, nw):

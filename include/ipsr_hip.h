@@ -509,6 +509,19 @@ int ipsr_conv3x3_bf16_packed(int op, const void* in, const float* weight, void* 
 size_t ipsr_conv4x4s2_bf16_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
                         void* ws, size_t ws_bytes, void* stream);
+/* netG's DILATED down convolution Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) (models/networks.py:198) on bf16 tensors, in the same coarse /
+ * fine terms and with the same arguments, weight layout and out_bf16 as ipsr_conv4x4s2_bf16: mode 0 fine -> coarse is its forward (reads the
+ * odd rows and odd columns of the fine tensor only: a 16-tap stride-1 correlation on that quarter), mode 1 coarse -> fine its input gradient
+ * (writes EVERY element of the fine tensor: values at the odd / odd positions, +0 elsewhere).  One launch of the bf16 kernel per pass behind
+ * the weight packing; on small maps the reduction is cut into runs whose fp32 partials (fine-sized in mode 1) a second launch adds in a fixed
+ * order.  Supported: nw in {16, 32, 64, 128}, nh a multiple of the tile's rows (256 / nw; 512 / nw where <= 64 channels are produced and nh
+ * allows it), reduction channels (mode 0: Cf, mode 1: Kc) a multiple of 16; anything else -> IPSR_ERR_UNSUPPORTED, checked before any
+ * launch.  The workspace query returns 0 where the shape is unsupported or an argument is bad; null pointers, a mode other than 0 / 1 and
+ * dimensions < 1 are IPSR_ERR_INVALID, as is an `in`, `out` or `ws` that is not 16-byte aligned; a short workspace is IPSR_ERR_WORKSPACE.
+ * ipsr_conv4x4s2_bf16 itself keeps refusing modes 4 and 5.  Added without an ABI version change (15): entries are added, none changes. */
+size_t ipsr_conv4x4s2_bf16_dil_workspace_bytes(int mode, int B, int Kc, int Cf, int nh, int nw);
+int ipsr_conv4x4s2_bf16_dil(int mode, const void* in, const float* weight, void* out, int B, int Kc, int Cf, int nh, int nw, int out_bf16,
+                            void* ws, size_t ws_bytes, void* stream);
 /* the same two passes on FP32 tensors with SPLIT-bf16 operands (the opt-in arithmetic "direct_bf16x3_s2" of the fp32 nets): fp32 NCHW in and
  * out, every operand a = hi + lo with hi = bf16(a), lo = bf16(a - hi), every product lo*hi + hi*lo + hi*hi on the bf16 matrix cores, fp32
  * accumulation; the split happens inside the kernel (one launch per pass plus the weight packing, no fp32-wide intermediates).  Error per
