@@ -1122,8 +1122,8 @@ static int launch_data_s2(const void* in, const float* w, void* out, int B, int 
 // RS new rows arrive meanwhile), both by LDS-DMA with the 16-byte chunks of a row XOR-swizzled / the row pitch odd in 16-byte slots so
 // that the 32 channels of a fragment read hit distinct banks.
 
-// The plan of all five weight-gradient kernels (this one, its split-bf16 form, the two k4 s2 p1 kernels and the dilated k4 s2 kernel further
-// down; wrw_geometry).
+// The plan of all six weight-gradient kernels (this one, its split-bf16 form, the two k4 s2 p1 kernels and the two dilated k4 s2 kernels
+// further down; wrw_geometry).
 // The a operand is the one whose channels index dW's rows (3x3: see above; k4 s2: the coarse tensor), w the one read through the taps
 // (k4 s2: the fine tensor); H x W is the grid the reduction runs over (k4 s2: the coarse grid nh x nw, the fine tensor is 2H x 2W).
 struct WrwGeom {
@@ -1134,20 +1134,21 @@ struct WrwGeom {
     int ring_plane;             // bytes of the ring (split-bf16: of one of its two planes, hi | lo); read by the split-bf16 kernels only
 };
 
-// What the five kernels differ in as far as the host is concerned: one row per kernel, read by wrw_geometry, wrw_ws_bytes and launch_wrw.
+// What the six kernels differ in as far as the host is concerned: one row per kernel, read by wrw_geometry, wrw_ws_bytes and launch_wrw.
 // LDS of a launch = 2 x TK x PX x 2 bytes of a (bf16: two buffers; split: hi | lo) + the ring (bf16: one plane; split: two).
-enum { WRW_3X3 = 0, WRW_3X3_SPLIT = 1, WRW_S2 = 2, WRW_S2_SPLIT = 3, WRW_DIL_SPLIT = 4 };
+enum { WRW_3X3 = 0, WRW_3X3_SPLIT = 1, WRW_S2 = 2, WRW_S2_SPLIT = 3, WRW_DIL_SPLIT = 4, WRW_DIL = 5 };
 struct WrwKind {
     int TK, TC, NT, PX;         // tile: a channels x w channels; taps (= NT of cb_slab_reduce_kernel); pixels per stage
     int ring_mul, ring_add;     // ring entries = ring_mul * RS + ring_add
     int wscale, wmax;           // a ring entry per grid row, both ways (k4 s2: 2 = rows per ring entry, pitch of 2 W pixels; dilated: 1, the
                                 // ring holds the sampled rows q); widest grid
-    int dma_add;                // bf16: one LDS-DMA round moves up to RS + dma_add ring entries, 5 slots per thread; split: -1, no DMA
+    int dma_add;                // ring by LDS-DMA: one round moves up to RS + dma_add ring entries, 5 slots per thread; -1: the ring is filled
+                                // through registers (the split kinds, and the bf16 dilated kind, which samples q on the way)
     bool split;                 // fp32 tensors, split-bf16 operands: two planes, no zero page, three MFMAs per product
     const char *who, *width_fmt, *rows_fmt, *ring_fmt;      // the messages, as each planner has always worded them
     const char *kernel, *reduce;                             // the names check_launch reports
 };
-constexpr WrwKind WRW_KINDS[5] = {
+constexpr WrwKind WRW_KINDS[6] = {
     // TK  TC  NT   PX  ring   wscale wmax dma split
     {128, 64,  9, 128, 2, 2,  1,    128,  0, false, "bf16 weight gradient",
      "%s: image width %d (16, 32, 64 or 128)", "%s: %d rows are not a multiple of %d", "%s: the row ring of a %d-wide image does not fit the LDS plan",
@@ -1164,12 +1165,15 @@ constexpr WrwKind WRW_KINDS[5] = {
     {128, 32, 16,  64, 1, 3,  1,    128, -1, true, "split-bf16 dilated 4x4 stride-2 weight gradient",
      "%s: coarse width %d (16, 32, 64 or 128)", "%s: %d coarse rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide grid does not fit the LDS plan",
      "conv_bf16x3_wrw_dil_kernel", "conv_bf16_wrw_dil_reduce_kernel"},
+    {128, 32, 16,  64, 1, 3,  1,    128, -1, false, "bf16 dilated 4x4 stride-2 weight gradient",
+     "%s: coarse width %d (16, 32, 64 or 128)", "%s: %d coarse rows are not a multiple of the %d rows of a stage", "%s: the row ring of a %d-wide grid does not fit the LDS plan",
+     "conv_bf16_wrw_dil_kernel", "conv_bf16_wrw_dil_reduce_kernel"},
 };
 constexpr int WB_K = WRW_KINDS[WRW_3X3].TK, WB_C = WRW_KINDS[WRW_3X3].TC, WB_PX = WRW_KINDS[WRW_3X3].PX, WB_THREADS = 512;
 constexpr int WB_A_BYTES = WB_K * WB_PX * 2;                 // 32 KB per buffer; the w-row ring gets the other 96 KB (largest: W = 16 -> 18 rows x 64 c
                                                              // x 5 slots x 16 B = 92 KB)
 
-// ---- what the five kernels share on the device ----
+// ---- what the six kernels share on the device ----
 struct WrwRun { int kt, ct, split, b, ylo; };               // tile, run, and the run's image and first grid row
 
 // workgroup -> (tile, run): the tiles of one run are neighbours
@@ -2068,7 +2072,160 @@ __global__ void __launch_bounds__(512, 1) conv_bf16x3_wrw_dil_kernel(const float
         }
 }
 
-// ---- the host side of the five weight-gradient kernels: one planner, one byte count, one launcher over WRW_KINDS ----
+// =====================================================================================================================================
+// The same dilated weight gradient on BF16 tensors (ipsr_conv4x4s2_bf16_dil_wrw; the opt-in switch set_direct_dilated_bf16_dw under bf16
+// activations): one plane and ONE MFMA per product.  Work split, slab store and reduction are conv_bf16_wrw_s2_kernel's, as is the coarse
+// operand: double-buffered by LDS-DMA, 2 x 16 KB, XOR-swizzled chunks, channels past Kc from the zero page.  The q ring, its zero rows, the
+// column-tap fragments (wd_taps) and the 128-wide form are conv_bf16x3_wrw_dil_kernel's with the one plane:
+//   * q is sampled on the way in: a thread loads 16 bytes (8 bf16) of an odd fine row into registers behind the previous step's
+//     multiplications, keeps the 4 odd pixels (two v_perm_b32) and stores 8 bytes.  No even fine row is loaded, no even fine column is stored;
+//   * q row y lives in ring slot (y + 2) mod (RS + 3); rows -2 and -1 are the ring's initial zeros, a row at or past nh loads row nh - 1 and
+//     stores zeros, channels past Cf store zeros, the halo slots (one in front of and one behind every (row, channel)) are zeroed once;
+//   * nw = 128 (WIDE): a step is half a q row, RS = 1, stages_per_wg counts ROWS, the ring is 4 rows.
+// A step that brings new rows has two barriers (every wave done reading the ring | the new rows stored, the coarse DMA landed); one otherwise.
+// LDS: coarse 2 x 16 KB; ring (RS + 3) rows x 32 cf x (nw / 8 + 3) slots x 16 B:
+//      nw = 16: 32768 + 17920 = 50688 B    nw = 32: 32768 + 17920 = 50688 B    nw = 64: 32768 + 22528 = 55296 B    nw = 128: 32768 + 38912 = 71680 B
+// Supported: nw in {16, 32, 64, 128}, nh a multiple of max(1, 64 / nw).  Deterministic: no atomics, every sum in a fixed order.
+
+// 8 consecutive bf16 pixels of an odd fine row -> the 4 odd ones
+__device__ __forceinline__ u32x2 wd_pick4_odd(const u32x4& v) { return u32x2{pack_hi(v.x, v.y), pack_hi(v.z, v.w)}; }
+
+template <bool WIDE>
+__global__ void __launch_bounds__(512, 1) conv_bf16_wrw_dil_kernel(const unsigned short* __restrict__ coarse, const unsigned short* __restrict__ fine,
+                                                                    const uint4* __restrict__ zero_page, WrwGeom g, float* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];          // A[2] | q-row ring
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, rh = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+    const WrwRun run = wrw_decode(g);
+    const int kt = run.kt, ct = run.ct, b = run.b, ylo = run.ylo, split = run.split;
+    const int Wf = 2 * g.W;
+    const size_t HWc = (size_t)g.H * g.W, HWf = 4 * HWc;
+    const int hpr = g.W >> 2;                                // 4-pixel half chunks per q row
+    unsigned char* const ring = lds + 2 * W2_A_BYTES;
+    const int row_bytes = W2_C * g.pitch * 16;
+
+    // ---- coarse rows: slot sigma = k * 8 + cs holds step chunk c8 = cs ^ (k & 7) of channel k; a step's 64 pixels are contiguous ------------
+    const unsigned short* ga[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int sigma = (wave + 8 * j) * 64 + lane;
+        const int k = sigma >> 3, c8 = (sigma & 7) ^ (k & 7);
+        const int kc = kt * W2_K + k;
+        ga[j] = kc < g.K ? coarse + ((size_t)b * g.K + kc) * HWc + (size_t)ylo * g.W + c8 * 8 : nullptr;
+    }
+    // ---- q rows: as in conv_bf16x3_wrw_dil_kernel: a lane owns half chunk (tid & 15) + 16 j (row fr, half chunk fx) of channel tid >> 4 -----
+    constexpr int NQ = WIDE ? 2 : 1;
+    const int c0 = tid >> 4;
+    const bool fok = ct * W2_C + c0 < g.C;                   // channels past Cf: a valid address (the last channel), zeros are stored
+    const unsigned short* gq = fine + ((size_t)b * g.C + (fok ? ct * W2_C + c0 : g.C - 1)) * HWf + Wf;          // q row 0 = fine row 1
+    int fr[NQ], fx[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int hi = (tid & 15) + 16 * j;
+        fr[j] = hi >> (g.wshift - 2); fx[j] = hi & (hpr - 1);
+    }
+    const int q_wr = (c0 * g.pitch + 1) * 16;                // + fx * 8
+
+    f32x16 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.0f;
+
+    auto dma_a = [&](int buf, int st) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const void* src = ga[j] ? static_cast<const void*>(ga[j] + (size_t)st * W2_PX) : static_cast<const void*>(zero_page);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + buf * W2_A_BYTES + (wave + 8 * j) * 1024), 16, 0, 0);
+        }
+    };
+    u32x4 fw[NQ];
+    // unit u (a stage; WIDE: a row): the q rows y0 + 1 .. y0 + RS, what it reads beyond the rows of unit u - 1.  Unconditional loads: a row
+    // below the image reads row nh - 1 instead and store_q stores zeros for it
+    auto load_q = [&](int u) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int y = ylo + u * g.RS + 1 + fr[j];
+            fw[j] = *reinterpret_cast<const u32x4*>(gq + (size_t)(y < g.H ? y : g.H - 1) * (2 * Wf) + fx[j] * 8);
+        }
+    };
+    auto store_q = [&](int u) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int y = ylo + u * g.RS + 1 + fr[j];
+            u32x2 v = wd_pick4_odd(fw[j]);
+            if (!(y < g.H && fok)) v = u32x2{0u, 0u};                            // row below the image / channel past Cf
+            *reinterpret_cast<u32x2*>(ring + ((y + 2) % g.NRING) * row_bytes + q_wr + fx[j] * 8) = v;
+        }
+    };
+
+    // prologue: the ring starts as zeros (halo slots and the rows above the image keep them); rows ylo - 2 .. ylo, then unit 0
+    for (int i = tid; i < g.ring_plane / 16; i += 512) *reinterpret_cast<u32x4*>(ring + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    dma_a(0, 0);
+    load_q(0);
+    __syncthreads();
+    for (int i = tid; i < 3 * W2_C * hpr; i += 512) {
+        const int m = i / (W2_C * hpr), rem = i - m * (W2_C * hpr);
+        const int c = rem / hpr, x4 = rem - c * hpr;
+        const int y = ylo - 2 + m, cf = ct * W2_C + c;
+        if (cf < g.C && y >= 0) {                            // else: the zeros stay
+            const unsigned short* src = fine + ((size_t)b * g.C + cf) * HWf + (size_t)(2 * y + 1) * Wf + x4 * 8;
+            *reinterpret_cast<u32x2*>(ring + ((y + 2) % g.NRING) * row_bytes + (c * g.pitch + 1) * 16 + x4 * 8) = wd_pick4_odd(*reinterpret_cast<const u32x4*>(src));
+        }
+    }
+    store_q(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    const int a_row = wk * 32 + r;
+    const int nsteps = WIDE ? 2 * g.stages_per_wg : g.stages_per_wg;
+    for (int st = 0; st < nsteps; ++st) {
+        const int cur = st & 1;
+        const int y0 = ylo + (WIDE ? st >> 1 : st * g.RS);
+        const bool more = st + 1 < nsteps, new_rows = more && (!WIDE || (st & 1));
+        if (more) dma_a(cur ^ 1, st + 1);                     // lands behind this step's multiplications
+        if (new_rows) load_q(WIDE ? (st + 1) >> 1 : st + 1);
+        const unsigned char* A = lds + cur * W2_A_BYTES;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                         // k-steps of 16 coarse pixels
+            const int f8 = 2 * j + h;
+            const bf16x8 fa = *reinterpret_cast<const bf16x8*>(A + ((a_row << 3) + (f8 ^ (a_row & 7))) * 16);
+            const int p0 = 16 * j + (WIDE ? 64 * (st & 1) : 0);
+            const int rs = WIDE ? 0 : p0 >> g.wshift, ox0 = (p0 & (g.W - 1)) + 8 * h;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const int slot = (y0 + rs + 2 * rh + ri) % g.NRING;             // q row y0 + rs + (tap row 2 rh + ri) - 2
+                u32x4 f[4];                                  // [column tap]
+                wd_taps(ring + slot * row_bytes + (r * g.pitch + 1 + (ox0 >> 3)) * 16, f);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[ri * 4 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, __builtin_bit_cast(bf16x8, f[t]), acc[ri * 4 + t], 0, 0, 0);
+            }
+        }
+        if (new_rows) {
+            __syncthreads();                                  // every wave is done reading the rows the new ones replace
+            store_q(WIDE ? (st + 1) >> 1 : st + 1);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    // partial result: slab[split][t = r * 4 + s][kc][cf] (lanes along cf)
+    const int Kp = g.ktiles * W2_K, Cp = g.ctiles * W2_C;
+    float* out = slabs + (size_t)split * 16 * Kp * Cp;
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ka = kt * W2_K + wk * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            out[((size_t)(rh * 8 + t) * Kp + ka) * Cp + ct * W2_C + r] = acc[t][e];
+        }
+}
+
+// ---- the host side of the six weight-gradient kernels: one planner, one byte count, one launcher over WRW_KINDS ----
 static size_t wrw_lds_bytes(const WrwKind& k, const WrwGeom& g) { return 2 * (size_t)k.TK * k.PX * 2 + (k.split ? 2 : 1) * (size_t)g.ring_plane; }
 
 // The limits, before any launch (3x3: K = Ka, C = Cb, the image H x W; k4 s2: K = Kc, C = Cf, the coarse grid nh x nw).
@@ -2101,7 +2258,7 @@ static size_t wrw_ws_bytes(int kind, int B, int K, int C, int H, int W)
     return (k.split ? 0 : 256) + (size_t)g.nsplit * k.NT * g.ktiles * k.TK * g.ctiles * k.TC * 4;
 }
 
-// a [B,K,H,W], w [B,C,wscale H,wscale W] (dilated: [B,C,2H,2W]) (bf16, or fp32 for the split kinds) -> dW [K][C][NT] fp32
+// a [B,K,H,W], w [B,C,wscale H,wscale W] (the dilated kinds: [B,C,2H,2W]) (bf16, or fp32 for the split kinds) -> dW [K][C][NT] fp32
 template <int KIND>
 static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int C, int H, int W, void* ws, size_t ws_bytes, hipStream_t st)
 {
@@ -2120,7 +2277,12 @@ static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int
     else if constexpr (KIND == WRW_3X3_SPLIT) kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_kernel);
     else if constexpr (KIND == WRW_S2) kernel = reinterpret_cast<const void*>(&conv_bf16_wrw_s2_kernel);
     else if constexpr (KIND == WRW_S2_SPLIT) kernel = reinterpret_cast<const void*>(&conv_bf16x3_wrw_s2_kernel);
-    else kernel = W == 128 ? reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<true>) : reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<false>);
+    else if constexpr (KIND == WRW_DIL_SPLIT)
+        kernel = W == 128 ? reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<true>) : reinterpret_cast<const void*>(&conv_bf16x3_wrw_dil_kernel<false>);
+    else {
+        static_assert(KIND == WRW_DIL, "one branch per row of WRW_KINDS");
+        kernel = W == 128 ? reinterpret_cast<const void*>(&conv_bf16_wrw_dil_kernel<true>) : reinterpret_cast<const void*>(&conv_bf16_wrw_dil_kernel<false>);
+    }
     if (int rc = cb_raise_lds(kernel, k.kernel)) return rc;
     profile_mark_start(st, 4);
     if constexpr (KIND == WRW_3X3)
@@ -2131,10 +2293,14 @@ static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int
         conv_bf16_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);
     else if constexpr (KIND == WRW_S2_SPLIT)
         conv_bf16x3_wrw_s2_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
-    else if (W == 128)
-        conv_bf16x3_wrw_dil_kernel<true><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
-    else
-        conv_bf16x3_wrw_dil_kernel<false><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    else if constexpr (KIND == WRW_DIL_SPLIT) {
+        if (W == 128) conv_bf16x3_wrw_dil_kernel<true><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+        else conv_bf16x3_wrw_dil_kernel<false><<<grid, WB_THREADS, smem, st>>>(static_cast<const float*>(a), static_cast<const float*>(w), g, slabs);
+    } else {
+        const unsigned short *ca = static_cast<const unsigned short*>(a), *fw = static_cast<const unsigned short*>(w);
+        if (W == 128) conv_bf16_wrw_dil_kernel<true><<<grid, WB_THREADS, smem, st>>>(ca, fw, zero_page, g, slabs);
+        else conv_bf16_wrw_dil_kernel<false><<<grid, WB_THREADS, smem, st>>>(ca, fw, zero_page, g, slabs);
+    }
     const double px = (double)B * H * W;
     profile_mark_stop(st, 4, (k.split ? 3.0 : 1.0) * 2.0 * k.NT * (double)(g.ktiles * k.TK) * (g.ctiles * k.TC) * px, 2.0 * k.NT * (double)K * C * px);
     if (int rc = check_launch(k.kernel)) return rc;
@@ -2297,6 +2463,20 @@ int ipsr_conv4x4s2_bf16x3_dil_wrw(const float* fine, const float* coarse, float*
     if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16x3_dil_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
     if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16x3_dil_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
     return launch_wrw<WRW_DIL_SPLIT>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t ipsr_conv4x4s2_bf16_dil_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw)
+{
+    if (cb_bad_dims("ipsr_conv4x4s2_bf16_dil_wrw_workspace_bytes", true, {B, Kc, Cf, nh, nw})) return 0;
+    return wrw_ws_bytes(WRW_DIL, B, Kc, Cf, nh, nw);
+}
+
+int ipsr_conv4x4s2_bf16_dil_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw, void* ws, size_t ws_bytes, void* stream)
+{
+    if (int rc = cb_null("ipsr_conv4x4s2_bf16_dil_wrw", {fine, coarse, dw, ws})) return rc;
+    if (int rc = cb_bad_dims("ipsr_conv4x4s2_bf16_dil_wrw", true, {B, Kc, Cf, nh, nw})) return rc;
+    if (int rc = cb_misaligned("ipsr_conv4x4s2_bf16_dil_wrw", "operands / workspace", {ws, fine, coarse, dw})) return rc;
+    return launch_wrw<WRW_DIL>(coarse, fine, dw, B, Kc, Cf, nh, nw, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t ipsr_conv3x3_bf16_wrw_workspace_bytes(int transposed, int B, int Cin, int H, int W, int Cout)

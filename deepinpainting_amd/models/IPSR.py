@@ -65,6 +65,8 @@ class IPSR(BaseModel):
         hipconv.set_direct_dilated_dw(bool(getattr(opt, 'direct_dilated_dw', False)))
         # opt-in, a switch of its own: their forward / input gradient under amp_bf16 on the direct bf16 kernel
         hipconv.set_direct_dilated_bf16(bool(getattr(opt, 'direct_dilated_bf16', False)))
+        # opt-in, a switch of its own: their weight gradient under amp_bf16 on the direct bf16 kernel
+        hipconv.set_direct_dilated_bf16_dw(bool(getattr(opt, 'direct_dilated_bf16_dw', False)))
         # conv-bias + InstanceNorm + activation in one HIP kernel each way (models/fused.py); False = plain torch modules
         networks.FusedSequential.enabled = bool(getattr(opt, 'fused_norm_act', True))
 

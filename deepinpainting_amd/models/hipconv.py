@@ -38,7 +38,9 @@ engine does not take into "miopen": no rule, and no forced mode, can hand an eng
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
                                   — and, by a switch of its own (`set_direct_dilated_bf16`), forward / input gradient of netG's dilated down
                                   convolution Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input
-                                  (ops.conv4x4s2_bf16_dil), instead of "wino_dil" / MIOpen; its weight gradient stays where it is
+                                  (ops.conv4x4s2_bf16_dil), instead of "wino_dil" / MIOpen — and, by another switch of its own
+                                  (`set_direct_dilated_bf16_dw`), that layer's weight gradient as the pixel reduction over the same
+                                  quarter (ops.conv4x4s2_bf16_dil_wrw), instead of "wino_dil" / MIOpen
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32=...)`, the four direct names of ops.DIRECT_PASSES): forward / input gradient on split-bf16 operands
                                   — and, by a switch of its own (`set_direct_dilated`), forward / input gradient of netG's dilated down convolution
                                   Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input, instead of "wino_dil"
@@ -134,6 +136,24 @@ def set_direct_dilated_bf16(on):
 def direct_dilated_bf16():
     """Whether `set_direct_dilated_bf16` is on."""
     return _DIRECT_DILATED_BF16
+
+
+_DIRECT_DILATED_BF16_DW = False    # opt-in: the dilated 4x4 stride-2 weight gradient under bf16 activations on the direct bf16 kernel
+
+
+def set_direct_dilated_bf16_dw(on):
+    """Opt-in, default off, independent of `set_conv_math` and of the three other dilated switches: under bf16 activations, the weight gradient
+    of the dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" or MIOpen has goes to the direct bf16 kernel
+    ("bf16d", ops.conv4x4s2_bf16_dil_wrw) on every shape it takes (`_dilated_bf16_dw_opt_in`).  The data passes, fp32 activations, forced
+    engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
+    global _DIRECT_DILATED_BF16_DW
+    _DIRECT_DILATED_BF16_DW = bool(on)
+    _SEL.clear()
+
+
+def direct_dilated_bf16_dw():
+    """Whether `set_direct_dilated_bf16_dw` is on."""
+    return _DIRECT_DILATED_BF16_DW
 
 
 def _direct_passes_on():
@@ -511,6 +531,8 @@ def _select_wrw_any(lay, bf16):
         # 3 -> 64 k4 s2 0.033 vs MIOpen's 0.057 ms, ConvT 128 -> 3 k3 0.152 vs 0.202, k4 s2 0.052 vs 0.063, 6 -> 64 0.118 vs 0.125 — and 2
         # launches instead of MIOpen's 5-6)
         eng = "thin_mfma" if thin else _bf16_direct_wrw(lay)
+    if bf16:
+        eng = _dilated_bf16_dw_opt_in(eng, lay)
     # the final guard, as in `_select_any`: "winograd", "wino_dil" and "wino_s2" weight gradients are answered without a probe
     return eng if engine_takes(eng, "wrw", None, lay, bf16) else "miopen"
 
@@ -527,6 +549,23 @@ def _bf16_direct_wrw(lay):
     if g is not None and g[3] >= 32 and ((g[0] + 127) // 128) * ((g[1] + 31) // 32) >= 4 and engine_takes("bf16d", "wrw", None, lay, True):
         return "bf16d"           # 1.2-1.4x MIOpen from four 128 x 32 output tiles up on coarse grids >= 32 wide; 16-wide grids and single tiles lose
     return "miopen"
+
+
+def _dilated_bf16_dw_opt_in(base, lay):
+    """bf16 activations under `set_direct_dilated_bf16_dw(True)`: the weight gradient of the dilated down convolution that the chain answers
+    "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) goes to the direct bf16 kernel wherever it takes the
+    shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated_bf16` follows for the data passes.  Mode
+    "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids (answered before this), netD's k4 s1 p1 and transposed layers stay.
+    Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_wrw_layers.txt): 64 -> 64 @256 against MIOpen
+    1.37x (0.117 vs 0.160 ms), 128 -> 128 @128 against MIOpen 1.62x, 256 -> 256 @64 against "wino_dil" 1.50x, 512 -> 512 @32 against "wino_dil"
+    0.64x (LOSES, 0.131 vs 0.084 ms: 16 runs of 16.8 MB slabs); every row's ranges apart.  The switch moves all four; the config-5 step rate
+    goes from 829.5 to 833.2 images/s with `set_direct_dilated_bf16` on in both columns (+0.4 %, five alternated rounds, the ranges apart).
+    Other batches and channel counts inside the kernel's limits were not measured."""
+    if not _DIRECT_DILATED_BF16_DW or _mode() != "auto" or _env("IPSR_BF16_ENGINES", "") != "" or base not in ("wino_dil", "miopen"):
+        return base
+    if _dil_geometry(lay) is not None and engine_takes("bf16d", "wrw", None, lay, True):
+        return "bf16d"
+    return base
 
 
 def _dil_geometry(lay):
@@ -673,12 +712,13 @@ def _fine_coarse(x, dy, lay):
 
 def _direct_case(lay, x3):
     """-> (case, g): which entry point of csrc/conv_bf16.hip a layer reaches on the direct bf16 (x3 False) / split-bf16 (x3 True) engines —
-    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, g = `_dil_geometry`; on the bf16 engine its data
-    passes only, and only while `set_direct_dilated_bf16` is on) — or (None, None) where their calls cannot express the layer.  The run calls
+    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, g = `_dil_geometry`; on the bf16 engine only
+    while `set_direct_dilated_bf16` or `set_direct_dilated_bf16_dw` is on: `_bf16d_takes` asks the first for the data passes, the second for
+    the weight gradient) — or (None, None) where their calls cannot express the layer.  The run calls
     and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" all branch on it."""
     if lay[6:] == _K3:
         return "k3", None
-    dilated = (x3 or _DIRECT_DILATED_BF16) and _is_dilated4(*lay[6:])
+    dilated = (x3 or _DIRECT_DILATED_BF16 or _DIRECT_DILATED_BF16_DW) and _is_dilated4(*lay[6:])
     g = _dil_geometry(lay) if dilated else _s2_geometry(lay)
     return (None if g is None else "dil" if dilated else "s2"), g
 
@@ -701,8 +741,11 @@ def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
 
 
 def _bf16d_wrw(x, dy, lay, math, sink):
-    if _direct_case(lay, False)[0] == "k3":
+    case, g = _direct_case(lay, False)
+    if case == "k3":
         return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
+    if case == "dil":
+        return ops.conv4x4s2_bf16_dil_wrw(x, dy, lay[1], *g, out=sink)        # Conv2d only: (fine, coarse) = (x, dy)
     return ops.conv4x4s2_bf16_wrw(*_fine_coarse(x, dy, lay), out=sink)
 
 
@@ -712,8 +755,10 @@ def _bf16d_takes(kind, op, lay, bf16):
         return False
     if case == "k3":
         return ops.conv3x3_bf16_supported(op, *lay[1:6]) if kind == "data" else ops.conv3x3_bf16_wrw_supported(*lay[:6])
-    if case == "dil":                        # no weight gradient: it stays on "wino_dil" / MIOpen
-        return kind == "data" and ops.conv4x4s2_bf16_dil_supported(_dil_mode(op) & ~ops.S2_DILATED, lay[1], *g)
+    if case == "dil":                        # each kind under its own switch
+        if kind == "data":
+            return _DIRECT_DILATED_BF16 and ops.conv4x4s2_bf16_dil_supported(_dil_mode(op) & ~ops.S2_DILATED, lay[1], *g)
+        return _DIRECT_DILATED_BF16_DW and ops.conv4x4s2_bf16_dil_wrw_supported(lay[1], *g)
     return ops.conv4x4s2_bf16_supported(_s2_mode(op), lay[1], *g) if kind == "data" else ops.conv4x4s2_bf16_wrw_supported(lay[1], *g)
 
 

@@ -797,6 +797,17 @@ def conv4x4s2_bf16x3_dil_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
     return _conv4x4s2_direct_wrw("bf16x3_dil", fine, coarse, B, Kc, Cf, nh, nw, out)
 
 
+def conv4x4s2_bf16_dil_wrw_supported(B, Kc, Cf, nh, nw):
+    return _lib.lib().ipsr_conv4x4s2_bf16_dil_wrw_workspace_bytes(B, Kc, Cf, nh, nw) > 0
+
+
+def conv4x4s2_bf16_dil_wrw(fine, coarse, B, Kc, Cf, nh, nw, out=None):
+    """Weight gradient [Kc,Cf,4,4] (fp32) of Conv2d(Cf, Kc, k4, stride 2, pad 3, dilation 2) from its bf16 input fine [B,Cf,2nh,2nw] and bf16
+    output gradient coarse [B,Kc,nh,nw] on the bf16 matrix cores (ipsr_conv4x4s2_bf16_dil_wrw): one MFMA per product, fp32 accumulation, only
+    the odd rows and odd columns of `fine` are used; `out` as in conv4x4s2_bf16_wrw."""
+    return _conv4x4s2_direct_wrw("bf16_dil", fine, coarse, B, Kc, Cf, nh, nw, out)
+
+
 def conv3x3_bf16_wrw_supported(transposed, B, Cin, H, W, Cout):
     return _lib.lib().ipsr_conv3x3_bf16_wrw_workspace_bytes(int(transposed), B, Cin, H, W, Cout) > 0
 

@@ -568,6 +568,17 @@ int ipsr_conv4x4s2_bf16x3_wrw(const float* fine, const float* coarse, float* dw,
 size_t ipsr_conv4x4s2_bf16x3_dil_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
 int ipsr_conv4x4s2_bf16x3_dil_wrw(const float* fine, const float* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
                                   void* ws, size_t ws_bytes, void* stream);
+/* the same weight gradient of the DILATED layer on BF16 tensors (the opt-in switch set_direct_dilated_bf16_dw under bf16 activations): fine
+ * [B,Cf,2nh,2nw] = the layer's bf16 input, coarse [B,Kc,nh,nw] = its bf16 output gradient -> dw [Kc][Cf][4][4] fp32, the sum above with one
+ * bf16 MFMA per product (products of bf16 are exact in fp32) and fp32 accumulation.  Only odd fine rows are loaded and no even fine column
+ * enters a product.  Two launches: partial [tap][kc][cf] slabs of the pixel runs, added in ascending order (deterministic, no atomics).
+ * Supported: nw in {16, 32, 64, 128}, nh a multiple of max(1, 64 / nw), any Kc, Cf, B >= 1; anything else -> IPSR_ERR_UNSUPPORTED, checked
+ * before any launch and before anything is written.  The workspace query returns 0 where the shape is unsupported, reason in
+ * ipsr_last_error(); a short workspace is IPSR_ERR_WORKSPACE; fine, coarse, dw and ws must be 16-byte aligned.  Added without an ABI
+ * version change (15): entries are added, none changes. */
+size_t ipsr_conv4x4s2_bf16_dil_wrw_workspace_bytes(int B, int Kc, int Cf, int nh, int nw);
+int ipsr_conv4x4s2_bf16_dil_wrw(const void* fine, const void* coarse, float* dw, int B, int Kc, int Cf, int nh, int nw,
+                                void* ws, size_t ws_bytes, void* stream);
 /* their weight gradient: x [B,Cin,H,W], dy [B,Cout,H,W] -> dw fp32 in the module's layout.  The reduction over pixels is cut over
  * workgroups; the partial results are added in a fixed order by a second launch (deterministic).  W in {16, 32, 64, 128}, H a multiple
  * of 128 / W.  form:
