@@ -5,9 +5,10 @@ nn.ConvTranspose2d modules whose parameters, names and state_dict keys are untou
 One engine per (operation, geometry), chosen by `select()` / `select_wrw()` from measurements on MI355X at the step's shapes
 (tools/bench_hipconv.py -> profiles/r02_hipconv_*.txt).  The engines are the records of `_ENGINES` below — the call that runs each
 pass, the support query that says which layers the engine accepts (`takes`), and what the engine needs.  A new engine is one record
-there (its passes, its `takes`, its flags) plus its rule in `_select` / `_select_wrw`; a new direct split-bf16 opt-in is one row of
-`_DIRECT_OPT_INS`.  A rule asks the record before it answers, and a last guard in `_select_any` / `_select_wrw_any` turns any answer its
-engine does not take into "miopen": no rule, and no forced mode, can hand an engine a layer it raises on.
+there (its passes, its `takes`, its flags) plus its rule in `_select` / `_select_wrw`; a new direct opt-in, for fp32 or for bf16
+activations, is one row of `_DIRECT_OPT_INS` (and, where it reaches a new entry point, one entry of `_DIRECT_ENTRIES`).  A rule asks the
+record before it answers, and a last guard in `_select_any` / `_select_wrw_any` turns any answer its engine does not take into "miopen":
+no rule, and no forced mode, can hand an engine a layer it raises on.
 
   "winograd"  csrc/winograd.hip   k3 s1 p1 forward / backward-data of Conv2d and ConvTranspose2d, F(4x4,3x3) on fp32 MFMA:
                                   2.0-2.4x MIOpen's F(2x2,3x3) assembly from 16x16 maps and 128 channels up
@@ -36,11 +37,13 @@ engine does not take into "miopen": no rule, and no forced mode, can hand an eng
                                   gradient as one pass over the input
   "bf16d"     csrc/conv_bf16.hip  bf16 activations (BASELINE config 5): the direct bf16 implicit GEMM, forward / input gradient / weight
                                   gradient of the k3 s1 p1 and k4 s2 p1 layers where the split-bf16 Winograd engines do not win
-                                  — and, by a switch of its own (`set_direct_dilated_bf16`), forward / input gradient of netG's dilated down
-                                  convolution Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input
-                                  (ops.conv4x4s2_bf16_dil), instead of "wino_dil" / MIOpen — and, by another switch of its own
-                                  (`set_direct_dilated_bf16_dw`), that layer's weight gradient as the pixel reduction over the same
-                                  quarter (ops.conv4x4s2_bf16_dil_wrw), instead of "wino_dil" / MIOpen
+                                  — and, by a switch of its own (`set_direct_dilated_bf16`, the "bf16_dil_data" row of `_DIRECT_OPT_INS`),
+                                  forward / input gradient of netG's dilated down convolution Conv2d(k4 s2 p3 d2) as a 16-tap correlation
+                                  on the odd / odd quarter of the input (ops.conv4x4s2_bf16_dil), instead of "wino_dil" / MIOpen — and, by
+                                  another switch of its own (`set_direct_dilated_bf16_dw`, the "bf16_dil_wrw" row), that layer's weight
+                                  gradient as the pixel reduction over the same quarter (ops.conv4x4s2_bf16_dil_wrw), instead of
+                                  "wino_dil" / MIOpen.  The engine takes a pass of that layer only while the pass's switch is on
+                                  (`_DIRECT_TAKES_SWITCH`)
   "bf16x3d"   csrc/conv_bf16.hip  fp32 activations, opt-in (`set_conv_math(fp32=...)`, the four direct names of ops.DIRECT_PASSES): forward / input gradient on split-bf16 operands
                                   — and, by a switch of its own (`set_direct_dilated`), forward / input gradient of netG's dilated down convolution
                                   Conv2d(k4 s2 p3 d2) as a 16-tap correlation on the odd / odd quarter of the input, instead of "wino_dil"
@@ -56,6 +59,7 @@ per-engine parity tests and for A/B timing.  Non-contiguous inputs and other dty
 """
 import os
 from collections import namedtuple
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -84,7 +88,20 @@ def set_conv_math(fp32=None, bf16=None):
     _SEL.clear()           # `select` memoises without the arithmetic
 
 
-_DIRECT_DILATED = False    # opt-in: the dilated 4x4 stride-2 data passes of "wino_dil" on the direct split-bf16 kernel (`set_direct_dilated`)
+# The four opt-in switches of netG's dilated down convolution, by the key of the row of `_DIRECT_OPT_INS` each one switches on: fp32 activations
+# on the direct split-bf16 kernels (data passes, weight gradient), bf16 activations on the direct bf16 kernels (the same two).
+_DIRECT_SWITCHES = {"dil_data": False, "dil_wrw": False, "bf16_dil_data": False, "bf16_dil_wrw": False}
+
+
+def _set_direct_switch(key, on):
+    _DIRECT_SWITCHES[key] = bool(on)
+    _SEL.clear()           # `select` memoises without the switches
+
+
+def _direct_passes_on():
+    """-> the keys of `_DIRECT_OPT_INS` that are switched on: the passes the fp32 arithmetic name moves (ops.DIRECT_PASSES) and the
+    `_DIRECT_SWITCHES` that are set.  The one place the switches are read."""
+    return ops.DIRECT_PASSES.get(_MATH["fp32"], frozenset()) | {key for key, on in _DIRECT_SWITCHES.items() if on}
 
 
 def set_direct_dilated(on):
@@ -92,9 +109,7 @@ def set_direct_dilated(on):
     convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" has go to the direct split-bf16 kernel ("bf16x3d",
     ops.conv4x4s2_bf16x3 with ops.S2_DILATED) on every shape it takes.  Weight gradients, bf16 activations, forced engines and the
     k4 s1 p1 layer stay where they are."""
-    global _DIRECT_DILATED
-    _DIRECT_DILATED = bool(on)
-    _SEL.clear()
+    _set_direct_switch("dil_data", on)
 
 
 def direct_dilated():
@@ -102,17 +117,12 @@ def direct_dilated():
     return "dil_data" in _direct_passes_on()
 
 
-_DIRECT_DILATED_DW = False # opt-in: the dilated 4x4 stride-2 weight gradient of "wino_dil" on the direct split-bf16 kernel (`set_direct_dilated_dw`)
-
-
 def set_direct_dilated_dw(on):
     """Opt-in, default off, independent of `set_conv_math` and of `set_direct_dilated`: under fp32 activations, the weight gradient of the
     dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" has goes to the direct split-bf16 kernel ("bf16x3w",
     ops.conv4x4s2_bf16x3_dil_wrw) on every shape it takes (the "dil_wrw" row of `_DIRECT_OPT_INS`).  The data passes, bf16 activations,
     forced engines, the k4 s1 p1 layer and "smallmap" grids stay where they are."""
-    global _DIRECT_DILATED_DW
-    _DIRECT_DILATED_DW = bool(on)
-    _SEL.clear()
+    _set_direct_switch("dil_wrw", on)
 
 
 def direct_dilated_dw():
@@ -120,51 +130,30 @@ def direct_dilated_dw():
     return "dil_wrw" in _direct_passes_on()
 
 
-_DIRECT_DILATED_BF16 = False   # opt-in: the dilated 4x4 stride-2 data passes under bf16 activations on the direct bf16 kernel (`set_direct_dilated_bf16`)
-
-
 def set_direct_dilated_bf16(on):
     """Opt-in, default off, independent of `set_conv_math`, `set_direct_dilated` and `set_direct_dilated_dw`: under bf16 activations, forward
     and input gradient of the dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" or MIOpen has go to the direct
-    bf16 kernel ("bf16d", ops.conv4x4s2_bf16_dil) on every shape it takes (`_dilated_bf16_opt_in`).  Weight gradients, fp32 activations, forced
-    engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
-    global _DIRECT_DILATED_BF16
-    _DIRECT_DILATED_BF16 = bool(on)
-    _SEL.clear()
+    bf16 kernel ("bf16d", ops.conv4x4s2_bf16_dil) on every shape it takes (the "bf16_dil_data" row of `_DIRECT_OPT_INS`).  Weight gradients,
+    fp32 activations, forced engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
+    _set_direct_switch("bf16_dil_data", on)
 
 
 def direct_dilated_bf16():
     """Whether `set_direct_dilated_bf16` is on."""
-    return _DIRECT_DILATED_BF16
-
-
-_DIRECT_DILATED_BF16_DW = False    # opt-in: the dilated 4x4 stride-2 weight gradient under bf16 activations on the direct bf16 kernel
+    return "bf16_dil_data" in _direct_passes_on()
 
 
 def set_direct_dilated_bf16_dw(on):
     """Opt-in, default off, independent of `set_conv_math` and of the three other dilated switches: under bf16 activations, the weight gradient
     of the dilated down convolution Conv2d(k4, stride 2, pad 3, dilation 2) that "wino_dil" or MIOpen has goes to the direct bf16 kernel
-    ("bf16d", ops.conv4x4s2_bf16_dil_wrw) on every shape it takes (`_dilated_bf16_dw_opt_in`).  The data passes, fp32 activations, forced
-    engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
-    global _DIRECT_DILATED_BF16_DW
-    _DIRECT_DILATED_BF16_DW = bool(on)
-    _SEL.clear()
+    ("bf16d", ops.conv4x4s2_bf16_dil_wrw) on every shape it takes (the "bf16_dil_wrw" row of `_DIRECT_OPT_INS`).  The data passes, fp32
+    activations, forced engines, "smallmap" grids and the k4 s1 p1 layer stay where they are."""
+    _set_direct_switch("bf16_dil_wrw", on)
 
 
 def direct_dilated_bf16_dw():
     """Whether `set_direct_dilated_bf16_dw` is on."""
-    return _DIRECT_DILATED_BF16_DW
-
-
-def _direct_passes_on():
-    """-> the keys of `_DIRECT_OPT_INS` that are switched on: the passes the fp32 arithmetic name moves (ops.DIRECT_PASSES), "dil_data" under
-    `set_direct_dilated`, "dil_wrw" under `set_direct_dilated_dw`.  The one place the three kinds of switch are read."""
-    on = ops.DIRECT_PASSES.get(_MATH["fp32"], frozenset())
-    if _DIRECT_DILATED:
-        on = on | {"dil_data"}
-    if _DIRECT_DILATED_DW:
-        on = on | {"dil_wrw"}
-    return on
+    return "bf16_dil_wrw" in _direct_passes_on()
 
 
 def _amp_bf16():
@@ -292,9 +281,7 @@ def _via_reach(kind, op, lay, bf16, reach):
 def _select_any(op, lay, bf16):
     eng = _select(op, lay)
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
-    if not bf16:
-        eng = _direct_opt_in("data", eng, op, lay)
-    elif not (_bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies):
+    if bf16 and not (_bf16_wins(eng, Cin, H, W, Cout) or _ENGINES[eng].fp32_copies):
         if _mode() == "auto" and _thin_wins(op, lay, True):
             eng = "thin"         # the vector-ALU stream kernels read / write bf16 tensors themselves (ipsr_conv3x3_thin_io)
         elif _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and op == ops.CONV_FWD and Cin == 3 and (k, stride, pad, dil) == (4, 2, 1, 1) and H * W >= 4096 \
@@ -304,8 +291,7 @@ def _select_any(op, lay, bf16):
             eng = "thin_f2m"
         else:
             eng = _bf16_direct(op, lay)
-    if bf16:
-        eng = _dilated_bf16_opt_in(eng, op, lay)
+    eng = _direct_opt_in("data", eng, op, lay, bf16)         # after the bf16 chain: the opt-ins replace its answer
     # the final guard: the rules and forced modes that probe nothing ("winograd", "wino_dil", IPSR_CONV_ENGINE=winograd) answer "miopen"
     # where their engine refuses the layer, instead of raising in `conv_nobias` on a layer torch computes
     return eng if engine_takes(eng, "data", op, lay, bf16) else "miopen"
@@ -334,23 +320,6 @@ def _bf16_direct(op, lay):
             return "bf16d" if nw >= 32 and ((Kc + 127) // 128) * B * nh * nw // 256 >= 128 else "miopen"
         return "bf16d"
     return "miopen"
-
-
-def _dilated_bf16_opt_in(base, op, lay):
-    """bf16 activations under `set_direct_dilated_bf16(True)`: the forward / input-gradient passes of the dilated down convolution that the
-    chain answers "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) go to the direct bf16 kernel
-    wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated` follows for
-    fp32.  Mode "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids, the weight gradient and netD's k4 s1 p1 stay.
-    Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_layers.txt, forward / input gradient):
-    64 -> 64 @256 against MIOpen 1.93x / 2.53x (0.077 / 0.073 vs 0.149 / 0.186 ms), 128 -> 128 @128 against MIOpen 1.75x / 2.47x, 256 -> 256 @64
-    against "wino_dil" 0.93x (LOSES, 0.086 vs 0.081 ms) / 1.13x, 512 -> 512 @32 against "wino_dil" 1.05x / 0.84x (LOSES, 0.091 vs 0.076 ms); every
-    row's ranges apart.  The switch moves all eight passes; the config-5 step rate goes from 821.3 to 834.4 images/s (+1.6 %, five alternated
-    rounds, the ranges apart).  Other batches and channel counts inside the kernel's limits were not measured."""
-    if not _DIRECT_DILATED_BF16 or _mode() != "auto" or _env("IPSR_BF16_ENGINES", "") != "" or base not in ("wino_dil", "miopen"):
-        return base
-    if op in (ops.CONV_FWD, ops.CONV_BWD_DATA) and _dil_geometry(lay) is not None and engine_takes("bf16d", "data", op, lay, True):
-        return "bf16d"
-    return base
 
 
 def _bf16_wins(eng, Cin, H, W, Cout, wrw=False):
@@ -524,15 +493,16 @@ def _select_wrw_any(lay, bf16):
     thin = _mode() == "auto" and _env("IPSR_NO_THIN", "0") != "1" and pad == 1 and dil == 1 and (k, stride) in ((3, 1), (4, 2)) and H * W >= 4096 \
         and engine_takes("thin_mfma", "wrw", None, lay, bf16)
     if not bf16:
-        # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8)
-        eng = "thin_mfma" if thin and eng == "miopen" else _direct_opt_in("wrw", eng, None, lay)
+        # fp32 activations: the same pixel reduction on v_mfma_f32_32x32x2_f32 (profiles/r04_thin_fp32.txt, batch 8).  It wins over the opt-ins:
+        # no row of `_DIRECT_OPT_INS` replaces "thin_mfma"
+        if thin and eng == "miopen":
+            eng = "thin_mfma"
     elif not (_bf16_wins(eng, Cin, H, W, Cout, True) or _ENGINES[eng].fp32_copies):
         # 3 / 6 channels on the narrow side: the pixel reduction on the bf16 matrix cores straight from NCHW (profiles/r04_thin_bf16.txt, batch 16:
         # 3 -> 64 k4 s2 0.033 vs MIOpen's 0.057 ms, ConvT 128 -> 3 k3 0.152 vs 0.202, k4 s2 0.052 vs 0.063, 6 -> 64 0.118 vs 0.125 — and 2
         # launches instead of MIOpen's 5-6)
         eng = "thin_mfma" if thin else _bf16_direct_wrw(lay)
-    if bf16:
-        eng = _dilated_bf16_dw_opt_in(eng, lay)
+    eng = _direct_opt_in("wrw", eng, None, lay, bf16)        # after the bf16 chain, as in `_select_any`
     # the final guard, as in `_select_any`: "winograd", "wino_dil" and "wino_s2" weight gradients are answered without a probe
     return eng if engine_takes(eng, "wrw", None, lay, bf16) else "miopen"
 
@@ -551,23 +521,6 @@ def _bf16_direct_wrw(lay):
     return "miopen"
 
 
-def _dilated_bf16_dw_opt_in(base, lay):
-    """bf16 activations under `set_direct_dilated_bf16_dw(True)`: the weight gradient of the dilated down convolution that the chain answers
-    "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) goes to the direct bf16 kernel wherever it takes the
-    shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated_bf16` follows for the data passes.  Mode
-    "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids (answered before this), netD's k4 s1 p1 and transposed layers stay.
-    Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_wrw_layers.txt): 64 -> 64 @256 against MIOpen
-    1.37x (0.117 vs 0.160 ms), 128 -> 128 @128 against MIOpen 1.62x, 256 -> 256 @64 against "wino_dil" 1.50x, 512 -> 512 @32 against "wino_dil"
-    0.64x (LOSES, 0.131 vs 0.084 ms: 16 runs of 16.8 MB slabs); every row's ranges apart.  The switch moves all four; the config-5 step rate
-    goes from 829.5 to 833.2 images/s with `set_direct_dilated_bf16` on in both columns (+0.4 %, five alternated rounds, the ranges apart).
-    Other batches and channel counts inside the kernel's limits were not measured."""
-    if not _DIRECT_DILATED_BF16_DW or _mode() != "auto" or _env("IPSR_BF16_ENGINES", "") != "" or base not in ("wino_dil", "miopen"):
-        return base
-    if _dil_geometry(lay) is not None and engine_takes("bf16d", "wrw", None, lay, True):
-        return "bf16d"
-    return base
-
-
 def _dil_geometry(lay):
     """(Kc, Cf, nh, nw) of a Conv2d(k4 s2 p3 d2) layer on an even map in the coarse / fine terms of ipsr_conv4x4s2_bf16x3, or None."""
     transposed, B, Cin, H, W, Cout, k, stride, pad, dil = lay
@@ -584,14 +537,17 @@ def _dil_mode(op):
 _DIL_WRW_MIOPEN_ROW = (64, 64, 128, 128)
 
 
-# ---- the direct split-bf16 opt-ins for fp32 activations: one row per pass a switch moves to "bf16x3d" / "bf16x3w" ---------------------------
-# key:      what switches the row on (`_direct_passes_on`): a pass name of ops.DIRECT_PASSES, or "dil_data" / "dil_wrw" for the two booleans
-# replaces: the base answers (`_select` / `_select_wrw`) the row may replace;  when(base, op, lay): what else must hold (op None for "wrw")
-# `_direct_opt_in` adds what every row shares: mode "auto" only (a forced engine is never overridden), and the engine must take the layer.
-_DirectOptIn = namedtuple("_DirectOptIn", "key kind engine replaces when")
+# ---- the direct opt-ins: one row per pass a switch moves to "bf16x3d" / "bf16x3w" (fp32 activations) or to "bf16d" (bf16 activations) --------
+# key:      what switches the row on (`_direct_passes_on`): a pass name of ops.DIRECT_PASSES, or a key of `_DIRECT_SWITCHES`
+# bf16:     the activation dtype the row is for: False fp32, True bf16
+# replaces: the answers of the chain before it (`_select` / `_select_wrw`, then the bf16 chain of `_select_any` / `_select_wrw_any`) the row
+#           may replace;  when(base, op, lay): what else must hold (op None for "wrw")
+# `_direct_opt_in` adds what every row shares: mode "auto" only (a forced engine is never overridden), for the bf16 rows IPSR_BF16_ENGINES unset
+# as well (the A/B values "all" / "none" are not overridden either), and the engine must take the layer.
+_DirectOptIn = namedtuple("_DirectOptIn", "key kind engine bf16 replaces when")
 _DIRECT_OPT_INS = (
     # the k3 s1 p1 forward / input gradient of "winograd": every shape the kernel takes, won or lost (profiles/direct_bf16x3_layers.txt)
-    _DirectOptIn("k3_data", "data", "bf16x3d", ("winograd",), lambda base, op, lay: True),
+    _DirectOptIn("k3_data", "data", "bf16x3d", False, ("winograd",), lambda base, op, lay: True),
     # "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k4 s2 p1 forward / input-gradient passes that "wino_s2" has go to the direct split-bf16
     # kernel (ops.conv4x4s2_bf16x3) where it takes the shape.  Measured at batch 8 on every such row of the step
     # (profiles/direct_bf16x3_s2_layers.txt): 1.23-2.51x "wino_s2" (0.037-0.106 vs 0.079-0.197 ms), every row's slowest round of the kernel
@@ -599,21 +555,21 @@ _DIRECT_OPT_INS = (
     # channel counts inside it were not measured.  Of MIOpen's k4 s2 p1 rows the kernel takes one in the step, netG's outermost
     # ConvTranspose2d 64 -> 64 @128 input gradient (0.072 vs 0.197 ms, 2.72x): that shape moves too, at any batch though only batch 8 was
     # measured; nothing else of MIOpen's does.
-    _DirectOptIn("s2_data", "data", "bf16x3d", ("wino_s2", "miopen"), lambda base, op, lay: _s2_geometry(lay) is not None and (
+    _DirectOptIn("s2_data", "data", "bf16x3d", False, ("wino_s2", "miopen"), lambda base, op, lay: _s2_geometry(lay) is not None and (
         base != "miopen" or (_s2_mode(op) == ops.S2_FINE_TO_COARSE and _s2_geometry(lay) == (64, 64, 128, 128)))),
     # `set_direct_dilated(True)`: the forward / input-gradient passes of the dilated down convolution that "wino_dil" has go to the direct
     # split-bf16 kernel wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.  Measured at batch 8 on the
     # step's four shapes (profiles/direct_bf16x3_dil_layers.txt, vs "wino_dil", forward / input gradient): 64 @256 wins 2.16x / 2.61x,
     # 128 @128 wins 1.55x / 1.72x, 512 @32 wins 1.47x / 1.30x, 256 @64 LOSES 0.82x / 0.93x; the switch moves all four, the step gains 1.5 %.
     # netD's k4 s1 p1 and the weight gradient stay on "wino_dil".
-    _DirectOptIn("dil_data", "data", "bf16x3d", ("wino_dil",),
+    _DirectOptIn("dil_data", "data", "bf16x3d", False, ("wino_dil",),
                  lambda base, op, lay: op in (ops.CONV_FWD, ops.CONV_BWD_DATA) and _dil_geometry(lay) is not None),
     # "direct_bf16x3_dw" / "direct_bf16x3_s2" / "direct_bf16x3_s2_dw": the k3 s1 p1 weight gradients that "winograd" / "miopen" have go to
     # the direct split-bf16 kernel (ops.conv3x3_bf16x3_wrw) on the shapes it takes from 32x32 maps up (`_bf16_direct_wrw`'s floor).  Measured
     # at batch 8 (profiles/direct_bf16x3_wrw_layers.txt): 2.6x MIOpen on 128 -> 128 @128x128, 1.2x / 1.5x the fp32 Winograd weight gradient
     # on 256 -> 256 / 512 -> 128 @64x64; 512 -> 512 @32x32 loses to it (0.136 vs 0.119 ms: the F(3x3,4x4) GEMM does 4x fewer
     # multiplications and its transforms are small there), so maps below 64x64 with >= 512 channels on both sides stay where they are.
-    _DirectOptIn("k3_wrw", "wrw", "bf16x3w", ("winograd", "miopen"), lambda base, op, lay: lay[6:] == (3, 1, 1, 1) and lay[3] * lay[4] >= 1024
+    _DirectOptIn("k3_wrw", "wrw", "bf16x3w", False, ("winograd", "miopen"), lambda base, op, lay: lay[6:] == (3, 1, 1, 1) and lay[3] * lay[4] >= 1024
                  and not (lay[3] * lay[4] < 4096 and min(lay[2], lay[5]) >= 512)),
     # "direct_bf16x3_s2_dw": the k4 s2 p1 weight gradients that "wino_s2" has go to the direct split-bf16 kernel (ops.conv4x4s2_bf16x3_wrw)
     # where it takes the shape (coarse grids 16, 32 or 64 wide).  Measured at batch 8 on every such row of the step
@@ -622,25 +578,47 @@ _DIRECT_OPT_INS = (
     # so the rule is every "wino_s2" weight gradient the kernel takes; other batches and the channel counts / grids `_s2_wins` admits beyond
     # the step's were not measured.  MIOpen's rows ("thin_mfma"'s 3-channel ends, netG's outermost 64 -> 64 on a 128-wide coarse grid, which
     # the kernel refuses), "smallmap", "one", the dilated family and grids below 16 wide stay where they are.
-    _DirectOptIn("s2_wrw", "wrw", "bf16x3w", ("wino_s2",), lambda base, op, lay: _s2_geometry(lay) is not None),
+    _DirectOptIn("s2_wrw", "wrw", "bf16x3w", False, ("wino_s2",), lambda base, op, lay: _s2_geometry(lay) is not None),
     # `set_direct_dilated_dw(True)`: the weight gradients of the dilated down convolution that "wino_dil" has go to the direct split-bf16
     # kernel (ops.conv4x4s2_bf16x3_dil_wrw) wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost.
     # Measured at batch 8 on the step's shapes (profiles/direct_bf16x3_dil_wrw_layers.txt): 1.84x "wino_dil" on 128 @128 (0.079 vs
     # 0.146 ms), 1.30x on 256 @64, 1.13x on 512 @32, the ranges apart in every row.  Of MIOpen's rows exactly one moves, at any batch though
     # only batch 8 was measured: 64 -> 64 @256x256, where the kernel's slowest round (0.1412 ms) is faster than MIOpen's fastest
     # (0.2164 ms), 1.68x on the medians.  The step gains 0.8-1.0 %.  netD's k4 s1 p1, "smallmap" grids and bf16 activations stay where they are.
-    _DirectOptIn("dil_wrw", "wrw", "bf16x3w", ("wino_dil", "miopen"), lambda base, op, lay: _dil_geometry(lay) is not None and (
+    _DirectOptIn("dil_wrw", "wrw", "bf16x3w", False, ("wino_dil", "miopen"), lambda base, op, lay: _dil_geometry(lay) is not None and (
         base != "miopen" or _dil_geometry(lay) == _DIL_WRW_MIOPEN_ROW)),
+    # bf16 activations under `set_direct_dilated_bf16(True)`: the forward / input-gradient passes of the dilated down convolution that the
+    # chain answers "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) go to the direct bf16 kernel
+    # wherever it takes the shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated` follows for
+    # fp32.  Mode "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids, the weight gradient and netD's k4 s1 p1 stay.
+    # Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_layers.txt, forward / input gradient):
+    # 64 -> 64 @256 against MIOpen 1.93x / 2.53x (0.077 / 0.073 vs 0.149 / 0.186 ms), 128 -> 128 @128 against MIOpen 1.75x / 2.47x, 256 -> 256 @64
+    # against "wino_dil" 0.93x (LOSES, 0.086 vs 0.081 ms) / 1.13x, 512 -> 512 @32 against "wino_dil" 1.05x / 0.84x (LOSES, 0.091 vs 0.076 ms); every
+    # row's ranges apart.  The switch moves all eight passes; the config-5 step rate goes from 821.3 to 834.4 images/s (+1.6 %, five alternated
+    # rounds, the ranges apart).  Other batches and channel counts inside the kernel's limits were not measured.
+    _DirectOptIn("bf16_dil_data", "data", "bf16d", True, ("wino_dil", "miopen"),
+                 lambda base, op, lay: op in (ops.CONV_FWD, ops.CONV_BWD_DATA) and _dil_geometry(lay) is not None),
+    # bf16 activations under `set_direct_dilated_bf16_dw(True)`: the weight gradient of the dilated down convolution that the chain answers
+    # "wino_dil" (kept by `_bf16_wins`: >= 256 channels up to 64x64) or "miopen" (the rest) goes to the direct bf16 kernel wherever it takes the
+    # shape (coarse grids 16 .. 128 wide) — every such shape, won or lost, the rule `set_direct_dilated_bf16` follows for the data passes.  Mode
+    # "auto" with IPSR_BF16_ENGINES unset only; "smallmap" grids (answered before this), netD's k4 s1 p1 and transposed layers stay.
+    # Against the switch-off answer at batch 16 on the step's four shapes (profiles/direct_bf16_dil_wrw_layers.txt): 64 -> 64 @256 against MIOpen
+    # 1.37x (0.117 vs 0.160 ms), 128 -> 128 @128 against MIOpen 1.62x, 256 -> 256 @64 against "wino_dil" 1.50x, 512 -> 512 @32 against "wino_dil"
+    # 0.64x (LOSES, 0.131 vs 0.084 ms: 16 runs of 16.8 MB slabs); every row's ranges apart.  The switch moves all four; the config-5 step rate
+    # goes from 829.5 to 833.2 images/s with `set_direct_dilated_bf16` on in both columns (+0.4 %, five alternated rounds, the ranges apart).
+    # Other batches and channel counts inside the kernel's limits were not measured.
+    _DirectOptIn("bf16_dil_wrw", "wrw", "bf16d", True, ("wino_dil", "miopen"), lambda base, op, lay: _dil_geometry(lay) is not None),
 )
 
 
-def _direct_opt_in(kind, base, op, lay):
-    """fp32 activations: -> the engine of the first row of `_DIRECT_OPT_INS` that moves this pass off its base answer, else `base`."""
-    if _mode() != "auto":
+def _direct_opt_in(kind, base, op, lay, bf16):
+    """-> the engine of the first row of `_DIRECT_OPT_INS` for this activation dtype that moves this pass off its base answer, else `base`."""
+    if _mode() != "auto" or (bf16 and _env("IPSR_BF16_ENGINES", "") != ""):
         return base
     on = _direct_passes_on()
     for row in _DIRECT_OPT_INS:
-        if row.kind == kind and row.key in on and base in row.replaces and row.when(base, op, lay) and engine_takes(row.engine, kind, op, lay, False):
+        if row.kind == kind and row.bf16 == bool(bf16) and row.key in on and base in row.replaces and row.when(base, op, lay) \
+                and engine_takes(row.engine, kind, op, lay, bf16):
             return row.engine
     return base
 
@@ -710,89 +688,76 @@ def _fine_coarse(x, dy, lay):
     return ((dy, x) if lay[0] else (x, dy)) + (lay[1],) + _s2_geometry(lay)
 
 
-def _direct_case(lay, x3):
-    """-> (case, g): which entry point of csrc/conv_bf16.hip a layer reaches on the direct bf16 (x3 False) / split-bf16 (x3 True) engines —
-    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, g = `_dil_geometry`; on the bf16 engine only
-    while `set_direct_dilated_bf16` or `set_direct_dilated_bf16_dw` is on: `_bf16d_takes` asks the first for the data passes, the second for
-    the weight gradient) — or (None, None) where their calls cannot express the layer.  The run calls
-    and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" all branch on it."""
+def _direct_case(lay):
+    """-> (case, g): which entry points of csrc/conv_bf16.hip a layer reaches on the direct bf16 / split-bf16 engines, from its geometry alone —
+    "k3" (k3 s1 p1), "s2" (k4 s2 p1, g = `_s2_geometry`), "dil" (the dilated down convolution, g = `_dil_geometry`) — or (None, None) where
+    their calls cannot express the layer.  The run calls and the `takes` of "bf16d" / "bf16x3d" / "bf16x3w" look `_DIRECT_ENTRIES` up by it."""
     if lay[6:] == _K3:
         return "k3", None
-    dilated = (x3 or _DIRECT_DILATED_BF16 or _DIRECT_DILATED_BF16_DW) and _is_dilated4(*lay[6:])
+    dilated = _is_dilated4(*lay[6:])
     g = _dil_geometry(lay) if dilated else _s2_geometry(lay)
     return (None if g is None else "dil" if dilated else "s2"), g
 
 
-def _direct_mode(case, op):
-    return _dil_mode(op) if case == "dil" else _s2_mode(op)
+# What the direct engines reach: (x3, case, kind) -> the ops.* call that runs the pass, its support query, and the mode argument of the k4 data
+# entries as a function of the pass's op.  x3: False = the bf16 kernels ("bf16d"), True = the split-bf16 ones on fp32 tensors ("bf16x3d" data,
+# "bf16x3w" weight gradient); case: `_direct_case`.  Names, not functions: looked up in `ops` at the call.  The split-bf16 dilated data pass is
+# the k4 s2 entry with ops.S2_DILATED or-ed into the mode; the bf16 one is an entry of its own that takes the plain mode.
+_DirectEntry = namedtuple("_DirectEntry", "run supported mode", defaults=(None,))
+_DIRECT_ENTRIES = {
+    (False, "k3", "data"): _DirectEntry("conv3x3_bf16", "conv3x3_bf16_supported"),
+    (False, "k3", "wrw"): _DirectEntry("conv3x3_bf16_wrw", "conv3x3_bf16_wrw_supported"),
+    (False, "s2", "data"): _DirectEntry("conv4x4s2_bf16", "conv4x4s2_bf16_supported", _s2_mode),
+    (False, "s2", "wrw"): _DirectEntry("conv4x4s2_bf16_wrw", "conv4x4s2_bf16_wrw_supported"),
+    (False, "dil", "data"): _DirectEntry("conv4x4s2_bf16_dil", "conv4x4s2_bf16_dil_supported", lambda op: _dil_mode(op) & ~ops.S2_DILATED),
+    (False, "dil", "wrw"): _DirectEntry("conv4x4s2_bf16_dil_wrw", "conv4x4s2_bf16_dil_wrw_supported"),
+    (True, "k3", "data"): _DirectEntry("conv3x3_bf16x3", "conv3x3_bf16x3_supported"),
+    (True, "k3", "wrw"): _DirectEntry("conv3x3_bf16x3_wrw", "conv3x3_bf16x3_wrw_supported"),
+    (True, "s2", "data"): _DirectEntry("conv4x4s2_bf16x3", "conv4x4s2_bf16x3_supported", _s2_mode),
+    (True, "s2", "wrw"): _DirectEntry("conv4x4s2_bf16x3_wrw", "conv4x4s2_bf16x3_wrw_supported"),
+    (True, "dil", "data"): _DirectEntry("conv4x4s2_bf16x3", "conv4x4s2_bf16x3_supported", _dil_mode),
+    (True, "dil", "wrw"): _DirectEntry("conv4x4s2_bf16x3_dil_wrw", "conv4x4s2_bf16x3_dil_wrw_supported"),
+}
+# The one place an engine's `takes` asks a switch: "bf16d" takes a pass of the dilated layer only while that pass's switch is on, so
+# `engine_takes("bf16d", ...)` follows `set_direct_dilated_bf16` / `set_direct_dilated_bf16_dw`.  "bf16x3d" / "bf16x3w" do NOT follow
+# `set_direct_dilated` / `set_direct_dilated_dw`: they take the dilated layer whatever the switches say, and only their rows of
+# `_DIRECT_OPT_INS` ask.  The asymmetry is how the two pairs were written; levelling it would change what `engine_takes` answers.
+_DIRECT_TAKES_SWITCH = {(False, "dil", "data"): "bf16_dil_data", (False, "dil", "wrw"): "bf16_dil_wrw"}
 
 
-def _bf16d_data(op, inp, w, lay, math, out_dtype, param):
-    """One pass of a module on the direct bf16 kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 / the dilated k4 s2 p3 d2 in their coarse /
-    fine form."""
-    if inp.dtype != torch.bfloat16:
-        inp = inp.to(torch.bfloat16)
-    case, g = _direct_case(lay, False)
+def _direct_data(x3, op, inp, w, lay, math, out_dtype, param):
+    """One pass of a module on the direct kernels (csrc/conv_bf16.hip): k3 s1 p1, or k4 s2 p1 / the dilated k4 s2 p3 d2 in their coarse / fine
+    form.  The bf16 kernels read bf16 tensors and write `out_dtype`; the split-bf16 ones read and write fp32."""
+    case, g = _direct_case(lay)
+    e = _DIRECT_ENTRIES[x3, case, "data"]
+    kw = {}
+    if not x3:
+        kw["out_dtype"] = out_dtype
+        if inp.dtype != torch.bfloat16:
+            inp = inp.to(torch.bfloat16)
     if case == "k3":
-        return ops.conv3x3_bf16(op, inp, w, lay[1:5], lay[5], out_dtype=out_dtype, **_frozen_pack(w, param))
-    if case == "dil":
-        return ops.conv4x4s2_bf16_dil(_dil_mode(op) & ~ops.S2_DILATED, inp, w, lay[1], *g, out_dtype=out_dtype)
-    return ops.conv4x4s2_bf16(_s2_mode(op), inp, w, lay[1], *g, out_dtype=out_dtype)
+        return getattr(ops, e.run)(op, inp, w, lay[1:5], lay[5], **kw, **_frozen_pack(w, param))
+    return getattr(ops, e.run)(e.mode(op), inp, w, lay[1], *g, **kw)
 
 
-def _bf16d_wrw(x, dy, lay, math, sink):
-    case, g = _direct_case(lay, False)
+def _direct_wrw(x3, x, dy, lay, math, sink):
+    case, g = _direct_case(lay)
+    run = getattr(ops, _DIRECT_ENTRIES[x3, case, "wrw"].run)
     if case == "k3":
-        return ops.conv3x3_bf16_wrw(lay[0], x, dy, lay[5], out=sink)
-    if case == "dil":
-        return ops.conv4x4s2_bf16_dil_wrw(x, dy, lay[1], *g, out=sink)        # Conv2d only: (fine, coarse) = (x, dy)
-    return ops.conv4x4s2_bf16_wrw(*_fine_coarse(x, dy, lay), out=sink)
+        return run(lay[0], x, dy, lay[5], out=sink)
+    return run(*((dy, x) if lay[0] else (x, dy)), lay[1], *g, out=sink)      # (fine, coarse) as in `_fine_coarse`; the dilated layer is Conv2d only
 
 
-def _bf16d_takes(kind, op, lay, bf16):
-    case, g = _direct_case(lay, False)
-    if not bf16 or case is None:             # reads bf16 activations
-        return False
+def _direct_takes(x3, kind, op, lay, bf16):
+    case, g = _direct_case(lay)
+    e = _DIRECT_ENTRIES.get((x3, case, kind))
+    switch = _DIRECT_TAKES_SWITCH.get((x3, case, kind))
+    if e is None or bool(bf16) == x3 or (switch is not None and switch not in _direct_passes_on()):      # "bf16d" reads bf16 activations, the
+        return False                                                                                     # split-bf16 pair fp32 ones
+    supported = getattr(ops, e.supported)
     if case == "k3":
-        return ops.conv3x3_bf16_supported(op, *lay[1:6]) if kind == "data" else ops.conv3x3_bf16_wrw_supported(*lay[:6])
-    if case == "dil":                        # each kind under its own switch
-        if kind == "data":
-            return _DIRECT_DILATED_BF16 and ops.conv4x4s2_bf16_dil_supported(_dil_mode(op) & ~ops.S2_DILATED, lay[1], *g)
-        return _DIRECT_DILATED_BF16_DW and ops.conv4x4s2_bf16_dil_wrw_supported(lay[1], *g)
-    return ops.conv4x4s2_bf16_supported(_s2_mode(op), lay[1], *g) if kind == "data" else ops.conv4x4s2_bf16_wrw_supported(lay[1], *g)
-
-
-def _bf16x3d_data(op, inp, w, lay, math, out_dtype, param):
-    """fp32 activations on the direct split-bf16 kernels: the same two shapes, and the dilated down convolution."""
-    case, g = _direct_case(lay, True)
-    if case == "k3":
-        return ops.conv3x3_bf16x3(op, inp, w, lay[1:5], lay[5], **_frozen_pack(w, param))
-    return ops.conv4x4s2_bf16x3(_direct_mode(case, op), inp, w, lay[1], *g)
-
-
-def _bf16x3d_takes(kind, op, lay, bf16):
-    case, g = _direct_case(lay, True)
-    if kind != "data" or bf16 or case is None:       # reads fp32 activations
-        return False
-    return ops.conv3x3_bf16x3_supported(op, *lay[1:6]) if case == "k3" else ops.conv4x4s2_bf16x3_supported(_direct_mode(case, op), lay[1], *g)
-
-
-def _bf16x3w_wrw(x, dy, lay, math, sink):
-    case, g = _direct_case(lay, True)
-    if case == "k3":
-        return ops.conv3x3_bf16x3_wrw(lay[0], x, dy, lay[5], out=sink)
-    if case == "dil":
-        return ops.conv4x4s2_bf16x3_dil_wrw(x, dy, lay[1], *g, out=sink)      # Conv2d only: (fine, coarse) = (x, dy)
-    return ops.conv4x4s2_bf16x3_wrw(*_fine_coarse(x, dy, lay), out=sink)
-
-
-def _bf16x3w_takes(kind, op, lay, bf16):
-    case, g = _direct_case(lay, True)
-    if kind != "wrw" or bf16 or case is None:
-        return False
-    if case == "k3":
-        return ops.conv3x3_bf16x3_wrw_supported(*lay[:6])
-    return (ops.conv4x4s2_bf16x3_dil_wrw_supported if case == "dil" else ops.conv4x4s2_bf16x3_wrw_supported)(lay[1], *g)
+        return supported(op, *lay[1:6]) if kind == "data" else supported(*lay[:6])
+    return supported(e.mode(op), lay[1], *g) if kind == "data" else supported(lay[1], *g)
 
 
 def _thin_mfma_wrw(x, dy, lay, math, sink):
@@ -863,9 +828,9 @@ _ENGINES = {
         lambda x, dy, lay, math, sink: ops.conv_to_one_wrw(x, dy, lay[6], lay[8], out=sink),
         lambda kind, op, lay, bf16: not lay[0] and lay[5] == 1 and (kind == "wrw" or op == ops.CONV_FWD) and ops.conv_to_one_supported(*lay[1:5], *lay[6:]),
         fp32_copies=True, sink=True),
-    "bf16d": _Engine(_bf16d_data, _bf16d_wrw, _bf16d_takes, bf16_io=True, sink=True, wrw_x_as_dy=True),
-    "bf16x3d": _Engine(_bf16x3d_data, takes=_bf16x3d_takes),
-    "bf16x3w": _Engine(None, _bf16x3w_wrw, _bf16x3w_takes, sink=True),
+    "bf16d": _Engine(partial(_direct_data, False), partial(_direct_wrw, False), partial(_direct_takes, False), bf16_io=True, sink=True, wrw_x_as_dy=True),
+    "bf16x3d": _Engine(partial(_direct_data, True), takes=lambda kind, op, lay, bf16: kind == "data" and _direct_takes(True, kind, op, lay, bf16)),
+    "bf16x3w": _Engine(None, partial(_direct_wrw, True), lambda kind, op, lay, bf16: kind == "wrw" and _direct_takes(True, kind, op, lay, bf16), sink=True),
     "miopen": _Engine(),
 }
 

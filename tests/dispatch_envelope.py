@@ -11,6 +11,8 @@ from collections import namedtuple
 
 K3, S2, DIL, K4S1 = (3, 1, 1, 1), (4, 2, 1, 1), (4, 2, 3, 2), (4, 1, 1, 1)      # (k, stride, pad, dil)
 OPT_IN_MATH = "direct_bf16x3_s2_dw"                                           # the widest of ops.DIRECT_PASSES
+# `switches` name -> (set_direct_dilated_bf16, set_direct_dilated_bf16_dw): the two dilated switches for bf16 activations
+BF16_DIL_SWITCHES = {"bf16_dil_data": (True, False), "bf16_dil_dw": (False, True), "bf16_dil": (True, True)}
 
 
 def out_extents(lay):
@@ -71,7 +73,7 @@ def takes(engine, kind, op, lay, bf16):
         return ops.conv2d_supported(op, B, Cin, H, W, Cout, k, stride, pad, dil)
     if engine == "one":
         return not transposed and Cout == 1 and (not data or op == ops.CONV_FWD) and ops.conv_to_one_supported(B, Cin, H, W, k, stride, pad, dil)
-    if engine in ("bf16d", "bf16x3d", "bf16x3w"):                # by geometry: k3; k4 s2 p1; dilated (the split-bf16 pair only)
+    if engine in ("bf16d", "bf16x3d", "bf16x3w"):                # by geometry: k3; k4 s2 p1; dilated ("bf16d": each kind under its own switch)
         x3 = engine != "bf16d"
         if x3 == bool(bf16):
             return False             # "bf16d" reads bf16 activations, the split-bf16 pair fp32 ones
@@ -81,9 +83,13 @@ def takes(engine, kind, op, lay, bf16):
             return (ops.conv3x3_bf16x3_wrw_supported if x3 else ops.conv3x3_bf16_wrw_supported)(transposed, B, Cin, H, W, Cout)
         if hc._is_dilated4(*geom):
             g = hc._dil_geometry(lay)
-            if not x3 or g is None:
+            if g is None:
                 return False
-            return ops.conv4x4s2_bf16x3_supported(hc._dil_mode(op), B, *g) if data else ops.conv4x4s2_bf16x3_dil_wrw_supported(B, *g)
+            if x3:                   # the split-bf16 pair answers whatever `set_direct_dilated` / `set_direct_dilated_dw` say
+                return ops.conv4x4s2_bf16x3_supported(hc._dil_mode(op), B, *g) if data else ops.conv4x4s2_bf16x3_dil_wrw_supported(B, *g)
+            if data:                 # the bf16 entry takes the plain mode, without ops.S2_DILATED
+                return hc.direct_dilated_bf16() and ops.conv4x4s2_bf16_dil_supported(ops.S2_FINE_TO_COARSE if op == ops.CONV_FWD else ops.S2_COARSE_TO_FINE, B, *g)
+            return hc.direct_dilated_bf16_dw() and ops.conv4x4s2_bf16_dil_wrw_supported(B, *g)
         g = hc._s2_geometry(lay)
         if g is None:
             return False
@@ -95,19 +101,26 @@ def takes(engine, kind, op, lay, bf16):
 
 @contextlib.contextmanager
 def switches(hipconv, name):
-    """Run under one setting of the in-process switches and put back what was there: "default" (fp32 arithmetic, both dilated switches
-    off), "opt_in" (`OPT_IN_MATH` with both dilated switches on), or any name of ops.DIRECT_PASSES (that arithmetic, both switches on)."""
-    was = (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw())
-    on = name != "default"
+    """Run under one setting of the in-process switches and put back what was there: "default" (fp32 arithmetic, the four dilated switches
+    off), "opt_in" (`OPT_IN_MATH` with both fp32 dilated switches on), any name of ops.DIRECT_PASSES (that arithmetic, both fp32 dilated
+    switches on) — these keep both bf16 dilated switches off — or a name of `BF16_DIL_SWITCHES` (those bf16 dilated switches on, the fp32
+    arithmetic and the fp32 pair at their defaults)."""
+    was = (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw(), hipconv.direct_dilated_bf16(), hipconv.direct_dilated_bf16_dw())
+    bf16_data, bf16_dw = BF16_DIL_SWITCHES.get(name, (False, False))
+    on = name != "default" and name not in BF16_DIL_SWITCHES
     try:
         hipconv.set_conv_math(fp32="fp32" if not on else OPT_IN_MATH if name == "opt_in" else name)
         hipconv.set_direct_dilated(on)
         hipconv.set_direct_dilated_dw(on)
+        hipconv.set_direct_dilated_bf16(bf16_data)
+        hipconv.set_direct_dilated_bf16_dw(bf16_dw)
         yield
     finally:
         hipconv.set_conv_math(fp32=was[0])
         hipconv.set_direct_dilated(was[1])
         hipconv.set_direct_dilated_dw(was[2])
+        hipconv.set_direct_dilated_bf16(was[3])
+        hipconv.set_direct_dilated_bf16_dw(was[4])
 
 
 def answers(hipconv, lay, bf16):
@@ -120,7 +133,7 @@ def answers(hipconv, lay, bf16):
 
 # ---- the corner table ------------------------------------------------------------------------------------------------------------------
 # One row = one module call: mod "conv" (nn.Conv2d) / "convT" (nn.ConvTranspose2d), cin -> cout of the MODULE, geom = (k, stride, pad, dil),
-# the input map H x W at batch B, bf16 = the input is a bf16 tensor, switches = "default" / "opt_in" (see `switches`), engines = the triple
+# the input map H x W at batch B, bf16 = the input is a bf16 tensor, switches = "default" / "opt_in" / a name of `BF16_DIL_SWITCHES` (see `switches`), engines = the triple
 # (forward, input gradient, weight gradient) the dispatcher answers.  Every row sits at its rule's minimum channel counts and holds at most
 # 16 384 pixels per image.
 class Row(namedtuple("Row", "mod cin cout geom H W B bf16 switches engines")):
@@ -228,4 +241,16 @@ ROWS = _rows(K3, False, "default", [
     ("conv", 64, 64, 64, 32, 1, "bf16x3d bf16x3d miopen"),
     ("conv", 128, 128, 48, 32, 1, "wino_dil wino_dil bf16x3w"),
     ("conv", 128, 128, 32, 64, 1, "bf16x3d bf16x3d bf16x3w"),
+]) + _rows(DIL, True, "bf16_dil", [                                  # bf16 activations, the dilated layer on the direct bf16 kernels
+    ("conv", 64, 64, 32, 64, 1, "bf16d bf16d bf16d"),                # base: MIOpen
+    ("conv", 64, 64, 64, 32, 3, "bf16d bf16d bf16d"),
+    ("conv", 256, 256, 32, 64, 1, "bf16d bf16d bf16d"),              # base: "wino_dil"
+    ("conv", 128, 130, 16, 256, 1, "bf16d miopen bf16d"),            # the input gradient refuses a produced count that is no tile multiple
+    ("conv", 256, 256, 16, 32, 1, "miopen miopen smallmap"),         # the "smallmap" grid stays
+    ("conv", 64, 64, 34, 64, 1, "miopen miopen miopen"),             # odd coarse height: the kernel refuses
+]) + _rows(DIL, True, "bf16_dil_data", [
+    ("conv", 256, 256, 64, 32, 3, "bf16d bf16d wino_dil"),
+    ("conv", 64, 64, 8, 256, 3, "bf16d bf16d miopen"),               # the 128-wide coarse grid
+]) + _rows(DIL, True, "bf16_dil_dw", [
+    ("conv", 256, 256, 32, 64, 1, "wino_dil wino_dil bf16d"),
 ])

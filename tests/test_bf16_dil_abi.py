@@ -206,7 +206,9 @@ def test_off_answers_as_before(switch):
         for op in (ops.CONV_FWD, ops.CONV_BWD_DATA):
             assert hc.engine_takes("bf16d", "data", op, lay, True) is False
         assert hc.engine_takes("bf16d", "wrw", None, lay, True) is False
-        assert hc._direct_case(lay, False) == (None, None)
+        # `_direct_case` answers from the geometry alone; what keeps the dilated entry out of reach is the entry's switch, which is off
+        assert hc._direct_case(lay) == ("dil", (C, C, H // 2, H // 2))
+        assert hc._DIRECT_TAKES_SWITCH[False, "dil", "data"] == "bf16_dil_data" and "bf16_dil_data" not in hc._direct_passes_on()
     assert "bf16d" not in [today[k] for k in today if "@" in k and "_fp32_" not in k]
 
 
@@ -227,7 +229,7 @@ def test_on_moves_the_data_passes_only(switch, monkeypatch):
         assert hc.engine_takes("bf16d", "data", ops.CONV_FWD, lay, True) and hc.engine_takes("bf16d", "data", ops.CONV_BWD_DATA, lay, True)
         assert not hc.engine_takes("bf16d", "wrw", None, lay, True)
         assert not hc.engine_takes("bf16d", "data", ops.CONV_FWD, lay, False)                # bf16 activations only
-        assert hc._direct_case(lay, False) == ("dil", (C, C, H // 2, H // 2))
+        assert hc._direct_case(lay) == ("dil", (C, C, H // 2, H // 2))
     assert not hc.engine_takes("bf16d", "data", ops.CONV_FWD, (False, B16, 512, 16, 16, 512, *DIL), True)
     # independent of the fp32 switches and of the arithmetic name
     hc.set_direct_dilated(True)
@@ -271,4 +273,4 @@ def test_flipping_the_switch_invalidates_the_memo(switch):
 def test_no_new_engine_and_no_new_opt_in_row(switch):
     assert sorted(switch._ENGINES) == sorted(["winograd", "wino_dil", "wino_s2", "thin", "thin_f2m", "thin_mfma", "smallmap", "direct", "one", "bf16d",
                                               "bf16x3d", "bf16x3w", "miopen"])
-    assert sorted(r.key for r in switch._DIRECT_OPT_INS) == sorted(["k3_data", "s2_data", "dil_data", "k3_wrw", "s2_wrw", "dil_wrw"])
+    assert sorted(r.key for r in switch._DIRECT_OPT_INS) == sorted(["k3_data", "s2_data", "dil_data", "k3_wrw", "s2_wrw", "dil_wrw", "bf16_dil_data", "bf16_dil_wrw"])

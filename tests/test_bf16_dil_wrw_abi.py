@@ -164,13 +164,16 @@ def test_off_answers_as_before(switch):
         assert today["wrw_bf16_%d@%d" % (C, H)] == eng, (C, H, today)
         lay = (False, B16, C, H, H, C, *DIL)
         assert hc.engine_takes("bf16d", "wrw", None, lay, True) is False
-        assert hc._direct_case(lay, False) == (None, None)
+        # `_direct_case` answers from the geometry alone; what keeps the dilated entry out of reach is the entry's switch, which is off
+        assert hc._direct_case(lay) == ("dil", (C, C, H // 2, H // 2))
+        assert hc._DIRECT_TAKES_SWITCH[False, "dil", "wrw"] == "bf16_dil_wrw" and "bf16_dil_wrw" not in hc._direct_passes_on()
     assert "bf16d" not in [today[k] for k in today if "@" in k and "_fp32_" not in k]
-    # only the data switch: `_direct_case` answers "dil", the weight gradient is still not taken and answers as before
+    # only the data switch: the weight gradient's own switch is still off, it is still not taken and answers as before
     hc.set_direct_dilated_bf16(True)
+    assert "bf16_dil_wrw" not in hc._direct_passes_on()
     for (C, H), eng in OFF.items():
         lay = (False, B16, C, H, H, C, *DIL)
-        assert hc._direct_case(lay, False) == ("dil", (C, C, H // 2, H // 2))
+        assert hc._direct_case(lay) == ("dil", (C, C, H // 2, H // 2))
         assert hc.engine_takes("bf16d", "wrw", None, lay, True) is False
         assert hc.engine_takes("bf16d", "data", ops.CONV_FWD, lay, True) is True
         assert hc.select_wrw(False, B16, C, H, H, C, *DIL, True) == eng
@@ -192,7 +195,7 @@ def test_on_moves_the_four_weight_gradients_only(switch, monkeypatch):
         assert hc.engine_takes("bf16d", "wrw", None, lay, True)
         assert not hc.engine_takes("bf16d", "wrw", None, lay, False)                         # bf16 activations only
         assert not hc.engine_takes("bf16d", "data", ops.CONV_FWD, lay, True) and not hc.engine_takes("bf16d", "data", ops.CONV_BWD_DATA, lay, True)
-        assert hc._direct_case(lay, False) == ("dil", (C, C, H // 2, H // 2))
+        assert hc._direct_case(lay) == ("dil", (C, C, H // 2, H // 2))
     # the coarse grid 8 wide, a transposed layer of the same numbers and netD's k4 s1 p1 are not taken
     assert not hc.engine_takes("bf16d", "wrw", None, (False, B16, 512, 16, 16, 512, *DIL), True)
     assert not hc.engine_takes("bf16d", "wrw", None, (True, B16, 128, 64, 64, 128, *DIL), True)
@@ -264,4 +267,4 @@ def test_the_engine_dispatches_on_the_geometry(switch, monkeypatch):
 def test_no_new_engine_and_no_new_opt_in_row(switch):
     assert sorted(switch._ENGINES) == sorted(["winograd", "wino_dil", "wino_s2", "thin", "thin_f2m", "thin_mfma", "smallmap", "direct", "one", "bf16d",
                                               "bf16x3d", "bf16x3w", "miopen"])
-    assert sorted(r.key for r in switch._DIRECT_OPT_INS) == sorted(["k3_data", "s2_data", "dil_data", "k3_wrw", "s2_wrw", "dil_wrw"])
+    assert sorted(r.key for r in switch._DIRECT_OPT_INS) == sorted(["k3_data", "s2_data", "dil_data", "k3_wrw", "s2_wrw", "dil_wrw", "bf16_dil_data", "bf16_dil_wrw"])

@@ -2,9 +2,10 @@
 
 The rules were measured on square maps at batch 8 / 16, and several bound H alone, or H * W alone, and channel counts from below only: they
 hand the engines elongated maps, one-row and one-column maps and other batches.  The checks:
-  * every answer of the sweep is the recorded one (digests per block, tests/golden/dispatch_envelope_digests.json);
+  * every answer of the sweep is the recorded one (digests per block, tests/golden/dispatch_envelope_digests.json); the two dilated switches
+    for bf16 activations move no block of fp32 activations, of IPSR_BF16_ENGINES=all or of another geometry;
   * `hipconv.engine_takes`, what the rules and the final guard ask, equals the independent restatement `dispatch_envelope.takes`; an engine
-    whose record refuses is never answered; the three kinds of direct opt-in switch build one set;
+    whose record refuses is never answered; the direct opt-in switches (the arithmetic name and the four dilated booleans) build one set;
   * no answer of `select` / `select_wrw` over a grid with H != W is one the chosen engine's own support query refuses (such a layer would
     raise NotImplementedError in `conv_nobias` although torch computes it);
   * every row of tests/dispatch_envelope.py's corner table still reaches the engines it names (tests/test_gpu_dispatch_envelope.py runs
@@ -36,7 +37,13 @@ SETTINGS = [("default", {}, "default", (False, True), CHANNELS_DEFAULT),
             ("direct_bf16x3_s2", {}, "direct_bf16x3_s2", (False,), CHANNELS), ("direct_bf16x3_s2_dw", {}, "direct_bf16x3_s2_dw", (False,), CHANNELS),
             ("bf16_all", {"IPSR_BF16_ENGINES": "all"}, "default", (True,), CHANNELS_DEFAULT),
             ("engine_direct", {"IPSR_CONV_ENGINE": "direct"}, "default", (False, True), CHANNELS),
-            ("engine_winograd", {"IPSR_CONV_ENGINE": "winograd"}, "default", (False, True), CHANNELS)]
+            ("engine_winograd", {"IPSR_CONV_ENGINE": "winograd"}, "default", (False, True), CHANNELS),
+            # the two dilated switches for bf16 activations (de.BF16_DIL_SWITCHES): each alone and both; both under fp32 activations, which they
+            # must not move; both under IPSR_BF16_ENGINES=all, where the opt-ins stand down
+            ("bf16_dil_data", {}, "bf16_dil_data", (True,), CHANNELS), ("bf16_dil_dw", {}, "bf16_dil_dw", (True,), CHANNELS),
+            ("bf16_dil", {}, "bf16_dil", (False, True), CHANNELS),
+            ("bf16_all_dil", {"IPSR_BF16_ENGINES": "all"}, "bf16_dil", (True,), CHANNELS)]
+assert CHANNELS_DEFAULT[:len(CHANNELS)] == CHANNELS      # `Sweep.common` compares the settings over their common channel pairs, the leading ones
 _ENV_SWITCHES = ("IPSR_CONV_ENGINE", "IPSR_NO_SMALLMAP", "IPSR_NO_THIN", "IPSR_SMALLMAP_MAX_POS", "IPSR_BF16_ENGINES")
 
 
@@ -60,7 +67,7 @@ DIGEST_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golde
 DIGEST_ENGINES = ["miopen", "winograd", "wino_dil", "wino_s2", "thin", "thin_f2m", "thin_mfma", "smallmap", "direct", "one", "bf16d", "bf16x3d", "bf16x3w"]
 _DIGITS = "0123456789abcdefghijklmnopqrstuvwxyz"
 
-Sweep = namedtuple("Sweep", "refused seen blocks disagree")
+Sweep = namedtuple("Sweep", "refused seen blocks disagree common")
 
 
 def _block_key(setting, bf16, B, geom):
@@ -75,14 +82,16 @@ def swept(built):
       seen      {(engine, kind): count} of every answer other than "miopen"
       blocks    {block key: (SHA-256 of the block's answers, their count)}, see `DIGEST_FIXTURE`
       disagree  the answers on which `hipconv.engine_takes` and `de.takes` differ, as `refused` (None under a hipconv.py from before the engine
-                records had `takes`: the digests can be checked against such a file, nothing else here can)"""
+                records had `takes`: the digests can be checked against such a file, nothing else here can)
+      common    {block key: SHA-256 of the block's answers over the channel pairs of `CHANNELS`}, the leading pairs of every setting: what two
+                settings swept with different channel lists are compared by"""
     from deepinpainting_amd import ops
     from deepinpainting_amd.models import hipconv
-    assert sorted(n for n, _, sw, _, _ in SETTINGS if sw != "default") == sorted(ops.DIRECT_PASSES)
+    assert sorted(n for n, _, sw, _, _ in SETTINGS if sw != "default" and sw not in de.BF16_DIL_SWITCHES) == sorted(ops.DIRECT_PASSES)
     code = {e: _DIGITS[i] for i, e in enumerate(DIGEST_ENGINES)}
     engine_takes = getattr(hipconv, "engine_takes", None)
     mp = pytest.MonkeyPatch()
-    refused, seen, points, blocks, disagree = [], {}, 0, {}, None if engine_takes is None else []
+    refused, seen, points, blocks, disagree, common = [], {}, 0, {}, None if engine_takes is None else [], {}
     try:
         mp.setattr(hipconv, "_FORCE", None)
         for name, env, sw, dtypes, channels in SETTINGS:
@@ -95,8 +104,10 @@ def swept(built):
                 for bf16 in dtypes:
                     for B in BATCHES:
                         for geom in GEOMS:
-                            chars = []
-                            for Cin, Cout in channels:
+                            key, chars = _block_key(name, bf16, B, geom), []
+                            for n, (Cin, Cout) in enumerate(channels):
+                                if n == len(CHANNELS):
+                                    common[key] = hashlib.sha256("".join(chars).encode("ascii")).hexdigest()
                                 for H in EXTENTS:
                                     for W in EXTENTS:
                                         for transposed in (False, True):
@@ -114,13 +125,14 @@ def swept(built):
                                                     refused.append((name, eng, kind, op, lay, bf16))
                                                 if engine_takes is not None and engine_takes(eng, kind, op, lay, bf16) != took:
                                                     disagree.append((name, eng, kind, op, lay, bf16))
-                            blocks[_block_key(name, bf16, B, geom)] = (hashlib.sha256("".join(chars).encode("ascii")).hexdigest(), len(chars))
+                            blocks[key] = (hashlib.sha256("".join(chars).encode("ascii")).hexdigest(), len(chars))
+                            common.setdefault(key, blocks[key][0])
                     hipconv._SEL.clear()             # the memo of a finished dtype is dead weight
     finally:
         mp.undo()
         hipconv.reload_env()
     print("dispatcher sweep: %d answers, %d on a HIP engine, %d refused" % (points, sum(seen.values()), len(refused)))
-    return Sweep(refused, seen, blocks, disagree)
+    return Sweep(refused, seen, blocks, disagree, common)
 
 
 @pytest.fixture(scope="module")
@@ -149,6 +161,24 @@ def test_sweep_answers_match_the_recorded_digests(swept):
     assert not moved, "%d of %d blocks moved (block: recorded count -> now): %s" % (
         len(moved), len(want), ", ".join("%s: %d -> %d" % (k, want[k][1], swept.blocks[k][1]) for k in moved))
     assert sum(n for _, n in want.values()) > 1000000 and len(want) >= 300
+
+
+def test_bf16_dilated_switches_move_nothing_else(swept):
+    """What the two dilated switches for bf16 activations must leave alone, block against block over the channel pairs of `CHANNELS`: fp32
+    activations (both on: the "default" answers); IPSR_BF16_ENGINES=all (both on: the "bf16_all" answers, the opt-ins stand down under any
+    value of that variable); and, under each of the three switch names, every geometry but the dilated one (the "default" answers)."""
+    moved = []
+    for B in BATCHES:
+        for geom in GEOMS:
+            same = [(("bf16_dil", False), ("default", False)), (("bf16_all_dil", True), ("bf16_all", True))]
+            same += [((name, True), ("default", True)) for name in de.BF16_DIL_SWITCHES if geom != de.DIL]
+            for (a, a16), (b, b16) in same:
+                ka, kb = _block_key(a, a16, B, geom), _block_key(b, b16, B, geom)
+                if swept.common[ka] != swept.common[kb]:
+                    moved.append((ka, kb))
+    assert not moved, moved
+    # ... and the dilated blocks do move under each name, or the comparison above compares nothing
+    assert all(swept.common[_block_key(name, True, 8, de.DIL)] != swept.common[_block_key("default", True, 8, de.DIL)] for name in de.BF16_DIL_SWITCHES)
 
 
 def test_engine_takes_is_the_independent_restatement(swept, hipconv):
@@ -232,31 +262,36 @@ def test_an_engine_that_refuses_is_never_answered(hipconv):
 
 
 def test_direct_switches_build_one_set(hipconv):
-    """`_direct_passes_on` over the 2 x 2 x 5 settings of the two dilated booleans and the fp32 arithmetic: the passes of ops.DIRECT_PASSES
-    for the name plus "dil_data" / "dil_wrw" for the booleans, and the public getters read the same set.  The direct names stay refused for
+    """`_direct_passes_on` over the 2^4 x 5 settings of the four dilated booleans and the fp32 arithmetic: the passes of ops.DIRECT_PASSES
+    for the name plus one key per boolean that is on, and the four public getters read the same set.  The direct names stay refused for
     bf16 activations."""
     from deepinpainting_amd import ops
-    was = (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw())
+    setters = {"dil_data": hipconv.set_direct_dilated, "dil_wrw": hipconv.set_direct_dilated_dw,
+               "bf16_dil_data": hipconv.set_direct_dilated_bf16, "bf16_dil_wrw": hipconv.set_direct_dilated_bf16_dw}
+    getters = {"dil_data": hipconv.direct_dilated, "dil_wrw": hipconv.direct_dilated_dw,
+               "bf16_dil_data": hipconv.direct_dilated_bf16, "bf16_dil_wrw": hipconv.direct_dilated_bf16_dw}
+    was = (hipconv._MATH["fp32"], {key: get() for key, get in getters.items()})
     try:
         for math in ["fp32"] + sorted(ops.DIRECT_PASSES):
-            for dil in (False, True):
-                for dil_dw in (False, True):
-                    hipconv.set_conv_math(fp32=math)
-                    hipconv.set_direct_dilated(dil)
-                    hipconv.set_direct_dilated_dw(dil_dw)
-                    want = set(ops.DIRECT_PASSES.get(math, ())) | ({"dil_data"} if dil else set()) | ({"dil_wrw"} if dil_dw else set())
-                    assert set(hipconv._direct_passes_on()) == want, (math, dil, dil_dw)
-                    assert (hipconv._MATH["fp32"], hipconv.direct_dilated(), hipconv.direct_dilated_dw()) == (math, dil, dil_dw)
-                    assert all(ops.direct_moves(math, key) == (key in want) for key in ("k3_data", "k3_wrw", "s2_data", "s2_wrw"))
-        assert set(r.key for r in hipconv._DIRECT_OPT_INS) == set().union(*ops.DIRECT_PASSES.values()) | {"dil_data", "dil_wrw"}
+            for bits in range(16):
+                on = {key: bool(bits >> i & 1) for i, key in enumerate(setters)}
+                hipconv.set_conv_math(fp32=math)
+                for key, val in on.items():
+                    setters[key](val)
+                want = set(ops.DIRECT_PASSES.get(math, ())) | set(key for key, val in on.items() if val)
+                assert set(hipconv._direct_passes_on()) == want, (math, on)
+                assert (hipconv._MATH["fp32"], {key: get() for key, get in getters.items()}) == (math, on)
+                assert all(get() is on[key] for key, get in getters.items())
+                assert all(ops.direct_moves(math, key) == (key in want) for key in ("k3_data", "k3_wrw", "s2_data", "s2_wrw"))
+        assert set(r.key for r in hipconv._DIRECT_OPT_INS) == set().union(*ops.DIRECT_PASSES.values()) | set(setters)
         for name in ops.DIRECT_PASSES:
             with pytest.raises(ValueError):
                 hipconv.set_conv_math(bf16=name)
         assert hipconv._MATH["bf16"] not in ops.DIRECT_PASSES
     finally:
         hipconv.set_conv_math(fp32=was[0])
-        hipconv.set_direct_dilated(was[1])
-        hipconv.set_direct_dilated_dw(was[2])
+        for key, val in was[1].items():
+            setters[key](val)
 
 
 # (engine, kind) whose rule admits one orientation only, and why

@@ -623,7 +623,7 @@ def test_split_bf16_winograd_arithmetic_all_families(math, io_bf16):
 # What each engine does to an fp32 operand on a call with a bf16 side (the reference is an fp32 MIOpen convolution of exactly what the
 # kernel multiplied; on an all-fp32 call nothing is rounded anywhere):
 #   engine      weights                                                          fp32 activation operand
-#   bf16d       rounded: csrc/conv_bf16.hip (cb_pack_weights_kernel, (__bf16)v;  rounded: models/hipconv.py `_bf16d_data` (.to(bf16)
+#   bf16d       rounded: csrc/conv_bf16.hip (cb_pack_weights_kernel, (__bf16)v;  rounded: models/hipconv.py `_direct_data` (.to(bf16)
 #               the k4 s2 p1 form packs through the same kernel)                  before the kernel; `_HipConv.backward` casts dy)
 #   thin_f2m    rounded: csrc/thin_conv.hip:470 (f2bf(w))                         rounded: the window gather feeds v_mfma_*_bf16
 #   thin        rounded: csrc/thin_conv.hip:47 / :98 (thin_rb when a side is bf16) rounded: csrc/thin_conv.hip:64 / :126
