@@ -27,6 +27,8 @@ void profile_mark_stop(hipStream_t st, int region = 0, double work = 0.0, double
 //   5  smallmap.hip: the tiled flag of `op` (IPSR_SMALLMAP_TILED) is ignored: such calls run the streaming kernels
 //   6  smallmap.hip: > 0 = the number of splits of the tiled regime's reduction (the plan's own choice otherwise); set it before the
 //      workspace query, which follows it
+//   7  winograd.hip / wino_fused.hip: the one-launch F(4x4,3x3) kernel for <= 64 produced channels: 0 = the size rule decides,
+//      1 = never (every call on three launches), 2 = wherever the kernel's envelope allows (fp32, K <= 64, C % 16 == 0), whatever the size
 int debug_option(int key);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -182,6 +184,11 @@ int launch_corr_argmax_bf16(const float* xn, const float* ref, int B, int C, int
 bool corr_R_bf16_supported(int C);
 size_t corr_R_bf16_ws_bytes(int B, int C, int N);
 int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, float* R, void* ws, size_t ws_bytes, hipStream_t st);
+
+// wino_fused.hip — the one-launch F(4x4,3x3) data pass; launch_winograd asks wino_fused_admits, then hands over the transformed
+// filter U[36][C][64]
+bool wino_fused_admits(int math, bool in_bf16, bool out_bf16, int B, int C, int K, int H, int W);
+int launch_wino_fused(const float* x, const float* U, const float* bias, float* y, int B, int C, int K, int H, int W, int epilogue, hipStream_t st);
 
 // conv_gemm.hip — implicit-GEMM convolutions on the fp32 matrix cores (see the file header)
 size_t conv_gemm_ws_bytes(int transposed, int B, int Cred, int M, int Hin, int Win, int Hout, int Wout, int k, int stride, int pad, int dil);

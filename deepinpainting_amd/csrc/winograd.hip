@@ -28,12 +28,15 @@
 //   wino_output_kernel   y[b][k][4ty+i][4tx+j] = (A^T M A)[i][j]
 // HBM traffic is 2.25x the activations each way (36 numbers per 16 pixels) — worth it from 128 channels up, where the
 // 4x smaller GEMM dominates; below that the direct kernels / MIOpen stay in charge (the Python dispatcher decides per shape).
+// Fused, ONE launch (wino_fused.hip; launch_winograd asks wino_fused_admits): fp32 data passes that produce at most 64 channels on
+// large maps, where that round trip was two thirds of the time; V and M stay in the CU, U is the WinoFilter<0> output as above.
 //
 // Numerics: the standard interpolation points (0, +-1, +-2, inf); fp32 error ~4e-6 of the output scale at 512 channels
 // (tests/test_gpu_conv.py measures it per shape against an fp64 convolution).
 #include <type_traits>
 
 #include "ipsr_common.h"
+#include "wino_transforms.h"
 
 namespace ipsr {
 
@@ -81,16 +84,7 @@ __device__ __forceinline__ void wino_load_sum(const float* __restrict__ M, const
     }
 }
 
-// ---- 1-D transforms --------------------------------------------------------------------------------
-__device__ __forceinline__ void wino_bt(const float d[6], float v[6])        // B^T d
-{
-    v[0] = 4.0f * d[0] - 5.0f * d[2] + d[4];
-    v[1] = -4.0f * d[1] - 4.0f * d[2] + d[3] + d[4];
-    v[2] = 4.0f * d[1] - 4.0f * d[2] - d[3] + d[4];
-    v[3] = -2.0f * d[1] - d[2] + 2.0f * d[3] + d[4];
-    v[4] = 2.0f * d[1] - d[2] - 2.0f * d[3] + d[4];
-    v[5] = 4.0f * d[1] - 5.0f * d[3] + d[5];
-}
+// ---- 1-D transforms (wino_bt = B^T d and wino_at = A^T m: wino_transforms.h, shared with wino_fused.hip) ---------------------
 __device__ __forceinline__ void wino_g(const float g[3], float u[6])         // G g
 {
     u[0] = 0.25f * g[0];
@@ -99,13 +93,6 @@ __device__ __forceinline__ void wino_g(const float g[3], float u[6])         // 
     u[3] = (1.0f / 24.0f) * g[0] + (1.0f / 12.0f) * g[1] + (1.0f / 6.0f) * g[2];
     u[4] = (1.0f / 24.0f) * g[0] - (1.0f / 12.0f) * g[1] + (1.0f / 6.0f) * g[2];
     u[5] = g[2];
-}
-__device__ __forceinline__ void wino_at(const float m[6], float y[4])        // A^T m
-{
-    y[0] = m[0] + m[1] + m[2] + m[3] + m[4];
-    y[1] = m[1] - m[2] + 2.0f * m[3] - 2.0f * m[4];
-    y[2] = m[1] + m[2] + 4.0f * m[3] + 4.0f * m[4];
-    y[3] = m[1] - m[2] + 8.0f * m[3] - 8.0f * m[4] + m[5];
 }
 
 // weight gradient, F(3x3, 4x4): dW(3x3) = A'^T [ (G' e G'^T) (.) (B^T d B) ] A'   (e = 4x4 tile of dy, d = 6x6 window of x)
@@ -1105,6 +1092,15 @@ int launch_winograd(const void* x, const float* w, void* y, int B, int C, int K,
     if (int rc = wino_launch_head("winograd", " (0 = fp32 MFMA, 2 / 3 = split bf16)", p, ar, ws, ws_bytes, &m, epilogue_ok)) return rc;
     if (u_cache) m.A = u_cache;
     const int remap = wino_remap();
+    if (wino_fused_admits(ar.math, ar.in_bf16, ar.out_bf16, B, C, K, H, W)) {
+        // one launch (wino_fused.hip): the windows and the products stay in the CU; only the filter transform runs ahead of it, and
+        // only when the cache does not hold it.  Not a launch of the GEMM kernel: nothing is recorded in profiling region 3.
+        if (!(u_cache && u_valid)) {
+            wino_one_kernel<WinoFilter<0>><<<op_grid(false, 0, p.rows, C), 256, 0, st>>>(WinoFilter<0>{w, C, K, p.rows, sc, sm, flip, m.A}, 0);
+            if (int rc = check_launch("wino_one_kernel<WinoFilter>")) return rc;
+        }
+        return launch_wino_fused(static_cast<const float*>(x), m.A, bias, static_cast<float*>(y), B, C, K, H, W, epilogue, st);
+    }
     with_mode(ar.math, [&](auto M) {
         constexpr int MODE = decltype(M)::value;
         with_type(ar.in_bf16, [&](auto* tag) {
