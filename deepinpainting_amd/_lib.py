@@ -132,6 +132,7 @@ SIGNATURES = {
     "ipsr_wino_gemm_split": (c_int, [c_int, c_int, c_int, c_void_p]),
     "ipsr_debug_force_wino_split": (c_int, [c_int, c_int, c_int]),
     "ipsr_debug_set_option": (c_int, [c_int, c_int]),
+    "ipsr_window_corr_plan": (c_int, [c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

@@ -641,6 +641,18 @@ int launch_window_corr_argmax(const float* R, const float* inv, int B, int h, in
     int32_t* pidx = p.pidx(ws);
     float* mval = p.extra<float>(ws, 0);
     int32_t* midx = p.extra<int32_t>(ws, 1);
+    // the LDS-tiled stencil (window_stencil.hip) where its plan admits the shape: the same partials in the same slice, over its own
+    // (never more) ranges of window rows; with one range they ARE the merged values
+    const WindowStencilPlan sp = window_stencil_plan(B, h, w, patch, p.ksplit);
+    if (sp.lds_tiled) {
+        if (sp.split == 1) {
+            if (int rc = launch_window_stencil(sp, R, inv, B, h, w, patch, mval, midx, st)) return rc;
+        } else {
+            if (int rc = launch_window_stencil(sp, R, inv, B, h, w, patch, pval, pidx, st)) return rc;
+            if (int rc = finish_argmax(pval, pidx, B, Np, sp.split, midx, mval, st, nullptr)) return rc;
+        }
+        return finish_argmax(mval, midx, B, Np, 1, nullptr, nullptr, st, partials);
+    }
     window_corr_argmax_kernel<<<dim3(cdiv(Np, 256), p.ksplit, B), 256, 0, st>>>(R, inv, h * w, w, nW, Np, patch, p.ksplit, p.kper, pval, pidx);
     if (int rc = check_launch("window_corr_argmax_kernel")) return rc;
     // fold the k-splits here, once: the stage kernel's consumers (one merge per 32x32 gather tile over K = C*p*p channels)
@@ -770,6 +782,22 @@ int launch_corr_R_bf16(const float* x, const float* ref, int B, int C, int N, fl
 }
 
 }  // namespace ipsr
+
+// What launch_window_corr_argmax would run (host only; the plan function is the launcher's)
+extern "C" int ipsr_window_corr_plan(int B, int h, int w, int patch, int* out)
+{
+    using namespace ipsr;
+    if (!out || B < 1 || patch < 1 || h < patch || w < patch)
+        return fail(IPSR_ERR_INVALID, "ipsr_window_corr_plan: bad argument B=%d h=%d w=%d shift_sz=%d out=%p", B, h, w, patch, (void*)out);
+    const int nW = w - patch + 1, Np = (h - patch + 1) * nW;
+    const WindowPlan p = window_plan(B, Np);
+    const WindowStencilPlan sp = window_stencil_plan(B, h, w, patch, p.ksplit);
+    out[0] = sp.lds_tiled ? 1 : 0;
+    out[1] = sp.lds_tiled ? sp.workgroups : cdiv(Np, 256) * p.ksplit * B;
+    out[2] = sp.lds_tiled ? sp.split : p.ksplit;
+    out[3] = sp.lds_tiled ? sp.lds_bytes : 0;
+    return IPSR_OK;
+}
 
 #ifdef IPSR_CLOCK_PROBE
 extern "C" int ipsr_debug_read_probe(unsigned long long* host, int n)

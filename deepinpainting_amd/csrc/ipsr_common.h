@@ -29,6 +29,8 @@ void profile_mark_stop(hipStream_t st, int region = 0, double work = 0.0, double
 //      workspace query, which follows it
 //   7  winograd.hip / wino_fused.hip: the one-launch F(4x4,3x3) kernel for <= 64 produced channels: 0 = the size rule decides,
 //      1 = never (every call on three launches), 2 = wherever the kernel's envelope allows (fp32, K <= 64, C % 16 == 0), whatever the size
+//   8  corr_argmax.hip / window_stencil.hip: the LDS-tiled window stencil of shift_sz > 1: 0 = the size rule decides, 1 = never (the
+//      streaming kernel in every call), 2 = wherever the kernel's envelope allows (patch >= 2, p*w*w + w floats within 160 KB of LDS)
 int debug_option(int key);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -165,6 +167,18 @@ int launch_window_prepare(const float* x, int B, int C, int h, int w, int patch,
 size_t window_corr_ws_bytes(int B, int Np);
 int launch_window_corr_argmax(const float* R, const float* inv, int B, int h, int w, int patch, void* ws, size_t ws_bytes, hipStream_t st,
                               CorrPartials* partials);
+// window_stencil.hip — the same partials by the LDS-tiled kernel.  launch_window_corr_argmax asks window_stencil_plan (`slices` =
+// what its own plan sized the partials for) and runs the streaming kernel where the answer is not lds_tiled
+struct WindowStencilPlan {
+    bool lds_tiled;        // false: the streaming kernel (the other fields are 0)
+    int workgroups;        // B * nH * split
+    int split, kper;       // ranges of window rows ky, rows per range
+    int nbuf;              // LDS buffers: 2 = the next ky's blocks are prefetched
+    int lds_bytes;         // dynamic LDS of a workgroup
+};
+WindowStencilPlan window_stencil_plan(int B, int h, int w, int patch, int slices);
+int launch_window_stencil(const WindowStencilPlan& p, const float* R, const float* inv, int B, int h, int w, int patch, float* pval, int32_t* pidx,
+                          hipStream_t st);
 size_t corr_argmax_ws_bytes(int B, int C, int N);
 // xn, ref: [B][C][N], rows N apart.  S_out != NULL: every correlation is stored as well ([B][N][N]).
 // partials != NULL: skip the merge kernel and hand the k-split partials to the caller (ind/vmax are then written by the

@@ -4,6 +4,7 @@ torch is used here for device memory and streams only; every computation is a HI
 libipsr_hip.so.  All functions require CUDA(HIP) tensors and raise otherwise — no fallback.
 """
 import contextlib
+import ctypes
 import threading
 import weakref
 from collections import namedtuple
@@ -212,6 +213,14 @@ def forward(x, ref, mask_point_idx_i32, patch=1, stride=1, want_attn=False, want
     if want_attn and attn is None:
         attn = _empty((B, 0, N), dtype=torch.float32, device=dev)
     return Forward(out, ind, vmax, attn, bidx)
+
+
+def window_corr_plan(B, h, w, patch):
+    """How the window arg-max of a shift_sz = `patch` forward would run (ipsr_window_corr_plan; host only, follows
+    ipsr_debug_set_option(8, v)) -> {"variant": 0 streaming / 1 LDS-tiled, "workgroups", "split", "lds_bytes"}."""
+    out = (ctypes.c_int * 4)()
+    _lib.check(_lib.lib().ipsr_window_corr_plan(int(B), int(h), int(w), int(patch), ctypes.cast(out, ctypes.c_void_p)), "ipsr_window_corr_plan")
+    return {"variant": out[0], "workgroups": out[1], "split": out[2], "lds_bytes": out[3]}
 
 
 def backward(grad_out, bwd_index, triple_w, M, patch=1):

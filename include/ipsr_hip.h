@@ -606,6 +606,16 @@ int ipsr_debug_force_wino_split(int nsplit, int xi_split, int nsplit_tail);
  * override above: process-global, off by default, never set by the product path. */
 int ipsr_debug_set_option(int key, int value);
 
+/* How the window arg-max of shift_sz > 1 (the p x p stencil over the 1x1 correlation R + arg-max, inside ipsr_forward,
+ * ipsr_forward_masks and ipsr_forward_bf16corr) would run for B maps of h x w and shift_sz = patch.  Host only, launches nothing;
+ * the same plan function as the launcher, so it follows ipsr_debug_set_option(8, v) (0 = the size rule, 1 = never LDS-tiled,
+ * 2 = LDS-tiled wherever the envelope allows: patch >= 2 and patch*w*w + w floats within a workgroup's 160 KB of LDS).
+ * out4 = {variant (0 = streaming kernel, 1 = LDS-tiled kernel of csrc/window_stencil.hip), workgroups, ranges the patch index k'
+ * is split into (their partials are merged by a second launch unless there is one), dynamic LDS bytes per workgroup}.
+ * The workspace of the forward entries does not depend on the variant.  IPSR_ERR_INVALID for B < 1, patch < 1, h < patch,
+ * w < patch or a null out4. */
+int ipsr_window_corr_plan(int B, int h, int w, int patch, int* out4 /*[host]*/);
+
 #ifdef __cplusplus
 }
 #endif
