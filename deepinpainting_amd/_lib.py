@@ -97,6 +97,8 @@ SIGNATURES = {
     "ipsr_l1_pair_loss_workspace_bytes": (c_size_t, [c_int]),
     "ipsr_l1_pair_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ipsr_loss_grad_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "ipsr_image_quality_workspace_bytes": (c_size_t, [c_int] * 5),
+    "ipsr_image_quality": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ipsr_profile_enable": (c_int, [c_int]),
     "ipsr_profile_enable_mask": (c_int, [c_int, ctypes.c_uint]),
     "ipsr_profile_read": (c_int, [c_void_p, c_int]),

@@ -1242,3 +1242,51 @@ def loss_grad_scale(grad_loss, g1, g2=None):
                                                g2.data_ptr() if g2 is not None else None, o2.data_ptr() if o2 is not None else None,
                                                g2.numel() if g2 is not None else 0, _stream()), "ipsr_loss_grad_scale")
     return o1, o2
+
+
+# ---- image quality (csrc/image_quality.hip): per-image SSIM, mean (x - y)^2 and mean |x - y| of a batch
+IQ_SSIM = 1                     # IPSR_IQ_SSIM of include/ipsr_hip.h
+_iq_windows = {}
+
+
+def ssim_window():
+    """The 11x11 SSIM window of DESIGN.md "Image quality": Gaussian of sigma 1.5 over mgrid[-5:6, -5:6], normalised, rounded to
+    float32 -> numpy float32 [11,11]."""
+    import numpy as np
+    x, y = np.mgrid[-5:6, -5:6]
+    g = np.exp(-(x ** 2 + y ** 2) / (2.0 * 1.5 ** 2))
+    return (g / g.sum()).astype(np.float32)
+
+
+def _iq_window(device):
+    """The window widened to float64 on `device` (121 doubles, made once per device)."""
+    w = _iq_windows.get(device.index)
+    if w is None:
+        w = torch.from_numpy(ssim_window().astype("float64").reshape(-1)).to(device)
+        _iq_windows[device.index] = w
+    return w
+
+
+def image_quality(x, y, ssim=True):
+    """x, y [B,C,H,W] (fp32; bf16 / fp16 are taken with .float()) -> float64 [B,3] on the device: per image the mean SSIM map, the
+    mean (x - y)^2 and the mean |x - y|.  ssim=False: column 0 is NaN (not computed), columns 1-2 are the same bits, any H, W >= 1.
+    No host synchronisation; runs on the current stream."""
+    if torch.is_tensor(x) and x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    if torch.is_tensor(y) and y.dtype in (torch.bfloat16, torch.float16):
+        y = y.float()
+    x, y = _req(x, torch.float32, "x"), _req(y, torch.float32, "y")
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError("image_quality: x %s and y %s must be two [B,C,H,W] tensors of one shape" % (tuple(x.shape), tuple(y.shape)))
+    B, C, H, W = x.shape
+    flags = IQ_SSIM if ssim else 0
+    L = _lib.lib()
+    nbytes = L.ipsr_image_quality_workspace_bytes(B, C, H, W, flags)
+    if nbytes == 0:                                     # refused shape: the entry itself says why, before any launch
+        _lib.check(L.ipsr_image_quality(x.data_ptr(), y.data_ptr(), B, C, H, W, flags, None, None, None, 0, _stream()), "ipsr_image_quality")
+    win = _iq_window(x.device) if ssim else None
+    out = _empty((B, 3), dtype=torch.float64, device=x.device)
+    ws = _workspace(nbytes, x.device)
+    _lib.check(L.ipsr_image_quality(x.data_ptr(), y.data_ptr(), B, C, H, W, flags, win.data_ptr() if ssim else None, out.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream()), "ipsr_image_quality")
+    return out

@@ -427,6 +427,24 @@ int ipsr_l1_pair_loss(const float* a1, const float* a2, const float* t, int n, f
 int ipsr_loss_grad_scale(const float* gscale /*[1]*/, const float* g1, float* out1, int n1, const float* g2, float* out2, int n2,
                          void* stream);
 
+/* ---- image quality: the evaluation path (csrc/image_quality.hip) -------------------------------------
+ * What test.ipynb cell 3 asks of `IQA_pytorch.SSIM(channels=3)(real_B, fake_B, as_loss=False)` and `torch.mean((real_B - fake_B)**2)`,
+ * and train.ipynb's validation loop of the mean absolute difference, for a whole batch:
+ *     x, y [B,C,H,W] fp32 NCHW  ->  out [B][3] float64 = { mean SSIM map, mean (x - y)^2, mean |x - y| } per image.
+ * SSIM: 11x11 window `window121` (121 doubles ON THE DEVICE, row-major: the float32 Gaussian of sigma 1.5 widened to double),
+ * depthwise, stride 1, no padding, C1 = 0.01^2, C2 = 0.03^2, cs clamped at 0, values as they are (no rescaling) — DESIGN.md
+ * "Image quality".  Every product and sum in fp64, fixed order, no atomics: the same bits call after call, and image b's row depends
+ * on image b alone.  flags: bit IPSR_IQ_SSIM asks for column 0; without it column 0 is a quiet NaN, columns 1-2 are bit-identical
+ * to a call with it, `window121` may be NULL and any H, W >= 1 is taken.  Two launches (workgroup partials, then one fold per image);
+ * the workspace (8-byte aligned) holds the partials.  Checked before the first launch, so that a refused call writes nothing: null
+ * pointers, B, C, H, W < 1, unknown flag bits -> IPSR_ERR_INVALID; H or W < 11 with IPSR_IQ_SSIM, more than 2^31 - 1 workgroups
+ * per image or B > 65535 -> IPSR_ERR_UNSUPPORTED (the query returns 0, reason in ipsr_last_error); short workspace ->
+ * IPSR_ERR_WORKSPACE.  Added without an ABI version change (15). */
+#define IPSR_IQ_SSIM 1
+size_t ipsr_image_quality_workspace_bytes(int B, int C, int H, int W, int flags);
+int ipsr_image_quality(const float* x, const float* y, int B, int C, int H, int W, int flags, const double* window121 /*[121]*/,
+                       double* out /*[B][3]*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement hook (bench.py) -----------------------------------------------------------------
  * Opt-in: when enabled, three kinds of regions are bracketed by a pair of HIP events recorded on the SAME stream the
  * work is launched on:
