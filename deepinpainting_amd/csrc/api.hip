@@ -34,6 +34,13 @@ int check_launch(const char* what)
     return IPSR_OK;
 }
 
+int raise_dynamic_lds(const void* kernel, const char* name, size_t bytes)
+{
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "%s: hipFuncSetAttribute(dynamic LDS %d): %s", name, (int)bytes, hipGetErrorString(e));
+    return IPSR_OK;
+}
+
 // ---- opt-in profiling rings ----------------------------------------------------------------------------
 // region 0: the correlation + arg-max kernel; 1: a whole ipsr_forward; 2: a whole ipsr_backward(_patch);
 // 3: every launch of the Winograd GEMM kernel (the convolutions' matrix-core kernel), with the launch's flop count;

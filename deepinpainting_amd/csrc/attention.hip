@@ -825,8 +825,8 @@ int launch_attention(const AttnArgs& a, hipStream_t st)
 #define LAUNCH_STAGE2(NCH, FULL)                                                                                     \
     do {                                                                                                             \
         if (lds > 48 * 1024)                                                                                         \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_stage_kernel<NCH, FULL>),             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
+            if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&attention_stage_kernel<NCH, FULL>),        \
+                                           "attention_stage_kernel", lds)) return rc;                                \
         attention_stage_kernel<NCH, FULL><<<grid, 256, lds, st>>>(a, nrec, nbits, ints);                                          \
     } while (0)
 #define LAUNCH_STAGE(NCH)                                                                                            \
@@ -853,8 +853,8 @@ int launch_attention(const AttnArgs& a, hipStream_t st)
     if (M > 0) {
         const size_t lds_c = compress_lds_bytes(M, Mc);
         if (lds_c > 48 * 1024) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_compress_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_compress_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
+            if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&attn_compress_kernel<true>), "attn_compress_kernel", lds_c)) return rc;
+            if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&attn_compress_kernel<false>), "attn_compress_kernel", lds_c)) return rc;
         }
         const int nthr = Mc < AC_MAXT ? ((Mc + 63) & ~63) : AC_MAXT;
         if (need_index) attn_compress_kernel<true><<<B, nthr, lds_c, st>>>(a.wn, a.wo, a.jq, a.mprime, a.rankflag, a.mpi, a.mpi_stride, a.mcount, N, M, Mc, a.ac, a.bwd_index, ints);

@@ -237,8 +237,8 @@ int launch_backward(const float* g, const int32_t* mpi, int M, const float* attn
 #define LAUNCH_BW2(RR, ST)                                                                                         \
     do {                                                                                                           \
         if (lds > 48 * 1024)                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ipsr_backward_kernel<RR, ST>),                \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
+            if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&ipsr_backward_kernel<RR, ST>),           \
+                                           "ipsr_backward_kernel", lds)) return rc;                                \
         ipsr_backward_kernel<RR, ST><<<dim3(cdiv(C, RR), B), BW_THREADS, lds, st>>>(g, bwd_index, ints, capB, triple_w, C, N, identity, bcap, gin); \
     } while (0)
 #define LAUNCH_BW(RR)                                                                                              \

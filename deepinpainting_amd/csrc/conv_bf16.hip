@@ -469,15 +469,6 @@ __global__ void __launch_bounds__(256) cb_split_reduce_kernel(const float* __res
     st4(out, i, a);
 }
 
-// Every kernel of this file may ask for up to CB_LDS_MAX of dynamic LDS.  The attribute belongs to the device the launch goes to: set per
-// launch, not once per process.
-static int cb_raise_lds(const void* kernel, const char* name)
-{
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CB_LDS_MAX);
-    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "%s: hipFuncSetAttribute(dynamic LDS %d): %s", name, CB_LDS_MAX, hipGetErrorString(e));
-    return IPSR_OK;
-}
-
 // Where a data-pass kernel writes: `out`, or under a reduction cut the runs' fp32 partials behind the `pack_bytes` of packed weights at Wp
 static void* cb_run_dst(int nsplit, uint4* Wp, size_t pack_bytes, void* out)
 {
@@ -1041,7 +1032,7 @@ static size_t data_ws_query(int kind, int form, int B, int C, int K, int Hl, int
 template <int MODE, int KT, int P, typename TOUT>
 static int cb_launch_kernel(const CbGeom& g, const void* in, const uint4* Wp, const uint4* zero_page, void* out, unsigned grid, size_t smem, hipStream_t st)
 {
-    if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), "conv_bf16_kernel")) return rc;
+    if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KT, P, TOUT>), "conv_bf16_kernel", CB_LDS_MAX)) return rc;
     conv_bf16_kernel<MODE, KT, P, TOUT><<<grid, CB_THREADS, smem, st>>>(static_cast<const unsigned short*>(in), Wp, zero_page, g, static_cast<TOUT*>(out));
     return IPSR_OK;
 }
@@ -1085,12 +1076,12 @@ static int launch_data(const void* in, const float* w, void* out, int B, int C, 
         if (int rc = (out_bf16 && g.nsplit == 1) ? cb_launch_tile<FORM, bf16_t>(g, in, Wp, zero_page, dst, grid, smem, st)
                                                  : cb_launch_tile<FORM, float>(g, in, Wp, zero_page, dst, grid, smem, st)) return rc;
     } else if constexpr (KIND == DATA_K3_SPLIT) {
-        if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel), k.kernel)) return rc;
+        if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_kernel), k.kernel, CB_LDS_MAX)) return rc;
         CxGeom x{B, C, K, Hl, Wl, g.wshift, g.R, g.NR, g.PW, g.NPOS, g.ktiles, g.ptiles, g.nstage, g.nsplit, g.sps, g.t_bytes, {}};
         for (int t = 0; t < 9; ++t) x.tapoff[t] = g.tapoff[0][t];
         conv_bf16x3_kernel<<<grid, CB_THREADS, smem, st>>>(static_cast<const float*>(in), Wp, lo_plane, x, static_cast<float*>(dst));
     } else {
-        if (int rc = cb_raise_lds(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<FORM>), k.kernel)) return rc;
+        if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&conv_bf16x3_s2_kernel<FORM>), k.kernel, CB_LDS_MAX)) return rc;
         conv_bf16x3_s2_kernel<FORM><<<grid, CB_THREADS, smem, st>>>(static_cast<const float*>(in), Wp, lo_plane, g, static_cast<float*>(dst));
     }
     const double outs = f.coarse ? (double)B * Hl * Wl : (double)B * g.Hout * g.Wout;
@@ -2283,7 +2274,7 @@ static int launch_wrw(const void* a, const void* w, float* dW, int B, int K, int
         static_assert(KIND == WRW_DIL, "one branch per row of WRW_KINDS");
         kernel = W == 128 ? reinterpret_cast<const void*>(&conv_bf16_wrw_dil_kernel<true>) : reinterpret_cast<const void*>(&conv_bf16_wrw_dil_kernel<false>);
     }
-    if (int rc = cb_raise_lds(kernel, k.kernel)) return rc;
+    if (int rc = raise_dynamic_lds(kernel, k.kernel, CB_LDS_MAX)) return rc;
     profile_mark_start(st, 4);
     if constexpr (KIND == WRW_3X3)
         conv_bf16_wrw_kernel<<<grid, WB_THREADS, smem, st>>>(static_cast<const unsigned short*>(a), static_cast<const unsigned short*>(w), zero_page, g, slabs);

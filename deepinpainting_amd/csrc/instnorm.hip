@@ -343,15 +343,20 @@ __global__ void __launch_bounds__(256) bias_act_bwd_kernel(const IO* __restrict_
 constexpr int IN_MAX_HW = 65536;       // 256 x 256: the outermost norm of netG (planes above 16384 must be vector aligned)
 constexpr int IN_MAX_HW_REG = 16384;   // largest plane a 256-thread workgroup holds in registers
 
-// Launch shape: wave-sized workgroups for small planes, 256 threads above; a thread holds at most 64 elements.
-#define IN_DISPATCH(KERNEL, IO, ...)                                                                                    \
-    do {                                                                                                                \
-        const bool vec = (HW & 3) == 0;                                                                                 \
-        if (HW <= 256) { if (vec) KERNEL<IO, 64, 4, true><<<planes, 64, 0, st>>>(__VA_ARGS__); else KERNEL<IO, 64, 4, false><<<planes, 64, 0, st>>>(__VA_ARGS__); }          \
-        else if (HW <= 1024) { if (vec) KERNEL<IO, 64, 16, true><<<planes, 64, 0, st>>>(__VA_ARGS__); else KERNEL<IO, 64, 16, false><<<planes, 64, 0, st>>>(__VA_ARGS__); }  \
-        else if (HW <= 4096) { if (vec) KERNEL<IO, 256, 16, true><<<planes, 256, 0, st>>>(__VA_ARGS__); else KERNEL<IO, 256, 16, false><<<planes, 256, 0, st>>>(__VA_ARGS__); } \
-        else { if (vec) KERNEL<IO, 256, 64, true><<<planes, 256, 0, st>>>(__VA_ARGS__); else KERNEL<IO, 256, 64, false><<<planes, 256, 0, st>>>(__VA_ARGS__); }              \
-    } while (0)
+// Launch shape: wave-sized workgroups for small planes, 256 threads above; a thread holds at most 64 elements.  Above IN_MAX_HW_REG a
+// plane takes 512 threads x 128 elements and is vector aligned (the launchers have refused the others).  f(threads, elements per thread, vec).
+template <typename F> static inline void in_dispatch(int HW, F&& f)
+{
+    auto by_vec = [&](auto T, auto NE) {
+        if ((HW & 3) == 0) f(T, NE, std::true_type{});
+        else f(T, NE, std::false_type{});
+    };
+    if (HW > IN_MAX_HW_REG) f(std::integral_constant<int, 512>{}, std::integral_constant<int, 128>{}, std::true_type{});
+    else if (HW <= 256) by_vec(std::integral_constant<int, 64>{}, std::integral_constant<int, 4>{});
+    else if (HW <= 1024) by_vec(std::integral_constant<int, 64>{}, std::integral_constant<int, 16>{});
+    else if (HW <= 4096) by_vec(std::integral_constant<int, 256>{}, std::integral_constant<int, 16>{});
+    else by_vec(std::integral_constant<int, 256>{}, std::integral_constant<int, 64>{});
+}
 
 int launch_instnorm_act_fwd(const void* x, const float* bias, const float* gamma, const float* beta, float eps, int act, float slope,
                             int B, int C, int HW, int io_bf16, void* y, float* mean, float* rstd, size_t ybs, void* y2, size_t y2bs, unsigned* tickets,
@@ -360,22 +365,16 @@ int launch_instnorm_act_fwd(const void* x, const float* bias, const float* gamma
     if (ybs == 0) ybs = (size_t)C * HW;
     if (HW > IN_MAX_HW) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_instnorm_act_forward: plane of %d elements > %d", HW, IN_MAX_HW);
     const int planes = B * C;
-    if (HW > IN_MAX_HW_REG) {
-        if (HW & 3) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_instnorm_act_forward: a plane of %d elements (> %d) must be a multiple of 4", HW, IN_MAX_HW_REG);
-        if (io_bf16)
-            instnorm_act_fwd_kernel<bf16_t, 512, 128, true><<<planes, 512, 0, st>>>(static_cast<const bf16_t*>(x), bias, gamma, beta, eps, act, slope,
-                                                                                   C, HW, static_cast<bf16_t*>(y), mean, rstd, ybs, static_cast<bf16_t*>(y2), y2bs, tickets);
-        else
-            instnorm_act_fwd_kernel<float, 512, 128, true><<<planes, 512, 0, st>>>(static_cast<const float*>(x), bias, gamma, beta, eps, act, slope,
-                                                                                  C, HW, static_cast<float*>(y), mean, rstd, ybs, static_cast<float*>(y2), y2bs, tickets);
-        return check_launch("instnorm_act_fwd_kernel");
-    }
-    if (io_bf16)
-        IN_DISPATCH(instnorm_act_fwd_kernel, bf16_t, static_cast<const bf16_t*>(x), bias, gamma, beta, eps, act, slope, C, HW,
-                    static_cast<bf16_t*>(y), mean, rstd, ybs, static_cast<bf16_t*>(y2), y2bs, tickets);
-    else
-        IN_DISPATCH(instnorm_act_fwd_kernel, float, static_cast<const float*>(x), bias, gamma, beta, eps, act, slope, C, HW,
-                    static_cast<float*>(y), mean, rstd, ybs, static_cast<float*>(y2), y2bs, tickets);
+    if (HW > IN_MAX_HW_REG && (HW & 3))
+        return fail(IPSR_ERR_UNSUPPORTED, "ipsr_instnorm_act_forward: a plane of %d elements (> %d) must be a multiple of 4", HW, IN_MAX_HW_REG);
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        in_dispatch(HW, [&](auto T, auto NE, auto VEC) {
+            constexpr int THREADS = decltype(T)::value;
+            instnorm_act_fwd_kernel<IO, THREADS, decltype(NE)::value, decltype(VEC)::value><<<planes, THREADS, 0, st>>>(
+                static_cast<const IO*>(x), bias, gamma, beta, eps, act, slope, C, HW, static_cast<IO*>(y), mean, rstd, ybs, static_cast<IO*>(y2), y2bs, tickets);
+        });
+    });
     return check_launch("instnorm_act_fwd_kernel");
 }
 
@@ -390,24 +389,18 @@ int launch_instnorm_act_bwd(const void* dy, const void* y, const void* x, const 
     if (sums && !ticket) return fail(IPSR_ERR_INVALID, "ipsr_instnorm_act_backward: batch sums need the C ticket words the forward entry point zeroed");
     if (!sums) ticket = nullptr;
     const int planes = B * C;
-    if (HW > IN_MAX_HW_REG) {
-        if (HW & 3) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_instnorm_act_backward: a plane of %d elements (> %d) must be a multiple of 4", HW, IN_MAX_HW_REG);
-        if (io_bf16)
-            instnorm_act_bwd_kernel<bf16_t, 512, 128, true, true><<<planes, 512, 0, st>>>(
-                static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y), static_cast<const bf16_t*>(x), bias, gamma, mean, rstd, act, slope, C, HW,
-                static_cast<bf16_t*>(dx), dgamma_p, dbeta_p, dbias_p, sums, ticket, dybs, ybs, static_cast<const bf16_t*>(dy2), dy2bs);
-        else
-            instnorm_act_bwd_kernel<float, 512, 128, true, true><<<planes, 512, 0, st>>>(
-                static_cast<const float*>(dy), static_cast<const float*>(y), static_cast<const float*>(x), bias, gamma, mean, rstd, act, slope, C, HW,
-                static_cast<float*>(dx), dgamma_p, dbeta_p, dbias_p, sums, ticket, dybs, ybs, static_cast<const float*>(dy2), dy2bs);
-        return check_launch("instnorm_act_bwd_kernel");
-    }
-    if (io_bf16)
-        IN_DISPATCH(instnorm_act_bwd_kernel, bf16_t, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y),
-                    static_cast<const bf16_t*>(x), bias, gamma, mean, rstd, act, slope, C, HW, static_cast<bf16_t*>(dx), dgamma_p, dbeta_p, dbias_p, sums, ticket, dybs, ybs, static_cast<const bf16_t*>(dy2), dy2bs);
-    else
-        IN_DISPATCH(instnorm_act_bwd_kernel, float, static_cast<const float*>(dy), static_cast<const float*>(y),
-                    static_cast<const float*>(x), bias, gamma, mean, rstd, act, slope, C, HW, static_cast<float*>(dx), dgamma_p, dbeta_p, dbias_p, sums, ticket, dybs, ybs, static_cast<const float*>(dy2), dy2bs);
+    if (HW > IN_MAX_HW_REG && (HW & 3))
+        return fail(IPSR_ERR_UNSUPPORTED, "ipsr_instnorm_act_backward: a plane of %d elements (> %d) must be a multiple of 4", HW, IN_MAX_HW_REG);
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        in_dispatch(HW, [&](auto T, auto NE, auto VEC) {
+            constexpr int THREADS = decltype(T)::value;
+            constexpr bool REX = THREADS == 512;              // the 512 x 128 form reads x again in its second pass
+            instnorm_act_bwd_kernel<IO, THREADS, decltype(NE)::value, decltype(VEC)::value, REX><<<planes, THREADS, 0, st>>>(
+                static_cast<const IO*>(dy), static_cast<const IO*>(y), static_cast<const IO*>(x), bias, gamma, mean, rstd, act, slope, C, HW,
+                static_cast<IO*>(dx), dgamma_p, dbeta_p, dbias_p, sums, ticket, dybs, ybs, static_cast<const IO*>(dy2), dy2bs);
+        });
+    });
     return check_launch("instnorm_act_bwd_kernel");
 }
 
@@ -417,13 +410,13 @@ int launch_bias_act_bwd(const void* dy, const void* y, int act, float slope, int
     if (sums && (!dbias_p || !ticket))
         return fail(IPSR_ERR_INVALID, "ipsr_bias_act_backward: batch sums need the partials and the C ticket words ipsr_bias_act zeroed");
     if (!sums) ticket = nullptr;
-    if (io_bf16)
-        bias_act_bwd_kernel<bf16_t><<<B * C, 256, 0, st>>>(static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y), act, slope, HW,
-                                                           static_cast<bf16_t*>(dx), dbias_p, C, sums, ticket, static_cast<const bf16_t*>(dy2), dy2bs);
-    else
-        bias_act_bwd_kernel<float><<<B * C, 256, 0, st>>>(static_cast<const float*>(dy), static_cast<const float*>(y), act, slope, HW,
-                                                          static_cast<float*>(dx), dbias_p, C, sums, ticket, static_cast<const float*>(dy2), dy2bs);
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        bias_act_bwd_kernel<IO><<<B * C, 256, 0, st>>>(static_cast<const IO*>(dy), static_cast<const IO*>(y), act, slope, HW, static_cast<IO*>(dx), dbias_p, C,
+                                                       sums, ticket, static_cast<const IO*>(dy2), dy2bs);
+    });
     return check_launch("bias_act_bwd_kernel");
 }
 
 }  // namespace ipsr
+

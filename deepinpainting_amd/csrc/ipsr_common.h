@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/ipsr_hip.h"
 
@@ -13,6 +14,9 @@ void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
 // Checks the launch that was just issued on `what`.
 int check_launch(const char* what);
+// Lets `kernel` ask for `bytes` of dynamic LDS (the default limit is 48 KB).  The attribute belongs to the device the launch goes to: callers
+// set it on every launch that needs it, never once per process.
+int raise_dynamic_lds(const void* kernel, const char* name, size_t bytes);
 
 // opt-in event bracketing of the dominant kernel (see ipsr_profile_enable in ipsr_hip.h)
 void profile_mark_start(hipStream_t st, int region = 0);
@@ -138,6 +142,21 @@ __device__ __forceinline__ void st4(bf16_t* p, size_t i4, float4 v)
     r.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
     r.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
     reinterpret_cast<uint2*>(p)[i4] = r;
+}
+
+// ---- launch dispatch: a runtime value picks the compile-time argument of a generic lambda, and the lambda writes the launch once ----
+// with_type(bf16, f): f(tag) with a null bf16_t* or float*; ELEM_T(tag) is the element type.
+template <typename F> static inline void with_type(bool bf16, F&& f)
+{
+    if (bf16) f(static_cast<bf16_t*>(nullptr));
+    else f(static_cast<float*>(nullptr));
+}
+#define ELEM_T(tag) std::remove_pointer_t<decltype(tag)>
+// with_int<3, 6>(v, f): f(std::integral_constant<int, N>{}) for the N of the list that equals v.  False, and no call, where none does:
+// the refusal stays with the caller.
+template <int... Ns, typename F> static inline bool with_int(int v, F&& f)
+{
+    return ((v == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
 }
 
 // mask_point_idx[l] as the kernels use it: the caller promises values in [0, N) (the host wrappers check what they can

@@ -189,8 +189,8 @@ int launch_patch_normalize(const float* x, int B, int C, int N, float* xn, float
 #define NORM_CASE(LL)                                                                                             \
     case LL:                                                                                                      \
         if (lds > 48 * 1024)                                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_normalize_reg_kernel<LL>),             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
+            if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&patch_normalize_reg_kernel<LL>),        \
+                                           "patch_normalize_reg_kernel", lds)) return rc;                         \
         patch_normalize_reg_kernel<LL><<<grid, NCOL * NSEG, lds, st>>>(x, C, N, Cp, xn, xT, inv);                 \
         return check_launch("patch_normalize_reg_kernel")
             NORM_CASE(64); NORM_CASE(32); NORM_CASE(16); NORM_CASE(8); NORM_CASE(4);

@@ -143,25 +143,33 @@ __global__ void __launch_bounds__(256) cat_relu_bwd_kernel(const IO* __restrict_
     }
 }
 
+// blocks per batch sample of the two cat_relu kernels: ~4 vectors (or elements, where HW % 4 != 0) per thread
+static int cat_relu_gx(int C1, int C2, int HW)
+{
+    const size_t n = (size_t)(C1 + C2) * HW;
+    const int gx = (int)((((HW & 3) == 0 ? n >> 2 : n) + 256 * 4 - 1) / (256 * 4));
+    return gx < 1 ? 1 : gx;
+}
+
 int launch_cat_relu_fwd(const void* y, const void* x, int B, int C1, int C2, int HW, int io_bf16, void* out, hipStream_t st)
 {
     if (B > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_cat_relu: batch %d > 65535", B);
-    const size_t n = (size_t)(C1 + C2) * HW;
-    int gx = (int)((((HW & 3) == 0 ? n >> 2 : n) + 256 * 4 - 1) / (256 * 4));
-    if (gx < 1) gx = 1;
-    if (io_bf16) cat_relu_fwd_kernel<bf16_t><<<dim3(gx, B), 256, 0, st>>>(static_cast<const bf16_t*>(y), static_cast<const bf16_t*>(x), C1, C2, HW, static_cast<bf16_t*>(out));
-    else cat_relu_fwd_kernel<float><<<dim3(gx, B), 256, 0, st>>>(static_cast<const float*>(y), static_cast<const float*>(x), C1, C2, HW, static_cast<float*>(out));
+    const dim3 grid(cat_relu_gx(C1, C2, HW), B);
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        cat_relu_fwd_kernel<IO><<<grid, 256, 0, st>>>(static_cast<const IO*>(y), static_cast<const IO*>(x), C1, C2, HW, static_cast<IO*>(out));
+    });
     return check_launch("cat_relu_fwd_kernel");
 }
 
 int launch_cat_relu_bwd(const void* g, const void* out, int B, int C1, int C2, int HW, int io_bf16, void* dy, void* dx, hipStream_t st)
 {
     if (B > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_cat_relu: batch %d > 65535", B);
-    const size_t n = (size_t)(C1 + C2) * HW;
-    int gx = (int)((((HW & 3) == 0 ? n >> 2 : n) + 256 * 4 - 1) / (256 * 4));
-    if (gx < 1) gx = 1;
-    if (io_bf16) cat_relu_bwd_kernel<bf16_t><<<dim3(gx, B), 256, 0, st>>>(static_cast<const bf16_t*>(g), static_cast<const bf16_t*>(out), C1, C2, HW, static_cast<bf16_t*>(dy), static_cast<bf16_t*>(dx));
-    else cat_relu_bwd_kernel<float><<<dim3(gx, B), 256, 0, st>>>(static_cast<const float*>(g), static_cast<const float*>(out), C1, C2, HW, static_cast<float*>(dy), static_cast<float*>(dx));
+    const dim3 grid(cat_relu_gx(C1, C2, HW), B);
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        cat_relu_bwd_kernel<IO><<<grid, 256, 0, st>>>(static_cast<const IO*>(g), static_cast<const IO*>(out), C1, C2, HW, static_cast<IO*>(dy), static_cast<IO*>(dx));
+    });
     return check_launch("cat_relu_bwd_kernel");
 }
 
@@ -174,15 +182,13 @@ int launch_bias_act(void* x, const float* bias, int B, int C, int HW, int act, f
     int gx = cdiv(per, 256 * 4);                        // ~4 vectors per thread
     if (gx < 1) gx = 1;
     const dim3 grid(gx, planes);
-    if (act < 0 || act > 2) return fail(IPSR_ERR_INVALID, "ipsr_bias_act: unknown activation %d", act);
-#define BA_LAUNCH(IO)                                                                                         \
-    switch (act) {                                                                                            \
-        case 0: bias_act_kernel<IO, 0><<<grid, 256, 0, st>>>(static_cast<IO*>(x), bias, C, HW, slope, static_cast<IO*>(y2), y2bs, tickets); break; \
-        case 1: bias_act_kernel<IO, 1><<<grid, 256, 0, st>>>(static_cast<IO*>(x), bias, C, HW, slope, static_cast<IO*>(y2), y2bs, tickets); break; \
-        default: bias_act_kernel<IO, 2><<<grid, 256, 0, st>>>(static_cast<IO*>(x), bias, C, HW, slope, static_cast<IO*>(y2), y2bs, tickets); break; \
-    }
-    if (io_bf16) { BA_LAUNCH(bf16_t) } else { BA_LAUNCH(float) }
-#undef BA_LAUNCH
+    const bool known = with_int<0, 1, 2>(act, [&](auto A) {
+        with_type(io_bf16, [&](auto* tag) {
+            using IO = ELEM_T(tag);
+            bias_act_kernel<IO, decltype(A)::value><<<grid, 256, 0, st>>>(static_cast<IO*>(x), bias, C, HW, slope, static_cast<IO*>(y2), y2bs, tickets);
+        });
+    });
+    if (!known) return fail(IPSR_ERR_INVALID, "ipsr_bias_act: unknown activation %d", act);
     return check_launch("bias_act_kernel");
 }
 
@@ -194,11 +200,12 @@ int launch_bias_relu_pool2(const void* x, const float* bias, int B, int C, int H
     const int per = (W & 3) == 0 ? Ho * (Wo >> 1) : Ho * Wo;
     int gx = cdiv(per, 256 * 2);
     if (gx < 1) gx = 1;
-    if (io_bf16)
-        bias_relu_pool2_kernel<bf16_t><<<dim3(gx, planes), 256, 0, st>>>(static_cast<const bf16_t*>(x), bias, C, H, W, static_cast<bf16_t*>(y));
-    else
-        bias_relu_pool2_kernel<float><<<dim3(gx, planes), 256, 0, st>>>(static_cast<const float*>(x), bias, C, H, W, static_cast<float*>(y));
+    with_type(io_bf16, [&](auto* tag) {
+        using IO = ELEM_T(tag);
+        bias_relu_pool2_kernel<IO><<<dim3(gx, planes), 256, 0, st>>>(static_cast<const IO*>(x), bias, C, H, W, static_cast<IO*>(y));
+    });
     return check_launch("bias_relu_pool2_kernel");
 }
 
 }  // namespace ipsr
+

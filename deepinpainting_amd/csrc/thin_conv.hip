@@ -726,6 +726,95 @@ __global__ void __launch_bounds__(256) one_wrw_kernel(const float* __restrict__ 
 
 using namespace ipsr;
 
+// ---- plans ------------------------------------------------------------------------------------------------------------------------
+// One struct per pass: the template arguments of its kernel, the grid, the rows a workgroup walks, dynamic LDS and workspace bytes.  One
+// function returns it and holds the pass's shape rules; the queries and the launcher both read it.  `fit` is the FIRST rule the shape
+// breaks, in the order the pass's entry reports them.  The entry's own checks (pointers, workspace) sit between those reports, so every
+// field but the grid is filled whatever the answer except THIN_NO_KERNEL, which leaves them 0 (what the queries then answer).
+//   THIN_NO_KERNEL   no kernel for the shape          THIN_ODD_WIDTH   few -> many stores pixel pairs
+//   THIN_GRID        an axis of the grid past 65535   THIN_LDS         the staging buffers exceed the pass's LDS
+enum ThinFit { THIN_FITS = 0, THIN_NO_KERNEL, THIN_GRID, THIN_ODD_WIDTH, THIN_LDS };
+
+// the element types of a pass's two tensors: bit 0 / bit 1 of its io code
+template <typename F> static inline void with_io(int io, F&& f)
+{
+    with_type(io & 1, [&](auto* a) { with_type(io & 2, [&](auto* b) { f(a, b); }); });
+}
+
+struct ThinF2mPlan { ThinFit fit; int I; dim3 grid; };
+static ThinF2mPlan thin_f2m_plan(int B, int I, int O, int H, int W)
+{
+    if (O % THIN_OC != 0 || (I != 3 && I != 6)) return {THIN_NO_KERNEL};
+    if ((size_t)B * (O / THIN_OC) > 65535 || H > 65535) return {THIN_GRID};
+    if (W & 1) return {THIN_ODD_WIDTH};
+    return {THIN_FITS, I, dim3(cdiv(W, 512), H, B * (O / THIN_OC))};
+}
+
+struct ThinM2fPlan { ThinFit fit; int O; dim3 grid; size_t lds_bytes; };
+static ThinM2fPlan thin_m2f_plan(int B, int I, int O, int H, int W)
+{
+    if ((O != 3 && O != 6) || W % 4 != 0) return {THIN_NO_KERNEL};
+    const size_t lds = (size_t)I * O * 9 * sizeof(float);        // every weight of the layer
+    return {lds > 48 * 1024 ? THIN_LDS : THIN_FITS, O, dim3(cdiv(W, 256), cdiv(H, 4), B), lds};
+}
+
+struct ThinWrwPlan { ThinFit fit; int Cs; dim3 grid; size_t ws_bytes; };
+static ThinWrwPlan thin_wrw_plan(int B, int Cb, int Cs, int H, int W)
+{
+    if (B < 1 || Cb < 1 || H < 1 || W < 1 || (Cs != 3 && Cs != 6) || Cb % THIN_CB != 0 || W % 4 != 0) return {THIN_NO_KERNEL};
+    const size_t gz = (size_t)B * (Cb / THIN_CB), nblk = gz * cdiv(H, THIN_ROWS) * cdiv(W, 256);
+    const size_t ws = align_up(nblk * THIN_CB * Cs * 9 * sizeof(float), 256) + 256;      // one partial gradient per workgroup
+    return {gz > 65535 ? THIN_GRID : THIN_FITS, Cs, dim3(cdiv(W, 256), cdiv(H, THIN_ROWS), (unsigned)gz), ws};
+}
+
+// few -> many on the matrix cores
+struct ThinF2mMfmaPlan { ThinFit fit; int MT, KS, rows; dim3 grid; };
+static ThinF2mMfmaPlan thin_f2m_mfma_plan(int B, int Cs, int O, int Ho, int Wo, int k, int stride)
+{
+    const bool k3 = k == 3 && stride == 1, k4 = k == 4 && stride == 2;
+    if (B < 1 || O < 1 || Ho < 1 || (Cs != 3 && Cs != 6) || !(k3 || k4) || Wo % 32 != 0 || O % 8 != 0) return {THIN_NO_KERNEL};
+    const int KS = (Cs * k * k + 15) / 16;                       // 2, 4, 3, 6
+    const int MT = O >= 128 && KS <= 4 ? 4 : 2;
+    const int otiles = cdiv(O, 32 * MT);
+    int rows = 4;
+    while ((long)B * otiles * cdiv(Ho, rows) > 2048 && rows < Ho) rows *= 2;
+    return {B > 65535 || otiles > 65535 ? THIN_GRID : THIN_FITS, MT, KS, rows, dim3(cdiv(Ho, rows), B, otiles)};
+}
+
+// thin weight gradients on the matrix cores
+struct ThinWrwMfmaPlan { ThinFit fit; int MT, RT, rows; dim3 grid; size_t ws_bytes; };
+static ThinWrwMfmaPlan thin_wrw_mfma_plan(int B, int Kb, int Cs, int Hb, int Wb, int k, int stride)
+{
+    const bool k3 = k == 3 && stride == 1, k4 = k == 4 && stride == 2;
+    if (B < 1 || Kb < 1 || Hb < 1 || (Cs != 3 && Cs != 6) || !(k3 || k4) || Wb % 16 != 0 || Wb < 16 || Kb % 8 != 0) return {THIN_NO_KERNEL};
+    const int R = Cs * k * k;                                    // 27, 54, 48, 96
+    const int RT = (R + 31) / 32;
+    const int MT = Kb >= 128 && RT <= 2 ? 4 : 2;                 // accumulator tiles per wave: at most 8
+    // rows per workgroup: two to four workgroups per CU
+    const int ktiles = cdiv(Kb, 32 * MT);
+    int rows = 4;
+    const long wgs = RT >= 2 ? 512 : 1024;                       // (measured: two gather tiles per step like longer runs, one tile more workgroups)
+    while ((long)B * ktiles * cdiv(Hb, rows) > wgs && rows < Hb) rows *= 2;
+    const int gx = cdiv(Hb, rows);
+    const size_t ws = align_up((size_t)ktiles * B * gx * (32 * MT) * (32 * RT) * sizeof(float), 256) + 256;      // a slab per workgroup
+    return {B > 65535 || ktiles > 65535 ? THIN_GRID : THIN_FITS, MT, RT, rows, dim3(gx, B, ktiles), ws};
+}
+
+// The to-one layer: op 0 forward, anything else sizes the LDS of the weight gradient (which takes no workspace).
+constexpr int ONE_LDS_MAX = 64 * 1024;
+struct ToOnePlan { ThinFit fit; int K, Ho, Wo, nchunk; size_t lds_bytes, ws_bytes; };
+static ToOnePlan to_one_plan(int op, int B, int C, int H, int W, int K, int pad)
+{
+    const int Ho = H + 2 * pad - K + 1, Wo = W + 2 * pad - K + 1;
+    if (B < 1 || C < 1 || pad < 0 || Ho < 1 || Wo < 1 || (K != 3 && K != 4) || Ho * cdiv(Wo, 4) > 256) return {THIN_NO_KERNEL};
+    const int nchunk = cdiv(C, ONE_CCH);
+    // two padded planes in flight, and the chunk's weights (forward) or two output-gradient planes and the waves' partial sums (gradient)
+    const size_t psz = (size_t)(H + 2 * pad) * (W + 2 * pad);
+    const size_t lds = (op == 0 ? 2 * psz + (size_t)ONE_CCH * K * K : 2 * psz + 2 * (size_t)Ho * Wo + 4 * K * K) * sizeof(float);
+    const size_t ws = align_up((size_t)B * nchunk * Ho * Wo * sizeof(float), 256) + 256;
+    return {B > 65535 ? THIN_GRID : lds > ONE_LDS_MAX ? THIN_LDS : THIN_FITS, K, Ho, Wo, nchunk, lds, ws};
+}
+
 extern "C" {
 
 // io: bit 0 = `in` is bf16, bit 1 = `out` is bf16 (as in ipsr_conv3x3_winograd_mp); 0 = the fp32 kernels of round 2.
@@ -737,31 +826,34 @@ int ipsr_conv3x3_thin_io(int op, const void* in, const float* w, const float* bi
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool ib = io & 1, ob = io & 2;
     if (op == 0) {          // few -> many
-        if (O % THIN_OC != 0 || (I != 3 && I != 6)) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs 3 or 6 inputs and outputs %% 16 == 0 (got %d -> %d)", I, O);
-        if ((size_t)B * (O / THIN_OC) > 65535 || H > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: grid too large");
-        if (W & 1) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs an even width (W=%d)", W);
+        const ThinF2mPlan p = thin_f2m_plan(B, I, O, H, W);
+        if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs 3 or 6 inputs and outputs %% 16 == 0 (got %d -> %d)", I, O);
+        if (p.fit == THIN_GRID) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: grid too large");
+        if (p.fit == THIN_ODD_WIDTH) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: few->many needs an even width (W=%d)", W);
         if (reinterpret_cast<uintptr_t>(out) & (ob ? 3u : 7u)) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin: few->many stores pixel pairs: out must be aligned to two elements");
-        const dim3 grid(cdiv(W, 512), H, B * (O / THIN_OC));
-#define THIN_F2M(II, TI, TO) thin_f2m_kernel<II, TI, TO><<<grid, 256, 0, st>>>(static_cast<const TI*>(in), w, bias, relu, static_cast<TO*>(out), B, O, H, W, so, si, flip)
-#define THIN_F2M_IO(II) do { if (ib && ob) THIN_F2M(II, bf16_t, bf16_t); else if (ib) THIN_F2M(II, bf16_t, float); else if (ob) THIN_F2M(II, float, bf16_t); else THIN_F2M(II, float, float); } while (0)
-        if (I == 3) THIN_F2M_IO(3); else THIN_F2M_IO(6);
-#undef THIN_F2M_IO
-#undef THIN_F2M
+        with_int<3, 6>(p.I, [&](auto II) {
+            with_io(io, [&](auto* ti, auto* to) {
+                using TI = ELEM_T(ti);
+                using TO = ELEM_T(to);
+                thin_f2m_kernel<decltype(II)::value, TI, TO><<<p.grid, 256, 0, st>>>(static_cast<const TI*>(in), w, bias, relu, static_cast<TO*>(out), B, O, H, W, so, si, flip);
+            });
+        });
         return check_launch("thin_f2m_kernel");
     }
     if (op == 1) {          // many -> few
         if (bias || relu) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: many->few has no epilogue");
-        if ((O != 3 && O != 6) || W % 4 != 0) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: many->few needs 3 or 6 outputs and W %% 4 == 0 (got %d -> %d, W=%d)", I, O, W);
+        const ThinM2fPlan p = thin_m2f_plan(B, I, O, H, W);
+        if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: many->few needs 3 or 6 outputs and W %% 4 == 0 (got %d -> %d, W=%d)", I, O, W);
         if ((reinterpret_cast<uintptr_t>(in) & (ib ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(out) & (ob ? 7u : 15u)))
             return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin: tensors must be aligned to four elements");
-        const size_t lds = (size_t)I * O * 9 * sizeof(float);
-        if (lds > 48 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: %d input channels exceed the LDS weight buffer", I);
-        const dim3 grid(cdiv(W, 256), cdiv(H, 4), B);
-#define THIN_M2F(OO, TI, TO) thin_m2f_kernel<OO, TI, TO><<<grid, 256, lds, st>>>(static_cast<const TI*>(in), w, static_cast<TO*>(out), B, I, H, W, so, si, flip)
-#define THIN_M2F_IO(OO) do { if (ib && ob) THIN_M2F(OO, bf16_t, bf16_t); else if (ib) THIN_M2F(OO, bf16_t, float); else if (ob) THIN_M2F(OO, float, bf16_t); else THIN_M2F(OO, float, float); } while (0)
-        if (O == 3) THIN_M2F_IO(3); else THIN_M2F_IO(6);
-#undef THIN_M2F_IO
-#undef THIN_M2F
+        if (p.fit == THIN_LDS) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin: %d input channels exceed the LDS weight buffer", I);
+        with_int<3, 6>(p.O, [&](auto OO) {
+            with_io(io, [&](auto* ti, auto* to) {
+                using TI = ELEM_T(ti);
+                using TO = ELEM_T(to);
+                thin_m2f_kernel<decltype(OO)::value, TI, TO><<<p.grid, 256, p.lds_bytes, st>>>(static_cast<const TI*>(in), w, static_cast<TO*>(out), B, I, H, W, so, si, flip);
+            });
+        });
         return check_launch("thin_m2f_kernel");
     }
     return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin: op %d", op);
@@ -775,32 +867,31 @@ int ipsr_conv3x3_thin(int op, const float* in, const float* w, const float* bias
 
 size_t ipsr_conv3x3_thin_wrw_workspace_bytes(int B, int Cb, int Cs, int H, int W)
 {
-    if (B < 1 || Cb < 1 || H < 1 || W < 1 || (Cs != 3 && Cs != 6) || Cb % THIN_CB != 0 || W % 4 != 0) return 0;
-    const size_t nblk = (size_t)B * (Cb / THIN_CB) * cdiv(H, THIN_ROWS) * cdiv(W, 256);
-    return align_up(nblk * THIN_CB * Cs * 9 * sizeof(float), 256) + 256;
+    return thin_wrw_plan(B, Cb, Cs, H, W).ws_bytes;
 }
 
 // io: bit 0 = `big` is bf16, bit 1 = `small` is bf16; the gradient is fp32 either way.
 int ipsr_conv3x3_thin_wrw_io(const void* big, const void* small, float* g, int B, int Cb, int Cs, int H, int W, int io, void* ws, size_t ws_bytes, void* stream)
 {
     if (!big || !small || !g || !ws || (io & ~3)) return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin_wrw: null pointer / bad io code");
-    const size_t need = ipsr_conv3x3_thin_wrw_workspace_bytes(B, Cb, Cs, H, W);
-    if (need == 0) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin_wrw: Cb=%d Cs=%d %dx%d is not implemented", Cb, Cs, H, W);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv3x3_thin_wrw: workspace %zu < %zu", ws_bytes, need);
+    const ThinWrwPlan p = thin_wrw_plan(B, Cb, Cs, H, W);
+    if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin_wrw: Cb=%d Cs=%d %dx%d is not implemented", Cb, Cs, H, W);
+    if (ws_bytes < p.ws_bytes) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv3x3_thin_wrw: workspace %zu < %zu", ws_bytes, p.ws_bytes);
     const bool bb = io & 1, sb = io & 2;
     if ((reinterpret_cast<uintptr_t>(big) & (bb ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(small) & (sb ? 7u : 15u)) || (reinterpret_cast<uintptr_t>(ws) & 15u))
         return fail(IPSR_ERR_INVALID, "ipsr_conv3x3_thin_wrw: tensors must be aligned to four elements, the workspace to 16 bytes");
-    if ((size_t)B * (Cb / THIN_CB) > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin_wrw: grid too large");
+    if (p.fit == THIN_GRID) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv3x3_thin_wrw: grid too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(ws);
-    const dim3 grid(cdiv(W, 256), cdiv(H, THIN_ROWS), B * (Cb / THIN_CB));
-#define THIN_WRW(CC, TBG, TSM) thin_wrw_kernel<CC, TBG, TSM><<<grid, 256, 0, st>>>(static_cast<const TBG*>(big), static_cast<const TSM*>(small), part, B, Cb, H, W)
-#define THIN_WRW_IO(CC) do { if (bb && sb) THIN_WRW(CC, bf16_t, bf16_t); else if (bb) THIN_WRW(CC, bf16_t, float); else if (sb) THIN_WRW(CC, float, bf16_t); else THIN_WRW(CC, float, float); } while (0)
-    if (Cs == 3) THIN_WRW_IO(3); else THIN_WRW_IO(6);
-#undef THIN_WRW_IO
-#undef THIN_WRW
+    with_int<3, 6>(p.Cs, [&](auto CC) {
+        with_io(io, [&](auto* tb, auto* ts) {
+            using TBG = ELEM_T(tb);
+            using TSM = ELEM_T(ts);
+            thin_wrw_kernel<decltype(CC)::value, TBG, TSM><<<p.grid, 256, 0, st>>>(static_cast<const TBG*>(big), static_cast<const TSM*>(small), part, B, Cb, H, W);
+        });
+    });
     if (int rc = check_launch("thin_wrw_kernel")) return rc;
-    thin_wrw_reduce_kernel<<<cdiv(Cb * Cs * 9, 256), 256, 0, st>>>(part, g, B, Cb, Cs, (int)(grid.x * grid.y));
+    thin_wrw_reduce_kernel<<<cdiv(Cb * Cs * 9, 256), 256, 0, st>>>(part, g, B, Cb, Cs, (int)(p.grid.x * p.grid.y));
     return check_launch("thin_wrw_reduce_kernel");
 }
 
@@ -809,24 +900,9 @@ int ipsr_conv3x3_thin_wrw(const float* big, const float* small, float* g, int B,
     return ipsr_conv3x3_thin_wrw_io(big, small, g, B, Cb, Cs, H, W, 0, ws, ws_bytes, stream);
 }
 
-// ---- few -> many on the matrix cores --------------------------------------------------------------------------------------------
-static int thin_f2m_mfma_plan(int B, int Cs, int O, int Ho, int Wo, int k, int stride, int* MT, int* KS, int* rows)
-{
-    const bool k3 = k == 3 && stride == 1, k4 = k == 4 && stride == 2;
-    if (B < 1 || O < 1 || Ho < 1 || (Cs != 3 && Cs != 6) || !(k3 || k4) || Wo % 32 != 0 || O % 8 != 0) return 0;
-    *KS = (Cs * k * k + 15) / 16;                             // 2, 4, 3, 6
-    *MT = O >= 128 && *KS <= 4 ? 4 : 2;
-    const int otiles = (O + 32 * *MT - 1) / (32 * *MT);
-    int r = 4;
-    while ((long)B * otiles * ((Ho + r - 1) / r) > 2048 && r < Ho) r *= 2;
-    *rows = r;
-    return otiles;
-}
-
 int ipsr_conv_thin_f2m_mfma_supported(int B, int Cs, int O, int Ho, int Wo, int k, int stride)
 {
-    int MT, KS, rows;
-    return thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride, &MT, &KS, &rows) > 0;
+    return thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride).fit != THIN_NO_KERNEL;
 }
 
 // in [B,Cs,Ho*stride,Wo*stride] (io bit 0: bf16, else fp32), out [B,O,Ho,Wo] (io bit 1: bf16, else fp32); weight element (o, cs, t) at
@@ -835,54 +911,31 @@ int ipsr_conv_thin_f2m_mfma(const void* in, const float* w, const float* bias, i
                             long so, long si, int flip, int io, void* stream)
 {
     if (!in || !w || !out || (io & ~3)) return fail(IPSR_ERR_INVALID, "ipsr_conv_thin_f2m_mfma: null pointer / bad io code");
-    int MT, KS, rows;
-    const int otiles = thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride, &MT, &KS, &rows);
-    if (!otiles) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_f2m_mfma: Cs=%d O=%d %dx%d k%d s%d is not implemented", Cs, O, Ho, Wo, k, stride);
+    const ThinF2mMfmaPlan p = thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride);
+    if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_f2m_mfma: Cs=%d O=%d %dx%d k%d s%d is not implemented", Cs, O, Ho, Wo, k, stride);
     if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(IPSR_ERR_INVALID, "ipsr_conv_thin_f2m_mfma: `out` must be 16-byte aligned");
-    if (B > 65535 || otiles > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_f2m_mfma: grid too large");
+    if (p.fit == THIN_GRID) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_f2m_mfma: grid too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((Ho + rows - 1) / rows, B, otiles);
     const int Hs = Ho * stride, Ws = Wo * stride;
-    const bool ib = io & 1, ob = io & 2;
-#define THIN_FM(MTT, KSS, TI, TO) thin_f2m_mfma_kernel<MTT, KSS, TI, TO><<<grid, 256, 0, st>>>(static_cast<const TI*>(in), w, bias, relu, static_cast<TO*>(out), \
-                                                                                       B, Cs, O, Hs, Ws, Ho, Wo, k, stride, 1, so, si, flip, rows)
-#define THIN_FM_IO(MTT, KSS) do { if (ib && ob) THIN_FM(MTT, KSS, bf16_t, bf16_t); else if (ib) THIN_FM(MTT, KSS, bf16_t, float); \
-                                  else if (ob) THIN_FM(MTT, KSS, float, bf16_t); else THIN_FM(MTT, KSS, float, float); } while (0)
-    if (MT == 4) {
-        if (KS == 2) THIN_FM_IO(4, 2); else if (KS == 3) THIN_FM_IO(4, 3); else THIN_FM_IO(4, 4);
-    } else {
-        if (KS == 2) THIN_FM_IO(2, 2); else if (KS == 3) THIN_FM_IO(2, 3); else if (KS == 4) THIN_FM_IO(2, 4); else THIN_FM_IO(2, 6);
-    }
-#undef THIN_FM_IO
-#undef THIN_FM
+    // MT = 4 comes with KS <= 4 only (thin_f2m_mfma_plan)
+    with_int<4, 2>(p.MT, [&](auto MTT) {
+        with_int<2, 3, 4, 6>(p.KS, [&](auto KSS) {
+            constexpr int MT = decltype(MTT)::value, KS = decltype(KSS)::value;
+            if constexpr (MT == 2 || KS <= 4)
+                with_io(io, [&](auto* ti, auto* to) {
+                    using TI = ELEM_T(ti);
+                    using TO = ELEM_T(to);
+                    thin_f2m_mfma_kernel<MT, KS, TI, TO><<<p.grid, 256, 0, st>>>(static_cast<const TI*>(in), w, bias, relu, static_cast<TO*>(out),
+                                                                               B, Cs, O, Hs, Ws, Ho, Wo, k, stride, 1, so, si, flip, p.rows);
+                });
+        });
+    });
     return check_launch("thin_f2m_mfma_kernel");
-}
-
-// ---- thin weight gradients on the matrix cores (bf16 wide tensor) ---------------------------------------------------------------
-static int thin_wrw_mfma_plan(int B, int Kb, int Cs, int Hb, int Wb, int k, int stride, int* MT, int* RT, int* rows_per_wg, int* gx)
-{
-    const bool k3 = k == 3 && stride == 1, k4 = k == 4 && stride == 2;
-    if (B < 1 || Kb < 1 || Hb < 1 || (Cs != 3 && Cs != 6) || !(k3 || k4) || Wb % 16 != 0 || Wb < 16) return 0;
-    const int R = Cs * k * k;                                 // 27, 54, 48, 96
-    *RT = (R + 31) / 32;
-    *MT = Kb >= 128 && *RT <= 2 ? 4 : 2;                      // accumulator tiles per wave: at most 8
-    if (Kb % 8 != 0) return 0;
-    // rows per workgroup: two to four workgroups per CU
-    const int ktiles = (Kb + 32 * *MT - 1) / (32 * *MT);
-    int rows = 4;
-    const long wgs = *RT >= 2 ? 512 : 1024;                   // (measured: two gather tiles per step like longer runs, one tile more workgroups)
-    while ((long)B * ktiles * ((Hb + rows - 1) / rows) > wgs && rows < Hb) rows *= 2;
-    *rows_per_wg = rows;
-    *gx = (Hb + rows - 1) / rows;
-    return ktiles;
 }
 
 size_t ipsr_conv_thin_wrw_mfma_workspace_bytes(int B, int Kb, int Cs, int Hb, int Wb, int k, int stride)
 {
-    int MT, RT, rows, gx;
-    const int ktiles = thin_wrw_mfma_plan(B, Kb, Cs, Hb, Wb, k, stride, &MT, &RT, &rows, &gx);
-    if (!ktiles) return 0;
-    return align_up((size_t)ktiles * B * gx * (32 * MT) * (32 * RT) * sizeof(float), 256) + 256;
+    return thin_wrw_mfma_plan(B, Kb, Cs, Hb, Wb, k, stride).ws_bytes;
 }
 
 // big [B,Kb,Hb,Wb], small [B,Cs,Hs,Ws], Hs = Hb (k3 s1 p1) or 2 Hb (k4 s2 p1); g [Kb][Cs][k][k] fp32.  io: bit 0 = `big` is bf16, bit 1 =
@@ -893,69 +946,64 @@ int ipsr_conv_thin_wrw_mfma(const void* big, const void* small, float* g, int B,
 {
     if (!big || !small || !g || !ws || (io & ~3)) return fail(IPSR_ERR_INVALID, "ipsr_conv_thin_wrw_mfma: null pointer / bad io code");
     if (io == 2) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_wrw_mfma: an fp32 wide tensor needs an fp32 narrow one");
-    const int small_bf16 = (io >> 1) & 1, big_bf16 = io & 1;
-    int MT, RT, rows, gx;
-    const int ktiles = thin_wrw_mfma_plan(B, Kb, Cs, Hb, Wb, k, stride, &MT, &RT, &rows, &gx);
-    if (!ktiles) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_wrw_mfma: Kb=%d Cs=%d %dx%d k%d s%d is not implemented", Kb, Cs, Hb, Wb, k, stride);
-    const size_t need = ipsr_conv_thin_wrw_mfma_workspace_bytes(B, Kb, Cs, Hb, Wb, k, stride);
-    if (ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv_thin_wrw_mfma: workspace %zu < %zu", ws_bytes, need);
+    const ThinWrwMfmaPlan p = thin_wrw_mfma_plan(B, Kb, Cs, Hb, Wb, k, stride);
+    if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_wrw_mfma: Kb=%d Cs=%d %dx%d k%d s%d is not implemented", Kb, Cs, Hb, Wb, k, stride);
+    if (ws_bytes < p.ws_bytes) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv_thin_wrw_mfma: workspace %zu < %zu", ws_bytes, p.ws_bytes);
     if ((reinterpret_cast<uintptr_t>(big) & 15u) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return fail(IPSR_ERR_INVALID, "ipsr_conv_thin_wrw_mfma: `big` / workspace must be 16-byte aligned");
-    if (B > 65535 || ktiles > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_wrw_mfma: grid too large");
+    if (p.fit == THIN_GRID) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_thin_wrw_mfma: grid too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* slabs = static_cast<float*>(ws);
     const int Hs = Hb * stride, Ws = Wb * stride, pad = 1;
-    const dim3 grid(gx, B, ktiles);
-#define THIN_WM(MTT, RTT, TBG, TSM) thin_wrw_mfma_kernel<MTT, RTT, TBG, TSM><<<grid, 256, 0, st>>>(static_cast<const TBG*>(big), static_cast<const TSM*>(small), slabs, \
-                                                                                            B, Kb, Cs, Hb, Wb, Hs, Ws, k, stride, pad, rows)
-#define THIN_WM_TS(MTT, RTT) do { if (!big_bf16) THIN_WM(MTT, RTT, float, float); else if (small_bf16) THIN_WM(MTT, RTT, bf16_t, bf16_t); \
-                                  else THIN_WM(MTT, RTT, bf16_t, float); } while (0)
-    if (MT == 4 && RT == 1) THIN_WM_TS(4, 1);
-    else if (MT == 4 && RT == 2) THIN_WM_TS(4, 2);
-    else if (RT == 1) THIN_WM_TS(2, 1);
-    else if (RT == 2) THIN_WM_TS(2, 2);
-    else THIN_WM_TS(2, 3);
-#undef THIN_WM_TS
-#undef THIN_WM
+    // MT = 4 comes with RT <= 2 only (thin_wrw_mfma_plan); an fp32 `big` has been refused a bf16 `small` above
+    with_int<4, 2>(p.MT, [&](auto MTT) {
+        with_int<1, 2, 3>(p.RT, [&](auto RTT) {
+            constexpr int MT = decltype(MTT)::value, RT = decltype(RTT)::value;
+            if constexpr (MT == 2 || RT <= 2)
+                with_io(io, [&](auto* tb, auto* ts) {
+                    using TBG = ELEM_T(tb);
+                    using TSM = ELEM_T(ts);
+                    if constexpr (std::is_same_v<TBG, bf16_t> || std::is_same_v<TSM, float>)
+                        thin_wrw_mfma_kernel<MT, RT, TBG, TSM><<<p.grid, 256, 0, st>>>(static_cast<const TBG*>(big), static_cast<const TSM*>(small), slabs,
+                                                                                   B, Kb, Cs, Hb, Wb, Hs, Ws, k, stride, pad, p.rows);
+                });
+        });
+    });
     if (int rc = check_launch("thin_wrw_mfma_kernel")) return rc;
-    thin_wrw_mfma_reduce_kernel<<<ktiles * 32 * MT > Kb ? Kb : ktiles * 32 * MT, 256, 0, st>>>(slabs, g, Kb, Cs * k * k, 32 * MT, 32 * RT, B * gx);
+    const int krows = (int)p.grid.z * 32 * p.MT;               // rows of the slabs: the k tiles, whole
+    thin_wrw_mfma_reduce_kernel<<<krows > Kb ? Kb : krows, 256, 0, st>>>(slabs, g, Kb, Cs * k * k, 32 * p.MT, 32 * p.RT, (int)(p.grid.y * p.grid.x));
     return check_launch("thin_wrw_mfma_reduce_kernel");
 }
 
 size_t ipsr_conv_to_one_workspace_bytes(int B, int C, int H, int W, int K, int pad)
 {
-    const int Ho = H + 2 * pad - K + 1, Wo = W + 2 * pad - K + 1;
-    if (B < 1 || C < 1 || pad < 0 || Ho < 1 || Wo < 1 || (K != 3 && K != 4) || Ho * cdiv(Wo, 4) > 256) return 0;
-    return align_up((size_t)B * cdiv(C, ONE_CCH) * Ho * Wo * sizeof(float), 256) + 256;
+    return to_one_plan(0, B, C, H, W, K, pad).ws_bytes;
 }
 
 int ipsr_conv_to_one(int op, const float* x, const float* other, float* out, int B, int C, int H, int W, int K, int pad,
                      void* ws, size_t ws_bytes, void* stream)
 {
     if (!x || !other || !out) return fail(IPSR_ERR_INVALID, "ipsr_conv_to_one: null pointer");
-    const int Ho = H + 2 * pad - K + 1, Wo = W + 2 * pad - K + 1;
-    const size_t need = ipsr_conv_to_one_workspace_bytes(B, C, H, W, K, pad);
-    if (need == 0) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: %dx%d k=%d p=%d is not implemented (k in {3,4}, at most 256 groups of 4 output pixels)", H, W, K, pad);
-    if (B > 65535) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: batch %d", B);
+    const ToOnePlan p = to_one_plan(op, B, C, H, W, K, pad);
+    if (p.fit == THIN_NO_KERNEL) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: %dx%d k=%d p=%d is not implemented (k in {3,4}, at most 256 groups of 4 output pixels)", H, W, K, pad);
+    if (p.fit == THIN_GRID) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: batch %d", B);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t psz = (size_t)(H + 2 * pad) * (W + 2 * pad);
+    const int Ho = p.Ho, Wo = p.Wo;
     if (op == 0) {                                    // forward: other = w [1][C][K][K], out = y [B][1][Ho][Wo]
-        if (!ws || ws_bytes < need) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv_to_one: workspace %zu < %zu", ws_bytes, need);
-        const int nchunk = cdiv(C, ONE_CCH);
-        const size_t lds = (2 * psz + (size_t)ONE_CCH * K * K) * sizeof(float);
-        if (lds > 64 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: a %dx%d plane exceeds the LDS staging buffers", H, W);
+        if (!ws || ws_bytes < p.ws_bytes) return fail(IPSR_ERR_WORKSPACE, "ipsr_conv_to_one: workspace %zu < %zu", ws_bytes, p.ws_bytes);
+        if (p.fit == THIN_LDS) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: a %dx%d plane exceeds the LDS staging buffers", H, W);
         float* part = static_cast<float*>(ws);
-        const dim3 grid(nchunk, B);
-        if (K == 4) one_fwd_kernel<4><<<grid, 256, lds, st>>>(x, other, part, C, H, W, Ho, Wo, pad, nchunk);
-        else one_fwd_kernel<3><<<grid, 256, lds, st>>>(x, other, part, C, H, W, Ho, Wo, pad, nchunk);
+        with_int<3, 4>(p.K, [&](auto KK) {
+            one_fwd_kernel<decltype(KK)::value><<<dim3(p.nchunk, B), 256, p.lds_bytes, st>>>(x, other, part, C, H, W, Ho, Wo, pad, p.nchunk);
+        });
         if (int rc = check_launch("one_fwd_kernel")) return rc;
-        one_fwd_sum_kernel<<<cdiv(B * Ho * Wo, 256), 256, 0, st>>>(part, out, B * Ho * Wo, Ho * Wo, nchunk);
+        one_fwd_sum_kernel<<<cdiv(B * Ho * Wo, 256), 256, 0, st>>>(part, out, B * Ho * Wo, Ho * Wo, p.nchunk);
         return check_launch("one_fwd_sum_kernel");
     }
     if (op == 2) {                                    // weight gradient: other = dy [B][1][Ho][Wo], out = dw [1][C][K][K]
-        const size_t lds = (2 * psz + 2 * (size_t)Ho * Wo + 4 * K * K) * sizeof(float);
-        if (lds > 64 * 1024) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: a %dx%d plane exceeds the LDS staging buffers", H, W);
-        if (K == 4) one_wrw_kernel<4><<<C, 256, lds, st>>>(x, other, out, B, C, H, W, Ho, Wo, pad);
-        else one_wrw_kernel<3><<<C, 256, lds, st>>>(x, other, out, B, C, H, W, Ho, Wo, pad);
+        if (p.fit == THIN_LDS) return fail(IPSR_ERR_UNSUPPORTED, "ipsr_conv_to_one: a %dx%d plane exceeds the LDS staging buffers", H, W);
+        with_int<3, 4>(p.K, [&](auto KK) {
+            one_wrw_kernel<decltype(KK)::value><<<C, 256, p.lds_bytes, st>>>(x, other, out, B, C, H, W, Ho, Wo, pad);
+        });
         return check_launch("one_wrw_kernel");
     }
     return fail(IPSR_ERR_INVALID, "ipsr_conv_to_one: op %d (0 forward, 2 weight gradient)", op);

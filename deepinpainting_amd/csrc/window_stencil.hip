@@ -217,8 +217,7 @@ static int ws_launch(const WindowStencilPlan& p, const float* R, const float* in
     int tq_log2 = 4;
     while ((1 << tq_log2) < nW && tq_log2 < 6) ++tq_log2;
     // more dynamic LDS than the default limit: raised on every launch (the attribute is per device, a static flag would be per process)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&window_stencil_lds_kernel<P, NQ>), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
-    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "window_stencil_lds_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", p.lds_bytes, hipGetErrorString(e));
+    if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&window_stencil_lds_kernel<P, NQ>), "window_stencil_lds_kernel", p.lds_bytes)) return rc;
     window_stencil_lds_kernel<P, NQ><<<(unsigned)p.workgroups, WS_THREADS, p.lds_bytes, st>>>(R, inv, h * w, w, nH, nW, patch, p.split, p.kper, tq_log2, p.nbuf,
                                                                                          (unsigned)(0x100000000ull / (unsigned)w) + 1u, pval, pidx);
     return check_launch("window_stencil_lds_kernel");

@@ -252,8 +252,7 @@ static int wf_launch(const float* x, const float* U, const float* bias, float* y
     const int TY = (H + 3) / 4, TX = (W + 3) / 4;
     const int nbx = cdiv(TX, WF_TCOLS), nby = cdiv(TY, WF_TROWS);
     // more dynamic LDS than the default limit: raised on every launch (the attribute is per device, a static flag would be per process)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_fused_kernel<EPI, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS_BYTES);
-    if (e != hipSuccess) return fail(IPSR_ERR_LAUNCH, "wino_fused_kernel: hipFuncSetAttribute(dynamic LDS %d): %s", WF_LDS_BYTES, hipGetErrorString(e));
+    if (int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&wino_fused_kernel<EPI, VEC>), "wino_fused_kernel", WF_LDS_BYTES)) return rc;
     wino_fused_kernel<EPI, VEC><<<(unsigned)((size_t)B * nby * nbx), WF_THREADS, WF_LDS_BYTES, st>>>(x, U, bias, y, C, K, H, W, TY, TX, nbx, nby);
     return check_launch("wino_fused_kernel");
 }

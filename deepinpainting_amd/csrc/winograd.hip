@@ -970,16 +970,8 @@ static inline bool arith_ok(const ConvArith& a) { return a.math == 0 || a.math =
 
 template <typename F> static inline void with_mode(int math, F&& f)
 {
-    if (math == 2) f(std::integral_constant<int, 2>{});
-    else if (math == 3) f(std::integral_constant<int, 3>{});
-    else f(std::integral_constant<int, 0>{});
+    if (!with_int<2, 3>(math, f)) f(std::integral_constant<int, 0>{});
 }
-template <typename F> static inline void with_type(bool bf16, F&& f)
-{
-    if (bf16) f(static_cast<bf16_t*>(nullptr));
-    else f(static_cast<float*>(nullptr));
-}
-#define ELEM_T(tag) std::remove_pointer_t<decltype(tag)>
 
 // The arithmetic stage of every family: M[xi][rows][cols] = sum over red of A[xi][red][rows] * B[xi][red][cols] for the 36 points.
 // TY x TX tiles per image, T in all, Tp = T rounded up to WG_BN.  The data passes have cols = Tp and red = the reduction

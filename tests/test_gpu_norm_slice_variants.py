@@ -8,18 +8,18 @@ imported here), so every plane size of that table is run again with the slice ar
 
   variant (T threads x E elements, form)   selected at            case ids (each in fp32 and bf16; each runs slice, y2 and dy2)
   ---------------------------------------  ---------------------  -------------------------------------------------------------
-  <64, 4>   scalar                         instnorm.hip:350       hw3, hw255
-  <64, 4>   vector                         instnorm.hip:350       hw4, hw256
-  <64, 16>  scalar                         instnorm.hip:351       hw257, hw1023
-  <64, 16>  vector                         instnorm.hip:351       hw260, hw1024
-  <256, 16> scalar                         instnorm.hip:352       hw1025, hw4095
-  <256, 16> vector                         instnorm.hip:352       hw1028, hw4096
-  <256, 64> scalar                         instnorm.hip:353       hw4097, hw16383
-  <256, 64> vector                         instnorm.hip:353       hw4100, hw16384
-  <512, 128> vector (REX)                  instnorm.hip:363-375 forward, :393-405 backward    hw16388, hw65536
+  <64, 4>   scalar                         in_dispatch            hw3, hw255
+  <64, 4>   vector                         in_dispatch            hw4, hw256
+  <64, 16>  scalar                         in_dispatch            hw257, hw1023
+  <64, 16>  vector                         in_dispatch            hw260, hw1024
+  <256, 16> scalar                         in_dispatch            hw1025, hw4095
+  <256, 16> vector                         in_dispatch            hw1028, hw4096
+  <256, 64> scalar                         in_dispatch            hw4097, hw16383
+  <256, 64> vector                         in_dispatch            hw4100, hw16384
+  <512, 128> vector (REX)                  in_dispatch                                       hw16388, hw65536
   slice addresses                          instnorm.hip:99 (y), :101 (y2), :194-198 (dy, y, dy2)
-  refused: strides, alignment, tickets     api.hip:489-492, :515-520, instnorm.hip:390        refuse_* (INVALID)
-  refused: plane sizes                     instnorm.hip:361-364, :389-394                     refuse_hw16385, refuse_hw65540
+  refused: strides, alignment, tickets     api.hip:489-492, :515-520, launch_instnorm_act_bwd  refuse_* (INVALID)
+  refused: plane sizes                     launch_instnorm_act_fwd / _bwd                     refuse_hw16385, refuse_hw65540
 
 Placement (an off-by-one in an offset or a stride lands in a NaN channel or moves a plane): y at channel 2 of C + 5 channels, y2 at
 channel 1 of C + 3; the backward reads dy and y from channel 2 of C + 5 and dy2 from channel 1 of C + 3.  Everything outside the

@@ -1,24 +1,24 @@
 """The fused instance norm + activation (csrc/instnorm.hip) in every launch variant, against torch in fp64.
 
-The launcher picks a workgroup shape from the plane size HW alone (IN_DISPATCH, instnorm.hip:347-357; the streaming "REX" shape
-above 16384 elements, :363-375 forward / :393-405 backward): a thread holds E elements, T threads a plane, so T*E is the regime's
+The launcher picks a workgroup shape from the plane size HW alone (`in_dispatch` of instnorm.hip, which also holds the streaming "REX"
+shape above 16384 elements): a thread holds E elements, T threads a plane, so T*E is the regime's
 capacity.  Each regime comes in a vector (HW % 4 == 0) and a scalar form; all come with fp32 and bf16 activations.  A case sits at
 a capacity edge (HW == T*E), one element past it (the next regime with a ragged last pass) or just below it, on non-square planes.
 
   variant (T threads x E elements, form)   HW range            selected at            case ids (each in fp32 and bf16)
   ---------------------------------------  ------------------  ---------------------  -----------------------------------------
-  <64, 4>   scalar                         2 .. 256            instnorm.hip:350       hw3, hw255
-  <64, 4>   vector                         4 .. 256            instnorm.hip:350       hw4, hw256
-  <64, 16>  scalar                         257 .. 1024         instnorm.hip:351       hw257, hw1023
-  <64, 16>  vector                         260 .. 1024         instnorm.hip:351       hw260, hw1024
-  <256, 16> scalar                         1025 .. 4096        instnorm.hip:352       hw1025, hw4095
-  <256, 16> vector                         1028 .. 4096        instnorm.hip:352       hw1028, hw4096
-  <256, 64> scalar                         4097 .. 16384       instnorm.hip:353       hw4097, hw16383
-  <256, 64> vector                         4100 .. 16384       instnorm.hip:353       hw4100, hw16384
-  <512, 128> vector (REX)                  16388 .. 65536      instnorm.hip:363-375   hw16388, hw65536
+  <64, 4>   scalar                         2 .. 256            in_dispatch            hw3, hw255
+  <64, 4>   vector                         4 .. 256            in_dispatch            hw4, hw256
+  <64, 16>  scalar                         257 .. 1024         in_dispatch            hw257, hw1023
+  <64, 16>  vector                         260 .. 1024         in_dispatch            hw260, hw1024
+  <256, 16> scalar                         1025 .. 4096        in_dispatch            hw1025, hw4095
+  <256, 16> vector                         1028 .. 4096        in_dispatch            hw1028, hw4096
+  <256, 64> scalar                         4097 .. 16384       in_dispatch            hw4097, hw16383
+  <256, 64> vector                         4100 .. 16384       in_dispatch            hw4100, hw16384
+  <512, 128> vector (REX)                  16388 .. 65536      in_dispatch            hw16388, hw65536
   refused: HW = 1 (IPSR_ERR_INVALID)       < 2                 api.hip:470            refuse_hw1
-  refused: scalar above the register limit 16385 (HW % 4 != 0) instnorm.hip:364, :394 refuse_hw16385
-  refused: above the largest plane         65540               instnorm.hip:361, :389 refuse_hw65540
+  refused: scalar above the register limit 16385 (HW % 4 != 0) the two launchers      refuse_hw16385
+  refused: above the largest plane         65540               the two launchers      refuse_hw65540
 
 Every case runs three configurations, so each variant meets every activation, affine and not, bias and not:
 (none, affine, bias), (relu, no affine, bias), (leaky, affine, no bias).
@@ -48,7 +48,7 @@ PLANES = {3: (1, 3), 4: (2, 2), 255: (15, 17), 256: (8, 32), 257: (1, 257), 260:
 
 
 def variant(HW):
-    """(T, E, vector) the launcher picks: instnorm.hip:347-357 (IN_DISPATCH) and :363-375 (above IN_MAX_HW_REG = 16384)."""
+    """(T, E, vector) the launcher picks: `in_dispatch` of instnorm.hip (the 512 x 128 form above IN_MAX_HW_REG = 16384)."""
     if HW > 65536 or HW < 2:
         return None
     if HW > 16384:

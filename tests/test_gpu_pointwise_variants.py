@@ -4,21 +4,21 @@ Each kernel has a vector form (16-byte accesses: HW % 4 == 0, for the pool W % 4
 tensors, and walks its plane in a grid-stride loop: a workgroup has 256 threads and the grid is sized for about 4 trips per thread
 (2 for the pool); bias_act_bwd_kernel gives one 256-thread workgroup a whole plane.
 
-  kernel / form                     selected at                       case ids (each in fp32 and bf16)
-  --------------------------------  --------------------------------  -------------------------------------------------------------
-  bias_act_kernel vector            pointwise.hip:39, grid :173-175   hw4, hw1024, hw4096 (one workgroup, four full trips), hw4100
-  bias_act_kernel scalar            pointwise.hip:49, grid :173-175   hw1, hw3, hw1023, hw1025, hw4097
-    second output y2 (slice)        pointwise.hip:38                  the same, through ipsr_bias_act_skip
-  bias_act_bwd_kernel vector        instnorm.hip:311                  hw4, hw256, hw1020, hw1024, hw1028, hw4100
-  bias_act_bwd_kernel scalar        instnorm.hip:327                  hw1, hw3, hw255, hw1023 (four trips)
-    dy2 (slice)                     instnorm.hip:309                  the same, through ipsr_bias_act_backward_skip
-  cat_relu_{fwd,bwd}_kernel vector  pointwise.hip:106 / :129, :150    c5+3 and c2+7 at hw4 .. hw4100
-  cat_relu_{fwd,bwd}_kernel scalar  pointwise.hip:113 / :138, :150    c5+3 and c2+7 at hw1 .. hw4097
-    y == NULL / dy == NULL          pointwise.hip:108, :114 / :131, :139   the same cases
-  bias_relu_pool2_kernel vector     pointwise.hip:68, grid :193-195   2x4, 5x8, 64x32, 66x64 (second workgroup)
-  bias_relu_pool2_kernel scalar     pointwise.hip:81, grid :193-195   2x2, 3x5, 7x9, 6x6 (even W, W % 4 == 2), 35x66 (second workgroup)
-  refused: > 65535 planes / batch   pointwise.hip:148, :159, :172, :192    refuse_* (UNSUPPORTED)
-  refused: act, alignment, strides  api.hip:431-473, :525-543, pointwise.hip:177   refuse_* (INVALID)
+  kernel / form                     selected at                                 case ids (each in fp32 and bf16)
+  --------------------------------  ------------------------------------------  -------------------------------------------------------------
+  bias_act_kernel vector            pointwise.hip:39, launch_bias_act           hw4, hw1024, hw4096 (one workgroup, four full trips), hw4100
+  bias_act_kernel scalar            pointwise.hip:49, launch_bias_act           hw1, hw3, hw1023, hw1025, hw4097
+    second output y2 (slice)        pointwise.hip:38                            the same, through ipsr_bias_act_skip
+  bias_act_bwd_kernel vector        instnorm.hip:311                            hw4, hw256, hw1020, hw1024, hw1028, hw4100
+  bias_act_bwd_kernel scalar        instnorm.hip:327                            hw1, hw3, hw255, hw1023 (four trips)
+    dy2 (slice)                     instnorm.hip:309                            the same, through ipsr_bias_act_backward_skip
+  cat_relu_{fwd,bwd}_kernel vector  pointwise.hip:106 / :129, cat_relu_gx       c5+3 and c2+7 at hw4 .. hw4100
+  cat_relu_{fwd,bwd}_kernel scalar  pointwise.hip:113 / :138, cat_relu_gx       c5+3 and c2+7 at hw1 .. hw4097
+    y == NULL / dy == NULL          pointwise.hip:108, :114 / :131, :139        the same cases
+  bias_relu_pool2_kernel vector     pointwise.hip:68, launch_bias_relu_pool2    2x4, 5x8, 64x32, 66x64 (second workgroup)
+  bias_relu_pool2_kernel scalar     pointwise.hip:81, launch_bias_relu_pool2    2x2, 3x5, 7x9, 6x6 (even W, W % 4 == 2), 35x66 (second workgroup)
+  refused: > 65535 planes / batch   the four launchers of pointwise.hip         refuse_* (UNSUPPORTED)
+  refused: act, alignment, strides  api.hip:431-473, :525-543, launch_bias_act  refuse_* (INVALID)
 
 Reference: these kernels do one add, one compare and one rounding per element, so the reference is the same expression evaluated by
 torch on the CPU in fp32 (bf16 inputs upcast, fp32 arithmetic, one rounding to bf16) and the comparison is bit for bit.  The backward
@@ -67,20 +67,20 @@ def _loop(per, per_wg_trips):
 
 
 def bias_act_variant(HW):
-    """(vector, workgroups, trips, ragged): pointwise.hip:39 and launch_bias_act, :173-175."""
+    """(vector, workgroups, trips, ragged): pointwise.hip:39 and launch_bias_act."""
     vec = HW % 4 == 0
     return (vec,) + _loop(HW // 4 if vec else HW, 4)
 
 
 def cat_relu_variant(C1, C2, HW):
-    """pointwise.hip:106 / :129 and launch_cat_relu_{fwd,bwd}, :149-151 / :160-162: one grid row walks a sample's C1 + C2 planes."""
+    """pointwise.hip:106 / :129 and launch_cat_relu_{fwd,bwd} (cat_relu_gx): one grid row walks a sample's C1 + C2 planes."""
     vec = HW % 4 == 0
     n = (C1 + C2) * HW
     return (vec,) + _loop(n // 4 if vec else n, 4)
 
 
 def pool_variant(H, W):
-    """pointwise.hip:68 and launch_bias_relu_pool2, :193-195: a thread of the vector form writes two adjacent outputs."""
+    """pointwise.hip:68 and launch_bias_relu_pool2: a thread of the vector form writes two adjacent outputs."""
     vec = W % 4 == 0
     Ho, Wo = H // 2, W // 2
     return (vec,) + _loop(Ho * (Wo // 2) if vec else Ho * Wo, 2)

@@ -4,53 +4,53 @@ Every case goes through the `ops` wrappers (ops.py:812-974).  tests/thin_conv_pl
 tables; tests/test_thin_conv_plan.py proves without a GPU that the tables reach every row below, and each test here asserts its
 own row again (`P.check_case`) before it compares numbers.
 
-  variant                                                                            selected at                    case ids
-  ---------------------------------------------------------------------------------  -----------------------------  ----------------------------------------
-  thin_f2m_mfma_kernel<4,2>                                                          thin_conv.hip:817-818, :852    convT136_3_k3_b1_5x32
-  thin_f2m_mfma_kernel<4,3>                                                          thin_conv.hip:817-818, :852    convT128_3_k4s2_b2_5x32
-  thin_f2m_mfma_kernel<4,4>                                                          thin_conv.hip:817-818, :852    conv6_136_k3_b1_6x32
-  thin_f2m_mfma_kernel<2,2>                                                          thin_conv.hip:817-818, :854    conv3_8_k3_b1_7x64, conv3_8_k3_b33_250x32
-  thin_f2m_mfma_kernel<2,3>                                                          thin_conv.hip:817-818, :854    conv3_40_k4s2_b2_6x64
-  thin_f2m_mfma_kernel<2,4>                                                          thin_conv.hip:817-818, :854    conv6_72_k3_b1_9x32
-  thin_f2m_mfma_kernel<2,6>                                                          thin_conv.hip:817-818, :854    convT24_6_k4s2_b2_5x32
-  thin_f2m_mfma_kernel: a second o tile with 8 live rows                             thin_conv.hip:819, :468, :575  conv6_136_k3_b1_6x32, conv6_72_k3_b1_9x32
-                                                                                                                    convT136_3_k3_b1_5x32
-  thin_f2m_mfma_kernel: ragged last row group, a wave idle                           thin_conv.hip:508              convT128_3_k4s2_b2_5x32, conv6_136_k3_b1_6x32
-                                                                                                                    conv3_8_k3_b1_7x64, conv3_40_k4s2_b2_6x64
-  thin_f2m_mfma_kernel: two x segments per row                                       thin_conv.hip:505, :516        conv3_8_k3_b1_7x64
-  thin_f2m_mfma_kernel: rows_per_wg 8, last group of 2 rows                          thin_conv.hip:820-821          conv3_8_k3_b33_250x32
-  thin_wrw_mfma_kernel<4,1>                                                          thin_conv.hip:867-868, :912    kb136_cs3_k3_b2_5x16
-  thin_wrw_mfma_kernel<4,2>                                                          thin_conv.hip:867-868, :913    kb128_cs3_k4_b1_6x48
-  thin_wrw_mfma_kernel<2,1>                                                          thin_conv.hip:867-868, :914    kb8_cs3_k3_b2_7x80, kb8_cs3_k3_b17_242x16
-  thin_wrw_mfma_kernel<2,2>                                                          thin_conv.hip:867-868, :915    kb72_cs6_k3_b1_5x16, kb8_cs6_k3_b9_230x16
-  thin_wrw_mfma_kernel<2,3>                                                          thin_conv.hip:867-868, :916    kb24_cs6_k4_b2_6x16
-  thin_wrw_mfma_kernel: ragged last row group at rows 4                              thin_conv.hip:295              kb136_cs3_k3_b2_5x16, kb128_cs3_k4_b1_6x48
-                                                                                                                    kb8_cs3_k3_b2_7x80, kb72_cs6_k3_b1_5x16
-                                                                                                                    kb24_cs6_k4_b2_6x16
-  thin_wrw_mfma_kernel: limit 1024 -> rows 8, last group of 2 rows                   thin_conv.hip:873-874          kb8_cs3_k3_b17_242x16
-  thin_wrw_mfma_kernel: limit 512 -> rows 8, last group of 6 rows                    thin_conv.hip:873-874          kb8_cs6_k3_b9_230x16
-  thin_wrw_mfma_kernel: two k tiles                                                  thin_conv.hip:871              kb136_cs3_k3_b2_5x16, kb72_cs6_k3_b1_5x16
-  thin_f2m_kernel<3>, flip 0 and 1                                                   thin_conv.hip:747, ops.py:874  f2m_b2_3_16_1x2, f2m_b1_3_48_2x1026
-  thin_f2m_kernel<6>, flip 0 and 1                                                   thin_conv.hip:747, ops.py:874  f2m_b1_6_32_3x514
-  thin_f2m_kernel: more than one block on x, y and z                                 thin_conv.hip:744              f2m_b1_6_32_3x514, f2m_b1_3_48_2x1026
-  thin_m2f_kernel<3>, flip 0 and 1                                                   thin_conv.hip:762, ops.py:874  m2f_b2_16_3_1x4, m2f_b1_455_3_2x8
-  thin_m2f_kernel<6>, flip 0 and 1                                                   thin_conv.hip:762, ops.py:874  m2f_b1_18_6_5x260, m2f_b1_227_6_3x4
-  thin_m2f_kernel: two blocks on x and y                                             thin_conv.hip:759              m2f_b1_18_6_5x260
-  thin_m2f_kernel: two blocks on z                                                   thin_conv.hip:759              m2f_b2_16_3_1x4
-  thin_m2f_kernel: the last I that fits the 48 KB of LDS                             thin_conv.hip:757-758          m2f_b1_455_3_2x8, m2f_b1_227_6_3x4
-  thin_wrw_kernel<3>                                                                 thin_conv.hip:799              wrw_b1_2_3_1x4, wrw_b1_2_3_3x260
-  thin_wrw_kernel<6>                                                                 thin_conv.hip:799              wrw_b2_4_6_65x8, wrw_b2_6_6_130x516
-  thin_wrw_kernel: a second row block (H > 64)                                       thin_conv.hip:796              wrw_b2_4_6_65x8, wrw_b2_6_6_130x516
-  thin_wrw_kernel: a second x block (W > 256)                                        thin_conv.hip:796              wrw_b1_2_3_3x260, wrw_b2_6_6_130x516
-  thin_wrw_kernel: more than one block on x, y and z                                 thin_conv.hip:796              wrw_b2_6_6_130x516
-  one_fwd_kernel<4> / one_wrw_kernel<4>: a 1 x 1 output                              thin_conv.hip:948, :957        one_b1_c1_4x4_k4p0
-  one_fwd_kernel<4>: exactly 256 groups, a second chunk of one channel, two samples  thin_conv.hip:927, :610        one_b2_c9_33x33_k4p1
-  one_fwd_kernel<3> / one_wrw_kernel<3>: pad 0, 224 groups                           thin_conv.hip:949, :958        one_b1_c8_34x30_k3p0
-  one_fwd_kernel<3>: Wo % 4 != 0                                                     thin_conv.hip:613, :650        one_b2_c7_6x9_k3p1, one_b1_c5_5x5_k3p2
-  one_fwd_kernel<3>: pad 2                                                           thin_conv.hip:606              one_b1_c5_5x5_k3p2
-  refused: few -> many at an odd width                          thin_conv.hip:742        f2m_odd_w
-  refused: many -> few one channel past the 48 KB of LDS        thin_conv.hip:757-758    m2f_i456_o3, m2f_i228_o6
-  refused: conv_to_one at 264 pixel groups                      thin_conv.hip:927        one_b1_c8_34x33_k4p1
+  variant                                                                            selected at                                        case ids
+  ---------------------------------------------------------------------------------  -------------------------------------------------  ----------------------------------------
+  thin_f2m_mfma_kernel<4,2>                                                          thin_f2m_mfma_plan (KS, MT)                        convT136_3_k3_b1_5x32
+  thin_f2m_mfma_kernel<4,3>                                                          thin_f2m_mfma_plan (KS, MT)                        convT128_3_k4s2_b2_5x32
+  thin_f2m_mfma_kernel<4,4>                                                          thin_f2m_mfma_plan (KS, MT)                        conv6_136_k3_b1_6x32
+  thin_f2m_mfma_kernel<2,2>                                                          thin_f2m_mfma_plan (KS, MT)                        conv3_8_k3_b1_7x64, conv3_8_k3_b33_250x32
+  thin_f2m_mfma_kernel<2,3>                                                          thin_f2m_mfma_plan (KS, MT)                        conv3_40_k4s2_b2_6x64
+  thin_f2m_mfma_kernel<2,4>                                                          thin_f2m_mfma_plan (KS, MT)                        conv6_72_k3_b1_9x32
+  thin_f2m_mfma_kernel<2,6>                                                          thin_f2m_mfma_plan (KS, MT)                        convT24_6_k4s2_b2_5x32
+  thin_f2m_mfma_kernel: a second o tile with 8 live rows                             thin_f2m_mfma_plan (otiles), thin_f2m_mfma_kernel  conv6_136_k3_b1_6x32, conv6_72_k3_b1_9x32
+                                                                                                                                        convT136_3_k3_b1_5x32
+  thin_f2m_mfma_kernel: ragged last row group, a wave idle                           thin_f2m_mfma_kernel                               convT128_3_k4s2_b2_5x32, conv6_136_k3_b1_6x32
+                                                                                                                                        conv3_8_k3_b1_7x64, conv3_40_k4s2_b2_6x64
+  thin_f2m_mfma_kernel: two x segments per row                                       thin_f2m_mfma_kernel                               conv3_8_k3_b1_7x64
+  thin_f2m_mfma_kernel: rows_per_wg 8, last group of 2 rows                          thin_f2m_mfma_plan (rows)                          conv3_8_k3_b33_250x32
+  thin_wrw_mfma_kernel<4,1>                                                          thin_wrw_mfma_plan (RT, MT)                        kb136_cs3_k3_b2_5x16
+  thin_wrw_mfma_kernel<4,2>                                                          thin_wrw_mfma_plan (RT, MT)                        kb128_cs3_k4_b1_6x48
+  thin_wrw_mfma_kernel<2,1>                                                          thin_wrw_mfma_plan (RT, MT)                        kb8_cs3_k3_b2_7x80, kb8_cs3_k3_b17_242x16
+  thin_wrw_mfma_kernel<2,2>                                                          thin_wrw_mfma_plan (RT, MT)                        kb72_cs6_k3_b1_5x16, kb8_cs6_k3_b9_230x16
+  thin_wrw_mfma_kernel<2,3>                                                          thin_wrw_mfma_plan (RT, MT)                        kb24_cs6_k4_b2_6x16
+  thin_wrw_mfma_kernel: ragged last row group at rows 4                              thin_wrw_mfma_kernel                               kb136_cs3_k3_b2_5x16, kb128_cs3_k4_b1_6x48
+                                                                                                                                        kb8_cs3_k3_b2_7x80, kb72_cs6_k3_b1_5x16
+                                                                                                                                        kb24_cs6_k4_b2_6x16
+  thin_wrw_mfma_kernel: limit 1024 -> rows 8, last group of 2 rows                   thin_wrw_mfma_plan (rows)                          kb8_cs3_k3_b17_242x16
+  thin_wrw_mfma_kernel: limit 512 -> rows 8, last group of 6 rows                    thin_wrw_mfma_plan (rows)                          kb8_cs6_k3_b9_230x16
+  thin_wrw_mfma_kernel: two k tiles                                                  thin_wrw_mfma_plan (ktiles)                        kb136_cs3_k3_b2_5x16, kb72_cs6_k3_b1_5x16
+  thin_f2m_kernel<3>, flip 0 and 1                                                   thin_f2m_plan (I), ops.conv3x3_thin                f2m_b2_3_16_1x2, f2m_b1_3_48_2x1026
+  thin_f2m_kernel<6>, flip 0 and 1                                                   thin_f2m_plan (I), ops.conv3x3_thin                f2m_b1_6_32_3x514
+  thin_f2m_kernel: more than one block on x, y and z                                 thin_f2m_plan (grid)                               f2m_b1_6_32_3x514, f2m_b1_3_48_2x1026
+  thin_m2f_kernel<3>, flip 0 and 1                                                   thin_m2f_plan (O), ops.conv3x3_thin                m2f_b2_16_3_1x4, m2f_b1_455_3_2x8
+  thin_m2f_kernel<6>, flip 0 and 1                                                   thin_m2f_plan (O), ops.conv3x3_thin                m2f_b1_18_6_5x260, m2f_b1_227_6_3x4
+  thin_m2f_kernel: two blocks on x and y                                             thin_m2f_plan (grid)                               m2f_b1_18_6_5x260
+  thin_m2f_kernel: two blocks on z                                                   thin_m2f_plan (grid)                               m2f_b2_16_3_1x4
+  thin_m2f_kernel: the last I that fits the 48 KB of LDS                             thin_m2f_plan (lds_bytes)                          m2f_b1_455_3_2x8, m2f_b1_227_6_3x4
+  thin_wrw_kernel<3>                                                                 thin_wrw_plan (Cs)                                 wrw_b1_2_3_1x4, wrw_b1_2_3_3x260
+  thin_wrw_kernel<6>                                                                 thin_wrw_plan (Cs)                                 wrw_b2_4_6_65x8, wrw_b2_6_6_130x516
+  thin_wrw_kernel: a second row block (H > 64)                                       thin_wrw_plan (grid)                               wrw_b2_4_6_65x8, wrw_b2_6_6_130x516
+  thin_wrw_kernel: a second x block (W > 256)                                        thin_wrw_plan (grid)                               wrw_b1_2_3_3x260, wrw_b2_6_6_130x516
+  thin_wrw_kernel: more than one block on x, y and z                                 thin_wrw_plan (grid)                               wrw_b2_6_6_130x516
+  one_fwd_kernel<4> / one_wrw_kernel<4>: a 1 x 1 output                              to_one_plan (K)                                    one_b1_c1_4x4_k4p0
+  one_fwd_kernel<4>: exactly 256 groups, a second chunk of one channel, two samples  to_one_plan, one_fwd_kernel                        one_b2_c9_33x33_k4p1
+  one_fwd_kernel<3> / one_wrw_kernel<3>: pad 0, 224 groups                           to_one_plan (K)                                    one_b1_c8_34x30_k3p0
+  one_fwd_kernel<3>: Wo % 4 != 0                                                     one_fwd_kernel                                     one_b2_c7_6x9_k3p1, one_b1_c5_5x5_k3p2
+  one_fwd_kernel<3>: pad 2                                                           one_fwd_kernel                                     one_b1_c5_5x5_k3p2
+  refused: few -> many at an odd width                          thin_f2m_plan            f2m_odd_w
+  refused: many -> few one channel past the 48 KB of LDS        thin_m2f_plan            m2f_i456_o3, m2f_i228_o6
+  refused: conv_to_one at 264 pixel groups                      to_one_plan              one_b1_c8_34x33_k4p1
 
 Two data regimes per case, both against fp64:
 

@@ -2,17 +2,17 @@
 
 A plain module (like bf16_conv_plan.py, guarded.py).  tests/test_thin_conv_plan.py ties it to the built library through the three
 workspace queries and `ipsr_conv_thin_f2m_mfma_supported`, and proves that the case tables below reach every variant;
-tests/test_gpu_thin_variants.py runs the tables.  Each function names the lines of thin_conv.hip it mirrors; integer arithmetic is
+tests/test_gpu_thin_variants.py runs the tables.  Each function names the plan function of thin_conv.hip it mirrors; integer arithmetic is
 C's (all operands non-negative, so `//` is the same division).
 
 A plan is a dict, `None` = the launcher refuses the shape (IPSR_ERR_UNSUPPORTED, workspace query 0).  Pointer alignment and the
 65535 limits of a grid axis are not restated: no case comes near them.
 """
 
-THIN_OC, THIN_CB, THIN_ROWS = 16, 2, 64                   # thin_conv.hip:19-21
-ONE_CCH = 8                                               # :599
-LDS_M2F = 48 * 1024                                       # :758
-LDS_ONE = 64 * 1024                                       # :945, :956
+THIN_OC, THIN_CB, THIN_ROWS = 16, 2, 64                   # the constants of thin_conv.hip
+ONE_CCH = 8
+LDS_M2F = 48 * 1024                                       # thin_m2f_plan
+LDS_ONE = 64 * 1024                                       # ONE_LDS_MAX (to_one_plan)
 
 
 def align_up(x, a):
@@ -32,7 +32,7 @@ def _row_groups(n, rows):
 
 
 def thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride):
-    """:813-824 (`thin_f2m_mfma_plan`) and the grid of :844."""
+    """`thin_f2m_mfma_plan`."""
     k3, k4 = k == 3 and stride == 1, k == 4 and stride == 2
     if B < 1 or O < 1 or Ho < 1 or Cs not in (3, 6) or not (k3 or k4) or Wo % 32 != 0 or O % 8 != 0:
         return None
@@ -48,7 +48,7 @@ def thin_f2m_mfma_plan(B, Cs, O, Ho, Wo, k, stride):
 
 
 def thin_wrw_mfma_plan(B, Kb, Cs, Hb, Wb, k, stride):
-    """:862-886 (`thin_wrw_mfma_plan`, `ipsr_conv_thin_wrw_mfma_workspace_bytes`)."""
+    """`thin_wrw_mfma_plan`."""
     k3, k4 = k == 3 and stride == 1, k == 4 and stride == 2
     if B < 1 or Kb < 1 or Hb < 1 or Cs not in (3, 6) or not (k3 or k4) or Wb % 16 != 0 or Wb < 16:
         return None
@@ -71,17 +71,17 @@ def thin_wrw_mfma_ws(B, Kb, Cs, Hb, Wb, k, stride):
 
 
 def thin_io_plan(op, B, I, O, H, W, bias=False, relu=False):
-    """ipsr_conv3x3_thin_io, :739-766: op 0 few -> many (I in {3, 6}), op 1 many -> few (O in {3, 6})."""
+    """ipsr_conv3x3_thin_io: op 0 `thin_f2m_plan`, few -> many (I in {3, 6}), op 1 `thin_m2f_plan` and the entry's refusal of an epilogue, many -> few (O in {3, 6})."""
     if B < 1 or I < 1 or O < 1 or H < 1 or W < 1:
         return None
     if op == 0:
-        if O % THIN_OC != 0 or I not in (3, 6) or W % 2 != 0:                            # :740, :742
+        if O % THIN_OC != 0 or I not in (3, 6) or W % 2 != 0:
             return None
         return dict(kernel="f2m", T=I, grid=(cdiv(W, 512), H, B * (O // THIN_OC)), lds=THIN_OC * I * 9 * 4)
-    if bias or relu or O not in (3, 6) or W % 4 != 0:                                    # :753-754
+    if bias or relu or O not in (3, 6) or W % 4 != 0:
         return None
     lds = I * O * 9 * 4
-    if lds > LDS_M2F:                                                                    # :758
+    if lds > LDS_M2F:
         return None
     return dict(kernel="m2f", T=O, grid=(cdiv(W, 256), cdiv(H, 4), B), lds=lds)
 
@@ -94,7 +94,7 @@ def thin_module_pass(op, Cin, Cout):
 
 
 def thin_wrw_plan(B, Cb, Cs, H, W):
-    """:776-781, :796."""
+    """`thin_wrw_plan`."""
     if B < 1 or Cb < 1 or H < 1 or W < 1 or Cs not in (3, 6) or Cb % THIN_CB != 0 or W % 4 != 0:
         return None
     grid = (cdiv(W, 256), cdiv(H, THIN_ROWS), B * (Cb // THIN_CB))
@@ -107,7 +107,7 @@ def thin_wrw_ws(B, Cb, Cs, H, W):
 
 
 def to_one_plan(B, C, H, W, K, pad):
-    """:924-929 and the LDS sizes of :944 / :955 (a plan whose `lds_fwd` / `lds_wrw` exceeds 64 KB is refused at the launch)."""
+    """`to_one_plan` with the LDS sizes of both operations (a plan whose `lds_fwd` / `lds_wrw` exceeds 64 KB is refused at the launch)."""
     Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
     if B < 1 or C < 1 or pad < 0 or Ho < 1 or Wo < 1 or K not in (3, 4) or Ho * cdiv(Wo, 4) > 256:
         return None
@@ -228,7 +228,7 @@ def check_case(cid):
     return got
 
 
-# ---- the variant table: (variant, selecting lines of thin_conv.hip / ops.py, predicate on a plan, case ids) ----------------------------
+# ---- the variant table: (variant, the plan field of thin_conv.hip or the kernel that selects it, predicate on a plan, case ids) ----------------------------
 def _fm(MT, KS):
     return lambda p: p["kernel"] == "f2m_mfma" and (p["MT"], p["KS"]) == (MT, KS)
 
@@ -238,54 +238,54 @@ def _wm(MT, RT):
 
 
 VARIANTS = (
-    ("thin_f2m_mfma_kernel<4,2>", "thin_conv.hip:817-818, :852", _fm(4, 2), ("convT136_3_k3_b1_5x32",)),
-    ("thin_f2m_mfma_kernel<4,3>", "thin_conv.hip:817-818, :852", _fm(4, 3), ("convT128_3_k4s2_b2_5x32",)),
-    ("thin_f2m_mfma_kernel<4,4>", "thin_conv.hip:817-818, :852", _fm(4, 4), ("conv6_136_k3_b1_6x32",)),
-    ("thin_f2m_mfma_kernel<2,2>", "thin_conv.hip:817-818, :854", _fm(2, 2), ("conv3_8_k3_b1_7x64", "conv3_8_k3_b33_250x32")),
-    ("thin_f2m_mfma_kernel<2,3>", "thin_conv.hip:817-818, :854", _fm(2, 3), ("conv3_40_k4s2_b2_6x64",)),
-    ("thin_f2m_mfma_kernel<2,4>", "thin_conv.hip:817-818, :854", _fm(2, 4), ("conv6_72_k3_b1_9x32",)),
-    ("thin_f2m_mfma_kernel<2,6>", "thin_conv.hip:817-818, :854", _fm(2, 6), ("convT24_6_k4s2_b2_5x32",)),
-    ("thin_f2m_mfma_kernel: a second o tile with 8 live rows", "thin_conv.hip:819, :468, :575", lambda p: p["kernel"] == "f2m_mfma" and p["otiles"] == 2 and p["live_rows_last_tile"] == 8,
+    ("thin_f2m_mfma_kernel<4,2>", "thin_f2m_mfma_plan (KS, MT)", _fm(4, 2), ("convT136_3_k3_b1_5x32",)),
+    ("thin_f2m_mfma_kernel<4,3>", "thin_f2m_mfma_plan (KS, MT)", _fm(4, 3), ("convT128_3_k4s2_b2_5x32",)),
+    ("thin_f2m_mfma_kernel<4,4>", "thin_f2m_mfma_plan (KS, MT)", _fm(4, 4), ("conv6_136_k3_b1_6x32",)),
+    ("thin_f2m_mfma_kernel<2,2>", "thin_f2m_mfma_plan (KS, MT)", _fm(2, 2), ("conv3_8_k3_b1_7x64", "conv3_8_k3_b33_250x32")),
+    ("thin_f2m_mfma_kernel<2,3>", "thin_f2m_mfma_plan (KS, MT)", _fm(2, 3), ("conv3_40_k4s2_b2_6x64",)),
+    ("thin_f2m_mfma_kernel<2,4>", "thin_f2m_mfma_plan (KS, MT)", _fm(2, 4), ("conv6_72_k3_b1_9x32",)),
+    ("thin_f2m_mfma_kernel<2,6>", "thin_f2m_mfma_plan (KS, MT)", _fm(2, 6), ("convT24_6_k4s2_b2_5x32",)),
+    ("thin_f2m_mfma_kernel: a second o tile with 8 live rows", "thin_f2m_mfma_plan (otiles), thin_f2m_mfma_kernel", lambda p: p["kernel"] == "f2m_mfma" and p["otiles"] == 2 and p["live_rows_last_tile"] == 8,
      ("conv6_136_k3_b1_6x32", "conv6_72_k3_b1_9x32", "convT136_3_k3_b1_5x32")),
-    ("thin_f2m_mfma_kernel: ragged last row group, a wave idle", "thin_conv.hip:508", lambda p: p["kernel"] == "f2m_mfma" and p["ragged"] and p["idle_waves"] >= 1,
+    ("thin_f2m_mfma_kernel: ragged last row group, a wave idle", "thin_f2m_mfma_kernel", lambda p: p["kernel"] == "f2m_mfma" and p["ragged"] and p["idle_waves"] >= 1,
      ("convT128_3_k4s2_b2_5x32", "conv6_136_k3_b1_6x32", "conv3_8_k3_b1_7x64", "conv3_40_k4s2_b2_6x64")),
-    ("thin_f2m_mfma_kernel: two x segments per row", "thin_conv.hip:505, :516", lambda p: p["kernel"] == "f2m_mfma" and p["xsegs"] == 2, ("conv3_8_k3_b1_7x64",)),
-    ("thin_f2m_mfma_kernel: rows_per_wg 8, last group of 2 rows", "thin_conv.hip:820-821", lambda p: p["kernel"] == "f2m_mfma" and p["rows"] == 8 and p["last_rows"] == 2,
+    ("thin_f2m_mfma_kernel: two x segments per row", "thin_f2m_mfma_kernel", lambda p: p["kernel"] == "f2m_mfma" and p["xsegs"] == 2, ("conv3_8_k3_b1_7x64",)),
+    ("thin_f2m_mfma_kernel: rows_per_wg 8, last group of 2 rows", "thin_f2m_mfma_plan (rows)", lambda p: p["kernel"] == "f2m_mfma" and p["rows"] == 8 and p["last_rows"] == 2,
      ("conv3_8_k3_b33_250x32",)),
-    ("thin_wrw_mfma_kernel<4,1>", "thin_conv.hip:867-868, :912", _wm(4, 1), ("kb136_cs3_k3_b2_5x16",)),
-    ("thin_wrw_mfma_kernel<4,2>", "thin_conv.hip:867-868, :913", _wm(4, 2), ("kb128_cs3_k4_b1_6x48",)),
-    ("thin_wrw_mfma_kernel<2,1>", "thin_conv.hip:867-868, :914", _wm(2, 1), ("kb8_cs3_k3_b2_7x80", "kb8_cs3_k3_b17_242x16")),
-    ("thin_wrw_mfma_kernel<2,2>", "thin_conv.hip:867-868, :915", _wm(2, 2), ("kb72_cs6_k3_b1_5x16", "kb8_cs6_k3_b9_230x16")),
-    ("thin_wrw_mfma_kernel<2,3>", "thin_conv.hip:867-868, :916", _wm(2, 3), ("kb24_cs6_k4_b2_6x16",)),
-    ("thin_wrw_mfma_kernel: ragged last row group at rows 4", "thin_conv.hip:295", lambda p: p["kernel"] == "wrw_mfma" and p["rows"] == 4 and p["ragged"],
+    ("thin_wrw_mfma_kernel<4,1>", "thin_wrw_mfma_plan (RT, MT)", _wm(4, 1), ("kb136_cs3_k3_b2_5x16",)),
+    ("thin_wrw_mfma_kernel<4,2>", "thin_wrw_mfma_plan (RT, MT)", _wm(4, 2), ("kb128_cs3_k4_b1_6x48",)),
+    ("thin_wrw_mfma_kernel<2,1>", "thin_wrw_mfma_plan (RT, MT)", _wm(2, 1), ("kb8_cs3_k3_b2_7x80", "kb8_cs3_k3_b17_242x16")),
+    ("thin_wrw_mfma_kernel<2,2>", "thin_wrw_mfma_plan (RT, MT)", _wm(2, 2), ("kb72_cs6_k3_b1_5x16", "kb8_cs6_k3_b9_230x16")),
+    ("thin_wrw_mfma_kernel<2,3>", "thin_wrw_mfma_plan (RT, MT)", _wm(2, 3), ("kb24_cs6_k4_b2_6x16",)),
+    ("thin_wrw_mfma_kernel: ragged last row group at rows 4", "thin_wrw_mfma_kernel", lambda p: p["kernel"] == "wrw_mfma" and p["rows"] == 4 and p["ragged"],
      ("kb136_cs3_k3_b2_5x16", "kb128_cs3_k4_b1_6x48", "kb8_cs3_k3_b2_7x80", "kb72_cs6_k3_b1_5x16", "kb24_cs6_k4_b2_6x16")),
-    ("thin_wrw_mfma_kernel: limit 1024 -> rows 8, last group of 2 rows", "thin_conv.hip:873-874", lambda p: p["kernel"] == "wrw_mfma" and (p["limit"], p["rows"], p["last_rows"]) == (1024, 8, 2),
+    ("thin_wrw_mfma_kernel: limit 1024 -> rows 8, last group of 2 rows", "thin_wrw_mfma_plan (rows)", lambda p: p["kernel"] == "wrw_mfma" and (p["limit"], p["rows"], p["last_rows"]) == (1024, 8, 2),
      ("kb8_cs3_k3_b17_242x16",)),
-    ("thin_wrw_mfma_kernel: limit 512 -> rows 8, last group of 6 rows", "thin_conv.hip:873-874", lambda p: p["kernel"] == "wrw_mfma" and (p["limit"], p["rows"], p["last_rows"]) == (512, 8, 6),
+    ("thin_wrw_mfma_kernel: limit 512 -> rows 8, last group of 6 rows", "thin_wrw_mfma_plan (rows)", lambda p: p["kernel"] == "wrw_mfma" and (p["limit"], p["rows"], p["last_rows"]) == (512, 8, 6),
      ("kb8_cs6_k3_b9_230x16",)),
-    ("thin_wrw_mfma_kernel: two k tiles", "thin_conv.hip:871", lambda p: p["kernel"] == "wrw_mfma" and p["ktiles"] == 2, ("kb136_cs3_k3_b2_5x16", "kb72_cs6_k3_b1_5x16")),
-    ("thin_f2m_kernel<3>, flip 0 and 1", "thin_conv.hip:747, ops.py:874", lambda p: p["kernel"] == "f2m" and p["T"] == 3, ("f2m_b2_3_16_1x2", "f2m_b1_3_48_2x1026")),
-    ("thin_f2m_kernel<6>, flip 0 and 1", "thin_conv.hip:747, ops.py:874", lambda p: p["kernel"] == "f2m" and p["T"] == 6, ("f2m_b1_6_32_3x514",)),
-    ("thin_f2m_kernel: more than one block on x, y and z", "thin_conv.hip:744", lambda p: p["kernel"] == "f2m" and min(p["grid"]) >= 2,
+    ("thin_wrw_mfma_kernel: two k tiles", "thin_wrw_mfma_plan (ktiles)", lambda p: p["kernel"] == "wrw_mfma" and p["ktiles"] == 2, ("kb136_cs3_k3_b2_5x16", "kb72_cs6_k3_b1_5x16")),
+    ("thin_f2m_kernel<3>, flip 0 and 1", "thin_f2m_plan (I), ops.conv3x3_thin", lambda p: p["kernel"] == "f2m" and p["T"] == 3, ("f2m_b2_3_16_1x2", "f2m_b1_3_48_2x1026")),
+    ("thin_f2m_kernel<6>, flip 0 and 1", "thin_f2m_plan (I), ops.conv3x3_thin", lambda p: p["kernel"] == "f2m" and p["T"] == 6, ("f2m_b1_6_32_3x514",)),
+    ("thin_f2m_kernel: more than one block on x, y and z", "thin_f2m_plan (grid)", lambda p: p["kernel"] == "f2m" and min(p["grid"]) >= 2,
      ("f2m_b1_6_32_3x514", "f2m_b1_3_48_2x1026")),
-    ("thin_m2f_kernel<3>, flip 0 and 1", "thin_conv.hip:762, ops.py:874", lambda p: p["kernel"] == "m2f" and p["T"] == 3, ("m2f_b2_16_3_1x4", "m2f_b1_455_3_2x8")),
-    ("thin_m2f_kernel<6>, flip 0 and 1", "thin_conv.hip:762, ops.py:874", lambda p: p["kernel"] == "m2f" and p["T"] == 6, ("m2f_b1_18_6_5x260", "m2f_b1_227_6_3x4")),
-    ("thin_m2f_kernel: two blocks on x and y", "thin_conv.hip:759", lambda p: p["kernel"] == "m2f" and p["grid"][0] >= 2 and p["grid"][1] >= 2, ("m2f_b1_18_6_5x260",)),
-    ("thin_m2f_kernel: two blocks on z", "thin_conv.hip:759", lambda p: p["kernel"] == "m2f" and p["grid"][2] >= 2, ("m2f_b2_16_3_1x4",)),
-    ("thin_m2f_kernel: the last I that fits the 48 KB of LDS", "thin_conv.hip:757-758", lambda p: p["kernel"] == "m2f" and LDS_M2F - p["T"] * 36 < p["lds"] <= LDS_M2F,
+    ("thin_m2f_kernel<3>, flip 0 and 1", "thin_m2f_plan (O), ops.conv3x3_thin", lambda p: p["kernel"] == "m2f" and p["T"] == 3, ("m2f_b2_16_3_1x4", "m2f_b1_455_3_2x8")),
+    ("thin_m2f_kernel<6>, flip 0 and 1", "thin_m2f_plan (O), ops.conv3x3_thin", lambda p: p["kernel"] == "m2f" and p["T"] == 6, ("m2f_b1_18_6_5x260", "m2f_b1_227_6_3x4")),
+    ("thin_m2f_kernel: two blocks on x and y", "thin_m2f_plan (grid)", lambda p: p["kernel"] == "m2f" and p["grid"][0] >= 2 and p["grid"][1] >= 2, ("m2f_b1_18_6_5x260",)),
+    ("thin_m2f_kernel: two blocks on z", "thin_m2f_plan (grid)", lambda p: p["kernel"] == "m2f" and p["grid"][2] >= 2, ("m2f_b2_16_3_1x4",)),
+    ("thin_m2f_kernel: the last I that fits the 48 KB of LDS", "thin_m2f_plan (lds_bytes)", lambda p: p["kernel"] == "m2f" and LDS_M2F - p["T"] * 36 < p["lds"] <= LDS_M2F,
      ("m2f_b1_455_3_2x8", "m2f_b1_227_6_3x4")),
-    ("thin_wrw_kernel<3>", "thin_conv.hip:799", lambda p: p["kernel"] == "wrw" and p["T"] == 3, ("wrw_b1_2_3_1x4", "wrw_b1_2_3_3x260")),
-    ("thin_wrw_kernel<6>", "thin_conv.hip:799", lambda p: p["kernel"] == "wrw" and p["T"] == 6, ("wrw_b2_4_6_65x8", "wrw_b2_6_6_130x516")),
-    ("thin_wrw_kernel: a second row block (H > 64)", "thin_conv.hip:796", lambda p: p["kernel"] == "wrw" and p["grid"][1] >= 2,
+    ("thin_wrw_kernel<3>", "thin_wrw_plan (Cs)", lambda p: p["kernel"] == "wrw" and p["T"] == 3, ("wrw_b1_2_3_1x4", "wrw_b1_2_3_3x260")),
+    ("thin_wrw_kernel<6>", "thin_wrw_plan (Cs)", lambda p: p["kernel"] == "wrw" and p["T"] == 6, ("wrw_b2_4_6_65x8", "wrw_b2_6_6_130x516")),
+    ("thin_wrw_kernel: a second row block (H > 64)", "thin_wrw_plan (grid)", lambda p: p["kernel"] == "wrw" and p["grid"][1] >= 2,
      ("wrw_b2_4_6_65x8", "wrw_b2_6_6_130x516")),
-    ("thin_wrw_kernel: a second x block (W > 256)", "thin_conv.hip:796", lambda p: p["kernel"] == "wrw" and p["grid"][0] >= 2,
+    ("thin_wrw_kernel: a second x block (W > 256)", "thin_wrw_plan (grid)", lambda p: p["kernel"] == "wrw" and p["grid"][0] >= 2,
      ("wrw_b1_2_3_3x260", "wrw_b2_6_6_130x516")),
-    ("thin_wrw_kernel: more than one block on x, y and z", "thin_conv.hip:796", lambda p: p["kernel"] == "wrw" and min(p["grid"]) >= 3,
+    ("thin_wrw_kernel: more than one block on x, y and z", "thin_wrw_plan (grid)", lambda p: p["kernel"] == "wrw" and min(p["grid"]) >= 3,
      ("wrw_b2_6_6_130x516",)),
-    ("one_fwd_kernel<4> / one_wrw_kernel<4>: a 1 x 1 output", "thin_conv.hip:948, :957", lambda p: p["kernel"] == "one" and p["K"] == 4 and p["groups"] == 1, ("one_b1_c1_4x4_k4p0",)),
-    ("one_fwd_kernel<4>: exactly 256 groups, a second chunk of one channel, two samples", "thin_conv.hip:927, :610", lambda p: p["kernel"] == "one" and p["K"] == 4 and p["groups"] == 256 and p["last_chunk"] == 1 and p["grid"] == (2, 2),
+    ("one_fwd_kernel<4> / one_wrw_kernel<4>: a 1 x 1 output", "to_one_plan (K)", lambda p: p["kernel"] == "one" and p["K"] == 4 and p["groups"] == 1, ("one_b1_c1_4x4_k4p0",)),
+    ("one_fwd_kernel<4>: exactly 256 groups, a second chunk of one channel, two samples", "to_one_plan, one_fwd_kernel", lambda p: p["kernel"] == "one" and p["K"] == 4 and p["groups"] == 256 and p["last_chunk"] == 1 and p["grid"] == (2, 2),
      ("one_b2_c9_33x33_k4p1",)),
-    ("one_fwd_kernel<3> / one_wrw_kernel<3>: pad 0, 224 groups", "thin_conv.hip:949, :958", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["pad"] == 0 and p["groups"] == 224, ("one_b1_c8_34x30_k3p0",)),
-    ("one_fwd_kernel<3>: Wo % 4 != 0", "thin_conv.hip:613, :650", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["Wo"] % 4 != 0 and p["Wo"] > 4, ("one_b2_c7_6x9_k3p1", "one_b1_c5_5x5_k3p2")),
-    ("one_fwd_kernel<3>: pad 2", "thin_conv.hip:606", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["pad"] == 2, ("one_b1_c5_5x5_k3p2",)),
+    ("one_fwd_kernel<3> / one_wrw_kernel<3>: pad 0, 224 groups", "to_one_plan (K)", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["pad"] == 0 and p["groups"] == 224, ("one_b1_c8_34x30_k3p0",)),
+    ("one_fwd_kernel<3>: Wo % 4 != 0", "one_fwd_kernel", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["Wo"] % 4 != 0 and p["Wo"] > 4, ("one_b2_c7_6x9_k3p1", "one_b1_c5_5x5_k3p2")),
+    ("one_fwd_kernel<3>: pad 2", "one_fwd_kernel", lambda p: p["kernel"] == "one" and p["K"] == 3 and p["pad"] == 2, ("one_b1_c5_5x5_k3p2",)),
 )
