@@ -21,6 +21,9 @@ SIGNATURES = {
     "ipsr_feat_mask_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ipsr_feat_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ipsr_index_prep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ipsr_mask_index_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ipsr_mask_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
     "ipsr_patch_normalize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ipsr_corr_argmax_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ipsr_corr_argmax": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -93,6 +96,10 @@ SIGNATURES = {
     "innercos_loss_fused": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "innercos_loss_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                        c_void_p, c_void_p, c_void_p]),
+    "innercos_loss_masks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "innercos_loss_backward_masks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_float,
+                                             c_void_p, c_void_p, c_void_p]),
     "ipsr_ragan_loss": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ipsr_l1_pair_loss_workspace_bytes": (c_size_t, [c_int]),
     "ipsr_l1_pair_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

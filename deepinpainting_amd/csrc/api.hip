@@ -236,6 +236,23 @@ int ipsr_index_prep(const uint8_t* feat, int h, int w, int patch, int stride, in
     return launch_index_prep(feat, h, w, patch, stride, mask_thred, flag, mask_point_idx, count, static_cast<hipStream_t>(stream));
 }
 
+size_t ipsr_mask_index_workspace_bytes(int R, int H, int W, int layers)
+{
+    if (R < 1 || H < 1 || W < 1 || layers < 0 || layers > 5) return 0;
+    return mask_index_plan(R, H, W, layers).ws_bytes;        // 0 as well where the mask is too small for `layers`
+}
+
+int ipsr_mask_index(const uint8_t* masks, int R, int H, int W, int layers, float threshold, int patch, int stride, int mask_thred,
+                    uint8_t* feat, int32_t* flag, int32_t* mask_point_idx, int32_t* counts, void* ws, size_t ws_bytes, void* stream)
+{
+    if (!masks || !flag || !mask_point_idx || !counts || (layers > 0 && !feat)) return fail(IPSR_ERR_INVALID, "ipsr_mask_index: null pointer");
+    if (R < 1 || layers < 0 || layers > 5 || H < 1 || W < 1 || (layers > 0 && (H < 2 || W < 2)))
+        return fail(IPSR_ERR_INVALID, "ipsr_mask_index: bad size R=%d H=%d W=%d layers=%d", R, H, W, layers);
+    if (patch < 1 || stride < 1) return fail(IPSR_ERR_INVALID, "ipsr_mask_index: bad geometry patch=%d stride=%d", patch, stride);
+    return launch_mask_index(masks, R, H, W, layers, threshold, patch, stride, mask_thred, feat, flag, mask_point_idx, counts, ws, ws_bytes,
+                             static_cast<hipStream_t>(stream));
+}
+
 int ipsr_patch_normalize(const float* x, int B, int C, int N, float* xn, float* inv, void* stream)
 {
     if (!x || !xn || !inv) return fail(IPSR_ERR_INVALID, "ipsr_patch_normalize: null pointer");
@@ -575,6 +592,27 @@ int innercos_loss_backward(const float* x, int B, int Cx, int Cuse, int N, const
     if (!x || !mask || !target || !grad_loss || !grad_x) return fail(IPSR_ERR_INVALID, "innercos_loss_backward: null pointer");
     if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_backward: bad size");
     return launch_innercos_backward(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
+}
+
+int innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target,
+                        float strength, float* loss, void* ws, size_t ws_bytes, void* stream)
+{
+    if (!x || !mask || !target || !loss || !ws) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: null pointer");
+    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: bad size B=%d Cx=%d Cuse=%d N=%d", B, Cx, Cuse, N);
+    if (mask_bstride != 0 && mask_bstride != N) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: mask_bstride %d is neither 0 nor N=%d", mask_bstride, N);
+    if (!aligned16(x) || !aligned16(target) || !aligned16(mask)) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: x/target/mask must be 16-byte aligned");
+    if (mask_bstride == 0) return launch_innercos_loss(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    return launch_innercos_loss_masks(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int innercos_loss_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target,
+                                 float strength, const float* grad_loss, float* grad_x, void* stream)
+{
+    if (!x || !mask || !target || !grad_loss || !grad_x) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: null pointer");
+    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: bad size");
+    if (mask_bstride != 0 && mask_bstride != N) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: mask_bstride %d is neither 0 nor N=%d", mask_bstride, N);
+    if (mask_bstride == 0) return launch_innercos_backward(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
+    return launch_innercos_backward_masks(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -124,6 +124,75 @@ __global__ void __launch_bounds__(256) innercos_backward_kernel(const float* __r
     }
 }
 
+// ---- one mask per sample: mask [B,N] ---------------------------------------------------------------------------------------------
+// The kernels above with the mask read inside the row loop, at the row of the sample that row belongs to: with two or more rows per
+// workgroup (B*Cuse > 4096) a workgroup's rows cross from one sample into the next.  Kernels of their own (no ticket path, which the
+// modules do not use), so that the shared-mask kernels stay as they were compiled.
+__global__ void __launch_bounds__(IC_THREADS) innercos_masks_kernel(const float* __restrict__ x, int Cx, int Cuse, int N, int rows, int rows_per_block,
+                                                                    const float* __restrict__ mask, const float* __restrict__ target, float strength,
+                                                                    double* __restrict__ partial)
+{
+    __shared__ double wsum[IC_THREADS / 64];
+    double acc = 0.0;
+    const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    if ((N & 3) == 0) {
+        const int n4 = N >> 2;
+        for (int i4 = threadIdx.x; i4 < n4; i4 += IC_THREADS) {
+            for (int row = r0; row < r1; ++row) {
+                const int b = row / Cuse, c = row - b * Cuse;                // uniform: scalar unit
+                const float4 mv = *reinterpret_cast<const float4*>(mask + (size_t)b * N + 4 * i4);
+                const float4 xv = *reinterpret_cast<const float4*>(x + ((size_t)b * Cx + c) * N + 4 * i4);
+                const float4 tv = *reinterpret_cast<const float4*>(target + (size_t)row * N + 4 * i4);
+                const float d0 = (xv.x * mv.x) * strength - tv.x;
+                const float d1 = (xv.y * mv.y) * strength - tv.y;
+                const float d2 = (xv.z * mv.z) * strength - tv.z;
+                const float d3 = (xv.w * mv.w) * strength - tv.w;
+                acc += (double)(d0 * d0);
+                acc += (double)(d1 * d1);
+                acc += (double)(d2 * d2);
+                acc += (double)(d3 * d3);
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < N; i += IC_THREADS) {
+            for (int row = r0; row < r1; ++row) {
+                const int b = row / Cuse, c = row - b * Cuse;
+                const float d = (x[((size_t)b * Cx + c) * N + i] * mask[(size_t)b * N + i]) * strength - target[(size_t)row * N + i];
+                acc += (double)(d * d);
+            }
+        }
+    }
+    acc = wave_sum_f64(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < IC_THREADS / 64; ++i) t += wsum[i];
+        partial[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(256) innercos_backward_masks_kernel(const float* __restrict__ x, int Cx, int Cuse, int N,
+                                                                      const float* __restrict__ mask, const float* __restrict__ target,
+                                                                      float strength, const float* __restrict__ grad_loss,
+                                                                      float two_over_count, size_t total_x, float* __restrict__ grad_x)
+{
+    const float scale = (*grad_loss) * two_over_count;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t per_x = (size_t)Cx * N;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_x; i += stride) {
+        const size_t b = i / per_x, rem = i - b * per_x;
+        const int c = (int)(rem / N), n = (int)(rem - (size_t)c * N);
+        float gv = 0.0f;
+        if (c < Cuse) {
+            const float m = mask[b * (size_t)N + n];
+            const float d = (x[i] * m) * strength - target[(b * Cuse + c) * (size_t)N + n];
+            gv = (d * scale) * (m * strength);
+        }
+        grad_x[i] = gv;
+    }
+}
+
 size_t innercos_ws_bytes(int B, int Cuse, int N)
 {
     (void)B; (void)Cuse; (void)N;
@@ -171,6 +240,35 @@ int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, con
     const float two_over_count = 2.0f / (float)((double)B * Cuse * N);
     innercos_backward_kernel<<<(int)nb, 256, 0, st>>>(x, Cx, Cuse, N, mask, target, strength, grad_loss, two_over_count, total_x, grad_x);
     return check_launch("innercos_backward_kernel");
+}
+
+// the grid, the tree and the fold of launch_innercos_loss
+int launch_innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
+                               float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st)
+{
+    if (ws_bytes < innercos_ws_bytes(B, Cuse, N)) return fail(IPSR_ERR_WORKSPACE, "innercos_loss_masks: workspace %zu < %zu", ws_bytes, innercos_ws_bytes(B, Cuse, N));
+    double* partial = reinterpret_cast<double*>(ws);
+    const int rows = B * Cuse;
+    const int rpb = (rows + IC_MAX_BLOCKS - 1) / IC_MAX_BLOCKS;
+    const int nblk = (rows + rpb - 1) / rpb;
+    profile_mark_start(st, 5);
+    innercos_masks_kernel<<<nblk, IC_THREADS, 0, st>>>(x, Cx, Cuse, N, rows, rpb, mask, target, strength, partial);
+    profile_mark_stop(st, 5, 2.0 * rows * (double)N * 4.0, 2.0 * rows * (double)N * 4.0);
+    if (int rc = check_launch("innercos_masks_kernel")) return rc;
+    innercos_final_kernel<<<1, 256, 0, st>>>(partial, nblk, 1.0 / ((double)rows * N), loss);
+    return check_launch("innercos_final_kernel");
+}
+
+int launch_innercos_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
+                                   const float* target, float strength, const float* grad_loss, float* grad_x,
+                                   hipStream_t st)
+{
+    const size_t total_x = (size_t)B * Cx * N;
+    size_t nb = (total_x + 255) / 256;
+    if (nb > 2048) nb = 2048;
+    const float two_over_count = 2.0f / (float)((double)B * Cuse * N);
+    innercos_backward_masks_kernel<<<(int)nb, 256, 0, st>>>(x, Cx, Cuse, N, mask, target, strength, grad_loss, two_over_count, total_x, grad_x);
+    return check_launch("innercos_backward_masks_kernel");
 }
 
 }  // namespace ipsr

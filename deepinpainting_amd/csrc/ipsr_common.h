@@ -172,6 +172,18 @@ int launch_feat_mask(const uint8_t* mask, int H, int W, int layers, float thresh
                      void* ws, size_t ws_bytes, hipStream_t st);
 int launch_index_prep(const uint8_t* feat, int h, int w, int patch, int stride, int mask_thred,
                       int32_t* flag, int32_t* mask_point_idx, int32_t* count, hipStream_t st);
+// both for R masks in one launch (layers == 0: the masks are feature masks already).  The plan: where a workgroup keeps the levels between
+// the mask and the feature mask
+struct MaskIndexPlan {
+    bool ok;               // false: the mask is too small for `layers` (the other fields are 0)
+    int h, w;              // the feature mask
+    bool in_lds;           // false: in the workgroup's slice of the workspace
+    size_t off_b, slice;   // the second buffer's offset in a slice, and a slice's bytes (= the dynamic LDS where in_lds)
+    size_t ws_bytes;
+};
+MaskIndexPlan mask_index_plan(int R, int H, int W, int layers);
+int launch_mask_index(const uint8_t* masks, int R, int H, int W, int layers, float threshold, int patch, int stride, int mask_thred,
+                      uint8_t* feat, int32_t* flag, int32_t* mask_point_idx, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st);
 // xT may be NULL (then the patch-major copy is not produced).
 // ldx / ldn: row strides of x / xn (0 = N); with ldn > N the pad columns of xn are zero-filled.
 int launch_patch_normalize(const float* x, int B, int C, int N, float* xn, float* xT, int Cp, float* inv,
@@ -284,5 +296,11 @@ int launch_innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, c
 int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
                              const float* target, float strength, const float* grad_loss, float* grad_x,
                              hipStream_t st);
+// mask [B,N], one row per sample (the shared mask stays with the launchers above)
+int launch_innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
+                               float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_innercos_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
+                                   const float* target, float strength, const float* grad_loss, float* grad_x,
+                                   hipStream_t st);
 
 }  // namespace ipsr

@@ -28,6 +28,12 @@ class _Ref(object):
 
 
 class IPSR_model(nn.Module):
+    # A/B switch (class-level, read here, by InnerCos / InnerCos2 and by util.cal_feat_mask_batch): a CUDA batch of per-sample masks goes
+    # through the batched entries — ONE ipsr_mask_index for feature masks + index, ONE innercos_loss_masks per tap.  False: one
+    # ipsr_feat_mask / ipsr_index_prep / innercos_loss call per sample, as before the batched entries existed (same results).  A shared
+    # mask ([1,1,H,W]) and CPU tensors never take the batched entries.
+    batched_masks = True
+
     def __init__(self, threshold, fixed_mask, shift_sz=1, stride=1, mask_thred=1, triple_weight=1):
         super(IPSR_model, self).__init__()
         self.threshold = threshold
@@ -45,6 +51,7 @@ class IPSR_model(nn.Module):
         self._index_shape = None
         self._flag32 = self._mpi32 = self._counts = None
         self._host_index = None
+        self._index_stash = None        # ((shift_sz, stride, mask_thred), flag, mpi, counts) of a set_mask that computed the index as well
         self._mask_src = None           # (tensor, version, layer_to_last, threshold) of the last set_mask: an unchanged mask keeps its index
         # capacity of the device-side index (columns of mask_point_idx handed to the kernels; everything the layer sizes by M —
         # compressed attention, backward CSR, LDS of the compress kernel — is sized by it):
@@ -64,8 +71,16 @@ class IPSR_model(nn.Module):
         if feat_mask is None and src is not None and src[0] is mask_global and src[1] == mask_global._version \
                 and src[2:] == (layer_to_last, threshold) and self.mask is not None:
             return self.mask                 # same mask tensor, not modified since: the feature mask and the index stand
+        self._index_stash = None
         if feat_mask is not None:
             mask = feat_mask
+        elif mask_global.size(0) > 1 and self.batched_masks and mask_global.is_cuda:
+            # per-sample masks: feature masks AND the index in one launch; _ensure_index adopts the index
+            from .. import ops
+            key = (int(self.shift_sz), int(self.stride), int(self.mask_thred))
+            feat, flag, mpi, counts = ops.mask_index(util.mask_rows(mask_global), int(layer_to_last), float(threshold), *key)
+            mask = feat[:, None]
+            self._index_stash = (key, flag, mpi, counts)
         elif mask_global.size(0) > 1:
             mask = util.cal_feat_mask_batch(mask_global, layer_to_last, threshold)
         else:
@@ -83,6 +98,9 @@ class IPSR_model(nn.Module):
     def _index_rows(self, masks):
         """masks [h,w] or [B,h,w] byte -> (flag32 [R,N], mpi32 [R,N] (-1 padded), counts [R] int32), R = 1 or B."""
         from .. import ops
+        if masks.dim() == 3 and self.batched_masks and masks.is_cuda:
+            return ops.mask_index(masks if masks.dtype == torch.uint8 else masks.to(torch.uint8), 0, 0.0,
+                                  int(self.shift_sz), int(self.stride), int(self.mask_thred))[1:]
         rows = [masks] if masks.dim() == 2 else list(masks)
         outs = [ops.index_prep(m if m.dtype == torch.uint8 else m.to(torch.uint8), int(self.shift_sz), int(self.stride), int(self.mask_thred))
                 for m in rows]
@@ -94,7 +112,12 @@ class IPSR_model(nn.Module):
         if self.cal_fixed_flag or self._index_shape != (self.h, self.w) or self._flag32 is None or self._flag32.device != input.device:
             assert self.mask is not None, 'set_mask() must be called before forward()'
             mask = self.mask if self.mask.device == input.device else self.mask.to(input.device)
-            flag32, mpi32, counts = self._index_rows(mask)
+            stash, self._index_stash = self._index_stash, None
+            if stash is not None and stash[0] == (int(self.shift_sz), int(self.stride), int(self.mask_thred)) \
+                    and stash[1].device == input.device and tuple(mask.shape[-2:]) == (self.h, self.w):
+                flag32, mpi32, counts = stash[1:]           # set_mask's own launch produced them
+            else:
+                flag32, mpi32, counts = self._index_rows(mask)
             n_win = (self.h - int(self.shift_sz) + 1) * (self.w - int(self.shift_sz) + 1)
             assert flag32.size(1) == n_win, 'mask %s does not match a %dx%d feature' % (tuple(self.mask.shape), self.h, self.w)
             cap = self.index_capacity

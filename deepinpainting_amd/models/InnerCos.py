@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..util import util
+from .IPSR_model import IPSR_model
 
 
 class _InnerCosLoss(torch.autograd.Function):
@@ -71,7 +72,10 @@ class InnerCos(nn.Module):
             cuse = in_data.size(1) if self._narrow is None else self._narrow
             self.bs, self.c = in_data.size(0), cuse
             self.former = in_data if self._narrow is None else in_data.narrow(1, 0, cuse)
-            if self.mask.dim() == 3:      # per-sample masks: equal-sized samples, so the batch mean is the mean of the per-sample means
+            if self.mask.dim() == 3 and IPSR_model.batched_masks and in_data.is_cuda:
+                # per-sample masks: ONE launch pair, the kernel reads row b of the mask for sample b
+                self.loss = _InnerCosLoss.apply(in_data, cuse, self.mask, self.target, float(self.strength))
+            elif self.mask.dim() == 3:    # the same by one call per sample: equal-sized samples, so the batch mean is the mean of the per-sample means
                 per = [_InnerCosLoss.apply(in_data[b:b + 1], cuse, self.mask[b], self.target[b:b + 1], float(self.strength))
                        for b in range(in_data.size(0))]
                 self.loss = torch.stack(per).mean()

@@ -92,6 +92,34 @@ def index_prep(feat_hw, patch, stride, mask_thred):
     return flag, mpi, cnt
 
 
+def mask_index(masks, layers, threshold, patch, stride, mask_thred):
+    """K1 + K2 for a batch of masks in ONE launch.  masks [R,H,W] (or [H,W]: R = 1) bool/uint8 -> (feat [R,h,w] u8, flag [R,N] i32,
+    mask_point_idx [R,N] i32 (row r: first counts[r] valid, -1 after them), counts [R] i32), every row what `feat_mask` followed by
+    `index_prep` gives for that mask.  layers == 0: `masks` are feature masks already, only the index part runs and feat is None."""
+    m = masks
+    if torch.is_tensor(m) and m.dtype == torch.bool:
+        m = m.to(torch.uint8)
+    m = _req(m, torch.uint8, "masks")
+    if m.dim() == 2:
+        m = m[None]
+    if m.dim() != 3:
+        raise RuntimeError("mask_index: masks must be [R,H,W] or [H,W], got %s" % (tuple(m.shape),))
+    R, H, W = m.shape
+    layers, patch, stride = int(layers), int(patch), int(stride)
+    h, w = feat_mask_out_dim(H, layers), feat_mask_out_dim(W, layers)
+    n = max((h - patch) // stride + 1, 0) * max((w - patch) // stride + 1, 0) if patch >= 1 and stride >= 1 else 0
+    feat = _empty((R, max(h, 0), max(w, 0)), dtype=torch.uint8, device=m.device) if layers > 0 else None
+    flag = _empty((R, n), dtype=torch.int32, device=m.device)
+    mpi = _empty((R, n), dtype=torch.int32, device=m.device)
+    cnt = _empty(R, dtype=torch.int32, device=m.device)
+    L = _lib.lib()
+    ws = _workspace(L.ipsr_mask_index_workspace_bytes(R, H, W, layers), m.device)
+    _lib.check(L.ipsr_mask_index(m.data_ptr(), R, H, W, layers, float(threshold), patch, stride, int(mask_thred),
+                                 feat.data_ptr() if feat is not None else None, flag.data_ptr(), mpi.data_ptr(), cnt.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream()), "ipsr_mask_index")
+    return feat, flag, mpi, cnt
+
+
 def patch_normalize(x_bcn):
     """K3.  x [B,C,N] -> (xn [B,C,N], inv [B,N])."""
     x = _req(x_bcn, torch.float32, "x")
@@ -1138,17 +1166,25 @@ _IC_TICKETS = {}
 
 
 def innercos_loss(x, cuse, mask_f32, target, strength, one_launch=False):
-    """K9.  x [B,Cx,h,w] (only the first `cuse` channels are read), target [B,cuse,h,w] -> loss [] fp32."""
+    """K9.  x [B,Cx,h,w] (only the first `cuse` channels are read), target [B,cuse,h,w] -> loss [] fp32.
+    mask_f32: N = h*w elements (one mask for the batch), or B*N ([B,h,w]: one mask per sample, the `_masks` entry)."""
     x = _req(x, torch.float32, "in_data")
     target = _req(target, torch.float32, "target")
     mask = _req(mask_f32, torch.float32, "mask")
     B, Cx = x.shape[0], x.shape[1]
     N = x.shape[2] * x.shape[3]
-    if tuple(target.shape) != (B, cuse, x.shape[2], x.shape[3]) or mask.numel() != N:
+    per_sample = B > 1 and mask.numel() == B * N
+    if tuple(target.shape) != (B, cuse, x.shape[2], x.shape[3]) or not (mask.numel() == N or per_sample):
         raise RuntimeError("InnerCos: target %s / mask %s do not match input %s" % (tuple(target.shape), tuple(mask.shape), tuple(x.shape)))
     loss = _empty((), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     ws = _workspace(L.innercos_workspace_bytes(B, cuse, N), x.device)
+    if per_sample:
+        if one_launch:
+            raise RuntimeError("InnerCos: the one-launch form takes one mask for the batch")
+        _lib.check(L.innercos_loss_masks(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), N, target.data_ptr(), float(strength),
+                                         loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "innercos_loss_masks")
+        return loss
     if one_launch:
         # the last workgroup folds the block partials.  Its arrival counter is a word of OUR memory, one per (device, stream) — the calls
         # of a stream are ordered, and every launch leaves the word zero — allocated (zeroed) once.  Measured SLOWER than two launches
@@ -1173,6 +1209,13 @@ def innercos_loss_backward(x, cuse, mask_f32, target, strength, grad_loss):
     B, Cx = x.shape[0], x.shape[1]
     N = x.shape[2] * x.shape[3]
     gx = _empty(x.shape, x.dtype, x.device)
+    if B > 1 and mask.numel() == B * N:              # one mask per sample
+        _lib.check(_lib.lib().innercos_loss_backward_masks(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), N, target.data_ptr(),
+                                                           float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
+                   "innercos_loss_backward_masks")
+        return gx
+    if mask.numel() != N:
+        raise RuntimeError("InnerCos: mask %s does not match input %s" % (tuple(mask.shape), tuple(x.shape)))
     _lib.check(_lib.lib().innercos_loss_backward(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(),
                                                  float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
                "innercos_loss_backward")

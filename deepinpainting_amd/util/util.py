@@ -20,9 +20,19 @@ def cal_feat_mask(inMask, conv_layers, threshold):
     return feat[None, None]
 
 
+def mask_rows(inMask):
+    """[B,1,H,W] (bool / 0-1 valued) -> [B,H,W] bool or byte, the rows as cal_feat_mask hands them to the kernel."""
+    m = inMask[:, 0]
+    return m if m.dtype in (torch.bool, torch.uint8) else m != 0
+
+
 def cal_feat_mask_batch(inMask, conv_layers, threshold):
-    """Per-sample masks (extension): cal_feat_mask of every [1,1,H,W] slice of a [B,1,H,W] mask -> [B,1,h,w] byte."""
+    """Per-sample masks (extension): cal_feat_mask of every [1,1,H,W] slice of a [B,1,H,W] mask -> [B,1,h,w] byte.
+    A CUDA batch is one launch (ops.mask_index; IPSR_model.batched_masks = False: one call per sample)."""
     assert inMask.dim() == 4, "mask must be 4 dimensions"
+    from ..models.IPSR_model import IPSR_model
+    if inMask.is_cuda and IPSR_model.batched_masks:
+        return ops.mask_index(mask_rows(inMask), int(conv_layers), float(threshold), 1, 1, 1)[0][:, None]
     return torch.cat([cal_feat_mask(inMask[b:b + 1], conv_layers, threshold) for b in range(inMask.size(0))], 0)
 
 

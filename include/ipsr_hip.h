@@ -62,6 +62,23 @@ int ipsr_index_prep(const uint8_t* feat, int h, int w, int patch, int stride, in
                     int32_t* flag /*[N]*/, int32_t* mask_point_idx /*[N]*/, int32_t* count /*[1]*/,
                     void* stream);
 
+/* ---- K1+K2  a batch of masks in one launch ---------------------------------------------------
+ * (extension: per-sample masks, see ipsr_forward_masks.)  masks [R,H,W] u8 (0/1) -> feat [R,h,w] u8,
+ * flag [R,N], mask_point_idx [R,N] (row r: first counts[r] entries valid, -1 after them), counts [R].
+ * Row r of every output is bit for bit what ipsr_feat_mask followed by ipsr_index_prep gives for
+ * mask r, with the same H, W, layers, patch, stride and mask_thred accepted.  ONE launch whatever R:
+ * a workgroup owns a mask from the first level to the -1 fill.  The levels in between stay in LDS
+ * where they fit (a 512x512 mask at 3 layers does) and go to the workgroup's slice of `ws` otherwise.
+ * layers == 0: `masks` already holds the feature masks [R,h,w] (H = h, W = w); only the index part
+ * runs and `feat` may be NULL.  Every output element is written by every call; the result does not
+ * depend on what `ws` holds.  `ws` is required (the query is never 0 for valid sizes). */
+size_t ipsr_mask_index_workspace_bytes(int R, int H, int W, int layers);
+int ipsr_mask_index(const uint8_t* masks /*[R,H,W] 0/1*/, int R, int H, int W, int layers, float threshold,
+                    int patch, int stride, int mask_thred,
+                    uint8_t* feat /*[R,h,w]; may be NULL when layers == 0*/,
+                    int32_t* flag /*[R,N]*/, int32_t* mask_point_idx /*[R,N], -1 past counts[r]*/, int32_t* counts /*[R]*/,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ---- K3  patch unfold + L2 normalisation ----------------------------------------------------
  * replaces NonparametricShift._extract_patches/_build (util/NonparametricShift.py:36-73):
  * inv[b][k] = 1/(||x[b,:,k]||_2 + 1e-8);  xn[b][c][k] = x[b][c][k] * inv[b][k]   (patch == 1). */
@@ -405,6 +422,16 @@ int innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, const fl
 int innercos_loss_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
                            const float* target, float strength, const float* grad_loss /*[1]*/,
                            float* grad_x /*[B,Cx,N]*/, void* stream);
+/* the same with one mask per sample (extension: per-sample masks).  mask_bstride: 0 = one mask [N] for the batch (these calls then ARE
+ * innercos_loss / innercos_loss_backward, bit for bit); N = mask [B,N], row b for sample b:
+ *     loss = sum_{b,c<Cuse,n} ((x[b,c,n]*mask[b,n])*strength - target)^2 / (B*Cuse*N)
+ * in the same fp32 terms, fp64 accumulation and fixed tree.  Any other mask_bstride: IPSR_ERR_INVALID.  Workspace: innercos_workspace_bytes. */
+int innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride,
+                        const float* target, float strength, float* loss /*[1]*/,
+                        void* ws, size_t ws_bytes, void* stream);
+int innercos_loss_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride,
+                                 const float* target, float strength, const float* grad_loss /*[1]*/,
+                                 float* grad_x /*[B,Cx,N]*/, void* stream);
 
 /* ---- loss heads: value and gradients in one launch (csrc/loss_head.hip) -----------------------------
  * The relativistic-average LSGAN loss of models/networks.py GANLoss, with s = sign * label:
