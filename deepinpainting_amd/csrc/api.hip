@@ -568,51 +568,54 @@ int ipsr_bias_act_backward_skip(const void* dy, const void* dy2, size_t dy2_batc
 
 size_t innercos_workspace_bytes(int B, int Cuse, int N) { return innercos_ws_bytes(B, Cuse, N); }
 
+// What the five InnerCos entries check alike, in the order they always had: null pointers (`a`, `b`: loss and workspace, or grad_loss and
+// grad_x), sizes, the mask row stride (0 from the entries that take one mask), and for the loss entries the alignment of their float4 loads.
+static int innercos_args(const char* who, bool loss_pass, const void* x, const void* mask, const void* target, const void* a, const void* b,
+                         int B, int Cx, int Cuse, int N, int mask_bstride)
+{
+    if (!x || !mask || !target || !a || !b) return fail(IPSR_ERR_INVALID, "%s: null pointer", who);
+    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1)
+        return loss_pass ? fail(IPSR_ERR_INVALID, "%s: bad size B=%d Cx=%d Cuse=%d N=%d", who, B, Cx, Cuse, N) : fail(IPSR_ERR_INVALID, "%s: bad size", who);
+    if (mask_bstride != 0 && mask_bstride != N) return fail(IPSR_ERR_INVALID, "%s: mask_bstride %d is neither 0 nor N=%d", who, mask_bstride, N);
+    if (loss_pass && (!aligned16(x) || !aligned16(target) || !aligned16(mask))) return fail(IPSR_ERR_INVALID, "%s: x/target/mask must be 16-byte aligned", who);
+    return IPSR_OK;
+}
+
 int innercos_loss(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
                   float strength, float* loss, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!x || !mask || !target || !loss || !ws) return fail(IPSR_ERR_INVALID, "innercos_loss: null pointer");
-    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss: bad size B=%d Cx=%d Cuse=%d N=%d", B, Cx, Cuse, N);
-    if (!aligned16(x) || !aligned16(target) || !aligned16(mask)) return fail(IPSR_ERR_INVALID, "innercos_loss: x/target/mask must be 16-byte aligned");
-    return launch_innercos_loss(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    if (int rc = innercos_args("innercos_loss", true, x, mask, target, loss, ws, B, Cx, Cuse, N, 0)) return rc;
+    return launch_innercos_loss(x, B, Cx, Cuse, N, mask, 0, target, strength, loss, ws, ws_bytes, nullptr, "innercos_loss", static_cast<hipStream_t>(stream));
 }
 
 int innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
                         float strength, float* loss, void* ws, size_t ws_bytes, unsigned* ticket, void* stream)
 {
-    if (!x || !mask || !target || !loss || !ws || !ticket) return fail(IPSR_ERR_INVALID, "innercos_loss_fused: null pointer");
-    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_fused: bad size B=%d Cx=%d Cuse=%d N=%d", B, Cx, Cuse, N);
-    if (!aligned16(x) || !aligned16(target) || !aligned16(mask)) return fail(IPSR_ERR_INVALID, "innercos_loss_fused: x/target/mask must be 16-byte aligned");
-    return launch_innercos_loss_fused(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, ticket, static_cast<hipStream_t>(stream));
+    if (!ticket) return fail(IPSR_ERR_INVALID, "innercos_loss_fused: null pointer");
+    if (int rc = innercos_args("innercos_loss_fused", true, x, mask, target, loss, ws, B, Cx, Cuse, N, 0)) return rc;
+    return launch_innercos_loss(x, B, Cx, Cuse, N, mask, 0, target, strength, loss, ws, ws_bytes, ticket, "innercos_loss", static_cast<hipStream_t>(stream));
 }
 
 int innercos_loss_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
                            float strength, const float* grad_loss, float* grad_x, void* stream)
 {
-    if (!x || !mask || !target || !grad_loss || !grad_x) return fail(IPSR_ERR_INVALID, "innercos_loss_backward: null pointer");
-    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_backward: bad size");
-    return launch_innercos_backward(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
+    if (int rc = innercos_args("innercos_loss_backward", false, x, mask, target, grad_loss, grad_x, B, Cx, Cuse, N, 0)) return rc;
+    return launch_innercos_backward(x, B, Cx, Cuse, N, mask, 0, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
 }
 
 int innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target,
                         float strength, float* loss, void* ws, size_t ws_bytes, void* stream)
 {
-    if (!x || !mask || !target || !loss || !ws) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: null pointer");
-    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: bad size B=%d Cx=%d Cuse=%d N=%d", B, Cx, Cuse, N);
-    if (mask_bstride != 0 && mask_bstride != N) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: mask_bstride %d is neither 0 nor N=%d", mask_bstride, N);
-    if (!aligned16(x) || !aligned16(target) || !aligned16(mask)) return fail(IPSR_ERR_INVALID, "innercos_loss_masks: x/target/mask must be 16-byte aligned");
-    if (mask_bstride == 0) return launch_innercos_loss(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, static_cast<hipStream_t>(stream));
-    return launch_innercos_loss_masks(x, B, Cx, Cuse, N, mask, target, strength, loss, ws, ws_bytes, static_cast<hipStream_t>(stream));
+    if (int rc = innercos_args("innercos_loss_masks", true, x, mask, target, loss, ws, B, Cx, Cuse, N, mask_bstride)) return rc;
+    return launch_innercos_loss(x, B, Cx, Cuse, N, mask, mask_bstride, target, strength, loss, ws, ws_bytes, nullptr,
+                                mask_bstride ? "innercos_loss_masks" : "innercos_loss", static_cast<hipStream_t>(stream));
 }
 
 int innercos_loss_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target,
                                  float strength, const float* grad_loss, float* grad_x, void* stream)
 {
-    if (!x || !mask || !target || !grad_loss || !grad_x) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: null pointer");
-    if (B < 1 || Cuse < 1 || Cx < Cuse || N < 1) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: bad size");
-    if (mask_bstride != 0 && mask_bstride != N) return fail(IPSR_ERR_INVALID, "innercos_loss_backward_masks: mask_bstride %d is neither 0 nor N=%d", mask_bstride, N);
-    if (mask_bstride == 0) return launch_innercos_backward(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
-    return launch_innercos_backward_masks(x, B, Cx, Cuse, N, mask, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
+    if (int rc = innercos_args("innercos_loss_backward_masks", false, x, mask, target, grad_loss, grad_x, B, Cx, Cuse, N, mask_bstride)) return rc;
+    return launch_innercos_backward(x, B, Cx, Cuse, N, mask, mask_bstride, target, strength, grad_loss, grad_x, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

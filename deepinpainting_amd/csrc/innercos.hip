@@ -12,7 +12,8 @@
 namespace ipsr {
 
 constexpr int IC_THREADS = 256;
-constexpr int IC_MAX_BLOCKS = 4096;
+constexpr int IC_MAX_BLOCKS = 4096;                       // workgroups of the streaming loss kernel, two launches
+constexpr int IC_FUSED_BLOCKS = 512;                      // ... with a ticket (one launch)
 
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
@@ -33,12 +34,17 @@ __global__ void __launch_bounds__(256) innercos_final_kernel(const double* __res
     if (threadIdx.x == 0) *loss = (float)(((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * inv_count);
 }
 
-// Round 4: a workgroup owns whole (sample, channel) rows — no 64-bit divisions per element, the mask float4 of a thread is loaded once.
+// Round 4: a workgroup owns whole (sample, channel) rows — no 64-bit divisions per element.  PER_SAMPLE says where the mask element is read,
+// the arithmetic is written once: false — mask [N], one for the batch, a thread's mask float4 is loaded once, before the row loop; true —
+// mask [B,N], loaded inside the row loop at the row of the sample that row belongs to (with two or more rows per workgroup, B*Cuse > 4096,
+// a workgroup's rows cross from one sample into the next).  The <false> instantiation compiles to the instructions of the kernel that had
+// no template parameter (profiles/innercos_unify_isa.txt).
 // ticket == nullptr (the shipped path): block partials, folded by innercos_final_kernel.  ticket != nullptr (innercos_loss_fused): the
 // LAST workgroup to finish (a word of caller memory, zero on entry, zero again on exit) folds them in the same launch.  Measured in the
 // training step at [8,512,32,32] (HIP events around the launch): two launches 8.9 + 5.8 us; ONE launch 19.1 us with 512 workgroups and
 // 70 us with 4096 — thousands of same-address atomics arrive at ~17 ns each, so the "last block" pattern that works for the norm
 // kernels' 8 arrivals per counter does not scale to one counter per launch.  The fused entry point stays (tested), the default is two.
+template <bool PER_SAMPLE>
 __global__ void __launch_bounds__(IC_THREADS) innercos_fused_kernel(const float* __restrict__ x, int Cx, int Cuse, int N, int rows, int rows_per_block,
                                                                     const float* __restrict__ mask, const float* __restrict__ target, float strength,
                                                                     double inv_count, double* __restrict__ partial, unsigned* __restrict__ ticket,
@@ -51,9 +57,11 @@ __global__ void __launch_bounds__(IC_THREADS) innercos_fused_kernel(const float*
     if ((N & 3) == 0) {
         const int n4 = N >> 2;
         for (int i4 = threadIdx.x; i4 < n4; i4 += IC_THREADS) {
-            const float4 mv = *reinterpret_cast<const float4*>(mask + 4 * i4);
+            float4 mv;
+            if constexpr (!PER_SAMPLE) mv = *reinterpret_cast<const float4*>(mask + 4 * i4);
             for (int row = r0; row < r1; ++row) {
                 const int b = row / Cuse, c = row - b * Cuse;                // uniform: scalar unit
+                if constexpr (PER_SAMPLE) mv = *reinterpret_cast<const float4*>(mask + (size_t)b * N + 4 * i4);
                 const float4 xv = *reinterpret_cast<const float4*>(x + ((size_t)b * Cx + c) * N + 4 * i4);
                 const float4 tv = *reinterpret_cast<const float4*>(target + (size_t)row * N + 4 * i4);
                 const float d0 = (xv.x * mv.x) * strength - tv.x;
@@ -68,10 +76,13 @@ __global__ void __launch_bounds__(IC_THREADS) innercos_fused_kernel(const float*
         }
     } else {
         for (int i = threadIdx.x; i < N; i += IC_THREADS) {
-            const float mv = mask[i];
+            float mv;
+            if constexpr (!PER_SAMPLE) mv = mask[i];
             for (int row = r0; row < r1; ++row) {
                 const int b = row / Cuse, c = row - b * Cuse;
-                const float d = (x[((size_t)b * Cx + c) * N + i] * mv) * strength - target[(size_t)row * N + i];
+                const float xv = x[((size_t)b * Cx + c) * N + i];
+                if constexpr (PER_SAMPLE) mv = mask[(size_t)b * N + i];
+                const float d = (xv * mv) * strength - target[(size_t)row * N + i];
                 acc += (double)(d * d);
             }
         }
@@ -102,7 +113,9 @@ __global__ void __launch_bounds__(IC_THREADS) innercos_fused_kernel(const float*
     }
 }
 
-// d loss / d x = grad_loss * 2/(B*Cuse*N) * ((x*m)*s - t) * (m*s) on the first Cuse channels, 0 elsewhere.
+// d loss / d x = grad_loss * 2/(B*Cuse*N) * ((x*m)*s - t) * (m*s) on the first Cuse channels, 0 elsewhere.  PER_SAMPLE as above: the mask
+// element of sample b is mask[n] or mask[b*N + n].
+template <bool PER_SAMPLE>
 __global__ void __launch_bounds__(256) innercos_backward_kernel(const float* __restrict__ x, int Cx, int Cuse, int N,
                                                                 const float* __restrict__ mask, const float* __restrict__ target,
                                                                 float strength, const float* __restrict__ grad_loss,
@@ -116,76 +129,7 @@ __global__ void __launch_bounds__(256) innercos_backward_kernel(const float* __r
         const int c = (int)(rem / N), n = (int)(rem - (size_t)c * N);
         float gv = 0.0f;
         if (c < Cuse) {
-            const float m = mask[n];
-            const float d = (x[i] * m) * strength - target[(b * Cuse + c) * (size_t)N + n];
-            gv = (d * scale) * (m * strength);
-        }
-        grad_x[i] = gv;
-    }
-}
-
-// ---- one mask per sample: mask [B,N] ---------------------------------------------------------------------------------------------
-// The kernels above with the mask read inside the row loop, at the row of the sample that row belongs to: with two or more rows per
-// workgroup (B*Cuse > 4096) a workgroup's rows cross from one sample into the next.  Kernels of their own (no ticket path, which the
-// modules do not use), so that the shared-mask kernels stay as they were compiled.
-__global__ void __launch_bounds__(IC_THREADS) innercos_masks_kernel(const float* __restrict__ x, int Cx, int Cuse, int N, int rows, int rows_per_block,
-                                                                    const float* __restrict__ mask, const float* __restrict__ target, float strength,
-                                                                    double* __restrict__ partial)
-{
-    __shared__ double wsum[IC_THREADS / 64];
-    double acc = 0.0;
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
-    if ((N & 3) == 0) {
-        const int n4 = N >> 2;
-        for (int i4 = threadIdx.x; i4 < n4; i4 += IC_THREADS) {
-            for (int row = r0; row < r1; ++row) {
-                const int b = row / Cuse, c = row - b * Cuse;                // uniform: scalar unit
-                const float4 mv = *reinterpret_cast<const float4*>(mask + (size_t)b * N + 4 * i4);
-                const float4 xv = *reinterpret_cast<const float4*>(x + ((size_t)b * Cx + c) * N + 4 * i4);
-                const float4 tv = *reinterpret_cast<const float4*>(target + (size_t)row * N + 4 * i4);
-                const float d0 = (xv.x * mv.x) * strength - tv.x;
-                const float d1 = (xv.y * mv.y) * strength - tv.y;
-                const float d2 = (xv.z * mv.z) * strength - tv.z;
-                const float d3 = (xv.w * mv.w) * strength - tv.w;
-                acc += (double)(d0 * d0);
-                acc += (double)(d1 * d1);
-                acc += (double)(d2 * d2);
-                acc += (double)(d3 * d3);
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < N; i += IC_THREADS) {
-            for (int row = r0; row < r1; ++row) {
-                const int b = row / Cuse, c = row - b * Cuse;
-                const float d = (x[((size_t)b * Cx + c) * N + i] * mask[(size_t)b * N + i]) * strength - target[(size_t)row * N + i];
-                acc += (double)(d * d);
-            }
-        }
-    }
-    acc = wave_sum_f64(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < IC_THREADS / 64; ++i) t += wsum[i];
-        partial[blockIdx.x] = t;
-    }
-}
-
-__global__ void __launch_bounds__(256) innercos_backward_masks_kernel(const float* __restrict__ x, int Cx, int Cuse, int N,
-                                                                      const float* __restrict__ mask, const float* __restrict__ target,
-                                                                      float strength, const float* __restrict__ grad_loss,
-                                                                      float two_over_count, size_t total_x, float* __restrict__ grad_x)
-{
-    const float scale = (*grad_loss) * two_over_count;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t per_x = (size_t)Cx * N;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_x; i += stride) {
-        const size_t b = i / per_x, rem = i - b * per_x;
-        const int c = (int)(rem / N), n = (int)(rem - (size_t)c * N);
-        float gv = 0.0f;
-        if (c < Cuse) {
-            const float m = mask[b * (size_t)N + n];
+            const float m = PER_SAMPLE ? mask[b * (size_t)N + n] : mask[n];
             const float d = (x[i] * m) * strength - target[(b * Cuse + c) * (size_t)N + n];
             gv = (d * scale) * (m * strength);
         }
@@ -199,76 +143,37 @@ size_t innercos_ws_bytes(int B, int Cuse, int N)
     return (size_t)IC_MAX_BLOCKS * sizeof(double) + 256;
 }
 
-int launch_innercos_loss(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
-                         float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st)
+int launch_innercos_loss(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target, float strength,
+                         float* loss, void* ws, size_t ws_bytes, unsigned* ticket, const char* who, hipStream_t st)
 {
-    if (ws_bytes < innercos_ws_bytes(B, Cuse, N)) return fail(IPSR_ERR_WORKSPACE, "innercos_loss: workspace %zu < %zu", ws_bytes, innercos_ws_bytes(B, Cuse, N));
+    if (ws_bytes < innercos_ws_bytes(B, Cuse, N)) return fail(IPSR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, innercos_ws_bytes(B, Cuse, N));
     double* partial = reinterpret_cast<double*>(ws);
     const int rows = B * Cuse;
-    const int rpb = (rows + IC_MAX_BLOCKS - 1) / IC_MAX_BLOCKS;           // a streaming kernel lives on waves in flight: up to 4096 workgroups
+    // a streaming kernel lives on waves in flight: up to 4096 workgroups.  With a ticket, few: every one of them is a same-address atomic
+    const int max_blocks = ticket ? IC_FUSED_BLOCKS : IC_MAX_BLOCKS;
+    const int rpb = (rows + max_blocks - 1) / max_blocks;
     const int nblk = (rows + rpb - 1) / rpb;
+    const double inv_count = 1.0 / ((double)rows * N);
     profile_mark_start(st, 5);
-    innercos_fused_kernel<<<nblk, IC_THREADS, 0, st>>>(x, Cx, Cuse, N, rows, rpb, mask, target, strength, 0.0, partial, nullptr, nullptr);
+    (mask_bstride ? innercos_fused_kernel<true> : innercos_fused_kernel<false>)<<<nblk, IC_THREADS, 0, st>>>(
+        x, Cx, Cuse, N, rows, rpb, mask, target, strength, inv_count, partial, ticket, loss);
     profile_mark_stop(st, 5, 2.0 * rows * (double)N * 4.0, 2.0 * rows * (double)N * 4.0);
     if (int rc = check_launch("innercos_fused_kernel")) return rc;
-    innercos_final_kernel<<<1, 256, 0, st>>>(partial, nblk, 1.0 / ((double)rows * N), loss);
+    if (ticket) return IPSR_OK;
+    innercos_final_kernel<<<1, 256, 0, st>>>(partial, nblk, inv_count, loss);
     return check_launch("innercos_final_kernel");
 }
 
-// `ticket`: one 32-bit word of caller memory, zero on entry (left zero)
-int launch_innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target, float strength, float* loss,
-                               void* ws, size_t ws_bytes, unsigned* ticket, hipStream_t st)
-{
-    if (ws_bytes < innercos_ws_bytes(B, Cuse, N)) return fail(IPSR_ERR_WORKSPACE, "innercos_loss: workspace %zu < %zu", ws_bytes, innercos_ws_bytes(B, Cuse, N));
-    const int rows = B * Cuse;
-    const int rpb = (rows + 511) / 512;                                   // few workgroups: every one of them is a same-address atomic
-    const int nb = (rows + rpb - 1) / rpb;
-    profile_mark_start(st, 5);
-    innercos_fused_kernel<<<nb, IC_THREADS, 0, st>>>(x, Cx, Cuse, N, rows, rpb, mask, target, strength, 1.0 / ((double)rows * N),
-                                                     reinterpret_cast<double*>(ws), ticket, loss);
-    profile_mark_stop(st, 5, 2.0 * rows * (double)N * 4.0, 2.0 * rows * (double)N * 4.0);
-    return check_launch("innercos_fused_kernel");
-}
-
-int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
-                             const float* target, float strength, const float* grad_loss, float* grad_x,
-                             hipStream_t st)
+int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target, float strength,
+                             const float* grad_loss, float* grad_x, hipStream_t st)
 {
     const size_t total_x = (size_t)B * Cx * N;
     size_t nb = (total_x + 255) / 256;
     if (nb > 2048) nb = 2048;
     const float two_over_count = 2.0f / (float)((double)B * Cuse * N);
-    innercos_backward_kernel<<<(int)nb, 256, 0, st>>>(x, Cx, Cuse, N, mask, target, strength, grad_loss, two_over_count, total_x, grad_x);
+    (mask_bstride ? innercos_backward_kernel<true> : innercos_backward_kernel<false>)<<<(int)nb, 256, 0, st>>>(
+        x, Cx, Cuse, N, mask, target, strength, grad_loss, two_over_count, total_x, grad_x);
     return check_launch("innercos_backward_kernel");
-}
-
-// the grid, the tree and the fold of launch_innercos_loss
-int launch_innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
-                               float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st)
-{
-    if (ws_bytes < innercos_ws_bytes(B, Cuse, N)) return fail(IPSR_ERR_WORKSPACE, "innercos_loss_masks: workspace %zu < %zu", ws_bytes, innercos_ws_bytes(B, Cuse, N));
-    double* partial = reinterpret_cast<double*>(ws);
-    const int rows = B * Cuse;
-    const int rpb = (rows + IC_MAX_BLOCKS - 1) / IC_MAX_BLOCKS;
-    const int nblk = (rows + rpb - 1) / rpb;
-    profile_mark_start(st, 5);
-    innercos_masks_kernel<<<nblk, IC_THREADS, 0, st>>>(x, Cx, Cuse, N, rows, rpb, mask, target, strength, partial);
-    profile_mark_stop(st, 5, 2.0 * rows * (double)N * 4.0, 2.0 * rows * (double)N * 4.0);
-    if (int rc = check_launch("innercos_masks_kernel")) return rc;
-    innercos_final_kernel<<<1, 256, 0, st>>>(partial, nblk, 1.0 / ((double)rows * N), loss);
-    return check_launch("innercos_final_kernel");
-}
-
-int launch_innercos_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
-                                   const float* target, float strength, const float* grad_loss, float* grad_x,
-                                   hipStream_t st)
-{
-    const size_t total_x = (size_t)B * Cx * N;
-    size_t nb = (total_x + 255) / 256;
-    if (nb > 2048) nb = 2048;
-    const float two_over_count = 2.0f / (float)((double)B * Cuse * N);
-    innercos_backward_masks_kernel<<<(int)nb, 256, 0, st>>>(x, Cx, Cuse, N, mask, target, strength, grad_loss, two_over_count, total_x, grad_x);
-    return check_launch("innercos_backward_masks_kernel");
 }
 
 }  // namespace ipsr

@@ -289,18 +289,11 @@ int launch_bias_act_bwd(const void* dy, const void* y, int act, float slope, int
                         float* sums, unsigned* tickets, const void* dy2, size_t dy2_bstride, hipStream_t st);
 
 size_t innercos_ws_bytes(int B, int Cuse, int N);
-int launch_innercos_loss(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
-                         float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st);
-int launch_innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target, float strength, float* loss,
-                               void* ws, size_t ws_bytes, unsigned* ticket, hipStream_t st);
-int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
-                             const float* target, float strength, const float* grad_loss, float* grad_x,
-                             hipStream_t st);
-// mask [B,N], one row per sample (the shared mask stays with the launchers above)
-int launch_innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, const float* target,
-                               float strength, float* loss, void* ws, size_t ws_bytes, hipStream_t st);
-int launch_innercos_backward_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
-                                   const float* target, float strength, const float* grad_loss, float* grad_x,
-                                   hipStream_t st);
+// mask_bstride: 0 — mask [N], one for the batch; N — mask [B,N], one row per sample
+// ticket: nullptr — two launches; else one 32-bit word of caller memory, zero on entry (left zero), and ONE launch.  who: the entry's name in messages
+int launch_innercos_loss(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target, float strength,
+                         float* loss, void* ws, size_t ws_bytes, unsigned* ticket, const char* who, hipStream_t st);
+int launch_innercos_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride, const float* target, float strength,
+                             const float* grad_loss, float* grad_x, hipStream_t st);
 
 }  // namespace ipsr

@@ -1176,29 +1176,33 @@ def innercos_loss(x, cuse, mask_f32, target, strength, one_launch=False):
     per_sample = B > 1 and mask.numel() == B * N
     if tuple(target.shape) != (B, cuse, x.shape[2], x.shape[3]) or not (mask.numel() == N or per_sample):
         raise RuntimeError("InnerCos: target %s / mask %s do not match input %s" % (tuple(target.shape), tuple(mask.shape), tuple(x.shape)))
+    if per_sample and one_launch:
+        raise RuntimeError("InnerCos: the one-launch form takes one mask for the batch")
     loss = _empty((), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     ws = _workspace(L.innercos_workspace_bytes(B, cuse, N), x.device)
     if per_sample:
-        if one_launch:
-            raise RuntimeError("InnerCos: the one-launch form takes one mask for the batch")
         _lib.check(L.innercos_loss_masks(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), N, target.data_ptr(), float(strength),
                                          loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "innercos_loss_masks")
-        return loss
-    if one_launch:
-        # the last workgroup folds the block partials.  Its arrival counter is a word of OUR memory, one per (device, stream) — the calls
-        # of a stream are ordered, and every launch leaves the word zero — allocated (zeroed) once.  Measured SLOWER than two launches
-        # (csrc/innercos.hip): kept for the C-ABI's completeness and its test, not used by the modules.
-        key = (x.device.index, _stream())
-        ticket = _IC_TICKETS.get(key)
-        if ticket is None:
-            ticket = _IC_TICKETS[key] = _zeros(64, dtype=torch.int32, device=x.device)
+    elif one_launch:
         _lib.check(L.innercos_loss_fused(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(), float(strength),
-                                         loss.data_ptr(), ws.data_ptr(), ws.numel(), ticket.data_ptr(), _stream()), "innercos_loss_fused")
-        return loss
-    _lib.check(L.innercos_loss(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(), float(strength),
-                               loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "innercos_loss")
+                                         loss.data_ptr(), ws.data_ptr(), ws.numel(), _innercos_ticket(x.device).data_ptr(), _stream()),
+                   "innercos_loss_fused")
+    else:
+        _lib.check(L.innercos_loss(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(), float(strength),
+                                   loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "innercos_loss")
     return loss
+
+
+def _innercos_ticket(device):
+    """The arrival counter of the one-launch form, whose last workgroup folds the block partials: a word of OUR memory, one per (device,
+    stream) — the calls of a stream are ordered, and every launch leaves the word zero — allocated (zeroed) once.  The form is measured
+    SLOWER than two launches (csrc/innercos.hip): kept for the C-ABI's completeness and its test, not used by the modules."""
+    key = (device.index, _stream())
+    ticket = _IC_TICKETS.get(key)
+    if ticket is None:
+        ticket = _IC_TICKETS[key] = _zeros(64, dtype=torch.int32, device=device)
+    return ticket
 
 
 def innercos_loss_backward(x, cuse, mask_f32, target, strength, grad_loss):
@@ -1208,17 +1212,18 @@ def innercos_loss_backward(x, cuse, mask_f32, target, strength, grad_loss):
     gl = _req(grad_loss.reshape(1).to(torch.float32), torch.float32, "grad_loss")
     B, Cx = x.shape[0], x.shape[1]
     N = x.shape[2] * x.shape[3]
+    per_sample = B > 1 and mask.numel() == B * N
+    if not (mask.numel() == N or per_sample):
+        raise RuntimeError("InnerCos: mask %s does not match input %s" % (tuple(mask.shape), tuple(x.shape)))
     gx = _empty(x.shape, x.dtype, x.device)
-    if B > 1 and mask.numel() == B * N:              # one mask per sample
+    if per_sample:
         _lib.check(_lib.lib().innercos_loss_backward_masks(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), N, target.data_ptr(),
                                                            float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
                    "innercos_loss_backward_masks")
-        return gx
-    if mask.numel() != N:
-        raise RuntimeError("InnerCos: mask %s does not match input %s" % (tuple(mask.shape), tuple(x.shape)))
-    _lib.check(_lib.lib().innercos_loss_backward(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(),
-                                                 float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
-               "innercos_loss_backward")
+    else:
+        _lib.check(_lib.lib().innercos_loss_backward(x.data_ptr(), B, Cx, cuse, N, mask.data_ptr(), target.data_ptr(),
+                                                     float(strength), gl.data_ptr(), gx.data_ptr(), _stream()),
+                   "innercos_loss_backward")
     return gx
 
 

@@ -422,8 +422,8 @@ int innercos_loss_fused(const float* x, int B, int Cx, int Cuse, int N, const fl
 int innercos_loss_backward(const float* x, int B, int Cx, int Cuse, int N, const float* mask,
                            const float* target, float strength, const float* grad_loss /*[1]*/,
                            float* grad_x /*[B,Cx,N]*/, void* stream);
-/* the same with one mask per sample (extension: per-sample masks).  mask_bstride: 0 = one mask [N] for the batch (these calls then ARE
- * innercos_loss / innercos_loss_backward, bit for bit); N = mask [B,N], row b for sample b:
+/* the same with one mask per sample (extension: per-sample masks): one kernel per pass, the mask row stride decides.  mask_bstride: 0 = one
+ * mask [N] for the batch (these calls then ARE innercos_loss / innercos_loss_backward, bit for bit); N = mask [B,N], row b for sample b:
  *     loss = sum_{b,c<Cuse,n} ((x[b,c,n]*mask[b,n])*strength - target)^2 / (B*Cuse*N)
  * in the same fp32 terms, fp64 accumulation and fixed tree.  Any other mask_bstride: IPSR_ERR_INVALID.  Workspace: innercos_workspace_bytes. */
 int innercos_loss_masks(const float* x, int B, int Cx, int Cuse, int N, const float* mask, int mask_bstride,

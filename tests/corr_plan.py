@@ -16,8 +16,8 @@ What reading the launchers shows, and the sweep of tests/test_corr_plan.py confi
 BM = BN = 128                                             # corr_argmax.hip: BM, BN
 FBK = 16                                                  # FBK
 PF = 4                                                    # PF
-IC_MAX_BLOCKS, IC_FUSED_BLOCKS = 4096, 512                # innercos.hip:15, :155
-IC_BWD_BLOCKS, IC_BWD_THREADS = 2048, 256                 # innercos.hip:169-172
+IC_MAX_BLOCKS, IC_FUSED_BLOCKS = 4096, 512                # innercos.hip: IC_MAX_BLOCKS, IC_FUSED_BLOCKS
+IC_BWD_BLOCKS, IC_BWD_THREADS = 2048, 256                 # launch_innercos_backward
 
 
 def align_up(x, a):
@@ -139,8 +139,8 @@ def forward_ws(B, C, h, w, M, patch, corr_bf16):
 
 # ---- InnerCos and the index kernel ------------------------------------------------------------------------------------------------
 def innercos_plan(B, Cuse, N, fused):
-    """innercos.hip:138-140 (two launches) / :154-156 (one launch) and the `(N & 3) == 0` of :51 -> (vector, rows per block, blocks,
-    rows of the last block)."""
+    """launch_innercos_loss without (two launches) / with a ticket (one launch) and the `(N & 3) == 0` of innercos_fused_kernel -> (vector,
+    rows per block, blocks, rows of the last block)."""
     rows = B * Cuse
     rpb = cdiv(rows, IC_FUSED_BLOCKS if fused else IC_MAX_BLOCKS)
     blocks = cdiv(rows, rpb)
@@ -148,7 +148,7 @@ def innercos_plan(B, Cuse, N, fused):
 
 
 def innercos_bwd_blocks(B, Cx, N):
-    """innercos.hip:168-170."""
+    """launch_innercos_backward: the grid."""
     return min(IC_BWD_BLOCKS, cdiv(B * Cx * N, IC_BWD_THREADS))
 
 
@@ -356,13 +356,13 @@ EDGES = (
      ("win_batch_limited",)),
     ("window plan: 64 slices sought, 63 launched (none empty)", "window_plan", lambda p: p["kind"] == "window" and p["window"][0] < p["sought"] and p["window"][2] == p["window"][0],
      ("win_empty_last_slice",)),
-    ("innercos_fused_kernel: scalar path (N % 4 != 0)", "innercos.hip:51, :70-77", _ic(vector=False), ("ic_scalar_small", "ic_rpb2_ragged_scalar")),
-    ("innercos_fused_kernel: vector path", "innercos.hip:51-68", _ic(vector=True), ("ic_vector_cx_wider", "ic_rpb2_ragged_vector", "ic_bwd_grid_stride")),
-    ("innercos_fused_kernel: two launches, 2 rows per block, last block 1 row", "innercos.hip:138-140, :50", _ic(rpb=2, last=1),
+    ("innercos_fused_kernel: scalar path (N % 4 != 0)", "innercos_fused_kernel: `(N & 3) == 0` else", _ic(vector=False), ("ic_scalar_small", "ic_rpb2_ragged_scalar")),
+    ("innercos_fused_kernel: vector path", "innercos_fused_kernel: `(N & 3) == 0`", _ic(vector=True), ("ic_vector_cx_wider", "ic_rpb2_ragged_vector", "ic_bwd_grid_stride")),
+    ("innercos_fused_kernel: two launches, 2 rows per block, last block 1 row", "launch_innercos_loss: rows per block", _ic(rpb=2, last=1),
      ("ic_rpb2_ragged_scalar", "ic_rpb2_ragged_vector")),
-    ("innercos_fused_kernel: one launch, 9 rows per block", "innercos.hip:154-156", _ic(fused_rpb=9), ("ic_rpb2_ragged_scalar", "ic_rpb2_ragged_vector")),
-    ("innercos_backward_kernel: Cx > Cuse (zero-filled channels)", "innercos.hip:118-123", _ic(cx_wider=True), ("ic_vector_cx_wider", "ic_rpb2_ragged_scalar", "ic_bwd_grid_stride")),
-    ("innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)", "innercos.hip:112-114, :168-170", _ic(bwd_blocks=2048, bwd_strides=True), ("ic_bwd_grid_stride",)),
+    ("innercos_fused_kernel: one launch, 9 rows per block", "launch_innercos_loss: with a ticket", _ic(fused_rpb=9), ("ic_rpb2_ragged_scalar", "ic_rpb2_ragged_vector")),
+    ("innercos_backward_kernel: Cx > Cuse (zero-filled channels)", "innercos_backward_kernel: `c < Cuse`", _ic(cx_wider=True), ("ic_vector_cx_wider", "ic_rpb2_ragged_scalar", "ic_bwd_grid_stride")),
+    ("innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)", "innercos_backward_kernel: stride loop", _ic(bwd_blocks=2048, bwd_strides=True), ("ic_bwd_grid_stride",)),
     ("index_prep_kernel: patch > 1, stride 2, threshold > 1", "mask_ops.hip:88-92, :118", lambda p: p["kind"] == "index_prep" and p["args"] != (1, 1, 1),
      ("ip_p2_s1_t2", "ip_p3_s2_t1", "ip_p3_s1_t9", "ip_p4_s2_t16", "ip_p2_s2_t4", "ip_40x40_p3_s1_t5")),
     ("index_prep_kernel: two 1024-chunks", "mask_ops.hip:84", lambda p: p["kind"] == "index_prep" and p["chunks"] == 2, ("ip_40x40_p3_s1_t5",)),

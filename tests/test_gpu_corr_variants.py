@@ -43,12 +43,12 @@ row below, and each test here asserts its own row again (`P.check_case`) before 
                                                                                                                         win_batch_limited, win_bf16_full_tiles, win_bf16_ragged
   window plan: split limited by the batch (8 < 16 slices)                  window_plan                                  win_batch_limited
   window plan: 64 slices sought, 63 launched (none empty)                  window_plan                                  win_empty_last_slice
-  innercos_fused_kernel: scalar path (N % 4 != 0)                          innercos.hip:51, :70-77                      ic_scalar_small, ic_rpb2_ragged_scalar
-  innercos_fused_kernel: vector path                                       innercos.hip:51-68                           ic_vector_cx_wider, ic_rpb2_ragged_vector, ic_bwd_grid_stride
-  innercos_fused_kernel: two launches, 2 rows per block, last block 1 row  innercos.hip:138-140, :50                    ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
-  innercos_fused_kernel: one launch, 9 rows per block                      innercos.hip:154-156                         ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
-  innercos_backward_kernel: Cx > Cuse (zero-filled channels)               innercos.hip:118-123                         ic_vector_cx_wider, ic_rpb2_ragged_scalar, ic_bwd_grid_stride
-  innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)       innercos.hip:112-114, :168-170               ic_bwd_grid_stride
+  innercos_fused_kernel: scalar path (N % 4 != 0)                          innercos_fused_kernel: `(N & 3) == 0` else   ic_scalar_small, ic_rpb2_ragged_scalar
+  innercos_fused_kernel: vector path                                       innercos_fused_kernel: `(N & 3) == 0`        ic_vector_cx_wider, ic_rpb2_ragged_vector, ic_bwd_grid_stride
+  innercos_fused_kernel: two launches, 2 rows per block, last block 1 row  launch_innercos_loss: rows per block         ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
+  innercos_fused_kernel: one launch, 9 rows per block                      launch_innercos_loss: with a ticket          ic_rpb2_ragged_scalar, ic_rpb2_ragged_vector
+  innercos_backward_kernel: Cx > Cuse (zero-filled channels)               innercos_backward_kernel: `c < Cuse`         ic_vector_cx_wider, ic_rpb2_ragged_scalar, ic_bwd_grid_stride
+  innercos_backward_kernel: grid-stride loop (> 2048 x 256 elements)       innercos_backward_kernel: stride loop        ic_bwd_grid_stride
   index_prep_kernel: patch > 1, stride 2, threshold > 1                    mask_ops.hip:88-92, :118                     ip_p2_s1_t2, ip_p3_s2_t1, ip_p3_s1_t9
                                                                                                                         ip_p4_s2_t16, ip_p2_s2_t4, ip_40x40_p3_s1_t5
   index_prep_kernel: two 1024-chunks                                       mask_ops.hip:84                              ip_40x40_p3_s1_t5

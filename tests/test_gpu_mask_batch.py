@@ -110,6 +110,7 @@ def test_mask_index_bool_masks_and_determinism(ops):
 IC_SHAPES = ((3, 8, 8, 5, 7),              # N = 35: the scalar path
              (2, 11, 8, 8, 8),             # the vector path, Cx > Cuse
              (5, 1023, 1023, 4, 4),        # 5115 rows: two rows per workgroup, a workgroup astride every sample boundary
+             (5, 1023, 1023, 3, 5),        # the same rows on the scalar path (N = 15)
              (4, 64, 64, 32, 32),
              (2, 1024, 512, 32, 32))
 STRENGTH = 0.7

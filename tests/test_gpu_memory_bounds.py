@@ -12,7 +12,7 @@ size its query reported.  Then:
 Workspace audit (what the carve code puts in each scratch buffer):
   floats only  wino_launch_head (winograd.hip), launch_smallmap (smallmap.hip) (transformed operands, products, split partials);
                conv_bf16.hip data_ws_bytes / cb_partial_bytes (zero page, packed bf16 weights, fp32 split partials); conv_gemm.hip:379-387 (packed operands,
-               split-K partials); thin_conv.hip (fp32 partials of the weight gradients); innercos.hip:44 (fp64 block partials)
+               split-K partials); thin_conv.hip (fp32 partials of the weight gradients); innercos.hip innercos_ws_bytes (fp64 block partials)
   integers     api.hip:89 (layer forward / backward: arg-max partial indices, rank flags, the sparse index); api.hip:209 (feat_mask
                bit masks); corr_argmax partial indices
 """
