@@ -17,11 +17,13 @@ Activations may be fp32 or bf16 (BASELINE config 5 runs the convolutions under b
 write bf16 and compute in fp32).  CPU tensors, other dtypes, planes above 256x256 (ops.INSTNORM_MAX_PLANE) or above 16384 elements
 and not a multiple of 4, and `FusedSequential.enabled = False` take the plain module-by-module path.
 """
+from typing import NamedTuple, Optional
+
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
+from . import hipconv      # conv_nobias / any_engine are looked up on the module at call time (tests replace them there)
 
 
 def _ticket_words(x, bias):
@@ -30,6 +32,17 @@ def _ticket_words(x, bias):
     if bias is None or not bias.requires_grad:
         return None
     return torch.empty(x.shape[1], dtype=torch.int32, device=x.device)
+
+
+def _norm_backward(ctx, dy, act, slope, **dy2):
+    """The backward the four norm nodes share -> (dx, dbias, dgamma, dbeta), the gradients of their first four inputs.  Each saves
+    (x, bias, gamma, y, mean, rstd, tickets); dy and y may be the wide concatenated tensors, read in place; dy2 / dy2_at: the
+    gradient of a second, relu'd output."""
+    x, bias, gamma, y, mean, rstd, tickets = ctx.saved_tensors
+    need_bias = bias is not None and ctx.needs_input_grad[1]
+    need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+    dx, dg, db, dbias = ops.instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, act, slope, need_affine, need_bias, tickets=tickets, **dy2)
+    return dx, dbias, dg, db
 
 
 class _InstNormAct(torch.autograd.Function):
@@ -43,11 +56,7 @@ class _InstNormAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, bias, gamma, y, mean, rstd, tickets = ctx.saved_tensors
-        need_bias = bias is not None and ctx.needs_input_grad[1]
-        need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
-        dx, dg, db, dbias = ops.instnorm_act_backward(dy, y, x, bias, gamma, mean, rstd, ctx.act, ctx.slope, need_affine, need_bias, tickets=tickets)
-        return dx, dbias, dg, db, None, None, None
+        return _norm_backward(ctx, dy, ctx.act, ctx.slope) + (None, None, None)
 
 
 class _BiasAct(torch.autograd.Function):
@@ -130,13 +139,10 @@ class _InstNormReLUCat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        y, bias, gamma, out, mean, rstd, tickets = ctx.saved_tensors
-        need_bias = bias is not None and ctx.needs_input_grad[1]
-        need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         g = g.contiguous()
-        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias, tickets=tickets)
-        _, dx = ops.cat_relu_backward(g, out, ctx.c1, skip_half_only=True)
-        return dyn, dbias, dg, db, None, dx
+        grads = _norm_backward(ctx, g, "relu", 0.0)
+        _, dx = ops.cat_relu_backward(g, ctx.saved_tensors[3], ctx.c1, skip_half_only=True)
+        return grads + (None, dx)
 
 
 class _InstNormActSkip(torch.autograd.Function):
@@ -156,14 +162,10 @@ class _InstNormActSkip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_x, g_buf):
-        y, bias, gamma, x_act, mean, rstd, tickets = ctx.saved_tensors
-        need_bias = bias is not None and ctx.needs_input_grad[1]
-        need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         if g_x is None:
-            g_x = torch.zeros_like(x_act)
-        dx, dg, db, dbias = ops.instnorm_act_backward(g_x.contiguous(), x_act, y, bias, gamma, mean, rstd, ctx.act, ctx.slope, need_affine, need_bias,
-                                                      dy2=None if g_buf is None else g_buf.contiguous(), dy2_at=ctx.c1, tickets=tickets)
-        return dx, dbias, dg, db, None, None, None, None
+            g_x = torch.zeros_like(ctx.saved_tensors[3])
+        return _norm_backward(ctx, g_x.contiguous(), ctx.act, ctx.slope, dy2=None if g_buf is None else g_buf.contiguous(),
+                              dy2_at=ctx.c1) + (None, None, None, None)
 
 
 class _InstNormReLUCatInto(torch.autograd.Function):
@@ -180,12 +182,49 @@ class _InstNormReLUCatInto(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        y, bias, gamma, out, mean, rstd, tickets = ctx.saved_tensors
-        need_bias = bias is not None and ctx.needs_input_grad[1]
-        need_affine = ctx.has_affine and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         g = g.contiguous()
-        dyn, dg, db, dbias = ops.instnorm_act_backward(g, out, y, bias, gamma, mean, rstd, "relu", 0.0, need_affine, need_bias, tickets=tickets)
-        return dyn, dbias, dg, db, None, g
+        return _norm_backward(ctx, g, "relu", 0.0) + (None, g)
+
+
+def _fusable(*tensors):
+    """What the kernels read and write: contiguous fp32 / bf16 (not e.g. channels_last)."""
+    return all(t.is_contiguous() and t.dtype in (torch.float32, torch.bfloat16) for t in tensors)
+
+
+def cat_skip(y, x, tail_relu):
+    """torch.cat([y, x], 1), with the consumer's in-place ReLU folded in when it asked for that."""
+    if tail_relu and y.is_cuda and _fusable(y, x) and y.dtype == x.dtype and y.shape[2:] == x.shape[2:]:
+        return _CatReLU.apply(y, x)
+    out = torch.cat([y, x], 1)
+    return torch.relu_(out) if tail_relu else out
+
+
+# ----------------------------------------------------------------------------------------------------
+# matching: what the module list alone decides
+# ----------------------------------------------------------------------------------------------------
+def _act_of(m):
+    """(name, slope) when m is an activation the kernels implement."""
+    if isinstance(m, nn.LeakyReLU):
+        return "leaky", float(m.negative_slope)
+    if isinstance(m, nn.ReLU):
+        return "relu", 0.0
+    return None
+
+
+def _plain_conv(m):
+    return type(m) in (nn.Conv2d, nn.ConvTranspose2d) and m.bias is not None and getattr(m, "padding_mode", "zeros") == "zeros"
+
+
+def _plain_inorm(m):
+    return isinstance(m, nn.InstanceNorm2d) and not m.track_running_stats
+
+
+def _head_act_of_child(m):
+    """A skip level whose first module is an in-place activation can have it absorbed by the producer."""
+    inner = getattr(m, "model", None)
+    if isinstance(inner, FusedSequential) and len(inner) > 0 and getattr(inner[0], "inplace", False):
+        return _act_of(inner[0])
+    return None
 
 
 def _tail_norm_channels(block):
@@ -197,35 +236,82 @@ def _tail_norm_channels(block):
     return int(inner[-1].num_features)
 
 
-def cat_skip(y, x, tail_relu):
-    """torch.cat([y, x], 1), with the consumer's in-place ReLU folded in when it asked for that."""
-    if tail_relu and y.is_cuda and y.dtype == x.dtype and y.dtype in (torch.float32, torch.bfloat16) \
-            and y.is_contiguous() and x.is_contiguous() and y.shape[2:] == x.shape[2:]:
-        return _CatReLU.apply(y, x)
-    out = torch.cat([y, x], 1)
-    return torch.relu_(out) if tail_relu else out
+class Step(NamedTuple):
+    """One step of a sequence: `n` consecutive modules and how they run."""
+    kind: str                   # "bias": conv -> bias kernel | "norm": [conv ->] norm kernel | "module": the module itself |
+                                # "head_act": the leading in-place activation, the module itself unless the producer absorbed it
+    conv: Optional[nn.Module]   # the convolution called without its bias (a norm step may have none)
+    norm: Optional[nn.Module]
+    act: Optional[tuple]        # (name, slope) the kernel applies; ("none", 0.0) where nothing fusable follows
+    act_of: Optional[str]       # whose activation that is: "level" (the next module), "child" (the head of the child level), None
+    child: Optional[nn.Module]  # the skip block entered with its head activation done
+    tail_relu: bool             # the in-place ReLU behind the child is applied by the child's concatenation
+    c1: Optional[int]           # _tail_norm_channels(child): the child can complete a concatenated tensor this step allocates
+    n: int
 
 
-def _act_of(m):
-    """(name, slope) when m is an activation the kernels implement."""
-    if isinstance(m, nn.LeakyReLU):
-        return "leaky", float(m.negative_slope)
-    if isinstance(m, nn.ReLU):
-        return "relu", 0.0
-    return None
+def match(mods):
+    """The steps of a module list; a pure function of the modules (no tensor is looked at)."""
+    steps, i = [], 0
+    while i < len(mods):
+        m = mods[i]
+        conv = m if _plain_conv(m) else None
+        j = i + (conv is not None)
+        norm = mods[j] if j < len(mods) and _plain_inorm(mods[j]) else None
+        j += norm is not None
+        if j == i:
+            head = i == 0 and getattr(m, "inplace", False) and _act_of(m) is not None
+            step = Step("head_act", None, None, _act_of(m), None, None, False, None, 1) if head else Step("module", None, None, None, None, None, False, None, 1)
+        else:
+            nxt = mods[j] if j < len(mods) else None            # what follows the conv / norm: this level's activation, a child level, or neither
+            act, act_of, child, tail, c1 = _act_of(nxt), "level", None, False, None
+            if act is None:
+                act, act_of = _head_act_of_child(nxt), "child"
+            if act is None:
+                act, act_of = ("none", 0.0), None
+            elif act_of == "child":
+                # the in-place ReLU a skip level's concatenated output runs into (models/networks.py:229,408)
+                tail = j + 1 < len(mods) and type(mods[j + 1]) is nn.ReLU and mods[j + 1].inplace
+                child, c1 = nxt, _tail_norm_channels(nxt)
+            step = Step("bias" if norm is None else "norm", conv, norm, act, act_of, child, tail, c1, j - i + (act_of is not None) + tail)
+        steps.append(step)
+        i += step.n
+    return steps
 
 
-def _conv_no_bias(m, x):
-    from .hipconv import conv_nobias
-    return conv_nobias(m, x)
+# ----------------------------------------------------------------------------------------------------
+# execution: what the tensors decide
+# ----------------------------------------------------------------------------------------------------
+def _fits_norm_kernel(y):
+    hw = y.size(2) * y.size(3)
+    return 2 <= hw <= ops.INSTNORM_MAX_PLANE and not (hw > 16384 and hw % 4)
 
 
-def _plain_conv(m):
-    return type(m) in (nn.Conv2d, nn.ConvTranspose2d) and m.bias is not None and getattr(m, "padding_mode", "zeros") == "zeros"
+def _plain_modules(st, y, rest):
+    """The step by torch where the kernels cannot take y (e.g. channels_last, too large for the plane-in-registers kernel)."""
+    dt = y.dtype
+    if st.norm is None:
+        x = y + st.conv.bias.view(1, -1, 1, 1).to(dt)
+    else:
+        if st.conv is not None:
+            y = y + st.conv.bias.view(1, -1, 1, 1)
+        # torch's own kernels, not MIOpen's batch norm (its backward put dx 30 % and dgamma 2 % off on 145x113 planes),
+        # and in fp32: bf16 activations are normalised in fp32 and stay bf16
+        with torch.backends.cudnn.flags(enabled=False):
+            x = st.norm(y.float()).to(dt) if dt == torch.bfloat16 else st.norm(y)
+    for m in rest:
+        x = m(x)
+    return x
 
 
-def _plain_inorm(m):
-    return isinstance(m, nn.InstanceNorm2d) and not m.track_running_stats
+def _into_child(st, node, skip_node, *args):
+    """Hand node(*args) to the child level: with FusedSequential.skip_source, and where the child can complete it, the skip-source form
+    of the node also writes the skip half of the child's concatenated tensor."""
+    if st.tail_relu and FusedSequential.skip_source and st.c1:
+        x, buf = skip_node.apply(*args, st.c1)
+    else:
+        x, buf = node.apply(*args), None
+    return st.child(x, head_act_done=True, tail_relu=st.tail_relu, cat_buf=buf)
 
 
 class FusedSequential(nn.Sequential):
@@ -236,126 +322,54 @@ class FusedSequential(nn.Sequential):
     def _get_name(self):    # prints like the reference's module tree (train.ipynb cell 1 output)
         return 'Sequential'
 
-    def _head_act_of_child(self, m):
-        """A skip level whose first module is an in-place activation can have it absorbed by the producer."""
-        inner = getattr(m, "model", None)
-        if isinstance(inner, FusedSequential) and len(inner) > 0 and getattr(inner[0], "inplace", False):
-            return _act_of(inner[0])
-        return None
+    def forward(self, x, level=None):
+        """seq(x): the tensor, as nn.Sequential.  seq(x, level=(head_act_done, cat_with, cat_buf)), the call of the skip blocks
+        (networks._SkipBlock): always (tensor, concatenated).  head_act_done: the producer of x applied this level's leading in-place
+        activation; cat_with: the level's input, when the caller wants relu(cat([this(x), cat_with], 1)) — a sequence that ends in a
+        norm produces it itself and says so; cat_buf: that concatenated tensor with its skip half already written."""
+        if level is None:
+            return self._run(x, False, None, None)[0]
+        return self._run(x, *level)
 
-    def _tail_relu_after(self, mods, j):
-        """True when mods[j] is the in-place ReLU a skip level's concatenated output runs into (models/networks.py:229,408)."""
-        return j < len(mods) and type(mods[j]) is nn.ReLU and mods[j].inplace
-
-    def forward(self, x, head_act_done=False, cat_with=None, cat_buf=None):
-        """cat_with: the level's input, when the caller (networks._cat_skip) wants relu(cat([this(x), cat_with], 1)) and this sequence
-        may produce it itself if it ends in a norm; the return value is then (tensor, concatenated?)."""
-        out = self._forward(x, head_act_done, cat_with, cat_buf)
-        if cat_with is None:
-            return out[0]
-        return out
-
-    def _forward(self, x, head_act_done, cat_with, cat_buf):
-        usable = FusedSequential.enabled and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
+    def _run(self, x, head_act_done, cat_with, cat_buf):
         mods = list(self)
-        n = len(mods)
         i = 0
         if head_act_done:                       # the producer already applied this level's leading in-place activation
-            assert n > 0 and _act_of(mods[0]) is not None
+            assert mods and _act_of(mods[0]) is not None
             i = 1
-        if not usable:
+        if not (FusedSequential.enabled and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)):
             for m in mods[i:]:
                 x = m(x)
             return x, False
-        while i < n:
-            m = mods[i]
-            conv = _plain_conv(m)
-            norm = mods[i + 1] if (conv and i + 1 < n and _plain_inorm(mods[i + 1])) else (m if _plain_inorm(m) else None)
-            if conv and norm is None:
-                # conv -> activation (same level, or the child's leading in-place one)
-                nxt = mods[i + 1] if i + 1 < n else None
-                act = _act_of(nxt) if nxt is not None else None
-                child_act = self._head_act_of_child(nxt) if (nxt is not None and act is None) else None
-                if act is None and child_act is None:
-                    # conv -> something the kernels do not fuse (Tanh of the outermost level, a loss): the plain module, unless a HIP
-                    # engine takes one of its passes (netG's last ConvTranspose2d 128 -> 3 @256x256: 0.13 vs 0.24 ms forward) — then
-                    # the bias is split off and added (with its gradient as a by-product) by the bias kernel
-                    from .hipconv import any_engine
-                    if any_engine(m, x):
-                        y = _conv_no_bias(m, x)
-                        x = _BiasAct.apply(y, m.bias, "none", 0.0) if (y.is_contiguous() and y.dtype in (torch.float32, torch.bfloat16)) \
-                            else y + m.bias.view(1, -1, 1, 1).to(y.dtype)
-                    else:
-                        x = m(x)
-                    i += 1
-                    continue
-                y = _conv_no_bias(m, x)
-                if not y.is_contiguous() or y.dtype not in (torch.float32, torch.bfloat16):      # e.g. channels_last: plain modules
-                    x = y + m.bias.view(1, -1, 1, 1).to(y.dtype)
-                    i += 1
-                    continue
-                if act is not None:
-                    x = _BiasAct.apply(y, m.bias, act[0], act[1])
-                    i += 2
-                else:
-                    tail = self._tail_relu_after(mods, i + 2)
-                    c1 = _tail_norm_channels(nxt) if (tail and FusedSequential.skip_source) else None
-                    if c1:      # this bias pass also writes the skip half of the child's concatenated tensor
-                        xa, buf = _BiasActSkip.apply(y, m.bias, child_act[0], child_act[1], c1)
-                        x = nxt(xa, head_act_done=True, tail_relu=tail, cat_buf=buf)
-                    else:
-                        x = nxt(_BiasAct.apply(y, m.bias, child_act[0], child_act[1]), head_act_done=True, tail_relu=tail)
-                    i += 3 if tail else 2
+        for st in match(mods)[i:]:              # an activation at the head is a step of its own
+            first, i = i, i + st.n
+            conv, norm = st.conv, st.norm
+            if conv is None and norm is None:
+                x = mods[first](x)
                 continue
-            if norm is not None:
-                if conv:
-                    y, bias, j = _conv_no_bias(m, x), m.bias, i + 2
-                else:
-                    y, bias, j = x, None, i + 1
-                hw = y.size(2) * y.size(3)
-                if hw > ops.INSTNORM_MAX_PLANE or (hw > 16384 and hw % 4) or hw < 2 or not y.is_contiguous() \
-                        or y.dtype not in (torch.float32, torch.bfloat16):
-                    dt = y.dtype
-                    if conv:                       # too large for the plane-in-registers kernel: plain modules
-                        y = y + m.bias.view(1, -1, 1, 1)
-                    # torch's own kernels, not MIOpen's batch norm (its backward put dx 30 % and dgamma 2 % off on 145x113 planes),
-                    # and in fp32: bf16 activations are normalised in fp32 and stay bf16
-                    with torch.backends.cudnn.flags(enabled=False):
-                        x = norm(y.float()).to(dt) if dt == torch.bfloat16 else norm(y)
-                    i = j
-                    continue
-                nxt = mods[j] if j < n else None
-                if nxt is None and cat_with is not None and cat_with.is_contiguous() and cat_with.dtype == y.dtype \
+            if conv is None:
+                y = x
+            elif st.kind == "bias" and st.act_of is None and not hipconv.any_engine(conv, x):
+                # conv -> something the kernels do not fuse (Tanh of the outermost level, a loss): the plain module, unless a HIP
+                # engine takes one of its passes (netG's last ConvTranspose2d 128 -> 3 @256x256: 0.13 vs 0.24 ms forward) — then
+                # the bias is split off and added (with its gradient as a by-product) by the bias kernel
+                x = conv(x)
+                continue
+            else:
+                y = hipconv.conv_nobias(conv, x)
+            if not _fusable(y) or (norm is not None and not _fits_norm_kernel(y)):
+                x = _plain_modules(st, y, mods[first + (conv is not None) + (norm is not None):i])
+                continue
+            if norm is None:
+                node, skip_node, args = _BiasAct, _BiasActSkip, (y, conv.bias)
+            else:
+                node, skip_node, args = _InstNormAct, _InstNormActSkip, (y, conv.bias if conv is not None else None, norm.weight, norm.bias, norm.eps)
+                if i == len(mods) and st.act_of is None and cat_with is not None and cat_with.is_contiguous() and cat_with.dtype == y.dtype \
                         and cat_with.shape[0] == y.shape[0] and cat_with.shape[2:] == y.shape[2:]:
                     # the level ends here: norm + skip concatenation + the parent's ReLU in one node
                     if cat_buf is not None and cat_buf.dtype == y.dtype and cat_buf.shape[0] == y.shape[0] and cat_buf.shape[2:] == y.shape[2:] \
                             and cat_buf.shape[1] == y.shape[1] + cat_with.shape[1]:
-                        return _InstNormReLUCatInto.apply(y, bias, norm.weight, norm.bias, norm.eps, cat_buf), True
-                    return _InstNormReLUCat.apply(y, bias, norm.weight, norm.bias, norm.eps, cat_with), True
-                act = _act_of(nxt) if nxt is not None else None
-                child_act = self._head_act_of_child(nxt) if (nxt is not None and act is None) else None
-                a = act or child_act or ("none", 0.0)
-                if act is None and child_act is not None:
-                    tail = self._tail_relu_after(mods, j + 1)
-                    c1 = _tail_norm_channels(nxt) if (tail and FusedSequential.skip_source) else None
-                    if c1:      # this norm also writes the skip half of the child's concatenated tensor
-                        x, buf = _InstNormActSkip.apply(y, bias, norm.weight, norm.bias, norm.eps, a[0], a[1], c1)
-                        x = nxt(x, head_act_done=True, tail_relu=tail, cat_buf=buf)
-                    else:
-                        x = _InstNormAct.apply(y, bias, norm.weight, norm.bias, norm.eps, a[0], a[1])
-                        x = nxt(x, head_act_done=True, tail_relu=tail)
-                    i = j + 2 if tail else j + 1
-                    continue
-                x = _InstNormAct.apply(y, bias, norm.weight, norm.bias, norm.eps, a[0], a[1])
-                if act is not None:
-                    i = j + 1
-                elif child_act is not None:
-                    tail = self._tail_relu_after(mods, j + 1)
-                    x = nxt(x, head_act_done=True, tail_relu=tail)
-                    i = j + 2 if tail else j + 1
-                else:
-                    i = j
-                continue
-            x = m(x)
-            i += 1
+                        return _InstNormReLUCatInto.apply(*args, cat_buf), True
+                    return _InstNormReLUCat.apply(*args, cat_with), True
+            x = node.apply(*args, *st.act) if st.child is None else _into_child(st, node, skip_node, *args, *st.act)
         return x, False

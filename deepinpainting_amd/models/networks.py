@@ -264,24 +264,24 @@ def l1_pair_loss(a1, a2, target, scale, criterion=F.l1_loss):
 # ----------------------------------------------------------------------------------------------------
 # U-Net building blocks
 # ----------------------------------------------------------------------------------------------------
-def _cat_skip(block, x, head_act_done=False, tail_relu=False, cat_buf=None):
-    """Shared forward of every skip block (:270-278, :358-366, :443-452).  `head_act_done`: the producer of x has already
-    applied this level's leading in-place activation; `tail_relu`: the consumer's in-place ReLU is to be applied to the
-    concatenated result here (both fused into kernels, see models/fused.py); `cat_buf`: the concatenated tensor, allocated by the
-    producer of x with its skip half relu(x) already in place (fused._InstNormActSkip) — the level's last norm completes it."""
-    if block.outermost:
-        y = block.model(x, head_act_done=head_act_done)
-        return torch.relu_(y) if tail_relu else y
-    if tail_relu and isinstance(block.model, FusedSequential):
-        y, done = block.model(x, head_act_done=head_act_done, cat_with=x, cat_buf=cat_buf)     # a level that ends in a norm concatenates by itself
+class _SkipBlock(nn.Module):
+    """What the three skip blocks share: `self.model`, a FusedSequential, and `self.outermost`."""
+
+    def forward(self, x, head_act_done=False, tail_relu=False, cat_buf=None):
+        """The forward of every skip block (:270-278, :358-366, :443-452).  `head_act_done`: the producer of x has already
+        applied this level's leading in-place activation; `tail_relu`: the consumer's in-place ReLU is to be applied to the
+        concatenated result here (both fused into kernels, see models/fused.py); `cat_buf`: the concatenated tensor, allocated by the
+        producer of x with its skip half relu(x) already in place (fused._InstNormActSkip) — the level's last norm completes it."""
+        cat_with = x if tail_relu and not self.outermost else None      # a level that ends in a norm concatenates by itself
+        y, done = self.model(x, level=(head_act_done, cat_with, cat_buf))
         if done:
             return y
-    else:
-        y = block.model(x, head_act_done=head_act_done)
-    h, w = x.size(2), x.size(3)
-    if h != y.size(2) or w != y.size(3):
-        y = F.interpolate(y, (h, w), mode='bilinear')
-    return cat_skip(y, x, tail_relu)
+        if self.outermost:
+            return torch.relu_(y) if tail_relu else y
+        h, w = x.size(2), x.size(3)
+        if h != y.size(2) or w != y.size(3):
+            y = F.interpolate(y, (h, w), mode='bilinear')
+        return cat_skip(y, x, tail_relu)
 
 
 def _block3_layers(outer_nc, inner_nc, input_nc, norm_layer):
@@ -322,7 +322,7 @@ def _assemble3(L, outer_nc, inner_nc, submodule, outermost, innermost, use_dropo
     return model
 
 
-class UnetSkipConnectionBlock_3(nn.Module):
+class UnetSkipConnectionBlock_3(_SkipBlock):
     """reference :212-278."""
 
     def __init__(self, outer_nc, inner_nc, input_nc, submodule=None, outermost=False, innermost=False,
@@ -334,11 +334,8 @@ class UnetSkipConnectionBlock_3(nn.Module):
         L = _block3_layers(outer_nc, inner_nc, input_nc, norm_layer)
         self.model = FusedSequential(*_assemble3(L, outer_nc, inner_nc, submodule, outermost, innermost, use_dropout))
 
-    def forward(self, x, head_act_done=False, tail_relu=False, cat_buf=None):
-        return _cat_skip(self, x, head_act_done, tail_relu, cat_buf)
 
-
-class IPSR(nn.Module):
+class IPSR(_SkipBlock):
     """The U-Net level that hosts the patch-attention layer (reference :281-366): after the 3x3 down conv
     (256->512 @ 32x32) come IPSR_model and the InnerCos tap, then the instance norm; InnerCos2 heads the
     up path.  The three objects are also appended to the caller's lists."""
@@ -364,9 +361,6 @@ class IPSR(nn.Module):
         self.model = FusedSequential(*_assemble3(L, outer_nc, inner_nc, submodule, outermost, innermost, use_dropout,
                                                mid_down=(ipsr, innerCos), head_up=(innerCos2,)))
 
-    def forward(self, x, head_act_done=False, tail_relu=False, cat_buf=None):
-        return _cat_skip(self, x, head_act_done, tail_relu, cat_buf)
-
 
 class UnetGeneratorIPSR(nn.Module):
     """netG (reference :187-209): innermost + (num_downs-5) + 1 plain 512-wide levels, the IPSR level,
@@ -391,7 +385,7 @@ class UnetGeneratorIPSR(nn.Module):
         return self.model(input)
 
 
-class UnetSkipConnectionBlock(nn.Module):
+class UnetSkipConnectionBlock(_SkipBlock):
     """pix2pix U-Net level of netP (reference :395-452): 4x4 stride-2 conv down, 4x4 stride-2 transposed conv up."""
 
     def __init__(self, outer_nc, inner_nc, input_nc, submodule=None, outermost=False, innermost=False,
@@ -416,9 +410,6 @@ class UnetSkipConnectionBlock(nn.Module):
             if use_dropout:
                 model.append(nn.Dropout(0.5))
         self.model = FusedSequential(*model)
-
-    def forward(self, x, head_act_done=False, tail_relu=False, cat_buf=None):
-        return _cat_skip(self, x, head_act_done, tail_relu, cat_buf)
 
 
 class UnetGenerator(nn.Module):
